@@ -8,8 +8,11 @@ full training step of the hot path: frequency layers -> HIP circuit forward -> M
 backward -> (RCCL all-reduce of the flat gradient when N>1) -> Adam.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 launched by torch.distributed.run,
-one rank per GPU.  Rank 0 prints ONE JSON line.  `value` = train samples/s over all ranks; the same line
-also carries forward-only circuit-evals/s, the roofline object of the dominant kernel and the CPU baseline.
+one rank per GPU.  Rank 0 prints ONE JSON line.  `value` = train samples/s over all ranks and `ms_per_step` = the time
+of one of the K timed steps (one window of exactly K steps after W warm-up steps); the same line also carries
+forward-only circuit-evals/s, the roofline object of the dominant kernel and the CPU baseline.
+`--dump-outputs DIR`: rank 0 writes what the last timed step left to its caller (parameters, gradients, loss sums) as
+DIR/<name>.npy, float64; the inputs and the initial parameters are seeded, so the same arguments give the same arrays.
 """
 import argparse
 import json
@@ -115,6 +118,19 @@ def tq_shaped_cpu(batch=128):
 
 
 FP64_VECTOR_PEAK_TFLOPS = 78.6
+DEVICE_WARMUP_S = 0.5
+
+
+def dump_outputs(out_dir, trainer):
+    """What the last timed step left its caller (DataParallelTrainer.train_steps / train_step): the updated parameters
+    (flat, the model's state_dict order), that step's gradients and its [sse, sum y^2] (summed over the ranks)."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    last = trainer._last.detach().cpu().numpy()
+    arrays = {'params': trainer.pflat.detach().cpu().numpy(), 'grads': last[:trainer.numel],
+              'loss_sums': last[trainer.numel:trainer.numel + 2]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def secondary_configs(dev, measure_many):
@@ -276,7 +292,11 @@ def main():
     ap.add_argument('--batch', type=int, default=BATCH, help='samples per GPU and step (the headline is 1024)')
     ap.add_argument('--backward-variant', default='auto',
                     help='measurement only: force an n <= 5 kernel variant (quanonet_amd._lib.BWD_VARIANTS); the headline is "auto"')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s results (parameters, gradients, loss sums) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         spawn_ranks(args)                                     # never returns
@@ -381,14 +401,25 @@ def main():
             print("data-parallel exchange: " + trainer.dp_exchange_reason, file=sys.stderr, flush=True)
         if not epoch_call and hasattr(step, 'many'):
             del step.many
+    # the device clock ramps up for tens of ms of load after idle (a window of 200 steps right after 20 warm-up steps ran
+    # ~6 % slow): forward launches over the resident batches bring it up first.  They leave the parameters and the Adam
+    # state alone, so the timed steps start from what the W warm-up steps leave, in every run with the same arguments.
+    warm_out = torch.empty(n_batches * batch, dtype=torch.float64, device=dev)
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < DEVICE_WARMUP_S:
+        _lib.model_forward_chunks(trainer.desc, branch, trunk, trainer.pflat, batch, out=warm_out)
+        torch.cuda.synchronize()
+    del warm_out
     if epoch_call:
         run_steps(0, args.warmup)
     else:
         for i in range(args.warmup):
             step(i)
-    elapsed, windows = measure(step, args.steps)
+    elapsed = timed_window(step, args.steps, 0)                # the timed region: EXACTLY --steps training steps
     samples_per_s = batch * world * args.steps / elapsed
     trainer.check_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)
 
     # N > 1: which devices the ranks ran on, and the same step through the OTHER exchanges in the same run (every rank
     # switches together), so that the line explains itself: the exchange inside the reduce kernel (the headline when the
@@ -530,17 +561,14 @@ def main():
                        "world_size": world, "backend": None if world == 1 else args.backend,
                        "same_device_rehearsal": bool(args.same_device), "devices": devices,
                        "ms_per_step_by_exchange": alternatives},
-            "timing": {"windows": len(windows), "steps_per_window": args.steps,
-                       "ms_per_step_median": 1e3 * elapsed / args.steps,
-                       "ms_per_step_first_window": 1e3 * windows[0] / args.steps,
-                       "ms_per_step_min": 1e3 * min(windows) / args.steps,
-                       "ms_per_step_max": 1e3 * max(windows) / args.steps,
+            "timing": {"timed_steps": args.steps, "warmup_steps": args.warmup, "device_warmup_s": DEVICE_WARMUP_S,
                        "issue": ("runs of up to 32 consecutive steps per host call (qhea_model_train_steps / "
                                  "qhea_model_dp_train_steps, the epoch loop of PTSolver.train: a step's reduce kernel writes "
                                  "the next step's layer records)"
                                  if epoch_call else "one host call per step (prep, circuit, reduce launches each)"),
-                       "note": "value = median over windows of EXACTLY `steps` training steps each, every window "
-                               "bracketed by barrier + device synchronize, max over ranks per window"},
+                       "note": "value and ms_per_step from ONE window of EXACTLY `steps` training steps, bracketed by "
+                               "barrier + device synchronize, max over ranks; before it, `device_warmup_s` of forward "
+                               "launches (parameters untouched) and `warmup` training steps"},
             "circuit_evals_per_s": evals_per_s,
             "circuit_evals_issue": ("one host call per forward launch (record preparation every call)"
                                     if os.environ.get('QHEA_BENCH_PER_STEP') else
