@@ -358,6 +358,31 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
                               int64_t dp_values, int64_t first_seq, double timeout_ms,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Model ensemble: R = n_models independent models of ONE descriptor trained side by side, each step of all R members as one
+ * launch per kernel (member = the grid's second dimension) -- a seed sweep of one configuration on one device.  Replaces
+ * the reference's concurrent seed processes (one training process per seed, each issuing its own small launches).
+ * Member m has its own rows (branch / trunk / y: member m's start at m * row_begin[n_steps] rows), parameters, Adam
+ * moments (params / exp_avg / exp_avg_sq: [n_models][P]) and gradient rows (grad + (m * n_steps + i) * grad_stride for
+ * step i); all members share the schedule row_begin / inv_batch_total, the step count and the hyper-parameters.
+ * Results are bitwise those of n_models qhea_model_train_steps calls, one per member, made under the backward variant the
+ * ensemble chose: the kernels are chosen as for ONE batch of n_models x B rows (qhea_set_backward_variant applies).
+ * Shapes the n <= 5 ZYZ kernels do not take (n >= 6, first-generation variants, shapes not eligible) run as n_models
+ * consecutive qhea_model_train_steps calls on the same stream, one workspace slice each.  An overrun in any member is
+ * reported by qhea_check_status on this workspace.  Workspace: qhea_model_ensemble_workspace_bytes for every batch size
+ * of the schedule (the largest of those).
+ */
+size_t qhea_model_ensemble_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch);
+int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_models, int64_t n_steps,
+                                    const int64_t* row_begin /*HOST [n_steps+1], the same schedule for every member*/,
+                                    const double* branch, const double* trunk, const double* y /*DEVICE, [n_models][rows]*/,
+                                    double* params /*DEVICE [n_models][P]*/, const double* ham_diag /*shared*/,
+                                    const double* inv_batch_total /*HOST [n_steps]*/,
+                                    double* grad /*DEVICE [n_models][n_steps][grad_stride]*/, int64_t grad_stride,
+                                    double* exp_avg /*DEVICE [n_models][P]*/, double* exp_avg_sq, int64_t first_step,
+                                    double lr, double beta1, double beta2, double eps, double weight_decay,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -278,11 +278,15 @@ __device__ __forceinline__ void prep_layer_body(const LayerInfo& cur, const Laye
     }
 }
 
+// (ensemble launches: member blockIdx.y's angles and workspace slice; the header is slice 0's, whoever the member)
 __global__ __launch_bounds__(64) void prep_zyz_kernel(Runs runs, int n, int L, const double* __restrict__ w,
                                                       char* __restrict__ rec, char* __restrict__ srec,
-                                                      double* __restrict__ gmap, WorkspaceHeader* hdr) {
+                                                      double* __restrict__ gmap, WorkspaceHeader* hdr, MemberStride ms) {
     const int l = blockIdx.x, j = threadIdx.x;
-    if (l == 0 && j == 0) header_init(hdr);
+    const long m = blockIdx.y;
+    if (l == 0 && j == 0 && m == 0) header_init(hdr);
+    w = member_ptr(w, m * ms.params * (long)sizeof(double));
+    rec = member_ptr(rec, m * ms.ws); srec = member_ptr(srec, m * ms.ws); gmap = member_ptr(gmap, m * ms.ws);
     __shared__ PrepShared sh;
     prep_layer_body(decode_layer(runs, n, l < L ? l : -1), decode_layer(runs, n, l - 1), n, l, j,
                     [&](int s, int k, int q) { return w[(long)s * 3 * n + k * n + q]; }, rec, srec, gmap, sh);
@@ -551,17 +555,22 @@ bool use_lds(int n, bool backward) {
     return lds_supported(n);
 }
 
-Layout make_layout(int n, const Shape& sh, int64_t B) {
+// B: rows of ONE model, which sizes the workspace (partial rows, tables); Bd: rows the launch carries, which choose the kernels
+// -- R x B for an ensemble launch of R members (qhea_model_ensemble_train_steps: the occupancy rules below are about the whole
+// grid), B otherwise.
+Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
     Layout L{};
     const int spw_packed = 64 >> lane_bits(n);
     L.lds_fwd = use_lds(n, false);
     L.lds_bwd = use_lds(n, true);
-    L.pair = !L.lds_bwd && use_pair(n, B);
+    L.pair = !L.lds_bwd && use_pair(n, Bd);
     const int spw = L.lds_bwd ? 1 : spw_packed;
     auto round_waves = [](long w) { return ((w + kWaves - 1) / kWaves) * kWaves; };   // padding waves write zeros
     L.nwaves_fwd = round_waves((B + spw_packed - 1) / spw_packed);
     L.nwaves = L.lds_bwd ? B : round_waves((B + spw - 1) / spw);                      // backward partial rows
     if (L.pair) L.nwaves = (B + spw - 1) / spw;                                       // one row per workgroup (= sample group)
+    const long nwaves_fwd_d = round_waves((Bd + spw_packed - 1) / spw_packed);        // ... and the same counts for the launch
+    const long groups_d = (Bd + spw - 1) / spw;                                       // (pipelined kernels: nwaves = groups)
     // second-generation kernels for n <= 5 (hea_zyz.hpp): the default when the shape is eligible; the first-generation
     // variants stay selectable (qhea_set_backward_variant) and take over for shapes whose (cos, sin) table exceeds LDS
     const int var = g_bwd_variant.load(std::memory_order_relaxed);
@@ -578,8 +587,8 @@ Layout make_layout(int n, const Shape& sh, int64_t B) {
     const bool fast = zok && zyz_fast_ld(sh.runs, n) != 0;
     // forward: private-ring kernel while the sweeps leave SIMDs free, shared-ring kernel (block-unrolled shapes) beyond;
     // other shapes fall back to the first-generation forward once two waves per SIMD are reached
-    L.zfwd_shared = fast && (var == QHEA_BWD_ZPACKED || (var == QHEA_BWD_AUTO && L.nwaves_fwd > (long)simd_count()));
-    L.zfwd = zok && (L.zfwd_shared || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZQUAD || L.nwaves_fwd <= 2L * simd_count());
+    L.zfwd_shared = fast && (var == QHEA_BWD_ZPACKED || (var == QHEA_BWD_AUTO && nwaves_fwd_d > (long)simd_count()));
+    L.zfwd = zok && (L.zfwd_shared || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZQUAD || nwaves_fwd_d <= 2L * simd_count());
     L.ztri = zok && L.pair;
     // batches that fill the SIMDs: the one-wave ZYZ kernel for the block-unrolled shapes (B = 16384 at cfg 2's circuit:
     // see DESIGN.md section 3.5), the first-generation packed kernel otherwise
@@ -600,8 +609,8 @@ Layout make_layout(int n, const Shape& sh, int64_t B) {
     // that the one-pipeline workgroups run in two rounds, 154 us at 1280).  QHEA_BWD_ZTRI2 forces them, QHEA_BWD_ZTRI never.
     L.zpipes = 1;
     const long cus = (long)simd_count() / 4;
-    const bool two_wanted = var == QHEA_BWD_ZTRI2 ? L.nwaves > cus
-                                                  : (var == QHEA_BWD_AUTO && L.nwaves > cus && L.nwaves <= 2 * cus);
+    const bool two_wanted = var == QHEA_BWD_ZTRI2 ? groups_d > cus
+                                                  : (var == QHEA_BWD_AUTO && groups_d > cus && groups_d <= 2 * cus);
     if (L.ztri && two_wanted) {
         const size_t cs_bytes = (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * (L.zsplit ? 32 : 16);
         const size_t lds = 2 * ztri_fixed_lds(kZRingDepth<2>) + 2 * cs_bytes +
@@ -612,7 +621,7 @@ Layout make_layout(int n, const Shape& sh, int64_t B) {
     // and the split-layout reverse walk shortens it (cfg 2's circuit, us per training step, all-lane / split reverse walk:
     // DESIGN.md section 3.3a).  Same partial-row layout as the one-pipeline kernel.
     L.zquad = L.ztri && L.zsplit && L.zpipes == 1 &&
-              (var == QHEA_BWD_ZQUAD || (var == QHEA_BWD_AUTO && L.nwaves <= cus));
+              (var == QHEA_BWD_ZQUAD || (var == QHEA_BWD_AUTO && groups_d <= cus));
     size_t p = kHeaderBytes;                         // WorkspaceHeader
     L.off_U = p;    p = align_up(p + (size_t)(sh.blk + 2) * n * kGateBytes);
     L.off_cs = p;   p = align_up(p + (size_t)B * sh.E * sizeof(double2));
@@ -620,13 +629,14 @@ Layout make_layout(int n, const Shape& sh, int64_t B) {
     L.off_rec = p;  p = align_up(p + (zok ? (size_t)(L.zL + 1 + 2 * kPadRecs) * kRecBytes : 0));   // padded both sides
     if (zok) L.off_rec += (size_t)kPadRecs * kRecBytes;                                           // -> record 0
     // one sample per wave: pays while every sweeping wave still gets a SIMD of its own
-    L.zfwd_split = L.zsplit && L.zfwd && !L.zfwd_shared && B <= (int64_t)simd_count();
+    L.zfwd_split = L.zsplit && L.zfwd && !L.zfwd_shared && Bd <= (int64_t)simd_count();
     L.off_srec = p; p = align_up(p + (L.zsplit ? (size_t)(L.zL + 1 + 2 * kPadRecs) * kRecBytes : 0));
     if (L.zsplit) L.off_srec += (size_t)kPadRecs * kRecBytes;
     L.off_gmap = p; p = align_up(p + (zok ? (size_t)sh.blk * n * kGmapDoubles * sizeof(double) : 0));
     L.total = p;
     return L;
 }
+Layout make_layout(int n, const Shape& sh, int64_t B) { return make_layout(n, sh, B, B); }
 
 __global__ void adam_kernel(long n, const double* __restrict__ g, AdamArgs a) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -640,10 +650,12 @@ inline void profile_end(hipStream_t st) {
     g_ev_start = nullptr; g_ev_stop = nullptr;
 }
 
-int launch_prep_zyz(int n, const Shape& sh, const double* w, char* ws, const Layout& L, hipStream_t st) {
-    hipLaunchKernelGGL(prep_zyz_kernel, dim3((unsigned)(L.zL + 1)), dim3(64), 0, st, sh.runs, n, L.zL, w,
+// R, ms: an ensemble launch (member = blockIdx.y, hea_zyz.hpp: MemberStride); ws and w are member 0's
+int launch_prep_zyz(int n, const Shape& sh, const double* w, char* ws, const Layout& L, hipStream_t st, int R = 1,
+                    const MemberStride& ms = MemberStride{}) {
+    hipLaunchKernelGGL(prep_zyz_kernel, dim3((unsigned)(L.zL + 1), (unsigned)R), dim3(64), 0, st, sh.runs, n, L.zL, w,
                        ws + L.off_rec, L.zsplit ? ws + L.off_srec : nullptr, reinterpret_cast<double*>(ws + L.off_gmap),
-                       reinterpret_cast<WorkspaceHeader*>(ws));
+                       reinterpret_cast<WorkspaceHeader*>(ws), ms);
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 int launch_zyz_forward(int n, const Shape& sh, int64_t B, const Layout& L, char* ws, const AngleSrc& src, double off, double co,
@@ -682,18 +694,22 @@ int launch_zyz_forward(int n, const Shape& sh, int64_t B, const Layout& L, char*
 }
 int launch_zyz_backward(int n, const Shape& sh, int64_t B, const Layout& L, char* ws, const AngleSrc& src, double off,
                         double co, const double* diag, int pauli, const double* g, const double* state_in, const double* y,
-                        const double* bias, double inv_bt, double* out, double* grad_x, double* partial, hipStream_t st) {
+                        const double* bias, double inv_bt, double* out, double* grad_x, double* partial, hipStream_t st,
+                        int R = 1, const MemberStride& ms = MemberStride{}) {
     const int fast = zyz_fast_ld(sh.runs, n);
     int nblocks = 0;
     for (int i = 0; i < sh.runs.nruns; ++i) nblocks += sh.runs.count[i];
-    const ZBwdArgs za{sh.runs, (long)B, (int)sh.E, (int)sh.blk, ws + L.off_rec, (int)((L.zL + 1) * kRecBytes), L.zL, src, off, co,
+    ZBwdArgs za{sh.runs, (long)B, (int)sh.E, (int)sh.blk, ws + L.off_rec, (int)((L.zL + 1) * kRecBytes), L.zL, src, off, co,
                       diag, pauli, g, state_in, y, bias, inv_bt, out, grad_x, partial,
                       &reinterpret_cast<WorkspaceHeader*>(ws)->status, fast, nblocks,
                       (L.zsplit && !L.zpacked) ? ws + L.off_srec : nullptr, L.zpipes};
+    za.ms = ms;
+    za.src.m_rows = ms.rows; za.src.m_params = ms.params;
+    const unsigned gy = (unsigned)R;
     const size_t dyn = (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * sizeof(double2);
     if (L.zpacked) {
         switch (n) {
-#define QHEA_CASE(NN) case NN: launch_bwd_zpacked_##NN(dim3((unsigned)L.nwaves), zp_cs_bytes(n, sh.E, kZPWaves * (64 >> n)), st, za); break;
+#define QHEA_CASE(NN) case NN: launch_bwd_zpacked_##NN(dim3((unsigned)L.nwaves, gy), zp_cs_bytes(n, sh.E, kZPWaves * (64 >> n)), st, za); break;
             QHEA_FOR_EACH_ZN(QHEA_CASE)
 #undef QHEA_CASE
             default: return QHEA_EUNSUPPORTED;
@@ -701,13 +717,13 @@ int launch_zyz_backward(int n, const Shape& sh, int64_t B, const Layout& L, char
         return QHEA_OK;
     }
     if (L.zquad && n == 5 && pauli == QHEA_PAULI_Z && za.srec) {
-        launch_bwd_zquad_5(dim3((unsigned)L.nwaves), zquad_fixed_lds(kPairRing) + 2 * dyn, st, za);
+        launch_bwd_zquad_5(dim3((unsigned)L.nwaves, gy), zquad_fixed_lds(kPairRing) + 2 * dyn, st, za);
         return QHEA_OK;
     }
     const size_t dyn_tri = (size_t)L.zpipes * (ztri_fixed_lds(L.zpipes == 2 ? kZRingDepth<2> : kZRingDepth<1>) + (za.srec ? 2 * dyn : dyn)) +
                            (L.zpipes == 2 ? (size_t)sh.blk * padded_3n(n) * sizeof(double) : 0);
     switch (n) {
-#define QHEA_CASE(NN) case NN: launch_bwd_ztri_##NN(dim3((unsigned)L.nwaves), dyn_tri, st, za); break;
+#define QHEA_CASE(NN) case NN: launch_bwd_ztri_##NN(dim3((unsigned)L.nwaves, gy), dyn_tri, st, za); break;
         QHEA_FOR_EACH_ZN(QHEA_CASE)
 #undef QHEA_CASE
         default: return QHEA_EUNSUPPORTED;
@@ -801,8 +817,20 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         int n, int blk, int kw, long nwaves, const double* __restrict__ partial, const double* w,
         long B, int E, EncDesc enc, const double* __restrict__ grad_x, const double* __restrict__ pred,
         const double* __restrict__ y, double inv_bt, GradMap gm, int nb_w, int nb_x, double* __restrict__ grad,
-        AdamArgs adam, const WorkspaceHeader* __restrict__ hdr, const double* gmap, FusePrep fp, DpX dpx) {
+        AdamArgs adam, const WorkspaceHeader* __restrict__ hdr, const double* gmap, FusePrep fp, DpX dpx, MemberStride ms) {
 #pragma clang fp contract(off)
+    {   // ensemble launches: member blockIdx.y's data, parameters, gradient rows and workspace slice (hdr: slice 0's)
+        const long m = blockIdx.y, wsb = m * ms.ws, pb = m * ms.params * (long)sizeof(double);
+        partial = member_ptr(partial, wsb); grad_x = member_ptr(grad_x, wsb); pred = member_ptr(pred, wsb);
+        gmap = member_ptr(gmap, wsb);
+        fp.rec = member_ptr(fp.rec, wsb); fp.srec = member_ptr(fp.srec, wsb); fp.gmap = member_ptr(fp.gmap, wsb);
+        w = member_ptr(w, pb);
+        adam.p = member_ptr(adam.p, pb); adam.m = member_ptr(adam.m, pb); adam.v = member_ptr(adam.v, pb);
+        y = member_ptr(y, m * ms.rows * (long)sizeof(double));
+        grad = member_ptr(grad, m * ms.grad * (long)sizeof(double));
+        // (enc stays as given -- its segments are indexed at run time, a modified copy would live in private memory: the
+        // frequency blocks move their input pointer themselves, and nothing here reads the encoding weights)
+    }
     __shared__ double acc[kRedThreads];
     __shared__ double acc2[kRedThreads];
     __shared__ int dp_failed;
@@ -872,7 +900,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             si = e < enc.seg[0].ncols ? 0 : 1;
             if (si) ee = e - enc.seg[0].ncols;
             const EncSeg& sg = enc.seg[si];
-            const double* __restrict__ in = sg.in + ee % sg.width;
+            const double* __restrict__ in = sg.in + (long)blockIdx.y * ms.rows * sg.width + ee % sg.width;
             const double* __restrict__ gx = grad_x + e;
             long b = slice;
             for (; b + 15L * kFreqSlices < B; b += 16L * kFreqSlices) {    // 32 loads in flight per thread: B = 1024 in ONE round trip
@@ -1071,15 +1099,16 @@ int model_info(const qhea_model_desc* d, ModelInfo& mi) {
 
 struct ModelLayout { Layout L; size_t off_gx, off_pred, total; };
 
-ModelLayout make_model_layout(const ModelInfo& mi, int64_t B) {
+ModelLayout make_model_layout(const ModelInfo& mi, int64_t B, int64_t Bd /* rows of the launch: R x B for an ensemble */) {
     ModelLayout M{};
-    M.L = make_layout(mi.n, mi.sh, B);
+    M.L = make_layout(mi.n, mi.sh, B, Bd);
     size_t p = M.L.total;
     M.off_gx = p;   p = align_up(p + (size_t)B * mi.sh.E * sizeof(double));
     M.off_pred = p; p = align_up(p + (size_t)B * sizeof(double));
     M.total = p;
     return M;
 }
+ModelLayout make_model_layout(const ModelInfo& mi, int64_t B) { return make_model_layout(mi, B, B); }
 
 EncDesc make_enc(const qhea_model_desc* d, const ModelInfo& mi, const double* branch, const double* trunk,
                  const double* params) {
@@ -1107,13 +1136,35 @@ int launch_prep_model(const ModelInfo& mi, int64_t B, const double* params, cons
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 
+// R-sequential ensemble fallback (qhea_model_ensemble_train_steps): member m > 0 ran on its own workspace slice, whose header
+// took its status; the overrun is moved into slice 0's header, the one qhea_check_status reads
+__global__ void status_fold_kernel(WorkspaceHeader* dst, WorkspaceHeader* src) {
+    if (threadIdx.x == 0 && src->magic == kWsMagic && src->status != 0) {
+        header_init(dst);
+        dst->status |= src->status;
+        src->status = 0;
+    }
+}
+
+// bytes of one member's workspace slice for a step of `batch` rows in an R-member ensemble: enough for the one-launch path
+// (kernels chosen for R x batch rows) and for the R-sequential one (chosen for batch rows)
+size_t ensemble_slice_bytes(const ModelInfo& mi, int64_t R, int64_t batch) {
+    const size_t a = make_model_layout(mi, batch, R * batch).total, b = make_model_layout(mi, batch).total;
+    return a > b ? a : b;
+}
+// whether a step of `batch` rows of an R-member ensemble runs as one launch per kernel (member = blockIdx.y): the ZYZ kernels
+bool ensemble_grid(const ModelInfo& mi, int64_t R, int64_t batch) {
+    const Layout L = make_model_layout(mi, batch, R * batch).L;
+    return L.ztri || L.zpacked;
+}
+
 }  // namespace qhea
 
 using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 440; }
+int qhea_version(void) { return 450; }
 
 const char* qhea_strerror(int code) {
     switch (code) {
@@ -1362,14 +1413,15 @@ static bool model_fuse_eligible(const ModelInfo& mi, const Layout& L) { return m
 static int launch_reduce_model(int nblocks, hipStream_t st, const ModelInfo& mi, int kw, long nwaves, const double* partial,
                                const double* params, int64_t batch, const EncDesc& enc, const double* gx, const double* pr,
                                const double* y, double inv_bt, const GradMap& gm, int nb_w, int nb_x, double* grad,
-                               const AdamArgs& adam, const char* ws, const double* gmap, const FusePrep& fp, const DpX* dpx) {
+                               const AdamArgs& adam, const char* ws, const double* gmap, const FusePrep& fp, const DpX* dpx,
+                               int R = 1, const MemberStride& ms = MemberStride{}) {
     const DpX none{};
     const DpX& dx = dpx ? *dpx : none;
-    const dim3 g((unsigned)nblocks), b(kRedThreads);
+    const dim3 g((unsigned)nblocks, (unsigned)R), b(kRedThreads);
     const WorkspaceHeader* hdr = reinterpret_cast<const WorkspaceHeader*>(ws);
 #define QHEA_LAUNCH_REDUCE(F, D)                                                                                          \
     hipLaunchKernelGGL((reduce_model_kernel<F, D>), g, b, 0, st, mi.n, (int)mi.sh.blk, kw, nwaves, partial, params + mi.off_ans, \
-                       (long)batch, (int)mi.sh.E, enc, gx, pr, y, inv_bt, gm, nb_w, nb_x, grad, adam, hdr, gmap, fp, dx)
+                       (long)batch, (int)mi.sh.E, enc, gx, pr, y, inv_bt, gm, nb_w, nb_x, grad, adam, hdr, gmap, fp, dx, ms)
     if (fp.ld != 0) { if (dpx) QHEA_LAUNCH_REDUCE(true, true); else QHEA_LAUNCH_REDUCE(true, false); }
     else            { if (dpx) QHEA_LAUNCH_REDUCE(false, true); else QHEA_LAUNCH_REDUCE(false, false); }
 #undef QHEA_LAUNCH_REDUCE
@@ -1386,10 +1438,12 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
                                 const double* y, const double* params, const double* ham_diag, double inv_batch_total,
                                 double* grad, double* pred, void* workspace, size_t workspace_bytes, void* stream,
                                 const AdamArgs& adam, bool records_ready = false, bool records_for_next = false,
-                                const DpX* dpx = nullptr) {
+                                const DpX* dpx = nullptr, int R = 1, const MemberStride& ms = MemberStride{}) {
     // records_ready / records_for_next (qhea_model_train_steps only): the previous step's reduce kernel has written this
     // step's layer records / this step's reduce kernel writes the next step's (FusePrep).  dpx (qhea_model_dp_train_steps):
-    // the reduce kernel's blocks exchange their gradients with the peer ranks before they update.
+    // the reduce kernel's blocks exchange their gradients with the peer ranks before they update.  R, ms
+    // (qhea_model_ensemble_train_steps only): R members in every launch, member 0's pointers given, workspace_bytes = one slice;
+    // the kernels are chosen for R x batch rows.
     ModelInfo mi;
     int rc = model_info(desc, mi);
     if (rc != QHEA_OK) return rc;
@@ -1400,7 +1454,7 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
         return hipMemsetAsync(grad, 0, sizeof(double) * (mi.P + 2), st) == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
     }
     if (!branch || !params || !y || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
-    const ModelLayout M = make_model_layout(mi, batch);
+    const ModelLayout M = make_model_layout(mi, batch, R * batch);
     if (!workspace || workspace_bytes < M.total) return QHEA_EWORKSPACE;
     char* ws = static_cast<char*>(workspace);
     const EncDesc enc = make_enc(desc, mi, branch, trunk, params);
@@ -1426,20 +1480,21 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
         }
         if (dpx && !dp_blocks_ok(nb_w + nb_x + 1)) return QHEA_EUNSUPPORTED;
         if (!records_ready) {
-            rc = launch_prep_zyz(mi.n, mi.sh, params + mi.off_ans, ws, M.L, st);
+            rc = launch_prep_zyz(mi.n, mi.sh, params + mi.off_ans, ws, M.L, st, R, ms);
             if (rc != QHEA_OK) return rc;
         }
         profile_begin(st);
         rc = launch_zyz_backward(mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
                                  desc->ham_pauli, nullptr, nullptr, y, mi.has_bias ? params + mi.off_bias : nullptr,
-                                 inv_batch_total, pr, gx, partial, st);
+                                 inv_batch_total, pr, gx, partial, st, R, ms);
         profile_end(st);
         if (rc != QHEA_OK) return rc;
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
         return launch_reduce_model(nb_w + nb_x + 1, st, mi, kw, M.L.nwaves, partial, params, batch, enc, gx, pr, y,
                                    inv_batch_total, gm, nb_w, nb_x, grad, adam, ws,
-                                   reinterpret_cast<const double*>(ws + M.L.off_gmap), fp, dpx);
+                                   reinterpret_cast<const double*>(ws + M.L.off_gmap), fp, dpx, R, ms);
     }
+    if (R != 1) return QHEA_EUNSUPPORTED;                       // (the ensemble entry point never asks: R-sequential calls there)
     if (records_ready || records_for_next) return QHEA_EINVAL;
     if (dpx && !dp_blocks_ok(nb_w + nb_x + 1)) return QHEA_EUNSUPPORTED;
     rc = launch_prep_model(mi, batch, params, enc, ws, M.L, st);
@@ -1609,6 +1664,81 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
                                             has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, ham_diag,
                                             inv_batch_total[i], grad + i * grad_stride, nullptr, workspace, workspace_bytes,
                                             stream, adam, ready, next, &dx);
+        if (rc != QHEA_OK) return rc;
+        ready = next;
+    }
+    return QHEA_OK;
+}
+
+size_t qhea_model_ensemble_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch) {
+    ModelInfo mi;
+    if (model_info(desc, mi) != QHEA_OK || n_models < 1 || batch < 0) return 0;
+    return (size_t)n_models * ensemble_slice_bytes(mi, n_models, batch);
+}
+
+int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_models, int64_t n_steps, const int64_t* row_begin,
+                                    const double* branch, const double* trunk, const double* y, double* params,
+                                    const double* ham_diag, const double* inv_batch_total, double* grad, int64_t grad_stride,
+                                    double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                    double beta2, double eps, double weight_decay, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    if (!desc || n_models < 1 || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad || first_step < 1)
+        return QHEA_EINVAL;
+    ModelInfo mi;
+    const int rc0 = model_info(desc, mi);
+    if (rc0 != QHEA_OK) return rc0;
+    if (grad_stride < mi.P + 2) return QHEA_EINVAL;
+    if (!pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
+    for (int64_t i = 0; i < n_steps; ++i)
+        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
+    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
+    if (has_trunk && !trunk) return QHEA_EINVAL;
+    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    // one slice per member, sized for every batch size of the schedule; one launch per kernel where every step runs the ZYZ
+    // kernels, R consecutive single-model calls otherwise
+    size_t slice = 0;
+    bool grid = true;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int64_t nb = row_begin[i + 1] - row_begin[i];
+        const size_t b = ensemble_slice_bytes(mi, n_models, nb);
+        if (b > slice) slice = b;
+        grid = grid && n_models <= 65535 && ensemble_grid(mi, n_models, nb);      // (gridDim.y)
+    }
+    if (!workspace || workspace_bytes / (size_t)n_models < slice) return QHEA_EWORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    const int64_t rows = row_begin[n_steps];                        // rows per member
+    if (!grid) {
+        for (int64_t m = 0; m < n_models; ++m) {
+            char* wm = ws + m * slice;
+            const int rc = qhea_model_train_steps(desc, n_steps, row_begin, branch + m * rows * desc->branch_in,
+                                                  has_trunk ? trunk + m * rows * desc->trunk_in : nullptr, y + m * rows,
+                                                  params + m * mi.P, ham_diag, inv_batch_total, grad + m * n_steps * grad_stride,
+                                                  grad_stride, exp_avg + m * mi.P, exp_avg_sq + m * mi.P, first_step, lr, beta1,
+                                                  beta2, eps, weight_decay, wm, slice, stream);
+            if (rc != QHEA_OK) return rc;
+            if (m > 0) {
+                hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
+                                   reinterpret_cast<WorkspaceHeader*>(wm));
+                if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+            }
+        }
+        return QHEA_OK;
+    }
+    const MemberStride ms{(long)rows, (long)mi.P, (long)(n_steps * grad_stride), (long)slice};
+    bool ready = false;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
+        bool next = false;
+        if (i + 1 < n_steps && row_begin[i + 2] - row_begin[i + 1] == nb)
+            next = model_fuse_eligible(mi, make_model_layout(mi, nb, n_models * nb).L);
+        const int64_t step = first_step + i;
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+        const int rc = model_loss_grad_impl(desc, nb, branch + r0 * desc->branch_in,
+                                            has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, ham_diag,
+                                            inv_batch_total[i], grad + i * grad_stride, nullptr, ws, slice, stream, adam,
+                                            ready, next, nullptr, (int)n_models, ms);
         if (rc != QHEA_OK) return rc;
         ready = next;
     }

@@ -59,14 +59,17 @@ __host__ __device__ inline int zyz_layer_count(const Runs& r, int n) {
 struct AngleSrc {
     const double* x;          // [B, E] or nullptr
     EncDesc enc;
+    long m_rows = 0, m_params = 0;      // ensemble launches (hea_zyz.hpp: MemberStride): member blockIdx.y's rows / parameters
 };
 __device__ __forceinline__ double enc_angle(const AngleSrc& a, int E, long b, int e) {
     if (a.x) return a.x[b * E + e];
     const int si = e < a.enc.seg[0].ncols ? 0 : 1;
     const EncSeg& sg = a.enc.seg[si];
     const int ee = si ? e - a.enc.seg[0].ncols : e;
-    const double v = sg.in[b * sg.width + ee % sg.width];
-    return sg.w ? v * sg.w[ee] + sg.b[ee] : v * sg.scale;
+    const long m = blockIdx.y;
+    const double v = sg.in[(b + m * a.m_rows) * sg.width + ee % sg.width];
+    const long ep = ee + m * a.m_params;
+    return sg.w ? v * sg.w[ep] + sg.b[ep] : v * sg.scale;
 }
 // rows [s0, s0 + ns) x E of the group's table, spread over `nthreads` threads (tid of them); samples past the batch
 // repeat the last one (their lanes carry lambda = 0)
@@ -671,6 +674,20 @@ struct ZFwdArgs {
     int fast_ld, nblocks;       // block-unrolled fast path: sub-layers per block (0 = generic walk), number of blocks
     const char* srec;           // split records (record 0), nullptr: shape not eligible (zsplit_eligible)
 };
+// Ensemble launches (qhea_model_ensemble_train_steps): R models of one shape in ONE launch, member m = blockIdx.y.  Every
+// per-member pointer moves by m x its stride once, at kernel entry; inside a member nothing changes (same work split, same
+// summation order), and with gridDim.y = 1 every pointer stays where it is.  The workspace header (status word) is NOT
+// per member: every member reports into slice 0's, which qhea_check_status reads.
+struct MemberStride {
+    long rows;          // rows between two members' data (y: doubles; branch / trunk: x the segment's width)
+    long params;        // doubles between two members' parameter vectors and Adam moments
+    long grad;          // doubles between two members' blocks of gradient rows
+    long ws;            // bytes between two members' workspace slices (records, gmap, grad_x, pred, partial rows)
+};
+template <class T>
+__host__ __device__ __forceinline__ T* member_ptr(T* p, long bytes) {      // (nullptr stays nullptr)
+    return p ? reinterpret_cast<T*>(reinterpret_cast<typename std::conditional<std::is_const<T>::value, const char, char>::type*>(p) + bytes) : p;
+}
 struct ZBwdArgs {
     Runs runs; long B; int E; int blk; const char* rec; int rec_bytes; int L; AngleSrc src; double off, co;
     const double* diag; int pauli; const double* g; const double* state_in; const double* y; const double* bias;
@@ -678,7 +695,36 @@ struct ZBwdArgs {
     int fast_ld, nblocks;
     const char* srec;           // split records for the forward phase, nullptr: all-lane forward sweep
     int pipes;                  // bwd_ztri_kernel: sample groups per workgroup (1 or 2)
+    MemberStride ms;            // ensemble launches (model-level calls only: src.x == nullptr)
 };
+// member blockIdx.y's pointers, computed where they are used: a copy of the arguments with moved pointers would live in
+// private memory (the run table and the encoding segments are indexed at run time), and the record pointers must stay
+// uniform for the buffer resources
+// Ensemble launch: the same arguments under their own type, which selects the kernels' member instantiation (member =
+// blockIdx.y); the single-model instantiation takes ZBwdArgs and keeps its code, registers and occupancy as they were.
+struct ZBwdArgsM : ZBwdArgs {};
+template <class T>
+__device__ __forceinline__ T* uniform_ptr(T* p) {           // (read off lane 0: the compiler then knows it is uniform)
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
+}
+template <class A> __device__ __forceinline__ long zm_ws(const A& a) { return (long)blockIdx.y * a.ms.ws; }
+__device__ __forceinline__ const char* zm_rec(const ZBwdArgs& a) { return a.rec; }
+__device__ __forceinline__ const char* zm_srec(const ZBwdArgs& a) { return a.srec; }
+__device__ __forceinline__ double* zm_out(const ZBwdArgs& a) { return a.out; }
+__device__ __forceinline__ double* zm_gx(const ZBwdArgs& a) { return a.grad_x; }
+__device__ __forceinline__ double* zm_part(const ZBwdArgs& a) { return a.partial; }
+__device__ __forceinline__ const double* zm_y(const ZBwdArgs& a) { return a.y; }
+__device__ __forceinline__ const double* zm_bias(const ZBwdArgs& a) { return a.bias; }
+__device__ __forceinline__ const char* zm_rec(const ZBwdArgsM& a) { return uniform_ptr(member_ptr(a.rec, zm_ws(a))); }
+__device__ __forceinline__ const char* zm_srec(const ZBwdArgsM& a) { return uniform_ptr(member_ptr(a.srec, zm_ws(a))); }
+__device__ __forceinline__ double* zm_out(const ZBwdArgsM& a) { return member_ptr(a.out, zm_ws(a)); }
+__device__ __forceinline__ double* zm_gx(const ZBwdArgsM& a) { return member_ptr(a.grad_x, zm_ws(a)); }
+__device__ __forceinline__ double* zm_part(const ZBwdArgsM& a) { return member_ptr(a.partial, zm_ws(a)); }
+__device__ __forceinline__ const double* zm_y(const ZBwdArgsM& a) { return member_ptr(a.y, (long)blockIdx.y * a.ms.rows * (long)sizeof(double)); }
+__device__ __forceinline__ const double* zm_bias(const ZBwdArgsM& a) { return member_ptr(a.bias, (long)blockIdx.y * a.ms.params * (long)sizeof(double)); }
 
 // kZFwdWaves sweeping waves + kFwdHelpers waves that only help to fill the (cos, sin) tables and then leave: the fill is
 // 2 x 600 fp64 sincos per sweeping wave at cfg 2, ~4 us if each does its own, and the sweep cannot start before it.  Four
@@ -807,8 +853,8 @@ __device__ __forceinline__ void wait_slot_free(int* cursor, int need, int* abort
 // with that many sub-layers per block.  Publishing protocol as in bwd_tri_kernel (hea_device.hpp).
 // SPLIT (n = 5, MODE != 0): the (cos, sin) table has the 32-byte entries of the split layout, and the forward phase is
 // swept in that layout by BOTH chain waves, one sample each (zsplit_forward).
-template <int N, int MODE, bool SPLIT, int RING>
-__device__ __forceinline__ void ztri_chain(const ZBwdArgs& a, int role, int lane, int klow, bool valid, long b,
+template <int N, int MODE, bool SPLIT, int RING, class A>
+__device__ __forceinline__ void ztri_chain(const A& a, int role, int lane, int klow, bool valid, long b,
                                            const double2* cs, char* my_ring, double2 (*psi_ring)[64],
                                            double2 (*lam_ring)[64], double2* psi_final, ZSync* sync, double* axis_ring) {
     using C = Cfg<N>;
@@ -821,8 +867,8 @@ __device__ __forceinline__ void ztri_chain(const ZBwdArgs& a, int role, int lane
     const double2* csrow = cs + ((lane >> C::LB) * (int)zyz_cs_row(N, E) + N) * (SPLIT ? 2 : 1);
     LayerStream<N> ls;
     BlockStream<N, MODE == 0 ? 1 : MODE> bs;
-    if constexpr (MODE == 0) ls.init(a.rec, a.rec_bytes, my_ring, lane, klow, a.L);
-    else bs.init(a.rec, a.L + 1, my_ring, lane, klow);
+    if constexpr (MODE == 0) ls.init(zm_rec(a), a.rec_bytes, my_ring, lane, klow, a.L);
+    else bs.init(zm_rec(a), a.L + 1, my_ring, lane, klow);
     double sr[1], si[1];
     int seen[kZSigma], safe = 0;
 #pragma unroll
@@ -831,7 +877,7 @@ __device__ __forceinline__ void ztri_chain(const ZBwdArgs& a, int role, int lane
     if constexpr (SPLIT) {
         if (!a.state_in) {
             SplitStream<MODE> ss;
-            ss.init_split(a.srec, a.L + 1, my_ring, lane);
+            ss.init_split(zm_srec(a), a.L + 1, my_ring, lane);
             const char* row = reinterpret_cast<const char*>(cs) + (role * (int)zyz_cs_row(5, E) + 5) * 32;
 #ifdef QHEA_PROFILE_WAITS
             const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
@@ -872,9 +918,9 @@ __device__ __forceinline__ void ztri_chain(const ZBwdArgs& a, int role, int lane
         {
             double v[1] = {h * (fr[0] * fr[0] + fi[0] * fi[0])};
             lane_reduce<1, C::LB>(v, lane);
-            const double pred = v[0] + (a.bias ? a.bias[0] : 0.0);
-            if (a.out && valid && klow == 0) a.out[b] = pred;
-            gb = a.y ? 2.0 * (pred - a.y[b]) * a.inv_bt : a.g[b];
+            const double pred = v[0] + (zm_bias(a) ? zm_bias(a)[0] : 0.0);
+            if (zm_out(a) && valid && klow == 0) zm_out(a)[b] = pred;
+            gb = zm_y(a) ? 2.0 * (pred - zm_y(a)[b]) * a.inv_bt : a.g[b];
         }
         if (!valid) gb = 0.0;
         sr[0] = gb * h * fr[0]; si[0] = gb * h * fi[0];
@@ -1068,8 +1114,8 @@ __device__ __forceinline__ int role_of_wave() {          // 0: psi, 1: lambda, 2
     return wv % kZPipeWaves;
 }
 template <int PIPES> constexpr int kZRingDepth = PIPES == 1 ? kPairRing : 8;      // LDS: 2 x (24 + 16 + 20) KB + the row
-template <int N, int PIPES>
-__global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_waves_per_eu(4, 4))) void bwd_ztri_kernel(ZBwdArgs a) {
+template <int N, int PIPES, class A = ZBwdArgs>
+__global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_waves_per_eu(4, 4))) void bwd_ztri_kernel(A a) {
     using C = Cfg<N>;
     static_assert(C::R == 1, "all-lane layout");
     constexpr int RING = kZRingDepth<PIPES>;
@@ -1108,7 +1154,7 @@ __global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_wav
         for (int w = 0; w < kZSigma; ++w) sync.cursor[w] = split_steps ? 0 : w;
         sync.next = 0;
     }
-    const bool split = N == 5 && a.srec != nullptr && a.fast_ld != 0;
+    const bool split = N == 5 && zm_srec(a) != nullptr && a.fast_ld != 0;
     const int cs_bytes = (int)(C::SPW * zyz_cs_row(N, E) * (split ? 32 : 16));
     double2* cs = reinterpret_cast<double2*>(lds_tables + pipe * cs_bytes);
     double* row_lds = reinterpret_cast<double*>(lds_tables + PIPES * cs_bytes);    // PIPES = 2: blk x KW sums of both groups
@@ -1138,7 +1184,7 @@ __global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_wav
         else ztri_chain<N, 0, false, RING>(a, role, lane, klow, valid, b, cs, my_ring, psi_ring, lam_ring, psi_final, &sync, axis_ring);
     } else {
         // ------------------------------------------------------------------ sigma waves: inner products + sums
-        double* __restrict__ part_w = a.partial + wave * (long)a.blk * C::KW;       // PIPES = 1: this group's row
+        double* __restrict__ part_w = zm_part(a) + wave * (long)a.blk * C::KW;       // PIPES = 1: this group's row
         const int me = role - 2;
         int seen_p = 0, seen_l = 0;
         // the X, Y, Z terms of this lane for every qubit, from psi (own p, partners qv) and lambda of one published step
@@ -1217,8 +1263,8 @@ __global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_wav
                         gx[Q] = em[3 * Q] * acc3[3 * Q] + em[3 * Q + 1] * acc3[3 * Q + 1] + em[3 * Q + 2] * acc3[3 * Q + 2];
                     });
                     store_sums(acc3, sub);
-                    if constexpr (N == 5) store_grad_x5(gx, lane, wave, a.B, E, a.grad_x, bl * N, N);
-                    else store_grad_x<N>(gx, lane, wave, a.B, E, a.grad_x, bl * N, N);
+                    if constexpr (N == 5) store_grad_x5(gx, lane, wave, a.B, E, zm_gx(a), bl * N, N);
+                    else store_grad_x<N>(gx, lane, wave, a.B, E, zm_gx(a), bl * N, N);
                 } else {
                     store_sums(acc3, sub);
                 }
@@ -1273,8 +1319,8 @@ __global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_wav
                                 gx[Q] = lm.x * qv[Q].y - lm.y * qv[Q].x;
                             }
                         });
-                        if constexpr (N == 5) store_grad_x5(gx, lane, wave, a.B, E, a.grad_x, col - ne + ch * N, m);
-                        else store_grad_x<N>(gx, lane, wave, a.B, E, a.grad_x, col - ne + ch * N, m);
+                        if constexpr (N == 5) store_grad_x5(gx, lane, wave, a.B, E, zm_gx(a), col - ne + ch * N, m);
+                        else store_grad_x<N>(gx, lane, wave, a.B, E, zm_gx(a), col - ne + ch * N, m);
                     }
                     col -= ne;
                 }
@@ -1289,7 +1335,7 @@ __global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_wav
     report_abort(&sync.abort, a.status, lane);
     if constexpr (PIPES > 1) {
         __syncthreads();                                   // every wave gets here, also after an overrun
-        double* __restrict__ row = a.partial + (long)blockIdx.x * a.blk * C::KW;
+        double* __restrict__ row = zm_part(a) + (long)blockIdx.x * a.blk * C::KW;
         for (int i = (int)threadIdx.x; i < a.blk * C::KW; i += 64 * kZPipeWaves * PIPES) store_through(&row[i], row_lds[i]);
     }
 }
@@ -1336,13 +1382,13 @@ __device__ __forceinline__ void split_ry_dag(double& x, const double2& u, unsign
 // chains run in the split layout: steps drawn from a counter, the RX-chunk gradients read off the block's first sub-layer's
 // products through the batch-invariant axes (see bwd_ztri_kernel, which has the same walk inline).  `prod`: NPROD consecutive
 // producer counters, all of which must have reached a step before its slot is read.
-template <int RING, int NPROD>
-__device__ __forceinline__ void zsigma_walk(const ZBwdArgs& a, int lane, int me, long wave, double2 (*psi_ring)[64], double2 (*lam_ring)[64],
+template <int RING, int NPROD, class A>
+__device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long wave, double2 (*psi_ring)[64], double2 (*lam_ring)[64],
                                             const double* axis_ring, int* prod, int* abort_flag, int* cursor, int* next) {
     constexpr int N = 5;
     using C = Cfg<N>;
     const int E = a.E;
-    double* __restrict__ part_w = a.partial + wave * (long)a.blk * C::KW;
+    double* __restrict__ part_w = zm_part(a) + wave * (long)a.blk * C::KW;
     int seen_c[NPROD];
 #pragma unroll
     for (int i = 0; i < NPROD; ++i) seen_c[i] = 0;
@@ -1402,7 +1448,7 @@ __device__ __forceinline__ void zsigma_walk(const ZBwdArgs& a, int lane, int me,
                 gx[Q] = em[3 * Q] * acc3[3 * Q] + em[3 * Q + 1] * acc3[3 * Q + 1] + em[3 * Q + 2] * acc3[3 * Q + 2];
             });
             store_sums(acc3, sub);
-            store_grad_x5(gx, lane, wave, a.B, E, a.grad_x, bl * N, N);
+            store_grad_x5(gx, lane, wave, a.B, E, zm_gx(a), bl * N, N);
         } else {
             store_sums(acc3, sub);
         }
@@ -1413,8 +1459,8 @@ __device__ __forceinline__ void zsigma_walk(const ZBwdArgs& a, int lane, int me,
     }
 }
 
-template <int LD, int RING, int NSIG>
-__device__ __forceinline__ void zquad_chain(const ZBwdArgs& a, int role /* 0: psi, 1: lambda */, int smp, int lane, bool valid, long b,
+template <int LD, int RING, int NSIG, class A>
+__device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: lambda */, int smp, int lane, bool valid, long b,
                                             const char* cs_tables, char* my_ring, double2 (*psi_ring)[64], double2 (*lam_ring)[64],
                                             double2* psi_final, ZQSync* sync, double* axis_ring) {
     constexpr int N = 5;
@@ -1424,7 +1470,7 @@ __device__ __forceinline__ void zquad_chain(const ZBwdArgs& a, int role /* 0: ps
     const int ring_rev = ring_source<N>(lane, true);
     const unsigned mask4 = lane_sign_mask<4>(lane);
     SplitStream<LD> ss;
-    ss.init_split(a.srec, a.L + 1, my_ring, lane);
+    ss.init_split(zm_srec(a), a.L + 1, my_ring, lane);
     const char* row = cs_tables + (smp * (int)zyz_cs_row(N, E) + N) * 32;          // entry of column 0 of this sample's row
     const int slot_idx = (((smp << 5) | k) << 1) | p;                              // this lane's double in an all-lane slot
     int seen[NSIG], safe = 0;
@@ -1444,9 +1490,9 @@ __device__ __forceinline__ void zquad_chain(const ZBwdArgs& a, int role /* 0: ps
         const double h = ham_weight<N>(k, a.off, a.co, a.diag);
         double v[1] = {h * (f.x * f.x + f.y * f.y)};
         lane_reduce<1, 5>(v, lane);                            // over the sample's 32 basis states (both halves hold the sum)
-        const double pred = v[0] + (a.bias ? a.bias[0] : 0.0);
-        if (a.out && valid && lane == 0) a.out[b] = pred;
-        double gb = a.y ? 2.0 * (pred - a.y[b]) * a.inv_bt : a.g[b];
+        const double pred = v[0] + (zm_bias(a) ? zm_bias(a)[0] : 0.0);
+        if (zm_out(a) && valid && lane == 0) zm_out(a)[b] = pred;
+        double gb = zm_y(a) ? 2.0 * (pred - zm_y(a)[b]) * a.inv_bt : a.g[b];
         if (!valid) gb = 0.0;
         x = gb * h * (p ? f.y : f.x);
     }
@@ -1531,8 +1577,8 @@ __device__ __forceinline__ void zquad_chain(const ZBwdArgs& a, int role /* 0: ps
     }
 }
 
-template <int RING, int NSIG>
-__global__ __launch_bounds__(64 * (4 + NSIG)) void bwd_zquad_kernel(ZBwdArgs a) {
+template <int RING, int NSIG, class A = ZBwdArgs>
+__global__ __launch_bounds__(64 * (4 + NSIG)) void bwd_zquad_kernel(A a) {
     constexpr int N = 5;
     using C = Cfg<N>;
     extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
@@ -1635,8 +1681,8 @@ __device__ __forceinline__ void enc_inv_with_inner(double (&pr)[1], double (&pi)
     }
 }
 
-template <int N, int LD>
-__device__ __forceinline__ void zpacked_body(const ZBwdArgs& a, int wib, int lane, int klow, bool valid, long b, long wave,
+template <int N, int LD, class A>
+__device__ __forceinline__ void zpacked_body(const A& a, int wib, int lane, int klow, bool valid, long b, long wave,
                                              const double2* cs, char* wg_ring, double* comb /* [2][kZPWaves][2 * KW] */) {
     using C = Cfg<N>;
     const int E = a.E;
@@ -1644,7 +1690,7 @@ __device__ __forceinline__ void zpacked_body(const ZBwdArgs& a, int wib, int lan
     const int ring_rev = ring_source<N>(lane, true);
     const double2* csrow = cs + (wib * C::SPW + (lane >> C::LB)) * (int)zp_cs_row(N, E) + N;
     BlockStream<N, LD, true> bs;
-    bs.init(a.rec, a.L + 1, wg_ring, lane, klow);
+    bs.init(zm_rec(a), a.L + 1, wg_ring, lane, klow);
     bs.loader = wib == 0;
 
     double pr[1], pi[1], lr[1], li[1];
@@ -1660,9 +1706,9 @@ __device__ __forceinline__ void zpacked_body(const ZBwdArgs& a, int wib, int lan
         const double h = ham_weight<N>(klow, a.off, a.co, a.diag);
         double v[1] = {h * (fr[0] * fr[0] + fi[0] * fi[0])};
         lane_reduce<1, C::LB>(v, lane);
-        const double pred = v[0] + (a.bias ? a.bias[0] : 0.0);
-        if (a.out && valid && klow == 0) a.out[b] = pred;
-        double gb = a.y ? 2.0 * (pred - a.y[b]) * a.inv_bt : a.g[b];
+        const double pred = v[0] + (zm_bias(a) ? zm_bias(a)[0] : 0.0);
+        if (zm_out(a) && valid && klow == 0) zm_out(a)[b] = pred;
+        double gb = zm_y(a) ? 2.0 * (pred - zm_y(a)[b]) * a.inv_bt : a.g[b];
         if (!valid) gb = 0.0;
         lr[0] = gb * h * fr[0]; li[0] = gb * h * fi[0];
         basis_change<N, true>(lr, li, a.pauli, lane);
@@ -1683,7 +1729,7 @@ __device__ __forceinline__ void zpacked_body(const ZBwdArgs& a, int wib, int lan
     // are combined before they leave the chip: every wave parks a block's sums in LDS, and after the next block's barrier one
     // wave adds the four in a fixed order and writes ONE row per workgroup -- a quarter of the partial rows (B = 16384 at cfg 2:
     // 63 MB instead of 252 MB written and read back per call).
-    double* __restrict__ row_w = a.partial + (long)blockIdx.x * a.blk * C::KW;
+    double* __restrict__ row_w = zm_part(a) + (long)blockIdx.x * a.blk * C::KW;
     constexpr int kSlotVals = 2 * C::KW;                          // room for LD <= 2 sub-layers of KW values
     auto combine = [&](int blk_done) {                            // the sums of block `blk_done` (parked before the last barrier)
         if (wib == (blk_done & (kZPWaves - 1)) && lane < LD * C::KW) {
@@ -1733,8 +1779,8 @@ __device__ __forceinline__ void zpacked_body(const ZBwdArgs& a, int wib, int lan
             enc_inv_with_inner<N, Q>(pr, pi, lr, li, bs.cs[Q], lane, gx[Q]);
             bs.cs[Q] = cn[Q];
         });
-        if constexpr (N == 5) store_grad_x5(gx, lane, wave, a.B, E, a.grad_x, bl * N, N);
-        else store_grad_x<N>(gx, lane, wave, a.B, E, a.grad_x, bl * N, N);
+        if constexpr (N == 5) store_grad_x5(gx, lane, wave, a.B, E, zm_gx(a), bl * N, N);
+        else store_grad_x<N>(gx, lane, wave, a.B, E, zm_gx(a), bl * N, N);
         apply_phase<true>(pr[0], pi[0], bs.dg[0]);
         apply_phase<true>(lr[0], li[0], bs.dg[0]);
         bs.dg[0] = bs.rd(nx, bs.a_dg);
@@ -1755,8 +1801,8 @@ __device__ __forceinline__ void zpacked_body(const ZBwdArgs& a, int wib, int lan
     combine(0);
 }
 
-template <int N>
-__global__ __launch_bounds__(kZPWaves * 64) void bwd_zpacked_kernel(ZBwdArgs a) {
+template <int N, class A = ZBwdArgs>
+__global__ __launch_bounds__(kZPWaves * 64) void bwd_zpacked_kernel(A a) {
     using C = Cfg<N>;
     static_assert(C::R == 1, "all-lane layout");
     extern __shared__ __attribute__((aligned(16))) char dyn_lds[];                 // kZPWaves x SPW x (E + 2N) (cos, sin)
