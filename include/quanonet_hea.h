@@ -92,6 +92,11 @@ int qhea_device_count(void);
 #define QHEA_BWD_ZQUAD  7      /* n = 5, block-unrolled shapes: the pipeline with BOTH sweeps of every chain in the split layout */
                                /* (one sample per chain wave, four chain waves per sample group).  AUTO runs it while every    */
                                /* CU holds at most one sample group; ZQUAD forces it at any batch                               */
+#define QHEA_BWD_ZSNAP  8      /* n = 5, block-unrolled shapes, two sample groups per workgroup: one chain wave per sample     */
+                               /* sweeps forward storing psi at every publication point, then walks lambda back in the split   */
+                               /* layout; the sigma waves read psi from those snapshots (no psi walk back).  AUTO runs it     */
+                               /* where it would take ZTRI2 (more sample groups than CUs, at most two per CU; single models, */
+                               /* Z / diagonal read-out); ZSNAP forces it at any batch, ZTRI2 forces the psi walk back        */
 int qhea_set_backward_variant(int variant);
 
 /*

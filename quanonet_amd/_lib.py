@@ -43,7 +43,7 @@ class ModelDesc(ctypes.Structure):
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
 MIN_LIB_VERSION = 450           # 0.4.5: + qhea_model_ensemble_train_steps (R models per launch, member = blockIdx.y)
-BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7}
+BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
 

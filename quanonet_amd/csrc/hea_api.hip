@@ -506,6 +506,9 @@ struct Layout {
     int zpipes;             // bwd_ztri_kernel: sample groups per workgroup (2 halves the partial rows; hea_zyz.hpp)
     bool zquad;             // quad-chain pipeline (bwd_zquad_kernel): reverse walks in the split layout too; batches of at most one
                             // sample group per CU (Z / diagonal read-out: checked at the launch)
+    bool zsnap;             // snapshot pipeline (bwd_zsnap_kernel): psi snapshots of the forward sweep at off_snap (single-model
+                            // layouts only; Z / diagonal read-out and no given final state: checked at the launch, else ztri<5, 2>)
+    size_t off_snap;
 };
 
 // Pipelined backward kernels (n <= 5): several waves per sample group (psi chain, lambda chain, sigma waves), so they
@@ -537,7 +540,8 @@ bool use_pair(int n, int64_t B) {
     if (n > 5 || B <= 0) return false;
     const int v = g_bwd_variant.load(std::memory_order_relaxed);
     if (v == QHEA_BWD_PACKED || v == QHEA_BWD_ZPACKED) return false;
-    if (v == QHEA_BWD_PAIR || v == QHEA_BWD_TRI || v == QHEA_BWD_ZTRI || v == QHEA_BWD_ZTRI2 || v == QHEA_BWD_ZQUAD) return true;
+    if (v == QHEA_BWD_PAIR || v == QHEA_BWD_TRI || v == QHEA_BWD_ZTRI || v == QHEA_BWD_ZTRI2 || v == QHEA_BWD_ZQUAD ||
+        v == QHEA_BWD_ZSNAP) return true;
     // measured at n = 5, cfg 2's circuit (us per training step, pipelined in two rounds / one wave per group,
     // profiles/r03_batch_sweep.txt, end of round 3): B = 1100 141.3 / 153.3, 1280 142.0 / 154.3, 1536 144.2 / 155.8,
     // 1792 216.2 / 156.9 -- pipelined while the sample groups fill at most 6/8 of the SIMDs (3 per CU: two rounds of the
@@ -576,7 +580,7 @@ Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
     const int var = g_bwd_variant.load(std::memory_order_relaxed);
     const bool zok = zyz_eligible(n, sh.E) &&
                      (var == QHEA_BWD_AUTO || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZPACKED ||
-                      var == QHEA_BWD_ZQUAD);
+                      var == QHEA_BWD_ZQUAD || var == QHEA_BWD_ZSNAP);
     // Measured at cfg 2's circuit (us per call incl. prep / reduce; first-generation / ZYZ form):
     //   forward   B = 1024 55 / 44,  4096 87 / 89,  16384 236 / 255 with a record ring per wave (22 KB of LDS per wave
     //             cap the waves per CU once the batch could fill them) -> one ring per workgroup beyond one wave per SIMD
@@ -588,7 +592,8 @@ Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
     // forward: private-ring kernel while the sweeps leave SIMDs free, shared-ring kernel (block-unrolled shapes) beyond;
     // other shapes fall back to the first-generation forward once two waves per SIMD are reached
     L.zfwd_shared = fast && (var == QHEA_BWD_ZPACKED || (var == QHEA_BWD_AUTO && nwaves_fwd_d > (long)simd_count()));
-    L.zfwd = zok && (L.zfwd_shared || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZQUAD || nwaves_fwd_d <= 2L * simd_count());
+    L.zfwd = zok && (L.zfwd_shared || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZQUAD || var == QHEA_BWD_ZSNAP ||
+                     nwaves_fwd_d <= 2L * simd_count());
     L.ztri = zok && L.pair;
     // batches that fill the SIMDs: the one-wave ZYZ kernel for the block-unrolled shapes (B = 16384 at cfg 2's circuit:
     // see DESIGN.md section 3.5), the first-generation packed kernel otherwise
@@ -610,6 +615,7 @@ Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
     L.zpipes = 1;
     const long cus = (long)simd_count() / 4;
     const bool two_wanted = var == QHEA_BWD_ZTRI2 ? groups_d > cus
+                          : var == QHEA_BWD_ZSNAP ? true
                                                   : (var == QHEA_BWD_AUTO && groups_d > cus && groups_d <= 2 * cus);
     if (L.ztri && two_wanted) {
         const size_t cs_bytes = (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * (L.zsplit ? 32 : 16);
@@ -633,6 +639,19 @@ Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
     L.off_srec = p; p = align_up(p + (L.zsplit ? (size_t)(L.zL + 1 + 2 * kPadRecs) * kRecBytes : 0));
     if (L.zsplit) L.off_srec += (size_t)kPadRecs * kRecBytes;
     L.off_gmap = p; p = align_up(p + (zok ? (size_t)sh.blk * n * kGmapDoubles * sizeof(double) : 0));
+    // Snapshot pipeline (bwd_zsnap_kernel): where AUTO takes two pipelines per workgroup (more sample groups than CUs, at most
+    // two per CU), the sigma waves read psi from the forward sweep's snapshots instead of a psi chain walking back (cfg 2,
+    // B = 1024: kernel 74.5 -> 70.0 us, step 0.0828 -> 0.0783 ms).  psi of every sample group at every
+    // publication point, 1 KB each (61 MB at B = 1024, cfg 2); the region exists only in the layouts that select the kernel,
+    // so qhea_workspace_bytes agrees with the call.  Single-model layouts only (ensembles keep bwd_ztri_kernel).
+    L.zsnap = L.ztri && L.zsplit && L.zpipes == 2 && B == Bd &&
+              (var == QHEA_BWD_ZSNAP || (var == QHEA_BWD_AUTO && groups_d > cus && groups_d <= 2 * cus));
+    L.off_snap = p;
+    if (L.zsnap) {
+        int nblocks = 0;
+        for (int i = 0; i < sh.runs.nruns; ++i) nblocks += sh.runs.count[i];
+        p = align_up(p + (size_t)(2 * L.nwaves) * nblocks * zyz_fast_ld(sh.runs, n) * kSnapBytes);
+    }
     L.total = p;
     return L;
 }
@@ -714,6 +733,11 @@ int launch_zyz_backward(int n, const Shape& sh, int64_t B, const Layout& L, char
 #undef QHEA_CASE
             default: return QHEA_EUNSUPPORTED;
         }
+        return QHEA_OK;
+    }
+    if (L.zsnap && n == 5 && pauli == QHEA_PAULI_Z && za.srec && !state_in && R == 1) {
+        za.snap = ws + L.off_snap;
+        launch_bwd_zsnap_5(dim3((unsigned)L.nwaves, gy), 2 * (zsnap_fixed_lds(kZSnapRing) + 2 * dyn) + (size_t)sh.blk * padded_3n(n) * sizeof(double), st, za);
         return QHEA_OK;
     }
     if (L.zquad && n == 5 && pauli == QHEA_PAULI_Z && za.srec) {
@@ -1193,7 +1217,7 @@ int qhea_clock_probe(int n_workgroups, int64_t iters, unsigned long long* ticks 
 }
 
 int qhea_set_backward_variant(int variant) {
-    if (variant < QHEA_BWD_AUTO || variant > QHEA_BWD_ZQUAD) return QHEA_EINVAL;
+    if (variant < QHEA_BWD_AUTO || variant > QHEA_BWD_ZSNAP) return QHEA_EINVAL;
     g_bwd_variant.store(variant, std::memory_order_relaxed);
     return QHEA_OK;
 }

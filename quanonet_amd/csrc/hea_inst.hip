@@ -74,6 +74,9 @@ void launch_bwd_zquad_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArg
     if (grid.y > 1) hipLaunchKernelGGL((bwd_zquad_kernel<kPairRing, kZSigma, ZBwdArgsM>), grid, dim3(64 * (4 + kZSigma)), dyn_lds, st, ZBwdArgsM{a});
     else hipLaunchKernelGGL((bwd_zquad_kernel<kPairRing, kZSigma>), grid, dim3(64 * (4 + kZSigma)), dyn_lds, st, a);
 }
+void launch_bwd_zsnap_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a) {     // single-model launches only
+    hipLaunchKernelGGL((bwd_zsnap_kernel<kZSnapRing>), grid, dim3(64 * (4 + 2 * kZSigma)), dyn_lds, st, a);
+}
 #endif
 #elif QHEA_N <= 5      // layout-experiment build: the ZYZ kernels need the all-lane layout and are never selected
 void QHEA_CAT(launch_fwd_zyz_, QHEA_N)(dim3, size_t, hipStream_t, const ZFwdArgs&) {}
@@ -83,6 +86,7 @@ void QHEA_CAT(launch_fwd_zshared_, QHEA_N)(dim3, size_t, hipStream_t, const ZFwd
 #if QHEA_N == 5
 void launch_fwd_split_5(dim3, size_t, hipStream_t, const ZFwdArgs&) {}
 void launch_bwd_zquad_5(dim3, size_t, hipStream_t, const ZBwdArgs&) {}
+void launch_bwd_zsnap_5(dim3, size_t, hipStream_t, const ZBwdArgs&) {}
 #endif
 #endif
 

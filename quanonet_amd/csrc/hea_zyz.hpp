@@ -606,8 +606,12 @@ struct SplitStream : BlockStream<5, LD, false> {
 
 // forward sweep of ONE sample in the split layout; csrow: the sample's table row, entry of column 0; returns this
 // lane's Re (lanes 0..31) or Im (lanes 32..63) of psi_N[lane & 31]
-template <int LD>
-__device__ __forceinline__ double zsplit_forward(SplitStream<LD>& bs, const char* csrow, int nblocks, int lane, int ring_fwd) {
+// SNAP (bwd_zsnap_kernel): the state is also stored at every publication point -- after a sub-layer's RY gates, in front of
+// its ring gather -- point f = LD b + s to snap_base + f kSnapBytes + snap_off (the all-lane hand-off order; plain stores)
+constexpr int kSnapBytes = 1024;               // one sample group's state at one publication point
+template <int LD, bool SNAP = false>
+__device__ __forceinline__ double zsplit_forward(SplitStream<LD>& bs, const char* csrow, int nblocks, int lane, int ring_fwd,
+                                                 char* snap_base = nullptr, unsigned snap_off = 0) {
     double x = lane == 0 ? 1.0 : 0.0;
     bs.template prime<1>(0, false);
     const char* cs_b = csrow;                            // entry of block b's first column
@@ -625,9 +629,15 @@ __device__ __forceinline__ double zsplit_forward(SplitStream<LD>& bs, const char
         static_for<0, 5>([&](auto q) { ce.g[decltype(q)::value] = bs.rd(cn, bs.a_cs[decltype(q)::value]); });
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto layer = [&](const LayerCoef<5>& c, bool ring) {
+    auto layer = [&](const LayerCoef<5>& c, bool ring, int pt) {
         split_phase(x, c.dg);
         static_for<0, 5>([&](auto q) { split_ry<decltype(q)::value>(x, c.g[decltype(q)::value]); });
+        if constexpr (SNAP) {
+            if (ring) {                                  // a global_store: a flat one would also count in lgkmcnt
+                typedef __attribute__((address_space(1))) double gdouble;
+                *(gdouble*)(snap_base + (size_t)(unsigned)pt * kSnapBytes + snap_off) = x;
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (ring) x = lane_gather(x, ring_fwd);
     };
@@ -635,19 +645,19 @@ __device__ __forceinline__ double zsplit_forward(SplitStream<LD>& bs, const char
         const char* cur = bs.template slot_rel<0>(sl);
         const char* nx = bs.template slot_rel<1>(sl);
         read_layer(ca, cur, 1);
-        layer(ce, false);
+        layer(ce, false, 0);
         if constexpr (LD == 2) {
             read_layer(cb, cur, 2);
-            layer(ca, true);
+            layer(ca, true, 2 * b);
             bs.template ahead_rel<kBDist + 1>(sl, b);    // in the gather's shadow
             __builtin_amdgcn_sched_barrier(0);
             bs.landed_late();
             read_chunk(nx, kb);
-            layer(cb, true);
+            layer(cb, true, 2 * b + 1);
         } else {
             bs.landed();
             read_chunk(nx, kb);
-            layer(ca, true);
+            layer(ca, true, b);
             bs.template ahead_rel<kBDist + 1>(sl, b);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -696,6 +706,7 @@ struct ZBwdArgs {
     const char* srec;           // split records for the forward phase, nullptr: all-lane forward sweep
     int pipes;                  // bwd_ztri_kernel: sample groups per workgroup (1 or 2)
     MemberStride ms;            // ensemble launches (model-level calls only: src.x == nullptr)
+    char* snap = nullptr;       // bwd_zsnap_kernel: psi snapshots, groups x nblocks x LD x kSnapBytes (single-model launches only)
 };
 // member blockIdx.y's pointers, computed where they are used: a copy of the arguments with moved pointers would live in
 // private memory (the run table and the encoding segments are indexed at run time), and the record pointers must stay
@@ -1382,9 +1393,13 @@ __device__ __forceinline__ void split_ry_dag(double& x, const double2& u, unsign
 // chains run in the split layout: steps drawn from a counter, the RX-chunk gradients read off the block's first sub-layer's
 // products through the batch-invariant axes (see bwd_ztri_kernel, which has the same walk inline).  `prod`: NPROD consecutive
 // producer counters, all of which must have reached a step before its slot is read.
-template <int RING, int NPROD, class A>
+// SNAP (bwd_zsnap_kernel): psi of step t is the forward sweep's snapshot of publication point nsteps - 1 - t, brought from the
+// group's snapshot region (`snap_rsrc`) into this wave's LDS double buffer (`psi_ring`: two slots) by LDS-DMA, issued one step
+// ahead, as soon as the step is known; the sums go into the workgroup's shared row (`row_lds`, two addends per element).
+template <int RING, int NPROD, bool SNAP = false, class A>
 __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long wave, double2 (*psi_ring)[64], double2 (*lam_ring)[64],
-                                            const double* axis_ring, int* prod, int* abort_flag, int* cursor, int* next) {
+                                            const double* axis_ring, int* prod, int* abort_flag, int* cursor, int* next,
+                                            u32x4 snap_rsrc = u32x4{}, double* row_lds = nullptr) {
     constexpr int N = 5;
     using C = Cfg<N>;
     const int E = a.E;
@@ -1405,9 +1420,21 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
     };
     auto store_sums = [&](double (&acc3)[C::KW], int sub) {
         const int vi = butterfly_sum<C::KW>(acc3, lane);
-        if (butterfly_owner<C::KW>(lane)) store_through(&part_w[(long)sub * C::KW + vi], acc3[0]);
+        if (butterfly_owner<C::KW>(lane)) {
+            if constexpr (SNAP) __hip_atomic_fetch_add(&row_lds[sub * C::KW + vi], acc3[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else store_through(&part_w[(long)sub * C::KW + vi], acc3[0]);
+        }
     };
     const int LDr = a.fast_ld, nsteps = a.nblocks * LDr;
+    // snapshot of step t into slot `sl` (sc1: from L2, never a vector-L1 line of an earlier step's data at that address).  The
+    // slots alternate per step of THIS wave (its steps are drawn, not consecutive)
+    const unsigned snap_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)(psi_ring[0]);
+    int cur = 0;
+    auto fetch_snap = [&](int t, int sl) {
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
+                     :: "s"(snap_lds + (unsigned)sl * kSnapBytes), "v"((unsigned)lane * 16u), "s"(snap_rsrc),
+                        "s"((unsigned)(nsteps - 1 - t) * kSnapBytes) : "memory", "m0");
+    };
     auto draw = [&]() {
         int v = 0;
         if (lane == 0) v = __hip_atomic_fetch_add(next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1416,6 +1443,15 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
     int mine = __builtin_amdgcn_readfirstlane(draw());
     __hip_atomic_store(&cursor[me], mine, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     int after_v = draw();
+    if constexpr (SNAP) {
+        // every snapshot exists once both chains have published once (they drain their stores before that); after this one
+        // wait the fetches need no further ordering
+        if (mine < nsteps) {
+#pragma unroll
+            for (int i = 0; i < NPROD; ++i) pair_wait_ge(&prod[i], 1, abort_flag, seen_c[i]);
+            fetch_snap(mine, 0);
+        }
+    }
     auto sigma_step = [&](auto chunk_c) {
         constexpr bool CHUNK = decltype(chunk_c)::value;
         const int t = mine;
@@ -1423,7 +1459,8 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
         const int sub = a.blk - 1 - t, bl = a.nblocks - 1 - j;
 #pragma unroll
         for (int i = 0; i < NPROD; ++i) pair_wait_ge(&prod[i], t + 1, abort_flag, seen_c[i]);
-        const double2* slot = psi_ring[t & (RING - 1)];
+        if constexpr (SNAP) wait_vmcnt<0>();              // this step's snapshot (issued a step ago) has landed
+        const double2* slot = SNAP ? psi_ring[cur] : psi_ring[t & (RING - 1)];
         const double2 pv = slot[lane];
         double2 qv[N];
         static_for<0, N>([&](auto q) { qv[decltype(q)::value] = slot[lane ^ (1 << decltype(q)::value)]; });
@@ -1437,6 +1474,10 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
         if (lane == 0) __hip_atomic_store(&cursor[me], after_v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         mine = __builtin_amdgcn_readfirstlane(after_v);
         after_v = draw();
+        if constexpr (SNAP) {
+            cur ^= 1;                                     // the other slot: read last in the previous step, long done
+            if (mine < nsteps) fetch_snap(mine, cur);
+        }
         double acc3[C::KW];
         products(acc3, pv, qv, lm);
         if constexpr (CHUNK) {
@@ -1459,10 +1500,12 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
     }
 }
 
-template <int LD, int RING, int NSIG, class A>
+// SNAP (bwd_zsnap_kernel): ONE chain wave per sample -- the forward sweep (storing psi at every publication point: `snap`, the
+// group's snapshot region), then lambda_N from the psi_N it holds and lambda walked back; role must be 1, there is no psi walk.
+template <int LD, int RING, int NSIG, bool SNAP = false, class A>
 __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: lambda */, int smp, int lane, bool valid, long b,
                                             const char* cs_tables, char* my_ring, double2 (*psi_ring)[64], double2 (*lam_ring)[64],
-                                            double2* psi_final, ZQSync* sync, double* axis_ring) {
+                                            double2* psi_final, ZQSync* sync, double* axis_ring, char* snap = nullptr) {
     constexpr int N = 5;
     __builtin_amdgcn_s_setprio(3);
     const int E = a.E, k = lane & 31, p = lane >> 5;
@@ -1477,15 +1520,20 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
 #pragma unroll
     for (int w = 0; w < NSIG; ++w) seen[w] = 0;
     double x;
-    if (role == 0) {
+    if constexpr (SNAP) {
+        x = zsplit_forward<LD, true>(ss, row, a.nblocks, lane, ring_fwd, snap, (unsigned)slot_idx * 8u);
+        reinterpret_cast<double*>(psi_final)[slot_idx] = x;     // read back below in the all-lane order by this same wave
+        handoff_release();
+    } else if (role == 0) {
         if (a.state_in) x = a.state_in[(((b << N) + k) << 1) | p];
         else x = zsplit_forward<LD>(ss, row, a.nblocks, lane, ring_fwd);
         reinterpret_cast<double*>(psi_final)[slot_idx] = x;
         handoff_release();
         if (lane == 0) __hip_atomic_store(&sync->ready[smp], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    } else {
+    }
+    if (SNAP || role == 1) {
         int seen_ready = 0;
-        pair_wait_ge(&sync->ready[smp], 1, &sync->abort, seen_ready);
+        if (!SNAP) pair_wait_ge(&sync->ready[smp], 1, &sync->abort, seen_ready);
         const double2 f = psi_final[(smp << 5) | k];
         const double h = ham_weight<N>(k, a.off, a.co, a.diag);
         double v[1] = {h * (f.x * f.x + f.y * f.y)};
@@ -1511,6 +1559,8 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
     // ---- block-unrolled reverse walk in the split layout (the all-lane one: ztri_chain)
     const int nb = a.nblocks;
     const unsigned a_dgd = (unsigned)k * 24u + (unsigned)(1 - p) * 8u;             // the inverse diagonal's two entries
+    // (drains vmcnt: with SNAP every snapshot store has reached L2 before the first publication releases a sigma wave, whose
+    // snapshot loads are ordered behind that publication -- zsigma_walk)
     ss.template prime<-1>(nb, true);
     split_phase_dag(x, ss.rd8(ss.slot(nb), a_dgd));                                // block nb's slot: its record 0 is the final diagonal
     ss.template step<-1>(nb);
@@ -1617,6 +1667,86 @@ __global__ __launch_bounds__(64 * (4 + NSIG)) void bwd_zquad_kernel(A a) {
         zsigma_walk<RING, 4>(a, lane, wv - 4, wave, psi_ring, lam_ring, axis_ring, &sync.psi_prod[0], &sync.abort, sync.cursor, &sync.next);
     }
     report_abort(&sync.abort, a.status, lane);
+}
+
+// ---------------------------------------------------------------------------------------
+// Snapshot pipeline (n = 5, block-unrolled shapes, Z / diagonal read-out): the backward kernel for batches with more sample
+// groups than CUs and at most two per CU (513 ... 1024 samples on 256 CUs), where bwd_ztri_kernel<5, 2> walked psi AND lambda
+// back in the all-lane layout.  The psi walk only recomputed states the forward sweep had already passed through, so here
+// the forward sweep keeps them: every chain wave stores its sample's state at each of the nblocks x LD publication points
+// (zsplit_forward<SNAP>: 8 bytes per lane in the all-lane hand-off order, one kSnapBytes slot per group and point, in the
+// workspace), then forms lambda_N from the psi_N it holds and walks lambda back in the split layout (zquad_chain<SNAP>).  That
+// keeps ONE chain wave per sample -- one per SIMD, at the front of the workgroup -- where a split-layout psi
+// walk (bwd_zquad_kernel) would need two.  The sigma waves (four per group, zsigma_walk<SNAP>) take psi from the snapshots
+// by LDS-DMA into a private double buffer; their sums and the partial-row layout are those of bwd_ztri_kernel<5, 2>.
+//     wave 0..3     chains: group wv / 2, sample wv % 2
+//     wave 4..      sigma waves: group (wv - 4) / kZSigma
+// Per group: [2 record rings | lambda ring | psi_N | sync | axis ring | kZSigma x 2 snapshot slots]; then the two groups'
+// (cos, sin) tables and the shared row.
+// ---------------------------------------------------------------------------------------
+constexpr int kZSnapRing = 8;
+__host__ __device__ constexpr size_t zsnap_fixed_lds(int ring) {
+    return 2 * (size_t)kBlockRingBytes + (size_t)ring * 1024 + 1024 + 256 + (size_t)kAxisRing * 15 * sizeof(double) +
+           (size_t)kZSigma * 2 * kSnapBytes;
+}
+template <int RING, class A = ZBwdArgs>
+__global__ __launch_bounds__(64 * (4 + 2 * kZSigma)) __attribute__((amdgpu_waves_per_eu(4, 4))) void bwd_zsnap_kernel(A a) {
+    constexpr int N = 5;
+    using C = Cfg<N>;
+    extern __shared__ __attribute__((aligned(16))) char dyn_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int tid = (int)threadIdx.x;
+    const int grp = wv < 4 ? (wv >> 1) : (wv - 4) / kZSigma;
+    char* fixed = dyn_lds + grp * (int)zsnap_fixed_lds(RING);
+    char* rec_ring = fixed;
+    double2 (*lam_ring)[64] = reinterpret_cast<double2 (*)[64]>(fixed + 2 * kBlockRingBytes);
+    double2* psi_final = reinterpret_cast<double2*>(fixed + 2 * kBlockRingBytes + RING * 1024);
+    ZQSync& sync = *reinterpret_cast<ZQSync*>(fixed + 2 * kBlockRingBytes + RING * 1024 + 1024);
+    static_assert(sizeof(ZQSync) <= 256, "reserved");
+    double* axis_ring = reinterpret_cast<double*>(fixed + 2 * kBlockRingBytes + RING * 1024 + 1024 + 256);
+    char* snap_bufs = fixed + 2 * kBlockRingBytes + RING * 1024 + 1024 + 256 + kAxisRing * 15 * sizeof(double);
+    char* lds_tables = dyn_lds + 2 * (int)zsnap_fixed_lds(RING);
+    const int E = a.E;
+    const int cs_bytes = (int)(C::SPW * zyz_cs_row(N, E) * 32);
+    double* row_lds = reinterpret_cast<double*>(lds_tables + 2 * cs_bytes);      // blk x KW sums of both groups
+    const long wave = (long)blockIdx.x * 2 + grp;                                // this wave's sample group
+    const int nsteps = a.nblocks * a.fast_ld;
+    char* snap = a.snap + wave * (long)nsteps * kSnapBytes;                       // the group's snapshot region
+    if (tid < 2) {
+        ZQSync& s = *reinterpret_cast<ZQSync*>(dyn_lds + tid * (int)zsnap_fixed_lds(RING) + 2 * kBlockRingBytes + RING * 1024 + 1024);
+        s.psi_prod[0] = s.psi_prod[1] = s.lam_prod[0] = s.lam_prod[1] = 0;
+        s.ready[0] = s.ready[1] = 0; s.abort = 0;
+        for (int w = 0; w < kZSigma; ++w) s.cursor[w] = 0;
+        s.next = 0;
+    }
+    for (int i = tid; i < a.blk * C::KW; i += 64 * (4 + 2 * kZSigma)) row_lds[i] = 0.0;
+    // both groups' rows in one pass: the four samples' rows are contiguous
+    fill_cs_split(reinterpret_cast<double4*>(lds_tables), a.src, E, (long)blockIdx.x * 2 * C::SPW, a.B, 2 * C::SPW, tid, 64 * (4 + 2 * kZSigma));
+    __syncthreads();
+
+    if (wv < 4) {
+        const int smp = wv & 1;
+        const long b_raw = wave * C::SPW + smp;
+        const bool valid = b_raw < a.B;
+        const long b = valid ? b_raw : a.B - 1;
+        char* my_ring = rec_ring + smp * kBlockRingBytes;
+        char* cs_tables = lds_tables + grp * cs_bytes;
+        char* snap_u = uniform_ptr(snap);
+        if (a.fast_ld == 2) zquad_chain<2, RING, kZSigma, true>(a, 1, smp, lane, valid, b, cs_tables, my_ring, lam_ring, lam_ring, psi_final, &sync, axis_ring, snap_u);
+        else zquad_chain<1, RING, kZSigma, true>(a, 1, smp, lane, valid, b, cs_tables, my_ring, lam_ring, lam_ring, psi_final, &sync, axis_ring, snap_u);
+    } else {
+        const int me = (wv - 4) % kZSigma;
+        const unsigned long long base = reinterpret_cast<unsigned long long>(uniform_ptr(snap));
+        const u32x4 rsrc{(unsigned)base, (unsigned)(base >> 32) & 0xffffu, (unsigned)nsteps * kSnapBytes, 0x00020000u};
+        double2 (*buf)[64] = reinterpret_cast<double2 (*)[64]>(snap_bufs + me * 2 * kSnapBytes);
+        zsigma_walk<RING, 2, true>(a, lane, me, wave, buf, lam_ring, axis_ring, &sync.lam_prod[0], &sync.abort, sync.cursor, &sync.next,
+                                   rsrc, row_lds);
+    }
+    report_abort(&sync.abort, a.status, lane);
+    __syncthreads();                                       // every wave gets here, also after an overrun
+    double* __restrict__ row = zm_part(a) + (long)blockIdx.x * a.blk * C::KW;
+    for (int i = tid; i < a.blk * C::KW; i += 64 * (4 + 2 * kZSigma)) store_through(&row[i], row_lds[i]);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1877,6 +2007,7 @@ __global__ __launch_bounds__(kZPWaves * 64) void fwd_zshared_kernel(ZFwdArgs a) 
 QHEA_FOR_EACH_ZN(QHEA_ZDECLARE)
 void launch_fwd_split_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArgs& a);
 void launch_bwd_zquad_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a);
+void launch_bwd_zsnap_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a);
 #undef QHEA_ZDECLARE
 
 }  // namespace qhea
