@@ -375,7 +375,8 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
  * Shapes the n <= 5 ZYZ kernels do not take (n >= 6, first-generation variants, shapes not eligible) run as n_models
  * consecutive qhea_model_train_steps calls on the same stream, one workspace slice each.  An overrun in any member is
  * reported by qhea_check_status on this workspace.  Workspace: qhea_model_ensemble_workspace_bytes for every batch size
- * of the schedule (the largest of those).
+ * of the schedule (the largest of those).  Bytes 64..111 of every member's slice hold that member's hyper-parameters for the
+ * one-launch path (written by the call itself; qhea_model_sweep_train_steps below).
  */
 size_t qhea_model_ensemble_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch);
 int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_models, int64_t n_steps,
@@ -387,6 +388,41 @@ int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_model
                                     double* exp_avg /*DEVICE [n_models][P]*/, double* exp_avg_sq, int64_t first_step,
                                     double lr, double beta1, double beta2, double eps, double weight_decay,
                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Model sweep: qhea_model_ensemble_train_steps for members that also differ in their read-out, fixed encoding scale and Adam
+ * learning rate -- an ablation grid of one circuit shape (the reference's reproduce_hamiltonian.sh / reproduce_benchmarks1.sh
+ * cells: --ham_pauli, --ham_bound, --ham_diag, --scale_coeff, --learning_rate x seeds) trained as one launch per kernel.
+ * `desc` fixes the shape only (model, n_qubits, net, input widths, trainable_freq); its ham_pauli, scale_coeff, ham_offset
+ * and ham_coeff are NOT used: member m reads out members[m].ham_pauli with H = ham_offset + ham_coeff * sum P_i, or
+ * diag(ham_diag + m * 2^n) when ham_diag != NULL (then every member must read out Z), encodes with members[m].scale_coeff
+ * when trainable_freq == 0, and takes Adam steps of members[m].lr (finite, >= 0; beta1, beta2, eps, weight_decay are shared).
+ * The other arguments are qhea_model_ensemble_train_steps' (same layouts, same workspace rules).  `members` is read before
+ * the call returns; the table reaches the device as kernel arguments (one small launch per 64 members and call), so the call
+ * stays hipGraph-capturable.  Results: member m's are bitwise those of qhea_model_train_steps with m's descriptor (desc with
+ * m's scale, offset, coeff, Pauli), lr = members[m].lr and ham_diag + m * 2^n, under the backward variant the sweep chose:
+ * the kernels are chosen as for ONE batch of n_models x B rows, and as for an X / Y model if any member reads out X or Y.
+ * Shapes outside the one-launch path run as n_models consecutive qhea_model_train_steps calls with the members' descriptors.
+ */
+typedef struct qhea_member_hparams {
+    double  scale_coeff;            /* the member's fixed encoding scale (trainable_freq == 0); ignored otherwise */
+    double  ham_offset, ham_coeff;  /* H = offset + coeff * sum P_i                                               */
+    double  lr;                     /* this call's Adam learning rate for the member                              */
+    int32_t ham_pauli;              /* QHEA_PAULI_*                                                               */
+    int32_t reserved;               /* 0                                                                          */
+} qhea_member_hparams;
+
+size_t qhea_model_sweep_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch);
+int qhea_model_sweep_train_steps(const qhea_model_desc* desc, int64_t n_models,
+                                 const qhea_member_hparams* members /*HOST [n_models]*/,
+                                 const double* ham_diag /*DEVICE [n_models][2^n] or NULL*/,
+                                 int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1], the same for every member*/,
+                                 const double* branch, const double* trunk, const double* y /*DEVICE, [n_models][rows]*/,
+                                 double* params /*DEVICE [n_models][P]*/, const double* inv_batch_total /*HOST [n_steps]*/,
+                                 double* grad /*DEVICE [n_models][n_steps][grad_stride]*/, int64_t grad_stride,
+                                 double* exp_avg /*DEVICE [n_models][P]*/, double* exp_avg_sq, int64_t first_step,
+                                 double beta1, double beta2, double eps, double weight_decay,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

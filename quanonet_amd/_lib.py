@@ -30,7 +30,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_adam_step', 'qhea_set_backward_variant', 'qhea_check_status',
            'qhea_dp_buffer_bytes', 'qhea_dp_alloc', 'qhea_dp_free', 'qhea_dp_export', 'qhea_dp_import', 'qhea_dp_close',
            'qhea_dp_allreduce_adam', 'qhea_dp_status', 'qhea_model_dp_train_steps', 'qhea_clock_probe',
-           'qhea_model_ensemble_workspace_bytes', 'qhea_model_ensemble_train_steps']
+           'qhea_model_ensemble_workspace_bytes', 'qhea_model_ensemble_train_steps',
+           'qhea_model_sweep_workspace_bytes', 'qhea_model_sweep_train_steps']
 
 
 class ModelDesc(ctypes.Structure):
@@ -41,8 +42,14 @@ class ModelDesc(ctypes.Structure):
                 ('scale_coeff', ctypes.c_double), ('ham_offset', ctypes.c_double), ('ham_coeff', ctypes.c_double)]
 
 
+class MemberHParams(ctypes.Structure):
+    """Mirror of `qhea_member_hparams` (include/quanonet_hea.h): one sweep member's read-out, fixed scale and learning rate."""
+    _fields_ = [('scale_coeff', ctypes.c_double), ('ham_offset', ctypes.c_double), ('ham_coeff', ctypes.c_double),
+                ('lr', ctypes.c_double), ('ham_pauli', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 450           # 0.4.5: + qhea_model_ensemble_train_steps (R models per launch, member = blockIdx.y)
+MIN_LIB_VERSION = 460           # 0.4.6: + qhea_model_sweep_train_steps (members differ in read-out, scale and lr)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -76,7 +83,7 @@ def load():
     lib.qhea_version.restype = ctypes.c_int
     if lib.qhea_version() < MIN_LIB_VERSION:
         raise QheaError(f"{LIB_PATH} is version {lib.qhea_version()}, this binding needs >= {MIN_LIB_VERSION} "
-                        f"(the model-ensemble entry points): rebuild it")
+                        f"(the model-sweep entry points): rebuild it")
     vp, dp = ctypes.c_void_p, ctypes.c_void_p
     i32p = ctypes.POINTER(ctypes.c_int32)
     lib.qhea_version.restype = ctypes.c_int
@@ -141,6 +148,13 @@ def load():
     lib.qhea_model_ensemble_train_steps.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, i64p, dp, dp, dp, dp, dp, f64p, dp,
                                                     ctypes.c_int64, dp, dp, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_size_t, vp]
+    lib.qhea_model_sweep_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_sweep_workspace_bytes.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64]
+    lib.qhea_model_sweep_train_steps.restype = ctypes.c_int
+    lib.qhea_model_sweep_train_steps.argtypes = [mdp, ctypes.c_int64, ctypes.POINTER(MemberHParams), dp, ctypes.c_int64, i64p,
+                                                 dp, dp, dp, dp, f64p, dp, ctypes.c_int64, dp, dp, ctypes.c_int64,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp,
+                                                 ctypes.c_size_t, vp]
     lib.qhea_clock_probe.restype = ctypes.c_int
     lib.qhea_clock_probe.argtypes = [ctypes.c_int, ctypes.c_int64, vp, vp]
     lib.qhea_model_param_count.restype = ctypes.c_int64
@@ -488,6 +502,64 @@ def model_ensemble_train_steps(desc, bounds, global_batches, branch, trunk, y, p
                                                  float(beta2), float(eps), float(weight_decay), _ptr(ws), ws.numel(),
                                                  _stream(branch.device))
     _check(rc, 'qhea_model_ensemble_train_steps')
+    return rows
+
+
+def member_hparams(scale_coeff, ham_offset, ham_coeff, lr, ham_pauli=0):
+    """One sweep member's MemberHParams (ham_pauli: 'Z' / 'X' / 'Y' or QHEA_PAULI_*)."""
+    return MemberHParams(float(scale_coeff), float(ham_offset), float(ham_coeff), float(lr), pauli_code(ham_pauli), 0)
+
+
+def model_sweep_workspace_bytes(desc, n_models, batch):
+    """qhea_model_sweep_workspace_bytes (current device's layout rules)."""
+    return int(load().qhea_model_sweep_workspace_bytes(ctypes.byref(desc), int(n_models), int(batch)))
+
+
+def model_sweep_train_steps(desc, members, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                            first_step, beta1, beta2, eps, weight_decay, ham_diag=None):
+    """
+    model_ensemble_train_steps for members that also differ in read-out, fixed scale and learning rate
+    (qhea_model_sweep_train_steps): `members` is a sequence of R MemberHParams (member_hparams), ham_diag None or [R, 2^n].
+    desc fixes the shape only.  Bitwise what model_train_steps gives for each member alone, with that member's descriptor,
+    learning rate and ham_diag row, under the backward variant the sweep chose.
+    """
+    lib = load()
+    n_steps = len(bounds) - 1
+    if n_steps <= 0:
+        return rows
+    if branch.dim() != 3:
+        raise QheaError("model_sweep_train_steps: branch must be [n_models, rows, branch_in]")
+    R, N = branch.shape[0], branch.shape[1]
+    if len(members) != R:
+        raise QheaError(f"model_sweep_train_steps: {len(members)} member records for {R} members")
+    _dev_f64(branch, 'branch', (R, N, desc.branch_in))
+    if desc.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (R, N, desc.trunk_in))
+    _dev_f64(y, 'y')
+    if tuple(y.shape) not in ((R, N), (R, N, 1)):
+        raise QheaError(f"y has shape {tuple(y.shape)}, expected ({R}, {N})")
+    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+        _dev_f64(t, nm)
+    P = params.shape[-1] if params.dim() == 2 else -1
+    if params.dim() != 2 or params.shape[0] != R or tuple(exp_avg.shape) != (R, P) or tuple(exp_avg_sq.shape) != (R, P):
+        raise QheaError("model_sweep_train_steps: params / exp_avg / exp_avg_sq must be [n_models, P]")
+    if rows.dim() != 3 or rows.shape[0] != R or rows.shape[1] != n_steps or rows.shape[2] < P + 2:
+        raise QheaError("model_sweep_train_steps: rows must be [n_models, n_steps, >= P+2]")
+    if bounds[0] < 0 or bounds[-1] != N or len(global_batches) != n_steps:
+        raise QheaError("model_sweep_train_steps: row bounds do not match the arrays")
+    _dev_f64(ham_diag, 'ham_diag', (R, 1 << desc.n_qubits))
+    with torch.cuda.device(branch.device):
+        nbytes = max(model_sweep_workspace_bytes(desc, R, bounds[i + 1] - bounds[i]) for i in range(n_steps))
+    ws = _workspace(branch.device, nbytes)
+    mh = (MemberHParams * R)(*members)
+    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
+    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_sweep_train_steps(ctypes.byref(desc), R, mh, _ptr(ham_diag), n_steps, rb, _ptr(branch), _ptr(trunk),
+                                              _ptr(y), _ptr(params), ib, _ptr(rows), int(rows.stride(1)), _ptr(exp_avg),
+                                              _ptr(exp_avg_sq), int(first_step), float(beta1), float(beta2), float(eps),
+                                              float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
+    _check(rc, 'qhea_model_sweep_train_steps')
     return rows
 
 

@@ -714,7 +714,7 @@ int launch_zyz_forward(int n, const Shape& sh, int64_t B, const Layout& L, char*
 int launch_zyz_backward(int n, const Shape& sh, int64_t B, const Layout& L, char* ws, const AngleSrc& src, double off,
                         double co, const double* diag, int pauli, const double* g, const double* state_in, const double* y,
                         const double* bias, double inv_bt, double* out, double* grad_x, double* partial, hipStream_t st,
-                        int R = 1, const MemberStride& ms = MemberStride{}) {
+                        int R = 1, const MemberStride& ms = MemberStride{}, const char* mrec = nullptr) {
     const int fast = zyz_fast_ld(sh.runs, n);
     int nblocks = 0;
     for (int i = 0; i < sh.runs.nruns; ++i) nblocks += sh.runs.count[i];
@@ -728,7 +728,7 @@ int launch_zyz_backward(int n, const Shape& sh, int64_t B, const Layout& L, char
     const size_t dyn = (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * sizeof(double2);
     if (L.zpacked) {
         switch (n) {
-#define QHEA_CASE(NN) case NN: launch_bwd_zpacked_##NN(dim3((unsigned)L.nwaves, gy), zp_cs_bytes(n, sh.E, kZPWaves * (64 >> n)), st, za); break;
+#define QHEA_CASE(NN) case NN: launch_bwd_zpacked_##NN(dim3((unsigned)L.nwaves, gy), zp_cs_bytes(n, sh.E, kZPWaves * (64 >> n)), st, za, mrec); break;
             QHEA_FOR_EACH_ZN(QHEA_CASE)
 #undef QHEA_CASE
             default: return QHEA_EUNSUPPORTED;
@@ -741,13 +741,13 @@ int launch_zyz_backward(int n, const Shape& sh, int64_t B, const Layout& L, char
         return QHEA_OK;
     }
     if (L.zquad && n == 5 && pauli == QHEA_PAULI_Z && za.srec) {
-        launch_bwd_zquad_5(dim3((unsigned)L.nwaves, gy), zquad_fixed_lds(kPairRing) + 2 * dyn, st, za);
+        launch_bwd_zquad_5(dim3((unsigned)L.nwaves, gy), zquad_fixed_lds(kPairRing) + 2 * dyn, st, za, mrec);
         return QHEA_OK;
     }
     const size_t dyn_tri = (size_t)L.zpipes * (ztri_fixed_lds(L.zpipes == 2 ? kZRingDepth<2> : kZRingDepth<1>) + (za.srec ? 2 * dyn : dyn)) +
                            (L.zpipes == 2 ? (size_t)sh.blk * padded_3n(n) * sizeof(double) : 0);
     switch (n) {
-#define QHEA_CASE(NN) case NN: launch_bwd_ztri_##NN(dim3((unsigned)L.nwaves, gy), dyn_tri, st, za); break;
+#define QHEA_CASE(NN) case NN: launch_bwd_ztri_##NN(dim3((unsigned)L.nwaves, gy), dyn_tri, st, za, mrec); break;
         QHEA_FOR_EACH_ZN(QHEA_CASE)
 #undef QHEA_CASE
         default: return QHEA_EUNSUPPORTED;
@@ -836,15 +836,27 @@ constexpr int kFuseMaxLd = 2;
 // the peers' exchange buffers, waits for the peers' (flags per block), adds them in rank order and only then writes the
 // gradient row, updates and -- FUSE -- writes the next records: the sum over the ranks costs no launch of its own
 // (hea_dp.hpp; bitwise the results of qhea_model_loss_grad + qhea_dp_allreduce_adam).
-template <bool FUSE, bool DP>        // (the fused one's LDS and registers do not weigh on the plain one)
+// Member learning rates (MT, ensemble launches of R > 1 members): member blockIdx.y's Adam step size is its MemberRec::lr
+// divided by the step's bias correction 1 - beta1^t, here, in IEEE double division -- the same rounding as the host's lr / bc1
+// of a single-model call.  The member's other Adam arguments are the launch's.
+struct MemberLr {
+    const char* mrec;           // member 0's MemberRec (hea_zyz.hpp), member m's ms.ws bytes further per member
+    double bc1;
+};
+template <bool FUSE, bool DP, bool MT = false>        // (the fused one's LDS and registers do not weigh on the plain one)
 __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         int n, int blk, int kw, long nwaves, const double* __restrict__ partial, const double* w,
         long B, int E, EncDesc enc, const double* __restrict__ grad_x, const double* __restrict__ pred,
         const double* __restrict__ y, double inv_bt, GradMap gm, int nb_w, int nb_x, double* __restrict__ grad,
-        AdamArgs adam, const WorkspaceHeader* __restrict__ hdr, const double* gmap, FusePrep fp, DpX dpx, MemberStride ms) {
+        AdamArgs adam, const WorkspaceHeader* __restrict__ hdr, const double* gmap, FusePrep fp, DpX dpx, MemberStride ms,
+        MemberLr mlr) {
 #pragma clang fp contract(off)
     {   // ensemble launches: member blockIdx.y's data, parameters, gradient rows and workspace slice (hdr: slice 0's)
         const long m = blockIdx.y, wsb = m * ms.ws, pb = m * ms.params * (long)sizeof(double);
+        if constexpr (MT) {
+            const MemberRec* mr = member_ptr(reinterpret_cast<const MemberRec*>(mlr.mrec), wsb);
+            adam.lr_over_bc1 = ((ConstMemberRec)mr)->lr / mlr.bc1;
+        }
         partial = member_ptr(partial, wsb); grad_x = member_ptr(grad_x, wsb); pred = member_ptr(pred, wsb);
         gmap = member_ptr(gmap, wsb);
         fp.rec = member_ptr(fp.rec, wsb); fp.srec = member_ptr(fp.srec, wsb); fp.gmap = member_ptr(fp.gmap, wsb);
@@ -1182,13 +1194,36 @@ bool ensemble_grid(const ModelInfo& mi, int64_t R, int64_t batch) {
     return L.ztri || L.zpacked;
 }
 
+// The members' hyper-parameters reach the device as kernel arguments: one launch per kMemberFill members and host call writes
+// each member's MemberRec (hea_zyz.hpp) into its workspace slice -- no pageable copy, nothing retained, capturable.
+constexpr int kMemberFill = 64;                 // 64 x 40 bytes of kernel arguments
+struct MemberFill { qhea_member_hparams h[kMemberFill]; };
+__global__ __launch_bounds__(kMemberFill) void member_fill_kernel(MemberFill f, int count, char* slice0, long slice_bytes,
+                                                                  const double* diag0, long diag_stride) {
+    const int i = threadIdx.x;
+    if (i >= count) return;
+    const qhea_member_hparams& h = f.h[i];
+    MemberRec r;
+    r.scale = h.scale_coeff; r.off = h.ham_offset; r.co = h.ham_coeff; r.lr = h.lr;
+    r.diag = diag0 ? diag0 + (long)i * diag_stride : nullptr;
+    r.pauli = h.ham_pauli; r.pad = 0;
+    *reinterpret_cast<MemberRec*>(slice0 + (long)i * slice_bytes + kMemberRecOffset) = r;
+}
+
+// The descriptor member m trains as: the shape of `desc`, m's read-out and fixed scale
+inline qhea_model_desc member_desc(const qhea_model_desc& d, const qhea_member_hparams& h) {
+    qhea_model_desc m = d;
+    m.scale_coeff = h.scale_coeff; m.ham_offset = h.ham_offset; m.ham_coeff = h.ham_coeff; m.ham_pauli = h.ham_pauli;
+    return m;
+}
+
 }  // namespace qhea
 
 using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 450; }
+int qhea_version(void) { return 460; }
 
 const char* qhea_strerror(int code) {
     switch (code) {
@@ -1438,16 +1473,18 @@ static int launch_reduce_model(int nblocks, hipStream_t st, const ModelInfo& mi,
                                const double* params, int64_t batch, const EncDesc& enc, const double* gx, const double* pr,
                                const double* y, double inv_bt, const GradMap& gm, int nb_w, int nb_x, double* grad,
                                const AdamArgs& adam, const char* ws, const double* gmap, const FusePrep& fp, const DpX* dpx,
-                               int R = 1, const MemberStride& ms = MemberStride{}) {
+                               int R = 1, const MemberStride& ms = MemberStride{}, const MemberLr* mlr = nullptr) {
     const DpX none{};
     const DpX& dx = dpx ? *dpx : none;
     const dim3 g((unsigned)nblocks, (unsigned)R), b(kRedThreads);
     const WorkspaceHeader* hdr = reinterpret_cast<const WorkspaceHeader*>(ws);
-#define QHEA_LAUNCH_REDUCE(F, D)                                                                                          \
-    hipLaunchKernelGGL((reduce_model_kernel<F, D>), g, b, 0, st, mi.n, (int)mi.sh.blk, kw, nwaves, partial, params + mi.off_ans, \
-                       (long)batch, (int)mi.sh.E, enc, gx, pr, y, inv_bt, gm, nb_w, nb_x, grad, adam, hdr, gmap, fp, dx, ms)
-    if (fp.ld != 0) { if (dpx) QHEA_LAUNCH_REDUCE(true, true); else QHEA_LAUNCH_REDUCE(true, false); }
-    else            { if (dpx) QHEA_LAUNCH_REDUCE(false, true); else QHEA_LAUNCH_REDUCE(false, false); }
+    const MemberLr ml = mlr ? *mlr : MemberLr{};
+#define QHEA_LAUNCH_REDUCE(F, D, M)                                                                                       \
+    hipLaunchKernelGGL((reduce_model_kernel<F, D, M>), g, b, 0, st, mi.n, (int)mi.sh.blk, kw, nwaves, partial, params + mi.off_ans, \
+                       (long)batch, (int)mi.sh.E, enc, gx, pr, y, inv_bt, gm, nb_w, nb_x, grad, adam, hdr, gmap, fp, dx, ms, ml)
+    if (mlr) { if (fp.ld != 0) QHEA_LAUNCH_REDUCE(true, false, true); else QHEA_LAUNCH_REDUCE(false, false, true); }
+    else if (fp.ld != 0) { if (dpx) QHEA_LAUNCH_REDUCE(true, true, false); else QHEA_LAUNCH_REDUCE(true, false, false); }
+    else                 { if (dpx) QHEA_LAUNCH_REDUCE(false, true, false); else QHEA_LAUNCH_REDUCE(false, false, false); }
 #undef QHEA_LAUNCH_REDUCE
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
@@ -1462,12 +1499,13 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
                                 const double* y, const double* params, const double* ham_diag, double inv_batch_total,
                                 double* grad, double* pred, void* workspace, size_t workspace_bytes, void* stream,
                                 const AdamArgs& adam, bool records_ready = false, bool records_for_next = false,
-                                const DpX* dpx = nullptr, int R = 1, const MemberStride& ms = MemberStride{}) {
+                                const DpX* dpx = nullptr, int R = 1, const MemberStride& ms = MemberStride{},
+                                const MemberLr* mlr = nullptr) {
     // records_ready / records_for_next (qhea_model_train_steps only): the previous step's reduce kernel has written this
     // step's layer records / this step's reduce kernel writes the next step's (FusePrep).  dpx (qhea_model_dp_train_steps):
     // the reduce kernel's blocks exchange their gradients with the peer ranks before they update.  R, ms
     // (qhea_model_ensemble_train_steps only): R members in every launch, member 0's pointers given, workspace_bytes = one slice;
-    // the kernels are chosen for R x batch rows.
+    // the kernels are chosen for R x batch rows.  mlr (R > 1): the members' MemberRecs (read-out, scale, lr) are in their slices.
     ModelInfo mi;
     int rc = model_info(desc, mi);
     if (rc != QHEA_OK) return rc;
@@ -1478,6 +1516,7 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
         return hipMemsetAsync(grad, 0, sizeof(double) * (mi.P + 2), st) == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
     }
     if (!branch || !params || !y || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
+    if (R > 1 && !mlr) return QHEA_EINVAL;                      // (the member kernels read every member's MemberRec)
     const ModelLayout M = make_model_layout(mi, batch, R * batch);
     if (!workspace || workspace_bytes < M.total) return QHEA_EWORKSPACE;
     char* ws = static_cast<char*>(workspace);
@@ -1510,13 +1549,13 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
         profile_begin(st);
         rc = launch_zyz_backward(mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
                                  desc->ham_pauli, nullptr, nullptr, y, mi.has_bias ? params + mi.off_bias : nullptr,
-                                 inv_batch_total, pr, gx, partial, st, R, ms);
+                                 inv_batch_total, pr, gx, partial, st, R, ms, mlr ? mlr->mrec : nullptr);
         profile_end(st);
         if (rc != QHEA_OK) return rc;
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
         return launch_reduce_model(nb_w + nb_x + 1, st, mi, kw, M.L.nwaves, partial, params, batch, enc, gx, pr, y,
                                    inv_batch_total, gm, nb_w, nb_x, grad, adam, ws,
-                                   reinterpret_cast<const double*>(ws + M.L.off_gmap), fp, dpx, R, ms);
+                                   reinterpret_cast<const double*>(ws + M.L.off_gmap), fp, dpx, R, ms, mlr);
     }
     if (R != 1) return QHEA_EUNSUPPORTED;                       // (the ensemble entry point never asks: R-sequential calls there)
     if (records_ready || records_for_next) return QHEA_EINVAL;
@@ -1694,6 +1733,89 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
     return QHEA_OK;
 }
 
+// qhea_model_ensemble_train_steps and qhea_model_sweep_train_steps: R members of one shape, member m with hyper-parameters hp(m)
+// (hp_fn(ctx, m)) and diagonal Hamiltonian diag0 + m * diag_stride (diag0 == nullptr: none).  The arguments have been checked by the caller.
+typedef qhea_member_hparams (*MemberHp)(const void* ctx, int64_t m);
+static int members_train_steps(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models, MemberHp hp_fn, const void* ctx,
+                        const double* diag0,
+                        int64_t diag_stride, int64_t n_steps, const int64_t* row_begin, const double* branch, const double* trunk,
+                        const double* y, double* params, const double* inv_batch_total, double* grad, int64_t grad_stride,
+                        double* exp_avg, double* exp_avg_sq, int64_t first_step, double beta1, double beta2, double eps,
+                        double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
+    auto hp = [&](int64_t m) { return hp_fn(ctx, m); };
+    // one slice per member, sized for every batch size of the schedule; one launch per kernel where every step runs the ZYZ
+    // kernels, R consecutive single-model calls otherwise
+    size_t slice = 0;
+    bool grid = true;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int64_t nb = row_begin[i + 1] - row_begin[i];
+        const size_t b = ensemble_slice_bytes(mi, n_models, nb);
+        if (b > slice) slice = b;
+        grid = grid && n_models <= 65535 && ensemble_grid(mi, n_models, nb);      // (gridDim.y)
+    }
+    if (!workspace || workspace_bytes / (size_t)n_models < slice) return QHEA_EWORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    const int64_t rows = row_begin[n_steps];                        // rows per member
+    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
+    if (!grid) {
+        for (int64_t m = 0; m < n_models; ++m) {
+            char* wm = ws + m * slice;
+            const qhea_member_hparams h = hp(m);
+            const qhea_model_desc dm = member_desc(*desc, h);
+            const int rc = qhea_model_train_steps(&dm, n_steps, row_begin, branch + m * rows * desc->branch_in,
+                                                  has_trunk ? trunk + m * rows * desc->trunk_in : nullptr, y + m * rows,
+                                                  params + m * mi.P, diag0 ? diag0 + m * diag_stride : nullptr, inv_batch_total,
+                                                  grad + m * n_steps * grad_stride, grad_stride, exp_avg + m * mi.P,
+                                                  exp_avg_sq + m * mi.P, first_step, h.lr, beta1, beta2, eps, weight_decay, wm,
+                                                  slice, stream);
+            if (rc != QHEA_OK) return rc;
+            if (m > 0) {
+                hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
+                                   reinterpret_cast<WorkspaceHeader*>(wm));
+                if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+            }
+        }
+        return QHEA_OK;
+    }
+    // One grid: R = 1 runs the single-model kernels on member 0's descriptor; R > 1 the member kernels, which read every
+    // member's read-out, scale and learning rate from its MemberRec.  The launch descriptor only chooses the kernels: a member
+    // that reads out X or Y gives the whole launch the kernels of an X / Y model (the split-layout chains are Z-only).
+    const qhea_member_hparams h0 = hp(0);
+    qhea_model_desc dl = member_desc(*desc, h0);
+    if (n_models > 1) {
+        for (int64_t m = 0; m < n_models; ++m)
+            if (hp(m).ham_pauli != QHEA_PAULI_Z) dl.ham_pauli = QHEA_PAULI_X;
+        for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
+            const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
+            MemberFill f{};
+            for (int i = 0; i < cnt; ++i) f.h[i] = hp(m0 + i);
+            hipLaunchKernelGGL(member_fill_kernel, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
+                               diag0 ? diag0 + m0 * diag_stride : nullptr, (long)diag_stride);
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        }
+    }
+    const MemberStride ms{(long)rows, (long)mi.P, (long)(n_steps * grad_stride), (long)slice};
+    bool ready = false;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
+        bool next = false;
+        if (i + 1 < n_steps && row_begin[i + 2] - row_begin[i + 1] == nb)
+            next = model_fuse_eligible(mi, make_model_layout(mi, nb, n_models * nb).L);
+        const int64_t step = first_step + i;
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const AdamArgs adam{params, exp_avg, exp_avg_sq, h0.lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+        const MemberLr mlr{ws + kMemberRecOffset, bc1};
+        const int rc = model_loss_grad_impl(&dl, nb, branch + r0 * desc->branch_in,
+                                            has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, diag0,
+                                            inv_batch_total[i], grad + i * grad_stride, nullptr, ws, slice, stream, adam,
+                                            ready, next, nullptr, (int)n_models, ms, n_models > 1 ? &mlr : nullptr);
+        if (rc != QHEA_OK) return rc;
+        ready = next;
+    }
+    return QHEA_OK;
+}
+
 size_t qhea_model_ensemble_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch) {
     ModelInfo mi;
     if (model_info(desc, mi) != QHEA_OK || n_models < 1 || batch < 0) return 0;
@@ -1715,58 +1837,49 @@ int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_model
     if (!pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
     for (int64_t i = 0; i < n_steps; ++i)
         if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
-    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
-    if (has_trunk && !trunk) return QHEA_EINVAL;
+    if (desc->model == QHEA_MODEL_QUANONET && !trunk) return QHEA_EINVAL;
     if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    // one slice per member, sized for every batch size of the schedule; one launch per kernel where every step runs the ZYZ
-    // kernels, R consecutive single-model calls otherwise
-    size_t slice = 0;
-    bool grid = true;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t nb = row_begin[i + 1] - row_begin[i];
-        const size_t b = ensemble_slice_bytes(mi, n_models, nb);
-        if (b > slice) slice = b;
-        grid = grid && n_models <= 65535 && ensemble_grid(mi, n_models, nb);      // (gridDim.y)
+    // a sweep whose members all share the descriptor's read-out and scale and `lr` (one shared ham_diag)
+    const qhea_member_hparams uni{desc->scale_coeff, desc->ham_offset, desc->ham_coeff, lr, desc->ham_pauli, 0};
+    return members_train_steps(desc, mi, n_models, [](const void* c, int64_t) { return *static_cast<const qhea_member_hparams*>(c); },
+                               &uni, ham_diag, 0, n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride,
+                               exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream);
+}
+
+size_t qhea_model_sweep_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch) {
+    return qhea_model_ensemble_workspace_bytes(desc, n_models, batch);      // (the MemberRecs live in the slices' headers)
+}
+
+int qhea_model_sweep_train_steps(const qhea_model_desc* desc, int64_t n_models, const qhea_member_hparams* members,
+                                 const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
+                                 const double* trunk, const double* y, double* params, const double* inv_batch_total,
+                                 double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq, int64_t first_step,
+                                 double beta1, double beta2, double eps, double weight_decay, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (!desc || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
+        first_step < 1)
+        return QHEA_EINVAL;
+    for (int64_t m = 0; m < n_models; ++m) {
+        const qhea_member_hparams& h = members[m];
+        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
+        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;               // ham_diag: every member reads out Z
+        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;        // (torch.optim.Adam refuses lr < 0 too)
     }
-    if (!workspace || workspace_bytes / (size_t)n_models < slice) return QHEA_EWORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    const int64_t rows = row_begin[n_steps];                        // rows per member
-    if (!grid) {
-        for (int64_t m = 0; m < n_models; ++m) {
-            char* wm = ws + m * slice;
-            const int rc = qhea_model_train_steps(desc, n_steps, row_begin, branch + m * rows * desc->branch_in,
-                                                  has_trunk ? trunk + m * rows * desc->trunk_in : nullptr, y + m * rows,
-                                                  params + m * mi.P, ham_diag, inv_batch_total, grad + m * n_steps * grad_stride,
-                                                  grad_stride, exp_avg + m * mi.P, exp_avg_sq + m * mi.P, first_step, lr, beta1,
-                                                  beta2, eps, weight_decay, wm, slice, stream);
-            if (rc != QHEA_OK) return rc;
-            if (m > 0) {
-                hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
-                                   reinterpret_cast<WorkspaceHeader*>(wm));
-                if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-            }
-        }
-        return QHEA_OK;
-    }
-    const MemberStride ms{(long)rows, (long)mi.P, (long)(n_steps * grad_stride), (long)slice};
-    bool ready = false;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
-        bool next = false;
-        if (i + 1 < n_steps && row_begin[i + 2] - row_begin[i + 1] == nb)
-            next = model_fuse_eligible(mi, make_model_layout(mi, nb, n_models * nb).L);
-        const int64_t step = first_step + i;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-        const int rc = model_loss_grad_impl(desc, nb, branch + r0 * desc->branch_in,
-                                            has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, ham_diag,
-                                            inv_batch_total[i], grad + i * grad_stride, nullptr, ws, slice, stream, adam,
-                                            ready, next, nullptr, (int)n_models, ms);
-        if (rc != QHEA_OK) return rc;
-        ready = next;
-    }
-    return QHEA_OK;
+    // the shape (and everything model_info checks) is the descriptor's; its scale and Hamiltonian fields are not used
+    const qhea_model_desc d0 = member_desc(*desc, members[0]);
+    ModelInfo mi;
+    const int rc0 = model_info(&d0, mi);
+    if (rc0 != QHEA_OK) return rc0;
+    if (grad_stride < mi.P + 2) return QHEA_EINVAL;
+    for (int64_t i = 0; i < n_steps; ++i)
+        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
+    if (desc->model == QHEA_MODEL_QUANONET && !trunk) return QHEA_EINVAL;
+    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    return members_train_steps(&d0, mi, n_models,
+                               [](const void* c, int64_t m) { return static_cast<const qhea_member_hparams*>(c)[m]; }, members,
+                               ham_diag, (int64_t)1 << mi.n, n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad,
+                               grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, workspace,
+                               workspace_bytes, stream);
 }
 
 int qhea_adam_step(int64_t n, double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t step,

@@ -48,10 +48,10 @@ void QHEA_CAT(launch_bwd_pair_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArgs
 void QHEA_CAT(launch_fwd_zyz_, QHEA_N)(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArgs& a) {
     hipLaunchKernelGGL(fwd_zyz_kernel<QHEA_N>, grid, dim3((kZFwdWaves + kFwdHelpers) * 64), dyn_lds, st, a);
 }
-// (grid.y > 1: an ensemble launch, member = blockIdx.y -- the kernels' member instantiation)
-void QHEA_CAT(launch_bwd_ztri_, QHEA_N)(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a) {
+// (grid.y > 1: an ensemble launch, member = blockIdx.y -- the kernels' member instantiation; mrec: member 0's MemberRec)
+void QHEA_CAT(launch_bwd_ztri_, QHEA_N)(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a, const char* mrec) {
     if (grid.y > 1) {
-        const ZBwdArgsM am{a};
+        const ZBwdArgsM am{a, mrec};
         if (a.pipes == 2) hipLaunchKernelGGL((bwd_ztri_kernel<QHEA_N, 2, ZBwdArgsM>), grid, dim3(2 * 64 * kZPipeWaves), dyn_lds, st, am);
         else hipLaunchKernelGGL((bwd_ztri_kernel<QHEA_N, 1, ZBwdArgsM>), grid, dim3(64 * kZPipeWaves), dyn_lds, st, am);
         return;
@@ -62,16 +62,16 @@ void QHEA_CAT(launch_bwd_ztri_, QHEA_N)(dim3 grid, size_t dyn_lds, hipStream_t s
 void QHEA_CAT(launch_fwd_zshared_, QHEA_N)(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArgs& a) {
     hipLaunchKernelGGL(fwd_zshared_kernel<QHEA_N>, grid, dim3(kZPWaves * 64), dyn_lds, st, a);
 }
-void QHEA_CAT(launch_bwd_zpacked_, QHEA_N)(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a) {
-    if (grid.y > 1) hipLaunchKernelGGL((bwd_zpacked_kernel<QHEA_N, ZBwdArgsM>), grid, dim3(kZPWaves * 64), dyn_lds, st, ZBwdArgsM{a});
+void QHEA_CAT(launch_bwd_zpacked_, QHEA_N)(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a, const char* mrec) {
+    if (grid.y > 1) hipLaunchKernelGGL((bwd_zpacked_kernel<QHEA_N, ZBwdArgsM>), grid, dim3(kZPWaves * 64), dyn_lds, st, ZBwdArgsM{a, mrec});
     else hipLaunchKernelGGL(bwd_zpacked_kernel<QHEA_N>, grid, dim3(kZPWaves * 64), dyn_lds, st, a);
 }
 #if QHEA_N == 5
 void launch_fwd_split_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArgs& a) {
     hipLaunchKernelGGL(fwd_split_kernel<5>, grid, dim3((kSplitWaves + kSplitHelpers) * 64), dyn_lds, st, a);
 }
-void launch_bwd_zquad_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a) {
-    if (grid.y > 1) hipLaunchKernelGGL((bwd_zquad_kernel<kPairRing, kZSigma, ZBwdArgsM>), grid, dim3(64 * (4 + kZSigma)), dyn_lds, st, ZBwdArgsM{a});
+void launch_bwd_zquad_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a, const char* mrec) {
+    if (grid.y > 1) hipLaunchKernelGGL((bwd_zquad_kernel<kPairRing, kZSigma, ZBwdArgsM>), grid, dim3(64 * (4 + kZSigma)), dyn_lds, st, ZBwdArgsM{a, mrec});
     else hipLaunchKernelGGL((bwd_zquad_kernel<kPairRing, kZSigma>), grid, dim3(64 * (4 + kZSigma)), dyn_lds, st, a);
 }
 void launch_bwd_zsnap_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a) {     // single-model launches only
@@ -80,12 +80,12 @@ void launch_bwd_zsnap_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArg
 #endif
 #elif QHEA_N <= 5      // layout-experiment build: the ZYZ kernels need the all-lane layout and are never selected
 void QHEA_CAT(launch_fwd_zyz_, QHEA_N)(dim3, size_t, hipStream_t, const ZFwdArgs&) {}
-void QHEA_CAT(launch_bwd_ztri_, QHEA_N)(dim3, size_t, hipStream_t, const ZBwdArgs&) {}
-void QHEA_CAT(launch_bwd_zpacked_, QHEA_N)(dim3, size_t, hipStream_t, const ZBwdArgs&) {}
+void QHEA_CAT(launch_bwd_ztri_, QHEA_N)(dim3, size_t, hipStream_t, const ZBwdArgs&, const char*) {}
+void QHEA_CAT(launch_bwd_zpacked_, QHEA_N)(dim3, size_t, hipStream_t, const ZBwdArgs&, const char*) {}
 void QHEA_CAT(launch_fwd_zshared_, QHEA_N)(dim3, size_t, hipStream_t, const ZFwdArgs&) {}
 #if QHEA_N == 5
 void launch_fwd_split_5(dim3, size_t, hipStream_t, const ZFwdArgs&) {}
-void launch_bwd_zquad_5(dim3, size_t, hipStream_t, const ZBwdArgs&) {}
+void launch_bwd_zquad_5(dim3, size_t, hipStream_t, const ZBwdArgs&, const char*) {}
 void launch_bwd_zsnap_5(dim3, size_t, hipStream_t, const ZBwdArgs&) {}
 #endif
 #endif

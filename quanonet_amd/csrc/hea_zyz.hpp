@@ -61,7 +61,14 @@ struct AngleSrc {
     EncDesc enc;
     long m_rows = 0, m_params = 0;      // ensemble launches (hea_zyz.hpp: MemberStride): member blockIdx.y's rows / parameters
 };
-__device__ __forceinline__ double enc_angle(const AngleSrc& a, int E, long b, int e) {
+// Sweep launches (qhea_model_sweep_train_steps): the member instantiation of the backward kernels passes member blockIdx.y's
+// fixed encoding scale (MemberRec::scale, hea_zyz.hpp) through AngleSrcM instead of the segment's shared one
+struct AngleSrcM {
+    const AngleSrc& s;
+    double scale;
+};
+template <bool MSCALE>
+__device__ __forceinline__ double enc_angle_impl(const AngleSrc& a, int E, long b, int e, double mscale) {
     if (a.x) return a.x[b * E + e];
     const int si = e < a.enc.seg[0].ncols ? 0 : 1;
     const EncSeg& sg = a.enc.seg[si];
@@ -69,11 +76,14 @@ __device__ __forceinline__ double enc_angle(const AngleSrc& a, int E, long b, in
     const long m = blockIdx.y;
     const double v = sg.in[(b + m * a.m_rows) * sg.width + ee % sg.width];
     const long ep = ee + m * a.m_params;
-    return sg.w ? v * sg.w[ep] + sg.b[ep] : v * sg.scale;
+    return sg.w ? v * sg.w[ep] + sg.b[ep] : v * (MSCALE ? mscale : sg.scale);
 }
+__device__ __forceinline__ double enc_angle(const AngleSrc& a, int E, long b, int e) { return enc_angle_impl<false>(a, E, b, e, 0.0); }
+__device__ __forceinline__ double enc_angle(const AngleSrcM& a, int E, long b, int e) { return enc_angle_impl<true>(a.s, E, b, e, a.scale); }
 // rows [s0, s0 + ns) x E of the group's table, spread over `nthreads` threads (tid of them); samples past the batch
 // repeat the last one (their lanes carry lambda = 0)
-__device__ __forceinline__ void fill_cs(double2* cs, const AngleSrc& src, int n, int E, long b0, long B, int ns, int tid, int nthreads,
+template <class S>
+__device__ __forceinline__ void fill_cs(double2* cs, const S& src, int n, int E, long b0, long B, int ns, int tid, int nthreads,
                                         int row_stride = 0 /* 0: zyz_cs_row(n, E) */) {
     const int row = row_stride ? row_stride : (int)zyz_cs_row(n, E);
     // (sample, column) pairs spread over the threads: short rows (cfg 1: E = 20) would leave most threads idle in a loop over
@@ -526,7 +536,8 @@ constexpr int kSRecRy = 768;
 __host__ __device__ inline bool zsplit_eligible(int n, long E, const Runs& r) {
     return n == 5 && zyz_fast_ld(r, n) != 0 && 2 * zyz_cs_row(n, E) * 32 <= kZCsBytes;
 }
-__device__ __forceinline__ void fill_cs_split(double4* cs, const AngleSrc& src, int E, long b0, long B, int ns, int tid, int nthreads) {
+template <class S>
+__device__ __forceinline__ void fill_cs_split(double4* cs, const S& src, int E, long b0, long B, int ns, int tid, int nthreads) {
     const int row = (int)zyz_cs_row(5, E);
     for (int i = tid; i < ns * E; i += nthreads) {              // (sample, column) pairs spread over the threads (fill_cs)
         const int s = i / E, e = i - s * E;
@@ -713,7 +724,22 @@ struct ZBwdArgs {
 // uniform for the buffer resources
 // Ensemble launch: the same arguments under their own type, which selects the kernels' member instantiation (member =
 // blockIdx.y); the single-model instantiation takes ZBwdArgs and keeps its code, registers and occupancy as they were.
-struct ZBwdArgsM : ZBwdArgs {};
+// mrec: member 0's MemberRec, member m's lies ms.ws bytes further per member (one in every workspace slice).
+struct ZBwdArgsM : ZBwdArgs {
+    const char* mrec;
+};
+// One member's hyper-parameters in its workspace slice (qhea_model_sweep_train_steps / qhea_model_ensemble_train_steps: written
+// by member_fill_kernel, hea_api.hip, at the start of every call that launches R > 1 members in one grid), in the spare bytes of
+// the slice's 256-byte header: read-out, fixed encoding scale and Adam learning rate differ per member, the shape does not.
+struct MemberRec {
+    double scale;               // fixed encoding scale (trainable_freq == 0)
+    double off, co;             // H = off + co * sum P_i
+    double lr;                  // Adam learning rate (the reduce kernel divides by the step's bias correction)
+    const double* diag;         // the member's diagonal Hamiltonian, or nullptr
+    int pauli;                  // QHEA_PAULI_*
+    int pad;
+};
+constexpr int kMemberRecOffset = 64;            // bytes into the slice (its WorkspaceHeader uses the first 16)
 template <class T>
 __device__ __forceinline__ T* uniform_ptr(T* p) {           // (read off lane 0: the compiler then knows it is uniform)
     const unsigned long long v = reinterpret_cast<unsigned long long>(p);
@@ -736,6 +762,22 @@ __device__ __forceinline__ double* zm_gx(const ZBwdArgsM& a) { return member_ptr
 __device__ __forceinline__ double* zm_part(const ZBwdArgsM& a) { return member_ptr(a.partial, zm_ws(a)); }
 __device__ __forceinline__ const double* zm_y(const ZBwdArgsM& a) { return member_ptr(a.y, (long)blockIdx.y * a.ms.rows * (long)sizeof(double)); }
 __device__ __forceinline__ const double* zm_bias(const ZBwdArgsM& a) { return member_ptr(a.bias, (long)blockIdx.y * a.ms.params * (long)sizeof(double)); }
+// read-out and encoding scale: the launch's for a single model, member blockIdx.y's record for an ensemble launch (wave-uniform
+// loads through the constant address space: scalar loads, the record is written by an earlier launch)
+typedef const __attribute__((address_space(4))) MemberRec* ConstMemberRec;
+__device__ __forceinline__ ConstMemberRec zm_mr(const ZBwdArgsM& a) {
+    return (ConstMemberRec)uniform_ptr(member_ptr(reinterpret_cast<const MemberRec*>(a.mrec), zm_ws(a)));
+}
+__device__ __forceinline__ double zm_off(const ZBwdArgs& a) { return a.off; }
+__device__ __forceinline__ double zm_co(const ZBwdArgs& a) { return a.co; }
+__device__ __forceinline__ const double* zm_diag(const ZBwdArgs& a) { return a.diag; }
+__device__ __forceinline__ int zm_pauli(const ZBwdArgs& a) { return a.pauli; }
+__device__ __forceinline__ const AngleSrc& zm_src(const ZBwdArgs& a) { return a.src; }
+__device__ __forceinline__ double zm_off(const ZBwdArgsM& a) { return zm_mr(a)->off; }
+__device__ __forceinline__ double zm_co(const ZBwdArgsM& a) { return zm_mr(a)->co; }
+__device__ __forceinline__ const double* zm_diag(const ZBwdArgsM& a) { return zm_mr(a)->diag; }
+__device__ __forceinline__ int zm_pauli(const ZBwdArgsM& a) { return zm_mr(a)->pauli; }
+__device__ __forceinline__ AngleSrcM zm_src(const ZBwdArgsM& a) { return AngleSrcM{a.src, zm_mr(a)->scale}; }
 
 // kZFwdWaves sweeping waves + kFwdHelpers waves that only help to fill the (cos, sin) tables and then leave: the fill is
 // 2 x 600 fp64 sincos per sweeping wave at cfg 2, ~4 us if each does its own, and the sweep cannot start before it.  Four
@@ -923,8 +965,8 @@ __device__ __forceinline__ void ztri_chain(const A& a, int role, int lane, int k
         int seen_ready = 0;
         pair_wait_ge(&sync->ready, 2, &sync->abort, seen_ready);
         double fr[1] = {psi_final[lane].x}, fi[1] = {psi_final[lane].y};
-        basis_change<N, false>(fr, fi, a.pauli, lane);
-        const double h = ham_weight<N>(klow, a.off, a.co, a.diag);
+        basis_change<N, false>(fr, fi, zm_pauli(a), lane);
+        const double h = ham_weight<N>(klow, zm_off(a), zm_co(a), zm_diag(a));
         double gb;
         {
             double v[1] = {h * (fr[0] * fr[0] + fi[0] * fi[0])};
@@ -935,7 +977,7 @@ __device__ __forceinline__ void ztri_chain(const A& a, int role, int lane, int k
         }
         if (!valid) gb = 0.0;
         sr[0] = gb * h * fr[0]; si[0] = gb * h * fi[0];
-        basis_change<N, true>(sr, si, a.pauli, lane);
+        basis_change<N, true>(sr, si, zm_pauli(a), lane);
     }
     double2 (*ring)[64] = role == 0 ? psi_ring : lam_ring;
     int* prod = role == 0 ? &sync->psi_prod : &sync->lam_prod;
@@ -1173,9 +1215,9 @@ __global__ __launch_bounds__(64 * kZPipeWaves * PIPES) __attribute__((amdgpu_wav
         for (int i = (int)threadIdx.x; i < a.blk * C::KW; i += 64 * kZPipeWaves * PIPES) row_lds[i] = 0.0;
     }
     if constexpr (N == 5) {
-        if (split) fill_cs_split(reinterpret_cast<double4*>(cs), a.src, E, wave * C::SPW, a.B, C::SPW, tid, 64 * kZPipeWaves);
+        if (split) fill_cs_split(reinterpret_cast<double4*>(cs), zm_src(a), E, wave * C::SPW, a.B, C::SPW, tid, 64 * kZPipeWaves);
     }
-    if (!split) fill_cs(cs, a.src, N, E, wave * C::SPW, a.B, C::SPW, tid, 64 * kZPipeWaves);   // all waves of the pipeline
+    if (!split) fill_cs(cs, zm_src(a), N, E, wave * C::SPW, a.B, C::SPW, tid, 64 * kZPipeWaves);   // all waves of the pipeline
     __syncthreads();
 
     if (role < 2) {
@@ -1535,7 +1577,7 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
         int seen_ready = 0;
         if (!SNAP) pair_wait_ge(&sync->ready[smp], 1, &sync->abort, seen_ready);
         const double2 f = psi_final[(smp << 5) | k];
-        const double h = ham_weight<N>(k, a.off, a.co, a.diag);
+        const double h = ham_weight<N>(k, zm_off(a), zm_co(a), zm_diag(a));
         double v[1] = {h * (f.x * f.x + f.y * f.y)};
         lane_reduce<1, 5>(v, lane);                            // over the sample's 32 basis states (both halves hold the sum)
         const double pred = v[0] + (zm_bias(a) ? zm_bias(a)[0] : 0.0);
@@ -1652,7 +1694,7 @@ __global__ __launch_bounds__(64 * (4 + NSIG)) void bwd_zquad_kernel(A a) {
         for (int w = 0; w < NSIG; ++w) sync.cursor[w] = 0;
         sync.next = 0;
     }
-    fill_cs_split(reinterpret_cast<double4*>(cs_tables), a.src, E, wave * C::SPW, a.B, C::SPW, tid, 64 * (4 + NSIG));
+    fill_cs_split(reinterpret_cast<double4*>(cs_tables), zm_src(a), E, wave * C::SPW, a.B, C::SPW, tid, 64 * (4 + NSIG));
     __syncthreads();
 
     if (wv < 4) {
@@ -1832,8 +1874,8 @@ __device__ __forceinline__ void zpacked_body(const A& a, int wib, int lane, int 
     }
     {   // upstream weight and lambda_N = g H psi_N (in the read-out basis, then rotated back)
         double fr[1] = {pr[0]}, fi[1] = {pi[0]};
-        basis_change<N, false>(fr, fi, a.pauli, lane);
-        const double h = ham_weight<N>(klow, a.off, a.co, a.diag);
+        basis_change<N, false>(fr, fi, zm_pauli(a), lane);
+        const double h = ham_weight<N>(klow, zm_off(a), zm_co(a), zm_diag(a));
         double v[1] = {h * (fr[0] * fr[0] + fi[0] * fi[0])};
         lane_reduce<1, C::LB>(v, lane);
         const double pred = v[0] + (zm_bias(a) ? zm_bias(a)[0] : 0.0);
@@ -1841,7 +1883,7 @@ __device__ __forceinline__ void zpacked_body(const A& a, int wib, int lane, int 
         double gb = zm_y(a) ? 2.0 * (pred - zm_y(a)[b]) * a.inv_bt : a.g[b];
         if (!valid) gb = 0.0;
         lr[0] = gb * h * fr[0]; li[0] = gb * h * fi[0];
-        basis_change<N, true>(lr, li, a.pauli, lane);
+        basis_change<N, true>(lr, li, zm_pauli(a), lane);
     }
 
     const int nb = a.nblocks;
@@ -1946,7 +1988,7 @@ __global__ __launch_bounds__(kZPWaves * 64) void bwd_zpacked_kernel(A a) {
     const long b = valid ? b_raw : a.B - 1;
     const int klow = lane & (C::LANES - 1);
     double2* cs = reinterpret_cast<double2*>(dyn_lds);
-    fill_cs(cs, a.src, N, a.E, (long)blockIdx.x * kZPWaves * C::SPW, a.B, kZPWaves * C::SPW, (int)threadIdx.x, kZPWaves * 64,
+    fill_cs(cs, zm_src(a), N, a.E, (long)blockIdx.x * kZPWaves * C::SPW, a.B, kZPWaves * C::SPW, (int)threadIdx.x, kZPWaves * 64,
             (int)zp_cs_row(N, a.E));
     __syncthreads();
     if (a.fast_ld == 2) zpacked_body<N, 2>(a, wib, lane, klow, valid, b, wave, cs, wg_ring, comb);
@@ -2002,11 +2044,11 @@ __global__ __launch_bounds__(kZPWaves * 64) void fwd_zshared_kernel(ZFwdArgs a) 
 #define QHEA_ZDECLARE(NN)                                                              \
     void launch_fwd_zyz_##NN(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArgs& a); \
     void launch_fwd_zshared_##NN(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArgs& a); \
-    void launch_bwd_ztri_##NN(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a);   \
-    void launch_bwd_zpacked_##NN(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a);
+    void launch_bwd_ztri_##NN(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a, const char* mrec);   \
+    void launch_bwd_zpacked_##NN(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a, const char* mrec);
 QHEA_FOR_EACH_ZN(QHEA_ZDECLARE)
 void launch_fwd_split_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArgs& a);
-void launch_bwd_zquad_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a);
+void launch_bwd_zquad_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a, const char* mrec);
 void launch_bwd_zsnap_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a);
 #undef QHEA_ZDECLARE
 

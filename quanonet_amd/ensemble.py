@@ -25,33 +25,44 @@ def _trainable(cfg):
     return str(cfg.get('if_trainable_freq', 'true')).lower() == 'true'
 
 
-def validate_configs(configs):
-    """Raise ValueError unless `configs` can train as one ensemble.  Touches no device."""
+def check_supported(configs, who='EnsembleSolver'):
+    """Raise ValueError for settings no one-launch-per-step training supports (the checks every member must pass alone)."""
     configs = list(configs)
     if not configs:
-        raise ValueError("EnsembleSolver needs at least one config")
+        raise ValueError(f"{who} needs at least one config")
     for c in configs:
         if int(c.get('world_size', 1)) > 1:
-            raise ValueError("EnsembleSolver runs on one device: world_size > 1 is not supported")
+            raise ValueError(f"{who} runs on one device: world_size > 1 is not supported")
         dp = sorted(k for k in c if k.startswith('dp_'))
         if dp:
-            raise ValueError(f"EnsembleSolver has no data-parallel step: remove {dp}")
+            raise ValueError(f"{who} has no data-parallel step: remove {dp}")
         if str(c.get('optimizer', 'adam')).lower() != 'adam':
-            raise ValueError(f"EnsembleSolver trains with Adam only (got optimizer={c.get('optimizer')!r})")
+            raise ValueError(f"{who} trains with Adam only (got optimizer={c.get('optimizer')!r})")
         extra = set(c.get('optimizer_kwargs', {}) or {}) - {'betas', 'eps', 'weight_decay'}
         if extra:
-            raise ValueError(f"EnsembleSolver's Adam takes betas / eps / weight_decay only (got {sorted(extra)})")
+            raise ValueError(f"{who}'s Adam takes betas / eps / weight_decay only (got {sorted(extra)})")
         if not c.get('epoch_call', True):
-            raise ValueError("EnsembleSolver issues each epoch from one host call: epoch_call=False is not supported")
+            raise ValueError(f"{who} issues each epoch from one host call: epoch_call=False is not supported")
         if c.get('skip_completed', False):
-            raise ValueError("EnsembleSolver trains every member: skip_completed is not supported")
+            raise ValueError(f"{who} trains every member: skip_completed is not supported")
+    return configs
+
+
+def check_shared(configs, free, what='one ensemble'):
+    """Raise ValueError if two configs differ in a key outside `free`."""
     ref = configs[0]
-    free = set(MEMBER_KEYS) | ({'scale_coeff'} if _trainable(ref) else set())
     for i, c in enumerate(configs[1:], 1):
-        for k in sorted((set(ref) | set(c)) - free):
+        for k in sorted((set(ref) | set(c)) - set(free)):
             if ref.get(k) != c.get(k):
                 raise ValueError(f"config {i} differs from config 0 in {k!r} ({c.get(k)!r} vs {ref.get(k)!r}): members of "
-                                 f"one ensemble may differ only in {sorted(free)}")
+                                 f"{what} may differ only in {sorted(free)}")
+
+
+def validate_configs(configs):
+    """Raise ValueError unless `configs` can train as one ensemble.  Touches no device."""
+    configs = check_supported(configs)
+    free = set(MEMBER_KEYS) | ({'scale_coeff'} if _trainable(configs[0]) else set())
+    check_shared(configs, free)
     return configs
 
 
@@ -60,15 +71,19 @@ class EnsembleSolver:
 
     def __init__(self, configs, data_dict, device=None, log=print):
         self.configs = validate_configs(configs)
+        self._build([data_dict] * len(self.configs), device, log)
+
+    def _build(self, data_dicts, device, log):
+        """one PTSolver per member (member m on data_dicts[m]), their parameters and Adam moments as rows of [R, P] tensors"""
         self.device = device if device is not None else torch.device('cuda')
         if self.device.type != 'cuda':
             raise RuntimeError("EnsembleSolver runs on a HIP device only (no CPU fallback)")
         self.log = log
         self.members = []
-        for c in self.configs:
+        for c, d in zip(self.configs, data_dicts):
             if c.get('seed') is not None:
                 torch.manual_seed(int(c['seed']))
-            self.members.append(PTSolver(c, data_dict, device=self.device, log=lambda *a, **k: None))
+            self.members.append(PTSolver(c, d, device=self.device, log=lambda *a, **k: None))
         tr0 = self.members[0].trainer
         if tr0.desc is None or not tr0.epoch_call:
             raise RuntimeError("EnsembleSolver needs the fused model-level training path (QuanONetPT / HEAQNNPT in fp64)")
@@ -116,7 +131,6 @@ class EnsembleSolver:
             os.makedirs(m.out_dir, exist_ok=True)
             m.best_model_path = os.path.join(m.out_dir, 'best_model.pt')
         opt0 = m0.trainer.optimizer
-        ham_diag = m0.trainer._ham_diag()
 
         def issue(staged):
             """queue one epoch's steps of every member; returns the device rows of their [sse | sum y^2]"""
@@ -124,10 +138,7 @@ class EnsembleSolver:
                 m.model.train()
             inputs, out = staged
             rows = torch.zeros(R, nb, nm + 2, dtype=torch.float64, device=self.device)
-            g = opt0.param_groups[0]
-            _lib.model_ensemble_train_steps(self.desc, bounds, gbs, inputs[0], inputs[1] if len(inputs) > 1 else None, out,
-                                            self.params, rows, self.exp_avg, self.exp_avg_sq, opt0.t + 1, g['lr'],
-                                            g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'], ham_diag=ham_diag)
+            self._train_steps(bounds, gbs, inputs, out, rows, opt0.t + 1)
             for m in self.members:
                 m.trainer.optimizer.t += nb
             return rows[:, :, nm:]
@@ -162,6 +173,16 @@ class EnsembleSolver:
             for m in self.members:
                 m._save(os.path.join(m.out_dir, 'final.pt'))
         return histories
+
+    def _train_steps(self, bounds, gbs, inputs, out, rows, first_step):
+        """one epoch's steps of every member, one launch per kernel and step"""
+        from . import _lib
+        m0 = self.members[0]
+        g = m0.trainer.optimizer.param_groups[0]
+        _lib.model_ensemble_train_steps(self.desc, bounds, gbs, inputs[0], inputs[1] if len(inputs) > 1 else None, out,
+                                        self.params, rows, self.exp_avg, self.exp_avg_sq, first_step, g['lr'],
+                                        g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'],
+                                        ham_diag=m0.trainer._ham_diag())
 
     def predict(self, inputs, batch_size=None):
         """Every member's predictions on the same inputs (the single-model forward path), as a list."""
