@@ -260,6 +260,45 @@ __device__ __forceinline__ int butterfly_sum(double (&v)[K], int lane) {
     v[0] = pair_sum<1>(v[0]);
     return idx;
 }
+// Per-sample variant for n = 5 (two samples of 32 lanes per wave): the same transposing steps on lane bits 4, 3, 2, 1 and a
+// pair sum on bit 0, lane bit 5 (the sample) left alone -- 8*3 + 4*5 + 2*5 + 7 + 3 = 64 instructions.  Afterwards both lanes
+// of every even / odd pair hold the 32-lane total of value `sample_slot(lane)` over their own sample.
+__device__ __forceinline__ int sample_slot(int lane) {
+    return ((lane >> 4) & 1) | (((lane >> 3) & 1) << 1) | (((lane >> 2) & 1) << 2) | (((lane >> 1) & 1) << 3);
+}
+__device__ __forceinline__ int sample_slot_lane(int slot, int sample) {       // even lane of `sample` holding `slot`
+    return (sample << 5) | ((slot & 1) << 4) | (((slot >> 1) & 1) << 3) | (((slot >> 2) & 1) << 2) | (((slot >> 3) & 1) << 1);
+}
+__device__ __forceinline__ void sample_butterfly_sum16(double (&v)[16], int lane) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                         // bit 4: v_permlane16_swap
+        const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(v[2 * i]), (unsigned)__double2loint(v[2 * i + 1]), false, false);
+        const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(v[2 * i]), (unsigned)__double2hiint(v[2 * i + 1]), false, false);
+        v[i] = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                         // bit 3: row_shr:8 into banks 2,3 / row_shl:8 into banks 0,1
+        const int alo = __double2loint(v[2 * i]), ahi = __double2hiint(v[2 * i]);
+        const int blo = __double2loint(v[2 * i + 1]), bhi = __double2hiint(v[2 * i + 1]);
+        const int a2lo = __builtin_amdgcn_update_dpp(alo, blo, 0x118, 0xF, 0xC, false), a2hi = __builtin_amdgcn_update_dpp(ahi, bhi, 0x118, 0xF, 0xC, false);
+        const int b2lo = __builtin_amdgcn_update_dpp(blo, alo, 0x108, 0xF, 0x3, false), b2hi = __builtin_amdgcn_update_dpp(bhi, ahi, 0x108, 0xF, 0x3, false);
+        v[i] = __hiloint2double(a2hi, a2lo) + __hiloint2double(b2hi, b2lo);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {                         // bit 2: row_shr:4 into banks 1,3 / row_shl:4 into banks 0,2
+        const int alo = __double2loint(v[2 * i]), ahi = __double2hiint(v[2 * i]);
+        const int blo = __double2loint(v[2 * i + 1]), bhi = __double2hiint(v[2 * i + 1]);
+        const int a2lo = __builtin_amdgcn_update_dpp(alo, blo, 0x114, 0xF, 0xA, false), a2hi = __builtin_amdgcn_update_dpp(ahi, bhi, 0x114, 0xF, 0xA, false);
+        const int b2lo = __builtin_amdgcn_update_dpp(blo, alo, 0x104, 0xF, 0x5, false), b2hi = __builtin_amdgcn_update_dpp(bhi, ahi, 0x104, 0xF, 0x5, false);
+        v[i] = __hiloint2double(a2hi, a2lo) + __hiloint2double(b2hi, b2lo);
+    }
+    {                                                     // bit 1: select + quad exchange
+        const bool up = (lane >> 1) & 1;
+        const double keep = up ? v[1] : v[0], send = up ? v[0] : v[1];
+        v[0] = keep + xchg<2>(send);
+    }
+    v[0] = pair_sum<1>(v[0]);
+}
 template <int K>
 __device__ __forceinline__ bool butterfly_owner(int lane) { return (lane & (K == 32 ? 1 : (K == 16 ? 3 : 7))) == 0; }
 // lane that holds value v after butterfly_sum<K> (the owner among those that do)

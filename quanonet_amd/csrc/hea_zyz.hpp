@@ -1472,6 +1472,13 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
     // slots alternate per step of THIS wave (its steps are drawn, not consecutive)
     const unsigned snap_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)(psi_ring[0]);
     int cur = 0;
+    // RX-chunk steps: this lane's slot after sample_butterfly_sum16, its axis entry, and for the lanes that store grad_x
+    // (the even lane of slot 3q of each sample) the lanes of slots 3q + 1, 3q + 2
+    const int vs = sample_slot(lane), ax_slot = vs < 3 * N ? vs : 3 * N - 1;
+    const int gx_src1 = sample_slot_lane(vs + 1, lane >> 5) * 4, gx_src2 = sample_slot_lane(vs + 2, lane >> 5) * 4;
+    const long bs = wave * C::SPW + (lane >> 5);
+    const bool gx_lane = (lane & 1) == 0 && vs < 3 * N && vs % 3 == 0 && bs < a.B;
+    double* __restrict__ gx_w = zm_gx(a) + bs * E + vs / 3;
     auto fetch_snap = [&](int t, int sl) {
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
                      :: "s"(snap_lds + (unsigned)sl * kSnapBytes), "v"((unsigned)lane * 16u), "s"(snap_rsrc),
@@ -1507,12 +1514,8 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
         double2 qv[N];
         static_for<0, N>([&](auto q) { qv[decltype(q)::value] = slot[lane ^ (1 << decltype(q)::value)]; });
         const double2 lm = lam_ring[t & (RING - 1)][lane];
-        double em[CHUNK ? 3 * N : 1];
-        if constexpr (CHUNK) {
-            const double* __restrict__ e = axis_ring + (bl & (kAxisRing - 1)) * (3 * N);
-#pragma unroll
-            for (int i = 0; i < 3 * N; ++i) em[i] = e[i];
-        }
+        double ax = 0.0;                                  // (read before the cursor moves on: it also frees the axis entry)
+        if constexpr (CHUNK) ax = axis_ring[(bl & (kAxisRing - 1)) * (3 * N) + ax_slot];
         if (lane == 0) __hip_atomic_store(&cursor[me], after_v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         mine = __builtin_amdgcn_readfirstlane(after_v);
         after_v = draw();
@@ -1523,15 +1526,17 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
         double acc3[C::KW];
         products(acc3, pv, qv, lm);
         if constexpr (CHUNK) {
-            double gx[C::KX];
-#pragma unroll
-            for (int i = 0; i < C::KX; ++i) gx[i] = 0.0;
-            static_for<0, N>([&](auto q) {
-                constexpr int Q = decltype(q)::value;
-                gx[Q] = em[3 * Q] * acc3[3 * Q] + em[3 * Q + 1] * acc3[3 * Q + 1] + em[3 * Q + 2] * acc3[3 * Q + 2];
-            });
-            store_sums(acc3, sub);
-            store_grad_x5(gx, lane, wave, a.B, E, zm_gx(a), bl * N, N);
+            // per-sample sums S: the chunk's gradients are n_q . (S_3q, S_3q+1, S_3q+2) of each sample, the parameter row
+            // S(sample 0) + S(sample 1)
+            sample_butterfly_sum16(acc3, lane);
+            const double pr = ax * acc3[0];
+            const double g = pr + lane_gather(pr, gx_src1) + lane_gather(pr, gx_src2);
+            const double tot = pair_sum<32>(acc3[0]);
+            if ((lane & 33) == 0) {
+                if constexpr (SNAP) __hip_atomic_fetch_add(&row_lds[sub * C::KW + vs], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                else store_through(&part_w[(long)sub * C::KW + vs], tot);
+            }
+            if (gx_lane) store_through(&gx_w[bl * N], g);
         } else {
             store_sums(acc3, sub);
         }
