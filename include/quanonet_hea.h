@@ -424,6 +424,36 @@ int qhea_model_sweep_train_steps(const qhea_model_desc* desc, int64_t n_models,
                                  double beta1, double beta2, double eps, double weight_decay,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Depth sweep: qhea_model_sweep_train_steps for members whose circuits also differ in depth -- a capacity grid (the
+ * reference's reproduce_capacity.sh / reproduce_circuit.sh / reproduce_scaling.sh: net_size = hb 2 ht 2 over hb x ht x seeds)
+ * trained as one launch per kernel and step.  descs[m] is member m's descriptor.  The descriptors may differ only in their
+ * depths: QuanONet net[0] (branch blocks) and net[2] (trunk blocks), HEAQNN net[0]; model, n_qubits, the other net entries,
+ * the input widths and trainable_freq must be equal (else QHEA_EINVAL).  Their ham_pauli, scale_coeff, ham_offset and ham_coeff
+ * are NOT used: read-out, fixed scale and lr are members[m]'s, as in qhea_model_sweep_train_steps.
+ * Layouts: Pmax = the largest qhea_model_param_count of the members.  params, exp_avg, exp_avg_sq are [n_models][Pmax]: member
+ * m's flat vector (the layout of its own descriptor) is at m * Pmax, the rest of its row is never read or written.  grad is
+ * [n_models][n_steps][grad_stride], grad_stride >= Pmax + 2; member m's row holds its P_m gradients, then sse, sum y^2.
+ * branch / trunk / y / ham_diag / row_begin / inv_batch_total as in qhea_model_sweep_train_steps.
+ * n <= 9: every step is one launch per kernel (member = the grid's second dimension) of the first-generation kernels with the
+ * packed backward, at any batch; member m's results are bitwise those of qhea_model_train_steps with m's sweep descriptor
+ * (descs[m] with members[m]'s read-out and scale), lr = members[m].lr and ham_diag + m * 2^n under QHEA_BWD_PACKED.
+ * n >= 10: n_models consecutive qhea_model_train_steps calls with those descriptors.  Workspace:
+ * qhea_model_depth_sweep_workspace_bytes for every batch size of the schedule (the largest of those); an overrun of any member
+ * is reported by qhea_check_status on it.
+ */
+size_t qhea_model_depth_sweep_workspace_bytes(const qhea_model_desc* descs /*HOST [n_models]*/, int64_t n_models, int64_t batch);
+int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs /*HOST [n_models]*/, int64_t n_models,
+                                       const qhea_member_hparams* members /*HOST [n_models]*/,
+                                       const double* ham_diag /*DEVICE [n_models][2^n] or NULL*/,
+                                       int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1], the same for every member*/,
+                                       const double* branch, const double* trunk, const double* y /*DEVICE, [n_models][rows]*/,
+                                       double* params /*DEVICE [n_models][Pmax]*/, const double* inv_batch_total /*HOST [n_steps]*/,
+                                       double* grad /*DEVICE [n_models][n_steps][grad_stride]*/, int64_t grad_stride,
+                                       double* exp_avg /*DEVICE [n_models][Pmax]*/, double* exp_avg_sq, int64_t first_step,
+                                       double beta1, double beta2, double eps, double weight_decay,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -771,28 +771,32 @@ int launch_prep(int n, const Shape& sh, int64_t B, const double* w, const double
 // model-level (fused) path: frequency layers + sincos in prep, MSE residual in the circuit
 // kernel, every parameter gradient in one reduce launch
 // ---------------------------------------------------------------------------------------
+// gate-table entry tid (n padding entries on each side) of the model-level prep kernels
+__device__ __forceinline__ void prep_gate_entry(int n, int blk, const double* __restrict__ w, double4* __restrict__ gates, long tid) {
+    const long g = tid - n;
+    double4 v0 = make_double4(1.0, 0.0, 0.0, 0.0);
+    if (g >= 0 && g < (long)blk * n) {
+        const int s = (int)(g / n), q = (int)(g % n);
+        const double* ws = w + (long)s * 3 * n;
+        double sa, ca, sb, cb, sc, cc;
+        fast_sincos(0.5 * ws[q], &sa, &ca);
+        fast_sincos(0.5 * ws[n + q], &sb, &cb);
+        fast_sincos(0.5 * ws[2 * n + q], &sc, &cc);
+        const double m00r = cb * ca, m00i = -sb * ca, m01r = -cb * sa, m01i = sb * sa;
+        const double m10r = cb * sa, m10i = sb * sa, m11r = cb * ca, m11i = sb * ca;
+        v0 = make_double4(cc * m00r - sc * m10r, cc * m00i - sc * m10i,
+                          cc * m01r - sc * m11r, cc * m01i - sc * m11i);
+    }
+    gates[2 * tid] = v0;
+    gates[2 * tid + 1] = make_double4(v0.x, -v0.y, -v0.z, v0.w);
+}
 __global__ void prep_model_kernel(int n, int blk, const double* __restrict__ w, double4* __restrict__ gates,
                                   long B, int E, EncDesc enc, double2* __restrict__ cs, WorkspaceHeader* hdr) {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid == 0) header_init(hdr);
     const long ng = (long)(blk + 2) * n;
     if (tid < ng) {
-        const long g = tid - n;
-        double4 v0 = make_double4(1.0, 0.0, 0.0, 0.0);
-        if (g >= 0 && g < (long)blk * n) {
-            const int s = (int)(g / n), q = (int)(g % n);
-            const double* ws = w + (long)s * 3 * n;
-            double sa, ca, sb, cb, sc, cc;
-            fast_sincos(0.5 * ws[q], &sa, &ca);
-            fast_sincos(0.5 * ws[n + q], &sb, &cb);
-            fast_sincos(0.5 * ws[2 * n + q], &sc, &cc);
-            const double m00r = cb * ca, m00i = -sb * ca, m01r = -cb * sa, m01i = sb * sa;
-            const double m10r = cb * sa, m10i = sb * sa, m11r = cb * ca, m11i = sb * ca;
-            v0 = make_double4(cc * m00r - sc * m10r, cc * m00i - sc * m10i,
-                              cc * m01r - sc * m11r, cc * m01i - sc * m11i);
-        }
-        gates[2 * tid] = v0;
-        gates[2 * tid + 1] = make_double4(v0.x, -v0.y, -v0.z, v0.w);
+        prep_gate_entry(n, blk, w, gates, tid);
     } else if (tid - ng < B * E) {
         const long t = tid - ng;
         const long b = t / E;
@@ -843,19 +847,67 @@ struct MemberLr {
     const char* mrec;           // member 0's MemberRec (hea_zyz.hpp), member m's ms.ws bytes further per member
     double bc1;
 };
-template <bool FUSE, bool DP, bool MT = false>        // (the fused one's LDS and registers do not weigh on the plain one)
+// Depth sweeps (DEPTH, with MT; qhea_model_depth_sweep_train_steps): member blockIdx.y's block counts are its MemberRec::depth,
+// and its blk, E, parameter layout and block roles follow from them (depth_map).  The launch's blk, E, gm.off_ans / off_sse /
+// off_w / off_b, nb_w and nb_x are the largest member's and not used; w is the member's parameter row (not its angles).  The
+// grid is sized for the largest member: a block beyond its member's last role returns at once.
+struct DepthMap {
+    int blk, E, nc0;                        // sub-layers, encoding columns, columns of segment 0
+    long off_w0, off_b0, off_w1, off_b1;    // frequency weights / biases per segment (< 0: fixed frequency)
+    long off_ans, P;
+};
+__host__ __device__ inline DepthMap depth_map(int n, bool quanonet, bool trainable, int c0, int c1, int ld0, int ld1) {
+    DepthMap d;                             // (the layout of model_info: bias, branch_freq, trunk_freq, quantum_layer)
+    d.nc0 = c0 * n;
+    const int nc1 = c1 * n;
+    d.E = d.nc0 + nc1;
+    d.blk = c0 * ld0 + c1 * ld1;
+    d.off_w0 = d.off_b0 = d.off_w1 = d.off_b1 = -1;
+    long p = quanonet ? 1 : 0;
+    if (trainable) {
+        if (quanonet) { d.off_w1 = p; p += nc1; d.off_b1 = p; p += nc1; }
+        d.off_w0 = p; p += d.nc0; d.off_b0 = p; p += d.nc0;
+    }
+    d.off_ans = p;
+    d.P = p + (long)d.blk * 3 * n;
+    return d;
+}
+struct DepthRed { int quanonet, trainable, ld0, ld1; };
+// DR: empty, or one DepthRed -- the depth-sweep instantiation (the others keep their exact argument list)
+template <bool FUSE, bool DP, bool MT = false, class... DR>   // (the fused one's LDS and registers do not weigh on the plain one)
 __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         int n, int blk, int kw, long nwaves, const double* __restrict__ partial, const double* w,
         long B, int E, EncDesc enc, const double* __restrict__ grad_x, const double* __restrict__ pred,
         const double* __restrict__ y, double inv_bt, GradMap gm, int nb_w, int nb_x, double* __restrict__ grad,
         AdamArgs adam, const WorkspaceHeader* __restrict__ hdr, const double* gmap, FusePrep fp, DpX dpx, MemberStride ms,
-        MemberLr mlr) {
+        MemberLr mlr, DR... dr_pack) {
 #pragma clang fp contract(off)
+    constexpr bool DEPTH = sizeof...(DR) != 0;
+    static_assert(!DEPTH || (MT && !FUSE && !DP), "depth sweeps: member learning rates, no fused records, one rank");
+    // A depth-sweep member's own GradMap entries and segment-0 width: locals (a modified copy of gm or enc would live in private
+    // memory); the other instantiations read the arguments where they are used, as they always did
+    long d_ans = 0, d_sse = 0, d_w0 = 0, d_b0 = 0, d_w1 = 0, d_b1 = 0;
+    int d_nc0 = 0;
+    auto g_ans = [&]() -> long { if constexpr (DEPTH) return d_ans; else return gm.off_ans; };
+    auto g_sse = [&]() -> long { if constexpr (DEPTH) return d_sse; else return gm.off_sse; };
+    auto nc0 = [&]() -> int { if constexpr (DEPTH) return d_nc0; else return enc.seg[0].ncols; };
     {   // ensemble launches: member blockIdx.y's data, parameters, gradient rows and workspace slice (hdr: slice 0's)
         const long m = blockIdx.y, wsb = m * ms.ws, pb = m * ms.params * (long)sizeof(double);
         if constexpr (MT) {
             const MemberRec* mr = member_ptr(reinterpret_cast<const MemberRec*>(mlr.mrec), wsb);
             adam.lr_over_bc1 = ((ConstMemberRec)mr)->lr / mlr.bc1;
+            if constexpr (DEPTH) {
+                const DepthRed dr = (dr_pack, ...);
+                const DepthMap d = depth_map(n, dr.quanonet != 0, dr.trainable != 0, ((ConstMemberRec)mr)->depth[0],
+                                             ((ConstMemberRec)mr)->depth[1], dr.ld0, dr.ld1);
+                blk = d.blk; E = d.E; d_nc0 = d.nc0;
+                nb_w = (blk * kw + red_cols(kw) - 1) / red_cols(kw);
+                nb_x = dr.trainable ? (E + kFreqCols - 1) / kFreqCols : 0;
+                d_ans = d.off_ans; d_sse = d.P;
+                d_w0 = d.off_w0; d_b0 = d.off_b0; d_w1 = d.off_w1; d_b1 = d.off_b1;
+                w = w + d.off_ans;
+                if ((int)blockIdx.x > nb_w + nb_x) return;
+            }
         }
         partial = member_ptr(partial, wsb); grad_x = member_ptr(grad_x, wsb); pred = member_ptr(pred, wsb);
         gmap = member_ptr(gmap, wsb);
@@ -925,7 +977,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
     const unsigned status = hdr->status;
     const double kNaN = std::numeric_limits<double>::quiet_NaN();
     if (bid < nb_w) {
-        reduce_xyz_block(bid, n, blk, kw, nwaves, partial, w, grad + gm.off_ans, acc, acc2, status != 0, gmap, &adam, gm.off_ans,
+        reduce_xyz_block(bid, n, blk, kw, nwaves, partial, w, grad + g_ans(), acc, acc2, status != 0, gmap, &adam, g_ans(),
                          0, nullptr, dp, &dp_failed, dp_loc, dp_xch);
     } else if (bid < nb_w + nb_x) {
         const int j = threadIdx.x % kFreqCols, slice = threadIdx.x / kFreqCols;
@@ -933,8 +985,8 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         double s0 = 0.0, s1 = 0.0;
         int si = 0, ee = e;
         if (e < E) {
-            si = e < enc.seg[0].ncols ? 0 : 1;
-            if (si) ee = e - enc.seg[0].ncols;
+            si = e < nc0() ? 0 : 1;
+            if (si) ee = e - nc0();
             const EncSeg& sg = enc.seg[si];
             const double* __restrict__ in = sg.in + (long)blockIdx.y * ms.rows * sg.width + ee % sg.width;
             const double* __restrict__ gx = grad_x + e;
@@ -974,7 +1026,10 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         __syncthreads();
         if (slice < kFreqStage) { acc[slice * kFreqCols + j] = u0; acc2[slice * kFreqCols + j] = u1; }
         __syncthreads();
-        const bool mine = slice == 0 && e < E && gm.off_w[si] >= 0;
+        // (read where they are used, as the segment's GradMap entries always were)
+        auto g_w = [&]() -> long { if constexpr (DEPTH) return si ? d_w1 : d_w0; else return gm.off_w[si]; };
+        auto g_b = [&]() -> long { if constexpr (DEPTH) return si ? d_b1 : d_b0; else return gm.off_b[si]; };
+        const bool mine = slice == 0 && e < E && g_w() >= 0;
         double t0 = 0.0, t1 = 0.0;
         bool skip = status != 0;
         if (mine) {
@@ -989,7 +1044,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             if (threadIdx.x == 0) { dp_failed = 0; *dp_count = 2 * __popcll(bal); }
             if (mine) {
                 dp_loc[2 * pos] = t0; dp_loc[2 * pos + 1] = t1;
-                dp_idx[2 * pos] = gm.off_b[si] + ee; dp_idx[2 * pos + 1] = gm.off_w[si] + ee;
+                dp_idx[2 * pos] = g_b() + ee; dp_idx[2 * pos + 1] = g_w() + ee;
             }
             __syncthreads();
             const bool ok = dpx_exchange_block(dpx, *dp_count, dp_loc, [dp_idx](int i) { return dp_idx[i]; }, dp_xch, &dp_failed);
@@ -1000,9 +1055,9 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             }
         }
         if (mine) {
-            store_through(&grad[gm.off_b[si] + ee], t0);
-            store_through(&grad[gm.off_w[si] + ee], t1);
-            if (adam.p && !skip) { adam_update(adam, gm.off_b[si] + ee, t0); adam_update(adam, gm.off_w[si] + ee, t1); }
+            store_through(&grad[g_b() + ee], t0);
+            store_through(&grad[g_w() + ee], t1);
+            if (adam.p && !skip) { adam_update(adam, g_b() + ee, t0); adam_update(adam, g_w() + ee, t1); }
         }
 #ifdef QHEA_REDUCE_STAMPS
         if (threadIdx.x == 0 && bid == nb_w) printf("reduce freq block: %llu clk\n", __builtin_amdgcn_s_memtime() - st0);
@@ -1030,8 +1085,8 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         if constexpr (DP) {
             if (threadIdx.x == 0) {
                 dp_failed = 0;
-                dp_loc[0] = sse; dp_idx[0] = gm.off_sse;
-                dp_loc[1] = sy2; dp_idx[1] = gm.off_sse + 1;
+                dp_loc[0] = sse; dp_idx[0] = g_sse();
+                dp_loc[1] = sy2; dp_idx[1] = g_sse() + 1;
                 if (gm.off_bias >= 0) { dp_loc[2] = gbias; dp_idx[2] = gm.off_bias; }
                 *dp_count = gm.off_bias >= 0 ? 3 : 2;
             }
@@ -1045,13 +1100,44 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             }
         }
         if (threadIdx.x == 0) {
-            store_through(&grad[gm.off_sse], sse);
-            store_through(&grad[gm.off_sse + 1], sy2);
+            store_through(&grad[g_sse()], sse);
+            store_through(&grad[g_sse() + 1], sy2);
             if (gm.off_bias >= 0) {
                 store_through(&grad[gm.off_bias], gbias);
                 if (adam.p && !skip) adam_update(adam, gm.off_bias, gbias);
             }
         }
+    }
+}
+
+// Depth sweeps: prep_model_kernel for member blockIdx.y, whose shape (depth_map) comes from its MemberRec -- gate table of its
+// blk sub-layers from its angles, (cos, sin) of its E encoding columns with its frequency layers or its fixed scale.  params:
+// member 0's row (rows ms.params doubles apart), gates / cs: member 0's slice, enc: segment inputs and widths only.  The grid
+// is sized for the largest member; threads beyond the member's entries write nothing.
+__global__ void prep_model_depth_kernel(int n, DepthRed dr, const double* __restrict__ params, double4* __restrict__ gates,
+                                        long B, EncDesc enc, double2* __restrict__ cs, WorkspaceHeader* hdr, const char* mrec,
+                                        MemberStride ms) {
+    const long m = blockIdx.y, wsb = m * ms.ws;
+    const ConstMemberRec mr = (ConstMemberRec)member_ptr(reinterpret_cast<const MemberRec*>(mrec), wsb);
+    const DepthMap d = depth_map(n, dr.quanonet != 0, dr.trainable != 0, mr->depth[0], mr->depth[1], dr.ld0, dr.ld1);
+    const double* __restrict__ p = params + m * ms.params;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid == 0 && m == 0) header_init(hdr);
+    const long ng = (long)(d.blk + 2) * n;
+    if (tid < ng) {
+        prep_gate_entry(n, d.blk, p + d.off_ans, member_ptr(gates, wsb), tid);
+    } else if (tid - ng < B * d.E) {
+        const long t = tid - ng;
+        const long b = t / d.E;
+        int e = (int)(t % d.E);
+        const int si = e < d.nc0 ? 0 : 1;
+        if (si) e -= d.nc0;
+        const EncSeg& sg = enc.seg[si];
+        const double v = sg.in[(b + m * ms.rows) * sg.width + e % sg.width];
+        const double x = dr.trainable ? v * p[(si ? d.off_w1 : d.off_w0) + e] + p[(si ? d.off_b1 : d.off_b0) + e] : v * mr->scale;
+        double sn, cn;
+        fast_sincos(0.5 * x, &sn, &cn);
+        member_ptr(cs, wsb)[t] = make_double2(cn, sn);
     }
 }
 
@@ -1196,9 +1282,13 @@ bool ensemble_grid(const ModelInfo& mi, int64_t R, int64_t batch) {
 
 // The members' hyper-parameters reach the device as kernel arguments: one launch per kMemberFill members and host call writes
 // each member's MemberRec (hea_zyz.hpp) into its workspace slice -- no pageable copy, nothing retained, capturable.
-constexpr int kMemberFill = 64;                 // 64 x 40 bytes of kernel arguments
+constexpr int kMemberFill = 64;                 // 64 x 40 (depth sweeps: 48) bytes of kernel arguments
 struct MemberFill { qhea_member_hparams h[kMemberFill]; };
-__global__ __launch_bounds__(kMemberFill) void member_fill_kernel(MemberFill f, int count, char* slice0, long slice_bytes,
+struct MemberFillDepth : MemberFill {           // depth sweeps: + the members' block counts (MemberRec::depth)
+    int32_t depth[kMemberFill][2];
+};
+template <class F>
+__global__ __launch_bounds__(kMemberFill) void member_fill_kernel(F f, int count, char* slice0, long slice_bytes,
                                                                   const double* diag0, long diag_stride) {
     const int i = threadIdx.x;
     if (i >= count) return;
@@ -1207,6 +1297,8 @@ __global__ __launch_bounds__(kMemberFill) void member_fill_kernel(MemberFill f, 
     r.scale = h.scale_coeff; r.off = h.ham_offset; r.co = h.ham_coeff; r.lr = h.lr;
     r.diag = diag0 ? diag0 + (long)i * diag_stride : nullptr;
     r.pauli = h.ham_pauli; r.pad = 0;
+    r.depth[0] = r.depth[1] = 0;
+    if constexpr (std::is_same<F, MemberFillDepth>::value) { r.depth[0] = f.depth[i][0]; r.depth[1] = f.depth[i][1]; }
     *reinterpret_cast<MemberRec*>(slice0 + (long)i * slice_bytes + kMemberRecOffset) = r;
 }
 
@@ -1223,7 +1315,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 460; }
+int qhea_version(void) { return 470; }
 
 const char* qhea_strerror(int code) {
     switch (code) {
@@ -1790,7 +1882,7 @@ static int members_train_steps(const qhea_model_desc* desc, const ModelInfo& mi,
             const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
             MemberFill f{};
             for (int i = 0; i < cnt; ++i) f.h[i] = hp(m0 + i);
-            hipLaunchKernelGGL(member_fill_kernel, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
+            hipLaunchKernelGGL(member_fill_kernel<MemberFill>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
                                diag0 ? diag0 + m0 * diag_stride : nullptr, (long)diag_stride);
             if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
         }
@@ -1880,6 +1972,218 @@ int qhea_model_sweep_train_steps(const qhea_model_desc* desc, int64_t n_models, 
                                ham_diag, (int64_t)1 << mi.n, n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad,
                                grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, workspace,
                                workspace_bytes, stream);
+}
+
+// ---- depth sweeps (qhea_model_depth_sweep_train_steps) ----
+// The members' descriptors: every field but the depths (QuanONet net[0] / net[2], HEAQNN net[0]) equal to member 0's, each one
+// valid on its own (its ham_* and scale fields are not used: read with a Z read-out).  env: the descriptor with the largest
+// depths of every run -- its shape bounds every member's E, blk and P, and sizes the slices and the grids.
+struct DepthSet {
+    qhea_model_desc env;
+    ModelInfo env_mi;
+    int64_t pmax = 0;
+    int c_max[2] = {0, 0};
+    DepthRed dr{};
+};
+static int depth_set(const qhea_model_desc* descs, int64_t R, DepthSet& ds) {
+    if (!descs || R < 1 || R > 65535) return QHEA_EINVAL;
+    const qhea_model_desc& d0 = descs[0];
+    const bool qn = d0.model == QHEA_MODEL_QUANONET;
+    ds.env = d0;
+    ds.env.ham_pauli = QHEA_PAULI_Z;
+    for (int64_t m = 0; m < R; ++m) {
+        const qhea_model_desc& d = descs[m];
+        if (d.model != d0.model || d.n_qubits != d0.n_qubits || d.branch_in != d0.branch_in || d.trunk_in != d0.trunk_in ||
+            d.trainable_freq != d0.trainable_freq || d.net[1] != d0.net[1] || d.net[3] != d0.net[3] ||
+            (!qn && d.net[2] != d0.net[2]))
+            return QHEA_EINVAL;
+        qhea_model_desc dz = d;
+        dz.ham_pauli = QHEA_PAULI_Z;
+        ModelInfo mi;
+        const int rc = model_info(&dz, mi);
+        if (rc != QHEA_OK) return rc;
+        // run 0 / run 1 of the launch's run table: QuanONet trunk (net[2] x net[3]) then branch (net[0] x net[1]); HEAQNN
+        // net[0] x net[1] and an empty run
+        const int c0 = qn ? d.net[2] : d.net[0], c1 = qn ? d.net[0] : 0;
+        ds.dr = DepthRed{qn ? 1 : 0, d.trainable_freq != 0 ? 1 : 0, qn ? d.net[3] : d.net[1], qn ? d.net[1] : 0};
+        if (depth_map(mi.n, qn, mi.trainable, c0, c1, ds.dr.ld0, ds.dr.ld1).P != mi.P) return QHEA_EUNSUPPORTED;
+        if (mi.P > ds.pmax) ds.pmax = mi.P;
+        if (c0 > ds.c_max[0]) ds.c_max[0] = c0;
+        if (c1 > ds.c_max[1]) ds.c_max[1] = c1;
+    }
+    if (qn) { ds.env.net[2] = ds.c_max[0]; ds.env.net[0] = ds.c_max[1]; }
+    else ds.env.net[0] = ds.c_max[0];
+    return model_info(&ds.env, ds.env_mi);
+}
+// member m's block counts of run 0 / run 1
+static void depth_counts(const qhea_model_desc& d, int32_t (&c)[2]) {
+    const bool qn = d.model == QHEA_MODEL_QUANONET;
+    c[0] = qn ? d.net[2] : d.net[0];
+    c[1] = qn ? d.net[0] : 0;
+}
+// One member's slice for `batch` rows (the largest member's shape): header (MemberRec at kMemberRecOffset), gate table, (cos, sin)
+// table, partial rows of the packed backward kernel, grad_x, predictions -- the first-generation single-model layout under
+// QHEA_BWD_PACKED
+struct DepthLayout { size_t off_U, off_cs, off_part, off_gx, off_pred, total; long nwaves; };
+static DepthLayout depth_layout(const ModelInfo& env, int64_t B) {
+    DepthLayout L{};
+    const int n = env.n, spw = 64 >> lane_bits(n);
+    L.nwaves = (((B + spw - 1) / spw + kWaves - 1) / kWaves) * kWaves;
+    size_t p = kHeaderBytes;
+    L.off_U = p;    p = align_up(p + (size_t)(env.sh.blk + 2) * n * kGateBytes);
+    L.off_cs = p;   p = align_up(p + (size_t)B * env.sh.E * sizeof(double2));
+    L.off_part = p; p = align_up(p + (size_t)L.nwaves * env.sh.blk * padded_3n(n) * sizeof(double));
+    L.off_gx = p;   p = align_up(p + (size_t)B * env.sh.E * sizeof(double));
+    L.off_pred = p; p = align_up(p + (size_t)B * sizeof(double));
+    L.total = p;
+    return L;
+}
+// n >= 10 (workgroup-resident kernels): the members run one after the other, each on its own single-model layout
+static size_t depth_slice_bytes(const qhea_model_desc* descs, int64_t R, const DepthSet& ds, int64_t batch) {
+    if (!lds_supported(ds.env_mi.n)) return depth_layout(ds.env_mi, batch).total;
+    size_t slice = 0;
+    for (int64_t m = 0; m < R; ++m) {
+        qhea_model_desc dz = descs[m];
+        dz.ham_pauli = QHEA_PAULI_Z;
+        ModelInfo mi;
+        if (model_info(&dz, mi) != QHEA_OK) return 0;
+        const size_t b = make_model_layout(mi, batch).total;
+        if (b > slice) slice = b;
+    }
+    return slice;
+}
+
+size_t qhea_model_depth_sweep_workspace_bytes(const qhea_model_desc* descs, int64_t n_models, int64_t batch) {
+    DepthSet ds;
+    if (depth_set(descs, n_models, ds) != QHEA_OK || batch < 0) return 0;
+    return (size_t)n_models * depth_slice_bytes(descs, n_models, ds, batch);
+}
+
+int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_models, const qhea_member_hparams* members,
+                                       const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
+                                       const double* trunk, const double* y, double* params, const double* inv_batch_total,
+                                       double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                                       int64_t first_step, double beta1, double beta2, double eps, double weight_decay,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!descs || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
+        first_step < 1)
+        return QHEA_EINVAL;
+    for (int64_t m = 0; m < n_models; ++m) {
+        const qhea_member_hparams& h = members[m];
+        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
+        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;
+        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;
+    }
+    DepthSet ds;
+    const int rc0 = depth_set(descs, n_models, ds);
+    if (rc0 != QHEA_OK) return rc0;
+    const ModelInfo& env = ds.env_mi;
+    if (grad_stride < ds.pmax + 2) return QHEA_EINVAL;
+    for (int64_t i = 0; i < n_steps; ++i)
+        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
+    const bool qn = ds.env.model == QHEA_MODEL_QUANONET;
+    if (qn && !trunk) return QHEA_EINVAL;
+    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    size_t slice = 0;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const size_t b = depth_slice_bytes(descs, n_models, ds, row_begin[i + 1] - row_begin[i]);
+        if (b > slice) slice = b;
+    }
+    if (!workspace || slice == 0 || workspace_bytes < (size_t)n_models * slice) return QHEA_EWORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    const int64_t rows = row_begin[n_steps];                        // rows per member
+    const int64_t diag_stride = (int64_t)1 << env.n;
+    if (lds_supported(env.n)) {                                      // one member after the other, each on its own descriptor
+        for (int64_t m = 0; m < n_models; ++m) {
+            const qhea_model_desc dm = member_desc(descs[m], members[m]);
+            char* wm = ws + m * slice;
+            const int rc = qhea_model_train_steps(&dm, n_steps, row_begin, branch + m * rows * dm.branch_in,
+                                                  qn ? trunk + m * rows * dm.trunk_in : nullptr, y + m * rows,
+                                                  params + m * ds.pmax, ham_diag ? ham_diag + m * diag_stride : nullptr,
+                                                  inv_batch_total, grad + m * n_steps * grad_stride, grad_stride,
+                                                  exp_avg + m * ds.pmax, exp_avg_sq + m * ds.pmax, first_step, members[m].lr,
+                                                  beta1, beta2, eps, weight_decay, wm, slice, stream);
+            if (rc != QHEA_OK) return rc;
+            if (m > 0) {
+                hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
+                                   reinterpret_cast<WorkspaceHeader*>(wm));
+                if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+            }
+        }
+        return QHEA_OK;
+    }
+    // One grid per kernel and step, member = blockIdx.y: every member's read-out, scale, learning rate and block counts reach
+    // its MemberRec first
+    for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
+        const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
+        MemberFillDepth f{};
+        for (int i = 0; i < cnt; ++i) {
+            f.h[i] = members[m0 + i];
+            depth_counts(descs[m0 + i], f.depth[i]);
+        }
+        hipLaunchKernelGGL(member_fill_kernel<MemberFillDepth>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
+                           ham_diag ? ham_diag + m0 * diag_stride : nullptr, (long)diag_stride);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    }
+    // the reduce grid: the most blocks any member's roles need (ansatz blocks, frequency blocks, the sse / bias block)
+    const int n = env.n, kw = padded_3n(n);
+    int red_blocks = 0;
+    for (int64_t m = 0; m < n_models; ++m) {
+        int32_t c[2];
+        depth_counts(descs[m], c);
+        const DepthMap d = depth_map(n, qn, ds.dr.trainable != 0, c[0], c[1], ds.dr.ld0, ds.dr.ld1);
+        const int nb = (d.blk * kw + red_cols(kw) - 1) / red_cols(kw) + (ds.dr.trainable ? (d.E + kFreqCols - 1) / kFreqCols : 0) + 1;
+        if (nb > red_blocks) red_blocks = nb;
+    }
+    Runs runs{};                                        // two runs of fixed (enc, ld); the counts are the members'
+    runs.nruns = 2;
+    runs.enc[0] = runs.enc[1] = n;
+    runs.ld[0] = ds.dr.ld0; runs.ld[1] = ds.dr.ld1;
+    const MemberStride ms{(long)rows, (long)ds.pmax, (long)(n_steps * grad_stride), (long)slice};
+    const char* mrec = ws + kMemberRecOffset;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
+        const DepthLayout L = depth_layout(env, nb);
+        const EncDesc enc = make_enc(&ds.env, env, branch + r0 * ds.env.branch_in, qn ? trunk + r0 * ds.env.trunk_in : nullptr,
+                                     params);
+        const long prep_total = (env.sh.blk + 2) * n + nb * env.sh.E;
+        hipLaunchKernelGGL(prep_model_depth_kernel, dim3((unsigned)((prep_total + 255) / 256), (unsigned)n_models), dim3(256), 0, st,
+                           n, ds.dr, (const double*)params, reinterpret_cast<double4*>(ws + L.off_U), (long)nb, enc,
+                           reinterpret_cast<double2*>(ws + L.off_cs), reinterpret_cast<WorkspaceHeader*>(ws), mrec, ms);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        double* gx = reinterpret_cast<double*>(ws + L.off_gx);
+        double* pr = reinterpret_cast<double*>(ws + L.off_pred);
+        double* partial = reinterpret_cast<double*>(ws + L.off_part);
+        const BwdArgs ba{runs, (long)nb, (int)env.sh.E, (int)env.sh.blk, reinterpret_cast<const double2*>(ws + L.off_cs),
+                         ws + L.off_U, 0, 0.0, 0.0, nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr,
+                         inv_batch_total[i], pr, gx, partial, QHEA_PAULI_Z, 0, n_models * L.nwaves > simd_count() ? 1 : 0,
+                         nullptr};
+        const dim3 grid((unsigned)(L.nwaves / kWaves), (unsigned)n_models);
+        profile_begin(st);
+        switch (n) {
+#define QHEA_CASE(NN) case NN: launch_bwd_depth_##NN(grid, st, ba, mrec, ms); break;
+            QHEA_FOR_EACH_N(QHEA_CASE)
+#undef QHEA_CASE
+            default: return QHEA_EUNSUPPORTED;
+        }
+        profile_end(st);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        const int64_t step = first_step + i;
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const AdamArgs adam{params, exp_avg, exp_avg_sq, members[0].lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+        GradMap gm{};
+        gm.off_ans = env.off_ans; gm.off_bias = env.off_bias; gm.off_sse = env.P;
+        for (int s = 0; s < 2; ++s) { gm.off_w[s] = env.off_w[s]; gm.off_b[s] = env.off_b[s]; }
+        hipLaunchKernelGGL((reduce_model_kernel<false, false, true, DepthRed>), dim3((unsigned)red_blocks, (unsigned)n_models),
+                           dim3(kRedThreads), 0, st, n, (int)env.sh.blk, kw, L.nwaves, (const double*)partial,
+                           (const double*)params, (long)nb, (int)env.sh.E, enc, (const double*)gx, (const double*)pr, y + r0,
+                           inv_batch_total[i], gm, 0, 0, grad + i * grad_stride, adam,
+                           reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr, FusePrep{}, DpX{}, ms,
+                           MemberLr{mrec, bc1}, ds.dr);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    }
+    return QHEA_OK;
 }
 
 int qhea_adam_step(int64_t n, double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t step,

@@ -973,10 +973,18 @@ __device__ __forceinline__ void store_grad_x5(double (&v)[8], int lane, long wav
 // ---------------------------------------------------------------------------------------
 // forward sweep (shared by the forward and backward kernels)
 // ---------------------------------------------------------------------------------------
-template <int N>
+// Block counts of the runs: the run table's, or -- MEM, a depth-sweep member (hea_zyz.hpp: DepthArgs) -- the member's own two
+// (its runs have the launch's (enc, ld), the counts are the member's)
+struct DepthCounts { int c0, c1; };
+template <bool MEM>
+__device__ __forceinline__ int run_count(const Runs& r, int ri, const DepthCounts& d) {
+    if constexpr (MEM) return ri == 0 ? d.c0 : d.c1;
+    else return r.count[ri];
+}
+template <int N, bool MEM = false>
 __device__ __forceinline__ void forward_sweep(double (&re)[Cfg<N>::R], double (&im)[Cfg<N>::R],
                                               const Runs& runs, CsStream<N>& csx, GateStream<N>& gs,
-                                              int lane, int ring_fwd) {
+                                              int lane, int ring_fwd, DepthCounts dc = DepthCounts{0, 0}) {
     using C = Cfg<N>;
 #pragma unroll
     for (int r = 0; r < C::R; ++r) { re[r] = 0.0; im[r] = 0.0; }
@@ -988,7 +996,7 @@ __device__ __forceinline__ void forward_sweep(double (&re)[Cfg<N>::R], double (&
         const int ne = runs.enc[ri], nld = runs.ld[ri];
         const bool fold = kFold<N> && nld > 0 && ne > 0;   // first RX chunk rides on the first sub-layer's gates
         const int m0 = ne < N ? ne : N;
-        for (int rep = 0; rep < runs.count[ri]; ++rep) {
+        for (int rep = 0; rep < run_count<MEM>(runs, ri, dc); ++rep) {
             if (!fold) {
                 for_gates_below<N>(ne, [&](auto q) {
                     constexpr int Q = decltype(q)::value;
@@ -1080,7 +1088,9 @@ __global__ __launch_bounds__(kWaves * 64) void fwd_kernel(Runs runs, long B, int
 // allocation at 256 (20 / 116 spilled) so that both are resident -- measured, forward + backward of 24 sub-layers,
 // uncapped / capped: n = 8 B = 1024 136 / 179 us, B = 2048 249 / 206 us, B = 4096 484 / 378 us; n = 9 B = 1024
 // 234 / 329 us, B = 2048 446 / 379 us, B = 4096 875 / 711 us.  The host picks (BwdArgs::dense).
-template <int N, int MINW = 1>
+// DA: empty for the single-model kernel; one DepthArgs (hea_zyz.hpp) for the depth-sweep member instantiation (member =
+// blockIdx.y), whose prologue moves the pointers to the member's and sets its E, blk, read-out and block counts.
+template <int N, int MINW = 1, class... DA>
 __global__ __launch_bounds__(kWaves * 64, MINW) void bwd_kernel(Runs runs, long B, int E, int blk,
                                                           const double2* __restrict__ cs,
                                                           const char* __restrict__ gates, int gates_bytes,
@@ -1093,8 +1103,27 @@ __global__ __launch_bounds__(kWaves * 64, MINW) void bwd_kernel(Runs runs, long 
                                                           double inv_bt,
                                                           double* __restrict__ out,
                                                           double* __restrict__ grad_x,
-                                                          double* __restrict__ partial) {
+                                                          double* __restrict__ partial, DA... da) {
     using C = Cfg<N>;
+    constexpr bool MEM = sizeof...(DA) != 0;
+    DepthCounts dc{0, 0};
+    if constexpr (MEM) {        // the member's counts, shape, read-out and pointers (the launch's are member 0's)
+        const auto d = (da, ...);
+        const auto mr = d.rec();
+        dc.c0 = mr->depth[0]; dc.c1 = mr->depth[1];
+        E = N * (dc.c0 + dc.c1);
+        blk = dc.c0 * runs.ld[0] + dc.c1 * runs.ld[1];
+        gates_bytes = (blk + 2) * N * kGateBytes;
+        off = mr->off; co = mr->co; diag = mr->diag; pauli = mr->pauli;
+        const long wsb = d.ws_bytes();
+        cs = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(cs) + wsb);
+        gates += wsb;
+        out = reinterpret_cast<double*>(reinterpret_cast<char*>(out) + wsb);
+        grad_x = reinterpret_cast<double*>(reinterpret_cast<char*>(grad_x) + wsb);
+        partial = reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + wsb);
+        y = reinterpret_cast<const double*>(reinterpret_cast<const char*>(y) + d.row_bytes());
+        if (bias) bias = reinterpret_cast<const double*>(reinterpret_cast<const char*>(bias) + d.param_bytes());
+    }
     __shared__ double2 cs_lds[kWaves * kCsPerWave + 16];   // +16: slack for the unclamped prefetch
     __shared__ double red_lds[C::LDSRED ? kWaves * C::REDW : 1];
     __shared__ __attribute__((aligned(16))) char gate_ring[kWaves * kRingBytesPerWave];
@@ -1122,7 +1151,7 @@ __global__ __launch_bounds__(kWaves * 64, MINW) void bwd_kernel(Runs runs, long 
             pr[r] = a.x; pi[r] = a.y;
         }
     } else {
-        forward_sweep<N>(pr, pi, runs, csx, gs, lane, ring_fwd);
+        forward_sweep<N, MEM>(pr, pi, runs, csx, gs, lane, ring_fwd, dc);
     }
 
     basis_change<N, false>(pr, pi, pauli, lane);
@@ -1164,7 +1193,7 @@ __global__ __launch_bounds__(kWaves * 64, MINW) void bwd_kernel(Runs runs, long 
         const bool one_chunk = ne <= N;
         const bool fold = kFold<N> && nld > 0 && ne > 0;   // the block's first RX chunk rides on sub-layer 0's gates
         const int m0 = ne < N ? ne : N;
-        for (int rep = 0; rep < runs.count[ri]; ++rep) {
+        for (int rep = 0; rep < run_count<MEM>(runs, ri, dc); ++rep) {
             if (one_chunk && !fold && ne > 0) csx.template prefetch<false>(col - ne);   // this block's angles, used after its sub-layers
             for (int l = nld - 1; l >= 0; --l) {
                 --sub;

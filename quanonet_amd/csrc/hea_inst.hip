@@ -28,6 +28,21 @@ void QHEA_CAT(launch_bwd_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArgs& a) 
                        a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x, a.partial);
 }
 
+// depth sweeps: member = blockIdx.y (hea_zyz.hpp: DepthArgs); dense as for the single-model kernel
+void QHEA_CAT(launch_bwd_depth_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArgs& a, const char* mrec, const MemberStride& ms) {
+#if QHEA_N == 8 || QHEA_N == 9
+    if (a.dense) {
+        hipLaunchKernelGGL((bwd_kernel<QHEA_N, 2, DepthArgs>), grid, dim3(kWaves * 64), 0, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates,
+                           a.gates_bytes, a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out,
+                           a.grad_x, a.partial, DepthArgs{mrec, ms});
+        return;
+    }
+#endif
+    hipLaunchKernelGGL((bwd_kernel<QHEA_N, 1, DepthArgs>), grid, dim3(kWaves * 64), 0, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates,
+                       a.gates_bytes, a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x,
+                       a.partial, DepthArgs{mrec, ms});
+}
+
 void QHEA_CAT(launch_bwd_pair_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArgs& a) {
 #if QHEA_N <= 5
     if (a.tri == 1) {

@@ -738,8 +738,11 @@ struct MemberRec {
     const double* diag;         // the member's diagonal Hamiltonian, or nullptr
     int pauli;                  // QHEA_PAULI_*
     int pad;
+    int depth[2];               // depth sweeps (qhea_model_depth_sweep_train_steps): the member's block counts of run 0 and
+                                // run 1 (QuanONet: trunk, branch; HEAQNN: its blocks, 0); 0 in the other member launches
 };
 constexpr int kMemberRecOffset = 64;            // bytes into the slice (its WorkspaceHeader uses the first 16)
+static_assert(kMemberRecOffset + sizeof(MemberRec) <= 256, "MemberRec lives in the slice's 256-byte header");
 template <class T>
 __device__ __forceinline__ T* uniform_ptr(T* p) {           // (read off lane 0: the compiler then knows it is uniform)
     const unsigned long long v = reinterpret_cast<unsigned long long>(p);
@@ -778,6 +781,24 @@ __device__ __forceinline__ double zm_co(const ZBwdArgsM& a) { return zm_mr(a)->c
 __device__ __forceinline__ const double* zm_diag(const ZBwdArgsM& a) { return zm_mr(a)->diag; }
 __device__ __forceinline__ int zm_pauli(const ZBwdArgsM& a) { return zm_mr(a)->pauli; }
 __device__ __forceinline__ AngleSrcM zm_src(const ZBwdArgsM& a) { return AngleSrcM{a.src, zm_mr(a)->scale}; }
+
+// Depth sweeps (qhea_model_depth_sweep_train_steps): the member instantiation of the first-generation packed backward kernel
+// (bwd_kernel<N, MINW, DepthArgs>, member = blockIdx.y).  The launch's run table is two runs of fixed (enc = n, ld) -- QuanONet
+// trunk, branch; HEAQNN its blocks and an empty run -- and member m's counts are its MemberRec::depth, read with scalar loads;
+// its E, blk and gate-table size follow from them.  The launch's pointers are member 0's: workspace-slice pointers move by
+// ms.ws bytes per member, y by ms.rows rows, the bias by ms.params doubles.  The grid's x dimension is the batch's sample
+// groups, the same for every member.
+struct DepthArgs {
+    const char* mrec;           // member 0's MemberRec
+    MemberStride ms;
+    // member blockIdx.y's record (scalar loads) and byte offsets: workspace slice, rows of y, parameter row
+    __device__ __forceinline__ ConstMemberRec rec() const {
+        return (ConstMemberRec)member_ptr(reinterpret_cast<const MemberRec*>(mrec), ws_bytes());
+    }
+    __device__ __forceinline__ long ws_bytes() const { return (long)blockIdx.y * ms.ws; }
+    __device__ __forceinline__ long row_bytes() const { return (long)blockIdx.y * ms.rows * (long)sizeof(double); }
+    __device__ __forceinline__ long param_bytes() const { return (long)blockIdx.y * ms.params * (long)sizeof(double); }
+};
 
 // kZFwdWaves sweeping waves + kFwdHelpers waves that only help to fill the (cos, sin) tables and then leave: the fill is
 // 2 x 600 fp64 sincos per sweeping wave at cfg 2, ~4 us if each does its own, and the sweep cannot start before it.  Four
@@ -2056,5 +2077,10 @@ void launch_fwd_split_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZFwdArg
 void launch_bwd_zquad_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a, const char* mrec);
 void launch_bwd_zsnap_5(dim3 grid, size_t dyn_lds, hipStream_t st, const ZBwdArgs& a);
 #undef QHEA_ZDECLARE
+// bwd_kernel<N, MINW, DepthArgs> for n = 2..9 (a.runs, a.B, a.cs, a.gates, a.y, a.bias, a.inv_bt, a.out, a.grad_x, a.partial, a.dense are
+// used; mrec: member 0's MemberRec)
+#define QHEA_DDECLARE(NN) void launch_bwd_depth_##NN(dim3 grid, hipStream_t st, const BwdArgs& a, const char* mrec, const MemberStride& ms);
+QHEA_FOR_EACH_N(QHEA_DDECLARE)
+#undef QHEA_DDECLARE
 
 }  // namespace qhea

@@ -89,20 +89,26 @@ class EnsembleSolver:
             raise RuntimeError("EnsembleSolver needs the fused model-level training path (QuanONetPT / HEAQNNPT in fp64)")
         self.desc = tr0.desc
         # the members' flat parameter vectors and Adam moments become rows of [R, P] tensors: one pointer per array for the
-        # ensemble call, and every member's module, optimizer and checkpoints keep working on their row
-        R, P = len(self.members), tr0.numel
-        self.params = torch.stack([m.trainer.pflat for m in self.members]).contiguous()
+        # ensemble call, and every member's module, optimizer and checkpoints keep working on their row (members of a depth
+        # sweep differ in size: member m's vector is the front of its row of [R, Pmax])
+        R = len(self.members)
+        self.numels = [m.trainer.numel for m in self.members]
+        P = max(self.numels)
+        self.params = torch.zeros(R, P, dtype=torch.float64, device=self.device)
+        for i, m in enumerate(self.members):
+            self.params[i, :self.numels[i]].copy_(m.trainer.pflat)
         self.exp_avg = torch.zeros(R, P, dtype=torch.float64, device=self.device)
         self.exp_avg_sq = torch.zeros(R, P, dtype=torch.float64, device=self.device)
         for i, m in enumerate(self.members):
             tr = m.trainer
-            tr.pflat = self.params[i]
+            tr.pflat = self.params[i, :self.numels[i]]
             off = 0
             for p in tr.params:
                 p.data = tr.pflat[off:off + p.numel()].view(p.shape)
                 off += p.numel()
             tr.optimizer.pflat = tr.pflat
-            tr.optimizer.exp_avg, tr.optimizer.exp_avg_sq = self.exp_avg[i], self.exp_avg_sq[i]
+            tr.optimizer.exp_avg = self.exp_avg[i, :self.numels[i]]
+            tr.optimizer.exp_avg_sq = self.exp_avg_sq[i, :self.numels[i]]
         self.rngs = [np.random.RandomState(c.get('seed')) for c in self.configs]
 
     def _stage_epoch(self, n, bs, nb):
@@ -124,7 +130,7 @@ class EnsembleSolver:
         nb = max(1, int(np.ceil(n / bs)))
         bounds = [min(i * bs, n) for i in range(nb)] + [n]
         gbs = [min(bs, n - i * bs) for i in range(nb)]
-        nm = m0.trainer.numel
+        nm = max(self.numels)
         histories = [{'loss_train': [], 'loss_test': []} for _ in range(R)]
         want_save = m0.config.get('if_save', True)
         for m in self.members:
@@ -141,7 +147,9 @@ class EnsembleSolver:
             self._train_steps(bounds, gbs, inputs, out, rows, opt0.t + 1)
             for m in self.members:
                 m.trainer.optimizer.t += nb
-            return rows[:, :, nm:]
+            if all(p == nm for p in self.numels):
+                return rows[:, :, nm:]
+            return torch.stack([rows[r, :, p:p + 2] for r, p in enumerate(self.numels)])   # member r's [sse | sum y^2]
 
         cur = issue(self._stage_epoch(n, bs, nb)) if epochs > 0 else None
         for epoch in range(epochs):
