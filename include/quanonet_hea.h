@@ -454,6 +454,33 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs /*HOST [n_mo
                                        double beta1, double beta2, double eps, double weight_decay,
                                        void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Qubit sweep: qhea_model_depth_sweep_train_steps for members whose circuits also differ in qubit count -- a scaling grid (the
+ * reference's reproduce_scaling.sh: Q2..Q8, each with its own hb x ht list, x seeds) trained side by side.  The descriptors may
+ * differ in n_qubits (2..12) and in their depths; model, the input widths, trainable_freq and the linear depths (QuanONet
+ * net[1] / net[3], HEAQNN net[1], net[2]) must be equal (else QHEA_EINVAL).  ham_diag is [n_models][2^nmax] (nmax = the largest
+ * n_qubits): member m reads the first 2^n_m entries of its row.  params / exp_avg / exp_avg_sq / grad / read-out / scale / lr
+ * and the per-member result as in qhea_model_depth_sweep_train_steps: member m's results are bitwise those of
+ * qhea_model_train_steps with m's sweep descriptor under QHEA_BWD_PACKED; row tails beyond P_m are never read or written.
+ * Members with n <= 9 share every step's launches: one prep launch, one backward launch per register class present (n = 2;
+ * n = 3..6) whose workgroups take (member, sample group) from a work list and one per n = 7, 8, 9 present, one reduce launch
+ * over every member's own roles.
+ * Members with n >= 10 then train one after another, each with qhea_model_train_steps on its own slice.  Workspace:
+ * qhea_model_qubit_sweep_workspace_bytes for the largest batch of the schedule; an overrun of any member is reported by
+ * qhea_check_status on it.
+ */
+size_t qhea_model_qubit_sweep_workspace_bytes(const qhea_model_desc* descs /*HOST [n_models]*/, int64_t n_models, int64_t batch);
+int qhea_model_qubit_sweep_train_steps(const qhea_model_desc* descs /*HOST [n_models]*/, int64_t n_models,
+                                       const qhea_member_hparams* members /*HOST [n_models]*/,
+                                       const double* ham_diag /*DEVICE [n_models][2^nmax] or NULL*/,
+                                       int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1], the same for every member*/,
+                                       const double* branch, const double* trunk, const double* y /*DEVICE, [n_models][rows]*/,
+                                       double* params /*DEVICE [n_models][Pmax]*/, const double* inv_batch_total /*HOST [n_steps]*/,
+                                       double* grad /*DEVICE [n_models][n_steps][grad_stride]*/, int64_t grad_stride,
+                                       double* exp_avg /*DEVICE [n_models][Pmax]*/, double* exp_avg_sq, int64_t first_step,
+                                       double beta1, double beta2, double eps, double weight_decay,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

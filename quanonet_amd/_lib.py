@@ -32,7 +32,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_dp_allreduce_adam', 'qhea_dp_status', 'qhea_model_dp_train_steps', 'qhea_clock_probe',
            'qhea_model_ensemble_workspace_bytes', 'qhea_model_ensemble_train_steps',
            'qhea_model_sweep_workspace_bytes', 'qhea_model_sweep_train_steps',
-           'qhea_model_depth_sweep_workspace_bytes', 'qhea_model_depth_sweep_train_steps']
+           'qhea_model_depth_sweep_workspace_bytes', 'qhea_model_depth_sweep_train_steps',
+           'qhea_model_qubit_sweep_workspace_bytes', 'qhea_model_qubit_sweep_train_steps']
 
 
 class ModelDesc(ctypes.Structure):
@@ -50,7 +51,7 @@ class MemberHParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 470           # 0.4.7: + qhea_model_depth_sweep_train_steps (members differ in depth too)
+MIN_LIB_VERSION = 480           # 0.4.8: + qhea_model_qubit_sweep_train_steps (members differ in qubit count too)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -163,6 +164,10 @@ def load():
                                                        i64p, dp, dp, dp, dp, f64p, dp, ctypes.c_int64, dp, dp, ctypes.c_int64,
                                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp,
                                                        ctypes.c_size_t, vp]
+    lib.qhea_model_qubit_sweep_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_qubit_sweep_workspace_bytes.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64]
+    lib.qhea_model_qubit_sweep_train_steps.restype = ctypes.c_int
+    lib.qhea_model_qubit_sweep_train_steps.argtypes = lib.qhea_model_depth_sweep_train_steps.argtypes
     lib.qhea_clock_probe.restype = ctypes.c_int
     lib.qhea_clock_probe.argtypes = [ctypes.c_int, ctypes.c_int64, vp, vp]
     lib.qhea_model_param_count.restype = ctypes.c_int64
@@ -638,6 +643,69 @@ def model_depth_sweep_train_steps(descs, members, bounds, global_batches, branch
                                                     _ptr(exp_avg_sq), int(first_step), float(beta1), float(beta2), float(eps),
                                                     float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
     _check(rc, 'qhea_model_depth_sweep_train_steps')
+    return rows
+
+
+def model_qubit_sweep_workspace_bytes(descs, batch):
+    """qhea_model_qubit_sweep_workspace_bytes for the members' descriptors; 0 if they cannot train as one qubit sweep."""
+    arr, R = _desc_array(descs)
+    return int(load().qhea_model_qubit_sweep_workspace_bytes(arr, R, int(batch)))
+
+
+def qubit_sweep_pmax(descs):
+    """Row length of a qubit sweep's parameter / moment arrays: the largest member's model_param_count."""
+    return max(model_param_count(d) for d in descs)
+
+
+def model_qubit_sweep_train_steps(descs, members, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                  first_step, beta1, beta2, eps, weight_decay, ham_diag=None):
+    """
+    model_depth_sweep_train_steps for members whose circuits also differ in qubit count (qhea_model_qubit_sweep_train_steps):
+    descs is the list of R member descriptors (equal but for n_qubits and the depth entries of net).  params / exp_avg /
+    exp_avg_sq: [R, Pmax]; rows: [R, n_steps, >= Pmax + 2]; ham_diag: [R, 2^nmax], member m's spectrum in the first 2^n_m entries
+    of its row.  Member m gets bitwise what model_train_steps gives for it alone under the packed backward variant.
+    """
+    lib = load()
+    n_steps = len(bounds) - 1
+    if n_steps <= 0:
+        return rows
+    if branch.dim() != 3:
+        raise QheaError("model_qubit_sweep_train_steps: branch must be [n_models, rows, branch_in]")
+    R, N = branch.shape[0], branch.shape[1]
+    if len(members) != R or len(descs) != R:
+        raise QheaError(f"model_qubit_sweep_train_steps: {len(descs)} descriptors / {len(members)} member records for {R} members")
+    d0 = descs[0]
+    _dev_f64(branch, 'branch', (R, N, d0.branch_in))
+    if d0.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (R, N, d0.trunk_in))
+    _dev_f64(y, 'y')
+    if tuple(y.shape) not in ((R, N), (R, N, 1)):
+        raise QheaError(f"y has shape {tuple(y.shape)}, expected ({R}, {N})")
+    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+        _dev_f64(t, nm)
+    P = qubit_sweep_pmax(descs)
+    if tuple(params.shape) != (R, P) or tuple(exp_avg.shape) != (R, P) or tuple(exp_avg_sq.shape) != (R, P):
+        raise QheaError(f"model_qubit_sweep_train_steps: params / exp_avg / exp_avg_sq must be [n_models, Pmax = {P}]")
+    if rows.dim() != 3 or rows.shape[0] != R or rows.shape[1] != n_steps or rows.shape[2] < P + 2:
+        raise QheaError("model_qubit_sweep_train_steps: rows must be [n_models, n_steps, >= Pmax+2]")
+    if bounds[0] < 0 or bounds[-1] != N or len(global_batches) != n_steps:
+        raise QheaError("model_qubit_sweep_train_steps: row bounds do not match the arrays")
+    _dev_f64(ham_diag, 'ham_diag', (R, 1 << max(d.n_qubits for d in descs)))
+    with torch.cuda.device(branch.device):
+        nbytes = model_qubit_sweep_workspace_bytes(descs, max(bounds[i + 1] - bounds[i] for i in range(n_steps)))
+    if nbytes == 0:
+        raise QheaError("model_qubit_sweep_train_steps: the descriptors differ in more than their qubit counts and depths")
+    ws = _workspace(branch.device, nbytes)
+    arr, _ = _desc_array(descs)
+    mh = (MemberHParams * R)(*members)
+    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
+    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_qubit_sweep_train_steps(arr, R, mh, _ptr(ham_diag), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
+                                                    _ptr(params), ib, _ptr(rows), int(rows.stride(1)), _ptr(exp_avg),
+                                                    _ptr(exp_avg_sq), int(first_step), float(beta1), float(beta2), float(eps),
+                                                    float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
+    _check(rc, 'qhea_model_qubit_sweep_train_steps')
     return rows
 
 

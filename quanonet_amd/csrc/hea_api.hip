@@ -2,13 +2,16 @@
 // workspace layout, the batch-invariant prep / reduce kernels and the per-qubit-count dispatch.
 #include <atomic>
 #include <cmath>
+#include <algorithm>
 #include <limits>
+#include <vector>
 
 #include "hea_device.hpp"
 #include "hea_zyz.hpp"
 #include "hea_sincos.hpp"
 #include "hea_adam.hpp"
 #include "hea_dp.hpp"
+#include "hea_qsweep.hpp"
 
 namespace qhea {
 
@@ -873,7 +876,18 @@ __host__ __device__ inline DepthMap depth_map(int n, bool quanonet, bool trainab
     return d;
 }
 struct DepthRed { int quanonet, trainable, ld0, ld1; };
-// DR: empty, or one DepthRed -- the depth-sweep instantiation (the others keep their exact argument list)
+// Qubit sweeps (QS, a DEPTH form; qhea_model_qubit_sweep_train_steps): the members differ in n as well.  The grid is a flat
+// list of every member's own roles -- work-list entries (member, role) in the slices' list regions (hea_qsweep.hpp: QsWork) --
+// and the member's n is its MemberRec::nq; its kw and partial-row count follow from it and the batch.  The launch's n, kw and
+// nwaves are not used.
+struct QubitRed {
+    DepthRed dr;
+    QsWork wk;
+};
+__device__ __forceinline__ DepthRed dr_of(const DepthRed& d) { return d; }
+__device__ __forceinline__ DepthRed dr_of(const QubitRed& q) { return q.dr; }
+// DR: empty, one DepthRed (the depth-sweep instantiation) or one QubitRed (the qubit-sweep one); the others keep their exact
+// argument list
 template <bool FUSE, bool DP, bool MT = false, class... DR>   // (the fused one's LDS and registers do not weigh on the plain one)
 __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         int n, int blk, int kw, long nwaves, const double* __restrict__ partial, const double* w,
@@ -883,6 +897,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         MemberLr mlr, DR... dr_pack) {
 #pragma clang fp contract(off)
     constexpr bool DEPTH = sizeof...(DR) != 0;
+    constexpr bool QS = (std::is_same<DR, QubitRed>::value || ...);
     static_assert(!DEPTH || (MT && !FUSE && !DP), "depth sweeps: member learning rates, no fused records, one rank");
     // A depth-sweep member's own GradMap entries and segment-0 width: locals (a modified copy of gm or enc would live in private
     // memory); the other instantiations read the arguments where they are used, as they always did
@@ -891,13 +906,24 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
     auto g_ans = [&]() -> long { if constexpr (DEPTH) return d_ans; else return gm.off_ans; };
     auto g_sse = [&]() -> long { if constexpr (DEPTH) return d_sse; else return gm.off_sse; };
     auto nc0 = [&]() -> int { if constexpr (DEPTH) return d_nc0; else return enc.seg[0].ncols; };
+    long mem = blockIdx.y;                              // member and role of this block (QS: its work-list entry's)
+    int bid = blockIdx.x;
+    if constexpr (QS) {
+        const int2 ent = qs_entry((dr_pack, ...).wk, ms.ws, (int)blockIdx.x);
+        mem = ent.x; bid = ent.y;
+    }
     {   // ensemble launches: member blockIdx.y's data, parameters, gradient rows and workspace slice (hdr: slice 0's)
-        const long m = blockIdx.y, wsb = m * ms.ws, pb = m * ms.params * (long)sizeof(double);
+        const long m = mem, wsb = m * ms.ws, pb = m * ms.params * (long)sizeof(double);
         if constexpr (MT) {
             const MemberRec* mr = member_ptr(reinterpret_cast<const MemberRec*>(mlr.mrec), wsb);
             adam.lr_over_bc1 = ((ConstMemberRec)mr)->lr / mlr.bc1;
+            if constexpr (QS) {                         // the member's own qubit count
+                n = ((ConstMemberRec)mr)->nq;
+                kw = padded_3n(n);
+                nwaves = qs_nwaves(n, B);
+            }
             if constexpr (DEPTH) {
-                const DepthRed dr = (dr_pack, ...);
+                const DepthRed dr = dr_of((dr_pack, ...));
                 const DepthMap d = depth_map(n, dr.quanonet != 0, dr.trainable != 0, ((ConstMemberRec)mr)->depth[0],
                                              ((ConstMemberRec)mr)->depth[1], dr.ld0, dr.ld1);
                 blk = d.blk; E = d.E; d_nc0 = d.nc0;
@@ -906,7 +932,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
                 d_ans = d.off_ans; d_sse = d.P;
                 d_w0 = d.off_w0; d_b0 = d.off_b0; d_w1 = d.off_w1; d_b1 = d.off_b1;
                 w = w + d.off_ans;
-                if ((int)blockIdx.x > nb_w + nb_x) return;
+                if (bid > nb_w + nb_x) return;
             }
         }
         partial = member_ptr(partial, wsb); grad_x = member_ptr(grad_x, wsb); pred = member_ptr(pred, wsb);
@@ -931,7 +957,6 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         __shared__ int count;
         dp_loc = loc; dp_xch = xch; dp_idx = idx; dp_count = &count;
     }
-    const int bid = blockIdx.x;
     const DpX* dp = DP ? &dpx : nullptr;
     QHEA_STAMP(0);
 #ifdef QHEA_REDUCE_STAMPS
@@ -988,7 +1013,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             si = e < nc0() ? 0 : 1;
             if (si) ee = e - nc0();
             const EncSeg& sg = enc.seg[si];
-            const double* __restrict__ in = sg.in + (long)blockIdx.y * ms.rows * sg.width + ee % sg.width;
+            const double* __restrict__ in = sg.in + mem * ms.rows * sg.width + ee % sg.width;
             const double* __restrict__ gx = grad_x + e;
             long b = slice;
             for (; b + 15L * kFreqSlices < B; b += 16L * kFreqSlices) {    // 32 loads in flight per thread: B = 1024 in ONE round trip
@@ -1123,6 +1148,37 @@ __global__ void prep_model_depth_kernel(int n, DepthRed dr, const double* __rest
     const double* __restrict__ p = params + m * ms.params;
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid == 0 && m == 0) header_init(hdr);
+    const long ng = (long)(d.blk + 2) * n;
+    if (tid < ng) {
+        prep_gate_entry(n, d.blk, p + d.off_ans, member_ptr(gates, wsb), tid);
+    } else if (tid - ng < B * d.E) {
+        const long t = tid - ng;
+        const long b = t / d.E;
+        int e = (int)(t % d.E);
+        const int si = e < d.nc0 ? 0 : 1;
+        if (si) e -= d.nc0;
+        const EncSeg& sg = enc.seg[si];
+        const double v = sg.in[(b + m * ms.rows) * sg.width + e % sg.width];
+        const double x = dr.trainable ? v * p[(si ? d.off_w1 : d.off_w0) + e] + p[(si ? d.off_b1 : d.off_b0) + e] : v * mr->scale;
+        double sn, cn;
+        fast_sincos(0.5 * x, &sn, &cn);
+        member_ptr(cs, wsb)[t] = make_double2(cn, sn);
+    }
+}
+
+// Qubit sweeps: prep_model_depth_kernel for members of different n -- member blockIdx.y's n is its MemberRec::nq.  The grid is
+// sized for the largest member; members with n >= 10 (trained on their own after the sweep's launches) write nothing.
+__global__ void prep_model_qubit_kernel(DepthRed dr, const double* __restrict__ params, double4* __restrict__ gates,
+                                        long B, EncDesc enc, double2* __restrict__ cs, WorkspaceHeader* hdr, const char* mrec,
+                                        MemberStride ms) {
+    const long m = blockIdx.y, wsb = m * ms.ws;
+    const ConstMemberRec mr = (ConstMemberRec)member_ptr(reinterpret_cast<const MemberRec*>(mrec), wsb);
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid == 0 && m == 0) header_init(hdr);
+    const int n = mr->nq;
+    if (n > 9) return;
+    const DepthMap d = depth_map(n, dr.quanonet != 0, dr.trainable != 0, mr->depth[0], mr->depth[1], dr.ld0, dr.ld1);
+    const double* __restrict__ p = params + m * ms.params;
     const long ng = (long)(d.blk + 2) * n;
     if (tid < ng) {
         prep_gate_entry(n, d.blk, p + d.off_ans, member_ptr(gates, wsb), tid);
@@ -1282,10 +1338,13 @@ bool ensemble_grid(const ModelInfo& mi, int64_t R, int64_t batch) {
 
 // The members' hyper-parameters reach the device as kernel arguments: one launch per kMemberFill members and host call writes
 // each member's MemberRec (hea_zyz.hpp) into its workspace slice -- no pageable copy, nothing retained, capturable.
-constexpr int kMemberFill = 64;                 // 64 x 40 (depth sweeps: 48) bytes of kernel arguments
+constexpr int kMemberFill = 64;                 // 64 x 40 (depth sweeps: 48, qubit sweeps: 52) bytes of kernel arguments
 struct MemberFill { qhea_member_hparams h[kMemberFill]; };
 struct MemberFillDepth : MemberFill {           // depth sweeps: + the members' block counts (MemberRec::depth)
     int32_t depth[kMemberFill][2];
+};
+struct MemberFillQubit : MemberFillDepth {      // qubit sweeps: + the members' qubit counts (MemberRec::nq)
+    int32_t nq[kMemberFill];
 };
 template <class F>
 __global__ __launch_bounds__(kMemberFill) void member_fill_kernel(F f, int count, char* slice0, long slice_bytes,
@@ -1296,10 +1355,20 @@ __global__ __launch_bounds__(kMemberFill) void member_fill_kernel(F f, int count
     MemberRec r;
     r.scale = h.scale_coeff; r.off = h.ham_offset; r.co = h.ham_coeff; r.lr = h.lr;
     r.diag = diag0 ? diag0 + (long)i * diag_stride : nullptr;
-    r.pauli = h.ham_pauli; r.pad = 0;
+    r.pauli = h.ham_pauli; r.nq = 0;
     r.depth[0] = r.depth[1] = 0;
-    if constexpr (std::is_same<F, MemberFillDepth>::value) { r.depth[0] = f.depth[i][0]; r.depth[1] = f.depth[i][1]; }
+    if constexpr (std::is_base_of<MemberFillDepth, F>::value) { r.depth[0] = f.depth[i][0]; r.depth[1] = f.depth[i][1]; }
+    if constexpr (std::is_same<F, MemberFillQubit>::value) r.nq = f.nq[i];
     *reinterpret_cast<MemberRec*>(slice0 + (long)i * slice_bytes + kMemberRecOffset) = r;
+}
+// Qubit sweeps: the work lists (hea_qsweep.hpp: QsWork) reach the slices' list regions the same way, kWorkFill entries per launch
+constexpr int kWorkFill = 256;                  // 2 KB of kernel arguments
+struct WorkFill { int2 e[kWorkFill]; };
+__global__ __launch_bounds__(kWorkFill) void work_fill_kernel(WorkFill f, int count, int k0, char* list0, long slice_bytes, int per) {
+    const int i = threadIdx.x;
+    if (i >= count) return;
+    const int k = k0 + i;
+    *reinterpret_cast<int2*>(list0 + (long)(k / per) * slice_bytes + (long)(k % per) * (long)sizeof(int2)) = f.e[i];
 }
 
 // The descriptor member m trains as: the shape of `desc`, m's read-out and fixed scale
@@ -1315,7 +1384,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 470; }
+int qhea_version(void) { return 480; }
 
 const char* qhea_strerror(int code) {
     switch (code) {
@@ -2182,6 +2251,293 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
                            reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr, FusePrep{}, DpX{}, ms,
                            MemberLr{mrec, bc1}, ds.dr);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    }
+    return QHEA_OK;
+}
+
+// ---- qubit sweeps (qhea_model_qubit_sweep_train_steps) ----
+// The members' descriptors: every field but n_qubits and the depths equal to member 0's, each one valid on its own (its ham_*
+// and scale fields are not used: read with a Z read-out).  Members with n <= 9 are wave-resident: they share the sweep's
+// launches; members with n >= 10 train one after the other on their own layouts.
+struct QubitMember {
+    ModelInfo mi;
+    int32_t c[2];               // block counts of run 0 / run 1 (MemberRec::depth)
+    DepthMap d;
+    bool wave;                  // n <= 9
+    double cost;                // length of the backward chain of one sample group (sub-layers x gates x amplitudes per lane)
+};
+struct QubitSet {
+    std::vector<QubitMember> mem;
+    int64_t pmax = 0;
+    int nmax = 0;
+    int n_wave = 0;
+    DepthRed dr{};
+};
+static int qubit_set(const qhea_model_desc* descs, int64_t R, QubitSet& qs) {
+    if (!descs || R < 1 || R > 65535) return QHEA_EINVAL;
+    const qhea_model_desc& d0 = descs[0];
+    const bool qn = d0.model == QHEA_MODEL_QUANONET;
+    qs.mem.resize((size_t)R);
+    for (int64_t m = 0; m < R; ++m) {
+        const qhea_model_desc& d = descs[m];
+        if (d.model != d0.model || d.branch_in != d0.branch_in || d.trunk_in != d0.trunk_in ||
+            d.trainable_freq != d0.trainable_freq || d.net[1] != d0.net[1] || d.net[3] != d0.net[3] ||
+            (!qn && d.net[2] != d0.net[2]))
+            return QHEA_EINVAL;
+        qhea_model_desc dz = d;
+        dz.ham_pauli = QHEA_PAULI_Z;
+        QubitMember& q = qs.mem[(size_t)m];
+        const int rc = model_info(&dz, q.mi);
+        if (rc != QHEA_OK) return rc;
+        const int n = q.mi.n;
+        depth_counts(d, q.c);
+        qs.dr = DepthRed{qn ? 1 : 0, d.trainable_freq != 0 ? 1 : 0, qn ? d.net[3] : d.net[1], qn ? d.net[1] : 0};
+        q.d = depth_map(n, qn, q.mi.trainable, q.c[0], q.c[1], qs.dr.ld0, qs.dr.ld1);
+        if (q.d.P != q.mi.P) return QHEA_EUNSUPPORTED;
+        q.wave = !lds_supported(n);
+        if (q.wave && !qs_built(n)) return QHEA_EUNSUPPORTED;      // (development builds)
+        q.cost = (double)q.d.blk * n * (double)(1 << (n - lane_bits(n)));
+        if (q.mi.P > qs.pmax) qs.pmax = q.mi.P;
+        if (n > qs.nmax) qs.nmax = n;
+        qs.n_wave += q.wave ? 1 : 0;
+    }
+    return QHEA_OK;
+}
+// Work lists for a schedule whose largest batch is Bmax: per register class its members' (member, sample group) entries, the
+// longest chain first (a short batch's launch skips the groups past its last sample); per n = 7..9 its members (member, 0);
+// then every member's reduce roles (ansatz blocks, frequency blocks, the sse / bias block) as (member, role).
+struct QubitPlan {
+    std::vector<int2> e;
+    int cls_begin[kQsClasses] = {0, 0}, cls_count[kQsClasses] = {0, 0};
+    int own_begin[kQsOwnHi - kQsOwnLo + 1] = {0, 0, 0}, own_count[kQsOwnHi - kQsOwnLo + 1] = {0, 0, 0};   // n = 7..9: (member, 0)
+    int red_begin = 0, red_count = 0;
+    int per = 1;                // entries per slice
+    size_t list_bytes = 0;
+};
+static int red_roles(const QubitMember& q, bool trainable) {
+    const int kw = padded_3n(q.mi.n);
+    return (q.d.blk * kw + red_cols(kw) - 1) / red_cols(kw) + (trainable ? (q.d.E + kFreqCols - 1) / kFreqCols : 0) + 1;
+}
+static void qubit_plan(const QubitSet& qs, int64_t Bmax, QubitPlan& P) {
+    const int64_t R = (int64_t)qs.mem.size();
+    for (int c = 0; c < kQsClasses; ++c) {
+        std::vector<int> ms;
+        for (int64_t m = 0; m < R; ++m)
+            if (qs.mem[m].wave && qs_class_of(qs.mem[m].mi.n) == c) ms.push_back((int)m);
+        std::stable_sort(ms.begin(), ms.end(), [&](int a, int b) { return qs.mem[a].cost > qs.mem[b].cost; });
+        P.cls_begin[c] = (int)P.e.size();
+        for (int m : ms) {
+            const long groups = qs_nwaves(qs.mem[m].mi.n, Bmax) / kWaves;
+            for (long g = 0; g < groups; ++g) P.e.push_back(make_int2(m, (int)g));
+        }
+        P.cls_count[c] = (int)P.e.size() - P.cls_begin[c];
+    }
+    for (int n = kQsOwnLo; n <= kQsOwnHi; ++n) {
+        P.own_begin[n - kQsOwnLo] = (int)P.e.size();
+        for (int64_t m = 0; m < R; ++m)
+            if (qs.mem[m].wave && qs.mem[m].mi.n == n) P.e.push_back(make_int2((int)m, 0));
+        P.own_count[n - kQsOwnLo] = (int)P.e.size() - P.own_begin[n - kQsOwnLo];
+    }
+    P.red_begin = (int)P.e.size();
+    for (int64_t m = 0; m < R; ++m)
+        if (qs.mem[m].wave)
+            for (int r = 0, nr = red_roles(qs.mem[m], qs.dr.trainable != 0); r < nr; ++r) P.e.push_back(make_int2((int)m, r));
+    P.red_count = (int)P.e.size() - P.red_begin;
+    P.per = (int)(((int64_t)P.e.size() + R - 1) / R);
+    if (P.per < 1) P.per = 1;
+    P.list_bytes = (size_t)P.per * sizeof(int2);
+}
+// One member's slice for `batch` rows: header (MemberRec at kMemberRecOffset), list region, then the depth sweep's regions --
+// gate table, (cos, sin) table, partial rows of the packed backward kernel, grad_x, predictions -- each sized for the largest
+// wave-resident member's, so that every member's lie at the same offsets.  At least a single-model layout of every n >= 10
+// member.
+struct QubitLayout { size_t off_list, off_U, off_cs, off_part, off_gx, off_pred, total; };
+static QubitLayout qubit_layout(const QubitSet& qs, int64_t B, size_t list_bytes) {
+    size_t u = 0, e = 0, part = 0;
+    for (const QubitMember& q : qs.mem) {
+        if (!q.wave) continue;
+        const int n = q.mi.n;
+        u = std::max(u, (size_t)(q.d.blk + 2) * n * kGateBytes);
+        e = std::max(e, (size_t)q.d.E);
+        part = std::max(part, (size_t)qs_nwaves(n, B) * q.d.blk * padded_3n(n) * sizeof(double));
+    }
+    QubitLayout L{};
+    size_t p = kHeaderBytes;
+    L.off_list = p; p = align_up(p + list_bytes);
+    L.off_U = p;    p = align_up(p + u);
+    L.off_cs = p;   p = align_up(p + (size_t)B * e * sizeof(double2));
+    L.off_part = p; p = align_up(p + part);
+    L.off_gx = p;   p = align_up(p + (size_t)B * e * sizeof(double));
+    L.off_pred = p; p = align_up(p + (size_t)B * sizeof(double));
+    L.total = p;
+    return L;
+}
+static size_t qubit_slice_bytes(const QubitSet& qs, int64_t B, size_t list_bytes) {
+    size_t slice = qs.n_wave > 0 ? qubit_layout(qs, B, list_bytes).total : 0;
+    for (const QubitMember& q : qs.mem)
+        if (!q.wave) slice = std::max(slice, make_model_layout(q.mi, B).total);
+    return slice;
+}
+
+size_t qhea_model_qubit_sweep_workspace_bytes(const qhea_model_desc* descs, int64_t n_models, int64_t batch) {
+    QubitSet qs;
+    if (qubit_set(descs, n_models, qs) != QHEA_OK || batch < 0) return 0;
+    QubitPlan plan;
+    qubit_plan(qs, batch, plan);
+    return (size_t)n_models * qubit_slice_bytes(qs, batch, plan.list_bytes);
+}
+
+int qhea_model_qubit_sweep_train_steps(const qhea_model_desc* descs, int64_t n_models, const qhea_member_hparams* members,
+                                       const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
+                                       const double* trunk, const double* y, double* params, const double* inv_batch_total,
+                                       double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                                       int64_t first_step, double beta1, double beta2, double eps, double weight_decay,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!descs || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
+        first_step < 1)
+        return QHEA_EINVAL;
+    for (int64_t m = 0; m < n_models; ++m) {
+        const qhea_member_hparams& h = members[m];
+        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
+        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;
+        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;
+    }
+    QubitSet qs;
+    const int rc0 = qubit_set(descs, n_models, qs);
+    if (rc0 != QHEA_OK) return rc0;
+    if (grad_stride < qs.pmax + 2) return QHEA_EINVAL;
+    int64_t bmax = 0;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
+        bmax = std::max(bmax, row_begin[i + 1] - row_begin[i]);
+    }
+    const bool qn = descs[0].model == QHEA_MODEL_QUANONET;
+    if (qn && !trunk) return QHEA_EINVAL;
+    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    QubitPlan plan;
+    qubit_plan(qs, bmax, plan);
+    const size_t slice = qubit_slice_bytes(qs, bmax, plan.list_bytes);     // (every region grows with the batch)
+    if (!workspace || slice == 0 || workspace_bytes < (size_t)n_models * slice) return QHEA_EWORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    const int64_t rows = row_begin[n_steps];                        // rows per member
+    const int64_t diag_stride = (int64_t)1 << qs.nmax;
+    if (qs.n_wave > 0) {
+        // every member's read-out, scale, learning rate, block counts and n reach its MemberRec, the work lists the slices'
+        // list regions
+        for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
+            const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
+            MemberFillQubit f{};
+            for (int i = 0; i < cnt; ++i) {
+                f.h[i] = members[m0 + i];
+                f.depth[i][0] = qs.mem[m0 + i].c[0]; f.depth[i][1] = qs.mem[m0 + i].c[1];
+                f.nq[i] = qs.mem[m0 + i].mi.n;
+            }
+            hipLaunchKernelGGL(member_fill_kernel<MemberFillQubit>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice,
+                               (long)slice, ham_diag ? ham_diag + m0 * diag_stride : nullptr, (long)diag_stride);
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        }
+        char* list0 = ws + kHeaderBytes;                             // (QubitLayout::off_list)
+        for (int k0 = 0; k0 < (int)plan.e.size(); k0 += kWorkFill) {
+            const int cnt = std::min<int>(kWorkFill, (int)plan.e.size() - k0);
+            WorkFill f{};
+            for (int i = 0; i < cnt; ++i) f.e[i] = plan.e[k0 + i];
+            hipLaunchKernelGGL(work_fill_kernel, dim3(1), dim3(kWorkFill), 0, st, f, cnt, k0, list0, (long)slice, plan.per);
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        }
+        const MemberStride ms{(long)rows, (long)qs.pmax, (long)(n_steps * grad_stride), (long)slice};
+        const char* mrec = ws + kMemberRecOffset;
+        QubitBwdArgs qa{};
+        for (int n = 2; n <= 9; ++n) {                              // two runs of fixed (enc = n, ld); the counts are the members'
+            Runs& r = qa.runs[n - 2];
+            r.nruns = 2;
+            r.enc[0] = r.enc[1] = n;
+            r.ld[0] = qs.dr.ld0; r.ld[1] = qs.dr.ld1;
+        }
+        const qhea_model_desc& d0 = descs[0];
+        const ModelInfo& mi0 = qs.mem[0].mi;
+        for (int64_t i = 0; i < n_steps; ++i) {
+            const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
+            const QubitLayout L = qubit_layout(qs, nb, plan.list_bytes);
+            const EncDesc enc = make_enc(&d0, mi0, branch + r0 * d0.branch_in, qn ? trunk + r0 * d0.trunk_in : nullptr, params);
+            long prep_total = 0;
+            for (const QubitMember& q : qs.mem)
+                if (q.wave) prep_total = std::max(prep_total, (long)(q.d.blk + 2) * q.mi.n + (long)nb * q.d.E);
+            hipLaunchKernelGGL(prep_model_qubit_kernel, dim3((unsigned)((prep_total + 255) / 256), (unsigned)n_models), dim3(256), 0,
+                               st, qs.dr, (const double*)params, reinterpret_cast<double4*>(ws + L.off_U), (long)nb, enc,
+                               reinterpret_cast<double2*>(ws + L.off_cs), reinterpret_cast<WorkspaceHeader*>(ws), mrec, ms);
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+            double* gx = reinterpret_cast<double*>(ws + L.off_gx);
+            double* pr = reinterpret_cast<double*>(ws + L.off_pred);
+            double* partial = reinterpret_cast<double*>(ws + L.off_part);
+            qa.B = nb; qa.inv_bt = inv_batch_total[i];
+            qa.cs = reinterpret_cast<const double2*>(ws + L.off_cs); qa.gates = ws + L.off_U;
+            qa.y = y + r0; qa.bias = qn ? params : nullptr;
+            qa.out = pr; qa.grad_x = gx; qa.partial = partial;
+            qa.mrec = mrec; qa.ms = ms;
+            profile_begin(st);
+            for (int c = 0; c < kQsClasses; ++c) {                  // one launch per register class present
+                if (plan.cls_count[c] == 0) continue;
+                qa.wk = QsWork{ws + L.off_list, plan.per, plan.cls_begin[c]};
+                const dim3 grid((unsigned)plan.cls_count[c]);
+                if (c == 0) launch_bwd_qsweep_0(grid, st, qa);
+                else launch_bwd_qsweep_1(grid, st, qa);
+            }
+            for (int n = kQsOwnLo; n <= kQsOwnHi; ++n) {            // n = 7..9: one launch per n present, member = blockIdx.y
+                const int cnt = plan.own_count[n - kQsOwnLo];
+                if (cnt == 0) continue;
+                const long nw = qs_nwaves(n, nb);
+                Runs runs{};
+                runs.nruns = 2;
+                runs.enc[0] = runs.enc[1] = n;
+                runs.ld[0] = qs.dr.ld0; runs.ld[1] = qs.dr.ld1;
+                const BwdArgs ba{runs, (long)nb, 0, 0, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U, 0, 0.0, 0.0,
+                                 nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr, inv_batch_total[i], pr, gx, partial,
+                                 QHEA_PAULI_Z, 0, cnt * nw > simd_count() ? 1 : 0, nullptr};
+                const QubitArgs q{mrec, ms, QsWork{ws + L.off_list, plan.per, plan.own_begin[n - kQsOwnLo]}};
+                const dim3 grid((unsigned)(nw / kWaves), (unsigned)cnt);
+                switch (n) {
+#define QHEA_CASE(NN) case NN: launch_bwd_qubit_##NN(grid, st, ba, q); break;
+                    QHEA_FOR_EACH_N(QHEA_CASE)
+#undef QHEA_CASE
+                    default: return QHEA_EUNSUPPORTED;
+                }
+            }
+            profile_end(st);
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+            const int64_t step = first_step + i;
+            const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+            const AdamArgs adam{params, exp_avg, exp_avg_sq, members[0].lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+            GradMap gm{};
+            gm.off_ans = mi0.off_ans; gm.off_bias = mi0.off_bias; gm.off_sse = mi0.P;
+            for (int s = 0; s < 2; ++s) { gm.off_w[s] = mi0.off_w[s]; gm.off_b[s] = mi0.off_b[s]; }
+            hipLaunchKernelGGL((reduce_model_kernel<false, false, true, QubitRed>), dim3((unsigned)plan.red_count), dim3(kRedThreads), 0,
+                               st, mi0.n, (int)mi0.sh.blk, padded_3n(mi0.n), 0L, (const double*)partial, (const double*)params,
+                               (long)nb, (int)mi0.sh.E, enc, (const double*)gx, (const double*)pr, y + r0, inv_batch_total[i], gm, 0, 0,
+                               grad + i * grad_stride, adam, reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr,
+                               FusePrep{}, DpX{}, ms, MemberLr{mrec, bc1},
+                               QubitRed{qs.dr, QsWork{ws + L.off_list, plan.per, plan.red_begin}});
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        }
+    }
+    // n >= 10 (workgroup-resident kernels): one member after the other, each on its own descriptor and slice; its status word
+    // is folded into slice 0's
+    for (int64_t m = 0; m < n_models; ++m) {
+        if (qs.mem[m].wave) continue;
+        const qhea_model_desc dm = member_desc(descs[m], members[m]);
+        char* wm = ws + m * slice;
+        const int rc = qhea_model_train_steps(&dm, n_steps, row_begin, branch + m * rows * dm.branch_in,
+                                              qn ? trunk + m * rows * dm.trunk_in : nullptr, y + m * rows,
+                                              params + m * qs.pmax, ham_diag ? ham_diag + m * diag_stride : nullptr,
+                                              inv_batch_total, grad + m * n_steps * grad_stride, grad_stride,
+                                              exp_avg + m * qs.pmax, exp_avg_sq + m * qs.pmax, first_step, members[m].lr,
+                                              beta1, beta2, eps, weight_decay, wm, slice, stream);
+        if (rc != QHEA_OK) return rc;
+        if (m > 0) {
+            hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
+                               reinterpret_cast<WorkspaceHeader*>(wm));
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        }
     }
     return QHEA_OK;
 }

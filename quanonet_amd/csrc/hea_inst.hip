@@ -2,6 +2,7 @@
 // (compile with -DQHEA_N=<n>; one object per n keeps the build parallel).
 #include "hea_device.hpp"
 #include "hea_zyz.hpp"
+#include "hea_qsweep.hpp"
 
 #ifndef QHEA_N
 #error "compile with -DQHEA_N=<qubits>"
@@ -41,6 +42,26 @@ void QHEA_CAT(launch_bwd_depth_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArg
     hipLaunchKernelGGL((bwd_kernel<QHEA_N, 1, DepthArgs>), grid, dim3(kWaves * 64), 0, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates,
                        a.gates_bytes, a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x,
                        a.partial, DepthArgs{mrec, ms});
+}
+
+// qubit sweeps, n = 7..9: member = the list entry blockIdx.y (hea_qsweep.hpp: QubitArgs); dense as for the single-model kernel.
+// (No kernel for the other n: their members run in the class kernels of hea_qsweep.hip.)
+void QHEA_CAT(launch_bwd_qubit_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArgs& a, const QubitArgs& q) {
+#if QHEA_N >= 7
+#if QHEA_N == 8 || QHEA_N == 9
+    if (a.dense) {
+        hipLaunchKernelGGL((bwd_kernel<QHEA_N, 2, QubitArgs>), grid, dim3(kWaves * 64), 0, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates,
+                           a.gates_bytes, a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out,
+                           a.grad_x, a.partial, q);
+        return;
+    }
+#endif
+    hipLaunchKernelGGL((bwd_kernel<QHEA_N, 1, QubitArgs>), grid, dim3(kWaves * 64), 0, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates,
+                       a.gates_bytes, a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x,
+                       a.partial, q);
+#else
+    (void)grid; (void)st; (void)a; (void)q;
+#endif
 }
 
 void QHEA_CAT(launch_bwd_pair_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArgs& a) {

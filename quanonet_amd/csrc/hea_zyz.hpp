@@ -737,7 +737,8 @@ struct MemberRec {
     double lr;                  // Adam learning rate (the reduce kernel divides by the step's bias correction)
     const double* diag;         // the member's diagonal Hamiltonian, or nullptr
     int pauli;                  // QHEA_PAULI_*
-    int pad;
+    int nq;                     // qubit sweeps (qhea_model_qubit_sweep_train_steps): the member's qubit count; 0 in the other
+                                // member launches
     int depth[2];               // depth sweeps (qhea_model_depth_sweep_train_steps): the member's block counts of run 0 and
                                 // run 1 (QuanONet: trunk, branch; HEAQNN: its blocks, 0); 0 in the other member launches
 };
