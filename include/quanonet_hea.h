@@ -372,8 +372,10 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
  * step i); all members share the schedule row_begin / inv_batch_total, the step count and the hyper-parameters.
  * Results are bitwise those of n_models qhea_model_train_steps calls, one per member, made under the backward variant the
  * ensemble chose: the kernels are chosen as for ONE batch of n_models x B rows (qhea_set_backward_variant applies).
- * Shapes the n <= 5 ZYZ kernels do not take (n >= 6, first-generation variants, shapes not eligible) run as n_models
- * consecutive qhea_model_train_steps calls on the same stream, one workspace slice each.  An overrun in any member is
+ * n >= 10 (n_models > 1): one launch per kernel too, the member form of the workgroup-resident backward kernel (one
+ * workgroup per sample and member).  Other shapes the n <= 5 ZYZ kernels do not take (n = 6..9, first-generation variants,
+ * shapes not eligible) run as n_models consecutive qhea_model_train_steps calls on the same stream, one workspace slice
+ * each.  An overrun in any member is
  * reported by qhea_check_status on this workspace.  Workspace: qhea_model_ensemble_workspace_bytes for every batch size
  * of the schedule (the largest of those).  Bytes 64..111 of every member's slice hold that member's hyper-parameters for the
  * one-launch path (written by the call itself; qhea_model_sweep_train_steps below).
@@ -402,7 +404,8 @@ int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_model
  * stays hipGraph-capturable.  Results: member m's are bitwise those of qhea_model_train_steps with m's descriptor (desc with
  * m's scale, offset, coeff, Pauli), lr = members[m].lr and ham_diag + m * 2^n, under the backward variant the sweep chose:
  * the kernels are chosen as for ONE batch of n_models x B rows, and as for an X / Y model if any member reads out X or Y.
- * Shapes outside the one-launch path run as n_models consecutive qhea_model_train_steps calls with the members' descriptors.
+ * n >= 10 takes the one-launch path of the workgroup-resident kernels as in qhea_model_ensemble_train_steps; other shapes
+ * outside the one-launch path run as n_models consecutive qhea_model_train_steps calls with the members' descriptors.
  */
 typedef struct qhea_member_hparams {
     double  scale_coeff;            /* the member's fixed encoding scale (trainable_freq == 0); ignored otherwise */
@@ -438,7 +441,8 @@ int qhea_model_sweep_train_steps(const qhea_model_desc* desc, int64_t n_models,
  * n <= 9: every step is one launch per kernel (member = the grid's second dimension) of the first-generation kernels with the
  * packed backward, at any batch; member m's results are bitwise those of qhea_model_train_steps with m's sweep descriptor
  * (descs[m] with members[m]'s read-out and scale), lr = members[m].lr and ham_diag + m * 2^n under QHEA_BWD_PACKED.
- * n >= 10: n_models consecutive qhea_model_train_steps calls with those descriptors.  Workspace:
+ * n >= 10: the same, with the member form of the workgroup-resident backward kernel (one workgroup per sample and member).
+ * Workspace:
  * qhea_model_depth_sweep_workspace_bytes for every batch size of the schedule (the largest of those); an overrun of any member
  * is reported by qhea_check_status on it.
  */
@@ -465,7 +469,8 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs /*HOST [n_mo
  * Members with n <= 9 share every step's launches: one prep launch, one backward launch per register class present (n = 2;
  * n = 3..6) whose workgroups take (member, sample group) from a work list and one per n = 7, 8, 9 present, one reduce launch
  * over every member's own roles.
- * Members with n >= 10 then train one after another, each with qhea_model_train_steps on its own slice.  Workspace:
+ * Members with n >= 10 share them too: one backward launch per n = 10, 11, 12 present (the workgroup-resident kernel, one
+ * workgroup per sample and member, longest chain first); their roles are in the one reduce launch.  Workspace:
  * qhea_model_qubit_sweep_workspace_bytes for the largest batch of the schedule; an overrun of any member is reported by
  * qhea_check_status on it.
  */

@@ -920,7 +920,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             if constexpr (QS) {                         // the member's own qubit count
                 n = ((ConstMemberRec)mr)->nq;
                 kw = padded_3n(n);
-                nwaves = qs_nwaves(n, B);
+                nwaves = qs_part_rows(n, B);
             }
             if constexpr (DEPTH) {
                 const DepthRed dr = dr_of((dr_pack, ...));
@@ -1167,7 +1167,7 @@ __global__ void prep_model_depth_kernel(int n, DepthRed dr, const double* __rest
 }
 
 // Qubit sweeps: prep_model_depth_kernel for members of different n -- member blockIdx.y's n is its MemberRec::nq.  The grid is
-// sized for the largest member; members with n >= 10 (trained on their own after the sweep's launches) write nothing.
+// sized for the largest member.  The workgroup-resident kernels (n >= 10) read the same tables as the wave-resident ones.
 __global__ void prep_model_qubit_kernel(DepthRed dr, const double* __restrict__ params, double4* __restrict__ gates,
                                         long B, EncDesc enc, double2* __restrict__ cs, WorkspaceHeader* hdr, const char* mrec,
                                         MemberStride ms) {
@@ -1176,7 +1176,6 @@ __global__ void prep_model_qubit_kernel(DepthRed dr, const double* __restrict__ 
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid == 0 && m == 0) header_init(hdr);
     const int n = mr->nq;
-    if (n > 9) return;
     const DepthMap d = depth_map(n, dr.quanonet != 0, dr.trainable != 0, mr->depth[0], mr->depth[1], dr.ld0, dr.ld1);
     const double* __restrict__ p = params + m * ms.params;
     const long ng = (long)(d.blk + 2) * n;
@@ -1384,7 +1383,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 480; }
+int qhea_version(void) { return 490; }
 
 const char* qhea_strerror(int code) {
     switch (code) {
@@ -1897,6 +1896,12 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
 // qhea_model_ensemble_train_steps and qhea_model_sweep_train_steps: R members of one shape, member m with hyper-parameters hp(m)
 // (hp_fn(ctx, m)) and diagonal Hamiltonian diag0 + m * diag_stride (diag0 == nullptr: none).  The arguments have been checked by the caller.
 typedef qhea_member_hparams (*MemberHp)(const void* ctx, int64_t m);
+static int members_lds_grid(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models, MemberHp hp_fn, const void* ctx,
+                            const double* diag0, int64_t diag_stride, int64_t n_steps, const int64_t* row_begin,
+                            const double* branch, const double* trunk, const double* y, double* params,
+                            const double* inv_batch_total, double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                            int64_t first_step, double beta1, double beta2, double eps, double weight_decay, char* ws, size_t slice,
+                            hipStream_t st);
 static int members_train_steps(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models, MemberHp hp_fn, const void* ctx,
                         const double* diag0,
                         int64_t diag_stride, int64_t n_steps, const int64_t* row_begin, const double* branch, const double* trunk,
@@ -1905,7 +1910,7 @@ static int members_train_steps(const qhea_model_desc* desc, const ModelInfo& mi,
                         double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
     auto hp = [&](int64_t m) { return hp_fn(ctx, m); };
     // one slice per member, sized for every batch size of the schedule; one launch per kernel where every step runs the ZYZ
-    // kernels, R consecutive single-model calls otherwise
+    // kernels or (n >= 10) the workgroup-resident ones, R consecutive single-model calls otherwise (n = 6..9)
     size_t slice = 0;
     bool grid = true;
     for (int64_t i = 0; i < n_steps; ++i) {
@@ -1919,6 +1924,12 @@ static int members_train_steps(const qhea_model_desc* desc, const ModelInfo& mi,
     char* ws = static_cast<char*>(workspace);
     const int64_t rows = row_begin[n_steps];                        // rows per member
     const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
+    if (!grid && n_models > 1 && lds_supported(mi.n)) {
+        const int rc = members_lds_grid(desc, mi, n_models, hp_fn, ctx, diag0, diag_stride, n_steps, row_begin, branch, trunk, y,
+                                        params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2,
+                                        eps, weight_decay, ws, slice, st);
+        if (rc != QHEA_EUNSUPPORTED) return rc;                   // (unsupported: found before anything was launched)
+    }
     if (!grid) {
         for (int64_t m = 0; m < n_models; ++m) {
             char* wm = ws + m * slice;
@@ -2091,13 +2102,13 @@ static void depth_counts(const qhea_model_desc& d, int32_t (&c)[2]) {
     c[1] = qn ? d.net[0] : 0;
 }
 // One member's slice for `batch` rows (the largest member's shape): header (MemberRec at kMemberRecOffset), gate table, (cos, sin)
-// table, partial rows of the packed backward kernel, grad_x, predictions -- the first-generation single-model layout under
-// QHEA_BWD_PACKED
+// table, partial rows of the backward kernel, grad_x, predictions -- the first-generation single-model layout under
+// QHEA_BWD_PACKED (n >= 10: the workgroup-resident kernel's, one partial row per sample)
 struct DepthLayout { size_t off_U, off_cs, off_part, off_gx, off_pred, total; long nwaves; };
 static DepthLayout depth_layout(const ModelInfo& env, int64_t B) {
     DepthLayout L{};
     const int n = env.n, spw = 64 >> lane_bits(n);
-    L.nwaves = (((B + spw - 1) / spw + kWaves - 1) / kWaves) * kWaves;
+    L.nwaves = lds_supported(n) ? (long)B : (((B + spw - 1) / spw + kWaves - 1) / kWaves) * kWaves;
     size_t p = kHeaderBytes;
     L.off_U = p;    p = align_up(p + (size_t)(env.sh.blk + 2) * n * kGateBytes);
     L.off_cs = p;   p = align_up(p + (size_t)B * env.sh.E * sizeof(double2));
@@ -2107,92 +2118,33 @@ static DepthLayout depth_layout(const ModelInfo& env, int64_t B) {
     L.total = p;
     return L;
 }
-// n >= 10 (workgroup-resident kernels): the members run one after the other, each on its own single-model layout
-static size_t depth_slice_bytes(const qhea_model_desc* descs, int64_t R, const DepthSet& ds, int64_t batch) {
-    if (!lds_supported(ds.env_mi.n)) return depth_layout(ds.env_mi, batch).total;
-    size_t slice = 0;
-    for (int64_t m = 0; m < R; ++m) {
-        qhea_model_desc dz = descs[m];
-        dz.ham_pauli = QHEA_PAULI_Z;
-        ModelInfo mi;
-        if (model_info(&dz, mi) != QHEA_OK) return 0;
-        const size_t b = make_model_layout(mi, batch).total;
-        if (b > slice) slice = b;
-    }
-    return slice;
-}
+static size_t depth_slice_bytes(const DepthSet& ds, int64_t batch) { return depth_layout(ds.env_mi, batch).total; }
 
-size_t qhea_model_depth_sweep_workspace_bytes(const qhea_model_desc* descs, int64_t n_models, int64_t batch) {
-    DepthSet ds;
-    if (depth_set(descs, n_models, ds) != QHEA_OK || batch < 0) return 0;
-    return (size_t)n_models * depth_slice_bytes(descs, n_models, ds, batch);
-}
-
-int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_models, const qhea_member_hparams* members,
-                                       const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
-                                       const double* trunk, const double* y, double* params, const double* inv_batch_total,
-                                       double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
-                                       int64_t first_step, double beta1, double beta2, double eps, double weight_decay,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (!descs || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
-        first_step < 1)
-        return QHEA_EINVAL;
-    for (int64_t m = 0; m < n_models; ++m) {
-        const qhea_member_hparams& h = members[m];
-        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
-        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;
-        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;
-    }
-    DepthSet ds;
-    const int rc0 = depth_set(descs, n_models, ds);
-    if (rc0 != QHEA_OK) return rc0;
+// One grid per kernel and step for R members of one model kind, n and run lengths whose block counts may differ (ds: their
+// envelope, DepthSet): depth sweeps, and ensembles / sweeps at n >= 10, whose members share one shape.  Member m's block counts
+// are those of descs[m * desc_step] (desc_step 0: one descriptor for all), its hyper-parameters hp_fn(hp_ctx, m), its diagonal
+// Hamiltonian diag0 + m * diag_stride.  n <= 9: the packed backward kernel's member form; n >= 10: the workgroup-resident one's.
+// The arguments and the slice size (>= depth_slice_bytes for every batch of the schedule) have been checked by the caller.
+static int depth_grid_steps(const DepthSet& ds, int64_t n_models, const qhea_model_desc* descs, int64_t desc_step, MemberHp hp_fn,
+                            const void* hp_ctx, const double* diag0, int64_t diag_stride, int64_t n_steps, const int64_t* row_begin,
+                            const double* branch, const double* trunk, const double* y, double* params,
+                            const double* inv_batch_total, double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                            int64_t first_step, double beta1, double beta2, double eps, double weight_decay, char* ws, size_t slice,
+                            hipStream_t st) {
     const ModelInfo& env = ds.env_mi;
-    if (grad_stride < ds.pmax + 2) return QHEA_EINVAL;
-    for (int64_t i = 0; i < n_steps; ++i)
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
     const bool qn = ds.env.model == QHEA_MODEL_QUANONET;
-    if (qn && !trunk) return QHEA_EINVAL;
-    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    size_t slice = 0;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const size_t b = depth_slice_bytes(descs, n_models, ds, row_begin[i + 1] - row_begin[i]);
-        if (b > slice) slice = b;
-    }
-    if (!workspace || slice == 0 || workspace_bytes < (size_t)n_models * slice) return QHEA_EWORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
     const int64_t rows = row_begin[n_steps];                        // rows per member
-    const int64_t diag_stride = (int64_t)1 << env.n;
-    if (lds_supported(env.n)) {                                      // one member after the other, each on its own descriptor
-        for (int64_t m = 0; m < n_models; ++m) {
-            const qhea_model_desc dm = member_desc(descs[m], members[m]);
-            char* wm = ws + m * slice;
-            const int rc = qhea_model_train_steps(&dm, n_steps, row_begin, branch + m * rows * dm.branch_in,
-                                                  qn ? trunk + m * rows * dm.trunk_in : nullptr, y + m * rows,
-                                                  params + m * ds.pmax, ham_diag ? ham_diag + m * diag_stride : nullptr,
-                                                  inv_batch_total, grad + m * n_steps * grad_stride, grad_stride,
-                                                  exp_avg + m * ds.pmax, exp_avg_sq + m * ds.pmax, first_step, members[m].lr,
-                                                  beta1, beta2, eps, weight_decay, wm, slice, stream);
-            if (rc != QHEA_OK) return rc;
-            if (m > 0) {
-                hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
-                                   reinterpret_cast<WorkspaceHeader*>(wm));
-                if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-            }
-        }
-        return QHEA_OK;
-    }
     // One grid per kernel and step, member = blockIdx.y: every member's read-out, scale, learning rate and block counts reach
     // its MemberRec first
     for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
         const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
         MemberFillDepth f{};
         for (int i = 0; i < cnt; ++i) {
-            f.h[i] = members[m0 + i];
-            depth_counts(descs[m0 + i], f.depth[i]);
+            f.h[i] = hp_fn(hp_ctx, m0 + i);
+            depth_counts(descs[(m0 + i) * desc_step], f.depth[i]);
         }
         hipLaunchKernelGGL(member_fill_kernel<MemberFillDepth>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
-                           ham_diag ? ham_diag + m0 * diag_stride : nullptr, (long)diag_stride);
+                           diag0 ? diag0 + m0 * diag_stride : nullptr, (long)diag_stride);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
     }
     // the reduce grid: the most blocks any member's roles need (ansatz blocks, frequency blocks, the sse / bias block)
@@ -2200,7 +2152,7 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
     int red_blocks = 0;
     for (int64_t m = 0; m < n_models; ++m) {
         int32_t c[2];
-        depth_counts(descs[m], c);
+        depth_counts(descs[m * desc_step], c);
         const DepthMap d = depth_map(n, qn, ds.dr.trainable != 0, c[0], c[1], ds.dr.ld0, ds.dr.ld1);
         const int nb = (d.blk * kw + red_cols(kw) - 1) / red_cols(kw) + (ds.dr.trainable ? (d.E + kFreqCols - 1) / kFreqCols : 0) + 1;
         if (nb > red_blocks) red_blocks = nb;
@@ -2230,7 +2182,10 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
                          nullptr};
         const dim3 grid((unsigned)(L.nwaves / kWaves), (unsigned)n_models);
         profile_begin(st);
-        switch (n) {
+        if (lds_supported(n)) {                          // one workgroup per (sample, member)
+            const int rc = launch_lds_bwd_depth(n, dim3((unsigned)nb, (unsigned)n_models), st, ba, DepthArgs{mrec, ms});
+            if (rc != QHEA_OK) return rc;
+        } else switch (n) {
 #define QHEA_CASE(NN) case NN: launch_bwd_depth_##NN(grid, st, ba, mrec, ms); break;
             QHEA_FOR_EACH_N(QHEA_CASE)
 #undef QHEA_CASE
@@ -2240,7 +2195,7 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
         const int64_t step = first_step + i;
         const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, members[0].lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+        const AdamArgs adam{params, exp_avg, exp_avg_sq, hp_fn(hp_ctx, 0).lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
         GradMap gm{};
         gm.off_ans = env.off_ans; gm.off_bias = env.off_bias; gm.off_sse = env.P;
         for (int s = 0; s < 2; ++s) { gm.off_w[s] = env.off_w[s]; gm.off_b[s] = env.off_b[s]; }
@@ -2255,22 +2210,92 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
     return QHEA_OK;
 }
 
+// Ensembles and sweeps at n >= 10 (members_train_steps, R > 1): a depth sweep whose members all have the descriptor's block
+// counts.  Its slices are the ensemble's (the single-model layout, which depth_layout reproduces).  QHEA_EUNSUPPORTED before
+// any launch when the shape has no depth-sweep form.
+static int members_lds_grid(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models, MemberHp hp_fn, const void* ctx,
+                            const double* diag0, int64_t diag_stride, int64_t n_steps, const int64_t* row_begin,
+                            const double* branch, const double* trunk, const double* y, double* params,
+                            const double* inv_batch_total, double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                            int64_t first_step, double beta1, double beta2, double eps, double weight_decay, char* ws, size_t slice,
+                            hipStream_t st) {
+    const bool qn = desc->model == QHEA_MODEL_QUANONET;
+    DepthSet ds;
+    ds.env = *desc;
+    ds.env.ham_pauli = QHEA_PAULI_Z;
+    if (model_info(&ds.env, ds.env_mi) != QHEA_OK) return QHEA_EUNSUPPORTED;
+    ds.pmax = mi.P;
+    int32_t c[2];
+    depth_counts(*desc, c);
+    ds.c_max[0] = c[0]; ds.c_max[1] = c[1];
+    ds.dr = DepthRed{qn ? 1 : 0, desc->trainable_freq != 0 ? 1 : 0, qn ? desc->net[3] : desc->net[1], qn ? desc->net[1] : 0};
+    if (depth_map(mi.n, qn, mi.trainable, c[0], c[1], ds.dr.ld0, ds.dr.ld1).P != mi.P) return QHEA_EUNSUPPORTED;
+    for (int64_t i = 0; i < n_steps; ++i)
+        if (depth_slice_bytes(ds, row_begin[i + 1] - row_begin[i]) > slice) return QHEA_EUNSUPPORTED;
+    return depth_grid_steps(ds, n_models, desc, 0, hp_fn, ctx, diag0, diag_stride, n_steps, row_begin, branch, trunk, y, params,
+                            inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, ws,
+                            slice, st);
+}
+
+size_t qhea_model_depth_sweep_workspace_bytes(const qhea_model_desc* descs, int64_t n_models, int64_t batch) {
+    DepthSet ds;
+    if (depth_set(descs, n_models, ds) != QHEA_OK || batch < 0) return 0;
+    return (size_t)n_models * depth_slice_bytes(ds, batch);
+}
+
+int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_models, const qhea_member_hparams* members,
+                                       const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
+                                       const double* trunk, const double* y, double* params, const double* inv_batch_total,
+                                       double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                                       int64_t first_step, double beta1, double beta2, double eps, double weight_decay,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!descs || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
+        first_step < 1)
+        return QHEA_EINVAL;
+    for (int64_t m = 0; m < n_models; ++m) {
+        const qhea_member_hparams& h = members[m];
+        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
+        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;
+        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;
+    }
+    DepthSet ds;
+    const int rc0 = depth_set(descs, n_models, ds);
+    if (rc0 != QHEA_OK) return rc0;
+    const ModelInfo& env = ds.env_mi;
+    if (grad_stride < ds.pmax + 2) return QHEA_EINVAL;
+    for (int64_t i = 0; i < n_steps; ++i)
+        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
+    const bool qn = ds.env.model == QHEA_MODEL_QUANONET;
+    if (qn && !trunk) return QHEA_EINVAL;
+    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    size_t slice = 0;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const size_t b = depth_slice_bytes(ds, row_begin[i + 1] - row_begin[i]);
+        if (b > slice) slice = b;
+    }
+    if (!workspace || slice == 0 || workspace_bytes < (size_t)n_models * slice) return QHEA_EWORKSPACE;
+    return depth_grid_steps(ds, n_models, descs, 1, [](const void* c, int64_t m) { return static_cast<const qhea_member_hparams*>(c)[m]; },
+                            members, ham_diag, (int64_t)1 << env.n, n_steps, row_begin, branch, trunk, y, params, inv_batch_total,
+                            grad, grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay,
+                            static_cast<char*>(workspace), slice, static_cast<hipStream_t>(stream));
+}
+
 // ---- qubit sweeps (qhea_model_qubit_sweep_train_steps) ----
 // The members' descriptors: every field but n_qubits and the depths equal to member 0's, each one valid on its own (its ham_*
-// and scale fields are not used: read with a Z read-out).  Members with n <= 9 are wave-resident: they share the sweep's
-// launches; members with n >= 10 train one after the other on their own layouts.
+// and scale fields are not used: read with a Z read-out).  Members with n <= 9 run the wave-resident kernels, members with
+// n >= 10 the workgroup-resident ones (hea_lds.hip); every member shares the sweep's launches.
 struct QubitMember {
     ModelInfo mi;
     int32_t c[2];               // block counts of run 0 / run 1 (MemberRec::depth)
     DepthMap d;
     bool wave;                  // n <= 9
-    double cost;                // length of the backward chain of one sample group (sub-layers x gates x amplitudes per lane)
+    double cost;                // length of the backward chain of one sample group (sub-layers x gates x amplitudes per lane;
+                                // n >= 10: per thread of the sample's workgroup, up to a constant)
 };
 struct QubitSet {
     std::vector<QubitMember> mem;
     int64_t pmax = 0;
     int nmax = 0;
-    int n_wave = 0;
     DepthRed dr{};
 };
 static int qubit_set(const qhea_model_desc* descs, int64_t R, QubitSet& qs) {
@@ -2299,17 +2324,19 @@ static int qubit_set(const qhea_model_desc* descs, int64_t R, QubitSet& qs) {
         q.cost = (double)q.d.blk * n * (double)(1 << (n - lane_bits(n)));
         if (q.mi.P > qs.pmax) qs.pmax = q.mi.P;
         if (n > qs.nmax) qs.nmax = n;
-        qs.n_wave += q.wave ? 1 : 0;
     }
     return QHEA_OK;
 }
 // Work lists for a schedule whose largest batch is Bmax: per register class its members' (member, sample group) entries, the
 // longest chain first (a short batch's launch skips the groups past its last sample); per n = 7..9 its members (member, 0);
-// then every member's reduce roles (ansatz blocks, frequency blocks, the sse / bias block) as (member, role).
+// per n = 10..12 its members (member, 0), the longest chain first; then every member's reduce roles (ansatz blocks, frequency
+// blocks, the sse / bias block) as (member, role).
+constexpr int kQsLdsLo = 10, kQsLdsHi = 12;     // workgroup-resident members: one launch per n, member = entry blockIdx.y
 struct QubitPlan {
     std::vector<int2> e;
     int cls_begin[kQsClasses] = {0, 0}, cls_count[kQsClasses] = {0, 0};
     int own_begin[kQsOwnHi - kQsOwnLo + 1] = {0, 0, 0}, own_count[kQsOwnHi - kQsOwnLo + 1] = {0, 0, 0};   // n = 7..9: (member, 0)
+    int lds_begin[kQsLdsHi - kQsLdsLo + 1] = {0, 0, 0}, lds_count[kQsLdsHi - kQsLdsLo + 1] = {0, 0, 0};   // n = 10..12: (member, 0)
     int red_begin = 0, red_count = 0;
     int per = 1;                // entries per slice
     size_t list_bytes = 0;
@@ -2338,28 +2365,34 @@ static void qubit_plan(const QubitSet& qs, int64_t Bmax, QubitPlan& P) {
             if (qs.mem[m].wave && qs.mem[m].mi.n == n) P.e.push_back(make_int2((int)m, 0));
         P.own_count[n - kQsOwnLo] = (int)P.e.size() - P.own_begin[n - kQsOwnLo];
     }
+    for (int n = kQsLdsLo; n <= kQsLdsHi; ++n) {
+        std::vector<int> ms;
+        for (int64_t m = 0; m < R; ++m)
+            if (qs.mem[m].mi.n == n) ms.push_back((int)m);
+        std::stable_sort(ms.begin(), ms.end(), [&](int a, int b) { return qs.mem[a].cost > qs.mem[b].cost; });
+        P.lds_begin[n - kQsLdsLo] = (int)P.e.size();
+        for (int m : ms) P.e.push_back(make_int2(m, 0));
+        P.lds_count[n - kQsLdsLo] = (int)P.e.size() - P.lds_begin[n - kQsLdsLo];
+    }
     P.red_begin = (int)P.e.size();
     for (int64_t m = 0; m < R; ++m)
-        if (qs.mem[m].wave)
-            for (int r = 0, nr = red_roles(qs.mem[m], qs.dr.trainable != 0); r < nr; ++r) P.e.push_back(make_int2((int)m, r));
+        for (int r = 0, nr = red_roles(qs.mem[m], qs.dr.trainable != 0); r < nr; ++r) P.e.push_back(make_int2((int)m, r));
     P.red_count = (int)P.e.size() - P.red_begin;
     P.per = (int)(((int64_t)P.e.size() + R - 1) / R);
     if (P.per < 1) P.per = 1;
     P.list_bytes = (size_t)P.per * sizeof(int2);
 }
 // One member's slice for `batch` rows: header (MemberRec at kMemberRecOffset), list region, then the depth sweep's regions --
-// gate table, (cos, sin) table, partial rows of the packed backward kernel, grad_x, predictions -- each sized for the largest
-// wave-resident member's, so that every member's lie at the same offsets.  At least a single-model layout of every n >= 10
-// member.
+// gate table, (cos, sin) table, partial rows of the member's backward kernel (qs_part_rows), grad_x, predictions -- each sized
+// for the largest member's, so that every member's lie at the same offsets.
 struct QubitLayout { size_t off_list, off_U, off_cs, off_part, off_gx, off_pred, total; };
 static QubitLayout qubit_layout(const QubitSet& qs, int64_t B, size_t list_bytes) {
     size_t u = 0, e = 0, part = 0;
     for (const QubitMember& q : qs.mem) {
-        if (!q.wave) continue;
         const int n = q.mi.n;
         u = std::max(u, (size_t)(q.d.blk + 2) * n * kGateBytes);
         e = std::max(e, (size_t)q.d.E);
-        part = std::max(part, (size_t)qs_nwaves(n, B) * q.d.blk * padded_3n(n) * sizeof(double));
+        part = std::max(part, (size_t)qs_part_rows(n, B) * q.d.blk * padded_3n(n) * sizeof(double));
     }
     QubitLayout L{};
     size_t p = kHeaderBytes;
@@ -2372,12 +2405,7 @@ static QubitLayout qubit_layout(const QubitSet& qs, int64_t B, size_t list_bytes
     L.total = p;
     return L;
 }
-static size_t qubit_slice_bytes(const QubitSet& qs, int64_t B, size_t list_bytes) {
-    size_t slice = qs.n_wave > 0 ? qubit_layout(qs, B, list_bytes).total : 0;
-    for (const QubitMember& q : qs.mem)
-        if (!q.wave) slice = std::max(slice, make_model_layout(q.mi, B).total);
-    return slice;
-}
+static size_t qubit_slice_bytes(const QubitSet& qs, int64_t B, size_t list_bytes) { return qubit_layout(qs, B, list_bytes).total; }
 
 size_t qhea_model_qubit_sweep_workspace_bytes(const qhea_model_desc* descs, int64_t n_models, int64_t batch) {
     QubitSet qs;
@@ -2422,122 +2450,115 @@ int qhea_model_qubit_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
     char* ws = static_cast<char*>(workspace);
     const int64_t rows = row_begin[n_steps];                        // rows per member
     const int64_t diag_stride = (int64_t)1 << qs.nmax;
-    if (qs.n_wave > 0) {
-        // every member's read-out, scale, learning rate, block counts and n reach its MemberRec, the work lists the slices'
-        // list regions
-        for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
-            const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
-            MemberFillQubit f{};
-            for (int i = 0; i < cnt; ++i) {
-                f.h[i] = members[m0 + i];
-                f.depth[i][0] = qs.mem[m0 + i].c[0]; f.depth[i][1] = qs.mem[m0 + i].c[1];
-                f.nq[i] = qs.mem[m0 + i].mi.n;
-            }
-            hipLaunchKernelGGL(member_fill_kernel<MemberFillQubit>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice,
-                               (long)slice, ham_diag ? ham_diag + m0 * diag_stride : nullptr, (long)diag_stride);
-            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    // every member's read-out, scale, learning rate, block counts and n reach its MemberRec, the work lists the slices'
+    // list regions
+    for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
+        const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
+        MemberFillQubit f{};
+        for (int i = 0; i < cnt; ++i) {
+            f.h[i] = members[m0 + i];
+            f.depth[i][0] = qs.mem[m0 + i].c[0]; f.depth[i][1] = qs.mem[m0 + i].c[1];
+            f.nq[i] = qs.mem[m0 + i].mi.n;
         }
-        char* list0 = ws + kHeaderBytes;                             // (QubitLayout::off_list)
-        for (int k0 = 0; k0 < (int)plan.e.size(); k0 += kWorkFill) {
-            const int cnt = std::min<int>(kWorkFill, (int)plan.e.size() - k0);
-            WorkFill f{};
-            for (int i = 0; i < cnt; ++i) f.e[i] = plan.e[k0 + i];
-            hipLaunchKernelGGL(work_fill_kernel, dim3(1), dim3(kWorkFill), 0, st, f, cnt, k0, list0, (long)slice, plan.per);
-            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        }
-        const MemberStride ms{(long)rows, (long)qs.pmax, (long)(n_steps * grad_stride), (long)slice};
-        const char* mrec = ws + kMemberRecOffset;
-        QubitBwdArgs qa{};
-        for (int n = 2; n <= 9; ++n) {                              // two runs of fixed (enc = n, ld); the counts are the members'
-            Runs& r = qa.runs[n - 2];
-            r.nruns = 2;
-            r.enc[0] = r.enc[1] = n;
-            r.ld[0] = qs.dr.ld0; r.ld[1] = qs.dr.ld1;
-        }
-        const qhea_model_desc& d0 = descs[0];
-        const ModelInfo& mi0 = qs.mem[0].mi;
-        for (int64_t i = 0; i < n_steps; ++i) {
-            const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
-            const QubitLayout L = qubit_layout(qs, nb, plan.list_bytes);
-            const EncDesc enc = make_enc(&d0, mi0, branch + r0 * d0.branch_in, qn ? trunk + r0 * d0.trunk_in : nullptr, params);
-            long prep_total = 0;
-            for (const QubitMember& q : qs.mem)
-                if (q.wave) prep_total = std::max(prep_total, (long)(q.d.blk + 2) * q.mi.n + (long)nb * q.d.E);
-            hipLaunchKernelGGL(prep_model_qubit_kernel, dim3((unsigned)((prep_total + 255) / 256), (unsigned)n_models), dim3(256), 0,
-                               st, qs.dr, (const double*)params, reinterpret_cast<double4*>(ws + L.off_U), (long)nb, enc,
-                               reinterpret_cast<double2*>(ws + L.off_cs), reinterpret_cast<WorkspaceHeader*>(ws), mrec, ms);
-            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-            double* gx = reinterpret_cast<double*>(ws + L.off_gx);
-            double* pr = reinterpret_cast<double*>(ws + L.off_pred);
-            double* partial = reinterpret_cast<double*>(ws + L.off_part);
-            qa.B = nb; qa.inv_bt = inv_batch_total[i];
-            qa.cs = reinterpret_cast<const double2*>(ws + L.off_cs); qa.gates = ws + L.off_U;
-            qa.y = y + r0; qa.bias = qn ? params : nullptr;
-            qa.out = pr; qa.grad_x = gx; qa.partial = partial;
-            qa.mrec = mrec; qa.ms = ms;
-            profile_begin(st);
-            for (int c = 0; c < kQsClasses; ++c) {                  // one launch per register class present
-                if (plan.cls_count[c] == 0) continue;
-                qa.wk = QsWork{ws + L.off_list, plan.per, plan.cls_begin[c]};
-                const dim3 grid((unsigned)plan.cls_count[c]);
-                if (c == 0) launch_bwd_qsweep_0(grid, st, qa);
-                else launch_bwd_qsweep_1(grid, st, qa);
-            }
-            for (int n = kQsOwnLo; n <= kQsOwnHi; ++n) {            // n = 7..9: one launch per n present, member = blockIdx.y
-                const int cnt = plan.own_count[n - kQsOwnLo];
-                if (cnt == 0) continue;
-                const long nw = qs_nwaves(n, nb);
-                Runs runs{};
-                runs.nruns = 2;
-                runs.enc[0] = runs.enc[1] = n;
-                runs.ld[0] = qs.dr.ld0; runs.ld[1] = qs.dr.ld1;
-                const BwdArgs ba{runs, (long)nb, 0, 0, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U, 0, 0.0, 0.0,
-                                 nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr, inv_batch_total[i], pr, gx, partial,
-                                 QHEA_PAULI_Z, 0, cnt * nw > simd_count() ? 1 : 0, nullptr};
-                const QubitArgs q{mrec, ms, QsWork{ws + L.off_list, plan.per, plan.own_begin[n - kQsOwnLo]}};
-                const dim3 grid((unsigned)(nw / kWaves), (unsigned)cnt);
-                switch (n) {
-#define QHEA_CASE(NN) case NN: launch_bwd_qubit_##NN(grid, st, ba, q); break;
-                    QHEA_FOR_EACH_N(QHEA_CASE)
-#undef QHEA_CASE
-                    default: return QHEA_EUNSUPPORTED;
-                }
-            }
-            profile_end(st);
-            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-            const int64_t step = first_step + i;
-            const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-            const AdamArgs adam{params, exp_avg, exp_avg_sq, members[0].lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-            GradMap gm{};
-            gm.off_ans = mi0.off_ans; gm.off_bias = mi0.off_bias; gm.off_sse = mi0.P;
-            for (int s = 0; s < 2; ++s) { gm.off_w[s] = mi0.off_w[s]; gm.off_b[s] = mi0.off_b[s]; }
-            hipLaunchKernelGGL((reduce_model_kernel<false, false, true, QubitRed>), dim3((unsigned)plan.red_count), dim3(kRedThreads), 0,
-                               st, mi0.n, (int)mi0.sh.blk, padded_3n(mi0.n), 0L, (const double*)partial, (const double*)params,
-                               (long)nb, (int)mi0.sh.E, enc, (const double*)gx, (const double*)pr, y + r0, inv_batch_total[i], gm, 0, 0,
-                               grad + i * grad_stride, adam, reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr,
-                               FusePrep{}, DpX{}, ms, MemberLr{mrec, bc1},
-                               QubitRed{qs.dr, QsWork{ws + L.off_list, plan.per, plan.red_begin}});
-            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        }
+        hipLaunchKernelGGL(member_fill_kernel<MemberFillQubit>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice,
+                           (long)slice, ham_diag ? ham_diag + m0 * diag_stride : nullptr, (long)diag_stride);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
     }
-    // n >= 10 (workgroup-resident kernels): one member after the other, each on its own descriptor and slice; its status word
-    // is folded into slice 0's
-    for (int64_t m = 0; m < n_models; ++m) {
-        if (qs.mem[m].wave) continue;
-        const qhea_model_desc dm = member_desc(descs[m], members[m]);
-        char* wm = ws + m * slice;
-        const int rc = qhea_model_train_steps(&dm, n_steps, row_begin, branch + m * rows * dm.branch_in,
-                                              qn ? trunk + m * rows * dm.trunk_in : nullptr, y + m * rows,
-                                              params + m * qs.pmax, ham_diag ? ham_diag + m * diag_stride : nullptr,
-                                              inv_batch_total, grad + m * n_steps * grad_stride, grad_stride,
-                                              exp_avg + m * qs.pmax, exp_avg_sq + m * qs.pmax, first_step, members[m].lr,
-                                              beta1, beta2, eps, weight_decay, wm, slice, stream);
-        if (rc != QHEA_OK) return rc;
-        if (m > 0) {
-            hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
-                               reinterpret_cast<WorkspaceHeader*>(wm));
-            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    char* list0 = ws + kHeaderBytes;                             // (QubitLayout::off_list)
+    for (int k0 = 0; k0 < (int)plan.e.size(); k0 += kWorkFill) {
+        const int cnt = std::min<int>(kWorkFill, (int)plan.e.size() - k0);
+        WorkFill f{};
+        for (int i = 0; i < cnt; ++i) f.e[i] = plan.e[k0 + i];
+        hipLaunchKernelGGL(work_fill_kernel, dim3(1), dim3(kWorkFill), 0, st, f, cnt, k0, list0, (long)slice, plan.per);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    }
+    const MemberStride ms{(long)rows, (long)qs.pmax, (long)(n_steps * grad_stride), (long)slice};
+    const char* mrec = ws + kMemberRecOffset;
+    QubitBwdArgs qa{};
+    for (int n = 2; n <= 9; ++n) {                              // two runs of fixed (enc = n, ld); the counts are the members'
+        Runs& r = qa.runs[n - 2];
+        r.nruns = 2;
+        r.enc[0] = r.enc[1] = n;
+        r.ld[0] = qs.dr.ld0; r.ld[1] = qs.dr.ld1;
+    }
+    const qhea_model_desc& d0 = descs[0];
+    const ModelInfo& mi0 = qs.mem[0].mi;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
+        const QubitLayout L = qubit_layout(qs, nb, plan.list_bytes);
+        const EncDesc enc = make_enc(&d0, mi0, branch + r0 * d0.branch_in, qn ? trunk + r0 * d0.trunk_in : nullptr, params);
+        long prep_total = 0;
+        for (const QubitMember& q : qs.mem)
+            prep_total = std::max(prep_total, (long)(q.d.blk + 2) * q.mi.n + (long)nb * q.d.E);
+        hipLaunchKernelGGL(prep_model_qubit_kernel, dim3((unsigned)((prep_total + 255) / 256), (unsigned)n_models), dim3(256), 0,
+                           st, qs.dr, (const double*)params, reinterpret_cast<double4*>(ws + L.off_U), (long)nb, enc,
+                           reinterpret_cast<double2*>(ws + L.off_cs), reinterpret_cast<WorkspaceHeader*>(ws), mrec, ms);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        double* gx = reinterpret_cast<double*>(ws + L.off_gx);
+        double* pr = reinterpret_cast<double*>(ws + L.off_pred);
+        double* partial = reinterpret_cast<double*>(ws + L.off_part);
+        qa.B = nb; qa.inv_bt = inv_batch_total[i];
+        qa.cs = reinterpret_cast<const double2*>(ws + L.off_cs); qa.gates = ws + L.off_U;
+        qa.y = y + r0; qa.bias = qn ? params : nullptr;
+        qa.out = pr; qa.grad_x = gx; qa.partial = partial;
+        qa.mrec = mrec; qa.ms = ms;
+        profile_begin(st);
+        for (int c = 0; c < kQsClasses; ++c) {                  // one launch per register class present
+            if (plan.cls_count[c] == 0) continue;
+            qa.wk = QsWork{ws + L.off_list, plan.per, plan.cls_begin[c]};
+            const dim3 grid((unsigned)plan.cls_count[c]);
+            if (c == 0) launch_bwd_qsweep_0(grid, st, qa);
+            else launch_bwd_qsweep_1(grid, st, qa);
         }
+        for (int n = kQsOwnLo; n <= kQsOwnHi; ++n) {            // n = 7..9: one launch per n present, member = blockIdx.y
+            const int cnt = plan.own_count[n - kQsOwnLo];
+            if (cnt == 0) continue;
+            const long nw = qs_nwaves(n, nb);
+            Runs runs{};
+            runs.nruns = 2;
+            runs.enc[0] = runs.enc[1] = n;
+            runs.ld[0] = qs.dr.ld0; runs.ld[1] = qs.dr.ld1;
+            const BwdArgs ba{runs, (long)nb, 0, 0, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U, 0, 0.0, 0.0,
+                             nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr, inv_batch_total[i], pr, gx, partial,
+                             QHEA_PAULI_Z, 0, cnt * nw > simd_count() ? 1 : 0, nullptr};
+            const QubitArgs q{mrec, ms, QsWork{ws + L.off_list, plan.per, plan.own_begin[n - kQsOwnLo]}};
+            const dim3 grid((unsigned)(nw / kWaves), (unsigned)cnt);
+            switch (n) {
+#define QHEA_CASE(NN) case NN: launch_bwd_qubit_##NN(grid, st, ba, q); break;
+                QHEA_FOR_EACH_N(QHEA_CASE)
+#undef QHEA_CASE
+                default: return QHEA_EUNSUPPORTED;
+            }
+        }
+        for (int n = kQsLdsLo; n <= kQsLdsHi; ++n) {            // n = 10..12: one launch per n present, one workgroup per
+            const int cnt = plan.lds_count[n - kQsLdsLo];         // (sample, member)
+            if (cnt == 0) continue;
+            Runs runs{};
+            runs.nruns = 2;
+            runs.enc[0] = runs.enc[1] = n;
+            runs.ld[0] = qs.dr.ld0; runs.ld[1] = qs.dr.ld1;
+            const BwdArgs ba{runs, (long)nb, 0, 0, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U, 0, 0.0, 0.0,
+                             nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr, inv_batch_total[i], pr, gx, partial,
+                             QHEA_PAULI_Z, 0, 0, nullptr};
+            const QubitArgs q{mrec, ms, QsWork{ws + L.off_list, plan.per, plan.lds_begin[n - kQsLdsLo]}};
+            const int rc = launch_lds_bwd_qubit(n, dim3((unsigned)nb, (unsigned)cnt), st, ba, q);
+            if (rc != QHEA_OK) return rc;
+        }
+        profile_end(st);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        const int64_t step = first_step + i;
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const AdamArgs adam{params, exp_avg, exp_avg_sq, members[0].lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+        GradMap gm{};
+        gm.off_ans = mi0.off_ans; gm.off_bias = mi0.off_bias; gm.off_sse = mi0.P;
+        for (int s = 0; s < 2; ++s) { gm.off_w[s] = mi0.off_w[s]; gm.off_b[s] = mi0.off_b[s]; }
+        hipLaunchKernelGGL((reduce_model_kernel<false, false, true, QubitRed>), dim3((unsigned)plan.red_count), dim3(kRedThreads), 0,
+                           st, mi0.n, (int)mi0.sh.blk, padded_3n(mi0.n), 0L, (const double*)partial, (const double*)params,
+                           (long)nb, (int)mi0.sh.E, enc, (const double*)gx, (const double*)pr, y + r0, inv_batch_total[i], gm, 0, 0,
+                           grad + i * grad_stride, adam, reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr,
+                           FusePrep{}, DpX{}, ms, MemberLr{mrec, bc1},
+                           QubitRed{qs.dr, QsWork{ws + L.off_list, plan.per, plan.red_begin}});
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
     }
     return QHEA_OK;
 }

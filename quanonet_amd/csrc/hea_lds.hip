@@ -28,6 +28,7 @@
 // Measured, cfg 5 (n = 12, Net40-2-20-2, B = 1024): forward 1.90 ms, forward + backward 8.47 ms (the previous
 // gate-pair-per-pass LDS kernels: 6.6 / 21.8 ms).
 #include "hea_device.hpp"
+#include "hea_qsweep.hpp"
 
 namespace qhea {
 
@@ -281,9 +282,11 @@ __device__ __forceinline__ void basis_lds(double2* s, const Bases<N, LG>& bs, in
     fwd_layer<N, LG, false>(s, bs, [&](int, double4& u) { u = uc; return true; });
 }
 
-template <int N, int LG>
+// MEM: a sweep member's block counts (run_count, hea_device.hpp) instead of the run table's
+template <int N, int LG, bool MEM = false>
 __device__ __forceinline__ void forward_lds(double2* psi, double4* gtab, const Bases<N, LG>& bs, const Runs& runs,
-                                            const double2* __restrict__ cs_b, const char* __restrict__ gates) {
+                                            const double2* __restrict__ cs_b, const char* __restrict__ gates,
+                                            DepthCounts dc = DepthCounts{0, 0}) {
     using L = LCfg<N, LG>;
 #pragma unroll
     for (int j = 0; j < L::M; ++j) {
@@ -294,7 +297,7 @@ __device__ __forceinline__ void forward_lds(double2* psi, double4* gtab, const B
     int col = 0, sub = 0;
     for (int ri = 0; ri < runs.nruns; ++ri) {
         const int ne = runs.enc[ri], nld = runs.ld[ri];
-        for (int rep = 0; rep < runs.count[ri]; ++rep) {
+        for (int rep = 0; rep < run_count<MEM>(runs, ri, dc); ++rep) {
             // RX(x[col+j]) on wire j % n, n wires per layer; the last layer is folded into the first sub-layer
             const int nchunks = (ne + N - 1) / N;
             const int nsep = (nld > 0 && ne > 0) ? nchunks - 1 : nchunks;
@@ -363,7 +366,11 @@ __global__ __launch_bounds__((LCfg<N, kFwdLG>::T)) void lds_fwd_kernel(Runs runs
 }
 
 // Backward: one row of `partial` per sample ([B][blk][KW]); grad_x written directly.
-template <int N>
+// DA: empty for the single-model kernel; one DepthArgs (depth sweeps, ensembles and sweeps: member = blockIdx.y) or one
+// QubitArgs (qubit sweeps: member = work-list entry blockIdx.y) for the member instantiations, whose prologue moves the
+// pointers to the member's and sets its E, blk, read-out and block counts, as bwd_kernel's does (hea_device.hpp).  The sample
+// is blockIdx.x in both forms.
+template <int N, class... DA>
 __global__ __launch_bounds__((LCfg<N, kBwdLG>::T)) void lds_bwd_kernel(Runs runs, long B, int E, int blk,
                                                              const double2* __restrict__ cs,
                                                              const char* __restrict__ gates, double off, double co,
@@ -373,10 +380,28 @@ __global__ __launch_bounds__((LCfg<N, kBwdLG>::T)) void lds_bwd_kernel(Runs runs
                                                              const double* __restrict__ y,
                                                              const double* __restrict__ bias, double inv_bt,
                                                              double* __restrict__ out, double* __restrict__ grad_x,
-                                                             double* __restrict__ partial) {
+                                                             double* __restrict__ partial, DA... da) {
     constexpr int LG = kBwdLG;
     using L = LCfg<N, LG>;
     constexpr int KW = L::KW;
+    constexpr bool MEM = sizeof...(DA) != 0;
+    DepthCounts dc{0, 0};
+    if constexpr (MEM) {        // the member's counts, shape, read-out and pointers (the launch's are member 0's)
+        const auto d = (da, ...);
+        const auto mr = d.rec();
+        dc.c0 = mr->depth[0]; dc.c1 = mr->depth[1];
+        E = N * (dc.c0 + dc.c1);
+        blk = dc.c0 * runs.ld[0] + dc.c1 * runs.ld[1];
+        off = mr->off; co = mr->co; diag = mr->diag; pauli = mr->pauli;
+        const long wsb = d.ws_bytes();
+        cs = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(cs) + wsb);
+        gates += wsb;
+        out = reinterpret_cast<double*>(reinterpret_cast<char*>(out) + wsb);
+        grad_x = reinterpret_cast<double*>(reinterpret_cast<char*>(grad_x) + wsb);
+        partial = reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + wsb);
+        y = reinterpret_cast<const double*>(reinterpret_cast<const char*>(y) + d.row_bytes());
+        if (bias) bias = reinterpret_cast<const double*>(reinterpret_cast<const char*>(bias) + d.param_bytes());
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double2* psi = reinterpret_cast<double2*>(smem);
     double2* lam = psi + L::DIM;
@@ -396,7 +421,7 @@ __global__ __launch_bounds__((LCfg<N, kBwdLG>::T)) void lds_bwd_kernel(Runs runs
         }
         __syncthreads();
     } else {
-        forward_lds<N, LG>(psi, gtab, bs, runs, cs_b, gates);
+        forward_lds<N, LG, MEM>(psi, gtab, bs, runs, cs_b, gates, dc);
     }
     basis_lds<N, LG>(psi, bs, pauli, false);
     double acc = 0.0;
@@ -425,7 +450,7 @@ __global__ __launch_bounds__((LCfg<N, kBwdLG>::T)) void lds_bwd_kernel(Runs runs
     for (int ri = runs.nruns - 1; ri >= 0; --ri) {
         const int ne = runs.enc[ri], nld = runs.ld[ri];
         const int nchunks = (ne + N - 1) / N;
-        for (int rep = 0; rep < runs.count[ri]; ++rep) {
+        for (int rep = 0; rep < run_count<MEM>(runs, ri, dc); ++rep) {
             const int nsep = (nld > 0 && ne > 0) ? nchunks - 1 : nchunks;      // see forward_lds
             const int m_merged = nsep < nchunks ? ne - nsep * N : 0;
             col -= ne;
@@ -526,9 +551,39 @@ int launch_bwd_n(long B, hipStream_t st, const BwdArgs& a) {
     return QHEA_OK;
 }
 
+// member launches: grid (samples, members); A = DepthArgs or QubitArgs
+template <int N, class A>
+int launch_bwd_member_n(dim3 grid, hipStream_t st, const BwdArgs& a, const A& m) {
+    using L = LCfg<N, kBwdLG>;
+    constexpr size_t smem = 2 * L::STATE_BYTES + L::SCRATCH_BYTES;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(lds_bwd_kernel<N, A>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        return QHEA_ELAUNCH;
+    hipLaunchKernelGGL((lds_bwd_kernel<N, A>), grid, dim3(L::T), smem, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates, a.off,
+                       a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x, a.partial, m);
+    return QHEA_OK;
+}
+template <class A>
+int launch_bwd_member(int n, dim3 grid, hipStream_t st, const BwdArgs& a, const A& m) {
+    switch (n) {
+        case 10: return launch_bwd_member_n<10>(grid, st, a, m);
+        case 11: return launch_bwd_member_n<11>(grid, st, a, m);
+        case 12: return launch_bwd_member_n<12>(grid, st, a, m);
+        default: return QHEA_EUNSUPPORTED;
+    }
+}
+
 }  // namespace
 
 bool lds_supported(int n) { return n >= 10 && n <= 12; }
+
+int launch_lds_bwd_depth(int n, dim3 grid, hipStream_t st, const BwdArgs& a, const DepthArgs& d) {
+    return launch_bwd_member(n, grid, st, a, d);
+}
+
+int launch_lds_bwd_qubit(int n, dim3 grid, hipStream_t st, const BwdArgs& a, const QubitArgs& q) {
+    return launch_bwd_member(n, grid, st, a, q);
+}
 
 int launch_lds_fwd(int n, long B, hipStream_t st, const FwdArgs& a) {
     switch (n) {

@@ -1,7 +1,8 @@
 // hea_qsweep.hpp -- qubit sweeps (qhea_model_qubit_sweep_train_steps): members of different qubit counts trained side by side.
 // The wave-resident members with n = 2..6 are split into register classes -- runs of consecutive n whose packed backward
 // kernels give the same waves per SIMD -- and each class is one backward launch per step, whose workgroups take
-// their (member, sample group) from a host-built work list.  n = 7..9 take one launch per n (QubitArgs).
+// their (member, sample group) from a host-built work list.  n = 7..9 take one launch per n (QubitArgs), and so do the
+// workgroup-resident members, n = 10..12 (lds_bwd_kernel<N, QubitArgs>, hea_lds.hip: DESIGN.md 7e).
 #pragma once
 #include "hea_device.hpp"
 #include "hea_zyz.hpp"
@@ -28,7 +29,12 @@ __host__ __device__ inline long qs_nwaves(int n, long B) {
     return (((B + spw - 1) / spw + kWaves - 1) / kWaves) * kWaves;
 }
 
-// Work lists: entries (member, sample group) of the backward launches and (member, role) of the reduce launch, 8 bytes each,
+// a member's partial rows: the packed backward kernel's waves (n <= 9), one row per sample for the workgroup-resident kernel
+// (n >= 10, hea_lds.hip)
+__host__ __device__ inline long qs_part_rows(int n, long B) { return n >= 10 ? B : qs_nwaves(n, B); }
+
+// Work lists: entries (member, sample group) of the backward launches -- (member, 0) for the launches of one n, 7..12 -- and
+// (member, role) of the reduce launch, 8 bytes each,
 // in the list regions of the members' workspace slices -- entry k is entry k % per of slice k / per's region, which starts at
 // `list` + (k / per) * slice bytes.  Written once per call (work_fill_kernel, hea_api.hip), read with one scalar load per
 // workgroup.  base: the launch's first entry.
@@ -83,5 +89,12 @@ struct QubitArgs {
 #define QHEA_QDECLARE(NN) void launch_bwd_qubit_##NN(dim3 grid, hipStream_t st, const BwdArgs& a, const QubitArgs& q);
 QHEA_FOR_EACH_N(QHEA_QDECLARE)
 #undef QHEA_QDECLARE
+
+// n = 10..12 (hea_lds.hip): the member forms of the workgroup-resident backward kernel, lds_bwd_kernel<N, DepthArgs> (member =
+// blockIdx.y: depth sweeps, ensembles and sweeps) and lds_bwd_kernel<N, QubitArgs> (member = work-list entry blockIdx.y: qubit
+// sweeps); grid.x = the batch, one workgroup per sample as in the single-model launch.  a: as for launch_lds_bwd, member 0's
+// pointers, its E / blk / read-out unused (the member's come from its MemberRec); QHEA_EUNSUPPORTED for other n.
+int launch_lds_bwd_depth(int n, dim3 grid, hipStream_t st, const BwdArgs& a, const DepthArgs& d);
+int launch_lds_bwd_qubit(int n, dim3 grid, hipStream_t st, const BwdArgs& a, const QubitArgs& q);
 
 }  // namespace qhea

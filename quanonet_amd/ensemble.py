@@ -2,7 +2,8 @@
 Model-ensemble training: the seeds of one configuration trained side by side on one device, every step of all R members as
 ONE launch per kernel (qhea_model_ensemble_train_steps: member = the grid's second dimension).  The reference starts the
 seeds of a sweep cell as concurrent processes (scripts/reproduce_benchmarks2.sh, its `for SEED` loop); at the paper's batch
-of 100 one model leaves most of the device idle, R models in one grid fill it.
+of 100 one model leaves most of the device idle, R models in one grid fill it.  Shapes with n <= 5 (ZYZ kernels) and n >= 10
+(workgroup-resident kernels) take the one-grid path; n = 6..9 train as R consecutive single-model calls.
 
 Member m is exactly the PTSolver run its config describes when launched after ``set_random_seed(seed_m)``: its model is
 built right after ``torch.manual_seed(seed_m)``, its batch order is drawn per epoch from ``np.random.RandomState(seed_m)``

@@ -5,9 +5,9 @@ P = 2^n, each with its own hb x ht list, x seeds; scripts/reproduce_circuit.sh: 
 and seed; DepthSweepSolver takes one qubit count at a time.
 
 Members may differ in everything DepthSweepSolver allows and in num_qubits (>= 2).  The linear depths, the input widths, the
-model type and the frequency mode are shared; a member's ham_diag has 2^num_qubits entries.  Every step of the members with
-n <= 9 is one prep launch, one backward launch per register class present and one reduce launch; members with n >= 10 then
-train one after another.  Member m is exactly the PTSolver run its config describes when launched after
+model type and the frequency mode are shared; a member's ham_diag has 2^num_qubits entries.  Every step of all members is one
+prep launch, one backward launch per register class (n <= 6) or qubit count (n = 7..12) present and one reduce launch.
+Member m is exactly the PTSolver run its config describes when launched after
 ``set_random_seed(seed_m)``, with its own checkpoints and history.  The parameters of all members live in one [R, Pmax] device
 tensor; member m's model parameters are views into the front of row m.
 """
