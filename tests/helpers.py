@@ -134,3 +134,136 @@ def trajectory_solver_inputs(name, prefix, **extra):
         data = {'train_input': a['input0'], 'train_output': a['y'], 'test_input': a['input0'][:40],
                 'test_output': a['y'][:40]}
     return cfg, data, a, order(model_type, trainable), seed
+
+
+# --------------------------------------------------------------------------------------------------
+# Kernels one call launches: stream capture through the HIP runtime's C API (relaxed mode); the graph is only read,
+# never instantiated or replayed.  The call runs once uncaptured first, so every buffer and workspace then exists.
+# --------------------------------------------------------------------------------------------------
+HIP_CAPTURE_RELAXED = 2
+HIP_GRAPH_NODE_KERNEL = 0
+
+
+def hip_runtime():
+    """the HIP runtime this process already uses (torch's), by its loaded path"""
+    import ctypes
+    import torch
+    torch.cuda.init()
+    with open('/proc/self/maps') as f:
+        paths = {line.split()[-1] for line in f if 'libamdhip64' in line}
+    assert paths, 'HIP runtime not loaded'
+    hip = ctypes.CDLL(sorted(paths)[0])
+    hip.hipStreamBeginCapture.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    hip.hipStreamEndCapture.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    hip.hipGraphGetNodes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+    hip.hipGraphNodeGetType.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    hip.hipGraphKernelNodeGetParams.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    hip.hipKernelNameRefByPtr.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    hip.hipKernelNameRefByPtr.restype = ctypes.c_char_p
+    hip.hipGraphDestroy.argtypes = [ctypes.c_void_p]
+    return hip
+
+
+def _kernel_node_params_type():
+    import ctypes
+
+    class Dim3(ctypes.Structure):
+        _fields_ = [('x', ctypes.c_uint32), ('y', ctypes.c_uint32), ('z', ctypes.c_uint32)]
+
+    class KernelNodeParams(ctypes.Structure):            # hipKernelNodeParams (hip_runtime_api.h)
+        _fields_ = [('blockDim', Dim3), ('extra', ctypes.c_void_p), ('func', ctypes.c_void_p), ('gridDim', Dim3),
+                    ('kernelParams', ctypes.c_void_p), ('sharedMemBytes', ctypes.c_uint32)]
+    return KernelNodeParams
+
+
+def _captured_kernel_nodes(dev, call, visit):
+    """visit(hip, node) for every kernel node of one captured call"""
+    import ctypes
+    import torch
+    from quanonet_amd import _lib
+    hip = hip_runtime()
+    s = torch.cuda.Stream(dev)
+    with torch.cuda.stream(s):
+        call()
+        _lib.check_status(dev)
+        s.synchronize()
+        h = ctypes.c_void_p(s.cuda_stream)
+        assert hip.hipStreamBeginCapture(h, HIP_CAPTURE_RELAXED) == 0
+        try:
+            call()
+        finally:
+            graph = ctypes.c_void_p()
+            rc = hip.hipStreamEndCapture(h, ctypes.byref(graph))
+        assert rc == 0 and graph.value
+    try:
+        n = ctypes.c_size_t(0)
+        assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
+        nodes = (ctypes.c_void_p * n.value)()
+        assert hip.hipGraphGetNodes(graph, nodes, ctypes.byref(n)) == 0
+        out = []
+        for i in range(n.value):
+            t = ctypes.c_int(-1)
+            assert hip.hipGraphNodeGetType(nodes[i], ctypes.byref(t)) == 0
+            if t.value == HIP_GRAPH_NODE_KERNEL:
+                out.append(visit(hip, nodes[i], s))
+        return out
+    finally:
+        assert hip.hipGraphDestroy(graph) == 0
+
+
+def kernels_launched(dev, call):
+    """number of kernel nodes of one captured call"""
+    return len(_captured_kernel_nodes(dev, call, lambda hip, node, s: None))
+
+
+def kernel_launches(dev, call):
+    """[(mangled kernel name, gridDim, blockDim)] of one captured call, in node order; gridDim / blockDim as (x, y, z)"""
+    import ctypes
+    P = _kernel_node_params_type()
+
+    def visit(hip, node, s):
+        p = P()
+        assert hip.hipGraphKernelNodeGetParams(node, ctypes.byref(p)) == 0
+        name = hip.hipKernelNameRefByPtr(p.func, ctypes.c_void_p(s.cuda_stream))
+        assert name, 'the HIP runtime has no name for a captured kernel'
+        return (name.decode(), (p.gridDim.x, p.gridDim.y, p.gridDim.z), (p.blockDim.x, p.blockDim.y, p.blockDim.z))
+    return _captured_kernel_nodes(dev, call, visit)
+
+
+def mangled_is(name, ident, targs=None):
+    """whether a mangled (Itanium) kernel name is the function `ident` -- its length-prefixed identifier, so that
+    '10bwd_kernel' never matches '14lds_bwd_kernel' -- and, given targs, whether its template arguments begin with those
+    integers ('Li5ELi2E' for <5, 2>)"""
+    import re
+    m = re.search(r'(?<![0-9])%d%s(I|E|v|P|R|S|$)' % (len(ident), re.escape(ident)), name)
+    if not m:
+        return False
+    if targs is None:
+        return True
+    want = 'I' + ''.join(f'Li{int(v)}E' for v in targs)
+    return name[m.end() - 1:].startswith(want)
+
+
+def oracle_adam_loop(model_cpu, names, branch, trunk, y, bounds, gbs, n, net, lr, model_type='QuanONet', **kw):
+    """Independent CPU loop: oracle loss/gradients (C engine) + torch.optim.Adam.  Returns (rows [steps, P+2], final flat
+    params).  kw: read-out arguments of the oracle's loss (ham_bound, ham_pauli, ham_diag)."""
+    import torch
+    from oracle import c_oracle as C
+    params = [p for _, p in model_cpu.named_parameters()]
+    opt = torch.optim.Adam(params, lr=lr)
+    rows = []
+    for i in range(len(gbs)):
+        lo, hi = bounds[i], bounds[i + 1]
+        sd = {k: v.detach().numpy() for k, v in model_cpu.state_dict().items()}
+        if model_type == 'QuanONet':
+            loss, grads, _ = O.quanonet_loss_and_grads(sd, branch[lo:hi], trunk[lo:hi], y[lo:hi], n, net,
+                                                       batch_total=gbs[i], engine=C, **kw)
+        else:
+            loss, grads, _ = O.heaqnn_loss_and_grads(sd, branch[lo:hi], y[lo:hi], n, net, batch_total=gbs[i], engine=C, **kw)
+        flat = np.concatenate([np.asarray(grads[k], np.float64).reshape(-1) for k in names])
+        rows.append(np.concatenate([flat, [loss * gbs[i], float((y[lo:hi] ** 2).sum())]]))
+        opt.zero_grad()
+        for k, p in zip(names, params):
+            p.grad = torch.from_numpy(np.asarray(grads[k], np.float64).reshape(p.shape).copy())
+        opt.step()
+    return np.stack(rows), np.concatenate([p.detach().numpy().reshape(-1) for p in params])

@@ -18,6 +18,7 @@ import torch
 
 from oracle import hea_oracle as O
 from oracle import c_oracle as C
+from tests.helpers import oracle_adam_loop
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -29,25 +30,6 @@ N_QUBITS, NET, B_IN, T_IN = 5, (40, 2, 20, 2), 100, 2          # bench.py's work
 def dev():
     assert torch.cuda.is_available()
     return torch.device('cuda:0')
-
-
-def _oracle_adam_loop(model_cpu, names, branch, trunk, y, bounds, gbs, n, net, lr):
-    """Independent CPU loop: oracle loss/gradients + torch.optim.Adam.  Returns (rows [steps, P+2], final flat params)."""
-    params = [p for _, p in model_cpu.named_parameters()]
-    opt = torch.optim.Adam(params, lr=lr)
-    rows = []
-    for i in range(len(gbs)):
-        lo, hi = bounds[i], bounds[i + 1]
-        sd = {k: v.detach().numpy() for k, v in model_cpu.state_dict().items()}
-        loss, grads, _ = O.quanonet_loss_and_grads(sd, branch[lo:hi], trunk[lo:hi], y[lo:hi], n, net,
-                                                   batch_total=gbs[i], engine=C)
-        flat = np.concatenate([np.asarray(grads[k], np.float64).reshape(-1) for k in names])
-        rows.append(np.concatenate([flat, [loss * gbs[i], float((y[lo:hi] ** 2).sum())]]))
-        opt.zero_grad()
-        for k, p in zip(names, params):
-            p.grad = torch.from_numpy(np.asarray(grads[k], np.float64).reshape(p.shape).copy())
-        opt.step()
-    return np.stack(rows), np.concatenate([p.detach().numpy().reshape(-1) for p in params])
 
 
 @pytest.mark.parametrize('batch,variant', [(1024, 'auto'), (512, 'auto'), (1000, 'auto'), (1024, 'ztri'), (512, 'ztri'),
@@ -73,7 +55,7 @@ def test_benched_train_steps_match_oracle_and_torch_adam(dev, batch, variant):
     import copy
     cpu_model = copy.deepcopy(model).double()
     names = [k for k, _ in cpu_model.named_parameters()]
-    want_rows, want_params = _oracle_adam_loop(cpu_model, names, branch, trunk, y, bounds, gbs, N_QUBITS, NET, lr)
+    want_rows, want_params = oracle_adam_loop(cpu_model, names, branch, trunk, y, bounds, gbs, N_QUBITS, NET, lr)
 
     _lib.set_backward_variant(variant)
     try:

@@ -1,10 +1,10 @@
 """
-GPU checks at BASELINE.json's FULL sizes (cfg 2, 4, 5), where the oracle is too slow for the whole batch:
-size-independent properties of the domain + the oracle on a random subset of samples.
+GPU checks at BASELINE.json's FULL sizes (cfg 2, 4, 5):
   * unit norm of every final state, outputs inside [lo, hi]
   * adjoint gradient == parameter-shift rule evaluated with the HIP forward pass itself (exact for these gates)
   * linearity in the upstream weight, additivity of grad_w over a batch split
-  * oracle (C restatement) on 6 random samples of the batch, 1e-10
+  * oracle (C restatement): cfg 2 and cfg 4 on the whole batch (out, grad_x, grad_w); cfg 5 on 64 random rows of the batch
+    (out, grad_x), and grad_w of a HIP call on exactly those rows; plus 6 random samples of every batch, 1e-10
 """
 import numpy as np
 import pytest
@@ -55,6 +55,17 @@ def test_full_size_properties(dev, name):
     ro, rgx, _ = C.hea_backward(n, cfgs, x[idx], w, g[idx], off, co)
     np.testing.assert_allclose(out.cpu().numpy()[idx], ro, rtol=0, atol=TOL)
     np.testing.assert_allclose(gx.cpu().numpy()[idx], rgx, rtol=0, atol=TOL)
+
+    # oracle on the whole batch (cfg 5: 64 rows of it, and grad_w of a HIP call on exactly those rows)
+    rows = np.arange(B) if n < 10 else np.sort(rng.choice(B, 64, replace=False))
+    ro, rgx, rgw = C.hea_backward(n, cfgs, x[rows], w, g[rows], off, co)
+    np.testing.assert_allclose(out.cpu().numpy()[rows], ro, rtol=0, atol=TOL)
+    np.testing.assert_allclose(gx.cpu().numpy()[rows], rgx, rtol=0, atol=TOL)
+    if n < 10:
+        np.testing.assert_allclose(gw.cpu().numpy(), rgw, rtol=0, atol=1e-9)
+    else:
+        _, gw_rows = _lib.hea_backward(sh, t(x[rows]), wd, t(g[rows]), off, co)
+        np.testing.assert_allclose(gw_rows.cpu().numpy(), rgw, rtol=0, atol=1e-9)
 
     # parameter-shift with the HIP forward itself: d/dw sum_b g_b f_b = sum_b g_b (f_b(+pi/2) - f_b(-pi/2)) / 2
     for (s, k, q) in [(0, 0, 0), (blk - 1, 2, n - 1), (blk // 2, 1, n // 2)]:

@@ -8,7 +8,6 @@ n present and step -- instead of one single-model call per member.
   member alone, row tails untouched;
 * members match the CPU oracle + torch.optim.Adam at 1e-10, and QubitSweepSolver matches the PTSolver runs of its configs.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -18,6 +17,7 @@ import torch
 from tests.test_ensemble import _antideriv, _data, _flat, _heaqnn, _oracle_adam, _quanonet, _run_single, _schedule
 from tests.test_depth_sweep import _run_depth
 from tests.test_qubit_sweep import SENTINEL, _run_qubit
+from tests.helpers import kernels_launched as _kernels_launched
 
 pytestmark = pytest.mark.gpu
 
@@ -87,58 +87,6 @@ def _qubit_call(dev, models, lrs, inputs, ys, bounds, gbs):
         _lib.model_qubit_sweep_train_steps(descs, hps, bounds, gbs, ins[0], ins[1] if len(ins) > 1 else None, y, params, rows,
                                            m_, v_, 1, 0.9, 0.999, 1e-8, 0.0)
     return call
-
-
-# ---- kernel launches per call: stream capture through the HIP runtime's C API (relaxed mode), the graph only counted ----
-def _hip_runtime():
-    """the HIP runtime this process already uses (torch's), by its loaded path"""
-    torch.cuda.init()
-    with open('/proc/self/maps') as f:
-        paths = {line.split()[-1] for line in f if 'libamdhip64' in line}
-    assert paths, 'HIP runtime not loaded'
-    hip = ctypes.CDLL(sorted(paths)[0])
-    hip.hipStreamBeginCapture.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    hip.hipStreamEndCapture.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-    hip.hipGraphGetNodes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
-    hip.hipGraphNodeGetType.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-    hip.hipGraphDestroy.argtypes = [ctypes.c_void_p]
-    return hip
-
-
-HIP_CAPTURE_RELAXED = 2
-HIP_GRAPH_NODE_KERNEL = 0
-
-
-def _kernels_launched(dev, call):
-    """kernel nodes of one captured call (run once uncaptured first: every buffer and workspace then exists)"""
-    from quanonet_amd import _lib
-    hip = _hip_runtime()
-    s = torch.cuda.Stream(dev)
-    with torch.cuda.stream(s):
-        call()
-        _lib.check_status(dev)
-        s.synchronize()
-        h = ctypes.c_void_p(s.cuda_stream)
-        assert hip.hipStreamBeginCapture(h, HIP_CAPTURE_RELAXED) == 0
-        try:
-            call()
-        finally:
-            graph = ctypes.c_void_p()
-            rc = hip.hipStreamEndCapture(h, ctypes.byref(graph))
-        assert rc == 0 and graph.value
-    try:
-        n = ctypes.c_size_t(0)
-        assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
-        nodes = (ctypes.c_void_p * n.value)()
-        assert hip.hipGraphGetNodes(graph, nodes, ctypes.byref(n)) == 0
-        kinds = []
-        for i in range(n.value):
-            t = ctypes.c_int(-1)
-            assert hip.hipGraphNodeGetType(nodes[i], ctypes.byref(t)) == 0
-            kinds.append(t.value)
-        return sum(k == HIP_GRAPH_NODE_KERNEL for k in kinds)
-    finally:
-        assert hip.hipGraphDestroy(graph) == 0
 
 
 def test_q10_ensemble_launches_do_not_grow_with_r(dev):
