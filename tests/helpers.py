@@ -267,3 +267,184 @@ def oracle_adam_loop(model_cpu, names, branch, trunk, y, bounds, gbs, n, net, lr
             p.grad = torch.from_numpy(np.asarray(grads[k], np.float64).reshape(p.shape).copy())
         opt.step()
     return np.stack(rows), np.concatenate([p.detach().numpy().reshape(-1) for p in params])
+
+
+# --------------------------------------------------------------------------------------------------
+# Member launches (qhea_model_{ensemble,sweep,depth_sweep,qubit_sweep}_train_steps): models, data, the calls on fresh device
+# tensors, each member's single-model run and the oracle + torch.optim.Adam loop of one member.
+# --------------------------------------------------------------------------------------------------
+def quanonet(n, b_in, t_in, net, seed, **kw):
+    """QuanONetPT in fp64 with seeded frequency biases and bias 0.1 (seed + 1)"""
+    import torch
+    from quanonet_amd.models import QuanONetPT
+    torch.manual_seed(seed)
+    m = QuanONetPT(n, b_in, t_in, net, **kw).double()
+    rng = np.random.default_rng(seed)
+    with torch.no_grad():
+        if hasattr(m, 'branch_freq') and hasattr(m.branch_freq, 'bias'):
+            m.branch_freq.bias.copy_(torch.from_numpy(rng.normal(scale=0.3, size=m.branch_freq.bias.shape)))
+            m.trunk_freq.bias.copy_(torch.from_numpy(rng.normal(scale=0.3, size=m.trunk_freq.bias.shape)))
+        m.bias.fill_(0.1 * (seed + 1))
+    return m
+
+
+def heaqnn(n, x_in, net, seed, **kw):
+    import torch
+    from quanonet_amd.models import HEAQNNPT
+    torch.manual_seed(seed)
+    kw.setdefault('scale_coeff', 0.1)
+    kw.setdefault('if_trainable_freq', True)
+    return HEAQNNPT(n, x_in, net, **kw).double()
+
+
+def flat(m):
+    import torch
+    return torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+
+
+def schedule(batch, steps=3, last=None):
+    """(row bounds, batch sizes) of `steps` steps of `batch` rows, the last one of `last` rows if given"""
+    sizes = [batch] * (steps - 1) + [last if last is not None else batch]
+    bounds = [0]
+    for s in sizes:
+        bounds.append(bounds[-1] + s)
+    return bounds, sizes
+
+
+def member_data(R, n_rows, widths, seed):
+    """R members' inputs ([normal, uniform, ...] of the given widths) and targets"""
+    rng = np.random.default_rng(seed)
+    inputs = [[rng.normal(size=(n_rows, w)) if k == 0 else rng.uniform(size=(n_rows, w)) for k, w in enumerate(widths)]
+              for _ in range(R)]
+    ys = [rng.normal(scale=0.5, size=n_rows) for _ in range(R)]
+    return inputs, ys
+
+
+def member_hp(desc, lr):
+    from quanonet_amd import _lib
+    return _lib.member_hparams(desc.scale_coeff, desc.ham_offset, desc.ham_coeff, lr, desc.ham_pauli)
+
+
+MEMBER_ENTRIES = ('ensemble', 'sweep', 'depth', 'qubit')
+
+
+def member_call(dev, entry, models, lrs, inputs, ys, bounds, gbs, ham_diag=None, sentinel=0.0, rows_sentinel=0.0, rows_extra=0,
+                desc=None):
+    """(call, (params, exp_avg, exp_avg_sq, rows)): one member entry point's call on fresh device tensors; the call may be run
+    or captured.  entry: 'ensemble' (models[0]'s descriptor, lrs[0], ham_diag one spectrum), 'sweep' (models[0]'s shape, each
+    member's read-out, scale and lr; ham_diag [R, 2^n]), 'depth' or 'qubit' (each member's descriptor; ham_diag: a spectrum per
+    member, padded with `sentinel` to the widest).  params / moments [R, Pmax], `sentinel` beyond each member's vector; rows
+    [R, steps, Pmax + 2 + rows_extra] filled with rows_sentinel.  desc: the ensemble / sweep descriptor if not models[0]'s."""
+    import torch
+    from quanonet_amd import _lib
+    assert entry in MEMBER_ENTRIES, entry
+    descs = [m.fused_desc() for m in models]
+    d0 = desc if desc is not None else descs[0]
+    R = len(models)
+    flats = [flat(m) for m in models]
+    P = max(f.numel() for f in flats)
+    params = torch.full((R, P), sentinel, dtype=torch.float64)
+    m_, v_ = params.clone(), params.clone()
+    for i, f in enumerate(flats):
+        params[i, :f.numel()] = f
+        m_[i, :f.numel()] = 0.0
+        v_[i, :f.numel()] = 0.0
+    params, m_, v_ = params.to(dev), m_.to(dev), v_.to(dev)
+    rows = torch.full((R, len(gbs), P + 2 + rows_extra), rows_sentinel, dtype=torch.float64, device=dev)
+    ins = [torch.from_numpy(np.stack([inp[k] for inp in inputs])).to(dev) for k in range(len(inputs[0]))]
+    y = torch.from_numpy(np.stack(ys)).to(dev)
+    b, t = ins[0], (ins[1] if len(ins) > 1 else None)
+    hd = None
+    if torch.is_tensor(ham_diag):
+        hd = ham_diag.to(dev)
+    elif ham_diag is not None and entry == 'ensemble':
+        hd = torch.from_numpy(np.asarray(ham_diag, np.float64)).to(dev)
+    elif ham_diag is not None:
+        width = max(len(h) for h in ham_diag)
+        hd = torch.full((R, width), sentinel, dtype=torch.float64)
+        for i, h in enumerate(ham_diag):
+            hd[i, :len(h)] = torch.from_numpy(np.asarray(h, np.float64))
+        hd = hd.to(dev)
+    hps = [member_hp(d, lr) for d, lr in zip(descs, lrs)]
+    if entry == 'ensemble':
+        def call():
+            _lib.model_ensemble_train_steps(d0, bounds, gbs, b, t, y, params, rows, m_, v_, 1, lrs[0], 0.9, 0.999, 1e-8, 0.0,
+                                            ham_diag=hd)
+    elif entry == 'sweep':
+        def call():
+            _lib.model_sweep_train_steps(d0, hps, bounds, gbs, b, t, y, params, rows, m_, v_, 1, 0.9, 0.999, 1e-8, 0.0,
+                                         ham_diag=hd)
+    else:
+        fn = _lib.model_depth_sweep_train_steps if entry == 'depth' else _lib.model_qubit_sweep_train_steps
+
+        def call():
+            fn(descs, hps, bounds, gbs, b, t, y, params, rows, m_, v_, 1, 0.9, 0.999, 1e-8, 0.0, ham_diag=hd)
+    return call, (params, m_, v_, rows)
+
+
+def run_members(dev, entry, models, lrs, inputs, ys, bounds, gbs, ham_diag=None, **kw):
+    """member_call run once: (params, exp_avg, exp_avg_sq, rows) on the CPU"""
+    from quanonet_amd import _lib
+    call, out = member_call(dev, entry, models, lrs, inputs, ys, bounds, gbs, ham_diag=ham_diag, **kw)
+    call()
+    _lib.check_status(dev)
+    return tuple(o.cpu() for o in out)
+
+
+def run_single(dev, desc, model, inputs, y, bounds, gbs, lr, ham_diag=None):
+    """model_train_steps of one model: (params, exp_avg, exp_avg_sq, rows) on the CPU"""
+    import torch
+    from quanonet_amd import _lib
+    params = flat(model).to(dev).contiguous()
+    P = params.numel()
+    m_, v_ = torch.zeros_like(params), torch.zeros_like(params)
+    rows = torch.zeros(len(gbs), P + 2, dtype=torch.float64, device=dev)
+    ins = [torch.from_numpy(t).to(dev) for t in inputs]
+    _lib.model_train_steps(desc, bounds, gbs, ins[0], ins[1] if len(ins) > 1 else None, torch.from_numpy(y).to(dev), params,
+                           rows, m_, v_, 1, lr, 0.9, 0.999, 1e-8, 0.0, ham_diag=ham_diag)
+    _lib.check_status(dev)
+    return params.cpu(), m_.cpu(), v_.cpu(), rows.cpu()
+
+
+def oracle_adam(model, lossgrad, inputs, y, bounds, gbs, lr):
+    """oracle loss / gradients (lossgrad(state dict, inputs, y, batch_total) -> (loss, grads)) + torch.optim.Adam on a CPU copy:
+    (rows [steps, P+2], final flat parameters)"""
+    return oracle_adam_state(model, lossgrad, inputs, y, bounds, gbs, lr)[:2]
+
+
+def oracle_adam_state(model, lossgrad, inputs, y, bounds, gbs, lr):
+    """oracle_adam, also returning torch.optim.Adam's exp_avg / exp_avg_sq flattened in parameter order"""
+    import copy
+    import torch
+    cpu = copy.deepcopy(model).cpu()
+    names = [k for k, _ in cpu.named_parameters()]
+    params = [p for _, p in cpu.named_parameters()]
+    opt = torch.optim.Adam(params, lr=lr)
+    rows = []
+    for i, gb in enumerate(gbs):
+        lo, hi = bounds[i], bounds[i + 1]
+        sd = {k: v.detach().numpy() for k, v in cpu.state_dict().items()}
+        loss, grads = lossgrad(sd, [t[lo:hi] for t in inputs], y[lo:hi], gb)
+        flat_g = np.concatenate([np.asarray(grads[k], np.float64).reshape(-1) for k in names])
+        rows.append(np.concatenate([flat_g, [loss * gb, float((y[lo:hi] ** 2).sum())]]))
+        for k, p in zip(names, params):
+            p.grad = torch.from_numpy(np.asarray(grads[k], np.float64).reshape(p.shape).copy())
+        opt.step()
+    st = [opt.state[p] for p in params]
+    m1 = np.concatenate([s['exp_avg'].numpy().reshape(-1) for s in st])
+    m2 = np.concatenate([s['exp_avg_sq'].numpy().reshape(-1) for s in st])
+    return np.stack(rows), np.concatenate([p.detach().numpy().reshape(-1) for p in params]), m1, m2
+
+
+def member_lossgrad(kind, n, net, ham_bound=(-5.0, 5.0), ham_pauli='Z', ham_diag=None, scale_coeff=None):
+    """oracle loss / gradients of one member (C engine) for oracle_adam: kind 'QuanONet' or 'HEAQNN'"""
+    from oracle import c_oracle as C
+
+    def f(sd, ins, y, gb):
+        kw = dict(ham_bound=ham_bound, batch_total=gb, ham_pauli=ham_pauli, ham_diag=ham_diag, scale_coeff=scale_coeff, engine=C)
+        if kind == 'QuanONet':
+            loss, grads, _ = O.quanonet_loss_and_grads(sd, ins[0], ins[1], y, n, net, **kw)
+        else:
+            loss, grads, _ = O.heaqnn_loss_and_grads(sd, ins[0], y, n, net, **kw)
+        return loss, grads
+    return f

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import run_members
 from tests.test_ensemble import _data, _flat, _heaqnn, _oracle_adam, _quanonet, _run_single, _schedule
 
 pytestmark = pytest.mark.gpu
@@ -29,27 +30,7 @@ def dev():
 
 def _run_depth(dev, models, lrs, inputs, ys, bounds, gbs, ham_diag=None):
     """the depth sweep on the members' own descriptors; params / moments rows padded with SENTINEL beyond each member"""
-    from quanonet_amd import _lib
-    descs = [m.fused_desc() for m in models]
-    R, P = len(models), _lib.depth_sweep_pmax(descs)
-    params = torch.full((R, P), SENTINEL, dtype=torch.float64)
-    for i, m in enumerate(models):
-        f = _flat(m)
-        params[i, :f.numel()] = f
-    params = params.to(dev)
-    m_, v_ = torch.full_like(params, SENTINEL), torch.full_like(params, SENTINEL)
-    for i, m in enumerate(models):
-        m_[i, :_flat(m).numel()] = 0.0
-        v_[i, :_flat(m).numel()] = 0.0
-    rows = torch.zeros(R, len(gbs), P + 2, dtype=torch.float64, device=dev)
-    ins = [torch.from_numpy(np.stack([inp[k] for inp in inputs])).to(dev) for k in range(len(inputs[0]))]
-    y = torch.from_numpy(np.stack(ys)).to(dev)
-    hd = None if ham_diag is None else torch.from_numpy(np.stack(ham_diag)).to(dev)
-    hps = [_lib.member_hparams(d.scale_coeff, d.ham_offset, d.ham_coeff, lr, d.ham_pauli) for d, lr in zip(descs, lrs)]
-    _lib.model_depth_sweep_train_steps(descs, hps, bounds, gbs, ins[0], ins[1] if len(ins) > 1 else None, y, params, rows, m_,
-                                       v_, 1, 0.9, 0.999, 1e-8, 0.0, ham_diag=hd)
-    _lib.check_status(dev)
-    return params.cpu(), m_.cpu(), v_.cpu(), rows.cpu()
+    return run_members(dev, 'depth', models, lrs, inputs, ys, bounds, gbs, ham_diag=ham_diag, sentinel=SENTINEL)
 
 
 def _bitwise(dev, models, lrs, inputs, ys, bounds, gbs, ham_diag=None, variant='packed'):

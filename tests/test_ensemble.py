@@ -10,7 +10,6 @@ descriptor, every step of all members as one launch per kernel (member = blockId
   every step), a ham_diag read-out, X read-out, HEAQNN Q5, and HEAQNN Q8 (the R-sequential fallback) -- match the oracle;
 * EnsembleSolver with seeds 0, 1, 2 matches three PTSolver runs made after set_random_seed(seed).
 """
-import copy
 import os
 
 import numpy as np
@@ -19,6 +18,8 @@ import torch
 
 from oracle import hea_oracle as O
 from oracle import c_oracle as C
+from tests.helpers import flat as _flat, heaqnn as _heaqnn, member_data as _data, oracle_adam as _oracle_adam
+from tests.helpers import quanonet as _quanonet, run_members, run_single as _run_single, schedule as _schedule
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -31,90 +32,8 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _quanonet(n, b_in, t_in, net, seed, **kw):
-    from quanonet_amd.models import QuanONetPT
-    torch.manual_seed(seed)
-    m = QuanONetPT(n, b_in, t_in, net, **kw).double()
-    rng = np.random.default_rng(seed)
-    with torch.no_grad():
-        if hasattr(m, 'branch_freq') and hasattr(m.branch_freq, 'bias'):
-            m.branch_freq.bias.copy_(torch.from_numpy(rng.normal(scale=0.3, size=m.branch_freq.bias.shape)))
-            m.trunk_freq.bias.copy_(torch.from_numpy(rng.normal(scale=0.3, size=m.trunk_freq.bias.shape)))
-        m.bias.fill_(0.1 * (seed + 1))
-    return m
-
-
-def _heaqnn(n, x_in, net, seed):
-    from quanonet_amd.models import HEAQNNPT
-    torch.manual_seed(seed)
-    return HEAQNNPT(n, x_in, net, scale_coeff=0.1, if_trainable_freq=True).double()
-
-
-def _flat(m):
-    return torch.cat([p.detach().reshape(-1) for p in m.parameters()])
-
-
-def _schedule(batch, steps=3, last=None):
-    sizes = [batch] * (steps - 1) + [last if last is not None else batch]
-    bounds = [0]
-    for s in sizes:
-        bounds.append(bounds[-1] + s)
-    return bounds, sizes
-
-
 def _run_ensemble(dev, desc, models, inputs, ys, bounds, gbs, lr, ham_diag=None):
-    from quanonet_amd import _lib
-    R = len(models)
-    params = torch.stack([_flat(m) for m in models]).to(dev).contiguous()
-    P = params.shape[1]
-    m_, v_ = torch.zeros_like(params), torch.zeros_like(params)
-    rows = torch.zeros(R, len(gbs), P + 2, dtype=torch.float64, device=dev)
-    ins = [torch.from_numpy(np.stack([inp[k] for inp in inputs])).to(dev) for k in range(len(inputs[0]))]   # [R, rows, width]
-    y = torch.from_numpy(np.stack(ys)).to(dev)
-    _lib.model_ensemble_train_steps(desc, bounds, gbs, ins[0], ins[1] if len(ins) > 1 else None, y, params, rows, m_, v_, 1,
-                                    lr, 0.9, 0.999, 1e-8, 0.0, ham_diag=ham_diag)
-    _lib.check_status(dev)
-    return params.cpu(), m_.cpu(), v_.cpu(), rows.cpu()
-
-
-def _run_single(dev, desc, model, inputs, y, bounds, gbs, lr, ham_diag=None):
-    from quanonet_amd import _lib
-    params = _flat(model).to(dev).contiguous()
-    P = params.numel()
-    m_, v_ = torch.zeros_like(params), torch.zeros_like(params)
-    rows = torch.zeros(len(gbs), P + 2, dtype=torch.float64, device=dev)
-    ins = [torch.from_numpy(t).to(dev) for t in inputs]
-    _lib.model_train_steps(desc, bounds, gbs, ins[0], ins[1] if len(ins) > 1 else None, torch.from_numpy(y).to(dev), params,
-                           rows, m_, v_, 1, lr, 0.9, 0.999, 1e-8, 0.0, ham_diag=ham_diag)
-    _lib.check_status(dev)
-    return params.cpu(), m_.cpu(), v_.cpu(), rows.cpu()
-
-
-def _oracle_adam(model, lossgrad, inputs, y, bounds, gbs, lr):
-    """oracle loss / gradients + torch.optim.Adam on a CPU copy: (rows [steps, P+2], final flat parameters)."""
-    cpu = copy.deepcopy(model).cpu()
-    names = [k for k, _ in cpu.named_parameters()]
-    params = [p for _, p in cpu.named_parameters()]
-    opt = torch.optim.Adam(params, lr=lr)
-    rows = []
-    for i, gb in enumerate(gbs):
-        lo, hi = bounds[i], bounds[i + 1]
-        sd = {k: v.detach().numpy() for k, v in cpu.state_dict().items()}
-        loss, grads = lossgrad(sd, [t[lo:hi] for t in inputs], y[lo:hi], gb)
-        flat = np.concatenate([np.asarray(grads[k], np.float64).reshape(-1) for k in names])
-        rows.append(np.concatenate([flat, [loss * gb, float((y[lo:hi] ** 2).sum())]]))
-        for k, p in zip(names, params):
-            p.grad = torch.from_numpy(np.asarray(grads[k], np.float64).reshape(p.shape).copy())
-        opt.step()
-    return np.stack(rows), np.concatenate([p.detach().numpy().reshape(-1) for p in params])
-
-
-def _data(R, n_rows, widths, seed):
-    rng = np.random.default_rng(seed)
-    inputs = [[rng.normal(size=(n_rows, w)) if k == 0 else rng.uniform(size=(n_rows, w)) for k, w in enumerate(widths)]
-              for _ in range(R)]
-    ys = [rng.normal(scale=0.5, size=n_rows) for _ in range(R)]
-    return inputs, ys
+    return run_members(dev, 'ensemble', models, [lr] * len(models), inputs, ys, bounds, gbs, ham_diag=ham_diag, desc=desc)
 
 
 HEADLINE = (5, 100, 2, (40, 2, 20, 2))

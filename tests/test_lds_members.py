@@ -17,7 +17,7 @@ import torch
 from tests.test_ensemble import _antideriv, _data, _flat, _heaqnn, _oracle_adam, _quanonet, _run_single, _schedule
 from tests.test_depth_sweep import _run_depth
 from tests.test_qubit_sweep import SENTINEL, _run_qubit
-from tests.helpers import kernels_launched as _kernels_launched
+from tests.helpers import kernels_launched as _kernels_launched, member_call
 
 pytestmark = pytest.mark.gpu
 
@@ -28,65 +28,19 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _hp(desc, lr):
-    from quanonet_amd import _lib
-    return _lib.member_hparams(desc.scale_coeff, desc.ham_offset, desc.ham_coeff, lr, desc.ham_pauli)
-
-
-def _tensors(dev, models, inputs, ys, n_steps):
-    params = torch.stack([_flat(m) for m in models]).to(dev).contiguous()
-    P = params.shape[1]
-    m_, v_ = torch.zeros_like(params), torch.zeros_like(params)
-    rows = torch.full((len(models), n_steps, P + 5), SENTINEL, dtype=torch.float64, device=dev)
-    ins = [torch.from_numpy(np.stack([inp[k] for inp in inputs])).to(dev) for k in range(len(inputs[0]))]
-    y = torch.from_numpy(np.stack(ys)).to(dev)
-    return params, m_, v_, rows, ins, y
-
-
 def _ensemble_call(dev, models, inputs, ys, bounds, gbs, lr, ham_diag=None):
     """(call, outputs): the ensemble call on fresh tensors, rows wider than P + 2 (SENTINEL tails)"""
-    from quanonet_amd import _lib
-    params, m_, v_, rows, ins, y = _tensors(dev, models, inputs, ys, len(gbs))
-    desc = models[0].fused_desc()
-
-    def call():
-        _lib.model_ensemble_train_steps(desc, bounds, gbs, ins[0], ins[1] if len(ins) > 1 else None, y, params, rows, m_, v_,
-                                        1, lr, 0.9, 0.999, 1e-8, 0.0, ham_diag=ham_diag)
-    return call, (params, m_, v_, rows)
+    return member_call(dev, 'ensemble', models, [lr] * len(models), inputs, ys, bounds, gbs, ham_diag=ham_diag,
+                       rows_sentinel=SENTINEL, rows_extra=3)
 
 
 def _sweep_call(dev, models, lrs, inputs, ys, bounds, gbs, ham_diag=None):
-    from quanonet_amd import _lib
-    params, m_, v_, rows, ins, y = _tensors(dev, models, inputs, ys, len(gbs))
-    descs = [m.fused_desc() for m in models]
-    hd = None if ham_diag is None else torch.from_numpy(np.stack(ham_diag)).to(dev)
-
-    def call():
-        _lib.model_sweep_train_steps(descs[0], [_hp(d, lr) for d, lr in zip(descs, lrs)], bounds, gbs, ins[0],
-                                     ins[1] if len(ins) > 1 else None, y, params, rows, m_, v_, 1, 0.9, 0.999, 1e-8, 0.0,
-                                     ham_diag=hd)
-    return call, (params, m_, v_, rows)
+    return member_call(dev, 'sweep', models, lrs, inputs, ys, bounds, gbs, ham_diag=ham_diag, rows_sentinel=SENTINEL,
+                       rows_extra=3)
 
 
 def _qubit_call(dev, models, lrs, inputs, ys, bounds, gbs):
-    from quanonet_amd import _lib
-    descs = [m.fused_desc() for m in models]
-    R, P = len(models), _lib.qubit_sweep_pmax(descs)
-    params = torch.zeros((R, P), dtype=torch.float64)
-    for i, m in enumerate(models):
-        f = _flat(m)
-        params[i, :f.numel()] = f
-    params = params.to(dev)
-    m_, v_ = torch.zeros_like(params), torch.zeros_like(params)
-    rows = torch.zeros((R, len(gbs), P + 2), dtype=torch.float64, device=dev)
-    ins = [torch.from_numpy(np.stack([inp[k] for inp in inputs])).to(dev) for k in range(len(inputs[0]))]
-    y = torch.from_numpy(np.stack(ys)).to(dev)
-    hps = [_hp(d, lr) for d, lr in zip(descs, lrs)]
-
-    def call():
-        _lib.model_qubit_sweep_train_steps(descs, hps, bounds, gbs, ins[0], ins[1] if len(ins) > 1 else None, y, params, rows,
-                                           m_, v_, 1, 0.9, 0.999, 1e-8, 0.0)
-    return call
+    return member_call(dev, 'qubit', models, lrs, inputs, ys, bounds, gbs)[0]
 
 
 def test_q10_ensemble_launches_do_not_grow_with_r(dev):

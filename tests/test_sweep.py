@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers import run_members
 from tests.test_ensemble import _antideriv, _data, _flat, _oracle_adam, _quanonet, _run_ensemble, _run_single, _schedule
 
 pytestmark = pytest.mark.gpu
@@ -28,26 +29,11 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _hp(desc, lr):
-    from quanonet_amd import _lib
-    return _lib.member_hparams(desc.scale_coeff, desc.ham_offset, desc.ham_coeff, lr, desc.ham_pauli)
-
-
 def _run_sweep(dev, desc, models, descs, lrs, inputs, ys, bounds, gbs, ham_diag=None):
-    from quanonet_amd import _lib
-    R = len(models)
-    params = torch.stack([_flat(m) for m in models]).to(dev).contiguous()
-    P = params.shape[1]
-    m_, v_ = torch.zeros_like(params), torch.zeros_like(params)
-    rows = torch.zeros(R, len(gbs), P + 2, dtype=torch.float64, device=dev)
-    ins = [torch.from_numpy(np.stack([inp[k] for inp in inputs])).to(dev) for k in range(len(inputs[0]))]
-    y = torch.from_numpy(np.stack(ys)).to(dev)
-    hd = None if ham_diag is None else torch.from_numpy(np.stack(ham_diag)).to(dev)
-    _lib.model_sweep_train_steps(desc, [_hp(d, lr) for d, lr in zip(descs, lrs)], bounds, gbs, ins[0],
-                                 ins[1] if len(ins) > 1 else None, y, params, rows, m_, v_, 1, 0.9, 0.999, 1e-8, 0.0,
-                                 ham_diag=hd)
-    _lib.check_status(dev)
-    return params.cpu(), m_.cpu(), v_.cpu(), rows.cpu()
+    """the sweep on `desc`'s shape; member m reads out as descs[m] (the members' own descriptors) with lrs[m]"""
+    assert all(d.ham_pauli == m.fused_desc().ham_pauli and d.scale_coeff == m.fused_desc().scale_coeff
+               for d, m in zip(descs, models))
+    return run_members(dev, 'sweep', models, lrs, inputs, ys, bounds, gbs, ham_diag=ham_diag, desc=desc)
 
 
 def _two_pipes(dev, variant, R, B):
