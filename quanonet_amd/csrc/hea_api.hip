@@ -166,64 +166,42 @@ struct PrepShared {
     GateZ gz[2][QHEA_MAX_QUBITS];           // [0]: this layer's gates, [1]: the previous layer's
     double2 half[2][3][QHEA_MAX_QUBITS];    // (cos, sin) of the half angles: one sincos per thread, not three in a row
 };
-// Record of layer l by a group of 64 threads (j = index within the group; threads of the block outside every group pass
-// j >= 64 and only join the two barriers).  wfetch(s, k, q) = ansatz angle w[s, k, q]: from global memory in
-// prep_zyz_kernel, from the block's freshly updated values where the reduce kernel writes the next step's records.
-// cur / prev = what layers l and l - 1 are (decode_layer(l < L ? l : -1), decode_layer(l - 1); the reduce kernel knows them
-// from its block index and skips the run table's integer divisions).
-template <class F>
-__device__ __forceinline__ void prep_layer_body(const LayerInfo& cur, const LayerInfo& prev, int n, int l, int j, F wfetch,
-                                                char* __restrict__ rec, char* __restrict__ srec, double* __restrict__ gmap,
-                                                PrepShared& sh) {
+// What the decomposition of gate (s, q) of ansatz sub-layer s = layer l leaves in memory besides its GateZ: the reduce kernel's
+// gradient-map entries, and -- sub-layer right after a full RX chunk -- the chunk's axes in the chunk's record (layer l - 1).
+__device__ __forceinline__ void gate_zyz_stores(const GateZ& g, const LayerInfo& prev, int n, int l, int s, int q,
+                                                char* __restrict__ rec, char* __restrict__ srec, double* __restrict__ gmap) {
 #pragma clang fp contract(off)
-    if (j < 0) j = 1 << 30;
-    if (j < 6 * n) {
-        // (j = which * 3n + k * n + q, without integer divisions: this runs between the Adam update and the records)
-        const int which = j >= 3 * n, r = j - (which ? 3 * n : 0), k = (r >= n) + (r >= 2 * n), q = r - k * n;
-        const LayerInfo& li = which ? prev : cur;
-        if (li.kind == 1) {
-            double sn, cn;
-            fast_sincos(0.5 * wfetch(li.s, k, q), &sn, &cn);
-            sh.half[which][k][q] = make_double2(cn, sn);
+    const double2 z = cmul(g.u, g.u);                    // e^{-i alpha}
+    double* gm = gmap + ((long)s * n + q) * kGmapDoubles;
+    // (everything written here is read by the NEXT launch: write-through stores, nothing left dirty in L2 for the
+    // end-of-kernel write-back -- which the next launch waits for)
+    store_through(reinterpret_cast<double2*>(gm), make_double2(g.cosb, g.sinb));
+    store_through(reinterpret_cast<double2*>(gm) + 1, make_double2(g.cosc, g.sinc));
+    store_through(reinterpret_cast<double2*>(gm) + 2, make_double2(z.x, -z.y));
+    // Sub-layer right after a full RX chunk: the chunk's gradients are read off THIS sub-layer's inner
+    // products (hea_zyz.hpp, bwd_ztri_kernel).  Between the two points lies W = prod_q RY(theta_q) RZ(beta_q),
+    // so Im<lam|X_q|psi> there = n . (X, Y, Z)_q here with n the axis of RY RZ X RZ^-1 RY^-1 =
+    // (cos beta cos theta, sin beta, -cos beta sin theta)  (the same for wire 4, whose gate runs as RY between
+    // RZ(+-pi/2): its Y there is that X).
+    // The three numbers ride in the chunk's own record (layer l - 1), whose RY part is otherwise unused.
+    if (prev.kind == 0 && prev.m == n && l >= 1) {
+        const double2 zb = cmul(g.v, g.v);               // e^{-i beta}
+        const double cb = zb.x, sb = -zb.y, ct = g.c * g.c - g.s * g.s, st = 2.0 * g.c * g.s;
+        double* em = reinterpret_cast<double*>(rec + (long)(l - 1) * kRecBytes + kRecRy) + 3 * q;
+        store_through(em, cb * ct); store_through(em + 1, sb); store_through(em + 2, -cb * st);
+        if (srec) {     // ... and in its split record, for the chains that walk back in the split layout (bwd_zquad_kernel)
+            double* es = reinterpret_cast<double*>(srec + (long)(l - 1) * kRecBytes + kSRecRy) + 3 * q;
+            store_through(es, cb * ct); store_through(es + 1, sb); store_through(es + 2, -cb * st);
         }
     }
-    __syncthreads();
-    QHEA_STAMP(5);
-    if (j < 2 * n) {                                   // one decomposition per thread, then everybody multiplies phasors
-        const int which = j >= n, q = j - (which ? n : 0);
-        const LayerInfo& li = which ? prev : cur;
-        if (li.kind == 1) {
-            const GateZ g = gate_zyz(sh.half[which][0][q], sh.half[which][1][q], sh.half[which][2][q]);
-            sh.gz[which][q] = g;
-            if (which == 0) {
-                const double2 z = cmul(g.u, g.u);                    // e^{-i alpha}
-                double* gm = gmap + ((long)li.s * n + q) * kGmapDoubles;
-                // (everything this body writes is read by the NEXT launch: write-through stores, nothing left dirty in L2 for the
-                // end-of-kernel write-back -- which the next launch waits for)
-                store_through(reinterpret_cast<double2*>(gm), make_double2(g.cosb, g.sinb));
-                store_through(reinterpret_cast<double2*>(gm) + 1, make_double2(g.cosc, g.sinc));
-                store_through(reinterpret_cast<double2*>(gm) + 2, make_double2(z.x, -z.y));
-                // Sub-layer right after a full RX chunk: the chunk's gradients are read off THIS sub-layer's inner
-                // products (hea_zyz.hpp, bwd_ztri_kernel).  Between the two points lies W = prod_q RY(theta_q) RZ(beta_q),
-                // so Im<lam|X_q|psi> there = n . (X, Y, Z)_q here with n the axis of RY RZ X RZ^-1 RY^-1 =
-                // (cos beta cos theta, sin beta, -cos beta sin theta)  (the same for wire 4, whose gate runs as RY between
-                // RZ(+-pi/2): its Y there is that X).
-                // The three numbers ride in the chunk's own record (layer l - 1), whose RY part is otherwise unused.
-                if (prev.kind == 0 && prev.m == n && l >= 1) {
-                    const double2 zb = cmul(g.v, g.v);               // e^{-i beta}
-                    const double cb = zb.x, sb = -zb.y, ct = g.c * g.c - g.s * g.s, st = 2.0 * g.c * g.s;
-                    double* em = reinterpret_cast<double*>(rec + (long)(l - 1) * kRecBytes + kRecRy) + 3 * q;
-                    store_through(em, cb * ct); store_through(em + 1, sb); store_through(em + 2, -cb * st);
-                    if (srec) {     // ... and in its split record, for the chains that walk back in the split layout (bwd_zquad_kernel)
-                        double* es = reinterpret_cast<double*>(srec + (long)(l - 1) * kRecBytes + kSRecRy) + 3 * q;
-                        store_through(es, cb * ct); store_through(es + 1, sb); store_through(es + 2, -cb * st);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    QHEA_STAMP(6);
+}
+
+// The stores of record l by a group of 64 threads (j = index within the group, >= 64: none) from the decompositions of
+// layer l's gates (zc: cur is an ansatz sub-layer) and of layer l - 1's (zp: prev is one); zc / zp are not read otherwise.
+__device__ __forceinline__ void prep_layer_records(const LayerInfo& cur, const LayerInfo& prev, int n, int l, int j,
+                                                   const GateZ* zc, const GateZ* zp,
+                                                   char* __restrict__ rec, char* __restrict__ srec) {
+#pragma clang fp contract(off)
     char* out = rec + (long)l * kRecBytes;
     if (j < (1 << n)) {
         // products of up to five unit phasors as trees of depth 3 ((f0 f1)(f2 f3)) f4 -- this thread's chain of dependent
@@ -239,13 +217,13 @@ __device__ __forceinline__ void prep_layer_body(const LayerInfo& cur, const Laye
         if (cur.kind == 1) {
             double2 vq[QHEA_MAX_QUBITS];
 #pragma unroll
-            for (int q = 0; q < 5; ++q) vq[q] = sh.gz[0][q < n ? q : 0].v;
+            for (int q = 0; q < 5; ++q) vq[q] = zc[q < n ? q : 0].v;
             ph = tree(vq, j);
         }
         if (prev.kind == 1) {
             double2 uq[QHEA_MAX_QUBITS];
 #pragma unroll
-            for (int q = 0; q < 5; ++q) uq[q] = sh.gz[1][q < n ? q : 0].u;
+            for (int q = 0; q < 5; ++q) uq[q] = zp[q < n ? q : 0].u;
             const double2 pu = tree(uq, ring_src_index(n, j));
             ph = cur.kind == 1 ? cmul(ph, pu) : pu;
         }
@@ -271,14 +249,49 @@ __device__ __forceinline__ void prep_layer_body(const LayerInfo& cur, const Laye
     } else if (j >= 32 && j < 32 + 2 * n) {
         const int q = (j - 32) >> 1, var = (j - 32) & 1;
         if (cur.kind == 1) {    // (an RX chunk's record keeps this part for the next sub-layer's axes, written by ITS block)
-            double2 e = make_double2(sh.gz[0][q].c, var ? sh.gz[0][q].s : -sh.gz[0][q].s);
+            double2 e = make_double2(zc[q].c, var ? zc[q].s : -zc[q].s);
             store_through(reinterpret_cast<double2*>(out + kRecRy + q * 32 + var * 16), e);
             if (srec) {     // wire 4: the swap form's variants (c, -s) / (s, c)
-                if (q == 4 && var == 1) e = make_double2(sh.gz[0][q].s, sh.gz[0][q].c);
+                if (q == 4 && var == 1) e = make_double2(zc[q].s, zc[q].c);
                 store_through(reinterpret_cast<double2*>(srec + (long)l * kRecBytes + kSRecRy + q * 32 + var * 16), e);
             }
         }
     }
+}
+
+// Record of layer l by a group of 64 threads (j = index within the group; threads of the block outside every group pass
+// j >= 64 and only join the two barriers).  wfetch(s, k, q) = ansatz angle w[s, k, q] (prep_zyz_kernel: from global memory).
+// cur / prev = what layers l and l - 1 are (decode_layer(l < L ? l : -1), decode_layer(l - 1)).  (The reduce kernel that
+// writes the next step's records does the first two phases per gate in the lanes of its Adam update instead, and then
+// prep_layer_records: the same functions on the same values.)
+template <class F>
+__device__ __forceinline__ void prep_layer_body(const LayerInfo& cur, const LayerInfo& prev, int n, int l, int j, F wfetch,
+                                                char* __restrict__ rec, char* __restrict__ srec, double* __restrict__ gmap,
+                                                PrepShared& sh) {
+#pragma clang fp contract(off)
+    if (j < 0) j = 1 << 30;
+    if (j < 6 * n) {
+        // (j = which * 3n + k * n + q, without integer divisions)
+        const int which = j >= 3 * n, r = j - (which ? 3 * n : 0), k = (r >= n) + (r >= 2 * n), q = r - k * n;
+        const LayerInfo& li = which ? prev : cur;
+        if (li.kind == 1) {
+            double sn, cn;
+            fast_sincos(0.5 * wfetch(li.s, k, q), &sn, &cn);
+            sh.half[which][k][q] = make_double2(cn, sn);
+        }
+    }
+    __syncthreads();
+    if (j < 2 * n) {                                   // one decomposition per thread, then everybody multiplies phasors
+        const int which = j >= n, q = j - (which ? n : 0);
+        const LayerInfo& li = which ? prev : cur;
+        if (li.kind == 1) {
+            const GateZ g = gate_zyz(sh.half[which][0][q], sh.half[which][1][q], sh.half[which][2][q]);
+            sh.gz[which][q] = g;
+            if (which == 0) gate_zyz_stores(g, prev, n, l, li.s, q, rec, srec, gmap);
+        }
+    }
+    __syncthreads();
+    prep_layer_records(cur, prev, n, l, j, sh.gz[0], sh.gz[1], rec, srec);
 }
 
 // (ensemble launches: member blockIdx.y's angles and workspace slice; the header is slice 0's, whoever the member)
@@ -331,13 +344,13 @@ __device__ __forceinline__ double2 slice_sum2(const double2* __restrict__ p, lon
 
 // grad_w[s,{0,1,2},q] from the per-wave (X,Y,Z) partial sums (column sums over waves of partial[wave][s][kw]).
 //   g_c = Y;  g_b = cos(c) Z + sin(c) X;  g_a = cos(b) Y - sin(b) cos(c) X + sin(b) sin(c) Z
-__device__ __forceinline__ void reduce_xyz_block(int bid, int n, int blk, int kw, long nwaves,
+// Returns, in the lanes that own an angle (slice 0, see `tri`), the angle after the update (or as it was: no update); 0 elsewhere.
+__device__ __forceinline__ double reduce_xyz_block(int bid, int n, int blk, int kw, long nwaves,
                                                  const double* __restrict__ partial, const double* w /* may alias adam->p */,
                                                  double* __restrict__ grad_w, double* acc /*[kRedThreads]*/, double* stage /*[8 * cols]: LDS apart from acc*/,
                                                  bool poisoned, const double* gmap /* ZYZ-form sums, or nullptr (the fused path rewrites the block's own entries at its end) */,
                                                  const AdamArgs* adam = nullptr, long adam_base = 0,
                                                  int cols_block = 0 /* columns per block if not red_cols(kw) */,
-                                                 double* newp = nullptr /* LDS [cols_block / kw][3][n]: the block's angles after the update */,
                                                  const DpX* dp = nullptr /* data-parallel step: exchange this block's gradients before the update */,
                                                  int* dp_failed = nullptr /* one int of LDS */,
                                                  double* dp_loc = nullptr /* LDS [kDpBlockValues] */,
@@ -357,7 +370,7 @@ __device__ __forceinline__ void reduce_xyz_block(int bid, int n, int blk, int kw
     const int s_fin = v >> lk, r_fin = v & (kw - 1), q_fin = r_fin / 3;
     // Gate (s, q)'s three columns X, Y, Z sit in three adjacent lanes: the X lane (`fin`) turns the sums into the gradients of
     // the gate's three angles, then each of the three lanes (`tri`, role k3) owns ONE angle: its gradient-row entry, its Adam
-    // update (three in parallel instead of three in a row), its entry of newp.
+    // update (three in parallel instead of three in a row), its updated value returned.
     const int k3 = r_fin % 3;
     const bool tri = slice == 0 && v < ncols && r_fin < 3 * n;
     const bool fin = tri && k3 == 0;
@@ -388,9 +401,20 @@ __device__ __forceinline__ void reduce_xyz_block(int bid, int n, int blk, int kw
     constexpr int kStage = 8;
     // (the first stage's results go to a region of their own and the X lane adds the second stage of its gate's three columns
     // itself -- the same additions in the same order as a thread per column would make: two barriers instead of four)
+    // (64 slices, every n <= 5: both stages unrolled, their LDS reads issued together instead of one round trip per term --
+    // the additions and their order are those of the loops)
+    constexpr int kFull = kStage * kStage;
     double t8 = 0.0;
     if (slice < kStage) {
-        for (int i = slice; i < nslices; i += kStage) t8 += acc[i * cols + j];
+        if (nslices == kFull) {
+            double a[kFull / kStage];
+#pragma unroll
+            for (int m = 0; m < kFull / kStage; ++m) a[m] = acc[(slice + m * kStage) * cols + j];
+#pragma unroll
+            for (int m = 0; m < kFull / kStage; ++m) t8 += a[m];
+        } else {
+            for (int i = slice; i < nslices; i += kStage) t8 += acc[i * cols + j];
+        }
         stage[slice * cols + j] = t8;
     }
     __syncthreads();
@@ -403,8 +427,15 @@ __device__ __forceinline__ void reduce_xyz_block(int bid, int n, int blk, int kw
     // (the lanes of slice 0 are all in wave 0: wave shuffles, executed by every wave alike, no barrier)
     double own = 0.0;
     if (tri) {
-        const int m = nslices < kStage ? nslices : kStage;
-        for (int i = 0; i < m; ++i) own += stage[i * cols + j];
+        if (nslices >= kStage) {
+            double a[kStage];
+#pragma unroll
+            for (int i = 0; i < kStage; ++i) a[i] = stage[i * cols + j];
+#pragma unroll
+            for (int i = 0; i < kStage; ++i) own += a[i];
+        } else {
+            for (int i = 0; i < nslices; ++i) own += stage[i * cols + j];
+        }
     }
     const double Yn = __shfl_down(own, 1), Zn = __shfl_down(own, 2);
     if (fin) {
@@ -444,15 +475,15 @@ __device__ __forceinline__ void reduce_xyz_block(int bid, int n, int blk, int kw
     const int bad_x = (ga == ga && gb == gb && gc == gc) ? 0 : 1;
     const double gb_n = __shfl_up(gb, 1), gc_n = __shfl_up(gc, 2);
     const int bad_1 = __shfl_up(bad_x, 1), bad_2 = __shfl_up(bad_x, 2);
+    double pn = 0.0;
     if (tri) {
         const double g = k3 == 0 ? ga : k3 == 1 ? gb_n : gc_n;
         const bool skip = poisoned || (k3 == 0 ? bad_x : k3 == 1 ? bad_1 : bad_2) != 0;
         store_through(&grad_w[(long)s * 3 * n + k3 * n + q], g);
-        double pn = ap;
+        pn = ap;
         if (upd && !skip) pn = adam_update_pre(*adam, my_idx, g, ap, am, av);     // this lane alone reads and writes this angle
-        if (newp)                                // (only with an update pending: ap holds the current angle)
-            newp[(s - ((bid * cols) >> lk)) * 3 * n + k3 * n + q] = pn;
     }
+    return pn;
 }
 
 __global__ __launch_bounds__(kRedThreads) void reduce_kernel(int n, int blk, int kw, long nwaves,
@@ -963,18 +994,37 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
     const unsigned long long st0 = __builtin_amdgcn_s_memtime();
 #endif
     if constexpr (FUSE) if (bid < nb_w) {           // (block-uniform)
-        __shared__ PrepShared psh[2 * kFuseMaxLd];          // one per record group: nbk x (ld + 1) <= 4
-        __shared__ double newp[kFuseMaxLd * 3 * QHEA_MAX_QUBITS];
+        __shared__ GateZ fgz[kFuseMaxLd][QHEA_MAX_QUBITS];     // the decompositions of the block's nbk x ld <= 2 sub-layers
         __shared__ double accbig[2 * kRedThreads];
-        reduce_xyz_block(bid, n, blk, kw, nwaves, partial, w, grad + gm.off_ans, accbig, acc, hdr->status != 0, gmap, &adam,
-                         gm.off_ans, fp.nbk * fp.ld * kw, newp, dp, &dp_failed, dp_loc, dp_xch);
+        const double pn = reduce_xyz_block(bid, n, blk, kw, nwaves, partial, w, grad + gm.off_ans, accbig, acc, hdr->status != 0,
+                                           gmap, &adam, gm.off_ans, fp.nbk * fp.ld * kw, dp, &dp_failed, dp_loc, dp_xch);
         QHEA_STAMP(3);
+        // The next step's records.  Sincos and decomposition per gate in the lanes that have just updated its angles (wave 0:
+        // lane 3q + k of sub-layer column group sl owns angle k of gate q), with no barrier: the lane of an angle takes the
+        // (cos, sin) of its half angle, the gate's k = 0 lane gathers the other two by wave shuffles and decomposes the gate --
+        // the functions and operands of prep_layer_body, so the records are bitwise those of prep_zyz_kernel.  Then one
+        // barrier, and the record groups multiply phasors.
+        const int tid = (int)threadIdx.x, lk = __builtin_ctz(kw), s0 = bid * fp.nbk * fp.ld, per = 1 + fp.ld;
+        const int sl = tid >> lk, r = tid & (kw - 1), q = r / 3, k3 = r - 3 * q;
+        const bool tri = tid < fp.nbk * fp.ld * kw && r < 3 * n && s0 + sl < blk;     // (reduce_xyz_block's `tri` lanes)
+        double sn = 0.0, cn = 1.0;
+        if (tri) fast_sincos(0.5 * pn, &sn, &cn);
+        QHEA_STAMP(5);
+        const double2 hb = make_double2(__shfl_down(cn, 1), __shfl_down(sn, 1));
+        const double2 hc = make_double2(__shfl_down(cn, 2), __shfl_down(sn, 2));
+        if (tri && k3 == 0) {
+            const GateZ gz = gate_zyz(make_double2(cn, sn), hb, hc);
+            fgz[sl][q] = gz;
+            const int cq = sl >= fp.ld ? 1 : 0, g = sl - cq * fp.ld;      // sub-layer g of the block's circuit block cq
+            const LayerInfo before = g == 0 ? LayerInfo{0, 0, n} : LayerInfo{1, s0 + sl - 1, 0};
+            gate_zyz_stores(gz, before, n, (bid * fp.nbk + cq) * per + 1 + g, s0 + sl, q, fp.rec, fp.srec, fp.gmap);
+        }
+        QHEA_STAMP(6);
         __syncthreads();
         QHEA_STAMP(4);
-        const int grp = (int)threadIdx.x >> 6, j = (int)threadIdx.x & 63;
+        const int grp = tid >> 6, j = tid & 63;
         // record groups of 64 threads: for each of the reduce block's nbk circuit blocks, its ld sub-layers' records and the
         // FOLLOWING chunk's record (whose diagonal takes this block's last sub-layer through the ring)
-        const int per = 1 + fp.ld, s0 = bid * fp.nbk * fp.ld;
         const bool act = grp < fp.nbk * per;
         const int cq = grp >= per ? 1 : 0;                 // (grp / per for the active groups: nbk <= 2)
         const int cb = bid * fp.nbk + cq, g = grp - cq * per;
@@ -984,15 +1034,15 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         const LayerInfo none{2, 0, 0}, chunk{0, 0, n};
         const LayerInfo cur = !act ? chunk : g < fp.ld ? LayerInfo{1, cb * fp.ld + g, 0} : (l < fp.L ? chunk : none);
         const LayerInfo prev = !act ? none : g == 0 ? chunk : LayerInfo{1, cb * fp.ld + g - 1, 0};
-        prep_layer_body(cur, prev, n, l, act ? j : -1,
-                        [&](int s, int k, int q) { return newp[(s - s0) * 3 * n + k * n + q]; }, fp.rec, fp.srec, fp.gmap,
-                        psh[act ? grp : 0]);
+        const int zi = act ? cq * fp.ld + g : 0;           // (the group's sub-layers' gates: zc = this record's, zp = the one before)
+        prep_layer_records(cur, prev, n, l, act ? j : 64, fgz[cur.kind == 1 ? zi : 0], fgz[prev.kind == 1 ? zi - 1 : 0],
+                           fp.rec, fp.srec);
 #ifdef QHEA_REDUCE_STAMPS
         if (threadIdx.x == 0 && bid == 30) {
             const unsigned long long e = __builtin_amdgcn_s_memtime();
             const unsigned long long* t = qhea_stamps;
-            printf("reduce block 30: prologue %llu, first slice %llu | loads+slice sums %llu | tree %llu | finish+adam (thread 0) %llu | barrier %llu | sincos %llu | decomposition %llu | phasors+stores %llu | total %llu clk\n",
-                   t[7] - t[0], t[8] - t[7], t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], e - t[6], e - t[0]);
+            printf("reduce block 30: prologue %llu, first slice %llu | loads+slice sums %llu | tree %llu | finish+adam (thread 0) %llu | sincos %llu | decomposition %llu | barrier %llu | phasors+stores %llu | total %llu clk\n",
+                   t[7] - t[0], t[8] - t[7], t[1] - t[0], t[2] - t[1], t[3] - t[2], t[5] - t[3], t[6] - t[5], t[4] - t[6], e - t[4], e - t[0]);
         }
 #endif
         return;
@@ -1003,7 +1053,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
     const double kNaN = std::numeric_limits<double>::quiet_NaN();
     if (bid < nb_w) {
         reduce_xyz_block(bid, n, blk, kw, nwaves, partial, w, grad + g_ans(), acc, acc2, status != 0, gmap, &adam, g_ans(),
-                         0, nullptr, dp, &dp_failed, dp_loc, dp_xch);
+                         0, dp, &dp_failed, dp_loc, dp_xch);
     } else if (bid < nb_w + nb_x) {
         const int j = threadIdx.x % kFreqCols, slice = threadIdx.x / kFreqCols;
         const int e = (bid - nb_w) * kFreqCols + j;
@@ -1012,8 +1062,25 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         if (e < E) {
             si = e < nc0() ? 0 : 1;
             if (si) ee = e - nc0();
-            const EncSeg& sg = enc.seg[si];
-            const double* __restrict__ in = sg.in + mem * ms.rows * sg.width + ee % sg.width;
+        }
+        // The segment's GradMap entries and input, chosen by a select between both segments' values: indexed by the run-time si
+        // they were loads from the kernel arguments' memory -- a dependent round trip before the first load of the sums (the
+        // input), and one after them before each store (the GradMap entries, read where they were used).
+        long ow, ob;
+        if constexpr (DEPTH) { ow = si ? d_w1 : d_w0; ob = si ? d_b1 : d_b0; }
+        else { ow = si ? gm.off_w[1] : gm.off_w[0]; ob = si ? gm.off_b[1] : gm.off_b[0]; }
+        auto g_w = [ow]() -> long { return ow; };
+        auto g_b = [ob]() -> long { return ob; };
+        const bool mine = slice == 0 && e < E && g_w() >= 0;
+        // the lane that updates column e's bias and weight loads their Adam state now: it travels with the sums, not after them
+        double pb = 0.0, mb = 0.0, vb = 0.0, pw = 0.0, mw = 0.0, vw = 0.0;
+        if (mine && adam.p) {
+            pb = adam.p[g_b() + ee]; mb = adam.m[g_b() + ee]; vb = adam.v[g_b() + ee];
+            pw = adam.p[g_w() + ee]; mw = adam.m[g_w() + ee]; vw = adam.v[g_w() + ee];
+        }
+        if (e < E) {
+            const int width = si ? enc.seg[1].width : enc.seg[0].width;
+            const double* __restrict__ in = (si ? enc.seg[1].in : enc.seg[0].in) + mem * ms.rows * width + ee % width;
             const double* __restrict__ gx = grad_x + e;
             long b = slice;
             for (; b + 15L * kFreqSlices < B; b += 16L * kFreqSlices) {    // 32 loads in flight per thread: B = 1024 in ONE round trip
@@ -1021,7 +1088,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     g[i] = gx[(b + (long)i * kFreqSlices) * E];
-                    v[i] = in[(b + (long)i * kFreqSlices) * sg.width];
+                    v[i] = in[(b + (long)i * kFreqSlices) * width];
                 }
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { s0 += g[i]; s1 += g[i] * v[i]; }
@@ -1031,7 +1098,7 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     g[i] = gx[(b + (long)i * kFreqSlices) * E];
-                    v[i] = in[(b + (long)i * kFreqSlices) * sg.width];
+                    v[i] = in[(b + (long)i * kFreqSlices) * width];
                 }
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { s0 += g[i]; s1 += g[i] * v[i]; }
@@ -1039,28 +1106,35 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             for (; b < B; b += kFreqSlices) {
                 const double g = gx[b * E];
                 s0 += g;
-                s1 += g * in[b * sg.width];
+                s1 += g * in[b * width];
             }
         }
+#ifdef QHEA_REDUCE_STAMPS
+        const unsigned long long f_loads = __builtin_amdgcn_s_memtime();
+#endif
         acc[slice * kFreqCols + j] = s0; acc2[slice * kFreqCols + j] = s1;
         __syncthreads();
-        // slices combined in two fixed-order stages (kFreqStage interleaved groups, then those), as reduce_xyz_block does
+        // slices combined in two fixed-order stages (kFreqStage interleaved groups, then those), as reduce_xyz_block does;
+        // both stages run in wave 0 (slices < kFreqStage are its lanes), so the second takes the first's sums by wave shuffles
+        static_assert(kFreqStage * kFreqCols == 64, "the frequency blocks' first-stage sums are wave 0's lanes");
         double u0 = 0.0, u1 = 0.0;
-        if (slice < kFreqStage)
-            for (int i = slice; i < kFreqSlices; i += kFreqStage) { u0 += acc[i * kFreqCols + j]; u1 += acc2[i * kFreqCols + j]; }
-        __syncthreads();
-        if (slice < kFreqStage) { acc[slice * kFreqCols + j] = u0; acc2[slice * kFreqCols + j] = u1; }
-        __syncthreads();
-        // (read where they are used, as the segment's GradMap entries always were)
-        auto g_w = [&]() -> long { if constexpr (DEPTH) return si ? d_w1 : d_w0; else return gm.off_w[si]; };
-        auto g_b = [&]() -> long { if constexpr (DEPTH) return si ? d_b1 : d_b0; else return gm.off_b[si]; };
-        const bool mine = slice == 0 && e < E && g_w() >= 0;
+        if (slice < kFreqStage) {       // (unrolled: the LDS reads issued together, the additions in the loop's order)
+            double a0[kFreqSlices / kFreqStage], a1[kFreqSlices / kFreqStage];
+#pragma unroll
+            for (int m = 0; m < kFreqSlices / kFreqStage; ++m) {
+                a0[m] = acc[(slice + m * kFreqStage) * kFreqCols + j]; a1[m] = acc2[(slice + m * kFreqStage) * kFreqCols + j];
+            }
+#pragma unroll
+            for (int m = 0; m < kFreqSlices / kFreqStage; ++m) { u0 += a0[m]; u1 += a1[m]; }
+        }
         double t0 = 0.0, t1 = 0.0;
         bool skip = status != 0;
-        if (mine) {
-            for (int i = 0; i < kFreqStage; ++i) { t0 += acc[i * kFreqCols + j]; t1 += acc2[i * kFreqCols + j]; }
-            if (skip) t0 = t1 = kNaN;
+#pragma unroll
+        for (int i = 0; i < kFreqStage; ++i) {          // (every lane shuffles; the `mine` lanes' sums are the ones used)
+            const double x0 = __shfl(u0, i * kFreqCols + j), x1 = __shfl(u1, i * kFreqCols + j);
+            t0 += x0; t1 += x1;
         }
+        if (mine && skip) t0 = t1 = kNaN;
         if constexpr (DP) {
             // the block's exchanged values, compacted: (bias, weight) gradient of every column of a trainable segment (the
             // `mine` threads are lanes 0 .. kFreqCols-1 of wave 0)
@@ -1082,13 +1156,20 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
         if (mine) {
             store_through(&grad[g_b() + ee], t0);
             store_through(&grad[g_w() + ee], t1);
-            if (adam.p && !skip) { adam_update(adam, g_b() + ee, t0); adam_update(adam, g_w() + ee, t1); }
+            if (adam.p && !skip) {
+                adam_update_pre(adam, g_b() + ee, t0, pb, mb, vb);
+                adam_update_pre(adam, g_w() + ee, t1, pw, mw, vw);
+            }
         }
 #ifdef QHEA_REDUCE_STAMPS
-        if (threadIdx.x == 0 && bid == nb_w) printf("reduce freq block: %llu clk\n", __builtin_amdgcn_s_memtime() - st0);
+        if (threadIdx.x == 0 && bid == nb_w)
+            printf("reduce freq block: loads+sums %llu | stages+adam %llu | total %llu clk\n", f_loads - st0,
+                   __builtin_amdgcn_s_memtime() - f_loads, __builtin_amdgcn_s_memtime() - st0);
 #endif
     } else {
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        double pb = 0.0, mb = 0.0, vb = 0.0;           // the bias's Adam state, loaded with the sums (frequency blocks: the same)
+        if (threadIdx.x == 0 && gm.off_bias >= 0 && adam.p) { pb = adam.p[gm.off_bias]; mb = adam.m[gm.off_bias]; vb = adam.v[gm.off_bias]; }
         for (long b = threadIdx.x; b < B; b += kRedThreads) {
             const double r = pred[b] - y[b];
             s0 += r * r; s1 += r; s2 += y[b] * y[b];
@@ -1129,9 +1210,12 @@ __global__ __launch_bounds__(kRedThreads) void reduce_model_kernel(
             store_through(&grad[g_sse() + 1], sy2);
             if (gm.off_bias >= 0) {
                 store_through(&grad[gm.off_bias], gbias);
-                if (adam.p && !skip) adam_update(adam, gm.off_bias, gbias);
+                if (adam.p && !skip) adam_update_pre(adam, gm.off_bias, gbias, pb, mb, vb);
             }
         }
+#ifdef QHEA_REDUCE_STAMPS
+        if (threadIdx.x == 0) printf("reduce tail block: %llu clk\n", __builtin_amdgcn_s_memtime() - st0);
+#endif
     }
 }
 
