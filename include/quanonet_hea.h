@@ -231,6 +231,62 @@ int qhea_model_forward(const qhea_model_desc* desc, int64_t batch,
                        double* pred /*DEVICE [B]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Noisy forward: pred[b] = the model under depolarizing gate noise and readout error, estimated from Monte-Carlo
+ * trajectories or from sampled shots; stderr_out[b] (optional) its standard error.  Replaces the deployment half of the
+ * reference's ibm_inference.py: `Estimator` with `options.default_shots = S` (shot mode) and, for p1 = p2 = readout = 0,
+ * `StatevectorEstimator` (the "Ideal Simulator" line).
+ *
+ * Noise model (the circuit above; locations in circuit order, which is also the order random numbers are consumed in):
+ *   - after each encoding RX, wires 0..n-1: one-qubit depolarizing with probability p1 (X, Y, Z each p1/3);
+ *   - after each wire's trainable rotation RY RZ RY (ONE single-qubit gate, as hardware compiles it), wires 0..n-1 of each
+ *     sub-layer: the same channel, p1;
+ *   - after each CNOT of the ring CNOT(1->0), CNOT(2->1), ..., CNOT(0->n-1): two-qubit depolarizing with probability p2 on
+ *     (control, target), each of the 15 non-identity Pauli pairs p2/15;
+ *   - readout: every measured bit flips independently with probability q = readout.
+ *   A block has n + 2 n ld locations: its n encoding locations, then per sub-layer n rotation locations and n CNOT locations.
+ * Estimators:
+ *   - expectation mode (shots = 0, trajectories = T >= 1): a trajectory's value is the exact read-out of its final state
+ *     with the readout error folded in: H -> offset + coeff (1 - 2q) sum_i P_i, or, with ham_diag,
+ *     diag'[k] = sum_j prod_i (bit_i(j) != bit_i(k) ? q : 1 - q) diag[j];  pred = mean over the T trajectories + bias.
+ *   - shot mode (shots = S >= 1): every shot is its own trajectory and ends in one bitstring k drawn from |psi|^2 (after a
+ *     noiseless basis change for X / Y read-outs: H for X, H S^dagger for Y), then readout flips; the shot's value is
+ *     offset + coeff sum_i (1 - 2 b_i), or diag[k] with ham_diag;  pred = mean over the S shots + bias.  (What an Estimator
+ *     with default_shots = S estimates for the reference's sum-Z Hamiltonian.)
+ *   stderr_out = sample standard deviation of the row's T (or S) values / sqrt(T) (0 for a single value).
+ *   p1 = p2 = q = 0 in expectation mode gives the ideal model output.
+ * Random numbers: Philox4x32-10, key = (low, high word of seed), counter = (c, trajectory, row_lo, row_hi) with the GLOBAL row
+ * index row0 + b, so a row's draws depend on (seed, row, trajectory) only -- not on the batch, the chunking or the launch.
+ *   - noise location l uses words 2 (l mod 2) and 2 (l mod 2) + 1 (w0, w1) of call c = floor(l / 2): an error occurs iff
+ *     w0 < floor(p 2^32) (64-bit comparison, so p = 1 always fires); the Pauli is (w1 * 3) >> 32 -> X, Y, Z for one qubit,
+ *     or k = 1 + ((w1 * 15) >> 32) for two: control Pauli k >> 2, target Pauli k & 3 (0 I, 1 X, 2 Y, 3 Z).
+ *   - shot mode, with L = the circuit's location count and m = ceil(L / 2): u = ((a >> 5) 2^26 + (b >> 6)) 2^-53 from words
+ *     (0, 1) of call m; the outcome is the first k with u < cdf[k] (|psi_k|^2 accumulated in index order in fp64; if none,
+ *     the last k with |psi_k|^2 > 0); bit i (i < n) flips iff word (2 + i) mod 4 of call m + (2 + i) / 4 is < floor(q 2^32).
+ * Summation: a row's values are added in a fixed order (trajectories in tiles of 64, slots of 64 / 2^n lanes, then tiles in
+ * order; no atomics), so results are bitwise reproducible and the same for any chunking.  Errors are applied as Pauli strings
+ * up to a global phase (expectations and sampling probabilities are exactly those of gate-by-gate insertion).
+ * Scope: n = 2..6, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.
+ * Errors, all before anything is launched: QHEA_EINVAL for p1, p2 or readout outside [0, 1], shots < 0, trajectories < 1 in
+ * expectation mode (or more than 2^32 - 1 values per row); QHEA_EUNSUPPORTED for n >= 7.  Launches: the prep kernel, the
+ * trajectory kernel, one finishing kernel; no allocation, no synchronisation (hipGraph-capturable).
+ */
+typedef struct qhea_noise {
+    double   p1, p2, readout;   /* depolarizing after each 1q gate / each CNOT; bit-flip per measured bit */
+    int64_t  shots;             /* 0: expectation mode; S >= 1: shot mode (one trajectory per shot)    */
+    int64_t  trajectories;      /* expectation mode: T >= 1 (ignored in shot mode)                     */
+    uint64_t seed;
+} qhea_noise;
+
+/* DEVICE scratch bytes for qhea_model_forward_noisy on `batch` rows (0 on a bad descriptor or noise setting). */
+size_t qhea_model_noisy_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise);
+int    qhea_model_forward_noisy(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                const qhea_noise* noise /*HOST*/,
+                                double* pred /*DEVICE [B]*/, double* stderr_out /*DEVICE [B] or NULL*/,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the
  * SAME parameters -- the chunk loop of PTSolver.evaluate / infer.predict (solvers/solver_pt.py:299-310, infer.py:274-289) in
  * one host call.  The layer records depend on the parameters alone, so one preparation launch serves all chunks of

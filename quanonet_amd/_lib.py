@@ -33,7 +33,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_ensemble_workspace_bytes', 'qhea_model_ensemble_train_steps',
            'qhea_model_sweep_workspace_bytes', 'qhea_model_sweep_train_steps',
            'qhea_model_depth_sweep_workspace_bytes', 'qhea_model_depth_sweep_train_steps',
-           'qhea_model_qubit_sweep_workspace_bytes', 'qhea_model_qubit_sweep_train_steps']
+           'qhea_model_qubit_sweep_workspace_bytes', 'qhea_model_qubit_sweep_train_steps',
+           'qhea_model_noisy_workspace_bytes', 'qhea_model_forward_noisy']
 
 
 class ModelDesc(ctypes.Structure):
@@ -50,8 +51,14 @@ class MemberHParams(ctypes.Structure):
                 ('lr', ctypes.c_double), ('ham_pauli', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class NoiseParams(ctypes.Structure):
+    """Mirror of `qhea_noise` (include/quanonet_hea.h): gate / readout error rates and the estimator of the noisy forward."""
+    _fields_ = [('p1', ctypes.c_double), ('p2', ctypes.c_double), ('readout', ctypes.c_double), ('shots', ctypes.c_int64),
+                ('trajectories', ctypes.c_int64), ('seed', ctypes.c_uint64)]
+
+
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 480           # 0.4.8: + qhea_model_qubit_sweep_train_steps (members differ in qubit count too)
+MIN_LIB_VERSION = 500           # 0.5.0: + qhea_model_forward_noisy (gate noise, readout error, finite shots)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -183,6 +190,12 @@ def load():
     lib.qhea_model_train_step.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, dp, ctypes.c_double, dp, dp, dp, dp,
                                           ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, vp, ctypes.c_size_t, vp]
+    npp = ctypes.POINTER(NoiseParams)
+    lib.qhea_model_noisy_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_workspace_bytes.argtypes = [mdp, ctypes.c_int64, npp]
+    lib.qhea_model_forward_noisy.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, dp, dp, dp, dp, npp, dp, dp, vp,
+                                             ctypes.c_size_t, vp]
     _lib = lib
     return lib
 
@@ -754,6 +767,33 @@ def model_dp_train_steps(desc, bounds, global_batches, branch, trunk, y, params,
         raise Unsupported("qhea_model_dp_train_steps: empty shard or reduce grid not resident at once")
     _check(rc, 'qhea_model_dp_train_steps')
     return rows
+
+
+def model_forward_noisy(desc, branch, trunk, params, noise, row0=0, ham_diag=None, out=None, stderr=None):
+    """
+    qhea_model_forward_noisy on all rows of branch / trunk in ONE call: (pred[B], stderr[B] or None).  `noise` is a NoiseParams;
+    row0 is the global index of the first row (the random streams are keyed by it).  Raises Unsupported for n >= 7 and
+    QheaError for a bad noise setting -- in both cases before anything is launched.
+    """
+    lib = load()
+    B = branch.shape[0]
+    _dev_f64(branch, 'branch', (B, desc.branch_in))
+    if desc.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
+    _dev_f64(params, 'params')
+    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
+    with torch.cuda.device(branch.device):
+        nbytes = int(lib.qhea_model_noisy_workspace_bytes(ctypes.byref(desc), int(B), ctypes.byref(noise)))
+    ws = _workspace(branch.device, nbytes) if nbytes else None
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_forward_noisy(ctypes.byref(desc), int(row0), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
+                                          _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(stderr), _ptr(ws),
+                                          0 if ws is None else ws.numel(), _stream(branch.device))
+    if rc == -2:
+        raise Unsupported("qhea_model_forward_noisy: unsupported circuit (n >= 7)")
+    _check(rc, 'qhea_model_forward_noisy')
+    return pred, stderr
 
 
 def clock_probe(device, n_workgroups=1024, iters=200000):

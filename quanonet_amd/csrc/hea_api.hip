@@ -12,6 +12,7 @@
 #include "hea_adam.hpp"
 #include "hea_dp.hpp"
 #include "hea_qsweep.hpp"
+#include "hea_noise.hpp"
 
 namespace qhea {
 
@@ -1397,6 +1398,30 @@ int launch_prep_model(const ModelInfo& mi, int64_t B, const double* params, cons
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 
+// the noisy forward's access to the model-level prep (hea_noise.hpp)
+int noise_model_shape(const qhea_model_desc* d, NoiseShape& ns) {
+    ModelInfo mi;
+    const int rc = model_info(d, mi);
+    if (rc != QHEA_OK) return rc;
+    ns.n = mi.n; ns.blk = (int)mi.sh.blk; ns.E = (int)mi.sh.E; ns.off_bias = mi.has_bias ? mi.off_bias : -1;
+    if (d->model == QHEA_MODEL_QUANONET) { ns.nb[0] = d->net[2]; ns.ld[0] = d->net[3]; ns.nb[1] = d->net[0]; ns.ld[1] = d->net[1]; }
+    else                                 { ns.nb[0] = d->net[0]; ns.ld[0] = d->net[1]; ns.nb[1] = 0;         ns.ld[1] = 0; }
+    return QHEA_OK;
+}
+
+int launch_noise_prep(const qhea_model_desc* d, int64_t B, const double* branch, const double* trunk, const double* params,
+                      double4* gates, double2* cs, void* hdr, hipStream_t st) {
+    ModelInfo mi;
+    const int rc = model_info(d, mi);
+    if (rc != QHEA_OK) return rc;
+    const long total = (mi.sh.blk + 2) * mi.n + B * mi.sh.E;
+    const int threads = 256;
+    hipLaunchKernelGGL(prep_model_kernel, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, st,
+                       mi.n, (int)mi.sh.blk, params + mi.off_ans, gates, (long)B, (int)mi.sh.E,
+                       make_enc(d, mi, branch, trunk, params), cs, reinterpret_cast<WorkspaceHeader*>(hdr));
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
 // R-sequential ensemble fallback (qhea_model_ensemble_train_steps): member m > 0 ran on its own workspace slice, whose header
 // took its status; the overrun is moved into slice 0's header, the one qhea_check_status reads
 __global__ void status_fold_kernel(WorkspaceHeader* dst, WorkspaceHeader* src) {
@@ -1467,7 +1492,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 490; }
+int qhea_version(void) { return 500; }
 
 const char* qhea_strerror(int code) {
     switch (code) {

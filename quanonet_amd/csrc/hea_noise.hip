@@ -1,0 +1,341 @@
+// hea_noise.hip -- qhea_model_forward_noisy: the model forward under depolarizing gate noise and readout error, estimated from
+// Monte-Carlo trajectories (expectation mode) or sampled shots (shot mode).  Noise model, random-number layout and estimators are
+// the contract stated in include/quanonet_hea.h; tests/noise_oracle.py replays them gate by gate.
+//
+// Layout: one amplitude per lane, n = 2..6; a wave holds 64 / 2^n (row, trajectory) slots of one row.  A work item is one wave
+// and kTile consecutive trajectories of one row; slot j runs trajectories j, j + slots, ... of the tile and keeps its (sum, sum of
+// squares) in trajectory order; the slots' sums are added in slot order into the item's partial, and the finish kernel adds a
+// row's items in tile order.  Every summation order therefore depends on n and the trajectory count only -- not on the batch,
+// the chunking or the grid -- and no floating-point atomics are used.
+//
+// Gates come from prep_model_kernel's tables (hea_noise.hpp): the fused RY RZ RY gate per wire and sub-layer, and (cos, sin) of
+// every encoding angle per row; RX is applied on its own because noise sits between it and the first rotation.  Sampled Paulis
+// are kept as an X mask and a Z mask (a Pauli string up to a global phase) and pushed through the CNOTs of the ring by Clifford
+// conjugation, so that a sub-layer's ring stays one lane gather followed by at most one gather for the whole sub-layer's errors
+// (skipped when no slot of the wave drew one).  Philox calls are shared by the lanes of a slot: at each segment (the encoding of
+// a block, or one sub-layer) lane k of the slot computes the segment's call k and turns its four words into the error codes of
+// its two locations; every location then reads its code from that lane.
+#include <cmath>
+#include <cstdint>
+
+#include "hea_noise.hpp"
+
+namespace qhea {
+namespace {
+
+constexpr int kTile = 64;                   // trajectories per work item (fixes the summation order: part of the contract)
+constexpr int kNoiseWaves = 4;              // waves per workgroup (independent; no LDS, no barrier)
+
+struct NoiseArgs {
+    const double4* gates;                   // prep table, entry 0 = padding entry -n
+    const double2* cs;                      // [B, E]
+    const double* diag;                     // ham_diag or NULL
+    const double* bias;                     // model bias or NULL
+    double off, co, q;                      // H = off + co sum P_i; readout flip probability
+    unsigned long long thr1, thr2, thrq;    // an event happens iff word < thr (thr = p 2^32)
+    long B, row0, T;                        // rows, global index of row 0, values (trajectories or shots) per row
+    int tiles, E, pauli, shots;             // tiles per row; shots != 0: shot mode
+    int nb[2], ld[2];
+    unsigned key0, key1;
+    unsigned L;                             // noise locations of the circuit
+    double2* partial;                       // [B * tiles] (sum, sum of squares)
+};
+
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 reference constants)
+__device__ __forceinline__ uint4 philox(uint4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x;
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c.z;
+        c = make_uint4((unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0);
+    }
+    return c;
+}
+
+// error codes of this lane's call (l0 / 2 + k) for the segment [l0, l0 + cnt) whose first n1 locations are one-qubit channels:
+// byte h = code of location 2c + h (0: no error; 1..3 one-qubit Pauli X, Y, Z; 1..15 two-qubit pair (code >> 2, code & 3))
+__device__ __forceinline__ unsigned segment_codes(const NoiseArgs& a, unsigned l0, unsigned cnt, unsigned n1, unsigned traj,
+                                                  unsigned long long row, int k) {
+    if ((a.thr1 | a.thr2) == 0) return 0;
+    const unsigned c = (l0 >> 1) + (unsigned)k;
+    const uint4 w = philox(make_uint4(c, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
+    unsigned out = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const unsigned l = 2 * c + h;
+        if (l >= l0 && l < l0 + cnt) {
+            const bool two = l - l0 >= n1;
+            const unsigned w0 = h ? w.z : w.x, w1 = h ? w.w : w.y;
+            if ((unsigned long long)w0 < (two ? a.thr2 : a.thr1))
+                out |= (1u + (unsigned)(((unsigned long long)w1 * (two ? 15u : 3u)) >> 32)) << (8 * h);
+        }
+    }
+    return out;
+}
+
+__device__ __forceinline__ unsigned code_at(unsigned codes, unsigned l0, unsigned l, int base) {
+    return (__shfl(codes, base + (int)((l >> 1) - (l0 >> 1))) >> (8 * (l & 1))) & 255u;
+}
+
+// Pauli p (0 I, 1 X, 2 Y, 3 Z) on wire w as (X mask, Z mask) bits, up to phase
+__device__ __forceinline__ int pauli_x(unsigned p, int w) { return (p == 1u || p == 2u) ? 1 << w : 0; }
+__device__ __forceinline__ int pauli_z(unsigned p, int w) { return p >= 2u ? 1 << w : 0; }
+
+// psi <- X^x Z^z psi (up to a global phase): psi'[k] = (-1)^popcount((k ^ x) & z) psi[k ^ x]
+__device__ __forceinline__ void apply_frame(double& re, double& im, int x, int z, int k, int base) {
+    if (__any(x | z)) {
+        const int src = k ^ x;
+        const double pr = __shfl(re, base + src), pi = __shfl(im, base + src);
+        const bool neg = __popc(src & z) & 1;
+        re = neg ? -pr : pr;
+        im = neg ? -pi : pi;
+    }
+}
+
+template <int N>
+__global__ __launch_bounds__(64 * kNoiseWaves) void noisy_fwd_kernel(NoiseArgs a) {
+    constexpr int D = 1 << N, SL = 64 / D;
+    const int lane = threadIdx.x & 63;
+    const long item = (long)blockIdx.x * kNoiseWaves + (threadIdx.x >> 6);
+    if (item >= a.B * a.tiles) return;                                   // whole waves
+    const long r = item / a.tiles;
+    const long t0 = (item - r * a.tiles) * (long)kTile;
+    const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
+    const int k = lane & (D - 1), base = lane - k, slot = lane / D;
+    const unsigned long long row = (unsigned long long)(a.row0 + r);
+    const double2* csr = a.cs + r * a.E;
+
+    int ring = k;                                                        // the ring CNOT(1->0) ... CNOT(0->n-1) as one gather
+#pragma unroll
+    for (int j = N - 1; j >= 0; --j) ring ^= ((ring >> ((j + 1) % N)) & 1) << j;
+
+    // expectation mode: value = off_term + sum_k p_k h(k), readout error folded in
+    double h = 0.0, off_term = 0.0;
+    if (!a.shots) {
+        if (a.diag) {
+            for (int j = 0; j < D; ++j) {
+                double w = 1.0;
+                for (int i = 0; i < N; ++i) w *= ((j ^ k) >> i) & 1 ? a.q : 1.0 - a.q;
+                h += w * a.diag[j];
+            }
+        } else {
+            h = a.co * (1.0 - 2.0 * a.q) * (double)(N - 2 * (int)__popc(k));
+            off_term = a.off;
+        }
+    }
+
+    double sum = 0.0, sq = 0.0;
+    for (int it = 0; it < tcount; it += SL) {
+        const int tj = it + slot;
+        const unsigned traj = (unsigned)(t0 + tj);
+        double re = k == 0 ? 1.0 : 0.0, im = 0.0;
+        unsigned loc = 0;
+        int s = 0, col = 0;
+        for (int g = 0; g < 2; ++g) {
+            for (int b = 0; b < a.nb[g]; ++b) {
+                // encoding RX on every wire, then one-qubit depolarizing noise on every wire
+                unsigned codes = segment_codes(a, loc, N, N, traj, row, k);
+                int x = 0, z = 0;
+#pragma unroll
+                for (int q = 0; q < N; ++q) {
+                    const double2 c = csr[col + q];
+                    const double pr = __shfl(re, lane ^ (1 << q)), pi = __shfl(im, lane ^ (1 << q));
+                    const double nr = c.x * re + c.y * pi, ni = c.x * im - c.y * pr;
+                    re = nr; im = ni;
+                    const unsigned p = code_at(codes, loc, loc + q, base);
+                    x |= pauli_x(p, q); z |= pauli_z(p, q);
+                }
+                apply_frame(re, im, x, z, k, base);
+                col += N; loc += N;
+                for (int l = 0; l < a.ld[g]; ++l, ++s, loc += 2 * N) {
+                    codes = segment_codes(a, loc, 2 * N, N, traj, row, k);
+                    x = 0; z = 0;
+#pragma unroll
+                    for (int q = 0; q < N; ++q) {                        // fused RY RZ RY per wire, then its noise
+                        const double4 v = a.gates[2 * (s * N + q + N) + ((k >> q) & 1)];
+                        const double pr = __shfl(re, lane ^ (1 << q)), pi = __shfl(im, lane ^ (1 << q));
+                        const double nr = v.x * re - v.y * im + v.z * pr - v.w * pi;
+                        const double ni = v.x * im + v.y * re + v.z * pi + v.w * pr;
+                        re = nr; im = ni;
+                        const unsigned p = code_at(codes, loc, loc + q, base);
+                        x |= pauli_x(p, q); z |= pauli_z(p, q);
+                    }
+#pragma unroll
+                    for (int j = 0; j < N; ++j) {                        // CNOT(c -> t) conjugates the frame, then its own noise
+                        const int c = (j + 1) % N, t = j;
+                        x ^= ((x >> c) & 1) << t;
+                        z ^= ((z >> t) & 1) << c;
+                        const unsigned p = code_at(codes, loc, loc + N + j, base);
+                        x ^= pauli_x(p >> 2, c) | pauli_x(p & 3u, t);
+                        z ^= pauli_z(p >> 2, c) | pauli_z(p & 3u, t);
+                    }
+                    const double pr = __shfl(re, base + ring), pi = __shfl(im, base + ring);
+                    re = pr; im = pi;
+                    apply_frame(re, im, x, z, k, base);
+                }
+            }
+        }
+        // noiseless basis change of the X / Y read-outs: H, or H S^dagger, on every wire
+        if (a.pauli != QHEA_PAULI_Z) {
+#pragma unroll
+            for (int q = 0; q < N; ++q) {
+                const int bit = (k >> q) & 1;
+                if (a.pauli == QHEA_PAULI_Y && bit) { const double t = re; re = im; im = -t; }
+                const double pr = __shfl(re, lane ^ (1 << q)), pi = __shfl(im, lane ^ (1 << q));
+                re = M_SQRT1_2 * (bit ? pr - re : re + pr);
+                im = M_SQRT1_2 * (bit ? pi - im : im + pi);
+            }
+        }
+        const double pk = re * re + im * im;
+        double v;
+        if (!a.shots) {
+            v = pk * h;
+#pragma unroll
+            for (int o = D / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+            v += off_term;
+        } else {
+            // one measured bitstring: u against the cdf in index order, then n readout flips
+            const unsigned cm = (a.L + 1) >> 1;
+            const uint4 w0 = philox(make_uint4(cm, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
+            const uint4 w1 = philox(make_uint4(cm + 1, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
+            const double u = ((double)(w0.x >> 5) * 67108864.0 + (double)(w0.y >> 6)) * 0x1p-53;
+            double acc = 0.0;
+            int out = -1, last = 0;
+            for (int j = 0; j < D; ++j) {
+                const double pj = __shfl(pk, base + j);
+                acc += pj;
+                if (out < 0 && u < acc) out = j;
+                if (pj > 0.0) last = j;
+            }
+            if (out < 0) out = last;
+            const unsigned rw[6] = {w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+            for (int i = 0; i < N; ++i) out ^= (unsigned long long)rw[i] < a.thrq ? 1 << i : 0;
+            v = a.diag ? a.diag[out] : a.off + a.co * (double)(N - 2 * (int)__popc(out));
+        }
+        if (tj < tcount) { sum += v; sq += v * v; }
+    }
+    double S = 0.0, Q = 0.0;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) { S += __shfl(sum, j * D); Q += __shfl(sq, j * D); }
+    if (lane == 0) a.partial[item] = make_double2(S, Q);
+}
+
+// row r: mean over its T values (+ bias), standard error = sample standard deviation / sqrt(T) (0 for T = 1)
+__global__ __launch_bounds__(256) void noisy_finish_kernel(const double2* __restrict__ partial, int tiles, long B, long T,
+                                                           const double* __restrict__ bias, double* __restrict__ pred,
+                                                           double* __restrict__ se) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= B) return;
+    double S = 0.0, Q = 0.0;
+    for (int t = 0; t < tiles; ++t) {
+        const double2 v = partial[r * tiles + t];
+        S += v.x; Q += v.y;
+    }
+    const double mean = S / (double)T;
+    pred[r] = mean + (bias ? bias[0] : 0.0);
+    if (se) {
+        const double var = T > 1 ? (Q - S * mean) / (double)(T - 1) : 0.0;
+        se[r] = var > 0.0 ? sqrt(var / (double)T) : 0.0;
+    }
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct NoiseLayout { size_t off_gates, off_cs, off_part, total; int tiles; };
+
+NoiseLayout noise_layout(const NoiseShape& ns, int64_t B, int64_t T) {
+    NoiseLayout L{};
+    L.tiles = (int)((T + kTile - 1) / kTile);
+    size_t p = 256;                                                      // header (prep_model_kernel stamps it)
+    L.off_gates = p; p = align256(p + (size_t)(ns.blk + 2) * ns.n * 2 * sizeof(double4));
+    L.off_cs = p;    p = align256(p + (size_t)B * ns.E * sizeof(double2));
+    L.off_part = p;  p = align256(p + (size_t)B * L.tiles * sizeof(double2));
+    L.total = p;
+    return L;
+}
+
+// values per row (T trajectories or S shots), or QHEA_EINVAL
+int64_t noise_values(const qhea_noise* nz) {
+    if (!nz) return QHEA_EINVAL;
+    for (double p : {nz->p1, nz->p2, nz->readout})
+        if (!(p >= 0.0 && p <= 1.0)) return QHEA_EINVAL;
+    if (nz->shots < 0) return QHEA_EINVAL;
+    const int64_t T = nz->shots > 0 ? nz->shots : nz->trajectories;
+    if (T < 1 || T > (int64_t)0xFFFFFFFF) return QHEA_EINVAL;          // trajectory index is one 32-bit counter word
+    return T;
+}
+
+unsigned long long threshold(double p) { return (unsigned long long)(p * 4294967296.0); }
+
+}  // namespace
+}  // namespace qhea
+
+using namespace qhea;
+
+extern "C" {
+
+size_t qhea_model_noisy_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise) {
+    NoiseShape ns;
+    const int64_t T = noise_values(noise);
+    if (T < 1 || batch < 0 || noise_model_shape(desc, ns) != QHEA_OK) return 0;
+    return noise_layout(ns, batch, T).total;
+}
+
+int qhea_model_forward_noisy(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch, const double* trunk,
+                             const double* params, const double* ham_diag, const qhea_noise* noise, double* pred,
+                             double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
+    NoiseShape ns;
+    int rc = noise_model_shape(desc, ns);
+    if (rc != QHEA_OK) return rc;
+    const int64_t T = noise_values(noise);
+    if (T < 1) return QHEA_EINVAL;
+    if (ns.n > 6) return QHEA_EUNSUPPORTED;                              // lane-resident states only
+    const bool pauli_ok = desc->ham_pauli == QHEA_PAULI_Z || ((desc->ham_pauli == QHEA_PAULI_X ||
+                                                               desc->ham_pauli == QHEA_PAULI_Y) && !ham_diag);
+    if (!pauli_ok || batch < 0 || row0 < 0) return QHEA_EINVAL;
+    if (batch == 0) return QHEA_OK;
+    if (!branch || !params || !pred || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
+    const NoiseLayout L = noise_layout(ns, batch, T);
+    if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
+    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
+    double2* part = reinterpret_cast<double2*>(ws + L.off_part);
+    rc = launch_noise_prep(desc, batch, branch, trunk, params, gates, cs, ws, st);
+    if (rc != QHEA_OK) return rc;
+
+    NoiseArgs a{};
+    a.gates = gates; a.cs = cs; a.diag = ham_diag;
+    a.bias = ns.off_bias >= 0 ? params + ns.off_bias : nullptr;
+    a.off = desc->ham_offset; a.co = desc->ham_coeff; a.q = noise->readout;
+    a.thr1 = threshold(noise->p1); a.thr2 = threshold(noise->p2); a.thrq = threshold(noise->readout);
+    a.B = batch; a.row0 = row0; a.T = T; a.tiles = L.tiles; a.E = ns.E; a.pauli = desc->ham_pauli;
+    a.shots = noise->shots > 0 ? 1 : 0;
+    unsigned locs = 0;
+    for (int g = 0; g < 2; ++g) {
+        a.nb[g] = ns.nb[g]; a.ld[g] = ns.ld[g];
+        locs += (unsigned)ns.nb[g] * (unsigned)(ns.n + 2 * ns.n * ns.ld[g]);
+    }
+    a.L = locs;
+    a.key0 = (unsigned)noise->seed; a.key1 = (unsigned)(noise->seed >> 32);
+    a.partial = part;
+    const long items = (long)batch * L.tiles;
+    const dim3 grid((unsigned)((items + kNoiseWaves - 1) / kNoiseWaves)), block(64 * kNoiseWaves);
+    switch (ns.n) {
+        case 2: hipLaunchKernelGGL(noisy_fwd_kernel<2>, grid, block, 0, st, a); break;
+        case 3: hipLaunchKernelGGL(noisy_fwd_kernel<3>, grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL(noisy_fwd_kernel<4>, grid, block, 0, st, a); break;
+        case 5: hipLaunchKernelGGL(noisy_fwd_kernel<5>, grid, block, 0, st, a); break;
+        case 6: hipLaunchKernelGGL(noisy_fwd_kernel<6>, grid, block, 0, st, a); break;
+        default: return QHEA_EUNSUPPORTED;
+    }
+    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    hipLaunchKernelGGL(noisy_finish_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, part, L.tiles, (long)batch,
+                       (long)T, a.bias, pred, stderr_out);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
+}  // extern "C"

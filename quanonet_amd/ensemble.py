@@ -201,3 +201,9 @@ class EnsembleSolver:
         """PTSolver.evaluate for every member (its best checkpoint, its metric.json); returns the list of metrics."""
         histories = histories if histories is not None else [None] * len(self.members)
         return [m.evaluate(h) for m, h in zip(self.members, histories)]
+
+    def evaluate_noisy(self, noise, out_name=None):
+        """PTSolver.evaluate_noisy for every member (its best checkpoint; out_dir/out_name when given, never metric.json); returns
+        the list of results.  Every member uses noise.seed, so the members see common random numbers: member differences are
+        not blurred by independent noise draws."""
+        return [m.evaluate_noisy(noise, out_name) for m in self.members]

@@ -1,0 +1,91 @@
+"""
+Evaluation of trained models under gate noise, readout error and finite shots (qhea_model_forward_noisy): the deployment
+questions of the reference's ibm_inference.py -- how many shots a model needs, what gate error rate it tolerates -- answered
+on the GPU before any QPU time is spent.  The noise model, the estimators and the random-number layout are stated in
+include/quanonet_hea.h.
+"""
+import dataclasses
+from dataclasses import dataclass
+
+import torch
+
+from . import _lib
+
+
+@dataclass(frozen=True)
+class NoiseModel:
+    """
+    p1: depolarizing probability after every single-qubit gate (each encoding RX; each wire's RY RZ RY counts as one gate);
+    p2: two-qubit depolarizing probability after every CNOT; readout: flip probability of every measured bit.
+    shots = 0: expectation mode, the mean over `trajectories` noisy runs of their exact read-outs (readout error folded in);
+    shots = S >= 1: S sampled bitstrings per row, what an Estimator with default_shots = S estimates.
+    seed: key of the counter-based random streams; a row's draws depend on (seed, global row index, trajectory) only.
+    """
+    p1: float = 0.0
+    p2: float = 0.0
+    readout: float = 0.0
+    shots: int = 0
+    trajectories: int = 1
+    seed: int = 0
+
+    def __post_init__(self):
+        for name in ('p1', 'p2', 'readout'):
+            v = getattr(self, name)
+            if not isinstance(v, (int, float)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"NoiseModel.{name} must lie in [0, 1] (got {v!r})")
+        for name in ('shots', 'trajectories', 'seed'):
+            if not isinstance(getattr(self, name), int) or isinstance(getattr(self, name), bool):
+                raise ValueError(f"NoiseModel.{name} must be an int (got {getattr(self, name)!r})")
+        if self.shots < 0:
+            raise ValueError(f"NoiseModel.shots must be >= 0 (got {self.shots})")
+        if self.shots == 0 and self.trajectories < 1:
+            raise ValueError(f"NoiseModel.trajectories must be >= 1 in expectation mode (got {self.trajectories})")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"NoiseModel.seed must fit in 64 unsigned bits (got {self.seed})")
+
+    def params(self):
+        """The C ABI's qhea_noise."""
+        return _lib.NoiseParams(float(self.p1), float(self.p2), float(self.readout), int(self.shots), int(self.trajectories),
+                                int(self.seed))
+
+    def asdict(self):
+        return dataclasses.asdict(self)
+
+
+def _model_inputs(model, inputs):
+    ins = list(inputs) if isinstance(inputs, (tuple, list)) else [inputs]
+    ins = [t.contiguous() for t in ins]
+    return ins[0], (ins[1] if len(ins) > 1 else None)
+
+
+def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
+    """
+    Predictions of a fp64 QuanONetPT / HEAQNNPT on a HIP device under `noise` (a NoiseModel): (pred [N, 1], stderr [N]).
+    inputs: (branch, trunk) for QuanONet, (x,) or x for HEAQNN.  Rows go in chunks of `chunk_rows`; chunk i passes its global
+    index row0 + i * chunk_rows, so the result is bitwise the same for any chunking.  Parameters in model.parameters() order
+    (the flat layout of the header), ham_diag as the trainer takes it.
+    """
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("noisy_predict takes a QuanONetPT or HEAQNNPT model")
+    params = list(model.parameters())
+    if not params or params[0].dtype != torch.float64 or not params[0].is_cuda:
+        raise _lib.QheaError("noisy_predict needs a float64 model on a HIP device (there is no CPU path)")
+    desc = model.fused_desc()
+    flat = torch.cat([p.detach().reshape(-1) for p in params])
+    if flat.numel() != _lib.model_param_count(desc):
+        raise _lib.QheaError("the model's parameters do not match the flat layout of its descriptor")
+    q = getattr(model, 'quantum_layer', None)
+    ham_diag = q.ham_diag if (q is not None and getattr(q, 'use_full_ham', False)) else None
+    if ham_diag is not None:
+        ham_diag = ham_diag.detach().to(torch.float64).contiguous()
+    branch, trunk = _model_inputs(model, inputs)
+    N = branch.shape[0]
+    pred = torch.empty(N, dtype=torch.float64, device=branch.device)
+    stderr = torch.empty(N, dtype=torch.float64, device=branch.device)
+    chunk = max(1, int(chunk_rows))
+    nz = noise.params()
+    for s in range(0, N, chunk):
+        e = min(N, s + chunk)
+        _lib.model_forward_noisy(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, row0=int(row0) + s,
+                                 ham_diag=ham_diag, out=pred[s:e], stderr=stderr[s:e])
+    return pred.unsqueeze(-1), stderr
