@@ -287,6 +287,31 @@ int    qhea_model_forward_noisy(const qhea_model_desc* desc, int64_t row0, int64
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Exact noisy forward: the two deterministic quantities the Monte-Carlo call above estimates, computed by carrying the density
+ * matrix through the circuit.  The noise model is the one stated for qhea_model_forward_noisy (p1, p2, readout of `noise`;
+ * its shots, trajectories and seed are ignored).
+ *   pred[b]     = the exact expectation of a read value under those channels + bias: what expectation mode converges to for
+ *                 T -> infinity and shot mode for S -> infinity.
+ *   shot_std[b] = (optional) the exact standard deviation of ONE shot's value (the read bitstring after its flips ->
+ *                 offset + coeff sum_i (1 - 2 b_i), or diag[k] with ham_diag): a row's standard error at S shots is
+ *                 shot_std / sqrt(S).  A variance that rounds below zero is returned as zero.
+ * Scope: n = 2..6, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.
+ * Errors, all before anything is launched and with the outputs untouched: QHEA_EINVAL for p1, p2 or readout outside [0, 1]
+ * (NaN included); QHEA_EUNSUPPORTED for n >= 7.  An empty batch returns QHEA_OK.
+ * Launches: two -- the prep kernel and the density-matrix kernel (4^n elements per row in LDS, 64 KiB per workgroup); no
+ * allocation, no synchronisation (hipGraph-capturable).  No atomics and a fixed summation order: a row's result does not depend
+ * on the batch or the chunking (bitwise).  Cost per row: about 2 * 2^n ideal forwards.
+ */
+/* DEVICE scratch bytes for qhea_model_forward_noisy_exact on `batch` rows (0 on a bad descriptor). */
+size_t qhea_model_exact_noisy_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+int    qhea_model_forward_noisy_exact(const qhea_model_desc* desc, int64_t batch,
+                                      const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                      const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                      const qhea_noise* noise /*HOST: p1, p2, readout used; shots, trajectories, seed ignored*/,
+                                      double* pred /*DEVICE [B]*/, double* shot_std /*DEVICE [B] or NULL*/,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the
  * SAME parameters -- the chunk loop of PTSolver.evaluate / infer.predict (solvers/solver_pt.py:299-310, infer.py:274-289) in
  * one host call.  The layer records depend on the parameters alone, so one preparation launch serves all chunks of

@@ -34,7 +34,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_sweep_workspace_bytes', 'qhea_model_sweep_train_steps',
            'qhea_model_depth_sweep_workspace_bytes', 'qhea_model_depth_sweep_train_steps',
            'qhea_model_qubit_sweep_workspace_bytes', 'qhea_model_qubit_sweep_train_steps',
-           'qhea_model_noisy_workspace_bytes', 'qhea_model_forward_noisy']
+           'qhea_model_noisy_workspace_bytes', 'qhea_model_forward_noisy',
+           'qhea_model_exact_noisy_workspace_bytes', 'qhea_model_forward_noisy_exact']
 
 
 class ModelDesc(ctypes.Structure):
@@ -58,7 +59,7 @@ class NoiseParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 500           # 0.5.0: + qhea_model_forward_noisy (gate noise, readout error, finite shots)
+MIN_LIB_VERSION = 510           # 0.5.1: + qhea_model_forward_noisy_exact (density-matrix forward under the same noise model)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -196,6 +197,10 @@ def load():
     lib.qhea_model_forward_noisy.restype = ctypes.c_int
     lib.qhea_model_forward_noisy.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, dp, dp, dp, dp, npp, dp, dp, vp,
                                              ctypes.c_size_t, vp]
+    lib.qhea_model_exact_noisy_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_exact_noisy_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
+    lib.qhea_model_forward_noisy_exact.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, npp, dp, dp, vp, ctypes.c_size_t, vp]
     _lib = lib
     return lib
 
@@ -794,6 +799,35 @@ def model_forward_noisy(desc, branch, trunk, params, noise, row0=0, ham_diag=Non
         raise Unsupported("qhea_model_forward_noisy: unsupported circuit (n >= 7)")
     _check(rc, 'qhea_model_forward_noisy')
     return pred, stderr
+
+
+def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None, out=None, shot_std=None):
+    """
+    qhea_model_forward_noisy_exact on all rows of branch / trunk in ONE call: (pred[B], shot_std[B] or None) -- the exact
+    expectation under `noise` (a NoiseParams; p1, p2, readout are used) and, where a shot_std tensor is given, the exact
+    standard deviation of one shot.  Raises Unsupported for n >= 7 and QheaError for a bad noise setting -- in both cases before
+    anything is launched.
+    """
+    lib = load()
+    B = branch.shape[0]
+    _dev_f64(branch, 'branch', (B, desc.branch_in))
+    if desc.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
+    _dev_f64(params, 'params')
+    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    _dev_f64(shot_std, 'shot_std', (B,))
+    pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
+    with torch.cuda.device(branch.device):
+        nbytes = int(lib.qhea_model_exact_noisy_workspace_bytes(ctypes.byref(desc), int(B)))
+    ws = _workspace(branch.device, nbytes) if nbytes else None
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_forward_noisy_exact(ctypes.byref(desc), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
+                                                _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(shot_std), _ptr(ws),
+                                                0 if ws is None else ws.numel(), _stream(branch.device))
+    if rc == -2:
+        raise Unsupported("qhea_model_forward_noisy_exact: unsupported circuit (n >= 7)")
+    _check(rc, 'qhea_model_forward_noisy_exact')
+    return pred, shot_std
 
 
 def clock_probe(device, n_workgroups=1024, iters=200000):

@@ -1492,7 +1492,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 500; }
+int qhea_version(void) { return 510; }
 
 const char* qhea_strerror(int code) {
     switch (code) {

@@ -202,8 +202,8 @@ class EnsembleSolver:
         histories = histories if histories is not None else [None] * len(self.members)
         return [m.evaluate(h) for m, h in zip(self.members, histories)]
 
-    def evaluate_noisy(self, noise, out_name=None):
+    def evaluate_noisy(self, noise, out_name=None, exact=False):
         """PTSolver.evaluate_noisy for every member (its best checkpoint; out_dir/out_name when given, never metric.json); returns
         the list of results.  Every member uses noise.seed, so the members see common random numbers: member differences are
-        not blurred by independent noise draws."""
-        return [m.evaluate_noisy(noise, out_name) for m in self.members]
+        not blurred by independent noise draws.  exact=True: every member's exact expectation instead (no draws at all)."""
+        return [m.evaluate_noisy(noise, out_name, exact=exact) for m in self.members]

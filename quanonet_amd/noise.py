@@ -58,18 +58,13 @@ def _model_inputs(model, inputs):
     return ins[0], (ins[1] if len(ins) > 1 else None)
 
 
-def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
-    """
-    Predictions of a fp64 QuanONetPT / HEAQNNPT on a HIP device under `noise` (a NoiseModel): (pred [N, 1], stderr [N]).
-    inputs: (branch, trunk) for QuanONet, (x,) or x for HEAQNN.  Rows go in chunks of `chunk_rows`; chunk i passes its global
-    index row0 + i * chunk_rows, so the result is bitwise the same for any chunking.  Parameters in model.parameters() order
-    (the flat layout of the header), ham_diag as the trainer takes it.
-    """
+def _call_args(model, inputs, who):
+    """(desc, flat parameters, ham_diag, branch, trunk) of a fp64 model on a HIP device, as the C ABI takes them"""
     if not hasattr(model, 'fused_desc'):
-        raise TypeError("noisy_predict takes a QuanONetPT or HEAQNNPT model")
+        raise TypeError(f"{who} takes a QuanONetPT or HEAQNNPT model")
     params = list(model.parameters())
     if not params or params[0].dtype != torch.float64 or not params[0].is_cuda:
-        raise _lib.QheaError("noisy_predict needs a float64 model on a HIP device (there is no CPU path)")
+        raise _lib.QheaError(f"{who} needs a float64 model on a HIP device (there is no CPU path)")
     desc = model.fused_desc()
     flat = torch.cat([p.detach().reshape(-1) for p in params])
     if flat.numel() != _lib.model_param_count(desc):
@@ -79,6 +74,17 @@ def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
     if ham_diag is not None:
         ham_diag = ham_diag.detach().to(torch.float64).contiguous()
     branch, trunk = _model_inputs(model, inputs)
+    return desc, flat, ham_diag, branch, trunk
+
+
+def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
+    """
+    Predictions of a fp64 QuanONetPT / HEAQNNPT on a HIP device under `noise` (a NoiseModel): (pred [N, 1], stderr [N]).
+    inputs: (branch, trunk) for QuanONet, (x,) or x for HEAQNN.  Rows go in chunks of `chunk_rows`; chunk i passes its global
+    index row0 + i * chunk_rows, so the result is bitwise the same for any chunking.  Parameters in model.parameters() order
+    (the flat layout of the header), ham_diag as the trainer takes it.
+    """
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'noisy_predict')
     N = branch.shape[0]
     pred = torch.empty(N, dtype=torch.float64, device=branch.device)
     stderr = torch.empty(N, dtype=torch.float64, device=branch.device)
@@ -89,3 +95,23 @@ def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
         _lib.model_forward_noisy(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, row0=int(row0) + s,
                                  ham_diag=ham_diag, out=pred[s:e], stderr=stderr[s:e])
     return pred.unsqueeze(-1), stderr
+
+
+def exact_noisy_predict(model, inputs, noise, chunk_rows=16384):
+    """
+    The exact counterpart of noisy_predict (qhea_model_forward_noisy_exact): (pred [N, 1], shot_std [N]) -- each row's exact
+    expectation under `noise` (its p1, p2 and readout; shots, trajectories and seed are ignored) and the exact standard
+    deviation of one shot, so that a row's standard error at S shots is shot_std / sqrt(S).  No sampling error, no random
+    numbers; n <= 6.  Rows go in chunks of `chunk_rows`; the result is bitwise the same for any chunking.
+    """
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'exact_noisy_predict')
+    N = branch.shape[0]
+    pred = torch.empty(N, dtype=torch.float64, device=branch.device)
+    shot_std = torch.empty(N, dtype=torch.float64, device=branch.device)
+    chunk = max(1, int(chunk_rows))
+    nz = noise.params()
+    for s in range(0, N, chunk):
+        e = min(N, s + chunk)
+        _lib.model_forward_noisy_exact(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, ham_diag=ham_diag,
+                                       out=pred[s:e], shot_std=shot_std[s:e])
+    return pred.unsqueeze(-1), shot_std

@@ -816,27 +816,33 @@ class PTSolver:
         self.log(f"Test Relative L2 Error: {metrics['rel_l2']:.6f}")
         return metrics
 
-    def evaluate_noisy(self, noise, out_name=None):
+    def evaluate_noisy(self, noise, out_name=None, exact=False):
         """
         The test set of `evaluate` predicted under `noise` (a quanonet_amd.noise.NoiseModel) from the best checkpoint:
         regression_metrics plus 'mean_stderr' (the rows' mean standard error) and 'noise' (the settings).  Writes
         out_dir/out_name when out_name is given and never touches metric.json (the run's "completed" marker).  Single rank.
+        exact=True: the metrics of the exact expectation under the noise channels (exact_noisy_predict; no sampling error,
+        noise.shots / trajectories / seed ignored), with 'exact': True and 'mean_shot_std' (the rows' mean one-shot standard
+        deviation) in place of 'mean_stderr'.
         """
-        from .noise import noisy_predict
+        from .noise import exact_noisy_predict, noisy_predict
         if self.world > 1:
             raise RuntimeError("evaluate_noisy runs on one rank (world_size == 1)")
         if self.best_model_path and os.path.exists(self.best_model_path):
             sd = torch.load(self.best_model_path, map_location=self.device, weights_only=True)
             self.model.load_state_dict(sd)
-        y_pred, stderr = noisy_predict(self.model, self.test_input, noise,
-                                       chunk_rows=self.config.get('eval_batch_size', 16384))
+        predict = exact_noisy_predict if exact else noisy_predict
+        y_pred, stderr = predict(self.model, self.test_input, noise, chunk_rows=self.config.get('eval_batch_size', 16384))
         y_true = torch.as_tensor(np.asarray(self.test_output), dtype=torch.float64).to(y_pred.device)
         metrics = regression_metrics(y_pred, y_true)
-        metrics['mean_stderr'] = float(stderr.mean().item()) if stderr.numel() else 0.0
+        spread = 'mean_shot_std' if exact else 'mean_stderr'
+        metrics[spread] = float(stderr.mean().item()) if stderr.numel() else 0.0
         metrics['noise'] = noise.asdict()
+        if exact:
+            metrics['exact'] = True
         if out_name:
             os.makedirs(self.out_dir, exist_ok=True)
             with open(os.path.join(self.out_dir, out_name), 'w') as f:
                 json.dump(metrics, f)
-        self.log(f"Noisy test Relative L2 Error: {metrics['rel_l2']:.6f} (mean stderr {metrics['mean_stderr']:.3g})")
+        self.log(f"Noisy test Relative L2 Error: {metrics['rel_l2']:.6f} ({spread.replace('_', ' ')} {metrics[spread]:.3g})")
         return metrics
