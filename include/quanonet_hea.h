@@ -312,6 +312,69 @@ int    qhea_model_forward_noisy_exact(const qhea_model_desc* desc, int64_t batch
                                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Noise-aware training: the MSE loss of the exact noisy forward above and its exact gradient, so that a model can be trained
+ * with the device's noise in the loss.  Replaces nothing in the reference (its training entry points optimise the ideal
+ * circuit; ibm_inference.py reads the device's gate and readout errors only to report them).
+ *
+ * The quantity.  Noise model: exactly the one stated for qhea_model_forward_noisy (p1 after each encoding RX and after each
+ * wire's fused RY RZ RY, p2 after each ring CNOT, the readout flip q folded into the value table h'); shots, trajectories and
+ * seed of `noise` are ignored.
+ *   pred_b       = what qhea_model_forward_noisy_exact returns for row b (exact noisy expectation + bias);
+ *   loss         = sum_b (pred_b - y_b)^2 * inv_batch_total;
+ *   grad[0..P)   = d loss / d params in the flat layout of qhea_model_loss_grad;  grad[P] = sum_b (pred_b - y_b)^2;
+ *   grad[P+1]    = sum_b y_b^2 -- the [P+2] buffer of the ideal call, so the data-parallel SUM and qhea_adam_step take it as is.
+ * The gradient is exact (no sampling, no random numbers): every channel is linear, so the adjoint recipe of qhea_backward
+ * carries over with psi -> rho and lambda -> the Heisenberg-picture observable O.  With rho_k the state after operation k and
+ * O_k the observable pulled back to that point (O_N = diag h' behind the H / H S^dagger of an X / Y read-out;
+ * O_{k-1} = Phi_k^dagger(O_k)):
+ *   - a rotation exp(-i theta sigma / 2) on wire q:  d pred / d theta = Im Tr(O_k sigma_q rho_k);  then rho_{k-1} = U^dagger rho_k U,
+ *     O_{k-1} = U^dagger O_k U.  The fused RY RZ RY is walked back as its three rotations;
+ *   - a depolarizing channel is self-adjoint: O takes the channel itself, rho its inverse (one qubit: off-diagonal pair
+ *     / (1 - 4p/3), diagonal pair (keep d0 - mix d1) / (1 - 4p/3); two qubits, lam = 16p/15: unequal-bit elements / (1 - lam),
+ *     the four equal-bit ones (x - (lam/4) S) / (1 - lam) with S their sum);  a CNOT is its own inverse on both.
+ * Chain rule as in qhea_model_loss_grad: ansatz angles sum over the rows with weight g_b = 2 (pred_b - y_b) inv_batch_total;
+ * trainable frequencies: weights[j] += g_b dpred_b/dx_j input_tiled[b, j], bias[j] += g_b dpred_b/dx_j; model bias: sum_b g_b.
+ *
+ * Conditioning and the guard.  Walking rho back multiplies its traceless part by
+ *   A = (1 - 4 p1 / 3)^(-L1) (1 - 16 p2 / 15)^(-L2),   L1 = E + n blk one-qubit locations, L2 = n blk CNOTs,
+ * while O shrinks by the same factor, so the traces stay bounded; measured (tests/test_noise_aware_abi.py) the
+ * inverse walk agrees with a walk over stored states to 1e-14 for log10 A up to 12 and is still clean at 18.  The calls refuse
+ * -- QHEA_EUNSUPPORTED, before anything is launched, outputs untouched -- p1 >= 3/4 or p2 >= 15/16 (a singular channel) and
+ * log10 A > 12; qhea_model_exact_noisy_log10_amplification returns log10 A (host only, no device needed; NaN for a bad
+ * descriptor or rates outside [0, 1], +inf for a singular channel).  At p1 = 1e-3, p2 = 1e-2 the Q5 Net40-2-20-2 model has
+ * log10 A = 3.3.
+ *
+ * Scope: n = 2..6, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.
+ * Errors, all before anything is launched and with the outputs untouched: QHEA_EINVAL for rates outside [0, 1] (NaN included),
+ * a NULL noise, a bad descriptor, a negative batch, NULL arrays; QHEA_EUNSUPPORTED for n >= 7 and for the guard;
+ * QHEA_EWORKSPACE.  An empty batch (or n_steps = 0) returns QHEA_OK.
+ * Launches: three per step -- the prep kernel, the density-matrix backward kernel (rho and O of a row in LDS, 2 x 16 * 4^n
+ * bytes; forward sweep, then the reverse walk), one reduce kernel (rows added per parameter, frequency
+ * chain rule, and in train_steps the Adam update of qhea_adam_step); no allocation, no synchronisation (hipGraph-capturable).
+ * No atomics and fixed summation orders: results are bitwise reproducible, and a row's pred and its d pred / d angle record do
+ * not depend on the batch, the grid or the rows beside it.  pred agrees with qhea_model_forward_noisy_exact to rounding (1e-13).
+ * qhea_model_train_steps_noisy_exact: arguments and semantics of qhea_model_train_steps with `noise` after ham_diag; bitwise a
+ * loop of qhea_model_loss_grad_noisy_exact + qhea_adam_step.  The workspace must fit the largest step.
+ */
+size_t qhea_model_exact_noisy_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+double qhea_model_exact_noisy_log10_amplification(const qhea_model_desc* desc, const qhea_noise* noise /*HOST*/);
+int    qhea_model_loss_grad_noisy_exact(const qhea_model_desc* desc, int64_t batch,
+                                        const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                        const double* params, const double* ham_diag,
+                                        const qhea_noise* noise /*HOST: p1, p2, readout used*/, double inv_batch_total,
+                                        double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                          const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                          const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                          const double* ham_diag, const qhea_noise* noise /*HOST*/,
+                                          const double* inv_batch_total /*HOST [n_steps]*/,
+                                          double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                          double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                          double beta2, double eps, double weight_decay, void* workspace,
+                                          size_t workspace_bytes, void* stream);
+
+/*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the
  * SAME parameters -- the chunk loop of PTSolver.evaluate / infer.predict (solvers/solver_pt.py:299-310, infer.py:274-289) in
  * one host call.  The layer records depend on the parameters alone, so one preparation launch serves all chunks of

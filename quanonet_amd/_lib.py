@@ -35,7 +35,9 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_depth_sweep_workspace_bytes', 'qhea_model_depth_sweep_train_steps',
            'qhea_model_qubit_sweep_workspace_bytes', 'qhea_model_qubit_sweep_train_steps',
            'qhea_model_noisy_workspace_bytes', 'qhea_model_forward_noisy',
-           'qhea_model_exact_noisy_workspace_bytes', 'qhea_model_forward_noisy_exact']
+           'qhea_model_exact_noisy_workspace_bytes', 'qhea_model_forward_noisy_exact',
+           'qhea_model_exact_noisy_grad_workspace_bytes', 'qhea_model_exact_noisy_log10_amplification',
+           'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact']
 
 
 class ModelDesc(ctypes.Structure):
@@ -59,7 +61,7 @@ class NoiseParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 510           # 0.5.1: + qhea_model_forward_noisy_exact (density-matrix forward under the same noise model)
+MIN_LIB_VERSION = 520           # 0.5.2: + qhea_model_loss_grad_noisy_exact / qhea_model_train_steps_noisy_exact (noise-aware training)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -201,6 +203,17 @@ def load():
     lib.qhea_model_exact_noisy_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
     lib.qhea_model_forward_noisy_exact.restype = ctypes.c_int
     lib.qhea_model_forward_noisy_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, npp, dp, dp, vp, ctypes.c_size_t, vp]
+    lib.qhea_model_exact_noisy_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_exact_noisy_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
+    lib.qhea_model_exact_noisy_log10_amplification.restype = ctypes.c_double
+    lib.qhea_model_exact_noisy_log10_amplification.argtypes = [mdp, npp]
+    lib.qhea_model_loss_grad_noisy_exact.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, dp, npp, ctypes.c_double, dp, dp, vp,
+                                                     ctypes.c_size_t, vp]
+    lib.qhea_model_train_steps_noisy_exact.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_exact.argtypes = [mdp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), dp, dp, dp, dp, dp, npp,
+                                                       ctypes.POINTER(ctypes.c_double), dp, ctypes.c_int64, dp, dp,
+                                                       ctypes.c_int64] + [ctypes.c_double] * 5 + [vp, ctypes.c_size_t, vp]
     _lib = lib
     return lib
 
@@ -828,6 +841,96 @@ def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None,
         raise Unsupported("qhea_model_forward_noisy_exact: unsupported circuit (n >= 7)")
     _check(rc, 'qhea_model_forward_noisy_exact')
     return pred, shot_std
+
+
+def model_exact_noisy_log10_amplification(desc, noise):
+    """
+    qhea_model_exact_noisy_log10_amplification (host only): log10 of the factor by which the gradient's inverse walk amplifies
+    the traceless part of rho for this shape and these rates; inf for a singular channel (p1 >= 3/4 or p2 >= 15/16), NaN for a
+    bad descriptor or rates.  The gradient calls refuse values above 12.
+    """
+    return float(load().qhea_model_exact_noisy_log10_amplification(ctypes.byref(desc), ctypes.byref(noise)))
+
+
+def _noisy_grad_ws(lib, desc, B, device):
+    with torch.cuda.device(device):
+        nbytes = int(lib.qhea_model_exact_noisy_grad_workspace_bytes(ctypes.byref(desc), int(B)))
+    return _workspace(device, nbytes) if nbytes else None
+
+
+def _check_noisy_grad(rc, who):
+    if rc == -2:
+        raise Unsupported(f"{who}: n >= 7, or rates and depth whose inverse walk is ill-conditioned (log10 amplification > 12, "
+                          "or a singular channel)")
+    _check(rc, who)
+
+
+def model_loss_grad_noisy_exact(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None, pred=None):
+    """
+    model_loss_grad under `noise` (a NoiseParams; p1, p2, readout are used): fills grad[P+2] = [d loss/d params | sse | sum y^2]
+    of the exact noisy prediction for this shard (qhea_model_loss_grad_noisy_exact); returns grad.  Raises Unsupported for
+    n >= 7 or a refused conditioning and QheaError for a bad noise setting, in both cases before anything is launched.
+    """
+    lib = load()
+    B = branch.shape[0]
+    _dev_f64(branch, 'branch', (B, desc.branch_in))
+    if desc.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
+    _dev_f64(y, 'y')
+    if y.numel() != B:
+        raise QheaError(f"y has {y.numel()} elements, expected {B}")
+    _dev_f64(params, 'params')
+    _dev_f64(grad, 'grad')
+    if grad.numel() < params.numel() + 2:
+        raise QheaError("model_loss_grad_noisy_exact: grad needs P + 2 entries")
+    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    _dev_f64(pred, 'pred', (B,))
+    ws = _noisy_grad_ws(lib, desc, B, branch.device)
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_loss_grad_noisy_exact(ctypes.byref(desc), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+                                                  _ptr(ham_diag), ctypes.byref(noise), float(inv_batch_total), _ptr(grad),
+                                                  _ptr(pred), _ptr(ws), 0 if ws is None else ws.numel(),
+                                                  _stream(branch.device))
+    _check_noisy_grad(rc, 'qhea_model_loss_grad_noisy_exact')
+    return grad
+
+
+def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                                  lr, beta1, beta2, eps, weight_decay, noise, ham_diag=None):
+    """
+    model_train_steps with the noise in the loss (qhea_model_train_steps_noisy_exact): step i trains on rows
+    bounds[i]:bounds[i+1] under `noise` with residual weight 1 / global_batches[i], leaves [grads | sse | sum y^2] in rows[i]
+    and applies Adam update first_step + i.  Bitwise a loop of model_loss_grad_noisy_exact + adam_step.
+    """
+    lib = load()
+    n_steps = len(bounds) - 1
+    if n_steps <= 0:
+        return rows
+    N = branch.shape[0]
+    _dev_f64(branch, 'branch', (N, desc.branch_in))
+    if desc.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (N, desc.trunk_in))
+    _dev_f64(y, 'y')
+    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+        _dev_f64(t, nm)
+    P = params.numel()
+    if y.numel() != N or bounds[-1] > N or len(global_batches) != n_steps:
+        raise QheaError("model_train_steps_noisy_exact: row bounds do not match the arrays")
+    if rows.dim() != 2 or rows.shape[0] < n_steps or rows.shape[1] < P + 2 or exp_avg.numel() != P or exp_avg_sq.numel() != P:
+        raise QheaError("model_train_steps_noisy_exact: flat vectors have inconsistent lengths")
+    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    biggest = max(bounds[i + 1] - bounds[i] for i in range(n_steps))
+    ws = _noisy_grad_ws(lib, desc, biggest, branch.device)
+    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
+    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_train_steps_noisy_exact(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
+                                                    _ptr(params), _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows),
+                                                    int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
+                                                    float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                                    _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_noisy_grad(rc, 'qhea_model_train_steps_noisy_exact')
+    return rows
 
 
 def clock_probe(device, n_workgroups=1024, iters=200000):

@@ -1409,6 +1409,18 @@ int noise_model_shape(const qhea_model_desc* d, NoiseShape& ns) {
     return QHEA_OK;
 }
 
+int noise_model_grad_map(const qhea_model_desc* d, NoiseGradMap& gm) {
+    ModelInfo mi;
+    const int rc = model_info(d, mi);
+    if (rc != QHEA_OK) return rc;
+    gm.P = mi.P; gm.off_ans = mi.off_ans;
+    for (int s = 0; s < 2; ++s) {
+        gm.off_w[s] = mi.trainable ? mi.off_w[s] : -1; gm.off_b[s] = mi.trainable ? mi.off_b[s] : -1;
+        gm.ncols[s] = (int)mi.enc_cols[s]; gm.width[s] = mi.width[s];
+    }
+    return QHEA_OK;
+}
+
 int launch_noise_prep(const qhea_model_desc* d, int64_t B, const double* branch, const double* trunk, const double* params,
                       double4* gates, double2* cs, void* hdr, hipStream_t st) {
     ModelInfo mi;
@@ -1492,7 +1504,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 510; }
+int qhea_version(void) { return 520; }
 
 const char* qhea_strerror(int code) {
     switch (code) {

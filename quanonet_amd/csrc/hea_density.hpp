@@ -1,0 +1,207 @@
+// hea_density.hpp -- what the density-matrix kernels share: the exact noisy forward (hea_density.hip) and its adjoint gradient
+// (hea_density_grad.hip).  Element layout, bank fold, the pass over two wires, the gates and the depolarizing channels in their
+// closed forms, and the forward sweep's passes; hea_density.hip describes the layout.  Everything sits in an unnamed namespace:
+// each of the two translation units compiles its own copy into its own kernels.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "hea_noise.hpp"
+
+namespace qhea {
+namespace {
+
+constexpr int kDensThreads = 256;
+constexpr int kDensStateBytes = 4096 * (int)sizeof(double2);             // 256 threads x 16 elements
+
+struct DensArgs {
+    const double4* gates;                   // prep table, entry 0 = padding entry -n
+    const double2* cs;                      // [B, E]
+    const double* diag;                     // ham_diag or NULL
+    const double* bias;                     // model bias or NULL
+    double off, co, q;                      // H = off + co sum P_i; readout flip probability
+    double d1_off, d1_keep, d1_mix;         // one-qubit channel: 1 - 4p/3, 1 - 2p/3, 2p/3
+    double d2_keep, d2_mix;                 // two-qubit channel: 1 - lam, lam / 4 (lam = 16 p / 15)
+    long B;
+    int E, pauli;
+    int nb[2], ld[2];
+    double* pred;
+    double* sd;                             // or NULL
+};
+
+struct Cx { double re, im; };
+struct U2 { Cx u00, u01, u10, u11; };
+
+__device__ __forceinline__ double2 cmul(Cx a, double2 b) { return make_double2(a.re * b.x - a.im * b.y, a.re * b.y + a.im * b.x); }
+__device__ __forceinline__ double2 cmulc(Cx a, double2 b) { return make_double2(a.re * b.x + a.im * b.y, a.re * b.y - a.im * b.x); }
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+
+// the 2 x 2 blocks of one wire (local elements base + S {0: rho00, 1: rho10, 2: rho01, 3: rho11}): rho <- U rho U^dagger
+template <int S>
+__device__ __forceinline__ void apply_gate(double2 (&e)[16], const U2& u) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        double2 r[4];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {                                    // U on the row index
+            const double2 x0 = e[b + S * (2 * c)], x1 = e[b + S * (2 * c + 1)];
+            r[2 * c] = cadd(cmul(u.u00, x0), cmul(u.u01, x1));
+            r[2 * c + 1] = cadd(cmul(u.u10, x0), cmul(u.u11, x1));
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {                                    // U* on the column index
+            const double2 x0 = r[a], x1 = r[a + 2];
+            e[b + S * a] = cadd(cmulc(u.u00, x0), cmulc(u.u01, x1));
+            e[b + S * (a + 2)] = cadd(cmulc(u.u10, x0), cmulc(u.u11, x1));
+        }
+    }
+}
+
+// one-qubit depolarizing channel on the same blocks
+template <int S>
+__device__ __forceinline__ void depolarize1(double2 (&e)[16], const DensArgs& a) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        const double2 d0 = e[b], d1 = e[b + 3 * S];
+        e[b] = make_double2(a.d1_keep * d0.x + a.d1_mix * d1.x, a.d1_keep * d0.y + a.d1_mix * d1.y);
+        e[b + 3 * S] = make_double2(a.d1_keep * d1.x + a.d1_mix * d0.x, a.d1_keep * d1.y + a.d1_mix * d0.y);
+        e[b + S].x *= a.d1_off; e[b + S].y *= a.d1_off;
+        e[b + 2 * S].x *= a.d1_off; e[b + 2 * S].y *= a.d1_off;
+    }
+}
+
+// wire q's pending gates of sub-layer s: (encoding RX, channel), fused RY RZ RY, channel
+template <int N, int S>
+__device__ __forceinline__ void wire_gates(double2 (&e)[16], const DensArgs& a, const double2* csr, int s, int col, bool enc,
+                                           int q) {
+    if (enc) {
+        const double2 c = csr[col + q];
+        apply_gate<S>(e, U2{{c.x, 0.0}, {0.0, -c.y}, {0.0, -c.y}, {c.x, 0.0}});
+        depolarize1<S>(e, a);
+    }
+    const double4 v = a.gates[2 * (s * N + q + N)];                      // (u00, u01); u10 = -conj(u01), u11 = conj(u00)
+    apply_gate<S>(e, U2{{v.x, v.y}, {v.z, v.w}, {-v.z, v.w}, {v.x, -v.y}});
+    depolarize1<S>(e, a);
+}
+
+// CNOT(c -> t) on both indices (local bits: 0 / 1 = t's row / column bit, 2 / 3 = c's), then the two-qubit channel
+__device__ __forceinline__ void cnot_depolarize2(double2 (&e)[16], const DensArgs& a) {
+    double2 r[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) r[k] = e[k ^ ((k >> 2) & 1) ^ (((k >> 3) & 1) << 1)];
+    const double sx = (r[0].x + r[3].x) + (r[12].x + r[15].x), sy = (r[0].y + r[3].y) + (r[12].y + r[15].y);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool eq = k == 0 || k == 3 || k == 12 || k == 15;          // row bits (c, t) = column bits
+        e[k].x = eq ? a.d2_keep * r[k].x + a.d2_mix * sx : a.d2_keep * r[k].x;
+        e[k].y = eq ? a.d2_keep * r[k].y + a.d2_mix * sy : a.d2_keep * r[k].y;
+    }
+}
+
+// LDS slot of element i of a row: the low nibble folded with the higher ones (fold is linear, so a pass folds its base once)
+__device__ __forceinline__ int fold(int i) { return ((i >> 4) ^ (i >> 8)) & 15; }
+template <int N> __device__ __forceinline__ int slot_fold(int slot) {
+    return N == 2 ? slot & 15 : N == 3 ? (slot & 3) * 5 : 0;             // rows that share a 16-lane group
+}
+
+// the pass over wires (t, c) = (J, J + 1 mod N): thread `rank` of the row owns the elements base | kt << 2t | kc << 2c
+template <int N, int J> struct Pass {
+    static constexpr int t = J, c = (J + 1) % N, lo = t < c ? t : c, hi = t < c ? c : t;
+    __device__ static __forceinline__ int base(int rank) {
+        int r = rank;
+        r = ((r >> (2 * lo)) << (2 * lo + 2)) | (r & ((1 << (2 * lo)) - 1));
+        r = ((r >> (2 * hi)) << (2 * hi + 2)) | (r & ((1 << (2 * hi)) - 1));
+        return r;
+    }
+    static constexpr int local(int k) { return ((k & 3) << (2 * t)) | ((k >> 2) << (2 * c)); }
+    __device__ static __forceinline__ void load(double2 (&e)[16], const double2* row, int b) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) e[k] = row[b ^ (local(k) ^ fold(local(k)))];
+    }
+    __device__ static __forceinline__ void store(const double2 (&e)[16], double2* row, int b) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) row[b ^ (local(k) ^ fold(local(k)))] = e[k];
+    }
+};
+
+template <int N, int J>
+__device__ __forceinline__ void ring_passes(double2* row, int rank, int sf, const DensArgs& a, const double2* csr, int s,
+                                            int col, bool enc, bool first) {
+    if constexpr (J < N) {
+        using P = Pass<N, J>;
+        const int i0 = P::base(rank), b = i0 ^ fold(i0) ^ sf;
+        double2 e[16];
+        if (J == 0 && first) {                                           // rho = |0><0|
+#pragma unroll
+            for (int k = 0; k < 16; ++k) e[k] = make_double2(k == 0 && rank == 0 ? 1.0 : 0.0, 0.0);
+        } else {
+            P::load(e, row, b);
+        }
+        if (J == 0) wire_gates<N, 1>(e, a, csr, s, col, enc, P::t);
+        if (J <= N - 2) wire_gates<N, 4>(e, a, csr, s, col, enc, P::c);
+        cnot_depolarize2(e, a);
+        P::store(e, row, b);
+        __syncthreads();
+        ring_passes<N, J + 1>(row, rank, sf, a, csr, s, col, enc, false);
+    }
+}
+
+// one-qubit gates on every wire, two wires per pass (J even; the last pass of an odd N wraps to wire 0 and leaves it alone):
+// KIND 0 = a block's encoding RX with its channel (blocks without sub-layers), 1 = H, 2 = H S^dagger (read-out basis, no noise)
+template <int N, int J, int KIND>
+__device__ __forceinline__ void wire_passes(double2* row, int rank, int sf, const DensArgs& a, const double2* csr, int col,
+                                            bool first) {
+    if constexpr (J < N) {
+        using P = Pass<N, J>;
+        const int i0 = P::base(rank), b = i0 ^ fold(i0) ^ sf;
+        double2 e[16];
+        if (J == 0 && first) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) e[k] = make_double2(k == 0 && rank == 0 ? 1.0 : 0.0, 0.0);
+        } else {
+            P::load(e, row, b);
+        }
+        const U2 h = KIND == 1 ? U2{{M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {-M_SQRT1_2, 0.0}}
+                               : U2{{M_SQRT1_2, 0.0}, {0.0, -M_SQRT1_2}, {M_SQRT1_2, 0.0}, {0.0, M_SQRT1_2}};
+        if (KIND == 0) {
+            const double2 c0 = csr[col + P::t];
+            apply_gate<1>(e, U2{{c0.x, 0.0}, {0.0, -c0.y}, {0.0, -c0.y}, {c0.x, 0.0}});
+            depolarize1<1>(e, a);
+            if (J + 1 < N) {
+                const double2 c1 = csr[col + P::c];
+                apply_gate<4>(e, U2{{c1.x, 0.0}, {0.0, -c1.y}, {0.0, -c1.y}, {c1.x, 0.0}});
+                depolarize1<4>(e, a);
+            }
+        } else {
+            apply_gate<1>(e, h);
+            if (J + 1 < N) apply_gate<4>(e, h);
+        }
+        P::store(e, row, b);
+        __syncthreads();
+        wire_passes<N, J + 2, KIND>(row, rank, sf, a, csr, col, false);
+    }
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct DensLayout { size_t off_gates, off_cs, total; };
+
+DensLayout dens_layout(const NoiseShape& ns, int64_t B) {
+    DensLayout L{};
+    size_t p = 256;                                                      // header (prep_model_kernel stamps it)
+    L.off_gates = p; p = align256(p + (size_t)(ns.blk + 2) * ns.n * 2 * sizeof(double4));
+    L.off_cs = p;    p = align256(p + (size_t)B * ns.E * sizeof(double2));
+    L.total = p;
+    return L;
+}
+
+bool rates_ok(const qhea_noise* nz) {
+    if (!nz) return false;
+    for (double p : {nz->p1, nz->p2, nz->readout})
+        if (!(p >= 0.0 && p <= 1.0)) return false;
+    return true;
+}
+}  // namespace
+}  // namespace qhea

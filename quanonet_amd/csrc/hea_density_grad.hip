@@ -1,0 +1,662 @@
+// hea_density_grad.hip -- qhea_model_loss_grad_noisy_exact / qhea_model_train_steps_noisy_exact: the MSE loss of the exact noisy
+// forward (hea_density.hip) and its exact gradient, by the adjoint walk through the density matrix.  The contract is stated in
+// include/quanonet_hea.h; tests/density_grad_reference.py restates the walk in numpy.
+//
+// density_bwd_kernel<N>: one launch per call.  A row's rho and its observable O both live in LDS in the layout of the forward
+// (hea_density.hpp; 2 x 16 * 4^n bytes per row; a workgroup is one wave and its 64 / 4^(n-2) rows, at n = 6 the row's four
+// waves).  The forward sweep carries rho to the end of the circuit and gives pred; O starts as diag h' (pulled back through the H / H S^dagger of an X / Y read-out); then the
+// passes run in reverse.  A reverse pass loads a thread's 16 elements of rho and of O, undoes the two-qubit channel and the CNOT
+// (rho: the channel's inverse; O: the channel itself, which is self-adjoint; the CNOT renaming is an involution on both), and
+// for each wire whose gates the forward applied in that pass: the one-qubit channel (inverse on rho), then for RY(w2), RZ(w1),
+// RY(w0) in turn the trace Im Tr(O sigma rho) followed by the un-rotation of both, and in a block's first sub-layer the
+// encoding's channel, trace and RX^dagger.  rho and O are Hermitian, so Tr(O sigma rho) = sum_k conj(O_k) (sigma rho)_k over the
+// elements a thread holds: no transposed partner is read.
+//
+// Sums: a trace is added over a thread's 16 elements, then over the row's lanes by a fixed butterfly, then (n = 6: four waves
+// per row) over the waves' partials in wave order through LDS.  The row's d pred / d angle goes to rec[angle][row] in the
+// workspace; reduce_density_kernel adds the rows of one parameter in a fixed order (lane l takes rows l, l + 64, ...; the 64
+// lane sums by the same butterfly), applies the frequency chain rule and -- train_steps -- the Adam update of hea_adam.hpp.
+// No atomics; nothing depends on the grid, and a row's record and pred do not depend on the batch or on other rows.
+#include "hea_density.hpp"
+#include "hea_adam.hpp"
+#include "hea_sincos.hpp"
+
+namespace qhea {
+namespace {
+
+constexpr int kTracesPerPass = 8;                                        // two wires x (three angles + the encoding)
+constexpr int kRedWaves = 4;                                             // reduce kernel: one parameter per wave
+// Threads of a density_bwd_kernel workgroup: a row's 4^(n-2) threads, at least QHEA_DENS_BWD_THREADS.  A workgroup's rows are
+// independent (they meet only at the pass barriers), so the choice changes no result; it decides how many CUs a small batch
+// spreads over and how many rows share a CU's LDS.  Measured at 64 and 256: one wave per workgroup is faster
+// at every batch measured (n = 5, batch 100: 1.55 against 1.93 ms per step), so that is what is built.
+#ifndef QHEA_DENS_BWD_THREADS
+#define QHEA_DENS_BWD_THREADS 64
+#endif
+template <int N> constexpr int bwd_threads() {
+    return (1 << (2 * N - 4)) > QHEA_DENS_BWD_THREADS ? (1 << (2 * N - 4)) : QHEA_DENS_BWD_THREADS;
+}
+
+struct DensGradArgs {
+    DensArgs f;                             // the forward's arguments (f.pred: the caller's pred or NULL; f.sd = NULL)
+    const double* w;                        // ansatz angles [blk, 3, n]
+    double o1_keep, o1_mix, o1_off;         // one-qubit channel on O (the forward's) ...
+    double r1_keep, r1_mix, r1_off;         // ... and its inverse on rho
+    double o2_keep, o2_mix, r2_keep, r2_mix;
+    double* pred_ws;                        // [B]
+    double* rec;                            // [E + 3 n blk][B]: d pred_b / d x[b, e], then d pred_b / d w[s, k, q]
+};
+
+// A pass' 32 LDS addresses depend on the thread alone, so the compiler computes those of every pass once, ahead of the loop
+// over the sub-layers, and keeps 32 n values alive through it (up to 198 AGPRs at n = 6, beside the 256 VGPRs the elements and
+// their arithmetic take).  A zero it cannot see through, taken inside the pass, makes it form them where they are used.
+__device__ __forceinline__ int opaque_zero() {
+    int z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+    return z;
+}
+
+// A trace is needed only when the pass ends, and the compiler would move its arithmetic down to there -- keeping the 32 elements
+// it reads alive past the un-rotation that replaces them, once per trace.  This pins the value where it is computed.
+__device__ __forceinline__ double pinned(double t) {
+    asm volatile("" : "+v"(t));
+    return t;
+}
+
+__device__ __forceinline__ double im_cj(double2 a, double2 b) { return a.x * b.y - a.y * b.x; }     // Im(conj(a) b)
+__device__ __forceinline__ double re_cj(double2 a, double2 b) { return a.x * b.x + a.y * b.y; }     // Re(conj(a) b)
+
+// this thread's share of Im Tr(O sigma_AX rho) for the wire of stride S (AX: 0 X, 1 Y, 2 Z)
+template <int S, int AX>
+__device__ __forceinline__ double trace16(const double2 (&o)[16], const double2 (&e)[16]) {
+    double t = 0.0;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {                                    // column bit; elements (row bit 0, row bit 1)
+            const double2 o0 = o[b + S * (2 * c)], o1 = o[b + S * (2 * c + 1)];
+            const double2 r0 = e[b + S * (2 * c)], r1 = e[b + S * (2 * c + 1)];
+            if (AX == 0) t += im_cj(o0, r1) + im_cj(o1, r0);
+            else if (AX == 1) t += re_cj(o1, r0) - re_cj(o0, r1);
+            else t += im_cj(o0, r0) - im_cj(o1, r1);
+        }
+    }
+    return t;
+}
+
+// one-qubit channel with given coefficients (the forward's on O, the inverse's on rho)
+template <int S>
+__device__ __forceinline__ void channel1(double2 (&e)[16], double keep, double mix, double off) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        const double2 d0 = e[b], d1 = e[b + 3 * S];
+        e[b] = make_double2(keep * d0.x + mix * d1.x, keep * d0.y + mix * d1.y);
+        e[b + 3 * S] = make_double2(keep * d1.x + mix * d0.x, keep * d1.y + mix * d0.y);
+        e[b + S].x *= off; e[b + S].y *= off;
+        e[b + 2 * S].x *= off; e[b + 2 * S].y *= off;
+    }
+}
+
+// e <- R e R^T with R = RY(theta)^dagger = [[c, s], [-s, c]]
+template <int S>
+__device__ __forceinline__ void unrotate_y(double2 (&e)[16], double c, double s) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        const double2 x00 = e[b], x10 = e[b + S], x01 = e[b + 2 * S], x11 = e[b + 3 * S];
+        const double2 r00 = make_double2(c * x00.x + s * x10.x, c * x00.y + s * x10.y);
+        const double2 r10 = make_double2(c * x10.x - s * x00.x, c * x10.y - s * x00.y);
+        const double2 r01 = make_double2(c * x01.x + s * x11.x, c * x01.y + s * x11.y);
+        const double2 r11 = make_double2(c * x11.x - s * x01.x, c * x11.y - s * x01.y);
+        e[b] = make_double2(c * r00.x + s * r01.x, c * r00.y + s * r01.y);
+        e[b + 2 * S] = make_double2(c * r01.x - s * r00.x, c * r01.y - s * r00.y);
+        e[b + S] = make_double2(c * r10.x + s * r11.x, c * r10.y + s * r11.y);
+        e[b + 3 * S] = make_double2(c * r11.x - s * r10.x, c * r11.y - s * r10.y);
+    }
+}
+
+// e <- U e U^dagger with U = RX(theta)^dagger = [[c, i s], [i s, c]]
+template <int S>
+__device__ __forceinline__ void unrotate_x(double2 (&e)[16], double c, double s) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        const double2 x00 = e[b], x10 = e[b + S], x01 = e[b + 2 * S], x11 = e[b + 3 * S];
+        // U on the row index: i s (x + i y) = (-s y, s x)
+        const double2 r00 = make_double2(c * x00.x - s * x10.y, c * x00.y + s * x10.x);
+        const double2 r10 = make_double2(c * x10.x - s * x00.y, c * x10.y + s * x00.x);
+        const double2 r01 = make_double2(c * x01.x - s * x11.y, c * x01.y + s * x11.x);
+        const double2 r11 = make_double2(c * x11.x - s * x01.y, c * x11.y + s * x01.x);
+        // U* on the column index: -i s (x + i y) = (s y, -s x)
+        e[b] = make_double2(c * r00.x + s * r01.y, c * r00.y - s * r01.x);
+        e[b + 2 * S] = make_double2(c * r01.x + s * r00.y, c * r01.y - s * r00.x);
+        e[b + S] = make_double2(c * r10.x + s * r11.y, c * r10.y - s * r11.x);
+        e[b + 3 * S] = make_double2(c * r11.x + s * r10.y, c * r11.y - s * r10.x);
+    }
+}
+
+// e <- D e D^dagger with D = RZ(theta)^dagger: rho10 *= exp(-i theta), rho01 *= exp(i theta); (c, s) = (cos, sin)(theta / 2)
+template <int S>
+__device__ __forceinline__ void unrotate_z(double2 (&e)[16], double c, double s) {
+    const double C = c * c - s * s, Sn = 2.0 * s * c;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        const double2 x10 = e[b + S], x01 = e[b + 2 * S];
+        e[b + S] = make_double2(C * x10.x + Sn * x10.y, C * x10.y - Sn * x10.x);
+        e[b + 2 * S] = make_double2(C * x01.x - Sn * x01.y, C * x01.y + Sn * x01.x);
+    }
+}
+
+// channel (inverse on rho), then CNOT(c -> t) on both indices: the reverse of cnot_depolarize2
+__device__ __forceinline__ void undo_cnot2(double2 (&e)[16], double keep, double mix) {
+    const double sx = (e[0].x + e[3].x) + (e[12].x + e[15].x), sy = (e[0].y + e[3].y) + (e[12].y + e[15].y);
+    double2 r[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool eq = k == 0 || k == 3 || k == 12 || k == 15;
+        r[k].x = eq ? keep * e[k].x + mix * sx : keep * e[k].x;
+        r[k].y = eq ? keep * e[k].y + mix * sy : keep * e[k].y;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) e[k] = r[k ^ ((k >> 2) & 1) ^ (((k >> 3) & 1) << 1)];
+}
+
+// encoding of wire q: channel, trace (slot 3 of the wire's four), RX^dagger
+template <int S>
+__device__ __forceinline__ void undo_encoding(double2 (&e)[16], double2 (&o)[16], const DensGradArgs& a, double2 c, double* tr) {
+    channel1<S>(e, a.r1_keep, a.r1_mix, a.r1_off);
+    channel1<S>(o, a.o1_keep, a.o1_mix, a.o1_off);
+    tr[3] = pinned(trace16<S, 0>(o, e));
+    unrotate_x<S>(e, c.x, c.y);
+    unrotate_x<S>(o, c.x, c.y);
+}
+
+// wire q's gates of sub-layer s in reverse; tr[k] = this thread's share of d pred / d w[s, k, q], tr[3] of d pred / d x[col + q]
+template <int N, int S>
+__device__ __forceinline__ void undo_wire(double2 (&e)[16], double2 (&o)[16], const DensGradArgs& a, const double2* csr, int s,
+                                          int col, bool enc, int q, double* tr) {
+    channel1<S>(e, a.r1_keep, a.r1_mix, a.r1_off);
+    channel1<S>(o, a.o1_keep, a.o1_mix, a.o1_off);
+    const double* ws = a.w + (long)s * 3 * N + q;
+    double sn, cn;
+    tr[2] = pinned(trace16<S, 1>(o, e));
+    fast_sincos(0.5 * ws[2 * N], &sn, &cn);
+    unrotate_y<S>(e, cn, sn);
+    unrotate_y<S>(o, cn, sn);
+    tr[1] = pinned(trace16<S, 2>(o, e));
+    fast_sincos(0.5 * ws[N], &sn, &cn);
+    unrotate_z<S>(e, cn, sn); unrotate_z<S>(o, cn, sn);
+    tr[0] = pinned(trace16<S, 1>(o, e));
+    fast_sincos(0.5 * ws[0], &sn, &cn);
+    unrotate_y<S>(e, cn, sn);
+    unrotate_y<S>(o, cn, sn);
+    tr[3] = 0.0;
+    if (enc) undo_encoding<S>(e, o, a, csr[col + q], tr);
+}
+
+// What the passes need of the workgroup: the row's rho and O, its rank and fold, where its record goes
+template <int N> struct RowCtx {
+    static constexpr int TPR = 1 << (2 * N - 4), WPR = TPR > 64 ? TPR / 64 : 1;
+    double2* rho; double2* obs;
+    double* red;                            // [2][WPR][kTracesPerPass], n = 6 only
+    int rank, sf, parity;
+    long r, B;
+    bool live;
+};
+
+// Adds tr[0 .. 8) over the row's threads and stores the sums whose record index idx[i] is >= 0.  Called by every thread of the
+// workgroup after a reverse pass has stored its elements, with the pass' closing barrier inside.
+template <int N>
+__device__ __forceinline__ void flush_traces(RowCtx<N>& cx, const DensGradArgs& a, double (&tr)[kTracesPerPass],
+                                             const int (&idx)[kTracesPerPass]) {
+    using C = RowCtx<N>;
+    constexpr int W = C::TPR < 64 ? C::TPR : 64;
+#pragma unroll
+    for (int i = 0; i < kTracesPerPass; ++i) {
+#pragma unroll
+        for (int o = W / 2; o >= 1; o >>= 1) tr[i] += __shfl_xor(tr[i], o);
+    }
+    if constexpr (C::WPR == 1) {
+        __syncthreads();
+        if (cx.rank == 0 && cx.live) {
+#pragma unroll
+            for (int i = 0; i < kTracesPerPass; ++i)
+                if (idx[i] >= 0) a.rec[(long)idx[i] * cx.B + cx.r] = tr[i];
+        }
+    } else {
+        double* red = cx.red + cx.parity * (C::WPR * kTracesPerPass);
+        const int tid = (int)threadIdx.x;
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < kTracesPerPass; ++i) red[(tid >> 6) * kTracesPerPass + i] = tr[i];
+        }
+        __syncthreads();
+        if (tid < kTracesPerPass && cx.live) {
+            int my = -1;
+#pragma unroll
+            for (int i = 0; i < kTracesPerPass; ++i) my = tid == i ? idx[i] : my;
+            if (my >= 0) {
+                double t = red[tid];
+                for (int wv = 1; wv < C::WPR; ++wv) t += red[wv * kTracesPerPass + tid];
+                a.rec[(long)my * cx.B + cx.r] = t;
+            }
+        }
+        cx.parity ^= 1;                                                  // the next pass' partials go to the other buffer
+    }
+}
+
+// the reverse of ring_passes: passes J = N - 1 .. 0 of sub-layer s
+template <int N, int J>
+__device__ __forceinline__ void ring_passes_back(RowCtx<N>& cx, const DensGradArgs& a, const double2* csr, int s, int col,
+                                                 bool enc) {
+    if constexpr (J >= 0) {
+        using P = Pass<N, J>;
+        const int i0 = P::base(cx.rank | opaque_zero()), b = i0 ^ fold(i0) ^ cx.sf;
+        double2 e[16], o[16];
+        P::load(e, cx.rho, b);
+        P::load(o, cx.obs, b);
+        undo_cnot2(e, a.r2_keep, a.r2_mix);
+        undo_cnot2(o, a.o2_keep, a.o2_mix);
+        double tr[kTracesPerPass];
+        int idx[kTracesPerPass];
+#pragma unroll
+        for (int i = 0; i < kTracesPerPass; ++i) { tr[i] = 0.0; idx[i] = -1; }
+        const int ans = a.f.E + s * 3 * N;
+        if (J <= N - 2) {
+            undo_wire<N, 4>(e, o, a, csr, s, col, enc, P::c, tr);
+            idx[0] = ans + P::c; idx[1] = ans + N + P::c; idx[2] = ans + 2 * N + P::c; idx[3] = enc ? col + P::c : -1;
+        }
+        if (J == 0) {
+            undo_wire<N, 1>(e, o, a, csr, s, col, enc, P::t, tr + 4);
+            idx[4] = ans + P::t; idx[5] = ans + N + P::t; idx[6] = ans + 2 * N + P::t; idx[7] = enc ? col + P::t : -1;
+        }
+        P::store(e, cx.rho, b);
+        P::store(o, cx.obs, b);
+        if (J <= N - 2) flush_traces<N>(cx, a, tr, idx);
+        else __syncthreads();
+        ring_passes_back<N, J - 1>(cx, a, csr, s, col, enc);
+    }
+}
+
+// the reverse of wire_passes<N, J, 0>: a block without sub-layers, its encoding gates only
+template <int N, int J>
+__device__ __forceinline__ void encoding_passes_back(RowCtx<N>& cx, const DensGradArgs& a, const double2* csr, int col) {
+    if constexpr (J < N) {
+        using P = Pass<N, J>;
+        const int i0 = P::base(cx.rank | opaque_zero()), b = i0 ^ fold(i0) ^ cx.sf;
+        double2 e[16], o[16];
+        P::load(e, cx.rho, b);
+        P::load(o, cx.obs, b);
+        double tr[kTracesPerPass];
+        int idx[kTracesPerPass];
+#pragma unroll
+        for (int i = 0; i < kTracesPerPass; ++i) { tr[i] = 0.0; idx[i] = -1; }
+        undo_encoding<1>(e, o, a, csr[col + P::t], tr);
+        idx[3] = col + P::t;
+        if (J + 1 < N) {
+            undo_encoding<4>(e, o, a, csr[col + P::c], tr + 4);
+            idx[7] = col + P::c;
+        }
+        P::store(e, cx.rho, b);
+        P::store(o, cx.obs, b);
+        flush_traces<N>(cx, a, tr, idx);
+        encoding_passes_back<N, J + 2>(cx, a, csr, col);
+    }
+}
+
+// U on every wire of one matrix in LDS (no noise): KIND 3 = H, 4 = S H (the daggers of the read-out basis changes)
+template <int N, int J, int KIND>
+__device__ __forceinline__ void basis_passes_back(double2* row, int rank, int sf) {
+    if constexpr (J < N) {
+        using P = Pass<N, J>;
+        const int i0 = P::base(rank | opaque_zero()), b = i0 ^ fold(i0) ^ sf;
+        double2 e[16];
+        P::load(e, row, b);
+        const U2 h = KIND == 3 ? U2{{M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {-M_SQRT1_2, 0.0}}
+                               : U2{{M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {0.0, M_SQRT1_2}, {0.0, -M_SQRT1_2}};
+        apply_gate<1>(e, h);
+        if (J + 1 < N) apply_gate<4>(e, h);
+        P::store(e, row, b);
+        __syncthreads();
+        basis_passes_back<N, J + 2, KIND>(row, rank, sf);
+    }
+}
+
+template <int N>
+__global__ __launch_bounds__(bwd_threads<N>()) void density_bwd_kernel(DensGradArgs a) {
+    using C = RowCtx<N>;
+    constexpr int TPR = C::TPR, RPW = bwd_threads<N>() / TPR, D = 1 << N, NE = 1 << (2 * N);
+    extern __shared__ __attribute__((aligned(16))) char dens_lds[];      // rho, O, h'[D], the waves' trace partials
+    double2* state = reinterpret_cast<double2*>(dens_lds);
+    double* hv = reinterpret_cast<double*>(dens_lds + 2 * RPW * NE * sizeof(double2));
+    const int tid = threadIdx.x, slot = tid / TPR, rank = tid % TPR;
+    long r = (long)blockIdx.x * RPW + slot;
+    const bool live = r < a.f.B;
+    if (!live) r = a.f.B - 1;                                            // a tail slot repeats the last row and stores nothing
+    const double2* csr = a.f.cs + r * a.f.E;
+    C cx;
+    cx.rho = state + slot * NE;
+    cx.obs = state + RPW * NE + slot * NE;
+    cx.red = hv + D;
+    cx.rank = rank; cx.sf = slot_fold<N>(slot); cx.parity = 0;
+    cx.r = r; cx.B = a.f.B; cx.live = live;
+    double2* row = cx.rho;
+    const int sf = cx.sf;
+
+    // value table under the readout confusion: n two-point mixes of h
+    double h = 0.0;
+    if (tid < D) h = a.f.diag ? a.f.diag[tid] : a.f.off + a.f.co * (double)(N - 2 * (int)__popc(tid));
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (tid < D) hv[tid] = h;
+        __syncthreads();
+        if (tid < D) h = (1.0 - a.f.q) * h + a.f.q * hv[tid ^ (1 << i)];
+        __syncthreads();
+    }
+    if (tid < D) hv[tid] = h;
+
+    // forward sweep: the passes of density_fwd_kernel
+    int s = 0, col = 0;
+    bool first = true;
+    for (int g = 0; g < 2; ++g) {
+        for (int b = 0; b < a.f.nb[g]; ++b) {
+            if (a.f.ld[g] == 0) {
+                wire_passes<N, 0, 0>(row, rank, sf, a.f, csr, col, first);
+                first = false;
+            }
+            for (int l = 0; l < a.f.ld[g]; ++l, ++s) {
+                ring_passes<N, 0>(row, rank, sf, a.f, csr, s, col, l == 0, first);
+                first = false;
+            }
+            col += N;
+        }
+    }
+    if (first) {                                                         // no block at all: rho = |0><0|
+        for (int i = rank; i < NE; i += TPR) row[i] = make_double2(0.0, 0.0);
+        __syncthreads();
+        if (rank == 0) row[fold(0) ^ sf] = make_double2(1.0, 0.0);
+        __syncthreads();
+    }
+    if (a.f.pauli == QHEA_PAULI_X) wire_passes<N, 0, 1>(row, rank, sf, a.f, csr, 0, false);
+    else if (a.f.pauli == QHEA_PAULI_Y) wire_passes<N, 0, 2>(row, rank, sf, a.f, csr, 0, false);
+
+    if (rank == 0 && live) {
+        double m1 = 0.0;
+        for (int k = 0; k < D; ++k) {
+            int i = 0;
+#pragma unroll
+            for (int w = 0; w < N; ++w) i |= ((k >> w) & 1) * (3 << (2 * w));
+            m1 += row[i ^ fold(i) ^ sf].x * hv[k];
+        }
+        const double p = m1 + (a.f.bias ? a.f.bias[0] : 0.0);
+        a.pred_ws[r] = p;
+        if (a.f.pred) a.f.pred[r] = p;
+    }
+
+    // O = diag h' in the read-out basis
+    for (int i = rank; i < NE; i += TPR) {
+        int k = 0;
+        bool diag = true;
+#pragma unroll
+        for (int w = 0; w < N; ++w) {
+            const int rb = (i >> (2 * w)) & 1, cb = (i >> (2 * w + 1)) & 1;
+            diag = diag && rb == cb;
+            k |= rb << w;
+        }
+        cx.obs[i ^ fold(i) ^ sf] = make_double2(diag ? hv[k] : 0.0, 0.0);
+    }
+    __syncthreads();
+    // back to the computational basis: rho and O through the daggers of the basis change
+    if (a.f.pauli == QHEA_PAULI_X) {
+        basis_passes_back<N, 0, 3>(cx.rho, rank, sf);
+        basis_passes_back<N, 0, 3>(cx.obs, rank, sf);
+    } else if (a.f.pauli == QHEA_PAULI_Y) {
+        basis_passes_back<N, 0, 4>(cx.rho, rank, sf);
+        basis_passes_back<N, 0, 4>(cx.obs, rank, sf);
+    }
+
+    // reverse walk: blocks, sub-layers and passes in reverse order
+    for (int g = 1; g >= 0; --g) {
+        for (int b = a.f.nb[g] - 1; b >= 0; --b) {
+            col -= N;
+            for (int l = a.f.ld[g] - 1; l >= 0; --l) {
+                --s;
+                ring_passes_back<N, N - 1>(cx, a, csr, s, col, l == 0);
+            }
+            if (a.f.ld[g] == 0) encoding_passes_back<N, 0>(cx, a, csr, col);
+        }
+    }
+}
+
+// Where output o of the reduce kernel comes from
+struct DensRed {
+    const double* rec; const double* pred; const double* y;
+    const double* in[2];                    // the segments' inputs
+    long B, P, off_ans, off_bias;
+    long off_w[2], off_b[2];
+    int ncols[2], width[2];
+    int E, nans;
+    double inv_bt;
+    double* grad;                           // [P + 2]
+    AdamArgs adam;
+};
+
+// One wave per output: the P gradients, then sum (pred - y)^2 and sum y^2.  Lane l adds rows l, l + 64, ... in order, the lanes'
+// sums meet in a fixed butterfly; lane 0 writes the result and, with adam.p, applies the update of its parameter.
+__global__ __launch_bounds__(64 * kRedWaves) void reduce_density_kernel(DensRed a) {
+    const long o = (long)blockIdx.x * kRedWaves + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (o >= a.P + 2) return;                                            // whole waves
+    // kind: 0 weighted record column, 1 the same times the tiled input, 2 sum g, 3 sse, 4 sum y^2
+    int kind = -1, colx = 0, seg = 0, e = 0;
+    if (o == a.P) kind = 3;
+    else if (o == a.P + 1) kind = 4;
+    else if (o == a.off_bias) kind = 2;
+    else if (o >= a.off_ans && o < a.off_ans + a.nans) { kind = 0; colx = a.E + (int)(o - a.off_ans); }
+    else {
+        for (int sg = 0; sg < 2; ++sg) {
+            if (a.off_w[sg] >= 0 && o >= a.off_w[sg] && o < a.off_w[sg] + a.ncols[sg]) { kind = 1; seg = sg; e = (int)(o - a.off_w[sg]); }
+            if (a.off_b[sg] >= 0 && o >= a.off_b[sg] && o < a.off_b[sg] + a.ncols[sg]) { kind = 0; seg = sg; e = (int)(o - a.off_b[sg]); }
+        }
+        colx = (seg ? a.ncols[0] : 0) + e;
+    }
+    double acc = 0.0;
+    if (kind >= 0) {
+        for (long b = lane; b < a.B; b += 64) {
+            const double yb = a.y[b], d = a.pred[b] - yb;
+            const double g = 2.0 * d * a.inv_bt;
+            double t;
+            if (kind == 0) t = g * a.rec[(long)colx * a.B + b];
+            else if (kind == 1) t = g * a.rec[(long)colx * a.B + b] * a.in[seg][b * a.width[seg] + e % a.width[seg]];
+            else if (kind == 2) t = g;
+            else if (kind == 3) t = d * d;
+            else t = yb * yb;
+            acc += t;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) {
+        a.grad[o] = acc;
+        if (a.adam.p && o < a.P) adam_update(a.adam, o, acc);
+    }
+}
+
+struct DensGradLayout { size_t off_gates, off_cs, off_pred, off_rec, total; };
+
+DensGradLayout dens_grad_layout(const NoiseShape& ns, int64_t B) {
+    DensGradLayout L{};
+    const DensLayout F = dens_layout(ns, B);
+    L.off_gates = F.off_gates; L.off_cs = F.off_cs;
+    size_t p = F.total;
+    L.off_pred = p; p = align256(p + (size_t)B * sizeof(double));
+    L.off_rec = p;  p = align256(p + (size_t)B * ((size_t)ns.E + (size_t)3 * ns.n * ns.blk) * sizeof(double));
+    L.total = p;
+    return L;
+}
+
+// log10 of the factor the inverse walk amplifies the traceless part of rho by; +inf for a singular channel
+double log10_amplification(const NoiseShape& ns, const qhea_noise* nz) {
+    const double k1 = 1.0 - 4.0 * nz->p1 / 3.0, k2 = 1.0 - 16.0 * nz->p2 / 15.0;
+    if (!(k1 > 0.0) || !(k2 > 0.0)) return INFINITY;
+    const double L1 = (double)ns.E + (double)ns.n * ns.blk, L2 = (double)ns.n * ns.blk;
+    return -(L1 * log10(k1) + L2 * log10(k2));
+}
+constexpr double kMaxLog10Amplification = 12.0;
+
+template <int N>
+int launch_density_bwd(const DensGradArgs& a, hipStream_t st) {
+    constexpr int T = bwd_threads<N>(), TPR = 1 << (2 * N - 4), RPW = T / TPR, WPR = TPR > 64 ? TPR / 64 : 1;
+    constexpr size_t smem = 2 * (size_t)RPW * (1 << (2 * N)) * sizeof(double2) + (1 << N) * sizeof(double) +
+                            2 * WPR * kTracesPerPass * sizeof(double);
+    // every launch: the attribute is per device, and a process may drive more than one
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(density_bwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)smem) != hipSuccess)
+        return QHEA_ELAUNCH;
+    hipLaunchKernelGGL(density_bwd_kernel<N>, dim3((unsigned)((a.f.B + RPW - 1) / RPW)), dim3(T), smem, st, a);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
+// everything that can be refused, refused before the first launch
+int check_call(const qhea_model_desc* desc, const double* ham_diag, const qhea_noise* noise, NoiseShape& ns, NoiseGradMap& gm) {
+    int rc = noise_model_shape(desc, ns);
+    if (rc != QHEA_OK) return rc;
+    rc = noise_model_grad_map(desc, gm);
+    if (rc != QHEA_OK) return rc;
+    if (!rates_ok(noise)) return QHEA_EINVAL;
+    if (ns.n > 6) return QHEA_EUNSUPPORTED;                              // 2 x 4^n elements per row in LDS
+    const bool pauli_ok = desc->ham_pauli == QHEA_PAULI_Z || ((desc->ham_pauli == QHEA_PAULI_X ||
+                                                               desc->ham_pauli == QHEA_PAULI_Y) && !ham_diag);
+    if (!pauli_ok) return QHEA_EINVAL;
+    if (!(log10_amplification(ns, noise) <= kMaxLog10Amplification)) return QHEA_EUNSUPPORTED;
+    return QHEA_OK;
+}
+
+// prep, density backward, reduce (+ Adam when adam.p) for one batch; the arguments have been checked
+int loss_grad_launch(const qhea_model_desc* desc, const NoiseShape& ns, const NoiseGradMap& gm, int64_t batch,
+                     const double* branch, const double* trunk, const double* y, const double* params, const double* ham_diag,
+                     const qhea_noise* noise, double inv_bt, double* grad, double* pred, char* ws, hipStream_t st,
+                     const AdamArgs& adam) {
+    const DensGradLayout L = dens_grad_layout(ns, batch);
+    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
+    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
+    int rc = launch_noise_prep(desc, batch, branch, trunk, params, gates, cs, ws, st);
+    if (rc != QHEA_OK) return rc;
+
+    DensGradArgs a{};
+    a.f.gates = gates; a.f.cs = cs; a.f.diag = ham_diag;
+    a.f.bias = ns.off_bias >= 0 ? params + ns.off_bias : nullptr;
+    a.f.off = desc->ham_offset; a.f.co = desc->ham_coeff; a.f.q = noise->readout;
+    a.f.d1_off = 1.0 - 4.0 * noise->p1 / 3.0; a.f.d1_keep = 1.0 - 2.0 * noise->p1 / 3.0; a.f.d1_mix = 2.0 * noise->p1 / 3.0;
+    const double lam = 16.0 * noise->p2 / 15.0;
+    a.f.d2_keep = 1.0 - lam; a.f.d2_mix = lam / 4.0;
+    a.f.B = batch; a.f.E = ns.E; a.f.pauli = desc->ham_pauli;
+    for (int g = 0; g < 2; ++g) { a.f.nb[g] = ns.nb[g]; a.f.ld[g] = ns.ld[g]; }
+    a.f.pred = pred; a.f.sd = nullptr;
+    a.w = params + gm.off_ans;
+    a.o1_keep = a.f.d1_keep; a.o1_mix = a.f.d1_mix; a.o1_off = a.f.d1_off;
+    a.r1_off = 1.0 / a.f.d1_off; a.r1_keep = a.f.d1_keep * a.r1_off; a.r1_mix = -a.f.d1_mix * a.r1_off;
+    a.o2_keep = a.f.d2_keep; a.o2_mix = a.f.d2_mix;
+    a.r2_keep = 1.0 / a.f.d2_keep; a.r2_mix = -a.f.d2_mix * a.r2_keep;
+    a.pred_ws = reinterpret_cast<double*>(ws + L.off_pred);
+    a.rec = reinterpret_cast<double*>(ws + L.off_rec);
+    switch (ns.n) {
+        case 2: rc = launch_density_bwd<2>(a, st); break;
+        case 3: rc = launch_density_bwd<3>(a, st); break;
+        case 4: rc = launch_density_bwd<4>(a, st); break;
+        case 5: rc = launch_density_bwd<5>(a, st); break;
+        case 6: rc = launch_density_bwd<6>(a, st); break;
+        default: rc = QHEA_EUNSUPPORTED;
+    }
+    if (rc != QHEA_OK) return rc;
+
+    DensRed d{};
+    d.rec = a.rec; d.pred = a.pred_ws; d.y = y;
+    d.in[0] = desc->model == QHEA_MODEL_QUANONET ? trunk : branch; d.in[1] = branch;
+    d.B = batch; d.P = gm.P; d.off_ans = gm.off_ans; d.off_bias = ns.off_bias;
+    for (int s = 0; s < 2; ++s) {
+        d.off_w[s] = gm.off_w[s]; d.off_b[s] = gm.off_b[s]; d.ncols[s] = gm.ncols[s]; d.width[s] = gm.width[s];
+    }
+    d.E = ns.E; d.nans = 3 * ns.n * ns.blk;
+    d.inv_bt = inv_bt; d.grad = grad; d.adam = adam;
+    hipLaunchKernelGGL(reduce_density_kernel, dim3((unsigned)((gm.P + 2 + kRedWaves - 1) / kRedWaves)), dim3(64 * kRedWaves), 0,
+                       st, d);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
+}  // namespace
+}  // namespace qhea
+
+using namespace qhea;
+
+extern "C" {
+
+size_t qhea_model_exact_noisy_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch) {
+    NoiseShape ns;
+    if (batch < 0 || noise_model_shape(desc, ns) != QHEA_OK) return 0;
+    return dens_grad_layout(ns, batch).total;
+}
+
+double qhea_model_exact_noisy_log10_amplification(const qhea_model_desc* desc, const qhea_noise* noise) {
+    NoiseShape ns;
+    if (noise_model_shape(desc, ns) != QHEA_OK || !rates_ok(noise)) return NAN;
+    return log10_amplification(ns, noise);
+}
+
+int qhea_model_loss_grad_noisy_exact(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk,
+                                     const double* y, const double* params, const double* ham_diag, const qhea_noise* noise,
+                                     double inv_batch_total, double* grad, double* pred, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    NoiseShape ns;
+    NoiseGradMap gm;
+    const int rc = check_call(desc, ham_diag, noise, ns, gm);
+    if (rc != QHEA_OK) return rc;
+    if (batch < 0) return QHEA_EINVAL;
+    if (batch == 0) return QHEA_OK;
+    if (!branch || !y || !params || !grad || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
+    if (!workspace || workspace_bytes < dens_grad_layout(ns, batch).total) return QHEA_EWORKSPACE;
+    return loss_grad_launch(desc, ns, gm, batch, branch, trunk, y, params, ham_diag, noise, inv_batch_total, grad, pred,
+                            static_cast<char*>(workspace), static_cast<hipStream_t>(stream), AdamArgs{});
+}
+
+int qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
+                                       const double* branch, const double* trunk, const double* y, double* params,
+                                       const double* ham_diag, const qhea_noise* noise, const double* inv_batch_total,
+                                       double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                                       int64_t first_step, double lr, double beta1, double beta2, double eps,
+                                       double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!desc || n_steps < 0 || first_step < 1) return QHEA_EINVAL;
+    NoiseShape ns;
+    NoiseGradMap gm;
+    const int rc0 = check_call(desc, ham_diag, noise, ns, gm);
+    if (rc0 != QHEA_OK) return rc0;
+    if (n_steps == 0) return QHEA_OK;
+    if (!row_begin || !inv_batch_total || !branch || !y || !grad || !params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    if (grad_stride < gm.P + 2) return QHEA_EINVAL;
+    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
+    if (has_trunk && !trunk) return QHEA_EINVAL;
+    size_t need = 0;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
+        const size_t b = dens_grad_layout(ns, row_begin[i + 1] - row_begin[i]).total;
+        need = b > need ? b : need;
+    }
+    if (!workspace || workspace_bytes < need) return QHEA_EWORKSPACE;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
+        const int64_t step = first_step + i;
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+        const int rc = loss_grad_launch(desc, ns, gm, nb, branch + r0 * desc->branch_in,
+                                        has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, ham_diag, noise,
+                                        inv_batch_total[i], grad + i * grad_stride, nullptr, static_cast<char*>(workspace),
+                                        static_cast<hipStream_t>(stream), adam);
+        if (rc != QHEA_OK) return rc;
+    }
+    return QHEA_OK;
+}
+
+}  // extern "C"

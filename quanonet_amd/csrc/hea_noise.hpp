@@ -24,4 +24,14 @@ int noise_model_shape(const qhea_model_desc* d, NoiseShape& ns);
 int launch_noise_prep(const qhea_model_desc* d, int64_t B, const double* branch, const double* trunk, const double* params,
                       double4* gates, double2* cs, void* hdr, hipStream_t st);
 
+// Where a model's gradients live in the flat parameter vector, and what feeds each encoding segment (segment 0: the first
+// ncols[0] columns of x -- QuanONet: trunk, HEAQNN: the input --, segment 1: QuanONet's branch columns): x[b, e] =
+// in[b, e % width] * w[e] + b[e] with trainable frequencies (off_w / off_b >= 0), in[b, e % width] * scale_coeff otherwise.
+struct NoiseGradMap {
+    long P, off_ans;
+    long off_w[2], off_b[2];
+    int ncols[2], width[2];
+};
+int noise_model_grad_map(const qhea_model_desc* d, NoiseGradMap& gm);
+
 }  // namespace qhea

@@ -79,6 +79,10 @@ class EnsembleSolver:
         self.device = device if device is not None else torch.device('cuda')
         if self.device.type != 'cuda':
             raise RuntimeError("EnsembleSolver runs on a HIP device only (no CPU fallback)")
+        if any(c.get('train_noise') is not None for c in self.configs):
+            # the member launches train the ideal circuit; a member that silently ignored its noise would be a wrong run
+            raise ValueError(f"{type(self).__name__}: config key train_noise is not supported in member launches "
+                             "(noise-aware training runs one model per PTSolver)")
         self.log = log
         self.members = []
         for c, d in zip(self.configs, data_dicts):

@@ -115,3 +115,31 @@ def exact_noisy_predict(model, inputs, noise, chunk_rows=16384):
         _lib.model_forward_noisy_exact(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, ham_diag=ham_diag,
                                        out=pred[s:e], shot_std=shot_std[s:e])
     return pred.unsqueeze(-1), shot_std
+
+
+def amplification(model, noise):
+    """
+    log10 of the factor by which the gradient's inverse walk amplifies the traceless part of rho for this model's circuit
+    under `noise`: (1 - 4 p1 / 3)^-L1 (1 - 16 p2 / 15)^-L2 over its L1 one-qubit and L2 CNOT noise locations.  The noise-aware
+    training calls refuse values above 12 (and singular channels, inf); no device is needed.
+    """
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("amplification takes a QuanONetPT or HEAQNNPT model")
+    return _lib.model_exact_noisy_log10_amplification(model.fused_desc(), noise.params())
+
+
+def exact_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
+    """
+    The MSE loss of the exact noisy prediction (exact_noisy_predict) and its exact gradient, as the flat [P + 2] tensor of
+    qhea_model_loss_grad_noisy_exact: d/dparams of sum_b (pred_b - y_b)^2 * inv_batch_total in model.parameters() order, then
+    sum (pred - y)^2 and sum y^2.  inv_batch_total defaults to 1 / rows (the mean); a shard of a larger batch passes the global
+    value.  The gradient is computed by the adjoint walk through the density matrix: no sampling, n <= 6.
+    """
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'exact_noisy_loss_and_grad')
+    B = branch.shape[0]
+    y = y.detach().to(torch.float64).reshape(-1).contiguous()
+    grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
+    if B == 0:
+        return grad
+    inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
+    return _lib.model_loss_grad_noisy_exact(desc, branch, trunk, y, flat, noise.params(), inv, grad, ham_diag=ham_diag)

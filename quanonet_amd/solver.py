@@ -226,6 +226,18 @@ class PeerExchange:
             self.own = None
 
 
+def _train_noise(v):
+    """config value / argument `train_noise` -> NoiseModel or None (a NoiseModel, or a dict of its fields)"""
+    if v is None:
+        return None
+    from .noise import NoiseModel
+    if isinstance(v, NoiseModel):
+        return v
+    if isinstance(v, dict):
+        return NoiseModel(**v)
+    raise ValueError(f"train_noise must be a quanonet_amd.noise.NoiseModel or a dict of its fields (got {type(v).__name__})")
+
+
 class DataParallelTrainer:
     """
     fused='auto': when the model is one of this package's QuanONetPT / HEAQNNPT (fp64, on a HIP
@@ -235,8 +247,9 @@ class DataParallelTrainer:
     """
 
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
-                 fused='auto', peer_exchange=True, log=None):
+                 fused='auto', peer_exchange=True, log=None, train_noise=None):
         self.model = model
+        self.train_noise = _train_noise(train_noise)
         self.world = int(world_size)
         self.dist = dist
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -292,6 +305,23 @@ class DataParallelTrainer:
                 self.peer, self.dp_exchange_reason = PeerExchange.create(dist, dist.get_rank(), self.world, self.numel + 2,
                                                                          p0.device, log=log)
                 self.peer_fused = self.peer is not None and self.desc is not None
+        if self.train_noise is not None:
+            # the loss is the exact noisy one (qhea_model_loss_grad_noisy_exact): refuse here what the call would refuse
+            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+                raise ValueError("train_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
+                                 "Adam with betas / eps / weight_decay only)")
+            from . import _lib
+            amp = _lib.model_exact_noisy_log10_amplification(self.desc, self.train_noise.params())
+            if self.desc.n_qubits > 6 or not amp <= 12.0:
+                raise ValueError(f"train_noise: noise-aware training takes n <= 6 and log10 amplification <= 12 (this model: "
+                                 f"n = {self.desc.n_qubits}, {amp:.2f}); see quanonet_amd.noise.amplification")
+            if self.peer_fused:
+                self.peer_fused = False
+                self.dp_exchange_reason = ("peer exchange as a separate kernel: the noise-aware step has no reduce kernel with "
+                                           "the exchange inside")
+            if log is not None:
+                log(f"noise-aware training: the loss and 'loss_train' are the exact noisy MSE under p1={self.train_noise.p1:g} "
+                    f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g} (log10 amplification {amp:.2f})")
 
     def broadcast_parameters(self):
         self.dist.broadcast(self.pflat, src=0)
@@ -320,8 +350,12 @@ class DataParallelTrainer:
             from . import _lib
             branch = inputs[0]
             trunk = inputs[1] if len(inputs) > 1 else None
-            _lib.model_loss_grad(self.desc, branch, trunk, y.reshape(-1), self.pflat, 1.0 / gb,
-                                 self.flat if out is None else out, ham_diag=self._ham_diag())
+            if self.train_noise is not None:
+                _lib.model_loss_grad_noisy_exact(self.desc, branch, trunk, y.reshape(-1), self.pflat, self.train_noise.params(),
+                                                 1.0 / gb, self.flat if out is None else out, ham_diag=self._ham_diag())
+            else:
+                _lib.model_loss_grad(self.desc, branch, trunk, y.reshape(-1), self.pflat, 1.0 / gb,
+                                     self.flat if out is None else out, ham_diag=self._ham_diag())
         else:
             self.flat.zero_()
             pred = self._forward(inputs)
@@ -347,6 +381,13 @@ class DataParallelTrainer:
             gb = float(global_batch if global_batch is not None else y.shape[0])
             opt, g = self.optimizer, self.optimizer.param_groups[0]
             opt.t += 1
+            if self.train_noise is not None:
+                _lib.model_train_steps_noisy_exact(self.desc, [0, y.shape[0]], [gb], inputs[0],
+                                                   inputs[1] if len(inputs) > 1 else None, y.reshape(-1), self.pflat,
+                                                   flat.view(1, -1), opt.exp_avg, opt.exp_avg_sq, opt.t, g['lr'], g['betas'][0],
+                                                   g['betas'][1], g['eps'], g['weight_decay'], self.train_noise.params(),
+                                                   ham_diag=self._ham_diag())
+                return flat
             _lib.model_train_step(self.desc, inputs[0], inputs[1] if len(inputs) > 1 else None, y.reshape(-1),
                                   self.pflat, 1.0 / gb, flat, opt.exp_avg, opt.exp_avg_sq, opt.t, g['lr'],
                                   g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'],
@@ -503,9 +544,16 @@ class DataParallelTrainer:
             self._last = rows[n_steps - 1]
             return rows
         opt, g = self.optimizer, self.optimizer.param_groups[0]
-        _lib.model_train_steps(self.desc, bounds, global_batches, inputs[0], inputs[1] if len(inputs) > 1 else None,
-                               y.reshape(-1), self.pflat, rows, opt.exp_avg, opt.exp_avg_sq, opt.t + 1, g['lr'],
-                               g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'], ham_diag=self._ham_diag())
+        if self.train_noise is not None:
+            _lib.model_train_steps_noisy_exact(self.desc, bounds, global_batches, inputs[0],
+                                               inputs[1] if len(inputs) > 1 else None, y.reshape(-1), self.pflat, rows,
+                                               opt.exp_avg, opt.exp_avg_sq, opt.t + 1, g['lr'], g['betas'][0], g['betas'][1],
+                                               g['eps'], g['weight_decay'], self.train_noise.params(),
+                                               ham_diag=self._ham_diag())
+        else:
+            _lib.model_train_steps(self.desc, bounds, global_batches, inputs[0], inputs[1] if len(inputs) > 1 else None,
+                                   y.reshape(-1), self.pflat, rows, opt.exp_avg, opt.exp_avg_sq, opt.t + 1, g['lr'],
+                                   g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'], ham_diag=self._ham_diag())
         opt.t += n_steps
         self._last = rows[n_steps - 1]
         return rows
@@ -567,7 +615,7 @@ class PTSolver:
                                            dist=dist, optimizer=config.get('optimizer', 'adam'),
                                            optimizer_kwargs=config.get('optimizer_kwargs', {}),
                                            peer_exchange=str(config.get('dp_exchange', 'peer')).lower() == 'peer',
-                                           log=self.log)
+                                           log=self.log, train_noise=config.get('train_noise'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None

@@ -1,0 +1,266 @@
+"""
+numpy reference for the noise-aware loss gradient (qhea_model_loss_grad_noisy_exact, include/quanonet_hea.h): the adjoint walk
+over the primitives of tests/density_reference.py, batched over rows.
+
+circuit_grad walks the circuit forward keeping rho after every rotation (the stored walk: no channel is ever inverted), starts
+the observable at O = B^dagger diag(h') B (B: the basis change of an X / Y read-out, h' the value table under the readout
+confusion) and pulls it back gate by gate: a depolarizing channel is self-adjoint, a unitary U takes O to U^dagger O U, and a
+rotation exp(-i theta sigma / 2) whose output state is rho_k contributes d pred / d theta = Im Tr(O_k sigma rho_k).
+inverse_walk_grad is the same walk with rho recomputed by inverting the channels, the way the kernel does it; the pair measures
+the conditioning of that inversion.  model_loss_grad adds the model around the circuit: frequency layers, bias, the MSE
+residual and the flat [P + 2] layout of the header.
+"""
+import numpy as np
+
+from oracle import hea_oracle as O
+from tests import density_reference as DR
+
+SIGMA = {'x': np.array([[0, 1], [1, 0]], complex), 'y': np.array([[0, -1j], [1j, 0]], complex),
+         'z': np.array([[1, 0], [0, -1]], complex)}
+
+
+def _rot(kind, ang):
+    """(m00, m01, m10, m11) of RX / RY / RZ, each a (B,) array or scalar"""
+    c, s = np.cos(ang / 2), np.sin(ang / 2)
+    if kind == 'x':
+        return (c, -1j * s, -1j * s, c)
+    if kind == 'y':
+        return (c + 0j, -s + 0j, s + 0j, c + 0j)
+    return (np.exp(-0.5j * ang), 0.0 * ang, 0.0 * ang, np.exp(0.5j * ang))
+
+
+def _dagger(m):
+    return (np.conj(m[0]), np.conj(m[2]), np.conj(m[1]), np.conj(m[3]))
+
+
+def _left(rho, n, q, sig):
+    """sigma_q rho"""
+    r = np.moveaxis(rho, DR._row_axis(n, q), 1)
+    r = np.einsum('ij,bj...->bi...', sig, r)
+    return np.moveaxis(r, 1, DR._row_axis(n, q))
+
+
+def _trace(obs, m, n):
+    """Tr(O M) per row"""
+    D = 1 << n
+    return np.einsum('bij,bji->b', obs.reshape(-1, D, D), m.reshape(-1, D, D))
+
+
+def _inv_depolarize1(rho, n, q, p):
+    if p == 0.0:
+        return rho
+    r = np.moveaxis(rho, (DR._row_axis(n, q), DR._col_axis(n, q)), (1, 2)).copy()
+    k, m, o = 1 - 2 * p / 3, 2 * p / 3, 1 - 4 * p / 3
+    d0, d1 = r[:, 0, 0].copy(), r[:, 1, 1].copy()
+    r[:, 0, 1] /= o
+    r[:, 1, 0] /= o
+    r[:, 0, 0] = (k * d0 - m * d1) / o
+    r[:, 1, 1] = (k * d1 - m * d0) / o
+    return np.moveaxis(r, (1, 2), (DR._row_axis(n, q), DR._col_axis(n, q)))
+
+
+def _depolarize2(rho, n, c, t, p, inverse=False):
+    """the two-qubit channel alone (no CNOT), or its inverse"""
+    if p == 0.0:
+        return rho
+    axes = (DR._row_axis(n, c), DR._row_axis(n, t), DR._col_axis(n, c), DR._col_axis(n, t))
+    r = np.moveaxis(rho, axes, (1, 2, 3, 4)).copy()
+    lam = 16 * p / 15
+    pairs = [(a, b) for a in (0, 1) for b in (0, 1)]
+    eq = [r[:, a, b, a, b].copy() for a, b in pairs]
+    tot = eq[0] + eq[1] + eq[2] + eq[3]
+    if inverse:
+        r /= 1 - lam
+        for v, (a, b) in zip(eq, pairs):
+            r[:, a, b, a, b] = (v - lam / 4 * tot) / (1 - lam)
+    else:
+        r *= 1 - lam
+        for v, (a, b) in zip(eq, pairs):
+            r[:, a, b, a, b] = (1 - lam) * v + lam / 4 * tot
+    return np.moveaxis(r, (1, 2, 3, 4), axes)
+
+
+def _cnot(rho, n, c, t):
+    return DR._cnot_depolarize2(rho, n, c, t, 0.0)
+
+
+def _ops(n, cfgs):
+    """the circuit as a list: ('x' | 'y' | 'z', wire, angle key), ('d1', wire), ('cd', control, target)"""
+    ops, col, s = [], 0, 0
+    for n_enc, ld in cfgs:
+        assert n_enc == n
+        for q in range(n):
+            ops += [('x', q, ('x', col + q)), ('d1', q)]
+        col += n
+        for _ in range(ld):
+            for q in range(n):
+                ops += [('y', q, ('w', s, 0, q)), ('z', q, ('w', s, 1, q)), ('y', q, ('w', s, 2, q)), ('d1', q)]
+            for j in range(n):
+                ops.append(('cd', (j + 1) % n, j))
+            s += 1
+    return ops
+
+
+def value_table(n, readout, offset=0.0, coeff=1.0, ham_diag=None):
+    """h'[k]: the read value of bitstring k, mixed over the readout flips"""
+    D = 1 << n
+    kk = np.arange(D)
+    if ham_diag is not None:
+        hv = np.asarray(ham_diag, np.float64)
+    else:
+        hv = offset + coeff * (n - 2.0 * sum((kk >> i) & 1 for i in range(n)))
+    conf = np.ones((D, D))
+    for i in range(n):
+        diff = ((kk[:, None] ^ kk[None, :]) >> i) & 1
+        conf *= np.where(diff, readout, 1.0 - readout)
+    return conf @ hv
+
+
+def circuit_grad(n, cfgs, x, w, p1, p2, readout, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', inverse=False):
+    """
+    (value[B], d value / d x [B, E], d value / d w [B, blk, 3, n]) of the exact noisy expectation (no bias).
+    inverse=False: rho after every rotation is kept from the forward sweep; True: rho is walked back through inverse channels.
+    """
+    pauli = O._check_pauli(ham_pauli, ham_diag)
+    x = np.asarray(x, np.float64)
+    w = np.asarray(w, np.float64)
+    B = x.shape[0]
+    ops = _ops(n, cfgs)
+
+    def angle(key):
+        return x[:, key[1]] if key[0] == 'x' else np.full(B, w[key[1], key[2], key[3]])
+
+    rho = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    rho[(slice(None),) + (0,) * (2 * n)] = 1.0
+    keep = {}
+    for k, op in enumerate(ops):
+        if op[0] == 'd1':
+            rho = DR._depolarize1(rho, n, op[1], p1)
+        elif op[0] == 'cd':
+            rho = DR._cnot_depolarize2(rho, n, op[1], op[2], p2)
+        else:
+            rho = DR._gate(rho, n, op[1], _rot(op[0], angle(op[2])))
+            if not inverse:
+                keep[k] = rho
+    # O_N = B^dagger diag(h') B
+    hv = value_table(n, readout, offset, coeff, ham_diag)
+    obs = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    obs.reshape(B, 1 << n, 1 << n)[:, np.arange(1 << n), np.arange(1 << n)] = hv
+    if pauli != 'Z':
+        for q in range(n):
+            obs = DR._gate(obs, n, q, (DR.SQ, DR.SQ, DR.SQ, -DR.SQ))                 # H is its own dagger
+            if pauli == 'Y':
+                obs = DR._gate(obs, n, q, (1.0, 0.0, 0.0, 1j))                       # S = (S^dagger)^dagger
+    value = np.real(_trace(obs, rho, n))
+    gx = np.zeros((B, x.shape[1]))
+    gw = np.zeros((B,) + w.shape)
+    for k in range(len(ops) - 1, -1, -1):
+        op = ops[k]
+        if op[0] == 'd1':
+            if inverse:
+                rho = _inv_depolarize1(rho, n, op[1], p1)
+            obs = DR._depolarize1(obs, n, op[1], p1)
+        elif op[0] == 'cd':
+            if inverse:
+                rho = _cnot(_depolarize2(rho, n, op[1], op[2], p2, True), n, op[1], op[2])
+            obs = _cnot(_depolarize2(obs, n, op[1], op[2], p2), n, op[1], op[2])
+        else:
+            if not inverse:
+                rho = keep.pop(k)
+            g = np.imag(_trace(obs, _left(rho, n, op[1], SIGMA[op[0]]), n))
+            key = op[2]
+            if key[0] == 'x':
+                gx[:, key[1]] = g
+            else:
+                gw[:, key[1], key[2], key[3]] = g
+            ud = _dagger(_rot(op[0], angle(key)))
+            if inverse:
+                rho = DR._gate(rho, n, op[1], ud)
+            obs = DR._gate(obs, n, op[1], ud)
+    return value, gx, gw
+
+
+def log10_amplification(n, cfgs, p1, p2):
+    """log10 of what the inverse walk multiplies the traceless part of rho by (inf for a singular channel)"""
+    blk = sum(ld for _, ld in cfgs)
+    L1, L2 = n * len(cfgs) + n * blk, n * blk
+    k1, k2 = 1 - 4 * p1 / 3, 1 - 16 * p2 / 15
+    if k1 <= 0 or k2 <= 0:
+        return np.inf
+    return -(L1 * np.log10(k1) + L2 * np.log10(k2))
+
+
+def spec_of(model):
+    """what model_loss_grad needs of a QuanONetPT / HEAQNNPT (read-out, shape, frequency kind)"""
+    from quanonet_amd.models import QuanONetPT
+    q = model.quantum_layer
+    quanonet = isinstance(model, QuanONetPT)
+    freq = model.branch_freq if quanonet else model.freq
+    trainable = hasattr(freq, 'weights')
+    return dict(kind='quanonet' if quanonet else 'heaqnn', n=model.num_qubits, net=tuple(model.net_size), trainable=trainable,
+                scale=None if trainable else float(freq.scale), offset=float(q.ham_offset), coeff=float(q.ham_coeff),
+                ham_diag=q.ham_diag.detach().cpu().numpy() if q.use_full_ham else None,
+                ham_pauli=('Z', 'X', 'Y')[q.ham_pauli])
+
+
+def _tiled(v, cols):
+    v = np.asarray(v, np.float64)
+    return np.tile(v, (1, -(-cols // v.shape[1])))[:, :cols]
+
+
+def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_total, inverse=False):
+    """
+    ([P + 2] buffer, pred[B]) of the header's qhea_model_loss_grad_noisy_exact: gradients of sum_b (pred_b - y_b)^2 *
+    inv_batch_total in the flat parameter layout, then sum (pred - y)^2 and sum y^2.
+    """
+    n, net = spec['n'], spec['net']
+    flat = np.asarray(flat, np.float64)
+    y = np.asarray(y, np.float64).reshape(-1)
+    quanonet = spec['kind'] == 'quanonet'
+    if quanonet:
+        cfgs = O.block_configs_quanonet(n, net)
+        segs = [('trunk', np.asarray(trunk, np.float64), net[2] * n), ('branch', np.asarray(branch, np.float64), net[0] * n)]
+    else:
+        cfgs = O.block_configs_heaqnn(n, net)
+        segs = [('x', np.asarray(branch, np.float64), net[0] * n)]
+    blk = sum(ld for _, ld in cfgs)
+    # flat layout: [bias] [branch w, b] [trunk w, b] ansatz  /  [w, b] ansatz
+    p = 1 if quanonet else 0
+    off = {}
+    if spec['trainable']:
+        for name, _, cols in (segs[::-1] if quanonet else segs):
+            off[name] = (p, p + cols)
+            p += 2 * cols
+    off_ans = p
+    P = p + blk * 3 * n
+    assert flat.size == P, (flat.size, P)
+    xs, tiles = [], []
+    for name, v, cols in segs:
+        t = _tiled(v, cols)
+        tiles.append(t)
+        if spec['trainable']:
+            ow, ob = off[name]
+            xs.append(t * flat[ow:ow + cols] + flat[ob:ob + cols])
+        else:
+            xs.append(t * spec['scale'])
+    x = np.concatenate(xs, axis=1)
+    w = flat[off_ans:].reshape(blk, 3, n)
+    value, gx, gw = circuit_grad(n, cfgs, x, w, p1, p2, readout, spec['offset'], spec['coeff'], spec['ham_diag'],
+                                 spec['ham_pauli'], inverse=inverse)
+    pred = value + (flat[0] if quanonet else 0.0)
+    g = 2.0 * (pred - y) * inv_batch_total
+    out = np.zeros(P + 2)
+    if quanonet:
+        out[0] = g.sum()
+    out[off_ans:P] = np.einsum('b,bskq->skq', g, gw).reshape(-1)
+    if spec['trainable']:
+        col = 0
+        for (name, _, cols), t in zip(segs, tiles):
+            ow, ob = off[name]
+            gcol = g[:, None] * gx[:, col:col + cols]
+            out[ow:ow + cols] = (gcol * t).sum(axis=0)
+            out[ob:ob + cols] = gcol.sum(axis=0)
+            col += cols
+    out[P] = ((pred - y) ** 2).sum()
+    out[P + 1] = (y ** 2).sum()
+    return out, pred
