@@ -462,16 +462,17 @@ def model_train_step(desc, branch, trunk, y, params, inv_batch_total, grad, exp_
     return grad
 
 
-def model_train_steps(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step, lr,
-                      beta1, beta2, eps, weight_decay, ham_diag=None):
-    """
-    One epoch's inner loop in one host call (qhea_model_train_steps): step i trains on rows bounds[i]:bounds[i+1] of the
-    contiguous branch / trunk / y with residual weight 1 / global_batches[i] and leaves [grads | sse | sum y^2] in rows[i].
-    """
-    lib = load()
+def _schedule(bounds, global_batches):
+    """(n_steps, row_begin, inv_batch_total, largest batch) of a training schedule: the two arrays as the C ABI takes them."""
     n_steps = len(bounds) - 1
-    if n_steps <= 0:
-        return rows
+    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
+    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
+    return n_steps, rb, ib, max(bounds[i + 1] - bounds[i] for i in range(n_steps))
+
+
+def _flat_train_schedule(who, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, ham_diag):
+    """The argument checks of the single-model schedule calls (who: the public function, for the messages); their _schedule."""
+    n_steps = len(bounds) - 1
     N = branch.shape[0]
     _dev_f64(branch, 'branch', (N, desc.branch_in))
     if desc.model == MODEL_QUANONET:
@@ -481,14 +482,25 @@ def model_train_steps(desc, bounds, global_batches, branch, trunk, y, params, ro
         _dev_f64(t, nm)
     P = params.numel()
     if y.numel() != N or bounds[-1] > N or len(global_batches) != n_steps:
-        raise QheaError("model_train_steps: row bounds do not match the arrays")
+        raise QheaError(f"{who}: row bounds do not match the arrays")
     if rows.dim() != 2 or rows.shape[0] < n_steps or rows.shape[1] < P + 2 or exp_avg.numel() != P or exp_avg_sq.numel() != P:
-        raise QheaError("model_train_steps: flat vectors have inconsistent lengths")
+        raise QheaError(f"{who}: flat vectors have inconsistent lengths")
     _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
-    biggest = max(bounds[i + 1] - bounds[i] for i in range(n_steps))
+    return _schedule(bounds, global_batches)
+
+
+def model_train_steps(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step, lr,
+                      beta1, beta2, eps, weight_decay, ham_diag=None):
+    """
+    One epoch's inner loop in one host call (qhea_model_train_steps): step i trains on rows bounds[i]:bounds[i+1] of the
+    contiguous branch / trunk / y with residual weight 1 / global_batches[i] and leaves [grads | sse | sum y^2] in rows[i].
+    """
+    lib = load()
+    if len(bounds) - 1 <= 0:
+        return rows
+    n_steps, rb, ib, biggest = _flat_train_schedule('model_train_steps', desc, bounds, global_batches, branch, trunk, y, params,
+                                                    rows, exp_avg, exp_avg_sq, ham_diag)
     ws = _model_ws(desc, biggest, branch.device)
-    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
-    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
     with torch.cuda.device(branch.device):
         rc = lib.qhea_model_train_steps(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
                                         _ptr(ham_diag), ib, _ptr(rows), int(rows.stride(0)), _ptr(exp_avg),
@@ -496,6 +508,78 @@ def model_train_steps(desc, bounds, global_batches, branch, trunk, y, params, ro
                                         float(eps), float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
     _check(rc, 'qhea_model_train_steps')
     return rows
+
+
+def _desc_array(descs):
+    descs = list(descs)
+    return (ModelDesc * max(1, len(descs)))(*descs), len(descs)
+
+
+def _member_train_steps(who, descs, members, lr, ws_bytes, zero_msg, diag_qubits, bounds, global_batches, branch, trunk, y,
+                        params, rows, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, ham_diag):
+    """
+    What model_ensemble / sweep / depth_sweep / qubit_sweep_train_steps share: the checks of the [R, N, ...] inputs, the [R, P]
+    state and the [R, n_steps, >= P+2] rows, the workspace, the marshalling and the call of qhea_<who>.  who: the public
+    function (for the messages).  descs: [desc], or -- zero_msg given -- the R members' descriptors, P then being the largest
+    member's parameter count and zero_msg the message for descriptors the library cannot take as one sweep.  members: the R
+    MemberHParams, or None for an ensemble (one lr, one shared ham_diag).  ws_bytes(R, batch): the workspace size query;
+    diag_qubits(descs): the qubit count that sizes a ham_diag row.
+    """
+    lib = load()
+    n_steps = len(bounds) - 1
+    if n_steps <= 0:
+        return rows
+    if branch.dim() != 3:
+        raise QheaError(f"{who}: branch must be [n_models, rows, branch_in]")
+    R, N = branch.shape[0], branch.shape[1]
+    per_member = zero_msg is not None
+    if members is not None and (len(members) != R or (per_member and len(descs) != R)):
+        n_descs = f"{len(descs)} descriptors / " if per_member else ""
+        raise QheaError(f"{who}: {n_descs}{len(members)} member records for {R} members")
+    d0 = descs[0]
+    _dev_f64(branch, 'branch', (R, N, d0.branch_in))
+    if d0.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (R, N, d0.trunk_in))
+    _dev_f64(y, 'y')
+    if tuple(y.shape) not in ((R, N), (R, N, 1)):
+        raise QheaError(f"y has shape {tuple(y.shape)}, expected ({R}, {N})")
+    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+        _dev_f64(t, nm)
+    if per_member:
+        P = depth_sweep_pmax(descs)
+        p_name, p_shape = 'Pmax', f'Pmax = {P}'
+    else:
+        P = params.shape[-1] if params.dim() == 2 else -1
+        p_name, p_shape = 'P', 'P'
+    if tuple(params.shape) != (R, P) or tuple(exp_avg.shape) != (R, P) or tuple(exp_avg_sq.shape) != (R, P):
+        raise QheaError(f"{who}: params / exp_avg / exp_avg_sq must be [n_models, {p_shape}]")
+    if rows.dim() != 3 or rows.shape[0] != R or rows.shape[1] != n_steps or rows.shape[2] < P + 2:
+        raise QheaError(f"{who}: rows must be [n_models, n_steps, >= {p_name}+2]")
+    if bounds[0] < 0 or bounds[-1] != N or len(global_batches) != n_steps:
+        raise QheaError(f"{who}: row bounds do not match the arrays")
+    _dev_f64(ham_diag, 'ham_diag', (() if members is None else (R,)) + (1 << diag_qubits(descs),))
+    with torch.cuda.device(branch.device):
+        nbytes = max(ws_bytes(R, b) for b in sorted({bounds[i + 1] - bounds[i] for i in range(n_steps)}))
+    if per_member and nbytes == 0:
+        raise QheaError(f"{who}: {zero_msg}")
+    ws = _workspace(branch.device, nbytes)
+    n_steps, rb, ib, _ = _schedule(bounds, global_batches)
+    head = (_desc_array(descs)[0], R)
+    data = (_ptr(branch), _ptr(trunk), _ptr(y), _ptr(params))
+    state = (ib, _ptr(rows), int(rows.stride(1)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step))
+    rest = (float(beta1), float(beta2), float(eps), float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
+    if members is None:
+        args = head + (n_steps, rb) + data + (_ptr(ham_diag),) + state + (float(lr),) + rest
+    else:
+        args = head + ((MemberHParams * R)(*members), _ptr(ham_diag), n_steps, rb) + data + state + rest
+    with torch.cuda.device(branch.device):
+        rc = getattr(lib, 'qhea_' + who)(*args)
+    _check(rc, 'qhea_' + who)
+    return rows
+
+
+def _same_qubits(descs):
+    return descs[0].n_qubits
 
 
 def model_ensemble_workspace_bytes(desc, n_models, batch):
@@ -511,42 +595,10 @@ def model_ensemble_train_steps(desc, bounds, global_batches, branch, trunk, y, p
     rows: [R, n_steps, >= P+2]; every member follows the same schedule (bounds, global_batches).  Bitwise what
     model_train_steps gives for each member alone under the backward variant the ensemble chose.
     """
-    lib = load()
-    n_steps = len(bounds) - 1
-    if n_steps <= 0:
-        return rows
-    if branch.dim() != 3:
-        raise QheaError("model_ensemble_train_steps: branch must be [n_models, rows, branch_in]")
-    R, N = branch.shape[0], branch.shape[1]
-    _dev_f64(branch, 'branch', (R, N, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (R, N, desc.trunk_in))
-    _dev_f64(y, 'y')
-    if tuple(y.shape) not in ((R, N), (R, N, 1)):
-        raise QheaError(f"y has shape {tuple(y.shape)}, expected ({R}, {N})")
-    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-        _dev_f64(t, nm)
-    P = params.shape[-1] if params.dim() == 2 else -1
-    if params.dim() != 2 or params.shape[0] != R or tuple(exp_avg.shape) != (R, P) or tuple(exp_avg_sq.shape) != (R, P):
-        raise QheaError("model_ensemble_train_steps: params / exp_avg / exp_avg_sq must be [n_models, P]")
-    if rows.dim() != 3 or rows.shape[0] != R or rows.shape[1] != n_steps or rows.shape[2] < P + 2:
-        raise QheaError("model_ensemble_train_steps: rows must be [n_models, n_steps, >= P+2]")
-    if bounds[0] < 0 or bounds[-1] != N or len(global_batches) != n_steps:
-        raise QheaError("model_ensemble_train_steps: row bounds do not match the arrays")
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
-    with torch.cuda.device(branch.device):
-        nbytes = max(model_ensemble_workspace_bytes(desc, R, bounds[i + 1] - bounds[i]) for i in range(n_steps))
-    ws = _workspace(branch.device, nbytes)
-    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
-    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_ensemble_train_steps(ctypes.byref(desc), R, n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
-                                                 _ptr(params), _ptr(ham_diag), ib, _ptr(rows), int(rows.stride(1)),
-                                                 _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step), float(lr), float(beta1),
-                                                 float(beta2), float(eps), float(weight_decay), _ptr(ws), ws.numel(),
-                                                 _stream(branch.device))
-    _check(rc, 'qhea_model_ensemble_train_steps')
-    return rows
+    return _member_train_steps('model_ensemble_train_steps', [desc], None, lr,
+                               lambda R, b: model_ensemble_workspace_bytes(desc, R, b), None, _same_qubits,
+                               bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                               beta1, beta2, eps, weight_decay, ham_diag)
 
 
 def member_hparams(scale_coeff, ham_offset, ham_coeff, lr, ham_pauli=0):
@@ -567,49 +619,10 @@ def model_sweep_train_steps(desc, members, bounds, global_batches, branch, trunk
     desc fixes the shape only.  Bitwise what model_train_steps gives for each member alone, with that member's descriptor,
     learning rate and ham_diag row, under the backward variant the sweep chose.
     """
-    lib = load()
-    n_steps = len(bounds) - 1
-    if n_steps <= 0:
-        return rows
-    if branch.dim() != 3:
-        raise QheaError("model_sweep_train_steps: branch must be [n_models, rows, branch_in]")
-    R, N = branch.shape[0], branch.shape[1]
-    if len(members) != R:
-        raise QheaError(f"model_sweep_train_steps: {len(members)} member records for {R} members")
-    _dev_f64(branch, 'branch', (R, N, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (R, N, desc.trunk_in))
-    _dev_f64(y, 'y')
-    if tuple(y.shape) not in ((R, N), (R, N, 1)):
-        raise QheaError(f"y has shape {tuple(y.shape)}, expected ({R}, {N})")
-    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-        _dev_f64(t, nm)
-    P = params.shape[-1] if params.dim() == 2 else -1
-    if params.dim() != 2 or params.shape[0] != R or tuple(exp_avg.shape) != (R, P) or tuple(exp_avg_sq.shape) != (R, P):
-        raise QheaError("model_sweep_train_steps: params / exp_avg / exp_avg_sq must be [n_models, P]")
-    if rows.dim() != 3 or rows.shape[0] != R or rows.shape[1] != n_steps or rows.shape[2] < P + 2:
-        raise QheaError("model_sweep_train_steps: rows must be [n_models, n_steps, >= P+2]")
-    if bounds[0] < 0 or bounds[-1] != N or len(global_batches) != n_steps:
-        raise QheaError("model_sweep_train_steps: row bounds do not match the arrays")
-    _dev_f64(ham_diag, 'ham_diag', (R, 1 << desc.n_qubits))
-    with torch.cuda.device(branch.device):
-        nbytes = max(model_sweep_workspace_bytes(desc, R, bounds[i + 1] - bounds[i]) for i in range(n_steps))
-    ws = _workspace(branch.device, nbytes)
-    mh = (MemberHParams * R)(*members)
-    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
-    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_sweep_train_steps(ctypes.byref(desc), R, mh, _ptr(ham_diag), n_steps, rb, _ptr(branch), _ptr(trunk),
-                                              _ptr(y), _ptr(params), ib, _ptr(rows), int(rows.stride(1)), _ptr(exp_avg),
-                                              _ptr(exp_avg_sq), int(first_step), float(beta1), float(beta2), float(eps),
-                                              float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
-    _check(rc, 'qhea_model_sweep_train_steps')
-    return rows
-
-
-def _desc_array(descs):
-    descs = list(descs)
-    return (ModelDesc * max(1, len(descs)))(*descs), len(descs)
+    return _member_train_steps('model_sweep_train_steps', [desc], members, None,
+                               lambda R, b: model_sweep_workspace_bytes(desc, R, b), None, _same_qubits,
+                               bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                               beta1, beta2, eps, weight_decay, ham_diag)
 
 
 def model_depth_sweep_workspace_bytes(descs, batch):
@@ -633,48 +646,11 @@ def model_depth_sweep_train_steps(descs, members, bounds, global_batches, branch
     gradients, then sse and sum y^2.  Member m gets bitwise what model_train_steps gives for it alone under the packed backward
     variant (n <= 9).
     """
-    lib = load()
-    n_steps = len(bounds) - 1
-    if n_steps <= 0:
-        return rows
-    if branch.dim() != 3:
-        raise QheaError("model_depth_sweep_train_steps: branch must be [n_models, rows, branch_in]")
-    R, N = branch.shape[0], branch.shape[1]
-    if len(members) != R or len(descs) != R:
-        raise QheaError(f"model_depth_sweep_train_steps: {len(descs)} descriptors / {len(members)} member records for {R} members")
-    d0 = descs[0]
-    _dev_f64(branch, 'branch', (R, N, d0.branch_in))
-    if d0.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (R, N, d0.trunk_in))
-    _dev_f64(y, 'y')
-    if tuple(y.shape) not in ((R, N), (R, N, 1)):
-        raise QheaError(f"y has shape {tuple(y.shape)}, expected ({R}, {N})")
-    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-        _dev_f64(t, nm)
-    P = depth_sweep_pmax(descs)
-    if tuple(params.shape) != (R, P) or tuple(exp_avg.shape) != (R, P) or tuple(exp_avg_sq.shape) != (R, P):
-        raise QheaError(f"model_depth_sweep_train_steps: params / exp_avg / exp_avg_sq must be [n_models, Pmax = {P}]")
-    if rows.dim() != 3 or rows.shape[0] != R or rows.shape[1] != n_steps or rows.shape[2] < P + 2:
-        raise QheaError("model_depth_sweep_train_steps: rows must be [n_models, n_steps, >= Pmax+2]")
-    if bounds[0] < 0 or bounds[-1] != N or len(global_batches) != n_steps:
-        raise QheaError("model_depth_sweep_train_steps: row bounds do not match the arrays")
-    _dev_f64(ham_diag, 'ham_diag', (R, 1 << d0.n_qubits))
-    with torch.cuda.device(branch.device):
-        nbytes = max(model_depth_sweep_workspace_bytes(descs, bounds[i + 1] - bounds[i]) for i in range(n_steps))
-    if nbytes == 0:
-        raise QheaError("model_depth_sweep_train_steps: the descriptors differ in more than their depths")
-    ws = _workspace(branch.device, nbytes)
-    arr, _ = _desc_array(descs)
-    mh = (MemberHParams * R)(*members)
-    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
-    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_depth_sweep_train_steps(arr, R, mh, _ptr(ham_diag), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
-                                                    _ptr(params), ib, _ptr(rows), int(rows.stride(1)), _ptr(exp_avg),
-                                                    _ptr(exp_avg_sq), int(first_step), float(beta1), float(beta2), float(eps),
-                                                    float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
-    _check(rc, 'qhea_model_depth_sweep_train_steps')
-    return rows
+    return _member_train_steps('model_depth_sweep_train_steps', descs, members, None,
+                               lambda R, b: model_depth_sweep_workspace_bytes(descs, b),
+                               "the descriptors differ in more than their depths", _same_qubits,
+                               bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                               beta1, beta2, eps, weight_decay, ham_diag)
 
 
 def model_qubit_sweep_workspace_bytes(descs, batch):
@@ -696,48 +672,12 @@ def model_qubit_sweep_train_steps(descs, members, bounds, global_batches, branch
     exp_avg_sq: [R, Pmax]; rows: [R, n_steps, >= Pmax + 2]; ham_diag: [R, 2^nmax], member m's spectrum in the first 2^n_m entries
     of its row.  Member m gets bitwise what model_train_steps gives for it alone under the packed backward variant.
     """
-    lib = load()
-    n_steps = len(bounds) - 1
-    if n_steps <= 0:
-        return rows
-    if branch.dim() != 3:
-        raise QheaError("model_qubit_sweep_train_steps: branch must be [n_models, rows, branch_in]")
-    R, N = branch.shape[0], branch.shape[1]
-    if len(members) != R or len(descs) != R:
-        raise QheaError(f"model_qubit_sweep_train_steps: {len(descs)} descriptors / {len(members)} member records for {R} members")
-    d0 = descs[0]
-    _dev_f64(branch, 'branch', (R, N, d0.branch_in))
-    if d0.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (R, N, d0.trunk_in))
-    _dev_f64(y, 'y')
-    if tuple(y.shape) not in ((R, N), (R, N, 1)):
-        raise QheaError(f"y has shape {tuple(y.shape)}, expected ({R}, {N})")
-    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-        _dev_f64(t, nm)
-    P = qubit_sweep_pmax(descs)
-    if tuple(params.shape) != (R, P) or tuple(exp_avg.shape) != (R, P) or tuple(exp_avg_sq.shape) != (R, P):
-        raise QheaError(f"model_qubit_sweep_train_steps: params / exp_avg / exp_avg_sq must be [n_models, Pmax = {P}]")
-    if rows.dim() != 3 or rows.shape[0] != R or rows.shape[1] != n_steps or rows.shape[2] < P + 2:
-        raise QheaError("model_qubit_sweep_train_steps: rows must be [n_models, n_steps, >= Pmax+2]")
-    if bounds[0] < 0 or bounds[-1] != N or len(global_batches) != n_steps:
-        raise QheaError("model_qubit_sweep_train_steps: row bounds do not match the arrays")
-    _dev_f64(ham_diag, 'ham_diag', (R, 1 << max(d.n_qubits for d in descs)))
-    with torch.cuda.device(branch.device):
-        nbytes = model_qubit_sweep_workspace_bytes(descs, max(bounds[i + 1] - bounds[i] for i in range(n_steps)))
-    if nbytes == 0:
-        raise QheaError("model_qubit_sweep_train_steps: the descriptors differ in more than their qubit counts and depths")
-    ws = _workspace(branch.device, nbytes)
-    arr, _ = _desc_array(descs)
-    mh = (MemberHParams * R)(*members)
-    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
-    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_qubit_sweep_train_steps(arr, R, mh, _ptr(ham_diag), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
-                                                    _ptr(params), ib, _ptr(rows), int(rows.stride(1)), _ptr(exp_avg),
-                                                    _ptr(exp_avg_sq), int(first_step), float(beta1), float(beta2), float(eps),
-                                                    float(weight_decay), _ptr(ws), ws.numel(), _stream(branch.device))
-    _check(rc, 'qhea_model_qubit_sweep_train_steps')
-    return rows
+    return _member_train_steps('model_qubit_sweep_train_steps', descs, members, None,
+                               lambda R, b: model_qubit_sweep_workspace_bytes(descs, b),
+                               "the descriptors differ in more than their qubit counts and depths",
+                               lambda ds: max(d.n_qubits for d in ds),
+                               bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                               beta1, beta2, eps, weight_decay, ham_diag)
 
 
 class Unsupported(QheaError):
@@ -754,26 +694,11 @@ def model_dp_train_steps(desc, bounds, global_batches, branch, trunk, y, params,
     for an empty shard or a reduce grid that would not be resident at once.
     """
     lib = load()
-    n_steps = len(bounds) - 1
-    if n_steps <= 0:
+    if len(bounds) - 1 <= 0:
         return rows
-    N = branch.shape[0]
-    _dev_f64(branch, 'branch', (N, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (N, desc.trunk_in))
-    _dev_f64(y, 'y')
-    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-        _dev_f64(t, nm)
-    P = params.numel()
-    if y.numel() != N or bounds[-1] > N or len(global_batches) != n_steps:
-        raise QheaError("model_dp_train_steps: row bounds do not match the arrays")
-    if rows.dim() != 2 or rows.shape[0] < n_steps or rows.shape[1] < P + 2 or exp_avg.numel() != P or exp_avg_sq.numel() != P:
-        raise QheaError("model_dp_train_steps: flat vectors have inconsistent lengths")
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
-    biggest = max(bounds[i + 1] - bounds[i] for i in range(n_steps))
+    n_steps, rb, ib, biggest = _flat_train_schedule('model_dp_train_steps', desc, bounds, global_batches, branch, trunk, y, params,
+                                                    rows, exp_avg, exp_avg_sq, ham_diag)
     ws = _model_ws(desc, biggest, branch.device)
-    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
-    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
     arr = (ctypes.c_void_p * world)(*buffers)
     with torch.cuda.device(branch.device):
         rc = lib.qhea_model_dp_train_steps(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
@@ -903,26 +828,11 @@ def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y
     and applies Adam update first_step + i.  Bitwise a loop of model_loss_grad_noisy_exact + adam_step.
     """
     lib = load()
-    n_steps = len(bounds) - 1
-    if n_steps <= 0:
+    if len(bounds) - 1 <= 0:
         return rows
-    N = branch.shape[0]
-    _dev_f64(branch, 'branch', (N, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (N, desc.trunk_in))
-    _dev_f64(y, 'y')
-    for t, nm in ((params, 'params'), (rows, 'rows'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-        _dev_f64(t, nm)
-    P = params.numel()
-    if y.numel() != N or bounds[-1] > N or len(global_batches) != n_steps:
-        raise QheaError("model_train_steps_noisy_exact: row bounds do not match the arrays")
-    if rows.dim() != 2 or rows.shape[0] < n_steps or rows.shape[1] < P + 2 or exp_avg.numel() != P or exp_avg_sq.numel() != P:
-        raise QheaError("model_train_steps_noisy_exact: flat vectors have inconsistent lengths")
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
-    biggest = max(bounds[i + 1] - bounds[i] for i in range(n_steps))
+    n_steps, rb, ib, biggest = _flat_train_schedule('model_train_steps_noisy_exact', desc, bounds, global_batches, branch, trunk, y, params,
+                                                    rows, exp_avg, exp_avg_sq, ham_diag)
     ws = _noisy_grad_ws(lib, desc, biggest, branch.device)
-    rb = (ctypes.c_int64 * (n_steps + 1))(*[int(b) for b in bounds])
-    ib = (ctypes.c_double * n_steps)(*[1.0 / float(g) for g in global_batches])
     with torch.cuda.device(branch.device):
         rc = lib.qhea_model_train_steps_noisy_exact(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
                                                     _ptr(params), _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows),

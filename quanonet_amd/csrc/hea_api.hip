@@ -13,6 +13,7 @@
 #include "hea_dp.hpp"
 #include "hea_qsweep.hpp"
 #include "hea_noise.hpp"
+#include "hea_train.hpp"
 
 namespace qhea {
 
@@ -1303,10 +1304,6 @@ struct ModelInfo {
     long P = 0, off_ans = 0, off_bias = -1, off_w[2] = {-1, -1}, off_b[2] = {-1, -1};
 };
 
-inline bool pauli_ok(int pauli, const double* ham_diag) {       // a diagonal Hamiltonian is a Z-basis object
-    return pauli == QHEA_PAULI_Z || ((pauli == QHEA_PAULI_X || pauli == QHEA_PAULI_Y) && !ham_diag);
-}
-
 int model_info(const qhea_model_desc* d, ModelInfo& mi) {
     if (!d) return QHEA_EINVAL;
     if (d->ham_pauli < QHEA_PAULI_Z || d->ham_pauli > QHEA_PAULI_Y) return QHEA_EINVAL;
@@ -1357,6 +1354,33 @@ int model_info(const qhea_model_desc* d, ModelInfo& mi) {
     mi.off_ans = p; p += mi.sh.blk * 3 * n;
     mi.P = p;
     return QHEA_OK;
+}
+
+GradMap grad_map(const ModelInfo& mi) {
+    GradMap gm{};
+    gm.off_ans = mi.off_ans; gm.off_bias = mi.off_bias; gm.off_sse = mi.P;
+    for (int s = 0; s < 2; ++s) { gm.off_w[s] = mi.off_w[s]; gm.off_b[s] = mi.off_b[s]; }
+    return gm;
+}
+
+// the run table of the depth and qubit sweeps: two runs of fixed (enc = n, ld); the counts are the members'
+Runs two_runs(int n, int ld0, int ld1) {
+    Runs r{};
+    r.nruns = 2;
+    r.enc[0] = r.enc[1] = n;
+    r.ld[0] = ld0; r.ld[1] = ld1;
+    return r;
+}
+
+// reduce blocks of a model of blk sub-layers and E encoding columns by role (reduce_model_kernel): ansatz blocks, frequency
+// blocks, and the sse / bias block
+struct RedBlocks {
+    int nb_w, nb_x;
+    int total() const { return nb_w + nb_x + 1; }
+};
+RedBlocks red_blocks(int n, long blk, long E, bool trainable) {
+    const int kw = padded_3n(n);
+    return RedBlocks{(int)((blk * kw + red_cols(kw) - 1) / red_cols(kw)), trainable ? (int)((E + kFreqCols - 1) / kFreqCols) : 0};
 }
 
 struct ModelLayout { Layout L; size_t off_gx, off_pred, total; };
@@ -1480,6 +1504,21 @@ __global__ __launch_bounds__(kMemberFill) void member_fill_kernel(F f, int count
     if constexpr (std::is_base_of<MemberFillDepth, F>::value) { r.depth[0] = f.depth[i][0]; r.depth[1] = f.depth[i][1]; }
     if constexpr (std::is_same<F, MemberFillQubit>::value) r.nq = f.nq[i];
     *reinterpret_cast<MemberRec*>(slice0 + (long)i * slice_bytes + kMemberRecOffset) = r;
+}
+// The fill launches of members 0 .. n_models - 1 (slices of `slice` bytes from ws on; member m's diagonal Hamiltonian is
+// diag0 + m * diag_stride, diag0 == nullptr: none): fill(f, i, m) sets element i of a launch's F from member m
+template <class F, class Fill>
+int fill_member_recs(int64_t n_models, char* ws, size_t slice, const double* diag0, int64_t diag_stride, hipStream_t st,
+                     Fill fill) {
+    for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
+        const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
+        F f{};
+        for (int i = 0; i < cnt; ++i) fill(f, i, m0 + i);
+        hipLaunchKernelGGL(member_fill_kernel<F>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
+                           diag0 ? diag0 + m0 * diag_stride : nullptr, (long)diag_stride);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    }
+    return QHEA_OK;
 }
 // Qubit sweeps: the work lists (hea_qsweep.hpp: QsWork) reach the slices' list regions the same way, kWorkFill entries per launch
 constexpr int kWorkFill = 256;                  // 2 KB of kernel arguments
@@ -1750,19 +1789,20 @@ static int model_fuse_blocks(const ModelInfo& mi, const Layout& L) {
 static bool model_fuse_eligible(const ModelInfo& mi, const Layout& L) { return model_fuse_blocks(mi, L) != 0; }
 
 // reduce launch of the model-level calls: FUSE = also writes the next step's records, dpx = exchanges with the peer ranks
-static int launch_reduce_model(int nblocks, hipStream_t st, const ModelInfo& mi, int kw, long nwaves, const double* partial,
-                               const double* params, int64_t batch, const EncDesc& enc, const double* gx, const double* pr,
-                               const double* y, double inv_bt, const GradMap& gm, int nb_w, int nb_x, double* grad,
+static int launch_reduce_model(const RedBlocks& rb, hipStream_t st, const ModelInfo& mi, long nwaves, const double* partial,
+                               const double* params, const StepView& v, const EncDesc& enc, const double* gx, const double* pr,
                                const AdamArgs& adam, const char* ws, const double* gmap, const FusePrep& fp, const DpX* dpx,
                                int R = 1, const MemberStride& ms = MemberStride{}, const MemberLr* mlr = nullptr) {
     const DpX none{};
     const DpX& dx = dpx ? *dpx : none;
-    const dim3 g((unsigned)nblocks, (unsigned)R), b(kRedThreads);
+    const dim3 g((unsigned)rb.total(), (unsigned)R), b(kRedThreads);
     const WorkspaceHeader* hdr = reinterpret_cast<const WorkspaceHeader*>(ws);
     const MemberLr ml = mlr ? *mlr : MemberLr{};
+    const GradMap gm = grad_map(mi);
 #define QHEA_LAUNCH_REDUCE(F, D, M)                                                                                       \
-    hipLaunchKernelGGL((reduce_model_kernel<F, D, M>), g, b, 0, st, mi.n, (int)mi.sh.blk, kw, nwaves, partial, params + mi.off_ans, \
-                       (long)batch, (int)mi.sh.E, enc, gx, pr, y, inv_bt, gm, nb_w, nb_x, grad, adam, hdr, gmap, fp, dx, ms, ml)
+    hipLaunchKernelGGL((reduce_model_kernel<F, D, M>), g, b, 0, st, mi.n, (int)mi.sh.blk, padded_3n(mi.n), nwaves, partial, \
+                       params + mi.off_ans, (long)v.nb, (int)mi.sh.E, enc, gx, pr, v.y, v.inv_bt, gm, rb.nb_w, rb.nb_x, v.grad, \
+                       adam, hdr, gmap, fp, dx, ms, ml)
     if (mlr) { if (fp.ld != 0) QHEA_LAUNCH_REDUCE(true, false, true); else QHEA_LAUNCH_REDUCE(false, false, true); }
     else if (fp.ld != 0) { if (dpx) QHEA_LAUNCH_REDUCE(true, true, false); else QHEA_LAUNCH_REDUCE(true, false, false); }
     else                 { if (dpx) QHEA_LAUNCH_REDUCE(false, true, false); else QHEA_LAUNCH_REDUCE(false, false, false); }
@@ -1776,9 +1816,9 @@ static int launch_reduce_model(int nblocks, hipStream_t st, const ModelInfo& mi,
 static_assert(kDpBlockValues >= 64 && kDpBlockValues >= 2 * kFreqCols, "dpx_exchange_block's LDS arrays");
 static bool dp_blocks_ok(int nblocks) { return nblocks <= kDpMaxBlocks && nblocks <= simd_count() / 4; }      // (all resident: blocks wait for their peers)
 
-static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk,
-                                const double* y, const double* params, const double* ham_diag, double inv_batch_total,
-                                double* grad, double* pred, void* workspace, size_t workspace_bytes, void* stream,
+// One step (v: its rows, gradient row and residual weight) of the model-level calls.
+static int model_loss_grad_impl(const qhea_model_desc* desc, const StepView& v, const double* params, const double* ham_diag,
+                                double* pred, void* workspace, size_t workspace_bytes, void* stream,
                                 const AdamArgs& adam, bool records_ready = false, bool records_for_next = false,
                                 const DpX* dpx = nullptr, int R = 1, const MemberStride& ms = MemberStride{},
                                 const MemberLr* mlr = nullptr) {
@@ -1790,27 +1830,23 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
     ModelInfo mi;
     int rc = model_info(desc, mi);
     if (rc != QHEA_OK) return rc;
-    if (batch < 0 || !grad || !pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
+    const int64_t batch = v.nb;
+    if (batch < 0 || !v.grad || !pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (batch == 0) {
         if (dpx) return QHEA_EUNSUPPORTED;                      // (an empty shard still owes the peers its zeros: caller's path)
-        return hipMemsetAsync(grad, 0, sizeof(double) * (mi.P + 2), st) == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+        return hipMemsetAsync(v.grad, 0, sizeof(double) * (mi.P + 2), st) == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
     }
-    if (!branch || !params || !y || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
+    if (!v.branch || !params || !v.y || (desc->model == QHEA_MODEL_QUANONET && !v.trunk)) return QHEA_EINVAL;
     if (R > 1 && !mlr) return QHEA_EINVAL;                      // (the member kernels read every member's MemberRec)
     const ModelLayout M = make_model_layout(mi, batch, R * batch);
     if (!workspace || workspace_bytes < M.total) return QHEA_EWORKSPACE;
     char* ws = static_cast<char*>(workspace);
-    const EncDesc enc = make_enc(desc, mi, branch, trunk, params);
+    const EncDesc enc = make_enc(desc, mi, v.branch, v.trunk, params);
     double* gx = reinterpret_cast<double*>(ws + M.off_gx);
     double* pr = pred ? pred : reinterpret_cast<double*>(ws + M.off_pred);
     double* partial = reinterpret_cast<double*>(ws + M.L.off_part);
-    GradMap gm{};
-    gm.off_ans = mi.off_ans; gm.off_bias = mi.off_bias; gm.off_sse = mi.P;
-    for (int s = 0; s < 2; ++s) { gm.off_w[s] = mi.off_w[s]; gm.off_b[s] = mi.off_b[s]; }
-    const int kw = padded_3n(mi.n);
-    int nb_w = (int)((mi.sh.blk * kw + red_cols(kw) - 1) / red_cols(kw));
-    const int nb_x = mi.trainable ? (int)((mi.sh.E + kFreqCols - 1) / kFreqCols) : 0;
+    RedBlocks rb = red_blocks(mi.n, mi.sh.blk, mi.sh.E, mi.trainable);
     FusePrep fp{};
     if (M.L.ztri || M.L.zpacked) {
         if (records_for_next) {
@@ -1820,34 +1856,33 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
             fp.L = M.L.zL; fp.runs = mi.sh.runs;
             fp.rec = ws + M.L.off_rec; fp.srec = M.L.zsplit ? ws + M.L.off_srec : nullptr;
             fp.gmap = reinterpret_cast<double*>(ws + M.L.off_gmap);
-            nb_w = (int)(mi.sh.blk / fp.ld / fp.nbk);          // one reduce block per circuit block (n = 2, ld = 1: per two)
+            rb.nb_w = (int)(mi.sh.blk / fp.ld / fp.nbk);        // one reduce block per circuit block (n = 2, ld = 1: per two)
         }
-        if (dpx && !dp_blocks_ok(nb_w + nb_x + 1)) return QHEA_EUNSUPPORTED;
+        if (dpx && !dp_blocks_ok(rb.total())) return QHEA_EUNSUPPORTED;
         if (!records_ready) {
             rc = launch_prep_zyz(mi.n, mi.sh, params + mi.off_ans, ws, M.L, st, R, ms);
             if (rc != QHEA_OK) return rc;
         }
         profile_begin(st);
         rc = launch_zyz_backward(mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
-                                 desc->ham_pauli, nullptr, nullptr, y, mi.has_bias ? params + mi.off_bias : nullptr,
-                                 inv_batch_total, pr, gx, partial, st, R, ms, mlr ? mlr->mrec : nullptr);
+                                 desc->ham_pauli, nullptr, nullptr, v.y, mi.has_bias ? params + mi.off_bias : nullptr,
+                                 v.inv_bt, pr, gx, partial, st, R, ms, mlr ? mlr->mrec : nullptr);
         profile_end(st);
         if (rc != QHEA_OK) return rc;
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        return launch_reduce_model(nb_w + nb_x + 1, st, mi, kw, M.L.nwaves, partial, params, batch, enc, gx, pr, y,
-                                   inv_batch_total, gm, nb_w, nb_x, grad, adam, ws,
+        return launch_reduce_model(rb, st, mi, M.L.nwaves, partial, params, v, enc, gx, pr, adam, ws,
                                    reinterpret_cast<const double*>(ws + M.L.off_gmap), fp, dpx, R, ms, mlr);
     }
     if (R != 1) return QHEA_EUNSUPPORTED;                       // (the ensemble entry point never asks: R-sequential calls there)
     if (records_ready || records_for_next) return QHEA_EINVAL;
-    if (dpx && !dp_blocks_ok(nb_w + nb_x + 1)) return QHEA_EUNSUPPORTED;
+    if (dpx && !dp_blocks_ok(rb.total())) return QHEA_EUNSUPPORTED;
     rc = launch_prep_model(mi, batch, params, enc, ws, M.L, st);
     if (rc != QHEA_OK) return rc;
     const dim3 grid((unsigned)(M.L.nwaves / kWaves));
     const BwdArgs ba{mi.sh.runs, (long)batch, (int)mi.sh.E, (int)mi.sh.blk,
                      reinterpret_cast<const double2*>(ws + M.L.off_cs), ws + M.L.off_U,
                      (int)((mi.sh.blk + 2) * mi.n * kGateBytes), desc->ham_offset, desc->ham_coeff, ham_diag,
-                     nullptr, nullptr, y, mi.has_bias ? params + mi.off_bias : nullptr, inv_batch_total,
+                     nullptr, nullptr, v.y, mi.has_bias ? params + mi.off_bias : nullptr, v.inv_bt,
                      pr, gx, partial, desc->ham_pauli, use_tri(), M.L.nwaves > simd_count() ? 1 : 0,
                      &reinterpret_cast<WorkspaceHeader*>(ws)->status};
     profile_begin(st);
@@ -1861,8 +1896,37 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, int64_t batch, cons
     }
     profile_end(st);
     if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    return launch_reduce_model(nb_w + nb_x + 1, st, mi, kw, M.L.nwaves, partial, params, batch, enc, gx, pr, y, inv_batch_total,
-                               gm, nb_w, nb_x, grad, adam, ws, nullptr, FusePrep{}, dpx);
+    return launch_reduce_model(rb, st, mi, M.L.nwaves, partial, params, v, enc, gx, pr, adam, ws, nullptr, FusePrep{}, dpx);
+}
+
+// The steps of qhea_model_train_steps and of qhea_model_dp_train_steps (dx: its exchange, step i's number first_seq + i); the
+// arguments have been checked.
+// Between two steps of equal batch size (same workspace layout) on a block-unrolled shape the first one's reduce kernel
+// writes the second one's layer records: nobody else can touch the parameters in between, so the prep launch is dropped.
+static int model_steps(const qhea_model_desc* desc, const ModelInfo& mi, const double* ham_diag, double lr, const TrainCall& c,
+                       DpX* dx = nullptr, int64_t first_seq = 0) {
+    bool ready = false;
+    for (int64_t i = 0; i < c.n_steps; ++i) {
+        const StepView v = step_view(c, i, *desc);
+        bool next = false;
+        if (i + 1 < c.n_steps && c.row_begin[i + 2] - c.row_begin[i + 1] == v.nb)
+            next = model_fuse_eligible(mi, make_model_layout(mi, v.nb).L);
+        if (dx) dx->seq = (unsigned long long)(first_seq + i);
+        const int rc = model_loss_grad_impl(desc, v, c.params, ham_diag, nullptr, c.workspace, c.workspace_bytes, c.stream,
+                                            adam_step(c, i, lr).adam, ready, next, dx);
+        if (rc != QHEA_OK) return rc;
+        ready = next;
+    }
+    return QHEA_OK;
+}
+
+// the optimizer state of a one-step call (qhea_model_train_step, qhea_adam_step) as a call record: step 0 is Adam step `step`
+static TrainCall optimizer_call(double* params, double* exp_avg, double* exp_avg_sq, int64_t step, double beta1, double beta2,
+                                double eps, double weight_decay) {
+    TrainCall c{};
+    c.params = params; c.exp_avg = exp_avg; c.exp_avg_sq = exp_avg_sq; c.first_step = step;
+    c.beta1 = beta1; c.beta2 = beta2; c.eps = eps; c.weight_decay = weight_decay;
+    return c;
 }
 
 int qhea_model_forward(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk,
@@ -1880,8 +1944,7 @@ int qhea_model_forward_chunks(const qhea_model_desc* desc, int64_t n_chunks, con
     if (rc0 != QHEA_OK) return rc0;
     const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
     if (has_trunk && !trunk) return QHEA_EINVAL;
-    for (int64_t i = 0; i < n_chunks; ++i)
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
+    if (schedule_max_batch(n_chunks, row_begin) < 0) return QHEA_EINVAL;
     // the layer records depend on the parameters alone: one prep launch serves every chunk whose workspace layout keeps
     // them where the last prep put them (chunks of equal size; a shorter last chunk gets its own)
     Layout last{};
@@ -1903,8 +1966,8 @@ int qhea_model_forward_chunks(const qhea_model_desc* desc, int64_t n_chunks, con
 int qhea_model_loss_grad(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk,
                          const double* y, const double* params, const double* ham_diag, double inv_batch_total,
                          double* grad, double* pred, void* workspace, size_t workspace_bytes, void* stream) {
-    return model_loss_grad_impl(desc, batch, branch, trunk, y, params, ham_diag, inv_batch_total, grad, pred, workspace,
-                                workspace_bytes, stream, AdamArgs{});
+    return model_loss_grad_impl(desc, StepView{0, batch, branch, trunk, y, grad, inv_batch_total}, params, ham_diag, pred,
+                                workspace, workspace_bytes, stream, AdamArgs{});
 }
 
 int qhea_model_train_step(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk,
@@ -1913,10 +1976,9 @@ int qhea_model_train_step(const qhea_model_desc* desc, int64_t batch, const doub
                           double beta1, double beta2, double eps, double weight_decay, void* workspace,
                           size_t workspace_bytes, void* stream) {
     if (step < 1 || !params || !exp_avg || !exp_avg_sq || batch <= 0) return QHEA_EINVAL;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-    return model_loss_grad_impl(desc, batch, branch, trunk, y, params, ham_diag, inv_batch_total, grad, pred, workspace,
-                                workspace_bytes, stream, adam);
+    const TrainCall opt = optimizer_call(params, exp_avg, exp_avg_sq, step, beta1, beta2, eps, weight_decay);
+    return model_loss_grad_impl(desc, StepView{0, batch, branch, trunk, y, grad, inv_batch_total}, params, ham_diag, pred,
+                                workspace, workspace_bytes, stream, adam_step(opt, 0, lr).adam);
 }
 
 int qhea_model_train_steps(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
@@ -1930,31 +1992,10 @@ int qhea_model_train_steps(const qhea_model_desc* desc, int64_t n_steps, const i
     ModelInfo mi;
     const int rc0 = model_info(desc, mi);
     if (rc0 != QHEA_OK) return rc0;
-    if (grad_stride < qhea_model_param_count(desc) + 2) return QHEA_EINVAL;
-    for (int64_t i = 0; i < n_steps; ++i)
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
-    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
-    if (has_trunk && !trunk) return QHEA_EINVAL;
-    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    // Between two steps of equal batch size (same workspace layout) on a block-unrolled shape the first one's reduce kernel
-    // writes the second one's layer records: nobody else can touch the parameters in between, so the prep launch is dropped.
-    bool ready = false;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
-        bool next = false;
-        if (i + 1 < n_steps && row_begin[i + 2] - row_begin[i + 1] == nb)
-            next = model_fuse_eligible(mi, make_model_layout(mi, nb).L);
-        const int64_t step = first_step + i;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-        const int rc = model_loss_grad_impl(desc, nb, branch + r0 * desc->branch_in,
-                                            has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, ham_diag,
-                                            inv_batch_total[i], grad + i * grad_stride, nullptr, workspace, workspace_bytes,
-                                            stream, adam, ready, next);
-        if (rc != QHEA_OK) return rc;
-        ready = next;
-    }
-    return QHEA_OK;
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    if (call_max_batch(call, mi.P, *desc) < 0) return QHEA_EINVAL;
+    return model_steps(desc, mi, ham_diag, lr, call);
 }
 
 int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
@@ -1972,8 +2013,7 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
     const int rc0 = model_info(desc, mi);
     if (rc0 != QHEA_OK) return rc0;
     if (grad_stride < mi.P + 2 || dp_values < mi.P + 2) return QHEA_EINVAL;
-    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
-    if (has_trunk && !trunk) return QHEA_EINVAL;
+    if (desc->model == QHEA_MODEL_QUANONET && !trunk) return QHEA_EINVAL;
     if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
     DpX dx{};
     for (int r = 0; r < world; ++r) {
@@ -1984,198 +2024,55 @@ int qhea_model_dp_train_steps(const qhea_model_desc* desc, int64_t n_steps, cons
     dx.timeout_ticks = (long long)(timeout_ms * 1e5);           // wall_clock64: 100 MHz
     // every step must be launchable BEFORE the first one is (a rank that stops half-way would leave its peers waiting):
     // no empty shard, and a reduce grid that fits the device and the exchange buffers' block flags
+    // (its own schedule rule: an empty shard is well-formed, and refused as unsupported)
     for (int64_t i = 0; i < n_steps; ++i) {
         if (row_begin[i] < 0 || row_begin[i + 1] < row_begin[i]) return QHEA_EINVAL;
         if (row_begin[i + 1] == row_begin[i]) return QHEA_EUNSUPPORTED;
     }
-    {
-        const int kw = padded_3n(mi.n);
-        const int nb_x = mi.trainable ? (int)((mi.sh.E + kFreqCols - 1) / kFreqCols) : 0;
-        const int nb_w = (int)((mi.sh.blk * kw + red_cols(kw) - 1) / red_cols(kw));     // (the fused reduce uses fewer)
-        if (!dp_blocks_ok(nb_w + nb_x + 1)) return QHEA_EUNSUPPORTED;
-    }
-    bool ready = false;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
-        bool next = false;
-        if (i + 1 < n_steps && row_begin[i + 2] - row_begin[i + 1] == nb)
-            next = model_fuse_eligible(mi, make_model_layout(mi, nb).L);
-        const int64_t step = first_step + i;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-        dx.seq = (unsigned long long)(first_seq + i);
-        const int rc = model_loss_grad_impl(desc, nb, branch + r0 * desc->branch_in,
-                                            has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, ham_diag,
-                                            inv_batch_total[i], grad + i * grad_stride, nullptr, workspace, workspace_bytes,
-                                            stream, adam, ready, next, &dx);
-        if (rc != QHEA_OK) return rc;
-        ready = next;
-    }
-    return QHEA_OK;
+    if (!dp_blocks_ok(red_blocks(mi.n, mi.sh.blk, mi.sh.E, mi.trainable).total())) return QHEA_EUNSUPPORTED;   // (the fused reduce uses fewer)
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    return model_steps(desc, mi, ham_diag, lr, call, &dx, first_seq);
 }
 
-// qhea_model_ensemble_train_steps and qhea_model_sweep_train_steps: R members of one shape, member m with hyper-parameters hp(m)
-// (hp_fn(ctx, m)) and diagonal Hamiltonian diag0 + m * diag_stride (diag0 == nullptr: none).  The arguments have been checked by the caller.
-typedef qhea_member_hparams (*MemberHp)(const void* ctx, int64_t m);
-static int members_lds_grid(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models, MemberHp hp_fn, const void* ctx,
-                            const double* diag0, int64_t diag_stride, int64_t n_steps, const int64_t* row_begin,
-                            const double* branch, const double* trunk, const double* y, double* params,
-                            const double* inv_batch_total, double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
-                            int64_t first_step, double beta1, double beta2, double eps, double weight_decay, char* ws, size_t slice,
-                            hipStream_t st);
-static int members_train_steps(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models, MemberHp hp_fn, const void* ctx,
-                        const double* diag0,
-                        int64_t diag_stride, int64_t n_steps, const int64_t* row_begin, const double* branch, const double* trunk,
-                        const double* y, double* params, const double* inv_batch_total, double* grad, int64_t grad_stride,
-                        double* exp_avg, double* exp_avg_sq, int64_t first_step, double beta1, double beta2, double eps,
-                        double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
-    auto hp = [&](int64_t m) { return hp_fn(ctx, m); };
-    // one slice per member, sized for every batch size of the schedule; one launch per kernel where every step runs the ZYZ
-    // kernels or (n >= 10) the workgroup-resident ones, R consecutive single-model calls otherwise (n = 6..9)
-    size_t slice = 0;
-    bool grid = true;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t nb = row_begin[i + 1] - row_begin[i];
-        const size_t b = ensemble_slice_bytes(mi, n_models, nb);
-        if (b > slice) slice = b;
-        grid = grid && n_models <= 65535 && ensemble_grid(mi, n_models, nb);      // (gridDim.y)
-    }
-    if (!workspace || workspace_bytes / (size_t)n_models < slice) return QHEA_EWORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    const int64_t rows = row_begin[n_steps];                        // rows per member
-    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
-    if (!grid && n_models > 1 && lds_supported(mi.n)) {
-        const int rc = members_lds_grid(desc, mi, n_models, hp_fn, ctx, diag0, diag_stride, n_steps, row_begin, branch, trunk, y,
-                                        params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2,
-                                        eps, weight_decay, ws, slice, st);
-        if (rc != QHEA_EUNSUPPORTED) return rc;                   // (unsupported: found before anything was launched)
-    }
-    if (!grid) {
-        for (int64_t m = 0; m < n_models; ++m) {
-            char* wm = ws + m * slice;
-            const qhea_member_hparams h = hp(m);
-            const qhea_model_desc dm = member_desc(*desc, h);
-            const int rc = qhea_model_train_steps(&dm, n_steps, row_begin, branch + m * rows * desc->branch_in,
-                                                  has_trunk ? trunk + m * rows * desc->trunk_in : nullptr, y + m * rows,
-                                                  params + m * mi.P, diag0 ? diag0 + m * diag_stride : nullptr, inv_batch_total,
-                                                  grad + m * n_steps * grad_stride, grad_stride, exp_avg + m * mi.P,
-                                                  exp_avg_sq + m * mi.P, first_step, h.lr, beta1, beta2, eps, weight_decay, wm,
-                                                  slice, stream);
-            if (rc != QHEA_OK) return rc;
-            if (m > 0) {
-                hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<WorkspaceHeader*>(ws),
-                                   reinterpret_cast<WorkspaceHeader*>(wm));
-                if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-            }
-        }
-        return QHEA_OK;
-    }
-    // One grid: R = 1 runs the single-model kernels on member 0's descriptor; R > 1 the member kernels, which read every
-    // member's read-out, scale and learning rate from its MemberRec.  The launch descriptor only chooses the kernels: a member
-    // that reads out X or Y gives the whole launch the kernels of an X / Y model (the split-layout chains are Z-only).
-    const qhea_member_hparams h0 = hp(0);
+// Ensembles and sweeps whose every step runs the ZYZ kernels (members_train_steps): one grid per kernel and step.  R = 1 runs
+// the single-model kernels on member 0's descriptor; R > 1 the member kernels, which read every member's read-out, scale and
+// learning rate from its MemberRec.  The arguments and the slice size have been checked by the caller.
+static int members_zyz_grid(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models,
+                            const qhea_member_hparams* members, int64_t member_step, const double* diag0, int64_t diag_stride,
+                            size_t slice, const TrainCall& c) {
+    hipStream_t st = c.st();
+    char* ws = c.ws();
+    // The launch descriptor only chooses the kernels: a member that reads out X or Y gives the whole launch the kernels of an
+    // X / Y model (the split-layout chains are Z-only).
+    const qhea_member_hparams& h0 = members[0];
     qhea_model_desc dl = member_desc(*desc, h0);
     if (n_models > 1) {
         for (int64_t m = 0; m < n_models; ++m)
-            if (hp(m).ham_pauli != QHEA_PAULI_Z) dl.ham_pauli = QHEA_PAULI_X;
-        for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
-            const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
-            MemberFill f{};
-            for (int i = 0; i < cnt; ++i) f.h[i] = hp(m0 + i);
-            hipLaunchKernelGGL(member_fill_kernel<MemberFill>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
-                               diag0 ? diag0 + m0 * diag_stride : nullptr, (long)diag_stride);
-            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        }
+            if (members[m * member_step].ham_pauli != QHEA_PAULI_Z) dl.ham_pauli = QHEA_PAULI_X;
+        const int rc = fill_member_recs<MemberFill>(n_models, ws, slice, diag0, diag_stride, st,
+                                                    [&](MemberFill& f, int i, int64_t m) { f.h[i] = members[m * member_step]; });
+        if (rc != QHEA_OK) return rc;
     }
-    const MemberStride ms{(long)rows, (long)mi.P, (long)(n_steps * grad_stride), (long)slice};
+    const MemberStride ms{(long)c.row_begin[c.n_steps] /* rows per member */, (long)mi.P, (long)(c.n_steps * c.grad_stride),
+                          (long)slice};
     bool ready = false;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
+    for (int64_t i = 0; i < c.n_steps; ++i) {
+        const StepView v = step_view(c, i, *desc);
         bool next = false;
-        if (i + 1 < n_steps && row_begin[i + 2] - row_begin[i + 1] == nb)
-            next = model_fuse_eligible(mi, make_model_layout(mi, nb, n_models * nb).L);
-        const int64_t step = first_step + i;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, h0.lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-        const MemberLr mlr{ws + kMemberRecOffset, bc1};
-        const int rc = model_loss_grad_impl(&dl, nb, branch + r0 * desc->branch_in,
-                                            has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, diag0,
-                                            inv_batch_total[i], grad + i * grad_stride, nullptr, ws, slice, stream, adam,
-                                            ready, next, nullptr, (int)n_models, ms, n_models > 1 ? &mlr : nullptr);
+        if (i + 1 < c.n_steps && c.row_begin[i + 2] - c.row_begin[i + 1] == v.nb)
+            next = model_fuse_eligible(mi, make_model_layout(mi, v.nb, n_models * v.nb).L);
+        const AdamStep as = adam_step(c, i, h0.lr);
+        const MemberLr mlr{ws + kMemberRecOffset, as.bc1};
+        const int rc = model_loss_grad_impl(&dl, v, c.params, diag0, nullptr, ws, slice, c.stream, as.adam, ready, next, nullptr,
+                                            (int)n_models, ms, n_models > 1 ? &mlr : nullptr);
         if (rc != QHEA_OK) return rc;
         ready = next;
     }
     return QHEA_OK;
 }
 
-size_t qhea_model_ensemble_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch) {
-    ModelInfo mi;
-    if (model_info(desc, mi) != QHEA_OK || n_models < 1 || batch < 0) return 0;
-    return (size_t)n_models * ensemble_slice_bytes(mi, n_models, batch);
-}
-
-int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_models, int64_t n_steps, const int64_t* row_begin,
-                                    const double* branch, const double* trunk, const double* y, double* params,
-                                    const double* ham_diag, const double* inv_batch_total, double* grad, int64_t grad_stride,
-                                    double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
-                                    double beta2, double eps, double weight_decay, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-    if (!desc || n_models < 1 || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad || first_step < 1)
-        return QHEA_EINVAL;
-    ModelInfo mi;
-    const int rc0 = model_info(desc, mi);
-    if (rc0 != QHEA_OK) return rc0;
-    if (grad_stride < mi.P + 2) return QHEA_EINVAL;
-    if (!pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
-    for (int64_t i = 0; i < n_steps; ++i)
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
-    if (desc->model == QHEA_MODEL_QUANONET && !trunk) return QHEA_EINVAL;
-    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    // a sweep whose members all share the descriptor's read-out and scale and `lr` (one shared ham_diag)
-    const qhea_member_hparams uni{desc->scale_coeff, desc->ham_offset, desc->ham_coeff, lr, desc->ham_pauli, 0};
-    return members_train_steps(desc, mi, n_models, [](const void* c, int64_t) { return *static_cast<const qhea_member_hparams*>(c); },
-                               &uni, ham_diag, 0, n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride,
-                               exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream);
-}
-
-size_t qhea_model_sweep_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch) {
-    return qhea_model_ensemble_workspace_bytes(desc, n_models, batch);      // (the MemberRecs live in the slices' headers)
-}
-
-int qhea_model_sweep_train_steps(const qhea_model_desc* desc, int64_t n_models, const qhea_member_hparams* members,
-                                 const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
-                                 const double* trunk, const double* y, double* params, const double* inv_batch_total,
-                                 double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq, int64_t first_step,
-                                 double beta1, double beta2, double eps, double weight_decay, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    if (!desc || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
-        first_step < 1)
-        return QHEA_EINVAL;
-    for (int64_t m = 0; m < n_models; ++m) {
-        const qhea_member_hparams& h = members[m];
-        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
-        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;               // ham_diag: every member reads out Z
-        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;        // (torch.optim.Adam refuses lr < 0 too)
-    }
-    // the shape (and everything model_info checks) is the descriptor's; its scale and Hamiltonian fields are not used
-    const qhea_model_desc d0 = member_desc(*desc, members[0]);
-    ModelInfo mi;
-    const int rc0 = model_info(&d0, mi);
-    if (rc0 != QHEA_OK) return rc0;
-    if (grad_stride < mi.P + 2) return QHEA_EINVAL;
-    for (int64_t i = 0; i < n_steps; ++i)
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
-    if (desc->model == QHEA_MODEL_QUANONET && !trunk) return QHEA_EINVAL;
-    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    return members_train_steps(&d0, mi, n_models,
-                               [](const void* c, int64_t m) { return static_cast<const qhea_member_hparams*>(c)[m]; }, members,
-                               ham_diag, (int64_t)1 << mi.n, n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad,
-                               grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, workspace,
-                               workspace_bytes, stream);
-}
-
-// ---- depth sweeps (qhea_model_depth_sweep_train_steps) ----
+// ---- depth sweeps (qhea_model_depth_sweep_train_steps), and the member grid of ensembles and sweeps at n >= 10 ----
 // The members' descriptors: every field but the depths (QuanONet net[0] / net[2], HEAQNN net[0]) equal to member 0's, each one
 // valid on its own (its ham_* and scale fields are not used: read with a Z read-out).  env: the descriptor with the largest
 // depths of every run -- its shape bounds every member's E, blk and P, and sizes the slices and the grids.
@@ -2186,6 +2083,29 @@ struct DepthSet {
     int c_max[2] = {0, 0};
     DepthRed dr{};
 };
+// member m's block counts of run 0 / run 1 of the launch's run table: QuanONet trunk (net[2] x net[3]) then branch
+// (net[0] x net[1]); HEAQNN net[0] x net[1] and an empty run
+static void depth_counts(const qhea_model_desc& d, int32_t (&c)[2]) {
+    const bool qn = d.model == QHEA_MODEL_QUANONET;
+    c[0] = qn ? d.net[2] : d.net[0];
+    c[1] = qn ? d.net[0] : 0;
+}
+static DepthRed depth_red(const qhea_model_desc& d) {
+    const bool qn = d.model == QHEA_MODEL_QUANONET;
+    return DepthRed{qn ? 1 : 0, d.trainable_freq != 0 ? 1 : 0, qn ? d.net[3] : d.net[1], qn ? d.net[1] : 0};
+}
+// Member d (mi: its model_info) joins the set: the run lengths, the largest counts and P.  QHEA_EUNSUPPORTED where the member
+// kernels' parameter layout (depth_map) is not the model's.
+static int depth_set_add(DepthSet& ds, const qhea_model_desc& d, const ModelInfo& mi) {
+    int32_t c[2];
+    depth_counts(d, c);
+    ds.dr = depth_red(d);
+    if (depth_map(mi.n, ds.dr.quanonet != 0, mi.trainable, c[0], c[1], ds.dr.ld0, ds.dr.ld1).P != mi.P) return QHEA_EUNSUPPORTED;
+    if (mi.P > ds.pmax) ds.pmax = mi.P;
+    if (c[0] > ds.c_max[0]) ds.c_max[0] = c[0];
+    if (c[1] > ds.c_max[1]) ds.c_max[1] = c[1];
+    return QHEA_OK;
+}
 static int depth_set(const qhea_model_desc* descs, int64_t R, DepthSet& ds) {
     if (!descs || R < 1 || R > 65535) return QHEA_EINVAL;
     const qhea_model_desc& d0 = descs[0];
@@ -2201,26 +2121,13 @@ static int depth_set(const qhea_model_desc* descs, int64_t R, DepthSet& ds) {
         qhea_model_desc dz = d;
         dz.ham_pauli = QHEA_PAULI_Z;
         ModelInfo mi;
-        const int rc = model_info(&dz, mi);
+        int rc = model_info(&dz, mi);
+        if (rc == QHEA_OK) rc = depth_set_add(ds, d, mi);
         if (rc != QHEA_OK) return rc;
-        // run 0 / run 1 of the launch's run table: QuanONet trunk (net[2] x net[3]) then branch (net[0] x net[1]); HEAQNN
-        // net[0] x net[1] and an empty run
-        const int c0 = qn ? d.net[2] : d.net[0], c1 = qn ? d.net[0] : 0;
-        ds.dr = DepthRed{qn ? 1 : 0, d.trainable_freq != 0 ? 1 : 0, qn ? d.net[3] : d.net[1], qn ? d.net[1] : 0};
-        if (depth_map(mi.n, qn, mi.trainable, c0, c1, ds.dr.ld0, ds.dr.ld1).P != mi.P) return QHEA_EUNSUPPORTED;
-        if (mi.P > ds.pmax) ds.pmax = mi.P;
-        if (c0 > ds.c_max[0]) ds.c_max[0] = c0;
-        if (c1 > ds.c_max[1]) ds.c_max[1] = c1;
     }
     if (qn) { ds.env.net[2] = ds.c_max[0]; ds.env.net[0] = ds.c_max[1]; }
     else ds.env.net[0] = ds.c_max[0];
     return model_info(&ds.env, ds.env_mi);
-}
-// member m's block counts of run 0 / run 1
-static void depth_counts(const qhea_model_desc& d, int32_t (&c)[2]) {
-    const bool qn = d.model == QHEA_MODEL_QUANONET;
-    c[0] = qn ? d.net[2] : d.net[0];
-    c[1] = qn ? d.net[0] : 0;
 }
 // One member's slice for `batch` rows (the largest member's shape): header (MemberRec at kMemberRecOffset), gate table, (cos, sin)
 // table, partial rows of the backward kernel, grad_x, predictions -- the first-generation single-model layout under
@@ -2243,69 +2150,60 @@ static size_t depth_slice_bytes(const DepthSet& ds, int64_t batch) { return dept
 
 // One grid per kernel and step for R members of one model kind, n and run lengths whose block counts may differ (ds: their
 // envelope, DepthSet): depth sweeps, and ensembles / sweeps at n >= 10, whose members share one shape.  Member m's block counts
-// are those of descs[m * desc_step] (desc_step 0: one descriptor for all), its hyper-parameters hp_fn(hp_ctx, m), its diagonal
-// Hamiltonian diag0 + m * diag_stride.  n <= 9: the packed backward kernel's member form; n >= 10: the workgroup-resident one's.
-// The arguments and the slice size (>= depth_slice_bytes for every batch of the schedule) have been checked by the caller.
-static int depth_grid_steps(const DepthSet& ds, int64_t n_models, const qhea_model_desc* descs, int64_t desc_step, MemberHp hp_fn,
-                            const void* hp_ctx, const double* diag0, int64_t diag_stride, int64_t n_steps, const int64_t* row_begin,
-                            const double* branch, const double* trunk, const double* y, double* params,
-                            const double* inv_batch_total, double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
-                            int64_t first_step, double beta1, double beta2, double eps, double weight_decay, char* ws, size_t slice,
-                            hipStream_t st) {
+// are those of descs[m * desc_step] (desc_step 0: one descriptor for all), its hyper-parameters members[m * member_step]
+// (member_step 0: one record for all), its diagonal Hamiltonian diag0 + m * diag_stride.  n <= 9: the packed backward kernel's
+// member form; n >= 10: the workgroup-resident one's.  The arguments and the slice size (>= depth_slice_bytes for every batch
+// of the schedule) have been checked by the caller.
+static int depth_grid_steps(const DepthSet& ds, int64_t n_models, const qhea_model_desc* descs, int64_t desc_step,
+                            const qhea_member_hparams* members, int64_t member_step, const double* diag0, int64_t diag_stride,
+                            size_t slice, const TrainCall& c) {
     const ModelInfo& env = ds.env_mi;
     const bool qn = ds.env.model == QHEA_MODEL_QUANONET;
-    const int64_t rows = row_begin[n_steps];                        // rows per member
+    char* ws = c.ws();
+    hipStream_t st = c.st();
     // One grid per kernel and step, member = blockIdx.y: every member's read-out, scale, learning rate and block counts reach
     // its MemberRec first
-    for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
-        const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
-        MemberFillDepth f{};
-        for (int i = 0; i < cnt; ++i) {
-            f.h[i] = hp_fn(hp_ctx, m0 + i);
-            depth_counts(descs[(m0 + i) * desc_step], f.depth[i]);
-        }
-        hipLaunchKernelGGL(member_fill_kernel<MemberFillDepth>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice, (long)slice,
-                           diag0 ? diag0 + m0 * diag_stride : nullptr, (long)diag_stride);
-        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    }
+    const int rc = fill_member_recs<MemberFillDepth>(n_models, ws, slice, diag0, diag_stride, st,
+                                                     [&](MemberFillDepth& f, int i, int64_t m) {
+        f.h[i] = members[m * member_step];
+        depth_counts(descs[m * desc_step], f.depth[i]);
+    });
+    if (rc != QHEA_OK) return rc;
     // the reduce grid: the most blocks any member's roles need (ansatz blocks, frequency blocks, the sse / bias block)
-    const int n = env.n, kw = padded_3n(n);
-    int red_blocks = 0;
+    const int n = env.n;
+    int red_grid = 0;
     for (int64_t m = 0; m < n_models; ++m) {
-        int32_t c[2];
-        depth_counts(descs[m * desc_step], c);
-        const DepthMap d = depth_map(n, qn, ds.dr.trainable != 0, c[0], c[1], ds.dr.ld0, ds.dr.ld1);
-        const int nb = (d.blk * kw + red_cols(kw) - 1) / red_cols(kw) + (ds.dr.trainable ? (d.E + kFreqCols - 1) / kFreqCols : 0) + 1;
-        if (nb > red_blocks) red_blocks = nb;
+        int32_t cnt[2];
+        depth_counts(descs[m * desc_step], cnt);
+        const DepthMap d = depth_map(n, qn, ds.dr.trainable != 0, cnt[0], cnt[1], ds.dr.ld0, ds.dr.ld1);
+        red_grid = std::max(red_grid, red_blocks(n, d.blk, d.E, ds.dr.trainable != 0).total());
     }
-    Runs runs{};                                        // two runs of fixed (enc, ld); the counts are the members'
-    runs.nruns = 2;
-    runs.enc[0] = runs.enc[1] = n;
-    runs.ld[0] = ds.dr.ld0; runs.ld[1] = ds.dr.ld1;
-    const MemberStride ms{(long)rows, (long)ds.pmax, (long)(n_steps * grad_stride), (long)slice};
+    const Runs runs = two_runs(n, ds.dr.ld0, ds.dr.ld1);
+    const MemberStride ms{(long)c.row_begin[c.n_steps] /* rows per member */, (long)ds.pmax, (long)(c.n_steps * c.grad_stride),
+                          (long)slice};
     const char* mrec = ws + kMemberRecOffset;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
-        const DepthLayout L = depth_layout(env, nb);
-        const EncDesc enc = make_enc(&ds.env, env, branch + r0 * ds.env.branch_in, qn ? trunk + r0 * ds.env.trunk_in : nullptr,
-                                     params);
-        const long prep_total = (env.sh.blk + 2) * n + nb * env.sh.E;
+    const GradMap gm = grad_map(env);
+    for (int64_t i = 0; i < c.n_steps; ++i) {
+        const StepView v = step_view(c, i, ds.env);
+        const DepthLayout L = depth_layout(env, v.nb);
+        const EncDesc enc = make_enc(&ds.env, env, v.branch, v.trunk, c.params);
+        const long prep_total = (env.sh.blk + 2) * n + v.nb * env.sh.E;
         hipLaunchKernelGGL(prep_model_depth_kernel, dim3((unsigned)((prep_total + 255) / 256), (unsigned)n_models), dim3(256), 0, st,
-                           n, ds.dr, (const double*)params, reinterpret_cast<double4*>(ws + L.off_U), (long)nb, enc,
+                           n, ds.dr, (const double*)c.params, reinterpret_cast<double4*>(ws + L.off_U), (long)v.nb, enc,
                            reinterpret_cast<double2*>(ws + L.off_cs), reinterpret_cast<WorkspaceHeader*>(ws), mrec, ms);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
         double* gx = reinterpret_cast<double*>(ws + L.off_gx);
         double* pr = reinterpret_cast<double*>(ws + L.off_pred);
         double* partial = reinterpret_cast<double*>(ws + L.off_part);
-        const BwdArgs ba{runs, (long)nb, (int)env.sh.E, (int)env.sh.blk, reinterpret_cast<const double2*>(ws + L.off_cs),
-                         ws + L.off_U, 0, 0.0, 0.0, nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr,
-                         inv_batch_total[i], pr, gx, partial, QHEA_PAULI_Z, 0, n_models * L.nwaves > simd_count() ? 1 : 0,
+        const BwdArgs ba{runs, (long)v.nb, (int)env.sh.E, (int)env.sh.blk, reinterpret_cast<const double2*>(ws + L.off_cs),
+                         ws + L.off_U, 0, 0.0, 0.0, nullptr, nullptr, nullptr, v.y, qn ? c.params : nullptr,
+                         v.inv_bt, pr, gx, partial, QHEA_PAULI_Z, 0, n_models * L.nwaves > simd_count() ? 1 : 0,
                          nullptr};
         const dim3 grid((unsigned)(L.nwaves / kWaves), (unsigned)n_models);
         profile_begin(st);
         if (lds_supported(n)) {                          // one workgroup per (sample, member)
-            const int rc = launch_lds_bwd_depth(n, dim3((unsigned)nb, (unsigned)n_models), st, ba, DepthArgs{mrec, ms});
-            if (rc != QHEA_OK) return rc;
+            const int rcl = launch_lds_bwd_depth(n, dim3((unsigned)v.nb, (unsigned)n_models), st, ba, DepthArgs{mrec, ms});
+            if (rcl != QHEA_OK) return rcl;
         } else switch (n) {
 #define QHEA_CASE(NN) case NN: launch_bwd_depth_##NN(grid, st, ba, mrec, ms); break;
             QHEA_FOR_EACH_N(QHEA_CASE)
@@ -2314,18 +2212,13 @@ static int depth_grid_steps(const DepthSet& ds, int64_t n_models, const qhea_mod
         }
         profile_end(st);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        const int64_t step = first_step + i;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, hp_fn(hp_ctx, 0).lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-        GradMap gm{};
-        gm.off_ans = env.off_ans; gm.off_bias = env.off_bias; gm.off_sse = env.P;
-        for (int s = 0; s < 2; ++s) { gm.off_w[s] = env.off_w[s]; gm.off_b[s] = env.off_b[s]; }
-        hipLaunchKernelGGL((reduce_model_kernel<false, false, true, DepthRed>), dim3((unsigned)red_blocks, (unsigned)n_models),
-                           dim3(kRedThreads), 0, st, n, (int)env.sh.blk, kw, L.nwaves, (const double*)partial,
-                           (const double*)params, (long)nb, (int)env.sh.E, enc, (const double*)gx, (const double*)pr, y + r0,
-                           inv_batch_total[i], gm, 0, 0, grad + i * grad_stride, adam,
+        const AdamStep as = adam_step(c, i, members[0].lr);
+        hipLaunchKernelGGL((reduce_model_kernel<false, false, true, DepthRed>), dim3((unsigned)red_grid, (unsigned)n_models),
+                           dim3(kRedThreads), 0, st, n, (int)env.sh.blk, padded_3n(n), L.nwaves, (const double*)partial,
+                           (const double*)c.params, (long)v.nb, (int)env.sh.E, enc, (const double*)gx, (const double*)pr, v.y,
+                           v.inv_bt, gm, 0, 0, v.grad, as.adam,
                            reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr, FusePrep{}, DpX{}, ms,
-                           MemberLr{mrec, bc1}, ds.dr);
+                           MemberLr{mrec, as.bc1}, ds.dr);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
     }
     return QHEA_OK;
@@ -2334,28 +2227,110 @@ static int depth_grid_steps(const DepthSet& ds, int64_t n_models, const qhea_mod
 // Ensembles and sweeps at n >= 10 (members_train_steps, R > 1): a depth sweep whose members all have the descriptor's block
 // counts.  Its slices are the ensemble's (the single-model layout, which depth_layout reproduces).  QHEA_EUNSUPPORTED before
 // any launch when the shape has no depth-sweep form.
-static int members_lds_grid(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models, MemberHp hp_fn, const void* ctx,
-                            const double* diag0, int64_t diag_stride, int64_t n_steps, const int64_t* row_begin,
-                            const double* branch, const double* trunk, const double* y, double* params,
-                            const double* inv_batch_total, double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
-                            int64_t first_step, double beta1, double beta2, double eps, double weight_decay, char* ws, size_t slice,
-                            hipStream_t st) {
-    const bool qn = desc->model == QHEA_MODEL_QUANONET;
+static int members_lds_grid(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models,
+                            const qhea_member_hparams* members, int64_t member_step, const double* diag0, int64_t diag_stride,
+                            size_t slice, const TrainCall& c) {
     DepthSet ds;
     ds.env = *desc;
     ds.env.ham_pauli = QHEA_PAULI_Z;
-    if (model_info(&ds.env, ds.env_mi) != QHEA_OK) return QHEA_EUNSUPPORTED;
-    ds.pmax = mi.P;
-    int32_t c[2];
-    depth_counts(*desc, c);
-    ds.c_max[0] = c[0]; ds.c_max[1] = c[1];
-    ds.dr = DepthRed{qn ? 1 : 0, desc->trainable_freq != 0 ? 1 : 0, qn ? desc->net[3] : desc->net[1], qn ? desc->net[1] : 0};
-    if (depth_map(mi.n, qn, mi.trainable, c[0], c[1], ds.dr.ld0, ds.dr.ld1).P != mi.P) return QHEA_EUNSUPPORTED;
-    for (int64_t i = 0; i < n_steps; ++i)
-        if (depth_slice_bytes(ds, row_begin[i + 1] - row_begin[i]) > slice) return QHEA_EUNSUPPORTED;
-    return depth_grid_steps(ds, n_models, desc, 0, hp_fn, ctx, diag0, diag_stride, n_steps, row_begin, branch, trunk, y, params,
-                            inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay, ws,
-                            slice, st);
+    if (model_info(&ds.env, ds.env_mi) != QHEA_OK || depth_set_add(ds, *desc, mi) != QHEA_OK) return QHEA_EUNSUPPORTED;
+    for (int64_t i = 0; i < c.n_steps; ++i)
+        if (depth_slice_bytes(ds, c.row_begin[i + 1] - c.row_begin[i]) > slice) return QHEA_EUNSUPPORTED;
+    return depth_grid_steps(ds, n_models, desc, 0, members, member_step, diag0, diag_stride, slice, c);
+}
+
+// qhea_model_ensemble_train_steps and qhea_model_sweep_train_steps: R members of one shape, member m with hyper-parameters
+// members[m * member_step] (member_step 0: one record for all) and diagonal Hamiltonian diag0 + m * diag_stride (diag0 ==
+// nullptr: none).  The arguments have been checked by the caller.
+static int members_train_steps(const qhea_model_desc* desc, const ModelInfo& mi, int64_t n_models,
+                               const qhea_member_hparams* members, int64_t member_step, const double* diag0,
+                               int64_t diag_stride, const TrainCall& c) {
+    // one slice per member, sized for every batch size of the schedule; one launch per kernel where every step runs the ZYZ
+    // kernels or (n >= 10) the workgroup-resident ones, R consecutive single-model calls otherwise (n = 6..9)
+    size_t slice = 0;
+    bool grid = true;
+    for (int64_t i = 0; i < c.n_steps; ++i) {
+        const int64_t nb = c.row_begin[i + 1] - c.row_begin[i];
+        const size_t b = ensemble_slice_bytes(mi, n_models, nb);
+        if (b > slice) slice = b;
+        grid = grid && n_models <= 65535 && ensemble_grid(mi, n_models, nb);      // (gridDim.y)
+    }
+    if (!c.workspace || c.workspace_bytes / (size_t)n_models < slice) return QHEA_EWORKSPACE;
+    if (grid) return members_zyz_grid(desc, mi, n_models, members, member_step, diag0, diag_stride, slice, c);
+    if (n_models > 1 && lds_supported(mi.n)) {
+        const int rc = members_lds_grid(desc, mi, n_models, members, member_step, diag0, diag_stride, slice, c);
+        if (rc != QHEA_EUNSUPPORTED) return rc;                   // (unsupported: found before anything was launched)
+    }
+    const int64_t rows = c.row_begin[c.n_steps];                    // rows per member
+    for (int64_t m = 0; m < n_models; ++m) {
+        const qhea_member_hparams& h = members[m * member_step];
+        const qhea_model_desc dm = member_desc(*desc, h);
+        TrainCall cm = c;                                           // member m's arrays and workspace slice
+        cm.branch += m * rows * desc->branch_in;
+        if (cm.trunk) cm.trunk += m * rows * desc->trunk_in;
+        cm.y += m * rows;
+        cm.params += m * mi.P; cm.exp_avg += m * mi.P; cm.exp_avg_sq += m * mi.P;
+        cm.grad += m * c.n_steps * c.grad_stride;
+        cm.workspace = c.ws() + m * slice; cm.workspace_bytes = slice;
+        const int rc = model_steps(&dm, mi, diag0 ? diag0 + m * diag_stride : nullptr, h.lr, cm);
+        if (rc != QHEA_OK) return rc;
+        if (m > 0) {
+            hipLaunchKernelGGL(status_fold_kernel, dim3(1), dim3(64), 0, c.st(), reinterpret_cast<WorkspaceHeader*>(c.workspace),
+                               reinterpret_cast<WorkspaceHeader*>(cm.workspace));
+            if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        }
+    }
+    return QHEA_OK;
+}
+
+size_t qhea_model_ensemble_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch) {
+    ModelInfo mi;
+    if (model_info(desc, mi) != QHEA_OK || n_models < 1 || batch < 0) return 0;
+    return (size_t)n_models * ensemble_slice_bytes(mi, n_models, batch);
+}
+
+int qhea_model_ensemble_train_steps(const qhea_model_desc* desc, int64_t n_models, int64_t n_steps, const int64_t* row_begin,
+                                    const double* branch, const double* trunk, const double* y, double* params,
+                                    const double* ham_diag, const double* inv_batch_total, double* grad, int64_t grad_stride,
+                                    double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                    double beta2, double eps, double weight_decay, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    if (!desc || n_models < 1 || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad || first_step < 1)
+        return QHEA_EINVAL;
+    ModelInfo mi;
+    const int rc0 = model_info(desc, mi);
+    if (rc0 != QHEA_OK) return rc0;
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    if (!pauli_ok(desc->ham_pauli, ham_diag) || call_max_batch(call, mi.P, *desc) < 0) return QHEA_EINVAL;
+    // a sweep whose members all share the descriptor's read-out and scale and `lr` (one shared ham_diag)
+    const qhea_member_hparams uni{desc->scale_coeff, desc->ham_offset, desc->ham_coeff, lr, desc->ham_pauli, 0};
+    return members_train_steps(desc, mi, n_models, &uni, 0, ham_diag, 0, call);
+}
+
+size_t qhea_model_sweep_workspace_bytes(const qhea_model_desc* desc, int64_t n_models, int64_t batch) {
+    return qhea_model_ensemble_workspace_bytes(desc, n_models, batch);      // (the MemberRecs live in the slices' headers)
+}
+
+int qhea_model_sweep_train_steps(const qhea_model_desc* desc, int64_t n_models, const qhea_member_hparams* members,
+                                 const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
+                                 const double* trunk, const double* y, double* params, const double* inv_batch_total,
+                                 double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq, int64_t first_step,
+                                 double beta1, double beta2, double eps, double weight_decay, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (!desc || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
+        first_step < 1)
+        return QHEA_EINVAL;
+    if (!member_records_ok(members, n_models, ham_diag)) return QHEA_EINVAL;
+    // the shape (and everything model_info checks) is the descriptor's; its scale and Hamiltonian fields are not used
+    const qhea_model_desc d0 = member_desc(*desc, members[0]);
+    ModelInfo mi;
+    const int rc0 = model_info(&d0, mi);
+    if (rc0 != QHEA_OK) return rc0;
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    if (call_max_batch(call, mi.P, d0) < 0) return QHEA_EINVAL;
+    return members_train_steps(&d0, mi, n_models, members, 1, ham_diag, (int64_t)1 << mi.n, call);
 }
 
 size_t qhea_model_depth_sweep_workspace_bytes(const qhea_model_desc* descs, int64_t n_models, int64_t batch) {
@@ -2373,32 +2348,20 @@ int qhea_model_depth_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
     if (!descs || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
         first_step < 1)
         return QHEA_EINVAL;
-    for (int64_t m = 0; m < n_models; ++m) {
-        const qhea_member_hparams& h = members[m];
-        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
-        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;
-        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;
-    }
+    if (!member_records_ok(members, n_models, ham_diag)) return QHEA_EINVAL;
     DepthSet ds;
     const int rc0 = depth_set(descs, n_models, ds);
     if (rc0 != QHEA_OK) return rc0;
-    const ModelInfo& env = ds.env_mi;
-    if (grad_stride < ds.pmax + 2) return QHEA_EINVAL;
-    for (int64_t i = 0; i < n_steps; ++i)
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
-    const bool qn = ds.env.model == QHEA_MODEL_QUANONET;
-    if (qn && !trunk) return QHEA_EINVAL;
-    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    if (call_max_batch(call, ds.pmax, ds.env) < 0) return QHEA_EINVAL;
     size_t slice = 0;
     for (int64_t i = 0; i < n_steps; ++i) {
         const size_t b = depth_slice_bytes(ds, row_begin[i + 1] - row_begin[i]);
         if (b > slice) slice = b;
     }
     if (!workspace || slice == 0 || workspace_bytes < (size_t)n_models * slice) return QHEA_EWORKSPACE;
-    return depth_grid_steps(ds, n_models, descs, 1, [](const void* c, int64_t m) { return static_cast<const qhea_member_hparams*>(c)[m]; },
-                            members, ham_diag, (int64_t)1 << env.n, n_steps, row_begin, branch, trunk, y, params, inv_batch_total,
-                            grad, grad_stride, exp_avg, exp_avg_sq, first_step, beta1, beta2, eps, weight_decay,
-                            static_cast<char*>(workspace), slice, static_cast<hipStream_t>(stream));
+    return depth_grid_steps(ds, n_models, descs, 1, members, 1, ham_diag, (int64_t)1 << ds.env_mi.n, slice, call);
 }
 
 // ---- qubit sweeps (qhea_model_qubit_sweep_train_steps) ----
@@ -2437,7 +2400,7 @@ static int qubit_set(const qhea_model_desc* descs, int64_t R, QubitSet& qs) {
         if (rc != QHEA_OK) return rc;
         const int n = q.mi.n;
         depth_counts(d, q.c);
-        qs.dr = DepthRed{qn ? 1 : 0, d.trainable_freq != 0 ? 1 : 0, qn ? d.net[3] : d.net[1], qn ? d.net[1] : 0};
+        qs.dr = depth_red(d);
         q.d = depth_map(n, qn, q.mi.trainable, q.c[0], q.c[1], qs.dr.ld0, qs.dr.ld1);
         if (q.d.P != q.mi.P) return QHEA_EUNSUPPORTED;
         q.wave = !lds_supported(n);
@@ -2463,8 +2426,7 @@ struct QubitPlan {
     size_t list_bytes = 0;
 };
 static int red_roles(const QubitMember& q, bool trainable) {
-    const int kw = padded_3n(q.mi.n);
-    return (q.d.blk * kw + red_cols(kw) - 1) / red_cols(kw) + (trainable ? (q.d.E + kFreqCols - 1) / kFreqCols : 0) + 1;
+    return red_blocks(q.mi.n, q.d.blk, q.d.E, trainable).total();
 }
 static void qubit_plan(const QubitSet& qs, int64_t Bmax, QubitPlan& P) {
     const int64_t R = (int64_t)qs.mem.size();
@@ -2536,55 +2498,22 @@ size_t qhea_model_qubit_sweep_workspace_bytes(const qhea_model_desc* descs, int6
     return (size_t)n_models * qubit_slice_bytes(qs, batch, plan.list_bytes);
 }
 
-int qhea_model_qubit_sweep_train_steps(const qhea_model_desc* descs, int64_t n_models, const qhea_member_hparams* members,
-                                       const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
-                                       const double* trunk, const double* y, double* params, const double* inv_batch_total,
-                                       double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
-                                       int64_t first_step, double beta1, double beta2, double eps, double weight_decay,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (!descs || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
-        first_step < 1)
-        return QHEA_EINVAL;
-    for (int64_t m = 0; m < n_models; ++m) {
-        const qhea_member_hparams& h = members[m];
-        if (h.ham_pauli < QHEA_PAULI_Z || h.ham_pauli > QHEA_PAULI_Y || h.reserved != 0) return QHEA_EINVAL;
-        if (!pauli_ok(h.ham_pauli, ham_diag)) return QHEA_EINVAL;
-        if (!(h.lr >= 0.0) || !std::isfinite(h.lr)) return QHEA_EINVAL;
-    }
-    QubitSet qs;
-    const int rc0 = qubit_set(descs, n_models, qs);
-    if (rc0 != QHEA_OK) return rc0;
-    if (grad_stride < qs.pmax + 2) return QHEA_EINVAL;
-    int64_t bmax = 0;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
-        bmax = std::max(bmax, row_begin[i + 1] - row_begin[i]);
-    }
-    const bool qn = descs[0].model == QHEA_MODEL_QUANONET;
-    if (qn && !trunk) return QHEA_EINVAL;
-    if (!params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    QubitPlan plan;
-    qubit_plan(qs, bmax, plan);
-    const size_t slice = qubit_slice_bytes(qs, bmax, plan.list_bytes);     // (every region grows with the batch)
-    if (!workspace || slice == 0 || workspace_bytes < (size_t)n_models * slice) return QHEA_EWORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    const int64_t rows = row_begin[n_steps];                        // rows per member
-    const int64_t diag_stride = (int64_t)1 << qs.nmax;
+// The launches of a qubit sweep (plan: its work lists for the schedule's largest batch; d0: member 0's descriptor, whose
+// input widths and frequency layout are every member's).  The arguments and the slice size have been checked by the caller.
+static int qubit_grid_steps(const QubitSet& qs, const QubitPlan& plan, int64_t n_models, const qhea_model_desc& d0,
+                            const qhea_member_hparams* members, const double* ham_diag, size_t slice, const TrainCall& c) {
+    const bool qn = d0.model == QHEA_MODEL_QUANONET;
+    hipStream_t st = c.st();
+    char* ws = c.ws();
     // every member's read-out, scale, learning rate, block counts and n reach its MemberRec, the work lists the slices'
     // list regions
-    for (int64_t m0 = 0; m0 < n_models; m0 += kMemberFill) {
-        const int cnt = (int)(n_models - m0 < kMemberFill ? n_models - m0 : kMemberFill);
-        MemberFillQubit f{};
-        for (int i = 0; i < cnt; ++i) {
-            f.h[i] = members[m0 + i];
-            f.depth[i][0] = qs.mem[m0 + i].c[0]; f.depth[i][1] = qs.mem[m0 + i].c[1];
-            f.nq[i] = qs.mem[m0 + i].mi.n;
-        }
-        hipLaunchKernelGGL(member_fill_kernel<MemberFillQubit>, dim3(1), dim3(kMemberFill), 0, st, f, cnt, ws + m0 * slice,
-                           (long)slice, ham_diag ? ham_diag + m0 * diag_stride : nullptr, (long)diag_stride);
-        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    }
+    const int rc = fill_member_recs<MemberFillQubit>(n_models, ws, slice, ham_diag, (int64_t)1 << qs.nmax, st,
+                                                     [&](MemberFillQubit& f, int i, int64_t m) {
+        f.h[i] = members[m];
+        f.depth[i][0] = qs.mem[m].c[0]; f.depth[i][1] = qs.mem[m].c[1];
+        f.nq[i] = qs.mem[m].mi.n;
+    });
+    if (rc != QHEA_OK) return rc;
     char* list0 = ws + kHeaderBytes;                             // (QubitLayout::off_list)
     for (int k0 = 0; k0 < (int)plan.e.size(); k0 += kWorkFill) {
         const int cnt = std::min<int>(kWorkFill, (int)plan.e.size() - k0);
@@ -2593,55 +2522,51 @@ int qhea_model_qubit_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
         hipLaunchKernelGGL(work_fill_kernel, dim3(1), dim3(kWorkFill), 0, st, f, cnt, k0, list0, (long)slice, plan.per);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
     }
-    const MemberStride ms{(long)rows, (long)qs.pmax, (long)(n_steps * grad_stride), (long)slice};
+    const MemberStride ms{(long)c.row_begin[c.n_steps] /* rows per member */, (long)qs.pmax, (long)(c.n_steps * c.grad_stride),
+                          (long)slice};
     const char* mrec = ws + kMemberRecOffset;
     QubitBwdArgs qa{};
-    for (int n = 2; n <= 9; ++n) {                              // two runs of fixed (enc = n, ld); the counts are the members'
-        Runs& r = qa.runs[n - 2];
-        r.nruns = 2;
-        r.enc[0] = r.enc[1] = n;
-        r.ld[0] = qs.dr.ld0; r.ld[1] = qs.dr.ld1;
-    }
-    const qhea_model_desc& d0 = descs[0];
+    for (int n = 2; n <= 9; ++n) qa.runs[n - 2] = two_runs(n, qs.dr.ld0, qs.dr.ld1);
     const ModelInfo& mi0 = qs.mem[0].mi;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
-        const QubitLayout L = qubit_layout(qs, nb, plan.list_bytes);
-        const EncDesc enc = make_enc(&d0, mi0, branch + r0 * d0.branch_in, qn ? trunk + r0 * d0.trunk_in : nullptr, params);
+    const GradMap gm = grad_map(mi0);
+    for (int64_t i = 0; i < c.n_steps; ++i) {
+        const StepView v = step_view(c, i, d0);
+        const QubitLayout L = qubit_layout(qs, v.nb, plan.list_bytes);
+        const EncDesc enc = make_enc(&d0, mi0, v.branch, v.trunk, c.params);
         long prep_total = 0;
         for (const QubitMember& q : qs.mem)
-            prep_total = std::max(prep_total, (long)(q.d.blk + 2) * q.mi.n + (long)nb * q.d.E);
+            prep_total = std::max(prep_total, (long)(q.d.blk + 2) * q.mi.n + (long)v.nb * q.d.E);
         hipLaunchKernelGGL(prep_model_qubit_kernel, dim3((unsigned)((prep_total + 255) / 256), (unsigned)n_models), dim3(256), 0,
-                           st, qs.dr, (const double*)params, reinterpret_cast<double4*>(ws + L.off_U), (long)nb, enc,
+                           st, qs.dr, (const double*)c.params, reinterpret_cast<double4*>(ws + L.off_U), (long)v.nb, enc,
                            reinterpret_cast<double2*>(ws + L.off_cs), reinterpret_cast<WorkspaceHeader*>(ws), mrec, ms);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
         double* gx = reinterpret_cast<double*>(ws + L.off_gx);
         double* pr = reinterpret_cast<double*>(ws + L.off_pred);
         double* partial = reinterpret_cast<double*>(ws + L.off_part);
-        qa.B = nb; qa.inv_bt = inv_batch_total[i];
+        qa.B = v.nb; qa.inv_bt = v.inv_bt;
         qa.cs = reinterpret_cast<const double2*>(ws + L.off_cs); qa.gates = ws + L.off_U;
-        qa.y = y + r0; qa.bias = qn ? params : nullptr;
+        qa.y = v.y; qa.bias = qn ? c.params : nullptr;
         qa.out = pr; qa.grad_x = gx; qa.partial = partial;
         qa.mrec = mrec; qa.ms = ms;
+        // the members' launches of n >= 7 (one per n present); dense: BwdArgs::dense
+        auto bwd_args = [&](int n, int dense) {
+            return BwdArgs{two_runs(n, qs.dr.ld0, qs.dr.ld1), (long)v.nb, 0, 0, reinterpret_cast<const double2*>(ws + L.off_cs),
+                           ws + L.off_U, 0, 0.0, 0.0, nullptr, nullptr, nullptr, v.y, qn ? c.params : nullptr, v.inv_bt, pr, gx,
+                           partial, QHEA_PAULI_Z, 0, dense, nullptr};
+        };
         profile_begin(st);
-        for (int c = 0; c < kQsClasses; ++c) {                  // one launch per register class present
-            if (plan.cls_count[c] == 0) continue;
-            qa.wk = QsWork{ws + L.off_list, plan.per, plan.cls_begin[c]};
-            const dim3 grid((unsigned)plan.cls_count[c]);
-            if (c == 0) launch_bwd_qsweep_0(grid, st, qa);
+        for (int cl = 0; cl < kQsClasses; ++cl) {               // one launch per register class present
+            if (plan.cls_count[cl] == 0) continue;
+            qa.wk = QsWork{ws + L.off_list, plan.per, plan.cls_begin[cl]};
+            const dim3 grid((unsigned)plan.cls_count[cl]);
+            if (cl == 0) launch_bwd_qsweep_0(grid, st, qa);
             else launch_bwd_qsweep_1(grid, st, qa);
         }
         for (int n = kQsOwnLo; n <= kQsOwnHi; ++n) {            // n = 7..9: one launch per n present, member = blockIdx.y
             const int cnt = plan.own_count[n - kQsOwnLo];
             if (cnt == 0) continue;
-            const long nw = qs_nwaves(n, nb);
-            Runs runs{};
-            runs.nruns = 2;
-            runs.enc[0] = runs.enc[1] = n;
-            runs.ld[0] = qs.dr.ld0; runs.ld[1] = qs.dr.ld1;
-            const BwdArgs ba{runs, (long)nb, 0, 0, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U, 0, 0.0, 0.0,
-                             nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr, inv_batch_total[i], pr, gx, partial,
-                             QHEA_PAULI_Z, 0, cnt * nw > simd_count() ? 1 : 0, nullptr};
+            const long nw = qs_nwaves(n, v.nb);
+            const BwdArgs ba = bwd_args(n, cnt * nw > simd_count() ? 1 : 0);
             const QubitArgs q{mrec, ms, QsWork{ws + L.off_list, plan.per, plan.own_begin[n - kQsOwnLo]}};
             const dim3 grid((unsigned)(nw / kWaves), (unsigned)cnt);
             switch (n) {
@@ -2654,34 +2579,46 @@ int qhea_model_qubit_sweep_train_steps(const qhea_model_desc* descs, int64_t n_m
         for (int n = kQsLdsLo; n <= kQsLdsHi; ++n) {            // n = 10..12: one launch per n present, one workgroup per
             const int cnt = plan.lds_count[n - kQsLdsLo];         // (sample, member)
             if (cnt == 0) continue;
-            Runs runs{};
-            runs.nruns = 2;
-            runs.enc[0] = runs.enc[1] = n;
-            runs.ld[0] = qs.dr.ld0; runs.ld[1] = qs.dr.ld1;
-            const BwdArgs ba{runs, (long)nb, 0, 0, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U, 0, 0.0, 0.0,
-                             nullptr, nullptr, nullptr, y + r0, qn ? params : nullptr, inv_batch_total[i], pr, gx, partial,
-                             QHEA_PAULI_Z, 0, 0, nullptr};
             const QubitArgs q{mrec, ms, QsWork{ws + L.off_list, plan.per, plan.lds_begin[n - kQsLdsLo]}};
-            const int rc = launch_lds_bwd_qubit(n, dim3((unsigned)nb, (unsigned)cnt), st, ba, q);
-            if (rc != QHEA_OK) return rc;
+            const int rcl = launch_lds_bwd_qubit(n, dim3((unsigned)v.nb, (unsigned)cnt), st, bwd_args(n, 0), q);
+            if (rcl != QHEA_OK) return rcl;
         }
         profile_end(st);
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        const int64_t step = first_step + i;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, members[0].lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-        GradMap gm{};
-        gm.off_ans = mi0.off_ans; gm.off_bias = mi0.off_bias; gm.off_sse = mi0.P;
-        for (int s = 0; s < 2; ++s) { gm.off_w[s] = mi0.off_w[s]; gm.off_b[s] = mi0.off_b[s]; }
+        const AdamStep as = adam_step(c, i, members[0].lr);
         hipLaunchKernelGGL((reduce_model_kernel<false, false, true, QubitRed>), dim3((unsigned)plan.red_count), dim3(kRedThreads), 0,
-                           st, mi0.n, (int)mi0.sh.blk, padded_3n(mi0.n), 0L, (const double*)partial, (const double*)params,
-                           (long)nb, (int)mi0.sh.E, enc, (const double*)gx, (const double*)pr, y + r0, inv_batch_total[i], gm, 0, 0,
-                           grad + i * grad_stride, adam, reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr,
-                           FusePrep{}, DpX{}, ms, MemberLr{mrec, bc1},
+                           st, mi0.n, (int)mi0.sh.blk, padded_3n(mi0.n), 0L, (const double*)partial, (const double*)c.params,
+                           (long)v.nb, (int)mi0.sh.E, enc, (const double*)gx, (const double*)pr, v.y, v.inv_bt, gm, 0, 0,
+                           v.grad, as.adam, reinterpret_cast<const WorkspaceHeader*>(ws), (const double*)nullptr,
+                           FusePrep{}, DpX{}, ms, MemberLr{mrec, as.bc1},
                            QubitRed{qs.dr, QsWork{ws + L.off_list, plan.per, plan.red_begin}});
         if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
     }
     return QHEA_OK;
+}
+
+int qhea_model_qubit_sweep_train_steps(const qhea_model_desc* descs, int64_t n_models, const qhea_member_hparams* members,
+                                       const double* ham_diag, int64_t n_steps, const int64_t* row_begin, const double* branch,
+                                       const double* trunk, const double* y, double* params, const double* inv_batch_total,
+                                       double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
+                                       int64_t first_step, double beta1, double beta2, double eps, double weight_decay,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!descs || n_models < 1 || !members || n_steps < 1 || !row_begin || !inv_batch_total || !branch || !y || !grad ||
+        first_step < 1)
+        return QHEA_EINVAL;
+    if (!member_records_ok(members, n_models, ham_diag)) return QHEA_EINVAL;
+    QubitSet qs;
+    const int rc0 = qubit_set(descs, n_models, qs);
+    if (rc0 != QHEA_OK) return rc0;
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    const int64_t bmax = call_max_batch(call, qs.pmax, descs[0]);
+    if (bmax < 0) return QHEA_EINVAL;
+    QubitPlan plan;
+    qubit_plan(qs, bmax, plan);
+    const size_t slice = qubit_slice_bytes(qs, bmax, plan.list_bytes);     // (every region grows with the batch)
+    if (!workspace || slice == 0 || workspace_bytes < (size_t)n_models * slice) return QHEA_EWORKSPACE;
+    return qubit_grid_steps(qs, plan, n_models, descs[0], members, ham_diag, slice, call);
 }
 
 int qhea_adam_step(int64_t n, double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t step,
@@ -2689,10 +2626,9 @@ int qhea_adam_step(int64_t n, double* params, const double* grads, double* exp_a
     if (n < 0 || step < 1) return QHEA_EINVAL;
     if (n == 0) return QHEA_OK;
     if (!params || !grads || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
+    const TrainCall opt = optimizer_call(params, exp_avg, exp_avg_sq, step, beta1, beta2, eps, weight_decay);
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       (long)n, grads, adam);
+                       (long)n, grads, adam_step(opt, 0, lr).adam);
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 

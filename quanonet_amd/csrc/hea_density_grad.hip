@@ -19,6 +19,7 @@
 // No atomics; nothing depends on the grid, and a row's record and pred do not depend on the batch or on other rows.
 #include "hea_density.hpp"
 #include "hea_adam.hpp"
+#include "hea_train.hpp"
 #include "hea_sincos.hpp"
 
 namespace qhea {
@@ -528,9 +529,7 @@ int check_call(const qhea_model_desc* desc, const double* ham_diag, const qhea_n
     if (rc != QHEA_OK) return rc;
     if (!rates_ok(noise)) return QHEA_EINVAL;
     if (ns.n > 6) return QHEA_EUNSUPPORTED;                              // 2 x 4^n elements per row in LDS
-    const bool pauli_ok = desc->ham_pauli == QHEA_PAULI_Z || ((desc->ham_pauli == QHEA_PAULI_X ||
-                                                               desc->ham_pauli == QHEA_PAULI_Y) && !ham_diag);
-    if (!pauli_ok) return QHEA_EINVAL;
+    if (!pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
     if (!(log10_amplification(ns, noise) <= kMaxLog10Amplification)) return QHEA_EUNSUPPORTED;
     return QHEA_OK;
 }
@@ -635,25 +634,15 @@ int qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n_st
     if (rc0 != QHEA_OK) return rc0;
     if (n_steps == 0) return QHEA_OK;
     if (!row_begin || !inv_batch_total || !branch || !y || !grad || !params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
-    if (grad_stride < gm.P + 2) return QHEA_EINVAL;
-    const bool has_trunk = desc->model == QHEA_MODEL_QUANONET;
-    if (has_trunk && !trunk) return QHEA_EINVAL;
-    size_t need = 0;
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    const int64_t bmax = call_max_batch(call, gm.P, *desc);
+    if (bmax < 0) return QHEA_EINVAL;
+    if (!workspace || workspace_bytes < dens_grad_layout(ns, bmax).total) return QHEA_EWORKSPACE;     // (every region grows with the batch)
     for (int64_t i = 0; i < n_steps; ++i) {
-        if (row_begin[i + 1] <= row_begin[i] || row_begin[i] < 0) return QHEA_EINVAL;
-        const size_t b = dens_grad_layout(ns, row_begin[i + 1] - row_begin[i]).total;
-        need = b > need ? b : need;
-    }
-    if (!workspace || workspace_bytes < need) return QHEA_EWORKSPACE;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
-        const int64_t step = first_step + i;
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        const AdamArgs adam{params, exp_avg, exp_avg_sq, lr / bc1, 1.0 / sqrt(bc2), beta1, beta2, eps, weight_decay};
-        const int rc = loss_grad_launch(desc, ns, gm, nb, branch + r0 * desc->branch_in,
-                                        has_trunk ? trunk + r0 * desc->trunk_in : nullptr, y + r0, params, ham_diag, noise,
-                                        inv_batch_total[i], grad + i * grad_stride, nullptr, static_cast<char*>(workspace),
-                                        static_cast<hipStream_t>(stream), adam);
+        const StepView v = step_view(call, i, *desc);
+        const int rc = loss_grad_launch(desc, ns, gm, v.nb, v.branch, v.trunk, v.y, params, ham_diag, noise, v.inv_bt, v.grad,
+                                        nullptr, call.ws(), call.st(), adam_step(call, i, lr).adam);
         if (rc != QHEA_OK) return rc;
     }
     return QHEA_OK;
