@@ -505,6 +505,8 @@ __global__ __launch_bounds__(kRedThreads) void reduce_kernel(int n, int blk, int
 struct Shape {
     long E = 0, blk = 0;
     Runs runs{};
+    int nblocks = 0;        // circuit blocks (the runs' counts added up)
+    int fast_ld = 0;        // zyz_fast_ld: sub-layers per block of a block-unrolled shape (hea_zyz.hpp), 0: not one
 };
 
 int make_shape(int n, int nb, const int32_t* enc, const int32_t* ld, Shape& sh) {
@@ -525,30 +527,13 @@ int make_shape(int n, int nb, const int32_t* enc, const int32_t* ld, Shape& sh) 
         }
     }
     if (sh.E > INT32_MAX || sh.blk > INT32_MAX) return QHEA_EINVAL;
+    sh.nblocks = nb;
+    sh.fast_ld = zyz_fast_ld(sh.runs, n);
     return QHEA_OK;
 }
 
 inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
-struct Layout {
-    size_t off_U, off_cs, off_part, off_rec, off_srec, off_gmap, total;
-    long nwaves, nwaves_fwd;
-    bool lds_fwd, lds_bwd, pair;
-    bool zfwd, zfwd_shared, ztri, zpacked;   // ZYZ-form kernels of hea_zyz.hpp (n <= 5): forward (private / shared record ring),
-                                             // pipelined backward, one-wave backward
-    int zL;                 // their layer count (records 0 .. zL)
-    bool zsplit;            // n = 5, block-unrolled shape, table fits: split records exist (forward sweeps in the split layout)
-    bool zfwd_split;        // ... and the forward kernel is the split one (batches that leave SIMDs free; Z / diagonal read-out)
-    int zpipes;             // bwd_ztri_kernel: sample groups per workgroup (2 halves the partial rows; hea_zyz.hpp)
-    bool zquad;             // quad-chain pipeline (bwd_zquad_kernel): reverse walks in the split layout too; batches of at most one
-                            // sample group per CU (Z / diagonal read-out: checked at the launch)
-    bool zsnap;             // snapshot pipeline (bwd_zsnap_kernel): psi snapshots of the forward sweep at off_snap (single-model
-                            // layouts only; Z / diagonal read-out and no given final state: checked at the launch, else ztri<5, 2>)
-    size_t off_snap;
-};
-
-// Pipelined backward kernels (n <= 5): several waves per sample group (psi chain, lambda chain, sigma waves), so they
-// pay while the packed kernel would leave SIMDs without a wave (hea_device.hpp: bwd_tri_kernel, bwd_pair_kernel)
 int simd_count() {                                // of the CURRENT device (cached per device ordinal)
     constexpr int kMaxDev = 64;
     static std::atomic<int> cached[kMaxDev];
@@ -565,82 +550,102 @@ int simd_count() {                                // of the CURRENT device (cach
     }
     return v;
 }
-// Backward-kernel choice for n <= 5: QHEA_BWD_AUTO picks by batch density (below); the parity tests and the batch
+// BwdArgs::dense (hea_inst.hip: the n = 8, 9 build of bwd_kernel for full devices): the launch has more waves than SIMDs
+int dense_bit(long waves) { return waves > simd_count() ? 1 : 0; }
+
+// Backward-kernel choice for n <= 5: QHEA_BWD_AUTO picks by batch density (bwd_kernel_for); the parity tests and the batch
 // sweeps force a variant through qhea_set_backward_variant().  Process-wide; it decides the partial-sum layout, so it
 // must not change between qhea_workspace_bytes() and the calls that use that size.
 std::atomic<int> g_bwd_variant{QHEA_BWD_AUTO};
-int use_tri() {                                   // which pipelined variant when use_pair() says "pipelined"
+int use_tri() {                                   // BwdArgs::tri: which first-generation pipelined kernel BwdKernel::PairTri is
     return g_bwd_variant.load(std::memory_order_relaxed) == QHEA_BWD_PAIR ? 0 : 1;   // default: psi / lambda / sigma waves
 }
-bool use_pair(int n, int64_t B) {
-    if (n > 5 || B <= 0) return false;
-    const int v = g_bwd_variant.load(std::memory_order_relaxed);
-    if (v == QHEA_BWD_PACKED || v == QHEA_BWD_ZPACKED) return false;
-    if (v == QHEA_BWD_PAIR || v == QHEA_BWD_TRI || v == QHEA_BWD_ZTRI || v == QHEA_BWD_ZTRI2 || v == QHEA_BWD_ZQUAD ||
-        v == QHEA_BWD_ZSNAP) return true;
-    // measured at n = 5, cfg 2's circuit (us per training step, pipelined in two rounds / one wave per group,
+
+// ---- which kernel a call runs: make_layout (what the workspace holds), then fwd_kernel_for / bwd_kernel_for ----
+// What the two kernel rules read besides the call's own traits.  kernel_inputs() fills all of it before make_layout sizes
+// anything, from (n, shape, B, Bd, variant, simd_count()): the *_workspace_bytes functions know nothing else.
+struct KernelInputs {
+    int var, simd;              // the variant and simd_count() the layout was made under
+    bool lds;                   // n >= 10: workgroup-resident kernels
+    bool records;               // a ZYZ-eligible shape under a variant that runs the ZYZ kernels
+    bool srecords;              // ... n = 5, block-unrolled shape, table fits: forward sweeps and chains in the split layout
+    bool fast;                  // records, and the shape is block-unrolled
+    bool two_fit;               // two pipelines' LDS (bwd_ztri_kernel<N, 2>) fits a workgroup
+    bool single;                // B == Bd: not a launch of several members
+    long rows_d, groups_d, fwd_waves_d;     // rows, sample groups and forward waves of the LAUNCH (Bd)
+};
+// What sizes the workspace, and so must agree between the *_workspace_bytes functions and the calls.
+struct Layout {
+    KernelInputs in;            // what fwd_kernel_for / bwd_kernel_for take
+    size_t off_U, off_cs, off_part, off_rec, off_srec, off_gmap, off_snap, total;
+    long nwaves, nwaves_fwd;    // partial rows of the backward kernel; waves of the first-generation / private-ring forward
+    int zL;                     // ZYZ layer count (records 0 .. zL)
+    bool records, srecords;     // layer records and gmap / split records exist (in.records, in.srecords)
+    bool snaps;                 // psi snapshots of the forward sweep at off_snap: the layouts whose backward is bwd_zsnap_kernel
+    // "Is the backward of the ZYZ family" (prep_zyz_kernel, sums through gmap), for every caller that asks it: the same as
+    // zyz_family(bwd_kernel_for(in, n, traits)) under ANY traits, because bwd_kernel_for reads the traits only to choose
+    // between ZYZ kernels (ZSnap / ZTri2, ZQuad / ZTri1).  The forward's family is another question: zyz_family(fwd_kernel_for).
+    bool zyz_bwd;
+};
+
+// The kernels that exist.  The ZYZ family (hea_zyz.hpp, n <= 5) comes last in both.
+enum class FwdKernel { First /* fwd_kernel */, Lds /* lds_fwd_kernel */, Zyz /* fwd_zyz_kernel: a record ring per wave */,
+                       ZShared /* fwd_zshared_kernel: one ring per workgroup */, Split /* fwd_split_kernel */ };
+enum class BwdKernel { Packed /* bwd_kernel, dense or not: dense_bit */, PairTri /* bwd_pair_kernel / bwd_tri_kernel: use_tri */,
+                       Lds /* lds_bwd_kernel */, ZTri1, ZTri2 /* bwd_ztri_kernel<N, 1 / 2> */, ZPacked, ZQuad, ZSnap };
+inline bool zyz_family(FwdKernel k) { return k >= FwdKernel::Zyz; }
+inline bool zyz_family(BwdKernel k) { return k >= BwdKernel::ZTri1; }
+// what a call adds to its layout: the read-out, whether the backward is given the final state, members in the launch
+struct CallTraits { int pauli = QHEA_PAULI_Z; bool state_given = false; int R = 1; };
+
+FwdKernel fwd_kernel_for(const KernelInputs& in, const CallTraits& c) {
+    // Workgroup-resident kernels (hea_lds.hip) for n >= 10; the wave-resident ones are built for n <= 9 only.
+    // Measured when both existed, 12 sub-layers, B = 1024, forward / forward+backward:
+    //   n = 10: 67 / 232 us vs 97 / 263 us wave-resident;  n = 11: 110 / 450 vs 144 / 1250 us (the wave-resident
+    //   backward spills);  n = 12: 205 / 880 us vs 367 us / 12.4 ms.
+    if (in.lds) return FwdKernel::Lds;
+    // second-generation kernels for n <= 5 (hea_zyz.hpp): the default when the shape is eligible (in.records); the
+    // first-generation forward takes over for shapes whose (cos, sin) table exceeds LDS.
+    // Measured at cfg 2's circuit (us per call incl. prep; first-generation / ZYZ form):
+    //   forward   B = 1024 55 / 44,  4096 87 / 89,  16384 236 / 255 with a record ring per wave (22 KB of LDS per wave
+    //             cap the waves per CU once the batch could fill them) -> one ring per workgroup beyond one wave per SIMD
+    // so: private-ring kernel while the sweeps leave SIMDs free, shared-ring kernel (block-unrolled shapes) beyond;
+    // other shapes fall back to the first-generation forward once two waves per SIMD are reached
+    const int var = in.var;
+    const bool shared = in.fast && (var == QHEA_BWD_ZPACKED || (var == QHEA_BWD_AUTO && in.fwd_waves_d > (long)in.simd));
+    const bool zyz = in.records && (shared || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZQUAD ||
+                                   var == QHEA_BWD_ZSNAP || in.fwd_waves_d <= 2L * in.simd);
+    if (!zyz) return FwdKernel::First;
+    if (shared) return FwdKernel::ZShared;
+    // split forward, one sample per wave: pays while every sweeping wave still gets a SIMD of its own; Z / diagonal read-out
+    // only -- X or Y: the private-ring forward
+    if (in.srecords && in.rows_d <= (int64_t)in.simd && c.pauli == QHEA_PAULI_Z) return FwdKernel::Split;
+    return FwdKernel::Zyz;
+}
+
+BwdKernel bwd_kernel_for(const KernelInputs& in, int n, const CallTraits& c) {
+    if (in.lds) return BwdKernel::Lds;                  // n >= 10 (measurements: fwd_kernel_for)
+    const int var = in.var;
+    const long cus = (long)in.simd / 4;
+    // Pipelined backward kernels (n <= 5): several waves per sample group (psi chain, lambda chain, sigma waves), so they
+    // pay while the packed kernel would leave SIMDs without a wave (hea_device.hpp: bwd_tri_kernel, bwd_pair_kernel).
+    // Measured at n = 5, cfg 2's circuit (us per training step, pipelined in two rounds / one wave per group,
     // profiles/r03_batch_sweep.txt, end of round 3): B = 1100 141.3 / 153.3, 1280 142.0 / 154.3, 1536 144.2 / 155.8,
     // 1792 216.2 / 156.9 -- pipelined while the sample groups fill at most 6/8 of the SIMDs (3 per CU: two rounds of the
     // one-pipeline workgroups; the third round starts beyond)
-    const int spw = 64 >> lane_bits(n);
-    return 8 * ((B + spw - 1) / spw) <= 6 * (int64_t)simd_count();
-}
-
-// Workgroup-resident kernels (hea_lds.hip) for n >= 10; the wave-resident ones are built for n <= 9 only.
-// Measured when both existed, 12 sub-layers, B = 1024, forward / forward+backward:
-//   n = 10: 67 / 232 us vs 97 / 263 us wave-resident;  n = 11: 110 / 450 vs 144 / 1250 us (the wave-resident
-//   backward spills);  n = 12: 205 / 880 us vs 367 us / 12.4 ms.
-bool use_lds(int n, bool backward) {
-    (void)backward;
-    return lds_supported(n);
-}
-
-// B: rows of ONE model, which sizes the workspace (partial rows, tables); Bd: rows the launch carries, which choose the kernels
-// -- R x B for an ensemble launch of R members (qhea_model_ensemble_train_steps: the occupancy rules below are about the whole
-// grid), B otherwise.
-Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
-    Layout L{};
-    const int spw_packed = 64 >> lane_bits(n);
-    L.lds_fwd = use_lds(n, false);
-    L.lds_bwd = use_lds(n, true);
-    L.pair = !L.lds_bwd && use_pair(n, Bd);
-    const int spw = L.lds_bwd ? 1 : spw_packed;
-    auto round_waves = [](long w) { return ((w + kWaves - 1) / kWaves) * kWaves; };   // padding waves write zeros
-    L.nwaves_fwd = round_waves((B + spw_packed - 1) / spw_packed);
-    L.nwaves = L.lds_bwd ? B : round_waves((B + spw - 1) / spw);                      // backward partial rows
-    if (L.pair) L.nwaves = (B + spw - 1) / spw;                                       // one row per workgroup (= sample group)
-    const long nwaves_fwd_d = round_waves((Bd + spw_packed - 1) / spw_packed);        // ... and the same counts for the launch
-    const long groups_d = (Bd + spw - 1) / spw;                                       // (pipelined kernels: nwaves = groups)
-    // second-generation kernels for n <= 5 (hea_zyz.hpp): the default when the shape is eligible; the first-generation
-    // variants stay selectable (qhea_set_backward_variant) and take over for shapes whose (cos, sin) table exceeds LDS
-    const int var = g_bwd_variant.load(std::memory_order_relaxed);
-    const bool zok = zyz_eligible(n, sh.E) &&
-                     (var == QHEA_BWD_AUTO || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZPACKED ||
-                      var == QHEA_BWD_ZQUAD || var == QHEA_BWD_ZSNAP);
-    // Measured at cfg 2's circuit (us per call incl. prep / reduce; first-generation / ZYZ form):
-    //   forward   B = 1024 55 / 44,  4096 87 / 89,  16384 236 / 255 with a record ring per wave (22 KB of LDS per wave
-    //             cap the waves per CU once the batch could fill them) -> one ring per workgroup beyond one wave per SIMD
+    const bool pipelined = n <= 5 && in.rows_d > 0 && var != QHEA_BWD_PACKED && var != QHEA_BWD_ZPACKED &&
+                           (var != QHEA_BWD_AUTO || 8 * in.groups_d <= 6 * (int64_t)in.simd);
+    // Measured at cfg 2's circuit (us per call incl. prep / reduce):
     //   backward  B = 1024 packed 189, tri 135, ztri 115, zpacked 173;  2048 251 / 255 / 208 / 180;
     //             4096 302 / 400 / 402 / 258;  16384 1159 / 1405 / 1580 / 846   (scripts/ablate/bsweep_all.py)
-    // so AUTO keeps round 1's rule for the pipeline (sample groups on at most 3/4 of the SIMDs) and takes the one-wave
-    // ZYZ kernel beyond.
-    const bool fast = zok && zyz_fast_ld(sh.runs, n) != 0;
-    // forward: private-ring kernel while the sweeps leave SIMDs free, shared-ring kernel (block-unrolled shapes) beyond;
-    // other shapes fall back to the first-generation forward once two waves per SIMD are reached
-    L.zfwd_shared = fast && (var == QHEA_BWD_ZPACKED || (var == QHEA_BWD_AUTO && nwaves_fwd_d > (long)simd_count()));
-    L.zfwd = zok && (L.zfwd_shared || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZQUAD || var == QHEA_BWD_ZSNAP ||
-                     nwaves_fwd_d <= 2L * simd_count());
-    L.ztri = zok && L.pair;
-    // batches that fill the SIMDs: the one-wave ZYZ kernel for the block-unrolled shapes (B = 16384 at cfg 2's circuit:
-    // see DESIGN.md section 3.5), the first-generation packed kernel otherwise
-    const bool zp_ok = zyz_eligible(n, sh.E) && zyz_fast_ld(sh.runs, n) != 0 && !L.lds_bwd;
-    L.zpacked = zp_ok && ((var == QHEA_BWD_AUTO && !L.pair) || var == QHEA_BWD_ZPACKED);
-    if (L.zpacked) {
-        L.pair = false; L.ztri = false;
-        L.nwaves = ((B + spw - 1) / spw + kZPWaves - 1) / kZPWaves;                 // one partial row per WORKGROUP (its four waves' sums added in LDS)
-    }
-    L.zL = zok ? zyz_layer_count(sh.runs, n) : 0;
-    L.zsplit = zok && zsplit_eligible(n, sh.E, sh.runs);
+    // so AUTO keeps round 1's rule for the pipeline (sample groups on at most 3/4 of the SIMDs) and, for batches that fill the
+    // SIMDs, takes the one-wave ZYZ kernel for the block-unrolled shapes (B = 16384 at cfg 2's circuit: see DESIGN.md section
+    // 3.5), the first-generation packed kernel otherwise
+    if (in.fast && (var == QHEA_BWD_ZPACKED || (var == QHEA_BWD_AUTO && !pipelined))) return BwdKernel::ZPacked;
+    if (!pipelined) return BwdKernel::Packed;
+    // the first-generation pipeline stays selectable (QHEA_BWD_PAIR / TRI) and takes over for shapes whose (cos, sin) table
+    // exceeds LDS
+    if (!in.records) return BwdKernel::PairTri;
     // Two pipelines per workgroup (bwd_ztri_kernel<N, 2>: their sigma waves add the two groups' sums in LDS, half the partial
     // rows).  With the chain waves laid out as the workgroup's waves 0..3 every SIMD hosts exactly ONE of the CU's four chain
     // waves; two separate five-wave workgroups (and round 2's pipeline-by-pipeline layout of the ten) put two chains on one
@@ -648,46 +653,81 @@ Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
     // one: B = 520 89.5 / 96.1, 640 90.0 / 97.8, 768 90.6 / 98.5, 896 91.1 / 99.3, 1024 91.3 / 101.1 (profiles/r03_batch_sweep.txt)
     // -- so AUTO takes two pipelines wherever the batch has more sample groups than the device has CUs (up to two per CU; beyond
     // that the one-pipeline workgroups run in two rounds, 154 us at 1280).  QHEA_BWD_ZTRI2 forces them, QHEA_BWD_ZTRI never.
-    L.zpipes = 1;
-    const long cus = (long)simd_count() / 4;
-    const bool two_wanted = var == QHEA_BWD_ZTRI2 ? groups_d > cus
-                          : var == QHEA_BWD_ZSNAP ? true
-                                                  : (var == QHEA_BWD_AUTO && groups_d > cus && groups_d <= 2 * cus);
-    if (L.ztri && two_wanted) {
-        const size_t cs_bytes = (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * (L.zsplit ? 32 : 16);
-        const size_t lds = 2 * ztri_fixed_lds(kZRingDepth<2>) + 2 * cs_bytes +
-                           (size_t)sh.blk * padded_3n(n) * sizeof(double);
-        if (lds <= 158 * 1024) { L.zpipes = 2; L.nwaves = (L.nwaves + 1) / 2; }      // one partial row per workgroup
+    const bool auto_two = var == QHEA_BWD_AUTO && in.groups_d > cus && in.groups_d <= 2 * cus;
+    const bool two_wanted = var == QHEA_BWD_ZTRI2 ? in.groups_d > cus : (var == QHEA_BWD_ZSNAP || auto_two);
+    if (two_wanted && in.two_fit) {
+        // Snapshot pipeline (bwd_zsnap_kernel): where AUTO takes two pipelines per workgroup, the sigma waves read psi from the
+        // forward sweep's snapshots instead of a psi chain walking back (cfg 2, B = 1024: kernel 74.5 -> 70.0 us, step 0.0828 ->
+        // 0.0783 ms).  Single-model layouts only (ensembles keep bwd_ztri_kernel); X or Y read-out, a
+        // given final state or several members: the two-pipeline ztri kernel
+        const bool snap_wanted = var == QHEA_BWD_ZSNAP || auto_two;
+        if (in.srecords && in.single && snap_wanted && n == 5 && c.pauli == QHEA_PAULI_Z && !c.state_given && c.R == 1)
+            return BwdKernel::ZSnap;
+        return BwdKernel::ZTri2;
     }
     // Quad-chain pipeline: where every CU holds at most one sample group the step time is the length of the dependent chain,
     // and the split-layout reverse walk shortens it (cfg 2's circuit, us per training step, all-lane / split reverse walk:
-    // DESIGN.md section 3.3a).  Same partial-row layout as the one-pipeline kernel.
-    L.zquad = L.ztri && L.zsplit && L.zpipes == 1 &&
-              (var == QHEA_BWD_ZQUAD || (var == QHEA_BWD_AUTO && groups_d <= cus));
+    // DESIGN.md section 3.3a).  Same partial-row layout as the one-pipeline kernel, which X or Y read-outs fall back to.
+    const bool quad_wanted = var == QHEA_BWD_ZQUAD || (var == QHEA_BWD_AUTO && in.groups_d <= cus);
+    if (in.srecords && quad_wanted && n == 5 && c.pauli == QHEA_PAULI_Z) return BwdKernel::ZQuad;
+    return BwdKernel::ZTri1;
+}
+
+// B: rows of ONE model, which sizes the workspace (partial rows, tables); Bd: rows the launch carries, which choose the kernels
+// -- R x B for an ensemble launch of R members (qhea_model_ensemble_train_steps: the occupancy rules above are about the whole
+// grid), B otherwise.
+KernelInputs kernel_inputs(int n, const Shape& sh, int64_t B, int64_t Bd) {
+    KernelInputs in{};
+    const int spw = 64 >> lane_bits(n);                // samples per wave of the wave-resident kernels
+    const int var = g_bwd_variant.load(std::memory_order_relaxed);
+    in.var = var; in.simd = simd_count(); in.lds = lds_supported(n);
+    in.records = zyz_eligible(n, sh.E) &&
+                 (var == QHEA_BWD_AUTO || var == QHEA_BWD_ZTRI || var == QHEA_BWD_ZTRI2 || var == QHEA_BWD_ZPACKED ||
+                  var == QHEA_BWD_ZQUAD || var == QHEA_BWD_ZSNAP);
+    in.fast = in.records && sh.fast_ld != 0;
+    in.srecords = in.records && zsplit_eligible(n, sh.E, sh.runs);
+    in.two_fit = in.records && 2 * ztri_fixed_lds(kZRingDepth<2>) + 2 * (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * (in.srecords ? 32 : 16) +
+                                   (size_t)sh.blk * padded_3n(n) * sizeof(double) <= 158 * 1024;
+    in.single = B == Bd; in.rows_d = Bd;
+    in.groups_d = (Bd + spw - 1) / spw;
+    in.fwd_waves_d = ((in.groups_d + kWaves - 1) / kWaves) * kWaves;
+    return in;
+}
+Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
+    Layout L{};
+    const int spw = 64 >> lane_bits(n);
+    auto round_waves = [](long w) { return ((w + kWaves - 1) / kWaves) * kWaves; };   // padding waves write zeros
+    L.in = kernel_inputs(n, sh, B, Bd);
+    L.records = L.in.records; L.srecords = L.in.srecords;
+    L.zL = L.records ? zyz_layer_count(sh.runs, n) : 0;
+    // the backward family first (the fall-backs by read-out, given state or member count stay inside a family's partial-row
+    // layout), then the partial rows from it
+    const BwdKernel fam = bwd_kernel_for(L.in, n, CallTraits{});
+    L.zyz_bwd = zyz_family(fam);
+    L.snaps = fam == BwdKernel::ZSnap;
+    const long groups = (B + spw - 1) / spw;
+    L.nwaves_fwd = round_waves(groups);
+    switch (fam) {
+        case BwdKernel::Lds:     L.nwaves = B; break;                                      // one row per sample
+        case BwdKernel::Packed:  L.nwaves = round_waves(groups); break;
+        case BwdKernel::ZPacked: L.nwaves = (groups + kZPWaves - 1) / kZPWaves; break;     // one row per WORKGROUP (its four waves' sums added in LDS)
+        case BwdKernel::ZTri2: case BwdKernel::ZSnap: L.nwaves = (groups + 1) / 2; break;  // one row per workgroup = two sample groups
+        default:                 L.nwaves = groups; break;                                 // one row per workgroup = sample group
+    }
     size_t p = kHeaderBytes;                         // WorkspaceHeader
     L.off_U = p;    p = align_up(p + (size_t)(sh.blk + 2) * n * kGateBytes);
     L.off_cs = p;   p = align_up(p + (size_t)B * sh.E * sizeof(double2));
     L.off_part = p; p = align_up(p + (size_t)L.nwaves * sh.blk * padded_3n(n) * sizeof(double));
-    L.off_rec = p;  p = align_up(p + (zok ? (size_t)(L.zL + 1 + 2 * kPadRecs) * kRecBytes : 0));   // padded both sides
-    if (zok) L.off_rec += (size_t)kPadRecs * kRecBytes;                                           // -> record 0
-    // one sample per wave: pays while every sweeping wave still gets a SIMD of its own
-    L.zfwd_split = L.zsplit && L.zfwd && !L.zfwd_shared && Bd <= (int64_t)simd_count();
-    L.off_srec = p; p = align_up(p + (L.zsplit ? (size_t)(L.zL + 1 + 2 * kPadRecs) * kRecBytes : 0));
-    if (L.zsplit) L.off_srec += (size_t)kPadRecs * kRecBytes;
-    L.off_gmap = p; p = align_up(p + (zok ? (size_t)sh.blk * n * kGmapDoubles * sizeof(double) : 0));
-    // Snapshot pipeline (bwd_zsnap_kernel): where AUTO takes two pipelines per workgroup (more sample groups than CUs, at most
-    // two per CU), the sigma waves read psi from the forward sweep's snapshots instead of a psi chain walking back (cfg 2,
-    // B = 1024: kernel 74.5 -> 70.0 us, step 0.0828 -> 0.0783 ms).  psi of every sample group at every
-    // publication point, 1 KB each (61 MB at B = 1024, cfg 2); the region exists only in the layouts that select the kernel,
-    // so qhea_workspace_bytes agrees with the call.  Single-model layouts only (ensembles keep bwd_ztri_kernel).
-    L.zsnap = L.ztri && L.zsplit && L.zpipes == 2 && B == Bd &&
-              (var == QHEA_BWD_ZSNAP || (var == QHEA_BWD_AUTO && groups_d > cus && groups_d <= 2 * cus));
+    const size_t rec_bytes = (size_t)(L.zL + 1 + 2 * kPadRecs) * kRecBytes;                       // padded both sides
+    L.off_rec = p;  p = align_up(p + (L.records ? rec_bytes : 0));
+    if (L.records) L.off_rec += (size_t)kPadRecs * kRecBytes;                                     // -> record 0
+    L.off_srec = p; p = align_up(p + (L.srecords ? rec_bytes : 0));
+    if (L.srecords) L.off_srec += (size_t)kPadRecs * kRecBytes;
+    L.off_gmap = p; p = align_up(p + (L.records ? (size_t)sh.blk * n * kGmapDoubles * sizeof(double) : 0));
+    // psi of every sample group at every publication point, 1 KB each (61 MB at B = 1024, cfg 2); the region exists only in the
+    // layouts that select the snapshot kernel, so qhea_workspace_bytes agrees with the call
     L.off_snap = p;
-    if (L.zsnap) {
-        int nblocks = 0;
-        for (int i = 0; i < sh.runs.nruns; ++i) nblocks += sh.runs.count[i];
-        p = align_up(p + (size_t)(2 * L.nwaves) * nblocks * zyz_fast_ld(sh.runs, n) * kSnapBytes);
-    }
+    if (L.snaps) p = align_up(p + (size_t)(2 * L.nwaves) * sh.nblocks * sh.fast_ld * kSnapBytes);
     L.total = p;
     return L;
 }
@@ -709,86 +749,117 @@ inline void profile_end(hipStream_t st) {
 int launch_prep_zyz(int n, const Shape& sh, const double* w, char* ws, const Layout& L, hipStream_t st, int R = 1,
                     const MemberStride& ms = MemberStride{}) {
     hipLaunchKernelGGL(prep_zyz_kernel, dim3((unsigned)(L.zL + 1), (unsigned)R), dim3(64), 0, st, sh.runs, n, L.zL, w,
-                       ws + L.off_rec, L.zsplit ? ws + L.off_srec : nullptr, reinterpret_cast<double*>(ws + L.off_gmap),
+                       ws + L.off_rec, L.srecords ? ws + L.off_srec : nullptr, reinterpret_cast<double*>(ws + L.off_gmap),
                        reinterpret_cast<WorkspaceHeader*>(ws), ms);
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
-int launch_zyz_forward(int n, const Shape& sh, int64_t B, const Layout& L, char* ws, const AngleSrc& src, double off, double co,
-                       const double* diag, int pauli, double* out, double* state_out, const double* bias, hipStream_t st) {
-    const int fast = zyz_fast_ld(sh.runs, n);
-    int nblocks = 0;
-    for (int i = 0; i < sh.runs.nruns; ++i) nblocks += sh.runs.count[i];
+// The ZYZ-family forward kernel k (fwd_kernel_for): its grid, its LDS bytes, its launch.  Like every circuit-kernel launcher
+// here, timed by qhea_profile_next_circuit_kernel; QHEA_EUNSUPPORTED: a qubit count this build lacks
+int launch_zyz_forward(FwdKernel k, int n, const Shape& sh, int64_t B, const Layout& L, char* ws, const AngleSrc& src, double off,
+                       double co, const double* diag, int pauli, double* out, double* state_out, const double* bias,
+                       hipStream_t st) {
     const ZFwdArgs za{sh.runs, (long)B, (int)sh.E, ws + L.off_rec, (int)((L.zL + 1) * kRecBytes), L.zL, src, off, co, diag,
-                      pauli, out, state_out, bias, fast, nblocks, L.zsplit ? ws + L.off_srec : nullptr};
-    if (L.zfwd_split && pauli == QHEA_PAULI_Z) {
-        const dim3 gs((unsigned)((B + kSplitWaves - 1) / kSplitWaves));
-        launch_fwd_split_5(gs, (size_t)kSplitWaves * zyz_cs_row(5, sh.E) * 32, st, za);
-        return QHEA_OK;
-    }
-    if (L.zfwd_shared) {
-        const long groups = (B + (64 >> n) - 1) / (64 >> n);
-        const dim3 gs((unsigned)((groups + kZPWaves - 1) / kZPWaves));
-        const size_t dyns = (size_t)kZPWaves * (64 >> n) * zyz_cs_row(n, sh.E) * sizeof(double2);
-        switch (n) {
-#define QHEA_CASE(NN) case NN: launch_fwd_zshared_##NN(gs, dyns, st, za); break;
-            QHEA_FOR_EACH_ZN(QHEA_CASE)
-#undef QHEA_CASE
-            default: return QHEA_EUNSUPPORTED;
-        }
-        return QHEA_OK;
-    }
-    const dim3 grid((unsigned)((L.nwaves_fwd + kZFwdWaves - 1) / kZFwdWaves));
-    const size_t dyn = (size_t)kZFwdWaves * (64 >> n) * zyz_cs_row(n, sh.E) * sizeof(double2);
-    switch (n) {
-#define QHEA_CASE(NN) case NN: launch_fwd_zyz_##NN(grid, dyn, st, za); break;
+                      pauli, out, state_out, bias, sh.fast_ld, sh.nblocks, L.srecords ? ws + L.off_srec : nullptr};
+    const size_t group_cs = (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * sizeof(double2);    // a sample group's (cos, sin) table
+    const long groups = (B + (64 >> n) - 1) / (64 >> n);
+    const dim3 shared_grid((unsigned)((groups + kZPWaves - 1) / kZPWaves));
+    const dim3 ring_grid((unsigned)((L.nwaves_fwd + kZFwdWaves - 1) / kZFwdWaves));
+    int rc = QHEA_EUNSUPPORTED;
+    profile_begin(st);
+    if (k == FwdKernel::Split) {
+        launch_fwd_split_5(dim3((unsigned)((B + kSplitWaves - 1) / kSplitWaves)), (size_t)kSplitWaves * zyz_cs_row(5, sh.E) * 32, st, za);
+        rc = QHEA_OK;
+    } else if (k == FwdKernel::ZShared) switch (n) {
+#define QHEA_CASE(NN) case NN: launch_fwd_zshared_##NN(shared_grid, kZPWaves * group_cs, st, za); rc = QHEA_OK; break;
         QHEA_FOR_EACH_ZN(QHEA_CASE)
 #undef QHEA_CASE
-        default: return QHEA_EUNSUPPORTED;
+    } else if (k == FwdKernel::Zyz) switch (n) {
+#define QHEA_CASE(NN) case NN: launch_fwd_zyz_##NN(ring_grid, kZFwdWaves * group_cs, st, za); rc = QHEA_OK; break;
+        QHEA_FOR_EACH_ZN(QHEA_CASE)
+#undef QHEA_CASE
     }
-    return QHEA_OK;
+    profile_end(st);
+    if (rc != QHEA_OK) return rc;
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
-int launch_zyz_backward(int n, const Shape& sh, int64_t B, const Layout& L, char* ws, const AngleSrc& src, double off,
+// the ZYZ-family backward kernel k (bwd_kernel_for): one partial row per workgroup, member = blockIdx.y
+int launch_zyz_backward(BwdKernel k, int n, const Shape& sh, int64_t B, const Layout& L, char* ws, const AngleSrc& src, double off,
                         double co, const double* diag, int pauli, const double* g, const double* state_in, const double* y,
                         const double* bias, double inv_bt, double* out, double* grad_x, double* partial, hipStream_t st,
                         int R = 1, const MemberStride& ms = MemberStride{}, const char* mrec = nullptr) {
-    const int fast = zyz_fast_ld(sh.runs, n);
-    int nblocks = 0;
-    for (int i = 0; i < sh.runs.nruns; ++i) nblocks += sh.runs.count[i];
+    const int pipes = (k == BwdKernel::ZTri2 || k == BwdKernel::ZSnap) ? 2 : 1;
+    const bool split = L.srecords && k != BwdKernel::ZPacked;       // the chains sweep forward in the split layout
     ZBwdArgs za{sh.runs, (long)B, (int)sh.E, (int)sh.blk, ws + L.off_rec, (int)((L.zL + 1) * kRecBytes), L.zL, src, off, co,
                       diag, pauli, g, state_in, y, bias, inv_bt, out, grad_x, partial,
-                      &reinterpret_cast<WorkspaceHeader*>(ws)->status, fast, nblocks,
-                      (L.zsplit && !L.zpacked) ? ws + L.off_srec : nullptr, L.zpipes};
+                      &reinterpret_cast<WorkspaceHeader*>(ws)->status, sh.fast_ld, sh.nblocks,
+                      split ? ws + L.off_srec : nullptr, pipes};
     za.ms = ms;
     za.src.m_rows = ms.rows; za.src.m_params = ms.params;
-    const unsigned gy = (unsigned)R;
+    const dim3 grid((unsigned)L.nwaves, (unsigned)R);
     const size_t dyn = (size_t)(64 >> n) * zyz_cs_row(n, sh.E) * sizeof(double2);
-    if (L.zpacked) {
-        switch (n) {
-#define QHEA_CASE(NN) case NN: launch_bwd_zpacked_##NN(dim3((unsigned)L.nwaves, gy), zp_cs_bytes(n, sh.E, kZPWaves * (64 >> n)), st, za, mrec); break;
-            QHEA_FOR_EACH_ZN(QHEA_CASE)
-#undef QHEA_CASE
-            default: return QHEA_EUNSUPPORTED;
-        }
-        return QHEA_OK;
-    }
-    if (L.zsnap && n == 5 && pauli == QHEA_PAULI_Z && za.srec && !state_in && R == 1) {
+    const size_t sums = (size_t)sh.blk * padded_3n(n) * sizeof(double);      // two pipelines: their sums added in LDS
+    const size_t dyn_tri = (size_t)pipes * (ztri_fixed_lds(pipes == 2 ? kZRingDepth<2> : kZRingDepth<1>) + (split ? 2 * dyn : dyn)) +
+                           (pipes == 2 ? sums : 0);
+    int rc = QHEA_EUNSUPPORTED;
+    profile_begin(st);
+    if (k == BwdKernel::ZSnap) {
         za.snap = ws + L.off_snap;
-        launch_bwd_zsnap_5(dim3((unsigned)L.nwaves, gy), 2 * (zsnap_fixed_lds(kZSnapRing) + 2 * dyn) + (size_t)sh.blk * padded_3n(n) * sizeof(double), st, za);
-        return QHEA_OK;
-    }
-    if (L.zquad && n == 5 && pauli == QHEA_PAULI_Z && za.srec) {
-        launch_bwd_zquad_5(dim3((unsigned)L.nwaves, gy), zquad_fixed_lds(kPairRing) + 2 * dyn, st, za, mrec);
-        return QHEA_OK;
-    }
-    const size_t dyn_tri = (size_t)L.zpipes * (ztri_fixed_lds(L.zpipes == 2 ? kZRingDepth<2> : kZRingDepth<1>) + (za.srec ? 2 * dyn : dyn)) +
-                           (L.zpipes == 2 ? (size_t)sh.blk * padded_3n(n) * sizeof(double) : 0);
-    switch (n) {
-#define QHEA_CASE(NN) case NN: launch_bwd_ztri_##NN(dim3((unsigned)L.nwaves, gy), dyn_tri, st, za, mrec); break;
+        launch_bwd_zsnap_5(grid, 2 * (zsnap_fixed_lds(kZSnapRing) + 2 * dyn) + sums, st, za);
+        rc = QHEA_OK;
+    } else if (k == BwdKernel::ZQuad) {
+        launch_bwd_zquad_5(grid, zquad_fixed_lds(kPairRing) + 2 * dyn, st, za, mrec);
+        rc = QHEA_OK;
+    } else if (k == BwdKernel::ZPacked) switch (n) {
+#define QHEA_CASE(NN) case NN: launch_bwd_zpacked_##NN(grid, zp_cs_bytes(n, sh.E, kZPWaves * (64 >> n)), st, za, mrec); rc = QHEA_OK; break;
         QHEA_FOR_EACH_ZN(QHEA_CASE)
+#undef QHEA_CASE
+    } else if (k == BwdKernel::ZTri1 || k == BwdKernel::ZTri2) switch (n) {
+#define QHEA_CASE(NN) case NN: launch_bwd_ztri_##NN(grid, dyn_tri, st, za, mrec); rc = QHEA_OK; break;
+        QHEA_FOR_EACH_ZN(QHEA_CASE)
+#undef QHEA_CASE
+    }
+    profile_end(st);
+    if (rc != QHEA_OK) return rc;
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
+// The first-generation and workgroup-resident circuit kernels (FwdKernel::First / Lds, BwdKernel::Packed / PairTri / Lds) on the
+// tables of prep_kernel / prep_model_kernel
+int launch_table_forward(FwdKernel k, int n, const Shape& sh, int64_t B, const Layout& L, const char* ws, double off, double co,
+                         const double* diag, int pauli, double* out, double* state_out, const double* bias, hipStream_t st) {
+    const FwdArgs fa{sh.runs, (long)B, (int)sh.E, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U,
+                     (int)((sh.blk + 2) * n * kGateBytes), off, co, diag, out, state_out, bias, pauli};
+    const dim3 grid((unsigned)(L.nwaves_fwd / kWaves));
+    profile_begin(st);
+    if (k == FwdKernel::Lds) {
+        if (launch_lds_fwd(n, (long)B, st, fa) != QHEA_OK) return QHEA_ELAUNCH;
+    } else switch (n) {
+#define QHEA_CASE(NN) case NN: launch_fwd_##NN(grid, st, fa); break;
+        QHEA_FOR_EACH_N(QHEA_CASE)
 #undef QHEA_CASE
         default: return QHEA_EUNSUPPORTED;
     }
-    return QHEA_OK;
+    profile_end(st);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+int launch_table_backward(BwdKernel k, int n, const Shape& sh, int64_t B, const Layout& L, char* ws, double off, double co,
+                          const double* diag, int pauli, const double* g, const double* state_in, const double* y,
+                          const double* bias, double inv_bt, double* out, double* grad_x, double* partial, hipStream_t st) {
+    const BwdArgs ba{sh.runs, (long)B, (int)sh.E, (int)sh.blk, reinterpret_cast<const double2*>(ws + L.off_cs), ws + L.off_U,
+                     (int)((sh.blk + 2) * n * kGateBytes), off, co, diag, g, state_in, y, bias, inv_bt, out, grad_x, partial,
+                     pauli, use_tri(), dense_bit(L.nwaves), &reinterpret_cast<WorkspaceHeader*>(ws)->status};
+    const dim3 packed_grid((unsigned)(L.nwaves / kWaves)), group_grid((unsigned)L.nwaves);
+    profile_begin(st);
+    if (k == BwdKernel::Lds) {
+        if (launch_lds_bwd(n, (long)B, st, ba) != QHEA_OK) return QHEA_ELAUNCH;
+    } else switch (n) {
+#define QHEA_CASE(NN) case NN: if (k == BwdKernel::PairTri) launch_bwd_pair_##NN(group_grid, st, ba); else launch_bwd_##NN(packed_grid, st, ba); break;
+        QHEA_FOR_EACH_N(QHEA_CASE)
+#undef QHEA_CASE
+        default: return QHEA_EUNSUPPORTED;
+    }
+    profile_end(st);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 
 int launch_prep(int n, const Shape& sh, int64_t B, const double* w, const double* x, char* ws, const Layout& L,
@@ -1475,10 +1546,7 @@ size_t ensemble_slice_bytes(const ModelInfo& mi, int64_t R, int64_t batch) {
     return a > b ? a : b;
 }
 // whether a step of `batch` rows of an R-member ensemble runs as one launch per kernel (member = blockIdx.y): the ZYZ kernels
-bool ensemble_grid(const ModelInfo& mi, int64_t R, int64_t batch) {
-    const Layout L = make_model_layout(mi, batch, R * batch).L;
-    return L.ztri || L.zpacked;
-}
+bool ensemble_grid(const ModelInfo& mi, int64_t R, int64_t batch) { return make_model_layout(mi, batch, R * batch).L.zyz_bwd; }
 
 // The members' hyper-parameters reach the device as kernel arguments: one launch per kMemberFill members and host call writes
 // each member's MemberRec (hea_zyz.hpp) into its workspace slice -- no pageable copy, nothing retained, capturable.
@@ -1616,35 +1684,16 @@ int qhea_forward(int n_qubits, int n_blocks, const int32_t* enc_per_block, const
     if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    if (L.zfwd) {
+    const FwdKernel k = fwd_kernel_for(L.in, CallTraits{ham_pauli});
+    if (zyz_family(k)) {
         rc = launch_prep_zyz(n_qubits, sh, w, ws, L, st);
         if (rc != QHEA_OK) return rc;
-        profile_begin(st);
-        rc = launch_zyz_forward(n_qubits, sh, batch, L, ws, AngleSrc{x, EncDesc{}}, ham_offset, ham_coeff, ham_diag, ham_pauli,
-                                out, state_out, nullptr, st);
-        profile_end(st);
-        if (rc != QHEA_OK) return rc;
-        return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+        return launch_zyz_forward(k, n_qubits, sh, batch, L, ws, AngleSrc{x, EncDesc{}}, ham_offset, ham_coeff, ham_diag, ham_pauli,
+                                  out, state_out, nullptr, st);
     }
     rc = launch_prep(n_qubits, sh, batch, w, x, ws, L, st);
     if (rc != QHEA_OK) return rc;
-    const dim3 grid((unsigned)(L.nwaves_fwd / kWaves));
-    const double2* cs = reinterpret_cast<const double2*>(ws + L.off_cs);
-    const char* gates = ws + L.off_U;
-    const int gates_bytes = (int)((sh.blk + 2) * n_qubits * kGateBytes);
-    const FwdArgs fa{sh.runs, (long)batch, (int)sh.E, cs, gates, gates_bytes, ham_offset, ham_coeff, ham_diag, out,
-                     state_out, nullptr, ham_pauli};
-    profile_begin(st);
-    if (L.lds_fwd) {
-        if (launch_lds_fwd(n_qubits, (long)batch, st, fa) != QHEA_OK) return QHEA_ELAUNCH;
-    } else switch (n_qubits) {
-#define QHEA_CASE(NN) case NN: launch_fwd_##NN(grid, st, fa); break;
-        QHEA_FOR_EACH_N(QHEA_CASE)
-#undef QHEA_CASE
-        default: return QHEA_EUNSUPPORTED;
-    }
-    profile_end(st);
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+    return launch_table_forward(k, n_qubits, sh, batch, L, ws, ham_offset, ham_coeff, ham_diag, ham_pauli, out, state_out, nullptr, st);
 }
 
 int qhea_backward(int n_qubits, int n_blocks, const int32_t* enc_per_block, const int32_t* ld_per_block,
@@ -1667,49 +1716,25 @@ int qhea_backward(int n_qubits, int n_blocks, const int32_t* enc_per_block, cons
     if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
     char* ws = static_cast<char*>(workspace);
     double* partial = reinterpret_cast<double*>(ws + L.off_part);
-    if (L.ztri || L.zpacked) {
+    const BwdKernel k = bwd_kernel_for(L.in, n_qubits, CallTraits{ham_pauli, state_in != nullptr});
+    if (L.zyz_bwd) {
         rc = launch_prep_zyz(n_qubits, sh, w, ws, L, st);
-        if (rc != QHEA_OK) return rc;
-        profile_begin(st);
-        rc = launch_zyz_backward(n_qubits, sh, batch, L, ws, AngleSrc{x, EncDesc{}}, ham_offset, ham_coeff, ham_diag, ham_pauli,
-                                 g, state_in, nullptr, nullptr, 0.0, out, grad_x, partial, st);
-        profile_end(st);
-        if (rc != QHEA_OK) return rc;
-        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        if (sh.blk > 0) {
-            const int kw = padded_3n(n_qubits);
-            const long ncols = sh.blk * kw;
-            hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((ncols + red_cols(kw) - 1) / red_cols(kw))), dim3(kRedThreads), 0, st,
-                               n_qubits, (int)sh.blk, kw, L.nwaves, partial, w, grad_w,
-                               reinterpret_cast<const WorkspaceHeader*>(ws), reinterpret_cast<const double*>(ws + L.off_gmap));
-        }
-        return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+        if (rc == QHEA_OK)
+            rc = launch_zyz_backward(k, n_qubits, sh, batch, L, ws, AngleSrc{x, EncDesc{}}, ham_offset, ham_coeff, ham_diag,
+                                     ham_pauli, g, state_in, nullptr, nullptr, 0.0, out, grad_x, partial, st);
+    } else {
+        rc = launch_prep(n_qubits, sh, batch, w, x, ws, L, st);
+        if (rc == QHEA_OK)
+            rc = launch_table_backward(k, n_qubits, sh, batch, L, ws, ham_offset, ham_coeff, ham_diag, ham_pauli, g, state_in,
+                                       nullptr, nullptr, 0.0, out, grad_x, partial, st);
     }
-    rc = launch_prep(n_qubits, sh, batch, w, x, ws, L, st);
     if (rc != QHEA_OK) return rc;
-    const dim3 grid((unsigned)(L.nwaves / kWaves));
-    const double2* cs = reinterpret_cast<const double2*>(ws + L.off_cs);
-    const char* gates = ws + L.off_U;
-    const int gates_bytes = (int)((sh.blk + 2) * n_qubits * kGateBytes);
-    const BwdArgs ba{sh.runs, (long)batch, (int)sh.E, (int)sh.blk, cs, gates, gates_bytes, ham_offset, ham_coeff, ham_diag, g,
-                     state_in, nullptr, nullptr, 0.0, out, grad_x, partial, ham_pauli, use_tri(),
-                     L.nwaves > simd_count() ? 1 : 0, &reinterpret_cast<WorkspaceHeader*>(ws)->status};
-    profile_begin(st);
-    if (L.lds_bwd) {
-        if (launch_lds_bwd(n_qubits, (long)batch, st, ba) != QHEA_OK) return QHEA_ELAUNCH;
-    } else switch (n_qubits) {
-#define QHEA_CASE(NN) case NN: if (L.pair) launch_bwd_pair_##NN(dim3((unsigned)L.nwaves), st, ba); else launch_bwd_##NN(grid, st, ba); break;
-        QHEA_FOR_EACH_N(QHEA_CASE)
-#undef QHEA_CASE
-        default: return QHEA_EUNSUPPORTED;
-    }
-    profile_end(st);
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    if (sh.blk > 0) {
-        const long ncols = sh.blk * padded_3n(n_qubits);
-        hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((ncols + red_cols(padded_3n(n_qubits)) - 1) / red_cols(padded_3n(n_qubits)))), dim3(kRedThreads), 0, st,
-                           n_qubits, (int)sh.blk, padded_3n(n_qubits), L.nwaves, partial, w, grad_w,
-                           reinterpret_cast<const WorkspaceHeader*>(ws), static_cast<const double*>(nullptr));
+    if (sh.blk > 0) {       // (the ZYZ kernels' sums are taken before the gate's last RZ: through gmap)
+        const int kw = padded_3n(n_qubits);
+        const long ncols = sh.blk * kw;
+        hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((ncols + red_cols(kw) - 1) / red_cols(kw))), dim3(kRedThreads), 0, st,
+                           n_qubits, (int)sh.blk, kw, L.nwaves, partial, w, grad_w, reinterpret_cast<const WorkspaceHeader*>(ws),
+                           L.zyz_bwd ? reinterpret_cast<const double*>(ws + L.off_gmap) : nullptr);
     }
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
@@ -1741,35 +1766,20 @@ static int model_forward_impl(const qhea_model_desc* desc, int64_t batch, const 
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     const EncDesc enc = make_enc(desc, mi, branch, trunk, params);
-    if (M.L.zfwd) {
+    const double* bias = mi.has_bias ? params + mi.off_bias : nullptr;
+    const FwdKernel k = fwd_kernel_for(M.L.in, CallTraits{desc->ham_pauli});
+    if (zyz_family(k)) {
         if (!records_ready) {
             rc = launch_prep_zyz(mi.n, mi.sh, params + mi.off_ans, ws, M.L, st);
             if (rc != QHEA_OK) return rc;
         }
-        profile_begin(st);
-        rc = launch_zyz_forward(mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
-                                desc->ham_pauli, pred, nullptr, mi.has_bias ? params + mi.off_bias : nullptr, st);
-        profile_end(st);
-        if (rc != QHEA_OK) return rc;
-        return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+        return launch_zyz_forward(k, mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
+                                  desc->ham_pauli, pred, nullptr, bias, st);
     }
     rc = launch_prep_model(mi, batch, params, enc, ws, M.L, st);
     if (rc != QHEA_OK) return rc;
-    const dim3 grid((unsigned)(M.L.nwaves_fwd / kWaves));
-    const FwdArgs fa{mi.sh.runs, (long)batch, (int)mi.sh.E, reinterpret_cast<const double2*>(ws + M.L.off_cs),
-                     ws + M.L.off_U, (int)((mi.sh.blk + 2) * mi.n * kGateBytes), desc->ham_offset, desc->ham_coeff,
-                     ham_diag, pred, nullptr, mi.has_bias ? params + mi.off_bias : nullptr, desc->ham_pauli};
-    profile_begin(st);
-    if (M.L.lds_fwd) {
-        if (launch_lds_fwd(mi.n, (long)batch, st, fa) != QHEA_OK) return QHEA_ELAUNCH;
-    } else switch (mi.n) {
-#define QHEA_CASE(NN) case NN: launch_fwd_##NN(grid, st, fa); break;
-        QHEA_FOR_EACH_N(QHEA_CASE)
-#undef QHEA_CASE
-        default: return QHEA_EUNSUPPORTED;
-    }
-    profile_end(st);
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+    return launch_table_forward(k, mi.n, mi.sh, batch, M.L, ws, desc->ham_offset, desc->ham_coeff, ham_diag, desc->ham_pauli, pred,
+                                nullptr, bias, st);
 }
 
 // the reduce kernel can write the next step's records: ZYZ kernels on a block-unrolled shape whose reduce block (ld x kw
@@ -1779,8 +1789,8 @@ static int model_forward_impl(const qhea_model_desc* desc, int64_t batch, const 
 // block, 8 columns (n = 2 with one sub-layer per block: the shipped Antideriv Q2 Net5-1-5-1 model) are half a reduce block, so
 // two consecutive circuit blocks share one (an even number of blocks is needed).
 static int model_fuse_blocks(const ModelInfo& mi, const Layout& L) {
-    const int ld = zyz_fast_ld(mi.sh.runs, mi.n), kw = padded_3n(mi.n);
-    if (!(L.ztri || L.zpacked) || ld < 1 || ld > kFuseMaxLd || mi.sh.blk % ld != 0) return 0;
+    const int ld = mi.sh.fast_ld, kw = padded_3n(mi.n);
+    if (!L.zyz_bwd || ld < 1 || ld > kFuseMaxLd || mi.sh.blk % ld != 0) return 0;
     const int cols = ld * kw;
     if (cols == 16 || cols == 32) return 1;
     if (cols == 8 && (mi.sh.blk / ld) % 2 == 0) return 2;
@@ -1848,13 +1858,15 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, const StepView& v, 
     double* partial = reinterpret_cast<double*>(ws + M.L.off_part);
     RedBlocks rb = red_blocks(mi.n, mi.sh.blk, mi.sh.E, mi.trainable);
     FusePrep fp{};
-    if (M.L.ztri || M.L.zpacked) {
+    const double* bias = mi.has_bias ? params + mi.off_bias : nullptr;
+    const BwdKernel k = bwd_kernel_for(M.L.in, mi.n, CallTraits{desc->ham_pauli, false, R});
+    if (M.L.zyz_bwd) {
         if (records_for_next) {
             if (!model_fuse_eligible(mi, M.L) || !adam.p) return QHEA_EINVAL;
-            fp.ld = zyz_fast_ld(mi.sh.runs, mi.n);
+            fp.ld = mi.sh.fast_ld;
             fp.nbk = model_fuse_blocks(mi, M.L);
             fp.L = M.L.zL; fp.runs = mi.sh.runs;
-            fp.rec = ws + M.L.off_rec; fp.srec = M.L.zsplit ? ws + M.L.off_srec : nullptr;
+            fp.rec = ws + M.L.off_rec; fp.srec = M.L.srecords ? ws + M.L.off_srec : nullptr;
             fp.gmap = reinterpret_cast<double*>(ws + M.L.off_gmap);
             rb.nb_w = (int)(mi.sh.blk / fp.ld / fp.nbk);        // one reduce block per circuit block (n = 2, ld = 1: per two)
         }
@@ -1863,13 +1875,10 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, const StepView& v, 
             rc = launch_prep_zyz(mi.n, mi.sh, params + mi.off_ans, ws, M.L, st, R, ms);
             if (rc != QHEA_OK) return rc;
         }
-        profile_begin(st);
-        rc = launch_zyz_backward(mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
-                                 desc->ham_pauli, nullptr, nullptr, v.y, mi.has_bias ? params + mi.off_bias : nullptr,
-                                 v.inv_bt, pr, gx, partial, st, R, ms, mlr ? mlr->mrec : nullptr);
-        profile_end(st);
+        rc = launch_zyz_backward(k, mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
+                                 desc->ham_pauli, nullptr, nullptr, v.y, bias, v.inv_bt, pr, gx, partial, st, R, ms,
+                                 mlr ? mlr->mrec : nullptr);
         if (rc != QHEA_OK) return rc;
-        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
         return launch_reduce_model(rb, st, mi, M.L.nwaves, partial, params, v, enc, gx, pr, adam, ws,
                                    reinterpret_cast<const double*>(ws + M.L.off_gmap), fp, dpx, R, ms, mlr);
     }
@@ -1877,25 +1886,10 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, const StepView& v, 
     if (records_ready || records_for_next) return QHEA_EINVAL;
     if (dpx && !dp_blocks_ok(rb.total())) return QHEA_EUNSUPPORTED;
     rc = launch_prep_model(mi, batch, params, enc, ws, M.L, st);
+    if (rc == QHEA_OK)
+        rc = launch_table_backward(k, mi.n, mi.sh, batch, M.L, ws, desc->ham_offset, desc->ham_coeff, ham_diag, desc->ham_pauli,
+                                   nullptr, nullptr, v.y, bias, v.inv_bt, pr, gx, partial, st);
     if (rc != QHEA_OK) return rc;
-    const dim3 grid((unsigned)(M.L.nwaves / kWaves));
-    const BwdArgs ba{mi.sh.runs, (long)batch, (int)mi.sh.E, (int)mi.sh.blk,
-                     reinterpret_cast<const double2*>(ws + M.L.off_cs), ws + M.L.off_U,
-                     (int)((mi.sh.blk + 2) * mi.n * kGateBytes), desc->ham_offset, desc->ham_coeff, ham_diag,
-                     nullptr, nullptr, v.y, mi.has_bias ? params + mi.off_bias : nullptr, v.inv_bt,
-                     pr, gx, partial, desc->ham_pauli, use_tri(), M.L.nwaves > simd_count() ? 1 : 0,
-                     &reinterpret_cast<WorkspaceHeader*>(ws)->status};
-    profile_begin(st);
-    if (M.L.lds_bwd) {
-        if (launch_lds_bwd(mi.n, (long)batch, st, ba) != QHEA_OK) return QHEA_ELAUNCH;
-    } else switch (mi.n) {
-#define QHEA_CASE(NN) case NN: if (M.L.pair) launch_bwd_pair_##NN(dim3((unsigned)M.L.nwaves), st, ba); else launch_bwd_##NN(grid, st, ba); break;
-        QHEA_FOR_EACH_N(QHEA_CASE)
-#undef QHEA_CASE
-        default: return QHEA_EUNSUPPORTED;
-    }
-    profile_end(st);
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
     return launch_reduce_model(rb, st, mi, M.L.nwaves, partial, params, v, enc, gx, pr, adam, ws, nullptr, FusePrep{}, dpx);
 }
 
@@ -1948,17 +1942,18 @@ int qhea_model_forward_chunks(const qhea_model_desc* desc, int64_t n_chunks, con
     // the layer records depend on the parameters alone: one prep launch serves every chunk whose workspace layout keeps
     // them where the last prep put them (chunks of equal size; a shorter last chunk gets its own)
     Layout last{};
-    bool have = false;
+    bool have = false;                  // `last`: where a prep_zyz launch of this call left the records
     for (int64_t i = 0; i < n_chunks; ++i) {
         const int64_t r0 = row_begin[i], nb = row_begin[i + 1] - r0;
         const Layout L = make_model_layout(mi, nb).L;
-        const bool ready = have && L.zfwd && last.zfwd && L.off_rec == last.off_rec && L.off_srec == last.off_srec &&
-                           L.off_gmap == last.off_gmap && L.zsplit == last.zsplit && L.zL == last.zL;
+        const bool zyz = zyz_family(fwd_kernel_for(L.in, CallTraits{desc->ham_pauli}));
+        const bool ready = have && zyz && L.off_rec == last.off_rec && L.off_srec == last.off_srec &&
+                           L.off_gmap == last.off_gmap && L.srecords == last.srecords && L.zL == last.zL;
         const int rc = model_forward_impl(desc, nb, branch + r0 * desc->branch_in,
                                           has_trunk ? trunk + r0 * desc->trunk_in : nullptr, params, ham_diag, pred + r0,
                                           workspace, workspace_bytes, stream, ready);
         if (rc != QHEA_OK) return rc;
-        if (!ready) { last = L; have = true; }
+        if (!ready) { last = L; have = zyz; }
     }
     return QHEA_OK;
 }
@@ -2197,7 +2192,7 @@ static int depth_grid_steps(const DepthSet& ds, int64_t n_models, const qhea_mod
         double* partial = reinterpret_cast<double*>(ws + L.off_part);
         const BwdArgs ba{runs, (long)v.nb, (int)env.sh.E, (int)env.sh.blk, reinterpret_cast<const double2*>(ws + L.off_cs),
                          ws + L.off_U, 0, 0.0, 0.0, nullptr, nullptr, nullptr, v.y, qn ? c.params : nullptr,
-                         v.inv_bt, pr, gx, partial, QHEA_PAULI_Z, 0, n_models * L.nwaves > simd_count() ? 1 : 0,
+                         v.inv_bt, pr, gx, partial, QHEA_PAULI_Z, 0, dense_bit(n_models * L.nwaves),
                          nullptr};
         const dim3 grid((unsigned)(L.nwaves / kWaves), (unsigned)n_models);
         profile_begin(st);
@@ -2566,7 +2561,7 @@ static int qubit_grid_steps(const QubitSet& qs, const QubitPlan& plan, int64_t n
             const int cnt = plan.own_count[n - kQsOwnLo];
             if (cnt == 0) continue;
             const long nw = qs_nwaves(n, v.nb);
-            const BwdArgs ba = bwd_args(n, cnt * nw > simd_count() ? 1 : 0);
+            const BwdArgs ba = bwd_args(n, dense_bit(cnt * nw));
             const QubitArgs q{mrec, ms, QsWork{ws + L.off_list, plan.per, plan.own_begin[n - kQsOwnLo]}};
             const dim3 grid((unsigned)(nw / kWaves), (unsigned)cnt);
             switch (n) {

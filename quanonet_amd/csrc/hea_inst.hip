@@ -76,7 +76,7 @@ void QHEA_CAT(launch_bwd_pair_, QHEA_N)(dim3 grid, hipStream_t st, const BwdArgs
                        a.gates_bytes, a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x,
                        a.partial, a.status);
 #else
-    (void)grid; (void)st; (void)a;      // never selected for n > 5 (hea_api.hip: make_layout)
+    (void)grid; (void)st; (void)a;      // never selected for n > 5 (hea_api.hip: bwd_kernel_for)
 #endif
 }
 

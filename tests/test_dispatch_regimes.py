@@ -1,8 +1,8 @@
 """
 Every kernel QHEA_BWD_AUTO chooses, at the edges where the choice flips, against the C oracle on the whole batch.
 
-``expected(n, cfgs, B, cus, ...)`` restates the automatic choice of hea_api.hip (make_layout and the launchers) in plain
-Python; each case captures the kernels its calls launch (tests/helpers.py: kernel_launches -- stream capture, the graph only
+``expected(n, cfgs, B, cus, ...)`` restates the automatic choice of hea_api.hip (kernel_inputs, then fwd_kernel_for and
+bwd_kernel_for) in plain Python, in their order; each case captures the kernels its calls launch (tests/helpers.py: kernel_launches -- stream capture, the graph only
 read) and asserts they are the ones ``expected`` names, then compares the results with the oracle.  If AUTO changes on
 purpose, the table here changes with it.
 
@@ -10,6 +10,7 @@ purpose, the table here changes with it.
     last group; block-unrolled and ragged shapes; the encoding widths either side of the ZYZ and split-layout limits; depths
     either side of the two-pipelines-per-workgroup LDS limit; n = 6..9 either side of the dense build; n = 10..12
   * read-outs X, Y and a diagonal Hamiltonian in every large-batch family
+  * every forced variant by kernel name at the smallest shapes where the rules can differ
   * model level: model_train_steps (records the reduce kernel wrote) against oracle gradients + torch.optim.Adam, fused
     records on both sides of model_fuse_eligible; model_forward_chunks over 2.5 chunks of 16384 rows
 """
@@ -35,35 +36,35 @@ TOL_MODEL = 1e-9           # model-level rows and parameters
 # ---------------------------------------------------------------------------------------------------------------------
 Regime = namedtuple('Regime', 'fwd bwd pipes dense')
 
-K_WAVES = 2                                  # hea_device.hpp:33 kWaves (the forward / packed waves round up to it)
+K_WAVES = 2                                  # hea_device.hpp kWaves (the forward / packed waves round up to it)
 ZCS_BYTES = 20480                            # hea_zyz.hpp kZCsBytes
 ZTRI2_FIXED = 2 * (4 * 3 * 1024) + 2 * 8 * 1024 + 1024 + 256 + 16 * 15 * 8   # ztri_fixed_lds(kZRingDepth<2> = 8): kBSlots = 4,
                                                                              # kRecBytes = 1024, kAxisRing = 16 (hea_zyz.hpp)
-ZTRI2_LDS_LIMIT = 158 * 1024                 # hea_api.hip:627
+ZTRI2_LDS_LIMIT = 158 * 1024                 # hea_api.hip kernel_inputs: two_fit
 
 
-def lane_bits(n):                            # hea_device.hpp:59
+def lane_bits(n):                            # hea_device.hpp lane_bits
     return n if n < 6 else 6
 
 
-def padded_3n(n):                            # hea_device.hpp:79
+def padded_3n(n):                            # hea_device.hpp padded_3n
     return 8 if 3 * n <= 8 else 16 if 3 * n <= 16 else 32 if 3 * n <= 32 else 64
 
 
-def zyz_eligible(n, E):                      # hea_zyz.hpp:47: the (cos, sin) table of a sample group fits
+def zyz_eligible(n, E):                      # hea_zyz.hpp zyz_eligible: the (cos, sin) table of a sample group fits
     return 2 <= n <= 5 and (64 >> n) * (E + 2 * n) * 16 <= ZCS_BYTES
 
 
-def fast_ld(n, cfgs):                        # hea_zyz.hpp:427 zyz_fast_ld: every block enc = n, one ld in {1, 2}
+def fast_ld(n, cfgs):                        # hea_zyz.hpp zyz_fast_ld (Shape::fast_ld): every block enc = n, one ld in {1, 2}
     ld = cfgs[0][1]
     return ld if ld in (1, 2) and all(e == n and d == ld for e, d in cfgs) else 0
 
 
-def zsplit_eligible(n, E, cfgs):             # hea_zyz.hpp:536
+def zsplit_eligible(n, E, cfgs):             # hea_zyz.hpp zsplit_eligible
     return n == 5 and fast_ld(n, cfgs) != 0 and 2 * (E + 2 * n) * 32 <= ZCS_BYTES
 
 
-def ztri2_lds(n, cfgs):                      # hea_api.hip:624-626: LDS of bwd_ztri_kernel<N, 2>
+def ztri2_lds(n, cfgs):                      # kernel_inputs, two_fit: LDS of bwd_ztri_kernel<N, 2>
     E, blk = O.circuit_sizes(n, cfgs)
     cs = (64 >> n) * (E + 2 * n) * (32 if zsplit_eligible(n, E, cfgs) else 16)
     return 2 * ZTRI2_FIXED + 2 * cs + blk * padded_3n(n) * 8
@@ -72,57 +73,58 @@ def ztri2_lds(n, cfgs):                      # hea_api.hip:624-626: LDS of bwd_z
 def expected(n, cfgs, B, cus, pauli='Z', state=False):
     """Regime(forward kernel, backward kernel, pipelines per workgroup, dense build) of a single-model call on B rows
     under QHEA_BWD_AUTO.  pauli: 'Z' (also a diagonal Hamiltonian), 'X' or 'Y'; state: the backward is given the final
-    state."""
-    simd = 4 * cus                                                        # hea_api.hip:519 simd_count
+    state.  In the order of hea_api.hip: what kernel_inputs leaves for the rules, then fwd_kernel_for, then bwd_kernel_for
+    (single-model call: KernelInputs::single, CallTraits::R == 1)."""
     E, _ = O.circuit_sizes(n, cfgs)
-    if n >= 10:                                                           # :560 use_lds, hea_lds.hip:578
-        return Regime('lds_fwd_kernel', 'lds_bwd_kernel', 1, False)
+    # kernel_inputs
+    simd = 4 * cus                                                        # simd (simd_count)
+    lds = n >= 10                                                         # lds (hea_lds.hip lds_supported)
     spw = 64 >> lane_bits(n)
-    groups = -(-B // spw)                                                 # :580
-    waves = -(-groups // K_WAVES) * K_WAVES                               # :575-576 (forward waves; packed backward rows)
-    pair = n <= 5 and 8 * groups <= 6 * simd                              # :542-554 use_pair
-    zok = zyz_eligible(n, E)                                              # :584
-    fast = zok and fast_ld(n, cfgs) != 0                                  # :594
-    zfwd_shared = fast and waves > simd                                   # :597
-    zfwd = zok and (zfwd_shared or waves <= 2 * simd)                     # :598
-    ztri = zok and pair                                                   # :600
-    zpacked = fast and not pair                                           # :603-604
-    zsplit = zok and zsplit_eligible(n, E, cfgs)                          # :610
-    pipes = 1
-    two_wanted = cus < groups <= 2 * cus                                  # :620-622
-    if ztri and two_wanted and ztri2_lds(n, cfgs) <= ZTRI2_LDS_LIMIT:     # :623-627
-        pipes = 2
-    zquad = ztri and zsplit and pipes == 1 and groups <= cus              # :632
-    zfwd_split = zsplit and zfwd and not zfwd_shared and B <= simd        # :641
-    zsnap = ztri and zsplit and pipes == 2 and two_wanted                 # :650
-    # forward (qhea_forward :1459, launch_zyz_forward :690-715)
-    if zfwd:
-        fwd = ('fwd_split_kernel' if zfwd_split and pauli == 'Z' else
-               'fwd_zshared_kernel' if zfwd_shared else 'fwd_zyz_kernel')
-    else:
+    groups = -(-B // spw)                                                 # groups_d
+    waves = -(-groups // K_WAVES) * K_WAVES                               # fwd_waves_d (also the packed backward's rows)
+    records = zyz_eligible(n, E)                                          # records (AUTO runs the ZYZ kernels)
+    fast = records and fast_ld(n, cfgs) != 0                              # fast
+    srecords = records and zsplit_eligible(n, E, cfgs)                    # srecords
+    two_fit = records and ztri2_lds(n, cfgs) <= ZTRI2_LDS_LIMIT           # two_fit
+    # fwd_kernel_for
+    shared = fast and waves > simd                                        # shared
+    zyz = records and (shared or waves <= 2 * simd)                       # zyz
+    if lds:
+        fwd = 'lds_fwd_kernel'
+    elif not zyz:
         fwd = 'fwd_kernel'
-    # backward (qhea_backward :1510-1545, launch_zyz_backward :732-757, hea_inst.hip launch_bwd_*)
-    dense = False
-    if zpacked:
-        bwd = 'bwd_zpacked_kernel'
-    elif ztri:
-        if zsnap and n == 5 and pauli == 'Z' and not state:               # :741
-            bwd = 'bwd_zsnap_kernel'
-        elif zquad and n == 5 and pauli == 'Z':                           # :746
-            bwd = 'bwd_zquad_kernel'
-        else:
-            bwd = 'bwd_ztri_kernel'
-    elif pair:
-        bwd = 'bwd_tri_kernel'                                            # use_tri(): AUTO is the psi / lambda / sigma form
+    elif shared:
+        fwd = 'fwd_zshared_kernel'
+    elif srecords and B <= simd and pauli == 'Z':                         # split forward; X / Y: the private-ring forward
+        fwd = 'fwd_split_kernel'
     else:
+        fwd = 'fwd_zyz_kernel'
+    # bwd_kernel_for
+    pipes, dense = 1, False
+    pipelined = n <= 5 and 8 * groups <= 6 * simd                         # pipelined
+    auto_two = cus < groups <= 2 * cus                                    # auto_two (= two_wanted, snap_wanted under AUTO)
+    if lds:
+        bwd = 'lds_bwd_kernel'
+    elif fast and not pipelined:
+        bwd = 'bwd_zpacked_kernel'
+    elif not pipelined:
         bwd = 'bwd_kernel'
-        dense = n in (8, 9) and waves > simd                              # :1536 BwdArgs::dense, hea_inst.hip:21
+        dense = n in (8, 9) and waves > simd                              # dense_bit, hea_inst.hip launch_bwd_NN
+    elif not records:
+        bwd = 'bwd_tri_kernel'                                            # use_tri(): AUTO is the psi / lambda / sigma form
+    elif auto_two and two_fit:
+        pipes = 2                                                         # snapshot pipeline; X / Y / given state: ztri<N, 2>
+        bwd = 'bwd_zsnap_kernel' if srecords and n == 5 and pauli == 'Z' and not state else 'bwd_ztri_kernel'
+    elif srecords and groups <= cus and n == 5 and pauli == 'Z':          # quad_wanted; X / Y: ztri<N, 1>
+        bwd = 'bwd_zquad_kernel'
+    else:
+        bwd = 'bwd_ztri_kernel'
     return Regime(fwd, bwd, pipes, dense)
 
 
 def expected_fused(n, cfgs, B, cus):
-    """whether model_train_steps' reduce kernel writes the next step's records (hea_api.hip:1621-1629
-    model_fuse_blocks; steps of equal batch size)"""
+    """whether model_train_steps' reduce kernel writes the next step's records (hea_api.hip model_fuse_blocks; steps of
+    equal batch size)"""
     r = expected(n, cfgs, B, cus)
     if r.bwd not in ('bwd_ztri_kernel', 'bwd_zpacked_kernel', 'bwd_zsnap_kernel', 'bwd_zquad_kernel'):
         return False
@@ -181,8 +183,8 @@ for _n in (2, 3, 4, 5):
     for _sn, _cfgs in _shapes(_n).items():
         for _lab, _bf in _batch_edges(_n):
             CIRCUIT_CASES.append((f'n{_n}-{_sn}-{_lab}', _n, _cfgs, _bf, ('Z',)))
-# encoding widths either side of the ZYZ limit (hea_zyz.hpp:47: E <= 76 / 154 / 312 / 630) and the split limit (n = 5,
-# :536: E <= 310), in blocks of enc = n
+# encoding widths either side of the ZYZ limit (zyz_eligible: E <= 76 / 154 / 312 / 630) and the split limit (n = 5,
+# zsplit_eligible: E <= 310), in blocks of enc = n
 for _n, _nbs in ((2, (38, 39)), (3, (51, 52)), (4, (78, 79)), (5, (62, 63, 126, 127))):
     for _nb in _nbs:
         for _lab, _bf in (('pipelined', lambda c: 300), ('groups=3cus+1', lambda c, n=_n: 3 * c * (64 >> n) + 1)):
@@ -209,7 +211,7 @@ CIRCUIT_CASES += [
 
 
 def _depth_cases():
-    """two depths either side of the zpipes = 2 LDS limit (hea_api.hip:624-627), inside the two-pipeline batch range:
+    """two depths either side of the two-pipeline LDS limit (kernel_inputs: two_fit), inside the two-pipeline batch range:
     two blocks of depth D (not block-unrolled for D > 2)"""
     out = []
     for n in (5, 3):
@@ -294,6 +296,90 @@ def test_circuit_regime_matches_oracle(dev, cus, case):
             got = _capture_circuit(dev, n, cfgs, B, ro, state)
             assert got == expected(n, cfgs, B, cus, pauli, state), (ro, state, got)
         _lib.check_status(dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# forced variants (qhea_set_backward_variant): the kernels by name at the smallest shapes where the rules can differ
+# ---------------------------------------------------------------------------------------------------------------------
+FORCED_VARIANTS = ('packed', 'pair', 'tri', 'ztri', 'zpacked', 'ztri2', 'zquad', 'zsnap')
+_U5 = [(5, 2)] * 2         # block-unrolled and split-eligible; B = 3 is one and a half sample groups
+FORCED_SHAPES = {          # id: (n, cfgs, B, read-out, backward given the final state)
+    'q5': (5, _U5, 3, 'Z', False),
+    'q5-X': (5, _U5, 3, 'X', False),                       # X read-out: zsnap / zquad / split forward fall back
+    'q5-state': (5, _U5, 3, 'Z', True),                    # given final state: zsnap falls back
+    'q3-ragged': (3, [(3, 1), (2, 2)], 9, 'Z', False),     # no fast ld: zpacked and zquad fall back
+    'q6': (6, [(6, 1)], 2, 'Z', False),                    # no pipelined or ZYZ kernel exists
+}
+# Regime per variant and shape as the library of the commit BEFORE the kernel rules were gathered into fwd_kernel_for /
+# bwd_kernel_for launched them on an MI355X (recorded, not derived from the code under test)
+FORCED_EXPECTED = {
+    'packed': {'q5': ('fwd_kernel', 'bwd_kernel', 1, False), 'q5-X': ('fwd_kernel', 'bwd_kernel', 1, False),
+               'q5-state': ('fwd_kernel', 'bwd_kernel', 1, False), 'q3-ragged': ('fwd_kernel', 'bwd_kernel', 1, False),
+               'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+    'pair': {'q5': ('fwd_kernel', 'bwd_pair_kernel', 1, False), 'q5-X': ('fwd_kernel', 'bwd_pair_kernel', 1, False),
+             'q5-state': ('fwd_kernel', 'bwd_pair_kernel', 1, False), 'q3-ragged': ('fwd_kernel', 'bwd_pair_kernel', 1, False),
+             'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+    'tri': {'q5': ('fwd_kernel', 'bwd_tri_kernel', 1, False), 'q5-X': ('fwd_kernel', 'bwd_tri_kernel', 1, False),
+            'q5-state': ('fwd_kernel', 'bwd_tri_kernel', 1, False), 'q3-ragged': ('fwd_kernel', 'bwd_tri_kernel', 1, False),
+            'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+    'ztri': {'q5': ('fwd_split_kernel', 'bwd_ztri_kernel', 1, False), 'q5-X': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 1, False),
+             'q5-state': ('fwd_split_kernel', 'bwd_ztri_kernel', 1, False), 'q3-ragged': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 1, False),
+             'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+    'zpacked': {'q5': ('fwd_zshared_kernel', 'bwd_zpacked_kernel', 1, False), 'q5-X': ('fwd_zshared_kernel', 'bwd_zpacked_kernel', 1, False),
+                'q5-state': ('fwd_zshared_kernel', 'bwd_zpacked_kernel', 1, False), 'q3-ragged': ('fwd_zyz_kernel', 'bwd_kernel', 1, False),
+                'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+    'ztri2': {'q5': ('fwd_split_kernel', 'bwd_ztri_kernel', 1, False), 'q5-X': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 1, False),
+              'q5-state': ('fwd_split_kernel', 'bwd_ztri_kernel', 1, False), 'q3-ragged': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 1, False),
+              'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+    'zquad': {'q5': ('fwd_split_kernel', 'bwd_zquad_kernel', 1, False), 'q5-X': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 1, False),
+              'q5-state': ('fwd_split_kernel', 'bwd_zquad_kernel', 1, False), 'q3-ragged': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 1, False),
+              'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+    'zsnap': {'q5': ('fwd_split_kernel', 'bwd_zsnap_kernel', 2, False), 'q5-X': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 2, False),
+              'q5-state': ('fwd_split_kernel', 'bwd_ztri_kernel', 2, False), 'q3-ragged': ('fwd_zyz_kernel', 'bwd_ztri_kernel', 2, False),
+              'q6': ('fwd_kernel', 'bwd_kernel', 1, False)},
+}
+_FORCED_REF = {}
+
+
+def _forced_reference(shape):
+    """inputs and oracle results of one forced-variant shape, computed once"""
+    if shape not in _FORCED_REF:
+        n, cfgs, B, ro, _ = FORCED_SHAPES[shape]
+        E, blk = O.circuit_sizes(n, cfgs)
+        rng = np.random.default_rng(sorted(FORCED_SHAPES).index(shape))
+        x = rng.uniform(-np.pi, np.pi, (B, E)); w = rng.uniform(-np.pi, np.pi, (blk, 3, n)); g = rng.normal(size=B)
+        off, co = O.ham_params(n, -2.0, 3.0)
+        ref_out, ref_st = C.hea_forward(n, cfgs, x, w, off, co, None, return_state=True, ham_pauli=ro)
+        _, ref_gx, ref_gw = C.hea_backward(n, cfgs, x, w, g, off, co, None, ham_pauli=ro)
+        _FORCED_REF[shape] = (x, w, g, off, co, ref_out, ref_st, ref_gx, ref_gw)
+    return _FORCED_REF[shape]
+
+
+@pytest.mark.parametrize('shape', list(FORCED_SHAPES))
+@pytest.mark.parametrize('variant', FORCED_VARIANTS)
+def test_forced_variant_kernels_and_oracle(dev, variant, shape):
+    from quanonet_amd import _lib
+    n, cfgs, B, ro, state = FORCED_SHAPES[shape]
+    x, w, g, off, co, ref_out, ref_st, ref_gx, ref_gw = _forced_reference(shape)
+    sh = _lib.CircuitShape(n, cfgs)
+    xd, wd, gd = _t(dev, x), _t(dev, w), _t(dev, g)
+    _lib.set_backward_variant(variant)
+    try:
+        out, st = _lib.hea_forward(sh, xd, wd, off, co, None, return_state=True, ham_pauli=ro)
+        if state:
+            (gx, gw), out2 = _lib.hea_backward(sh, xd, wd, gd, off, co, None, state=st, ham_pauli=ro), out
+        else:
+            gx, gw, out2 = _lib.hea_backward(sh, xd, wd, gd, off, co, None, want_out=True, ham_pauli=ro)
+        _lib.check_status(dev)
+        got = _capture_circuit(dev, n, cfgs, B, ro, state)
+    finally:
+        _lib.set_backward_variant('auto')
+    assert got == Regime(*FORCED_EXPECTED[variant][shape]), got
+    np.testing.assert_allclose(out.cpu().numpy(), ref_out, rtol=0, atol=TOL, err_msg='out')
+    np.testing.assert_allclose(st.cpu().numpy(), ref_st, rtol=0, atol=TOL, err_msg='state')
+    np.testing.assert_allclose(out2.cpu().numpy(), ref_out, rtol=0, atol=TOL, err_msg='backward out')
+    np.testing.assert_allclose(gx.cpu().numpy(), ref_gx, rtol=0, atol=TOL, err_msg='grad_x')
+    np.testing.assert_allclose(gw.cpu().numpy(), ref_gw, rtol=0, atol=TOL_W, err_msg='grad_w')
 
 
 # ---------------------------------------------------------------------------------------------------------------------
