@@ -287,6 +287,44 @@ int    qhea_model_forward_noisy(const qhea_model_desc* desc, int64_t row0, int64
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Noisy forward for n = 7..12: the quantity of qhea_model_forward_noisy, word for word -- its noise model, location order,
+ * estimators, read-outs, stderr_out and arguments -- for the qubit counts where a state no longer sits one amplitude per lane.
+ * Random numbers: unchanged.  Philox4x32-10, counter = (call, trajectory, row_lo, row_hi) with the global row index; the
+ * per-location words and the shot-mode words of call m = ceil(L / 2) onward are those stated above (the readout-flip rule
+ * reaches call m + 3 at n = 12).
+ * Summation, each order a function of n and the number of values per row only:
+ *   1. a row's values go in tiles of 64 trajectories; a row's tile sums are added in tile order;
+ *   2. inside a tile the trajectories are added in trajectory order;
+ *   3. read-out sum_k p_k h(k) (h = the folded read-out, with ham_diag the table diag' built bit by bit,
+ *      h <- (1 - q) h + q h[k ^ 2^i] for i = 0..n-1):
+ *        n = 7..9:   per lane l (0..63) the terms k = l + 64 r in the order r = 0, 1, ..; then the 64 lane sums by the xor
+ *                    butterfly, offsets 32, 16, 8, 4, 2, 1 (lane l adds lane l ^ offset);
+ *        n = 10..12: per thread t (0 .. 2^(n-4) - 1) the terms k = 16 t + j in the order j = 0..15; then the butterfly over
+ *                    each group of 64 threads, then the groups in order;
+ *   4. shot mode, cdf[k] = below(k) + scan(k):
+ *        n = 7..9:   blocks of 64 consecutive k; scan = the Hillis-Steele inclusive scan of |psi_k|^2 over the block
+ *                    (distances 1, 2, .. 32; position i adds position i - d when i >= d); below = the blocks' totals (scan at
+ *                    the block's last position) added in block order from 0;
+ *        n = 10..12: chunks of 16 consecutive k; scan = the chunk's running sum in index order; below = the totals of the
+ *                    earlier groups of 64 chunks added in order from 0, plus the Hillis-Steele inclusive scan of the chunk totals
+ *                    over the group at the chunk before this one (0 for a group's first chunk);
+ *      the outcome is the first k with u < cdf[k]; if there is none, the last k with |psi_k|^2 > 0.
+ * No floating-point atomics; results are bitwise reproducible and the same for any chunking.
+ * Scope: n = 7..12, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.  n <= 6 is QHEA_EUNSUPPORTED:
+ * qhea_model_forward_noisy is the implementation for those sizes.  Every other error is the call's above (and QHEA_EINVAL for
+ * batch * ceil(values / 64) > 2^31 - 1: a launch has one work item per row and tile), all before anything is launched.  Launches: the prep kernel, (ham_diag in expectation mode: the kernel that builds diag',) the trajectory kernel,
+ * the finishing kernel; no allocation, no synchronisation (hipGraph-capturable).
+ */
+/* DEVICE scratch bytes for qhea_model_forward_noisy_wide on `batch` rows (0 on a bad descriptor or noise setting, or n <= 6). */
+size_t qhea_model_noisy_wide_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise);
+int    qhea_model_forward_noisy_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                     const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                     const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                     const qhea_noise* noise /*HOST*/,
+                                     double* pred /*DEVICE [B]*/, double* stderr_out /*DEVICE [B] or NULL*/,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Exact noisy forward: the two deterministic quantities the Monte-Carlo call above estimates, computed by carrying the density
  * matrix through the circuit.  The noise model is the one stated for qhea_model_forward_noisy (p1, p2, readout of `noise`;
  * its shots, trajectories and seed are ignored).

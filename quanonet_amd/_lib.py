@@ -35,6 +35,7 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_depth_sweep_workspace_bytes', 'qhea_model_depth_sweep_train_steps',
            'qhea_model_qubit_sweep_workspace_bytes', 'qhea_model_qubit_sweep_train_steps',
            'qhea_model_noisy_workspace_bytes', 'qhea_model_forward_noisy',
+           'qhea_model_noisy_wide_workspace_bytes', 'qhea_model_forward_noisy_wide',
            'qhea_model_exact_noisy_workspace_bytes', 'qhea_model_forward_noisy_exact',
            'qhea_model_exact_noisy_grad_workspace_bytes', 'qhea_model_exact_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact']
@@ -61,7 +62,7 @@ class NoiseParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 520           # 0.5.2: + qhea_model_loss_grad_noisy_exact / qhea_model_train_steps_noisy_exact (noise-aware training)
+MIN_LIB_VERSION = 530           # 0.5.3: + qhea_model_forward_noisy_wide (noisy evaluation at n = 7..12)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -199,6 +200,10 @@ def load():
     lib.qhea_model_forward_noisy.restype = ctypes.c_int
     lib.qhea_model_forward_noisy.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, dp, dp, dp, dp, npp, dp, dp, vp,
                                              ctypes.c_size_t, vp]
+    lib.qhea_model_noisy_wide_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_wide_workspace_bytes.argtypes = lib.qhea_model_noisy_workspace_bytes.argtypes
+    lib.qhea_model_forward_noisy_wide.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy_wide.argtypes = lib.qhea_model_forward_noisy.argtypes
     lib.qhea_model_exact_noisy_workspace_bytes.restype = ctypes.c_size_t
     lib.qhea_model_exact_noisy_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
     lib.qhea_model_forward_noisy_exact.restype = ctypes.c_int
@@ -712,13 +717,11 @@ def model_dp_train_steps(desc, bounds, global_batches, branch, trunk, y, params,
     return rows
 
 
-def model_forward_noisy(desc, branch, trunk, params, noise, row0=0, ham_diag=None, out=None, stderr=None):
-    """
-    qhea_model_forward_noisy on all rows of branch / trunk in ONE call: (pred[B], stderr[B] or None).  `noise` is a NoiseParams;
-    row0 is the global index of the first row (the random streams are keyed by it).  Raises Unsupported for n >= 7 and
-    QheaError for a bad noise setting -- in both cases before anything is launched.
-    """
+def _forward_noisy(wide, desc, branch, trunk, params, noise, row0, ham_diag, out, stderr):
+    """The two trajectory entry points share one argument list: qhea_model_forward_noisy (n <= 6) and ..._noisy_wide (n >= 7)."""
     lib = load()
+    tag, refused = ('noisy_wide', 'n <= 6') if wide else ('noisy', 'n >= 7')
+    entry = f'qhea_model_forward_{tag}'
     B = branch.shape[0]
     _dev_f64(branch, 'branch', (B, desc.branch_in))
     if desc.model == MODEL_QUANONET:
@@ -726,17 +729,36 @@ def model_forward_noisy(desc, branch, trunk, params, noise, row0=0, ham_diag=Non
     _dev_f64(params, 'params')
     _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
     pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
+    ws_bytes = getattr(lib, f'qhea_model_{tag}_workspace_bytes')
     with torch.cuda.device(branch.device):
-        nbytes = int(lib.qhea_model_noisy_workspace_bytes(ctypes.byref(desc), int(B), ctypes.byref(noise)))
+        nbytes = int(ws_bytes(ctypes.byref(desc), int(B), ctypes.byref(noise)))
     ws = _workspace(branch.device, nbytes) if nbytes else None
     with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_forward_noisy(ctypes.byref(desc), int(row0), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
-                                          _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(stderr), _ptr(ws),
-                                          0 if ws is None else ws.numel(), _stream(branch.device))
+        rc = getattr(lib, entry)(ctypes.byref(desc), int(row0), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
+                                 _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(stderr), _ptr(ws),
+                                 0 if ws is None else ws.numel(), _stream(branch.device))
     if rc == -2:
-        raise Unsupported("qhea_model_forward_noisy: unsupported circuit (n >= 7)")
-    _check(rc, 'qhea_model_forward_noisy')
+        raise Unsupported(f"{entry}: unsupported circuit ({refused})")
+    _check(rc, entry)
     return pred, stderr
+
+
+def model_forward_noisy(desc, branch, trunk, params, noise, row0=0, ham_diag=None, out=None, stderr=None):
+    """
+    qhea_model_forward_noisy on all rows of branch / trunk in ONE call: (pred[B], stderr[B] or None).  `noise` is a NoiseParams;
+    row0 is the global index of the first row (the random streams are keyed by it).  Raises Unsupported for n >= 7 and
+    QheaError for a bad noise setting -- in both cases before anything is launched.
+    """
+    return _forward_noisy(False, desc, branch, trunk, params, noise, row0, ham_diag, out, stderr)
+
+
+def model_forward_noisy_wide(desc, branch, trunk, params, noise, row0=0, ham_diag=None, out=None, stderr=None):
+    """
+    qhea_model_forward_noisy_wide: model_forward_noisy for n = 7..12 -- the same arguments, quantity and random streams.  Raises
+    Unsupported for n <= 6 (model_forward_noisy is the path for those) and QheaError for a bad noise setting, both before
+    anything is launched.
+    """
+    return _forward_noisy(True, desc, branch, trunk, params, noise, row0, ham_diag, out, stderr)
 
 
 def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None, out=None, shot_std=None):

@@ -1611,7 +1611,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 520; }
+int qhea_version(void) { return 530; }
 
 const char* qhea_strerror(int code) {
     switch (code) {

@@ -27,94 +27,14 @@
 // the barriers keep from overlapping with the arithmetic when only one workgroup fits a CU (backward, n = 12).
 // Measured, cfg 5 (n = 12, Net40-2-20-2, B = 1024): forward 1.90 ms, forward + backward 8.47 ms (the previous
 // gate-pair-per-pass LDS kernels: 6.6 / 21.8 ms).
-#include "hea_device.hpp"
+#include "hea_lds.hpp"
 #include "hea_qsweep.hpp"
 
 namespace qhea {
 
 namespace {
 
-struct c2 { double x, y; };
-
-constexpr int kFwdLG = 4;      // gate qubits per pass (see LCfg): forward kernel
-#ifndef QHEA_LDS_BWD_LG
-#define QHEA_LDS_BWD_LG 3
-#endif
-constexpr int kBwdLG = QHEA_LDS_BWD_LG;      // backward kernel
-
-// LG = log2(amplitudes a thread holds per pass) = gate qubits per pass.  Forward kernel: 4 (256 threads at n = 12,
-// two workgroups per CU).  Backward kernel: 3 (512 threads at n = 12, 248 VGPRs): psi + lambda fill the LDS, so one
-// workgroup per CU, and the larger workgroup gives two waves per SIMD at the price of a fourth pass per layer --
-// measured the two cancel almost exactly (forward + backward, LG = 3 / 4: n = 10 193 / 200 us, n = 11 410 / 415 us
-// per 12 sub-layers, cfg 5 8.46 / 8.47 ms), LG = 3 kept.
-template <int N, int LG>
-struct LCfg {
-    static_assert(N >= 10 && N <= 12, "workgroup-resident kernels: n = 10..12");
-    static_assert(LG == 3 || LG == 4, "3 or 4 gate qubits per pass");
-    static constexpr int M = 1 << LG;                 // amplitudes per thread and pass
-    static constexpr int T = 1 << (N - LG);           // threads per sample
-    static constexpr int NW = T / 64;                 // waves
-    static constexpr int NP = (N + LG - 1) / LG;      // passes per gate layer
-    static constexpr int DIM = 1 << N;
-    static constexpr int KW = Cfg<N>::KW;             // padded 3n = row width of `partial` (reduce_kernel)
-    static constexpr size_t STATE_BYTES = (size_t)16 << N;
-    static constexpr size_t SCRATCH_BYTES = (size_t)NW * 64 * sizeof(double) + 16 * sizeof(double4);   // sums + gate table
-};
-template <int N, int P, int LG>
-struct Pass {
-    static constexpr int Q0 = LG * P;                                  // gate qubits [Q0, Q1)
-    static constexpr int Q1 = (LG * P + LG < N) ? LG * P + LG : N;
-    static constexpr int A = (LG * P + LG <= N) ? LG * P : N - LG;     // lowest of the LG index bits held per thread
-};
-
-// Which passes need a workgroup barrier between them.  thread_part maps the lane bits of a thread (t bits 0..5) and
-// the pass's LG local bits onto index bits [0, 6 + LG) whenever A <= 6, and the wave number onto the bits above: the
-// passes with A <= 6 (LG = 3: A = 0, 3, 6; LG = 4: A = 0, 4) all work on the SAME 2^(6+LG) amplitudes per wave.  Between
-// two of them only the wave's own LDS accesses have to stay in order -- which the LDS pipe does for one wave's
-// instructions -- so the waves of a workgroup drift apart there and one wave's LDS round trip overlaps another's
-// arithmetic (with a barrier after every pass all waves load, compute and store in step: no overlap with one
-// workgroup per CU).  Only the last pass (index bits above 6 + LG) exchanges amplitudes between waves.
-template <int N, int LG, int PA, int PB>
-constexpr bool wave_local_passes() { return Pass<N, PA, LG>::A <= 6 && Pass<N, PB, LG>::A <= 6; }
-template <bool WAVE_LOCAL>
-__device__ __forceinline__ void pass_sync() {
-    if constexpr (WAVE_LOCAL) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // compiler ordering only: stores before ...
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");       // ... the next pass's loads
-    } else {
-        __syncthreads();
-    }
-}
-
-// LDS index swizzle (an involution, linear over GF(2)): whatever the pass, the 16-byte accesses of 16 neighbouring
-// lanes fall into 16 different bank quads.  LG = 4: bits 0..3 ^= bits 4..7.  LG = 3 (passes at bits 0, 3, 6, 9 or a
-// ragged last one): bits 0..2 ^= bits 4..6 and bit 3 ^= bit 6.
-template <int LG>
-__host__ __device__ constexpr int phys(int k) {
-    return LG == 4 ? (k ^ ((k >> 4) & 15)) : (k ^ ((k >> 4) & 7) ^ (((k >> 6) & 1) << 3));
-}
-// CNOT ring as a map of basis indices: |k> -> |ring(k)>, CNOT(control (i+1)%n, target i) for i = 0..n-1 in order
-template <int N>
-__host__ __device__ constexpr int ring_dst(int k) {
-    for (int i = 0; i < N; ++i) k ^= ((k >> ((i + 1) % N)) & 1) << i;
-    return k;
-}
-// index bits of thread t for a pass with base bit A (the LG bits A..A+LG-1 are the per-thread local index j)
-template <int A, int LG>
-__device__ __forceinline__ int thread_part(int t) { return ((t >> A) << (A + LG)) | (t & ((1 << A) - 1)); }
-
-// [[a,b],[-conj b, conj a]] on (p0,p1); u = (ar, ai, br, bi)
-__device__ __forceinline__ void su2(c2& p0, c2& p1, const double4& u) {
-    const c2 a0 = p0, a1 = p1;
-    p0.x = u.x * a0.x - u.y * a0.y + u.z * a1.x - u.w * a1.y;
-    p0.y = u.x * a0.y + u.y * a0.x + u.z * a1.y + u.w * a1.x;
-    p1.x = u.x * a1.x + u.y * a1.y - u.z * a0.x - u.w * a0.y;
-    p1.y = u.x * a1.y - u.y * a1.x - u.z * a0.y + u.w * a0.x;
-}
-__device__ __forceinline__ double4 dagger(double4 u) { return make_double4(u.x, -u.y, -u.z, -u.w); }
-// RX as an SU(2) in the same form: a = c, b = -i s  ->  (c, 0, 0, -s)
-__device__ __forceinline__ double4 rx_su2(double2 cs) { return make_double4(cs.x, 0.0, 0.0, -cs.y); }
+// the pass layout (LCfg, Pass, Bases), phys, ring_dst and load_group / apply_group / store_group: hea_lds.hpp
 
 // merge_rx / rotated_x_axis (the RX fold) are shared with the wave-resident kernels: hea_device.hpp
 
@@ -137,47 +57,6 @@ __device__ __forceinline__ void inner(const c2& p0, const c2& p1, const c2& l0, 
     Y = fma(-l0.x, p1.x, Y); Y = fma(-l0.y, p1.y, Y); Y = fma(l1.x, p0.x, Y); Y = fma(l1.y, p0.y, Y);
     Z = fma(l0.x, p0.y, Z); Z = fma(-l0.y, p0.x, Z); Z = fma(-l1.x, p1.y, Z); Z = fma(l1.y, p1.x, Z);
 }
-
-// the 2^LG amplitudes of this thread for a pass with base bit A: local index j <-> index bits A..A+LG-1.
-// `base` = phys(thread_part) (in place) or phys(ring(thread_part)) (through the ring); both maps are linear
-// over GF(2), so amplitude j sits at base ^ constant_j.
-template <int N, int A, bool RING, int LG>
-__device__ __forceinline__ void load_group(const double2* s, int base, c2 (&v)[1 << LG]) {
-    static_for<0, (1 << LG)>([&](auto jj) {
-        constexpr int J = decltype(jj)::value;
-        constexpr int CJ = RING ? phys<LG>(ring_dst<N>(J << A)) : phys<LG>(J << A);
-        const double2 a = s[base ^ CJ];
-        v[J].x = a.x; v[J].y = a.y;
-    });
-}
-template <int N, int A, bool RING, int LG>
-__device__ __forceinline__ void store_group(double2* s, int base, const c2 (&v)[1 << LG]) {
-    static_for<0, (1 << LG)>([&](auto jj) {
-        constexpr int J = decltype(jj)::value;
-        constexpr int CJ = RING ? phys<LG>(ring_dst<N>(J << A)) : phys<LG>(J << A);
-        s[base ^ CJ] = make_double2(v[J].x, v[J].y);
-    });
-}
-template <int LBIT, int LG>
-__device__ __forceinline__ void apply_group(c2 (&v)[1 << LG], const double4& u) {
-    static_for<0, (1 << LG)>([&](auto jj) {
-        constexpr int J = decltype(jj)::value;
-        if constexpr (!(J & (1 << LBIT))) su2(v[J], v[J | (1 << LBIT)], u);
-    });
-}
-
-template <int N, int LG>
-struct Bases {                        // per-thread LDS index bases, computed once per kernel
-    int plain[LCfg<N, LG>::NP];       // phys(thread_part<A_p>(t))
-    int ring;                         // phys(ring(thread_part<A_last>(t)))
-    __device__ __forceinline__ void init(int t) {
-        static_for<0, LCfg<N, LG>::NP>([&](auto p) {
-            constexpr int P = decltype(p)::value;
-            plain[P] = phys<LG>(thread_part<Pass<N, P, LG>::A, LG>(t));
-        });
-        ring = phys<LG>(ring_dst<N>(thread_part<Pass<N, LCfg<N, LG>::NP - 1, LG>::A, LG>(t)));
-    }
-};
 
 // One forward gate layer.  gate(q, u) fills u and returns whether qubit q has a gate (wave-uniform).
 // RING: the last pass scatters through the CNOT ring.

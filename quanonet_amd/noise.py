@@ -1,5 +1,5 @@
 """
-Evaluation of trained models under gate noise, readout error and finite shots (qhea_model_forward_noisy): the deployment
+Evaluation of trained models under gate noise, readout error and finite shots (qhea_model_forward_noisy, n <= 12): the deployment
 questions of the reference's ibm_inference.py -- how many shots a model needs, what gate error rate it tolerates -- answered
 on the GPU before any QPU time is spent.  The noise model, the estimators and the random-number layout are stated in
 include/quanonet_hea.h.
@@ -82,7 +82,8 @@ def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
     Predictions of a fp64 QuanONetPT / HEAQNNPT on a HIP device under `noise` (a NoiseModel): (pred [N, 1], stderr [N]).
     inputs: (branch, trunk) for QuanONet, (x,) or x for HEAQNN.  Rows go in chunks of `chunk_rows`; chunk i passes its global
     index row0 + i * chunk_rows, so the result is bitwise the same for any chunking.  Parameters in model.parameters() order
-    (the flat layout of the header), ham_diag as the trainer takes it.
+    (the flat layout of the header), ham_diag as the trainer takes it.  n <= 6 runs qhea_model_forward_noisy, n = 7..12
+    qhea_model_forward_noisy_wide: one quantity, one random stream, one code path per n.
     """
     desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'noisy_predict')
     N = branch.shape[0]
@@ -90,10 +91,11 @@ def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
     stderr = torch.empty(N, dtype=torch.float64, device=branch.device)
     chunk = max(1, int(chunk_rows))
     nz = noise.params()
+    forward = _lib.model_forward_noisy_wide if desc.n_qubits >= 7 else _lib.model_forward_noisy
     for s in range(0, N, chunk):
         e = min(N, s + chunk)
-        _lib.model_forward_noisy(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, row0=int(row0) + s,
-                                 ham_diag=ham_diag, out=pred[s:e], stderr=stderr[s:e])
+        forward(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, row0=int(row0) + s, ham_diag=ham_diag,
+                out=pred[s:e], stderr=stderr[s:e])
     return pred.unsqueeze(-1), stderr
 
 
