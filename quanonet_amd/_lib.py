@@ -272,6 +272,14 @@ def _model_ws(desc, rows, device):
     return _workspace(device, nbytes)
 
 
+def _sized_ws(device, size_fn, *args):
+    """The workspace a size function asks for, queried with `device` current; None where it answers 0 (the call that follows
+    then reports what is wrong with its arguments)."""
+    with torch.cuda.device(device):
+        nbytes = int(size_fn(*args))
+    return _workspace(device, nbytes) if nbytes else None
+
+
 def _workspace(device, nbytes):
     """Grow-only per-device scratch tensor (caller-owned from the C ABI's point of view)."""
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
@@ -368,6 +376,17 @@ def make_model_desc(model, n_qubits, net_size, branch_in, trunk_in, trainable_fr
     return d
 
 
+def _model_inputs(desc, branch, trunk, params, ham_diag):
+    """What every model-level call checks of its inputs; returns the row count."""
+    B = branch.shape[0]
+    _dev_f64(branch, 'branch', (B, desc.branch_in))
+    if desc.model == MODEL_QUANONET:
+        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
+    _dev_f64(params, 'params')
+    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    return B
+
+
 def model_param_count(desc):
     n = int(load().qhea_model_param_count(ctypes.byref(desc)))
     if n < 0:
@@ -377,12 +396,7 @@ def model_param_count(desc):
 
 def model_forward(desc, branch, trunk, params, ham_diag=None, out=None):
     lib = load()
-    B = branch.shape[0]
-    _dev_f64(branch, 'branch', (B, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
-    _dev_f64(params, 'params')
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
     pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
     ws = _model_ws(desc, B, branch.device)
     with torch.cuda.device(branch.device):
@@ -396,12 +410,7 @@ def model_forward_chunks(desc, branch, trunk, params, chunk, ham_diag=None, out=
     """model_forward over all rows in chunks of `chunk` rows from ONE host call: one record preparation for all equal-sized
     chunks (qhea_model_forward_chunks); bitwise the chunk-by-chunk calls."""
     lib = load()
-    N = branch.shape[0]
-    _dev_f64(branch, 'branch', (N, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (N, desc.trunk_in))
-    _dev_f64(params, 'params')
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    N = _model_inputs(desc, branch, trunk, params, ham_diag)
     pred = out if out is not None else torch.empty(N, dtype=torch.float64, device=branch.device)
     if N == 0:
         return pred
@@ -419,16 +428,11 @@ def model_forward_chunks(desc, branch, trunk, params, chunk, ham_diag=None, out=
 def model_loss_grad(desc, branch, trunk, y, params, inv_batch_total, grad, ham_diag=None, pred=None):
     """Fills grad[P+2] = [d loss/d params | sse | sum y^2] for this shard; returns grad."""
     lib = load()
-    B = branch.shape[0]
-    _dev_f64(branch, 'branch', (B, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(y, 'y')
     if y.numel() != B:
         raise QheaError(f"y has {y.numel()} elements, expected {B}")
-    _dev_f64(params, 'params')
     _dev_f64(grad, 'grad')
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
     _dev_f64(pred, 'pred', (B,))
     ws = _model_ws(desc, B, branch.device)
     with torch.cuda.device(branch.device):
@@ -443,18 +447,14 @@ def model_train_step(desc, branch, trunk, y, params, inv_batch_total, grad, exp_
                      beta2, eps, weight_decay, ham_diag=None, pred=None):
     """Single-device step: loss + gradients + Adam update of `params` in three launches; returns grad."""
     lib = load()
-    B = branch.shape[0]
-    _dev_f64(branch, 'branch', (B, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(y, 'y')
     if y.numel() != B:
         raise QheaError(f"y has {y.numel()} elements, expected {B}")
-    for t, nm in ((params, 'params'), (grad, 'grad'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+    for t, nm in ((grad, 'grad'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
         _dev_f64(t, nm)
     if not (exp_avg.numel() == exp_avg_sq.numel() == params.numel() and grad.numel() == params.numel() + 2):
         raise QheaError("model_train_step: flat vectors have inconsistent lengths")
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
     _dev_f64(pred, 'pred', (B,))
     ws = _model_ws(desc, B, branch.device)
     with torch.cuda.device(branch.device):
@@ -722,17 +722,10 @@ def _forward_noisy(wide, desc, branch, trunk, params, noise, row0, ham_diag, out
     lib = load()
     tag, refused = ('noisy_wide', 'n <= 6') if wide else ('noisy', 'n >= 7')
     entry = f'qhea_model_forward_{tag}'
-    B = branch.shape[0]
-    _dev_f64(branch, 'branch', (B, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
-    _dev_f64(params, 'params')
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
     pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
-    ws_bytes = getattr(lib, f'qhea_model_{tag}_workspace_bytes')
-    with torch.cuda.device(branch.device):
-        nbytes = int(ws_bytes(ctypes.byref(desc), int(B), ctypes.byref(noise)))
-    ws = _workspace(branch.device, nbytes) if nbytes else None
+    ws = _sized_ws(branch.device, getattr(lib, f'qhea_model_{tag}_workspace_bytes'), ctypes.byref(desc), int(B),
+                   ctypes.byref(noise))
     with torch.cuda.device(branch.device):
         rc = getattr(lib, entry)(ctypes.byref(desc), int(row0), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
                                  _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(stderr), _ptr(ws),
@@ -769,17 +762,10 @@ def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None,
     anything is launched.
     """
     lib = load()
-    B = branch.shape[0]
-    _dev_f64(branch, 'branch', (B, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
-    _dev_f64(params, 'params')
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(shot_std, 'shot_std', (B,))
     pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
-    with torch.cuda.device(branch.device):
-        nbytes = int(lib.qhea_model_exact_noisy_workspace_bytes(ctypes.byref(desc), int(B)))
-    ws = _workspace(branch.device, nbytes) if nbytes else None
+    ws = _sized_ws(branch.device, lib.qhea_model_exact_noisy_workspace_bytes, ctypes.byref(desc), int(B))
     with torch.cuda.device(branch.device):
         rc = lib.qhea_model_forward_noisy_exact(ctypes.byref(desc), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
                                                 _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(shot_std), _ptr(ws),
@@ -800,9 +786,7 @@ def model_exact_noisy_log10_amplification(desc, noise):
 
 
 def _noisy_grad_ws(lib, desc, B, device):
-    with torch.cuda.device(device):
-        nbytes = int(lib.qhea_model_exact_noisy_grad_workspace_bytes(ctypes.byref(desc), int(B)))
-    return _workspace(device, nbytes) if nbytes else None
+    return _sized_ws(device, lib.qhea_model_exact_noisy_grad_workspace_bytes, ctypes.byref(desc), int(B))
 
 
 def _check_noisy_grad(rc, who):
@@ -819,18 +803,13 @@ def model_loss_grad_noisy_exact(desc, branch, trunk, y, params, noise, inv_batch
     n >= 7 or a refused conditioning and QheaError for a bad noise setting, in both cases before anything is launched.
     """
     lib = load()
-    B = branch.shape[0]
-    _dev_f64(branch, 'branch', (B, desc.branch_in))
-    if desc.model == MODEL_QUANONET:
-        _dev_f64(trunk, 'trunk', (B, desc.trunk_in))
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(y, 'y')
     if y.numel() != B:
         raise QheaError(f"y has {y.numel()} elements, expected {B}")
-    _dev_f64(params, 'params')
     _dev_f64(grad, 'grad')
     if grad.numel() < params.numel() + 2:
         raise QheaError("model_loss_grad_noisy_exact: grad needs P + 2 entries")
-    _dev_f64(ham_diag, 'ham_diag', (1 << desc.n_qubits,))
     _dev_f64(pred, 'pred', (B,))
     ws = _noisy_grad_ws(lib, desc, B, branch.device)
     with torch.cuda.device(branch.device):

@@ -12,7 +12,7 @@
 #include "hea_adam.hpp"
 #include "hea_dp.hpp"
 #include "hea_qsweep.hpp"
-#include "hea_noise.hpp"
+#include "hea_model.hpp"
 #include "hea_train.hpp"
 
 namespace qhea {
@@ -29,7 +29,6 @@ struct WorkspaceHeader {
     int pad;
 };
 constexpr unsigned long long kWsMagic = 0x51484541'57530001ull;      // "QHEAWS" + layout version
-constexpr size_t kHeaderBytes = 256;
 __device__ __forceinline__ void header_init(WorkspaceHeader* h) {
     if (h->magic != kWsMagic) { h->status = 0; h->pad = 0; h->magic = kWsMagic; }
 }
@@ -502,12 +501,27 @@ __global__ __launch_bounds__(kRedThreads) void reduce_kernel(int n, int blk, int
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-struct Shape {
-    long E = 0, blk = 0;
-    Runs runs{};
-    int nblocks = 0;        // circuit blocks (the runs' counts added up)
-    int fast_ld = 0;        // zyz_fast_ld: sub-layers per block of a block-unrolled shape (hea_zyz.hpp), 0: not one
-};
+int append_blocks(Shape& sh, long count, int enc, int ld) {
+    if (count == 0) return QHEA_OK;
+    sh.E += count * enc;
+    sh.blk += count * ld;
+    const int k = sh.runs.nruns;
+    if (k > 0 && sh.runs.enc[k - 1] == enc && sh.runs.ld[k - 1] == ld) {
+        sh.runs.count[k - 1] += (int)count;
+    } else {
+        if (k == kMaxRuns) return QHEA_EUNSUPPORTED;
+        sh.runs.count[k] = (int)count; sh.runs.enc[k] = enc; sh.runs.ld[k] = ld;
+        sh.runs.nruns = k + 1;
+    }
+    return QHEA_OK;
+}
+
+int finish_shape(int n, long nb, Shape& sh) {
+    if (sh.E > INT32_MAX || sh.blk > INT32_MAX) return QHEA_EINVAL;
+    sh.nblocks = (int)nb;
+    sh.fast_ld = zyz_fast_ld(sh.runs, n);
+    return QHEA_OK;
+}
 
 int make_shape(int n, int nb, const int32_t* enc, const int32_t* ld, Shape& sh) {
     if (n < QHEA_MIN_QUBITS || n > QHEA_MAX_QUBITS || nb < 0) return QHEA_EINVAL;
@@ -515,24 +529,11 @@ int make_shape(int n, int nb, const int32_t* enc, const int32_t* ld, Shape& sh) 
     sh.runs.nruns = 0;
     for (int b = 0; b < nb; ++b) {
         if (enc[b] < 0 || ld[b] < 0) return QHEA_EINVAL;
-        sh.E += enc[b];
-        sh.blk += ld[b];
-        const int k = sh.runs.nruns;
-        if (k > 0 && sh.runs.enc[k - 1] == enc[b] && sh.runs.ld[k - 1] == ld[b]) {
-            sh.runs.count[k - 1]++;
-        } else {
-            if (k == kMaxRuns) return QHEA_EUNSUPPORTED;
-            sh.runs.count[k] = 1; sh.runs.enc[k] = enc[b]; sh.runs.ld[k] = ld[b];
-            sh.runs.nruns = k + 1;
-        }
+        const int rc = append_blocks(sh, 1, enc[b], ld[b]);
+        if (rc != QHEA_OK) return rc;
     }
-    if (sh.E > INT32_MAX || sh.blk > INT32_MAX) return QHEA_EINVAL;
-    sh.nblocks = nb;
-    sh.fast_ld = zyz_fast_ld(sh.runs, n);
-    return QHEA_OK;
+    return finish_shape(n, nb, sh);
 }
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int simd_count() {                                // of the CURRENT device (cached per device ordinal)
     constexpr int kMaxDev = 64;
@@ -714,20 +715,20 @@ Layout make_layout(int n, const Shape& sh, int64_t B, int64_t Bd) {
         case BwdKernel::ZTri2: case BwdKernel::ZSnap: L.nwaves = (groups + 1) / 2; break;  // one row per workgroup = two sample groups
         default:                 L.nwaves = groups; break;                                 // one row per workgroup = sample group
     }
-    size_t p = kHeaderBytes;                         // WorkspaceHeader
-    L.off_U = p;    p = align_up(p + (size_t)(sh.blk + 2) * n * kGateBytes);
-    L.off_cs = p;   p = align_up(p + (size_t)B * sh.E * sizeof(double2));
-    L.off_part = p; p = align_up(p + (size_t)L.nwaves * sh.blk * padded_3n(n) * sizeof(double));
+    const TableLayout t = table_layout(n, sh, B);
+    L.off_U = t.off_gates; L.off_cs = t.off_cs;
+    size_t p = t.end;
+    L.off_part = p; p = align256(p + (size_t)L.nwaves * sh.blk * padded_3n(n) * sizeof(double));
     const size_t rec_bytes = (size_t)(L.zL + 1 + 2 * kPadRecs) * kRecBytes;                       // padded both sides
-    L.off_rec = p;  p = align_up(p + (L.records ? rec_bytes : 0));
+    L.off_rec = p;  p = align256(p + (L.records ? rec_bytes : 0));
     if (L.records) L.off_rec += (size_t)kPadRecs * kRecBytes;                                     // -> record 0
-    L.off_srec = p; p = align_up(p + (L.srecords ? rec_bytes : 0));
+    L.off_srec = p; p = align256(p + (L.srecords ? rec_bytes : 0));
     if (L.srecords) L.off_srec += (size_t)kPadRecs * kRecBytes;
-    L.off_gmap = p; p = align_up(p + (L.records ? (size_t)sh.blk * n * kGmapDoubles * sizeof(double) : 0));
+    L.off_gmap = p; p = align256(p + (L.records ? (size_t)sh.blk * n * kGmapDoubles * sizeof(double) : 0));
     // psi of every sample group at every publication point, 1 KB each (61 MB at B = 1024, cfg 2); the region exists only in the
     // layouts that select the snapshot kernel, so qhea_workspace_bytes agrees with the call
     L.off_snap = p;
-    if (L.snaps) p = align_up(p + (size_t)(2 * L.nwaves) * sh.nblocks * sh.fast_ld * kSnapBytes);
+    if (L.snaps) p = align256(p + (size_t)(2 * L.nwaves) * sh.nblocks * sh.fast_ld * kSnapBytes);
     L.total = p;
     return L;
 }
@@ -1366,15 +1367,6 @@ __global__ __launch_bounds__(64) void clock_probe_kernel(long iters, unsigned lo
     if (x == 123.456) out[0] = 0;                        // keep the chain
 }
 
-struct ModelInfo {
-    Shape sh;
-    int n = 0;
-    long enc_cols[2] = {0, 0};
-    int width[2] = {0, 0};
-    bool trainable = false, has_bias = false;
-    long P = 0, off_ans = 0, off_bias = -1, off_w[2] = {-1, -1}, off_b[2] = {-1, -1};
-};
-
 int model_info(const qhea_model_desc* d, ModelInfo& mi) {
     if (!d) return QHEA_EINVAL;
     if (d->ham_pauli < QHEA_PAULI_Z || d->ham_pauli > QHEA_PAULI_Y) return QHEA_EINVAL;
@@ -1383,43 +1375,31 @@ int model_info(const qhea_model_desc* d, ModelInfo& mi) {
     for (int i = 0; i < 4; ++i) if (d->net[i] < 0) return QHEA_EINVAL;
     mi.n = n;
     mi.trainable = d->trainable_freq != 0;
-    long nb = 0;
     // block list: QuanONet = td x (n, tl) then bd x (n, bl) (core/quantum_circuits_tq.py:130-138); HEAQNN = depth x (n, ld)
-    int32_t* e = nullptr; int32_t* l = nullptr;
-    long Eb = 0, Et = 0;
     if (d->model == QHEA_MODEL_QUANONET) {
         if (d->branch_in <= 0 || d->trunk_in <= 0) return QHEA_EINVAL;
-        const int bd = d->net[0], bl = d->net[1], td = d->net[2], tl = d->net[3];
-        nb = (long)td + bd;
-        e = new int32_t[nb > 0 ? nb : 1]; l = new int32_t[nb > 0 ? nb : 1];
-        for (int i = 0; i < td; ++i) { e[i] = n; l[i] = tl; }
-        for (int i = 0; i < bd; ++i) { e[td + i] = n; l[td + i] = bl; }
-        Et = (long)td * n; Eb = (long)bd * n;
-        mi.enc_cols[0] = Et; mi.enc_cols[1] = Eb;           // x columns: trunk first (core/models_pt.py:164)
-        mi.width[0] = d->trunk_in; mi.width[1] = d->branch_in;
+        mi.nb[0] = d->net[2]; mi.ld[0] = d->net[3]; mi.nb[1] = d->net[0]; mi.ld[1] = d->net[1];
+        mi.width[0] = d->trunk_in; mi.width[1] = d->branch_in;   // x columns: trunk first (core/models_pt.py:164)
         mi.has_bias = true;
     } else if (d->model == QHEA_MODEL_HEAQNN) {
         if (d->branch_in <= 0) return QHEA_EINVAL;
-        nb = d->net[0];
-        e = new int32_t[nb > 0 ? nb : 1]; l = new int32_t[nb > 0 ? nb : 1];
-        for (int i = 0; i < nb; ++i) { e[i] = n; l[i] = d->net[1]; }
-        mi.enc_cols[0] = (long)d->net[0] * n; mi.enc_cols[1] = 0;
+        mi.nb[0] = d->net[0]; mi.ld[0] = d->net[1]; mi.nb[1] = 0; mi.ld[1] = 0;
         mi.width[0] = d->branch_in; mi.width[1] = 1;
         mi.has_bias = false;
     } else {
         return QHEA_EINVAL;
     }
-    const int rc = make_shape(n, (int)nb, e, l, mi.sh);
-    delete[] e; delete[] l;
+    for (int g = 0; g < 2; ++g) {
+        mi.enc_cols[g] = (long)mi.nb[g] * n;
+        append_blocks(mi.sh, mi.nb[g], n, mi.ld[g]);             // (two runs at the most: never refused)
+    }
+    const int rc = finish_shape(n, (long)mi.nb[0] + mi.nb[1], mi.sh);
     if (rc != QHEA_OK) return rc;
     long p = 0;
     if (mi.has_bias) { mi.off_bias = p; p += 1; }             // nn.Module order: own parameter `bias` first
-    if (mi.trainable) {
-        if (d->model == QHEA_MODEL_QUANONET) {               // then branch_freq, trunk_freq, quantum_layer
-            mi.off_w[1] = p; p += Eb; mi.off_b[1] = p; p += Eb;
-            mi.off_w[0] = p; p += Et; mi.off_b[0] = p; p += Et;
-        } else {
-            mi.off_w[0] = p; p += mi.enc_cols[0]; mi.off_b[0] = p; p += mi.enc_cols[0];
+    if (mi.trainable) {                                        // then branch_freq, trunk_freq (QuanONet), quantum_layer
+        for (int g = d->model == QHEA_MODEL_QUANONET ? 1 : 0; g >= 0; --g) {
+            mi.off_w[g] = p; p += mi.enc_cols[g]; mi.off_b[g] = p; p += mi.enc_cols[g];
         }
     }
     mi.off_ans = p; p += mi.sh.blk * 3 * n;
@@ -1460,8 +1440,8 @@ ModelLayout make_model_layout(const ModelInfo& mi, int64_t B, int64_t Bd /* rows
     ModelLayout M{};
     M.L = make_layout(mi.n, mi.sh, B, Bd);
     size_t p = M.L.total;
-    M.off_gx = p;   p = align_up(p + (size_t)B * mi.sh.E * sizeof(double));
-    M.off_pred = p; p = align_up(p + (size_t)B * sizeof(double));
+    M.off_gx = p;   p = align256(p + (size_t)B * mi.sh.E * sizeof(double));
+    M.off_pred = p; p = align256(p + (size_t)B * sizeof(double));
     M.total = p;
     return M;
 }
@@ -1482,50 +1462,13 @@ EncDesc make_enc(const qhea_model_desc* d, const ModelInfo& mi, const double* br
     return enc;
 }
 
-int launch_prep_model(const ModelInfo& mi, int64_t B, const double* params, const EncDesc& enc, char* ws,
-                      const Layout& L, hipStream_t st) {
-    const long total = (mi.sh.blk + 2) * mi.n + B * mi.sh.E;
-    const int threads = 256;
-    hipLaunchKernelGGL(prep_model_kernel, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, st,
-                       mi.n, (int)mi.sh.blk, params + mi.off_ans, reinterpret_cast<double4*>(ws + L.off_U),
-                       (long)B, (int)mi.sh.E, enc, reinterpret_cast<double2*>(ws + L.off_cs),
-                       reinterpret_cast<WorkspaceHeader*>(ws));
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
-}
-
-// the noisy forward's access to the model-level prep (hea_noise.hpp)
-int noise_model_shape(const qhea_model_desc* d, NoiseShape& ns) {
-    ModelInfo mi;
-    const int rc = model_info(d, mi);
-    if (rc != QHEA_OK) return rc;
-    ns.n = mi.n; ns.blk = (int)mi.sh.blk; ns.E = (int)mi.sh.E; ns.off_bias = mi.has_bias ? mi.off_bias : -1;
-    if (d->model == QHEA_MODEL_QUANONET) { ns.nb[0] = d->net[2]; ns.ld[0] = d->net[3]; ns.nb[1] = d->net[0]; ns.ld[1] = d->net[1]; }
-    else                                 { ns.nb[0] = d->net[0]; ns.ld[0] = d->net[1]; ns.nb[1] = 0;         ns.ld[1] = 0; }
-    return QHEA_OK;
-}
-
-int noise_model_grad_map(const qhea_model_desc* d, NoiseGradMap& gm) {
-    ModelInfo mi;
-    const int rc = model_info(d, mi);
-    if (rc != QHEA_OK) return rc;
-    gm.P = mi.P; gm.off_ans = mi.off_ans;
-    for (int s = 0; s < 2; ++s) {
-        gm.off_w[s] = mi.trainable ? mi.off_w[s] : -1; gm.off_b[s] = mi.trainable ? mi.off_b[s] : -1;
-        gm.ncols[s] = (int)mi.enc_cols[s]; gm.width[s] = mi.width[s];
-    }
-    return QHEA_OK;
-}
-
-int launch_noise_prep(const qhea_model_desc* d, int64_t B, const double* branch, const double* trunk, const double* params,
-                      double4* gates, double2* cs, void* hdr, hipStream_t st) {
-    ModelInfo mi;
-    const int rc = model_info(d, mi);
-    if (rc != QHEA_OK) return rc;
+int launch_prep_model(const qhea_model_desc* d, const ModelInfo& mi, int64_t B, const double* branch, const double* trunk,
+                      const double* params, double4* gates, double2* cs, void* hdr, hipStream_t st) {
     const long total = (mi.sh.blk + 2) * mi.n + B * mi.sh.E;
     const int threads = 256;
     hipLaunchKernelGGL(prep_model_kernel, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, st,
                        mi.n, (int)mi.sh.blk, params + mi.off_ans, gates, (long)B, (int)mi.sh.E,
-                       make_enc(d, mi, branch, trunk, params), cs, reinterpret_cast<WorkspaceHeader*>(hdr));
+                       make_enc(d, mi, branch, trunk, params), cs, static_cast<WorkspaceHeader*>(hdr));
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 
@@ -1776,7 +1719,8 @@ static int model_forward_impl(const qhea_model_desc* desc, int64_t batch, const 
         return launch_zyz_forward(k, mi.n, mi.sh, batch, M.L, ws, AngleSrc{nullptr, enc}, desc->ham_offset, desc->ham_coeff, ham_diag,
                                   desc->ham_pauli, pred, nullptr, bias, st);
     }
-    rc = launch_prep_model(mi, batch, params, enc, ws, M.L, st);
+    rc = launch_prep_model(desc, mi, batch, branch, trunk, params, reinterpret_cast<double4*>(ws + M.L.off_U),
+                           reinterpret_cast<double2*>(ws + M.L.off_cs), ws, st);
     if (rc != QHEA_OK) return rc;
     return launch_table_forward(k, mi.n, mi.sh, batch, M.L, ws, desc->ham_offset, desc->ham_coeff, ham_diag, desc->ham_pauli, pred,
                                 nullptr, bias, st);
@@ -1885,7 +1829,8 @@ static int model_loss_grad_impl(const qhea_model_desc* desc, const StepView& v, 
     if (R != 1) return QHEA_EUNSUPPORTED;                       // (the ensemble entry point never asks: R-sequential calls there)
     if (records_ready || records_for_next) return QHEA_EINVAL;
     if (dpx && !dp_blocks_ok(rb.total())) return QHEA_EUNSUPPORTED;
-    rc = launch_prep_model(mi, batch, params, enc, ws, M.L, st);
+    rc = launch_prep_model(desc, mi, batch, v.branch, v.trunk, params, reinterpret_cast<double4*>(ws + M.L.off_U),
+                           reinterpret_cast<double2*>(ws + M.L.off_cs), ws, st);
     if (rc == QHEA_OK)
         rc = launch_table_backward(k, mi.n, mi.sh, batch, M.L, ws, desc->ham_offset, desc->ham_coeff, ham_diag, desc->ham_pauli,
                                    nullptr, nullptr, v.y, bias, v.inv_bt, pr, gx, partial, st);
@@ -2132,12 +2077,12 @@ static DepthLayout depth_layout(const ModelInfo& env, int64_t B) {
     DepthLayout L{};
     const int n = env.n, spw = 64 >> lane_bits(n);
     L.nwaves = lds_supported(n) ? (long)B : (((B + spw - 1) / spw + kWaves - 1) / kWaves) * kWaves;
-    size_t p = kHeaderBytes;
-    L.off_U = p;    p = align_up(p + (size_t)(env.sh.blk + 2) * n * kGateBytes);
-    L.off_cs = p;   p = align_up(p + (size_t)B * env.sh.E * sizeof(double2));
-    L.off_part = p; p = align_up(p + (size_t)L.nwaves * env.sh.blk * padded_3n(n) * sizeof(double));
-    L.off_gx = p;   p = align_up(p + (size_t)B * env.sh.E * sizeof(double));
-    L.off_pred = p; p = align_up(p + (size_t)B * sizeof(double));
+    const TableLayout t = table_layout(env, B);
+    L.off_U = t.off_gates; L.off_cs = t.off_cs;
+    size_t p = t.end;
+    L.off_part = p; p = align256(p + (size_t)L.nwaves * env.sh.blk * padded_3n(n) * sizeof(double));
+    L.off_gx = p;   p = align256(p + (size_t)B * env.sh.E * sizeof(double));
+    L.off_pred = p; p = align256(p + (size_t)B * sizeof(double));
     L.total = p;
     return L;
 }
@@ -2474,12 +2419,12 @@ static QubitLayout qubit_layout(const QubitSet& qs, int64_t B, size_t list_bytes
     }
     QubitLayout L{};
     size_t p = kHeaderBytes;
-    L.off_list = p; p = align_up(p + list_bytes);
-    L.off_U = p;    p = align_up(p + u);
-    L.off_cs = p;   p = align_up(p + (size_t)B * e * sizeof(double2));
-    L.off_part = p; p = align_up(p + part);
-    L.off_gx = p;   p = align_up(p + (size_t)B * e * sizeof(double));
-    L.off_pred = p; p = align_up(p + (size_t)B * sizeof(double));
+    L.off_list = p; p = align256(p + list_bytes);
+    L.off_U = p;    p = align256(p + u);
+    L.off_cs = p;   p = align256(p + (size_t)B * e * sizeof(double2));
+    L.off_part = p; p = align256(p + part);
+    L.off_gx = p;   p = align256(p + (size_t)B * e * sizeof(double));
+    L.off_pred = p; p = align256(p + (size_t)B * sizeof(double));
     L.total = p;
     return L;
 }

@@ -116,49 +116,33 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_exact_noisy_workspace_bytes(const qhea_model_desc* desc, int64_t batch) {
-    NoiseShape ns;
-    if (batch < 0 || noise_model_shape(desc, ns) != QHEA_OK) return 0;
-    return dens_layout(ns, batch).total;
+    ModelInfo mi;
+    if (batch < 0 || model_info(desc, mi) != QHEA_OK) return 0;
+    return dens_layout(mi, batch).total;
 }
 
 int qhea_model_forward_noisy_exact(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk,
                                    const double* params, const double* ham_diag, const qhea_noise* noise, double* pred,
                                    double* shot_std, void* workspace, size_t workspace_bytes, void* stream) {
-    NoiseShape ns;
-    int rc = noise_model_shape(desc, ns);
-    if (rc != QHEA_OK) return rc;
-    if (!rates_ok(noise)) return QHEA_EINVAL;
-    if (ns.n > 6) return QHEA_EUNSUPPORTED;                              // 4^n elements per row in LDS
-    const bool pauli_ok = desc->ham_pauli == QHEA_PAULI_Z || ((desc->ham_pauli == QHEA_PAULI_X ||
-                                                               desc->ham_pauli == QHEA_PAULI_Y) && !ham_diag);
-    if (!pauli_ok || batch < 0) return QHEA_EINVAL;
-    if (batch == 0) return QHEA_OK;
-    if (!branch || !params || !pred || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
-    const DensLayout L = dens_layout(ns, batch);
+    NoisyCall c;
+    int rc = noisy_call_check({QHEA_MIN_QUBITS, 6 /* 4^n elements per row in LDS */, false, false}, desc, ham_diag, noise, 0,
+                              batch, trunk, {branch, params, pred}, workspace, stream, c);
+    if (rc != QHEA_OK || c.empty) return rc;
+    const DensLayout L = dens_layout(c.mi, batch);
     if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
-    rc = launch_noise_prep(desc, batch, branch, trunk, params, gates, cs, ws, st);
+    double4* gates = reinterpret_cast<double4*>(c.ws + L.off_gates);
+    double2* cs = reinterpret_cast<double2*>(c.ws + L.off_cs);
+    rc = launch_prep_model(desc, c.mi, batch, branch, trunk, params, gates, cs, c.ws, c.st);
     if (rc != QHEA_OK) return rc;
 
-    DensArgs a{};
-    a.gates = gates; a.cs = cs; a.diag = ham_diag;
-    a.bias = ns.off_bias >= 0 ? params + ns.off_bias : nullptr;
-    a.off = desc->ham_offset; a.co = desc->ham_coeff; a.q = noise->readout;
-    a.d1_off = 1.0 - 4.0 * noise->p1 / 3.0; a.d1_keep = 1.0 - 2.0 * noise->p1 / 3.0; a.d1_mix = 2.0 * noise->p1 / 3.0;
-    const double lam = 16.0 * noise->p2 / 15.0;
-    a.d2_keep = 1.0 - lam; a.d2_mix = lam / 4.0;
-    a.B = batch; a.E = ns.E; a.pauli = desc->ham_pauli;
-    for (int g = 0; g < 2; ++g) { a.nb[g] = ns.nb[g]; a.ld[g] = ns.ld[g]; }
+    DensArgs a = dens_args(desc, c.mi, noise, params, ham_diag, batch, gates, cs);
     a.pred = pred; a.sd = shot_std;
-    switch (ns.n) {
-        case 2: return launch_density<2>(a, st);
-        case 3: return launch_density<3>(a, st);
-        case 4: return launch_density<4>(a, st);
-        case 5: return launch_density<5>(a, st);
-        case 6: return launch_density<6>(a, st);
+    switch (c.mi.n) {
+        case 2: return launch_density<2>(a, c.st);
+        case 3: return launch_density<3>(a, c.st);
+        case 4: return launch_density<4>(a, c.st);
+        case 5: return launch_density<5>(a, c.st);
+        case 6: return launch_density<6>(a, c.st);
         default: return QHEA_EUNSUPPORTED;
     }
 }

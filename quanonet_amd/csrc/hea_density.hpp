@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "hea_noise.hpp"
+#include "hea_noise_traj.hpp"
 
 namespace qhea {
 namespace {
@@ -184,24 +184,26 @@ __device__ __forceinline__ void wire_passes(double2* row, int rank, int sf, cons
     }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct DensLayout { size_t off_gates, off_cs, total; };
 
-DensLayout dens_layout(const NoiseShape& ns, int64_t B) {
-    DensLayout L{};
-    size_t p = 256;                                                      // header (prep_model_kernel stamps it)
-    L.off_gates = p; p = align256(p + (size_t)(ns.blk + 2) * ns.n * 2 * sizeof(double4));
-    L.off_cs = p;    p = align256(p + (size_t)B * ns.E * sizeof(double2));
-    L.total = p;
-    return L;
+DensLayout dens_layout(const ModelInfo& mi, int64_t B) {
+    const TableLayout t = table_layout(mi, B);
+    return DensLayout{t.off_gates, t.off_cs, t.end};
 }
 
-bool rates_ok(const qhea_noise* nz) {
-    if (!nz) return false;
-    for (double p : {nz->p1, nz->p2, nz->readout})
-        if (!(p >= 0.0 && p <= 1.0)) return false;
-    return true;
+// everything of DensArgs but the outputs (pred, sd)
+DensArgs dens_args(const qhea_model_desc* desc, const ModelInfo& mi, const qhea_noise* noise, const double* params,
+                   const double* ham_diag, int64_t batch, const double4* gates, const double2* cs) {
+    DensArgs a{};
+    a.gates = gates; a.cs = cs; a.diag = ham_diag;
+    a.bias = mi.has_bias ? params + mi.off_bias : nullptr;
+    a.off = desc->ham_offset; a.co = desc->ham_coeff; a.q = noise->readout;
+    a.d1_off = 1.0 - 4.0 * noise->p1 / 3.0; a.d1_keep = 1.0 - 2.0 * noise->p1 / 3.0; a.d1_mix = 2.0 * noise->p1 / 3.0;
+    const double lam = 16.0 * noise->p2 / 15.0;
+    a.d2_keep = 1.0 - lam; a.d2_mix = lam / 4.0;
+    a.B = batch; a.E = (int)mi.sh.E; a.pauli = desc->ham_pauli;
+    for (int g = 0; g < 2; ++g) { a.nb[g] = mi.nb[g]; a.ld[g] = mi.ld[g]; }
+    return a;
 }
 }  // namespace
 }  // namespace qhea

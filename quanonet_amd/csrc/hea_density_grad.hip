@@ -488,25 +488,16 @@ __global__ __launch_bounds__(64 * kRedWaves) void reduce_density_kernel(DensRed 
 
 struct DensGradLayout { size_t off_gates, off_cs, off_pred, off_rec, total; };
 
-DensGradLayout dens_grad_layout(const NoiseShape& ns, int64_t B) {
+DensGradLayout dens_grad_layout(const ModelInfo& mi, int64_t B) {
     DensGradLayout L{};
-    const DensLayout F = dens_layout(ns, B);
+    const DensLayout F = dens_layout(mi, B);
     L.off_gates = F.off_gates; L.off_cs = F.off_cs;
     size_t p = F.total;
     L.off_pred = p; p = align256(p + (size_t)B * sizeof(double));
-    L.off_rec = p;  p = align256(p + (size_t)B * ((size_t)ns.E + (size_t)3 * ns.n * ns.blk) * sizeof(double));
+    L.off_rec = p;  p = align256(p + (size_t)B * ((size_t)mi.sh.E + (size_t)3 * mi.n * mi.sh.blk) * sizeof(double));
     L.total = p;
     return L;
 }
-
-// log10 of the factor the inverse walk amplifies the traceless part of rho by; +inf for a singular channel
-double log10_amplification(const NoiseShape& ns, const qhea_noise* nz) {
-    const double k1 = 1.0 - 4.0 * nz->p1 / 3.0, k2 = 1.0 - 16.0 * nz->p2 / 15.0;
-    if (!(k1 > 0.0) || !(k2 > 0.0)) return INFINITY;
-    const double L1 = (double)ns.E + (double)ns.n * ns.blk, L2 = (double)ns.n * ns.blk;
-    return -(L1 * log10(k1) + L2 * log10(k2));
-}
-constexpr double kMaxLog10Amplification = 12.0;
 
 template <int N>
 int launch_density_bwd(const DensGradArgs& a, hipStream_t st) {
@@ -521,48 +512,29 @@ int launch_density_bwd(const DensGradArgs& a, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 
-// everything that can be refused, refused before the first launch
-int check_call(const qhea_model_desc* desc, const double* ham_diag, const qhea_noise* noise, NoiseShape& ns, NoiseGradMap& gm) {
-    int rc = noise_model_shape(desc, ns);
-    if (rc != QHEA_OK) return rc;
-    rc = noise_model_grad_map(desc, gm);
-    if (rc != QHEA_OK) return rc;
-    if (!rates_ok(noise)) return QHEA_EINVAL;
-    if (ns.n > 6) return QHEA_EUNSUPPORTED;                              // 2 x 4^n elements per row in LDS
-    if (!pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
-    if (!(log10_amplification(ns, noise) <= kMaxLog10Amplification)) return QHEA_EUNSUPPORTED;
-    return QHEA_OK;
-}
+constexpr NoisyKind kGradKind{QHEA_MIN_QUBITS, 6 /* 2 x 4^n elements per row in LDS */, false, true};
 
 // prep, density backward, reduce (+ Adam when adam.p) for one batch; the arguments have been checked
-int loss_grad_launch(const qhea_model_desc* desc, const NoiseShape& ns, const NoiseGradMap& gm, int64_t batch,
-                     const double* branch, const double* trunk, const double* y, const double* params, const double* ham_diag,
-                     const qhea_noise* noise, double inv_bt, double* grad, double* pred, char* ws, hipStream_t st,
-                     const AdamArgs& adam) {
-    const DensGradLayout L = dens_grad_layout(ns, batch);
+int loss_grad_launch(const qhea_model_desc* desc, const ModelInfo& mi, int64_t batch, const double* branch, const double* trunk,
+                     const double* y, const double* params, const double* ham_diag, const qhea_noise* noise, double inv_bt,
+                     double* grad, double* pred, char* ws, hipStream_t st, const AdamArgs& adam) {
+    const DensGradLayout L = dens_grad_layout(mi, batch);
     double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
     double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
-    int rc = launch_noise_prep(desc, batch, branch, trunk, params, gates, cs, ws, st);
+    int rc = launch_prep_model(desc, mi, batch, branch, trunk, params, gates, cs, ws, st);
     if (rc != QHEA_OK) return rc;
 
     DensGradArgs a{};
-    a.f.gates = gates; a.f.cs = cs; a.f.diag = ham_diag;
-    a.f.bias = ns.off_bias >= 0 ? params + ns.off_bias : nullptr;
-    a.f.off = desc->ham_offset; a.f.co = desc->ham_coeff; a.f.q = noise->readout;
-    a.f.d1_off = 1.0 - 4.0 * noise->p1 / 3.0; a.f.d1_keep = 1.0 - 2.0 * noise->p1 / 3.0; a.f.d1_mix = 2.0 * noise->p1 / 3.0;
-    const double lam = 16.0 * noise->p2 / 15.0;
-    a.f.d2_keep = 1.0 - lam; a.f.d2_mix = lam / 4.0;
-    a.f.B = batch; a.f.E = ns.E; a.f.pauli = desc->ham_pauli;
-    for (int g = 0; g < 2; ++g) { a.f.nb[g] = ns.nb[g]; a.f.ld[g] = ns.ld[g]; }
+    a.f = dens_args(desc, mi, noise, params, ham_diag, batch, gates, cs);
     a.f.pred = pred; a.f.sd = nullptr;
-    a.w = params + gm.off_ans;
+    a.w = params + mi.off_ans;
     a.o1_keep = a.f.d1_keep; a.o1_mix = a.f.d1_mix; a.o1_off = a.f.d1_off;
     a.r1_off = 1.0 / a.f.d1_off; a.r1_keep = a.f.d1_keep * a.r1_off; a.r1_mix = -a.f.d1_mix * a.r1_off;
     a.o2_keep = a.f.d2_keep; a.o2_mix = a.f.d2_mix;
     a.r2_keep = 1.0 / a.f.d2_keep; a.r2_mix = -a.f.d2_mix * a.r2_keep;
     a.pred_ws = reinterpret_cast<double*>(ws + L.off_pred);
     a.rec = reinterpret_cast<double*>(ws + L.off_rec);
-    switch (ns.n) {
+    switch (mi.n) {
         case 2: rc = launch_density_bwd<2>(a, st); break;
         case 3: rc = launch_density_bwd<3>(a, st); break;
         case 4: rc = launch_density_bwd<4>(a, st); break;
@@ -575,13 +547,13 @@ int loss_grad_launch(const qhea_model_desc* desc, const NoiseShape& ns, const No
     DensRed d{};
     d.rec = a.rec; d.pred = a.pred_ws; d.y = y;
     d.in[0] = desc->model == QHEA_MODEL_QUANONET ? trunk : branch; d.in[1] = branch;
-    d.B = batch; d.P = gm.P; d.off_ans = gm.off_ans; d.off_bias = ns.off_bias;
+    d.B = batch; d.P = mi.P; d.off_ans = mi.off_ans; d.off_bias = mi.off_bias;
     for (int s = 0; s < 2; ++s) {
-        d.off_w[s] = gm.off_w[s]; d.off_b[s] = gm.off_b[s]; d.ncols[s] = gm.ncols[s]; d.width[s] = gm.width[s];
+        d.off_w[s] = mi.off_w[s]; d.off_b[s] = mi.off_b[s]; d.ncols[s] = (int)mi.enc_cols[s]; d.width[s] = mi.width[s];
     }
-    d.E = ns.E; d.nans = 3 * ns.n * ns.blk;
+    d.E = (int)mi.sh.E; d.nans = 3 * mi.n * (int)mi.sh.blk;
     d.inv_bt = inv_bt; d.grad = grad; d.adam = adam;
-    hipLaunchKernelGGL(reduce_density_kernel, dim3((unsigned)((gm.P + 2 + kRedWaves - 1) / kRedWaves)), dim3(64 * kRedWaves), 0,
+    hipLaunchKernelGGL(reduce_density_kernel, dim3((unsigned)((mi.P + 2 + kRedWaves - 1) / kRedWaves)), dim3(64 * kRedWaves), 0,
                        st, d);
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
@@ -594,31 +566,27 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_exact_noisy_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch) {
-    NoiseShape ns;
-    if (batch < 0 || noise_model_shape(desc, ns) != QHEA_OK) return 0;
-    return dens_grad_layout(ns, batch).total;
+    ModelInfo mi;
+    if (batch < 0 || model_info(desc, mi) != QHEA_OK) return 0;
+    return dens_grad_layout(mi, batch).total;
 }
 
 double qhea_model_exact_noisy_log10_amplification(const qhea_model_desc* desc, const qhea_noise* noise) {
-    NoiseShape ns;
-    if (noise_model_shape(desc, ns) != QHEA_OK || !rates_ok(noise)) return NAN;
-    return log10_amplification(ns, noise);
+    ModelInfo mi;
+    if (model_info(desc, mi) != QHEA_OK || !rates_ok(noise)) return NAN;
+    return log10_amplification(mi, noise);
 }
 
 int qhea_model_loss_grad_noisy_exact(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk,
                                      const double* y, const double* params, const double* ham_diag, const qhea_noise* noise,
                                      double inv_batch_total, double* grad, double* pred, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    NoiseShape ns;
-    NoiseGradMap gm;
-    const int rc = check_call(desc, ham_diag, noise, ns, gm);
-    if (rc != QHEA_OK) return rc;
-    if (batch < 0) return QHEA_EINVAL;
-    if (batch == 0) return QHEA_OK;
-    if (!branch || !y || !params || !grad || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
-    if (!workspace || workspace_bytes < dens_grad_layout(ns, batch).total) return QHEA_EWORKSPACE;
-    return loss_grad_launch(desc, ns, gm, batch, branch, trunk, y, params, ham_diag, noise, inv_batch_total, grad, pred,
-                            static_cast<char*>(workspace), static_cast<hipStream_t>(stream), AdamArgs{});
+    NoisyCall c;
+    const int rc = noisy_call_check(kGradKind, desc, ham_diag, noise, 0, batch, trunk, {branch, y, params, grad}, workspace, stream, c);
+    if (rc != QHEA_OK || c.empty) return rc;
+    if (!workspace || workspace_bytes < dens_grad_layout(c.mi, batch).total) return QHEA_EWORKSPACE;
+    return loss_grad_launch(desc, c.mi, batch, branch, trunk, y, params, ham_diag, noise, inv_batch_total, grad, pred, c.ws, c.st,
+                            AdamArgs{});
 }
 
 int qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
@@ -628,21 +596,19 @@ int qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n_st
                                        int64_t first_step, double lr, double beta1, double beta2, double eps,
                                        double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
     if (!desc || n_steps < 0 || first_step < 1) return QHEA_EINVAL;
-    NoiseShape ns;
-    NoiseGradMap gm;
-    const int rc0 = check_call(desc, ham_diag, noise, ns, gm);
-    if (rc0 != QHEA_OK) return rc0;
-    if (n_steps == 0) return QHEA_OK;
-    if (!row_begin || !inv_batch_total || !branch || !y || !grad || !params || !exp_avg || !exp_avg_sq) return QHEA_EINVAL;
+    NoisyCall c;
+    const int rc0 = noisy_call_check(kGradKind, desc, ham_diag, noise, 0, n_steps, trunk,
+                                     {row_begin, inv_batch_total, branch, y, grad, params, exp_avg, exp_avg_sq}, workspace, stream, c);
+    if (rc0 != QHEA_OK || c.empty) return rc0;
     const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
                          first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
-    const int64_t bmax = call_max_batch(call, gm.P, *desc);
+    const int64_t bmax = call_max_batch(call, c.mi.P, *desc);
     if (bmax < 0) return QHEA_EINVAL;
-    if (!workspace || workspace_bytes < dens_grad_layout(ns, bmax).total) return QHEA_EWORKSPACE;     // (every region grows with the batch)
+    if (!workspace || workspace_bytes < dens_grad_layout(c.mi, bmax).total) return QHEA_EWORKSPACE;    // (every region grows with the batch)
     for (int64_t i = 0; i < n_steps; ++i) {
         const StepView v = step_view(call, i, *desc);
-        const int rc = loss_grad_launch(desc, ns, gm, v.nb, v.branch, v.trunk, v.y, params, ham_diag, noise, v.inv_bt, v.grad,
-                                        nullptr, call.ws(), call.st(), adam_step(call, i, lr).adam);
+        const int rc = loss_grad_launch(desc, c.mi, v.nb, v.branch, v.trunk, v.y, params, ham_diag, noise, v.inv_bt, v.grad,
+                                        nullptr, c.ws, c.st, adam_step(call, i, lr).adam);
         if (rc != QHEA_OK) return rc;
     }
     return QHEA_OK;

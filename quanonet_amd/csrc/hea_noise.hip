@@ -8,7 +8,7 @@
 // row's items in tile order.  Every summation order therefore depends on n and the trajectory count only -- not on the batch,
 // the chunking or the grid -- and no floating-point atomics are used.
 //
-// Gates come from prep_model_kernel's tables (hea_noise.hpp): the fused RY RZ RY gate per wire and sub-layer, and (cos, sin) of
+// Gates come from prep_model_kernel's tables (hea_model.hpp): the fused RY RZ RY gate per wire and sub-layer, and (cos, sin) of
 // every encoding angle per row; RX is applied on its own because noise sits between it and the first rotation.  Sampled Paulis
 // are kept as an X mask and a Z mask (a Pauli string up to a global phase) and pushed through the CNOTs of the ring by Clifford
 // conjugation, so that a sub-layer's ring stays one lane gather followed by at most one gather for the whole sub-layer's errors
@@ -184,18 +184,20 @@ __global__ __launch_bounds__(256) void noisy_finish_kernel(const double2* __rest
     }
 }
 
-struct NoiseLayout { size_t off_gates, off_cs, off_part, total; int tiles; };
-
-NoiseLayout noise_layout(const NoiseShape& ns, int64_t B, int64_t T) {
-    NoiseLayout L{};
-    L.tiles = (int)((T + kTile - 1) / kTile);
-    size_t p = 256;                                                      // header (prep_model_kernel stamps it)
-    L.off_gates = p; p = align256(p + (size_t)(ns.blk + 2) * ns.n * 2 * sizeof(double4));
-    L.off_cs = p;    p = align256(p + (size_t)B * ns.E * sizeof(double2));
-    L.off_part = p;  p = align256(p + (size_t)B * L.tiles * sizeof(double2));
-    L.total = p;
-    return L;
+int launch_noisy(const NoiseArgs& a, int n, double*, hipStream_t st) {
+    const long items = a.B * a.tiles;
+    const dim3 grid((unsigned)((items + kNoiseWaves - 1) / kNoiseWaves)), block(64 * kNoiseWaves);
+    switch (n) {
+        case 2: hipLaunchKernelGGL(noisy_fwd_kernel<2>, grid, block, 0, st, a); break;
+        case 3: hipLaunchKernelGGL(noisy_fwd_kernel<3>, grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL(noisy_fwd_kernel<4>, grid, block, 0, st, a); break;
+        case 5: hipLaunchKernelGGL(noisy_fwd_kernel<5>, grid, block, 0, st, a); break;
+        case 6: hipLaunchKernelGGL(noisy_fwd_kernel<6>, grid, block, 0, st, a); break;
+        default: return QHEA_EUNSUPPORTED;
+    }
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
+constexpr TrajUnit kLaneUnit{QHEA_MIN_QUBITS, 6, false, launch_noisy};      // lane-resident states only
 
 }  // namespace
 
@@ -213,50 +215,14 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_noisy_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise) {
-    NoiseShape ns;
-    const int64_t T = noise_values(noise);
-    if (T < 1 || batch < 0 || noise_model_shape(desc, ns) != QHEA_OK) return 0;
-    return noise_layout(ns, batch, T).total;
+    return traj_workspace_bytes(kLaneUnit, desc, batch, noise);
 }
 
 int qhea_model_forward_noisy(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch, const double* trunk,
                              const double* params, const double* ham_diag, const qhea_noise* noise, double* pred,
                              double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
-    NoiseShape ns;
-    int rc = noise_model_shape(desc, ns);
-    if (rc != QHEA_OK) return rc;
-    const int64_t T = noise_values(noise);
-    if (T < 1) return QHEA_EINVAL;
-    if (ns.n > 6) return QHEA_EUNSUPPORTED;                              // lane-resident states only
-    const bool pauli_ok = desc->ham_pauli == QHEA_PAULI_Z || ((desc->ham_pauli == QHEA_PAULI_X ||
-                                                               desc->ham_pauli == QHEA_PAULI_Y) && !ham_diag);
-    if (!pauli_ok || batch < 0 || row0 < 0) return QHEA_EINVAL;
-    if (batch == 0) return QHEA_OK;
-    if (!branch || !params || !pred || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
-    const NoiseLayout L = noise_layout(ns, batch, T);
-    if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
-    double2* part = reinterpret_cast<double2*>(ws + L.off_part);
-    rc = launch_noise_prep(desc, batch, branch, trunk, params, gates, cs, ws, st);
-    if (rc != QHEA_OK) return rc;
-
-    NoiseArgs a = noise_args(desc, ns, noise, params, ham_diag, row0, batch, T);
-    a.gates = gates; a.cs = cs; a.partial = part;
-    const long items = (long)batch * L.tiles;
-    const dim3 grid((unsigned)((items + kNoiseWaves - 1) / kNoiseWaves)), block(64 * kNoiseWaves);
-    switch (ns.n) {
-        case 2: hipLaunchKernelGGL(noisy_fwd_kernel<2>, grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL(noisy_fwd_kernel<3>, grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(noisy_fwd_kernel<4>, grid, block, 0, st, a); break;
-        case 5: hipLaunchKernelGGL(noisy_fwd_kernel<5>, grid, block, 0, st, a); break;
-        case 6: hipLaunchKernelGGL(noisy_fwd_kernel<6>, grid, block, 0, st, a); break;
-        default: return QHEA_EUNSUPPORTED;
-    }
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    return launch_noisy_finish(part, L.tiles, batch, T, a.bias, pred, stderr_out, st);
+    return traj_forward(kLaneUnit, desc, row0, batch, branch, trunk, params, ham_diag, noise, pred, stderr_out, workspace,
+                        workspace_bytes, stream);
 }
 
 }  // extern "C"

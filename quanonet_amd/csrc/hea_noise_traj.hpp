@@ -1,10 +1,15 @@
-// hea_noise_traj.hpp -- what the trajectory kernels of the noisy forward share: hea_noise.hip (n = 2..6, one amplitude per lane)
-// and hea_noise_wide.hip (n = 7..12, registers or LDS).  The argument record, the Philox stream and its error codes, the Pauli
-// frame bits, the checks of a qhea_noise and the finish launch that turns tile sums into a row's mean and standard error.
+// hea_noise_traj.hpp -- what the noisy entry points share.  All four units (hea_noise.hip, hea_noise_wide.hip, hea_density.hip,
+// hea_density_grad.hip): the checks of a qhea_noise and the argument checks that open every call (noisy_call_check).  The two
+// trajectory units (n = 2..6, one amplitude per lane; n = 7..12, registers or LDS): the argument record, the Philox stream and
+// its error codes, the Pauli frame bits, the workspace layout and the body of the entry point around a unit's kernels.
 #pragma once
+#include <climits>
+#include <cmath>
 #include <cstdint>
+#include <initializer_list>
 
-#include "hea_noise.hpp"
+#include "hea_model.hpp"
+#include "hea_train.hpp"
 
 namespace qhea {
 
@@ -66,35 +71,82 @@ __device__ __forceinline__ unsigned code_at(unsigned codes, unsigned l0, unsigne
 __device__ __forceinline__ int pauli_x(unsigned p, int w) { return (p == 1u || p == 2u) ? 1 << w : 0; }
 __device__ __forceinline__ int pauli_z(unsigned p, int w) { return p >= 2u ? 1 << w : 0; }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline bool rates_ok(const qhea_noise* nz) {
+    if (!nz) return false;
+    for (double p : {nz->p1, nz->p2, nz->readout})
+        if (!(p >= 0.0 && p <= 1.0)) return false;
+    return true;
+}
 
 // values per row (T trajectories or S shots), or QHEA_EINVAL
 inline int64_t noise_values(const qhea_noise* nz) {
-    if (!nz) return QHEA_EINVAL;
-    for (double p : {nz->p1, nz->p2, nz->readout})
-        if (!(p >= 0.0 && p <= 1.0)) return QHEA_EINVAL;
-    if (nz->shots < 0) return QHEA_EINVAL;
+    if (!rates_ok(nz) || nz->shots < 0) return QHEA_EINVAL;
     const int64_t T = nz->shots > 0 ? nz->shots : nz->trajectories;
     if (T < 1 || T > (int64_t)0xFFFFFFFF) return QHEA_EINVAL;          // trajectory index is one 32-bit counter word
     return T;
 }
 
+// log10 of the factor the gradient's inverse walk amplifies the traceless part of rho by; +inf for a singular channel
+inline double log10_amplification(const ModelInfo& mi, const qhea_noise* nz) {
+    const double k1 = 1.0 - 4.0 * nz->p1 / 3.0, k2 = 1.0 - 16.0 * nz->p2 / 15.0;
+    if (!(k1 > 0.0) || !(k2 > 0.0)) return INFINITY;
+    const double L1 = (double)mi.sh.E + (double)mi.n * mi.sh.blk, L2 = (double)mi.n * mi.sh.blk;
+    return -(L1 * log10(k1) + L2 * log10(k2));
+}
+constexpr double kMaxLog10Amplification = 12.0;
+
+// What differs between the noisy calls' checks: the qubit counts the call's kernels exist for, whether the noise setting
+// carries a value count (trajectory calls) or rates only, and whether the call walks the channels back (gradient calls)
+struct NoisyKind { int nmin, nmax; bool trajectories, inverse_walk; };
+// What a call knows once it has passed them
+struct NoisyCall {
+    ModelInfo mi;
+    int64_t T = 0;                          // values per row (trajectory calls)
+    bool empty = false;                     // QHEA_OK and nothing to do
+    hipStream_t st = nullptr;
+    char* ws = nullptr;
+};
+// Everything a noisy call is refused for before it sizes its workspace, in the order the ABI reports it: the descriptor, the
+// noise setting, the qubit range (QHEA_EUNSUPPORTED), the read-out, the conditioning (QHEA_EUNSUPPORTED), then count < 0 or
+// row0 < 0, count == 0 (QHEA_OK, c.empty) and the pointers the call cannot do without (`required`, and a QuanONet's trunk).
+// count: the rows of the call, or the steps of a schedule; row0: 0 where the call has none.
+inline int noisy_call_check(const NoisyKind& k, const qhea_model_desc* desc, const double* ham_diag, const qhea_noise* noise,
+                            int64_t row0, int64_t count, const double* trunk, std::initializer_list<const void*> required,
+                            void* workspace, void* stream, NoisyCall& c) {
+    const int rc = model_info(desc, c.mi);
+    if (rc != QHEA_OK) return rc;
+    if (k.trajectories) c.T = noise_values(noise);
+    if (k.trajectories ? c.T < 1 : !rates_ok(noise)) return QHEA_EINVAL;
+    if (c.mi.n < k.nmin || c.mi.n > k.nmax) return QHEA_EUNSUPPORTED;
+    if (!pauli_ok(desc->ham_pauli, ham_diag)) return QHEA_EINVAL;
+    if (k.inverse_walk && !(log10_amplification(c.mi, noise) <= kMaxLog10Amplification)) return QHEA_EUNSUPPORTED;
+    if (count < 0 || row0 < 0) return QHEA_EINVAL;
+    c.empty = count == 0;
+    if (c.empty) return QHEA_OK;
+    for (const void* p : required)
+        if (!p) return QHEA_EINVAL;
+    if (desc->model == QHEA_MODEL_QUANONET && !trunk) return QHEA_EINVAL;
+    c.st = static_cast<hipStream_t>(stream);
+    c.ws = static_cast<char*>(workspace);
+    return QHEA_OK;
+}
+
 inline unsigned long long threshold(double p) { return (unsigned long long)(p * 4294967296.0); }
 
 // everything of NoiseArgs that the descriptor and the noise setting fix; the caller adds the workspace pointers
-inline NoiseArgs noise_args(const qhea_model_desc* desc, const NoiseShape& ns, const qhea_noise* noise, const double* params,
+inline NoiseArgs noise_args(const qhea_model_desc* desc, const ModelInfo& mi, const qhea_noise* noise, const double* params,
                             const double* ham_diag, int64_t row0, int64_t batch, int64_t T) {
     NoiseArgs a{};
     a.diag = ham_diag;
-    a.bias = ns.off_bias >= 0 ? params + ns.off_bias : nullptr;
+    a.bias = mi.has_bias ? params + mi.off_bias : nullptr;
     a.off = desc->ham_offset; a.co = desc->ham_coeff; a.q = noise->readout;
     a.thr1 = threshold(noise->p1); a.thr2 = threshold(noise->p2); a.thrq = threshold(noise->readout);
-    a.B = batch; a.row0 = row0; a.T = T; a.tiles = (int)((T + kTile - 1) / kTile); a.E = ns.E; a.pauli = desc->ham_pauli;
+    a.B = batch; a.row0 = row0; a.T = T; a.tiles = (int)((T + kTile - 1) / kTile); a.E = (int)mi.sh.E; a.pauli = desc->ham_pauli;
     a.shots = noise->shots > 0 ? 1 : 0;
     unsigned locs = 0;
     for (int g = 0; g < 2; ++g) {
-        a.nb[g] = ns.nb[g]; a.ld[g] = ns.ld[g];
-        locs += (unsigned)ns.nb[g] * (unsigned)(ns.n + 2 * ns.n * ns.ld[g]);
+        a.nb[g] = mi.nb[g]; a.ld[g] = mi.ld[g];
+        locs += (unsigned)mi.nb[g] * (unsigned)(mi.n + 2 * mi.n * mi.ld[g]);
     }
     a.L = locs;
     a.key0 = (unsigned)noise->seed; a.key1 = (unsigned)(noise->seed >> 32);
@@ -104,5 +156,58 @@ inline NoiseArgs noise_args(const qhea_model_desc* desc, const NoiseShape& ns, c
 // noisy_finish_kernel (hea_noise.hip) on `st`: row r's tiles added in tile order, mean (+ bias) and standard error
 int launch_noisy_finish(const double2* partial, int tiles, int64_t B, int64_t T, const double* bias, double* pred, double* se,
                         hipStream_t st);
+
+// A trajectory unit: the qubit counts of its kernels, whether it keeps ham_diag under the readout confusion in a region of its
+// own (`mix`: 2 x 2^n doubles, NULL without one), and its launch of the trajectory kernel for a.B * a.tiles work items
+struct TrajUnit {
+    int nmin, nmax;
+    bool wide;
+    int (*launch)(const NoiseArgs& a, int n, double* mix, hipStream_t st);
+};
+
+struct TrajLayout { size_t off_gates, off_cs, off_part, off_mix /* wide units */, total; int tiles; };
+inline TrajLayout traj_layout(const TrajUnit& u, const ModelInfo& mi, int64_t B, int64_t T) {
+    TrajLayout L{};
+    L.tiles = (int)((T + kTile - 1) / kTile);
+    const TableLayout t = table_layout(mi, B);
+    L.off_gates = t.off_gates; L.off_cs = t.off_cs;
+    size_t p = t.end;
+    L.off_part = p; p = align256(p + (size_t)B * L.tiles * sizeof(double2));
+    if (u.wide) { L.off_mix = p; p = align256(p + ((size_t)2 << mi.n) * sizeof(double)); }
+    L.total = p;
+    return L;
+}
+
+// qhea_model_noisy_workspace_bytes answers for every qubit count, ..._noisy_wide_workspace_bytes for its own from nmin on
+inline size_t traj_workspace_bytes(const TrajUnit& u, const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise) {
+    ModelInfo mi;
+    const int64_t T = noise_values(noise);
+    if (T < 1 || batch < 0 || model_info(desc, mi) != QHEA_OK || (u.wide && mi.n < u.nmin)) return 0;
+    return traj_layout(u, mi, batch, T).total;
+}
+
+// qhea_model_forward_noisy and qhea_model_forward_noisy_wide: checks, prep, the unit's trajectories, finish
+inline int traj_forward(const TrajUnit& u, const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
+                        const double* trunk, const double* params, const double* ham_diag, const qhea_noise* noise, double* pred,
+                        double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
+    NoisyCall c;
+    int rc = noisy_call_check({u.nmin, u.nmax, true, false}, desc, ham_diag, noise, row0, batch, trunk, {branch, params, pred},
+                              workspace, stream, c);
+    if (rc != QHEA_OK || c.empty) return rc;
+    const TrajLayout L = traj_layout(u, c.mi, batch, c.T);
+    if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
+    if (u.wide && (int64_t)batch * L.tiles > (int64_t)INT_MAX) return QHEA_EINVAL;      // one workgroup per (row, tile)
+    double4* gates = reinterpret_cast<double4*>(c.ws + L.off_gates);
+    double2* cs = reinterpret_cast<double2*>(c.ws + L.off_cs);
+    double2* part = reinterpret_cast<double2*>(c.ws + L.off_part);
+    rc = launch_prep_model(desc, c.mi, batch, branch, trunk, params, gates, cs, c.ws, c.st);
+    if (rc != QHEA_OK) return rc;
+
+    NoiseArgs a = noise_args(desc, c.mi, noise, params, ham_diag, row0, batch, c.T);
+    a.gates = gates; a.cs = cs; a.partial = part;
+    rc = u.launch(a, c.mi.n, u.wide ? reinterpret_cast<double*>(c.ws + L.off_mix) : nullptr, c.st);
+    if (rc != QHEA_OK) return rc;
+    return launch_noisy_finish(part, L.tiles, batch, c.T, a.bias, pred, stderr_out, c.st);
+}
 
 }  // namespace qhea

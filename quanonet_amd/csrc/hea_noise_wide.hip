@@ -444,19 +444,25 @@ int launch_wide(const NoiseArgs& a, const double* hd, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 
-struct WideLayout { size_t off_gates, off_cs, off_part, off_mix, total; int tiles; };
-
-WideLayout wide_layout(const NoiseShape& ns, int64_t B, int64_t T) {
-    WideLayout L{};
-    L.tiles = (int)((T + kTile - 1) / kTile);
-    size_t p = 256;                                                      // header (prep_model_kernel stamps it)
-    L.off_gates = p; p = align256(p + (size_t)(ns.blk + 2) * ns.n * 2 * sizeof(double4));
-    L.off_cs = p;    p = align256(p + (size_t)B * ns.E * sizeof(double2));
-    L.off_part = p;  p = align256(p + (size_t)B * L.tiles * sizeof(double2));
-    L.off_mix = p;   p = align256(p + ((size_t)2 << ns.n) * sizeof(double));
-    L.total = p;
-    return L;
+// ham_diag goes through readout_mix_kernel first where the kernels read it mixed (expectation mode)
+int launch_noisy_wide(const NoiseArgs& a, int n, double* mix, hipStream_t st) {
+    const double* hd = nullptr;
+    if (a.diag && !a.shots) {
+        hipLaunchKernelGGL(readout_mix_kernel, dim3(1), dim3(256), 0, st, a.diag, a.q, n, mix);
+        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+        hd = mix + ((size_t)((n - 1) & 1) << n);
+    }
+    switch (n) {
+        case 7: return launch_wide<7>(a, hd, st);
+        case 8: return launch_wide<8>(a, hd, st);
+        case 9: return launch_wide<9>(a, hd, st);
+        case 10: return launch_wide<10>(a, hd, st);
+        case 11: return launch_wide<11>(a, hd, st);
+        case 12: return launch_wide<12>(a, hd, st);
+        default: return QHEA_EUNSUPPORTED;
+    }
 }
+constexpr TrajUnit kWideUnit{7, QHEA_MAX_QUBITS, true, launch_noisy_wide};   // qhea_model_forward_noisy is the path below 7
 
 }  // namespace
 }  // namespace qhea
@@ -466,57 +472,14 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_noisy_wide_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise) {
-    NoiseShape ns;
-    const int64_t T = noise_values(noise);
-    if (T < 1 || batch < 0 || noise_model_shape(desc, ns) != QHEA_OK || ns.n < 7) return 0;
-    return wide_layout(ns, batch, T).total;
+    return traj_workspace_bytes(kWideUnit, desc, batch, noise);
 }
 
 int qhea_model_forward_noisy_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
                                   const double* trunk, const double* params, const double* ham_diag, const qhea_noise* noise,
                                   double* pred, double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
-    NoiseShape ns;
-    int rc = noise_model_shape(desc, ns);
-    if (rc != QHEA_OK) return rc;
-    const int64_t T = noise_values(noise);
-    if (T < 1) return QHEA_EINVAL;
-    if (ns.n < 7) return QHEA_EUNSUPPORTED;                              // qhea_model_forward_noisy is the path for those
-    const bool pauli_ok = desc->ham_pauli == QHEA_PAULI_Z || ((desc->ham_pauli == QHEA_PAULI_X ||
-                                                               desc->ham_pauli == QHEA_PAULI_Y) && !ham_diag);
-    if (!pauli_ok || batch < 0 || row0 < 0) return QHEA_EINVAL;
-    if (batch == 0) return QHEA_OK;
-    if (!branch || !params || !pred || (desc->model == QHEA_MODEL_QUANONET && !trunk)) return QHEA_EINVAL;
-    const WideLayout L = wide_layout(ns, batch, T);
-    if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
-    if ((int64_t)batch * L.tiles > (int64_t)INT_MAX) return QHEA_EINVAL;  // one workgroup per (row, tile)
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
-    double2* part = reinterpret_cast<double2*>(ws + L.off_part);
-    double* mix = reinterpret_cast<double*>(ws + L.off_mix);
-    rc = launch_noise_prep(desc, batch, branch, trunk, params, gates, cs, ws, st);
-    if (rc != QHEA_OK) return rc;
-
-    NoiseArgs a = noise_args(desc, ns, noise, params, ham_diag, row0, batch, T);
-    a.gates = gates; a.cs = cs; a.partial = part;
-    const double* hd = nullptr;
-    if (ham_diag && !a.shots) {
-        hipLaunchKernelGGL(readout_mix_kernel, dim3(1), dim3(256), 0, st, ham_diag, a.q, ns.n, mix);
-        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        hd = mix + ((size_t)((ns.n - 1) & 1) << ns.n);
-    }
-    switch (ns.n) {
-        case 7: rc = launch_wide<7>(a, hd, st); break;
-        case 8: rc = launch_wide<8>(a, hd, st); break;
-        case 9: rc = launch_wide<9>(a, hd, st); break;
-        case 10: rc = launch_wide<10>(a, hd, st); break;
-        case 11: rc = launch_wide<11>(a, hd, st); break;
-        case 12: rc = launch_wide<12>(a, hd, st); break;
-        default: return QHEA_EUNSUPPORTED;
-    }
-    if (rc != QHEA_OK) return rc;
-    return launch_noisy_finish(part, L.tiles, batch, T, a.bias, pred, stderr_out, st);
+    return traj_forward(kWideUnit, desc, row0, batch, branch, trunk, params, ham_diag, noise, pred, stderr_out, workspace,
+                        workspace_bytes, stream);
 }
 
 }  // extern "C"
