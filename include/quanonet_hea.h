@@ -413,6 +413,70 @@ int    qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n
                                           size_t workspace_bytes, void* stream);
 
 /*
+ * Exact noisy forward under a calibrated device noise model: pred and shot_std of qhea_model_forward_noisy_exact, with the three
+ * numbers of qhea_noise replaced by what a backend's calibration reports -- a gate error per wire and per coupled pair, a
+ * readout error per qubit and direction, T1 and T2 per qubit -- and with the time the sequential CNOT ring takes.  Replaces the
+ * question the reference's ibm_inference.py profile_hardware prepares (it reads exactly these quantities before a job).
+ *
+ * Timeline of sub-layer s of a block (all wires of a layer act at once; the ring is sequential):
+ *   - if s is the block's first sub-layer: an encoding layer of duration t_rx, RX on every wire;
+ *   - a rotation layer of duration t_rot, the fused RY RZ RY on every wire;
+ *   - n CNOT slots of duration t_cx each; slot j holds CNOT(control (j+1) mod n -> target j).
+ *   A block with linear depth 0 has its encoding layer only.
+ * Channels, in this order:
+ *   - after a one-qubit gate on wire q: depolarizing with p1[q] (rho -> (1 - p) rho + p/3 sum_P P rho P, as in qhea_noise), then
+ *     relaxation of wire q for the layer's duration;
+ *   - in slot j: the CNOT, then two-qubit depolarizing with p2[j] on its two wires (each of the 15 non-identity Pauli pairs
+ *     p2[j]/15; lam = 16 p2[j] / 15 in the closed form), then relaxation for t_cx on both of its wires;
+ *   - if idle != 0: every other wire also relaxes for t_cx in that slot;
+ *   - read-out: the noiseless basis change for X / Y as above; then bit q reads 1 given 0 with probability readout01[q] and 0
+ *     given 1 with probability readout10[q], independently per bit.
+ * Relaxation of wire q for time t is the zero-temperature T1 / T2 channel on that wire's 2 x 2 blocks:
+ *     rho01, rho10 <- exp(-t / t2[q]) (rho01, rho10);   z <- exp(-t / t1[q]) z + (1 - exp(-t / t1[q])) tr,
+ *   z = rho00 - rho11, tr = rho00 + rho11.  t1 or t2 = +infinity means no decay.  It is not a Pauli channel: it is non-unital and
+ *   pulls the wire towards |0>.
+ * Closed form.  Every one-wire channel here is phase-covariant, a triple (off, a, b): off-diagonals times `off`, z -> a z + b tr,
+ *     rho00' = (1 + a + b)/2 rho00 + (1 - a + b)/2 rho11,   rho11' = (1 - a - b)/2 rho00 + (1 + a - b)/2 rho11.
+ *   Depolarizing is (1 - 4p/3, 1 - 4p/3, 0), relaxation (exp(-t/t2), exp(-t/t1), 1 - exp(-t/t1)); "second after first" is
+ *   off = off2 off1, a = a2 a1, b = a2 b1 + b2.  Relaxation of one wire commutes with everything on other wires and consecutive
+ *   relaxations of one wire add their times, so the model folds exactly into four channel sites per wire (D = depolarizing,
+ *   R = relaxation):
+ *     site                                              wire 0                       wire q >= 1
+ *     0 ENC (after the encoding RX)                     D(p1[0]) then R(t_rx)        D(p1[q]) then R(t_rx)
+ *     1 ROT (after the fused rotation)                  D(p1[0]) then R(t_rot)       D(p1[q]) then R(t_rot + (q-1) t_cx)
+ *     2 CTL (after the slot where the wire is control)  R(t_cx)                      R(t_cx)
+ *     3 TGT (after the slot where the wire is target)   R((n-1) t_cx)                R((n-q) t_cx)
+ *   With idle = 0 every CTL and TGT entry is R(t_cx) and ROT carries t_rot only.
+ * qhea_device_noise_tables (host only, no device needed) returns that composition: chan[site][q] = (off, a, b) as [4][n][3]
+ * doubles and lam2[j] = 16 p2[j] / 15; QHEA_EINVAL for a setting the forward call refuses with it (n = 2..12).  It is
+ * deliberately wider than the forward call (n <= 6): the composition is host arithmetic that holds for any ring, and the
+ * forward call checks a setting for n = 7..12 with the same code before it answers QHEA_EUNSUPPORTED.
+ * qhea_model_forward_noisy_device_exact: arguments, workspace (qhea_model_exact_noisy_workspace_bytes), outputs, launches (two,
+ * hipGraph-capturable), determinism (bitwise independent of batch and chunking, no atomics) and cost of
+ * qhea_model_forward_noisy_exact.  With p1[q] = p1, p2[j] = p2, readout01 = readout10 = readout, infinite t1 / t2 it computes
+ * that call's quantity (to rounding; the channels are evaluated in the triple form), with all rates 0 the ideal model.
+ * Scope: n = 2..6, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.  Out of scope: thermal
+ * excited-state population, crosstalk, routing (the ring is taken to be native on the chosen wires), gradients.
+ * Errors, all before anything is launched or any device is touched, outputs untouched: QHEA_EINVAL for a NULL setting or a NULL
+ * array in it, n_wires != n, a probability outside [0, 1] or NaN, a duration that is negative, NaN or infinite, t1 or t2 <= 0 or
+ * NaN, t2 > 2 t1; then QHEA_EUNSUPPORTED for n >= 7; then the errors of qhea_model_forward_noisy_exact.
+ */
+typedef struct qhea_device_noise {
+    int32_t n_wires, idle;      /* n_wires must equal the model's n; idle != 0: wires outside a slot relax during it */
+    const double *p1, *p2, *readout01, *readout10, *t1, *t2;   /* HOST, [n_wires] each; p2[j] belongs to slot j */
+    double t_rx, t_rot, t_cx;   /* durations in the unit of t1 / t2 */
+} qhea_device_noise;
+
+int qhea_device_noise_tables(int n, const qhea_device_noise* dn /*HOST*/, double* chan /*HOST [4][n][3]*/,
+                             double* lam2 /*HOST [n]*/);
+int qhea_model_forward_noisy_device_exact(const qhea_model_desc* desc, int64_t batch,
+                                          const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                          const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                          const qhea_device_noise* dn /*HOST*/,
+                                          double* pred /*DEVICE [B]*/, double* shot_std /*DEVICE [B] or NULL*/,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the
  * SAME parameters -- the chunk loop of PTSolver.evaluate / infer.predict (solvers/solver_pt.py:299-310, infer.py:274-289) in
  * one host call.  The layer records depend on the parameters alone, so one preparation launch serves all chunks of

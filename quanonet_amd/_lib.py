@@ -38,7 +38,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_noisy_wide_workspace_bytes', 'qhea_model_forward_noisy_wide',
            'qhea_model_exact_noisy_workspace_bytes', 'qhea_model_forward_noisy_exact',
            'qhea_model_exact_noisy_grad_workspace_bytes', 'qhea_model_exact_noisy_log10_amplification',
-           'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact']
+           'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact',
+           'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact']
 
 
 class ModelDesc(ctypes.Structure):
@@ -61,8 +62,16 @@ class NoiseParams(ctypes.Structure):
                 ('trajectories', ctypes.c_int64), ('seed', ctypes.c_uint64)]
 
 
+class DeviceNoiseParams(ctypes.Structure):
+    """Mirror of `qhea_device_noise` (include/quanonet_hea.h): per-wire gate, readout and relaxation figures of a device and
+    the layer durations.  The six arrays are host memory that the caller keeps alive for as long as the record is used."""
+    _fields_ = [('n_wires', ctypes.c_int32), ('idle', ctypes.c_int32)] + \
+               [(name, ctypes.POINTER(ctypes.c_double)) for name in ('p1', 'p2', 'readout01', 'readout10', 't1', 't2')] + \
+               [('t_rx', ctypes.c_double), ('t_rot', ctypes.c_double), ('t_cx', ctypes.c_double)]
+
+
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 530           # 0.5.3: + qhea_model_forward_noisy_wide (noisy evaluation at n = 7..12)
+MIN_LIB_VERSION = 540           # 0.5.4: + qhea_model_forward_noisy_device_exact (exact evaluation under a device noise model)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -219,6 +228,11 @@ def load():
     lib.qhea_model_train_steps_noisy_exact.argtypes = [mdp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), dp, dp, dp, dp, dp, npp,
                                                        ctypes.POINTER(ctypes.c_double), dp, ctypes.c_int64, dp, dp,
                                                        ctypes.c_int64] + [ctypes.c_double] * 5 + [vp, ctypes.c_size_t, vp]
+    dnp = ctypes.POINTER(DeviceNoiseParams)
+    lib.qhea_device_noise_tables.restype = ctypes.c_int
+    lib.qhea_device_noise_tables.argtypes = [ctypes.c_int, dnp, f64p, f64p]
+    lib.qhea_model_forward_noisy_device_exact.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy_device_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, dnp, dp, dp, vp, ctypes.c_size_t, vp]
     _lib = lib
     return lib
 
@@ -773,6 +787,43 @@ def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None,
     if rc == -2:
         raise Unsupported("qhea_model_forward_noisy_exact: unsupported circuit (n >= 7)")
     _check(rc, 'qhea_model_forward_noisy_exact')
+    return pred, shot_std
+
+
+def device_noise_tables(n, noise):
+    """
+    qhea_device_noise_tables (host only, no device needed): (chan [4, n, 3], lam2 [n]) as numpy arrays -- the (off, a, b)
+    triples of the four channel sites per wire (ENC, ROT, CTL, TGT) and 16 p2[j] / 15 per CNOT slot for `noise`, a
+    DeviceNoiseParams.  Raises QheaError for a setting the library refuses.
+    """
+    import numpy as np
+    n = int(n)
+    chan = np.zeros((4, max(n, 0), 3), dtype=np.float64)
+    lam2 = np.zeros(max(n, 0), dtype=np.float64)
+    f64p = ctypes.POINTER(ctypes.c_double)
+    _check(load().qhea_device_noise_tables(n, ctypes.byref(noise), chan.ctypes.data_as(f64p), lam2.ctypes.data_as(f64p)),
+           'qhea_device_noise_tables')
+    return chan, lam2
+
+
+def model_forward_noisy_device_exact(desc, branch, trunk, params, noise, ham_diag=None, out=None, shot_std=None):
+    """
+    qhea_model_forward_noisy_device_exact on all rows of branch / trunk in ONE call: model_forward_noisy_exact with `noise` a
+    DeviceNoiseParams (per-wire rates, T1 / T2, layer durations).  Raises Unsupported for n >= 7 and QheaError for a bad noise
+    setting -- in both cases before anything is launched.
+    """
+    lib = load()
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
+    _dev_f64(shot_std, 'shot_std', (B,))
+    pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
+    ws = _sized_ws(branch.device, lib.qhea_model_exact_noisy_workspace_bytes, ctypes.byref(desc), int(B))
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_forward_noisy_device_exact(ctypes.byref(desc), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
+                                                       _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(shot_std),
+                                                       _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    if rc == -2:
+        raise Unsupported("qhea_model_forward_noisy_device_exact: unsupported circuit (n >= 7)")
+    _check(rc, 'qhea_model_forward_noisy_device_exact')
     return pred, shot_std
 
 

@@ -1554,7 +1554,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 530; }
+int qhea_version(void) { return 540; }
 
 const char* qhea_strerror(int code) {
     switch (code) {

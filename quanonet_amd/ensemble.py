@@ -209,5 +209,6 @@ class EnsembleSolver:
     def evaluate_noisy(self, noise, out_name=None, exact=False):
         """PTSolver.evaluate_noisy for every member (its best checkpoint; out_dir/out_name when given, never metric.json); returns
         the list of results.  Every member uses noise.seed, so the members see common random numbers: member differences are
-        not blurred by independent noise draws.  exact=True: every member's exact expectation instead (no draws at all)."""
+        not blurred by independent noise draws.  exact=True: every member's exact expectation instead (no draws at all); a
+        quanonet_amd.noise.DeviceNoise is evaluated that way only (ValueError with exact=False)."""
         return [m.evaluate_noisy(noise, out_name, exact=exact) for m in self.members]

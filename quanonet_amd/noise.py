@@ -4,7 +4,9 @@ questions of the reference's ibm_inference.py -- how many shots a model needs, w
 on the GPU before any QPU time is spent.  The noise model, the estimators and the random-number layout are stated in
 include/quanonet_hea.h.
 """
+import ctypes
 import dataclasses
+import math
 from dataclasses import dataclass
 
 import torch
@@ -52,6 +54,183 @@ class NoiseModel:
         return dataclasses.asdict(self)
 
 
+_PER_WIRE = ('p1', 'p2', 'readout01', 'readout10', 't1', 't2')
+_DURATIONS = ('t_rx', 't_rot', 't_cx')
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+@dataclass(frozen=True)
+class DeviceNoise:
+    """
+    The calibrated device noise model of qhea_device_noise (include/quanonet_hea.h), for the exact evaluation
+    (exact_noisy_predict, evaluate_noisy(exact=True)); n <= 6.
+    p1[q]: depolarizing probability after every single-qubit gate on wire q; p2[j]: two-qubit depolarizing probability after
+    the CNOT of ring slot j (control (j+1) mod n -> target j); readout01[q] / readout10[q]: probability that bit q reads 1
+    given 0 / 0 given 1; t1[q], t2[q]: relaxation times of wire q (math.inf: no decay; t2 <= 2 t1).  Each of the six is one
+    float for every wire or a sequence with one entry per wire.  t_rx, t_rot, t_cx: durations of the encoding layer, the
+    rotation layer and one CNOT slot, in the unit of t1 / t2.  idle: wires outside a CNOT slot relax during it (the ring is
+    sequential, so a sub-layer lasts n slots).  The defaults are the ideal circuit.
+    """
+    p1: object = 0.0
+    p2: object = 0.0
+    readout01: object = 0.0
+    readout10: object = 0.0
+    t1: object = math.inf
+    t2: object = math.inf
+    t_rx: float = 0.0
+    t_rot: float = 0.0
+    t_cx: float = 0.0
+    idle: bool = True
+
+    def __post_init__(self):
+        for name in _PER_WIRE:
+            v = getattr(self, name)
+            if not _number(v):
+                try:
+                    v = tuple(v)
+                except TypeError:
+                    v = (v,)
+                if not v or not all(_number(x) for x in v):
+                    raise ValueError(f"DeviceNoise.{name} must be a number or a non-empty sequence of numbers "
+                                     f"(got {getattr(self, name)!r})")
+                v = tuple(float(x) for x in v)
+                object.__setattr__(self, name, v)
+            for x in (v if isinstance(v, tuple) else (v,)):
+                if name in ('t1', 't2'):
+                    if not x > 0.0:
+                        raise ValueError(f"DeviceNoise.{name} must be > 0 (got {x!r})")
+                elif not 0.0 <= x <= 1.0:
+                    raise ValueError(f"DeviceNoise.{name} must lie in [0, 1] (got {x!r})")
+        lengths = {len(getattr(self, name)) for name in _PER_WIRE if isinstance(getattr(self, name), tuple)}
+        if len(lengths) > 1:
+            raise ValueError(f"DeviceNoise: the per-wire sequences differ in length ({sorted(lengths)})")
+        wires = lengths.pop() if lengths else 1
+        for q in range(wires):
+            if self._at('t2', q) > 2.0 * self._at('t1', q):
+                raise ValueError(f"DeviceNoise: t2 must not exceed 2 t1 (wire {q}: t1 = {self._at('t1', q)!r}, "
+                                 f"t2 = {self._at('t2', q)!r})")
+        for name in _DURATIONS:
+            v = getattr(self, name)
+            if not _number(v) or not 0.0 <= v < math.inf:
+                raise ValueError(f"DeviceNoise.{name} must be a finite duration >= 0 (got {v!r})")
+        if not isinstance(self.idle, bool):
+            raise ValueError(f"DeviceNoise.idle must be a bool (got {self.idle!r})")
+
+    def _at(self, name, q):
+        v = getattr(self, name)
+        return v[q] if isinstance(v, tuple) else float(v)
+
+    def _wires(self, name, n):
+        v = getattr(self, name)
+        if isinstance(v, tuple):
+            if len(v) != n:
+                raise ValueError(f"DeviceNoise.{name} has {len(v)} entries, the circuit has {n} wires")
+            return v
+        return (float(v),) * n
+
+    def params(self, n):
+        """The C ABI's qhea_device_noise for an n-qubit circuit (the record keeps its six arrays alive)."""
+        n = int(n)
+        arrays = [(ctypes.c_double * n)(*self._wires(name, n)) for name in _PER_WIRE]
+        f64p = ctypes.POINTER(ctypes.c_double)
+        rec = _lib.DeviceNoiseParams(n, 1 if self.idle else 0, *[ctypes.cast(a, f64p) for a in arrays], float(self.t_rx),
+                                     float(self.t_rot), float(self.t_cx))
+        rec._arrays = arrays
+        return rec
+
+    def tables(self, n):
+        """(chan [4, n, 3], lam2 [n]) of qhea_device_noise_tables: the (off, a, b) triple of every channel site (ENC, ROT, CTL,
+        TGT) and wire, with the idle decay folded in, and 16 p2[j] / 15 per CNOT slot.  No device needed."""
+        return _lib.device_noise_tables(n, self.params(n))
+
+    def asdict(self):
+        """JSON-serialisable (json.dumps(..., allow_nan=False) accepts it): per-wire sequences as lists, an infinite t1 / t2
+        as the string 'Infinity' -- what float() reads back, so DeviceNoise.fromdict(json.loads(...)) restores the setting."""
+        def enc(v):
+            if isinstance(v, tuple):
+                return [enc(x) for x in v]
+            return 'Infinity' if isinstance(v, float) and math.isinf(v) else v
+        return {f.name: enc(getattr(self, f.name)) for f in dataclasses.fields(self)}
+
+    @classmethod
+    def fromdict(cls, d):
+        """The inverse of asdict."""
+        def dec(v):
+            if isinstance(v, (list, tuple)):
+                return tuple(dec(x) for x in v)
+            return float(v) if isinstance(v, str) else v
+        return cls(**{k: dec(v) for k, v in d.items()})
+
+    @classmethod
+    def uniform(cls, noise_model):
+        """The NoiseModel's channels as a DeviceNoise: its p1 on every wire, its p2 in every slot, its symmetric readout flip in
+        both directions, no relaxation.  (shots, trajectories and seed have no counterpart: the evaluation is exact.)"""
+        return cls(p1=float(noise_model.p1), p2=float(noise_model.p2), readout01=float(noise_model.readout),
+                   readout10=float(noise_model.readout))
+
+    @classmethod
+    def from_calibration(cls, cal, wires, pulses_rx=2, pulses_rot=2, idle=True):
+        """
+        The model for the ring placed on the physical qubits `wires` (wire q of the circuit = qubit wires[q]), from a plain
+        dict of the quantities the reference's profile_hardware reads from a backend:
+          cal['qubits'][str(k)]: 'T1', 'T2', 'sx_error', 'sx_length', and 'readout_error' or the pair 'prob_meas1_prep0' /
+                                 'prob_meas0_prep1' (the pair wins where both are given);
+          cal['pairs']['a_b']:   'gate_error', 'gate_length' of the two-qubit gate on qubits a and b, either order.
+        Average gate infidelities r become this project's depolarizing probabilities: p = 3 r / 2 for one qubit, p = 5 r / 4 for
+        two.  A layer of `pulses` sx pulses has p1 = 1 - (1 - p_sx)^pulses and lasts pulses * sx_length (the longest of the
+        wires: the layer is one event on every wire at once); t_cx is the longest gate_length on the ring.  pulses_rx and
+        pulses_rot must be equal (ValueError otherwise): the model has one p1 per wire for both of its layers, so two pulse
+        counts would have no setting that states them.  `idle` is DeviceNoise.idle.  All times in the unit the calibration
+        uses.  A ring edge without a calibrated pair raises ValueError.  T2 above 2 T1 (a calibration can report it within
+        its error bars) is clipped.
+        """
+        wires = [int(k) for k in wires]
+        n = len(wires)
+        if n < 2 or len(set(wires)) != n:
+            raise ValueError(f"from_calibration: wires must name at least two distinct qubits (got {wires})")
+        qubits, pairs = cal.get('qubits', {}), cal.get('pairs', {})
+        per = []
+        for k in wires:
+            if str(k) not in qubits:
+                raise ValueError(f"from_calibration: qubit {k} is not in the calibration")
+            per.append(qubits[str(k)])
+        slots = []
+        for j in range(n):                                               # slot j: control wires[(j + 1) % n] -> target wires[j]
+            a, b = wires[(j + 1) % n], wires[j]
+            edge = pairs.get(f'{a}_{b}', pairs.get(f'{b}_{a}'))
+            if edge is None:
+                raise ValueError(f"from_calibration: ring edge ({a}, {b}) has no calibrated two-qubit gate; choose wires whose "
+                                 "ring is native on the device (routing is out of scope)")
+            slots.append(edge)
+
+        def layer_p1(c, pulses):
+            return 1.0 - (1.0 - min(1.0, 1.5 * float(c['sx_error']))) ** int(pulses)
+        if pulses_rx != pulses_rot:
+            # one p1 per wire in the model: a wire's two layers must compile to the same number of pulses
+            raise ValueError("from_calibration: pulses_rx and pulses_rot must be equal (the model has one p1 per wire)")
+        sx_len = max(float(c['sx_length']) for c in per)
+        r01 = [float(c.get('prob_meas1_prep0', c.get('readout_error', 0.0))) for c in per]
+        r10 = [float(c.get('prob_meas0_prep1', c.get('readout_error', 0.0))) for c in per]
+        t1 = [float(c['T1']) for c in per]
+        t2 = [min(float(c['T2']), 2.0 * float(c['T1'])) for c in per]
+        return cls(p1=[layer_p1(c, pulses_rx) for c in per], p2=[min(1.0, 1.25 * float(e['gate_error'])) for e in slots],
+                   readout01=r01, readout10=r10, t1=t1, t2=t2, t_rx=int(pulses_rx) * sx_len, t_rot=int(pulses_rot) * sx_len,
+                   t_cx=max(float(e['gate_length']) for e in slots), idle=idle)
+
+
+def _uniform_only(noise, who, why):
+    if isinstance(noise, DeviceNoise):
+        raise ValueError(f"{who} takes a NoiseModel, not a DeviceNoise: {why}; exact_noisy_predict and "
+                         "evaluate_noisy(exact=True) evaluate a DeviceNoise")
+
+
+_TRAJECTORY_WHY = "the trajectory kernels sample Pauli errors only and relaxation is not a Pauli channel"
+_GRADIENT_WHY = "the gradient's reverse walk inverts the uniform depolarizing channels only"
+
+
 def _model_inputs(model, inputs):
     ins = list(inputs) if isinstance(inputs, (tuple, list)) else [inputs]
     ins = [t.contiguous() for t in ins]
@@ -85,6 +264,7 @@ def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
     (the flat layout of the header), ham_diag as the trainer takes it.  n <= 6 runs qhea_model_forward_noisy, n = 7..12
     qhea_model_forward_noisy_wide: one quantity, one random stream, one code path per n.
     """
+    _uniform_only(noise, 'noisy_predict', _TRAJECTORY_WHY)
     desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'noisy_predict')
     N = branch.shape[0]
     pred = torch.empty(N, dtype=torch.float64, device=branch.device)
@@ -105,17 +285,22 @@ def exact_noisy_predict(model, inputs, noise, chunk_rows=16384):
     expectation under `noise` (its p1, p2 and readout; shots, trajectories and seed are ignored) and the exact standard
     deviation of one shot, so that a row's standard error at S shots is shot_std / sqrt(S).  No sampling error, no random
     numbers; n <= 6.  Rows go in chunks of `chunk_rows`; the result is bitwise the same for any chunking.
+    `noise` may also be a DeviceNoise: the same two quantities under the calibrated device model
+    (qhea_model_forward_noisy_device_exact).
     """
     desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'exact_noisy_predict')
     N = branch.shape[0]
     pred = torch.empty(N, dtype=torch.float64, device=branch.device)
     shot_std = torch.empty(N, dtype=torch.float64, device=branch.device)
     chunk = max(1, int(chunk_rows))
-    nz = noise.params()
+    if isinstance(noise, DeviceNoise):
+        forward, nz = _lib.model_forward_noisy_device_exact, noise.params(desc.n_qubits)
+    else:
+        forward, nz = _lib.model_forward_noisy_exact, noise.params()
     for s in range(0, N, chunk):
         e = min(N, s + chunk)
-        _lib.model_forward_noisy_exact(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, ham_diag=ham_diag,
-                                       out=pred[s:e], shot_std=shot_std[s:e])
+        forward(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, ham_diag=ham_diag, out=pred[s:e],
+                shot_std=shot_std[s:e])
     return pred.unsqueeze(-1), shot_std
 
 
@@ -127,6 +312,7 @@ def amplification(model, noise):
     """
     if not hasattr(model, 'fused_desc'):
         raise TypeError("amplification takes a QuanONetPT or HEAQNNPT model")
+    _uniform_only(noise, 'amplification', _GRADIENT_WHY)
     return _lib.model_exact_noisy_log10_amplification(model.fused_desc(), noise.params())
 
 
@@ -137,6 +323,7 @@ def exact_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
     sum (pred - y)^2 and sum y^2.  inv_batch_total defaults to 1 / rows (the mean); a shard of a larger batch passes the global
     value.  The gradient is computed by the adjoint walk through the density matrix: no sampling, n <= 6.
     """
+    _uniform_only(noise, 'exact_noisy_loss_and_grad', _GRADIENT_WHY)
     desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'exact_noisy_loss_and_grad')
     B = branch.shape[0]
     y = y.detach().to(torch.float64).reshape(-1).contiguous()

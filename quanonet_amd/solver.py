@@ -230,9 +230,10 @@ def _train_noise(v):
     """config value / argument `train_noise` -> NoiseModel or None (a NoiseModel, or a dict of its fields)"""
     if v is None:
         return None
-    from .noise import NoiseModel
+    from .noise import _GRADIENT_WHY, NoiseModel, _uniform_only
     if isinstance(v, NoiseModel):
         return v
+    _uniform_only(v, 'train_noise', _GRADIENT_WHY)
     if isinstance(v, dict):
         return NoiseModel(**v)
     raise ValueError(f"train_noise must be a quanonet_amd.noise.NoiseModel or a dict of its fields (got {type(v).__name__})")
@@ -871,11 +872,14 @@ class PTSolver:
         out_dir/out_name when out_name is given and never touches metric.json (the run's "completed" marker).  Single rank.
         exact=True: the metrics of the exact expectation under the noise channels (exact_noisy_predict; no sampling error,
         noise.shots / trajectories / seed ignored), with 'exact': True and 'mean_shot_std' (the rows' mean one-shot standard
-        deviation) in place of 'mean_stderr'.
+        deviation) in place of 'mean_stderr'.  A quanonet_amd.noise.DeviceNoise (per-wire rates, T1 / T2, the ring's idle
+        decay) is evaluated with exact=True only.
         """
-        from .noise import exact_noisy_predict, noisy_predict
+        from .noise import _TRAJECTORY_WHY, _uniform_only, exact_noisy_predict, noisy_predict
         if self.world > 1:
             raise RuntimeError("evaluate_noisy runs on one rank (world_size == 1)")
+        if not exact:
+            _uniform_only(noise, 'evaluate_noisy(exact=False)', _TRAJECTORY_WHY)
         if self.best_model_path and os.path.exists(self.best_model_path):
             sd = torch.load(self.best_model_path, map_location=self.device, weights_only=True)
             self.model.load_state_dict(sd)
