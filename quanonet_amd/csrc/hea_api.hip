@@ -128,6 +128,23 @@ __device__ inline GateZ gate_zyz(const double2& ha, const double2& hb, const dou
     return g;
 }
 
+// Tangent form of the split records' RY part (hea_zyz.hpp, SplitCoef): per wire q < 4 the gate's t = s / c, and the
+// sub-layer's scale P = c0 c1 c2 c3 that wire 4's coefficients carry.  A cosine below 2^-100 in magnitude is replaced by
+// +-2^-100 first (sign kept, +0 -> +): that moves the state by < 1e-30 and keeps t, and four such gates' P t's, finite.
+// ONE definition for every kernel that writes records (they are compared bitwise): the same operands in the same order.
+__device__ __forceinline__ double tan_cos(double c) {
+    constexpr double kTiny = 0x1p-100;
+    return fabs(c) < kTiny ? (signbit(c) ? -kTiny : kTiny) : c;
+}
+__device__ __forceinline__ double tan_t(const GateZ& g) {
+#pragma clang fp contract(off)
+    return g.s / tan_cos(g.c);
+}
+__device__ __forceinline__ double tan_scale(const GateZ* z /* the sub-layer's five gates */) {
+#pragma clang fp contract(off)
+    return (tan_cos(z[0].c) * tan_cos(z[1].c)) * (tan_cos(z[2].c) * tan_cos(z[3].c));
+}
+
 // source index of the CNOT ring as a permutation of basis indices (n <= 5): after the ring, amplitude k is the old
 // amplitude ring_src_index(n, k)  (== ring_source<N>(lane, false) >> 2 of hea_device.hpp)
 __device__ __forceinline__ int ring_src_index(int n, int k) {
@@ -252,9 +269,15 @@ __device__ __forceinline__ void prep_layer_records(const LayerInfo& cur, const L
         if (cur.kind == 1) {    // (an RX chunk's record keeps this part for the next sub-layer's axes, written by ITS block)
             double2 e = make_double2(zc[q].c, var ? zc[q].s : -zc[q].s);
             store_through(reinterpret_cast<double2*>(out + kRecRy + q * 32 + var * 16), e);
-            if (srec) {     // wire 4: the swap form's variants (c, -s) / (s, c)
-                if (q == 4 && var == 1) e = make_double2(zc[q].s, zc[q].c);
-                store_through(reinterpret_cast<double2*>(srec + (long)l * kRecBytes + kSRecRy + q * 32 + var * 16), e);
+            if (srec) {     // (n = 5) wires 0..3: -t / +t; wire 4: the swap form's variants P (c, -s) / P (s, c)
+                char* sry = srec + (long)l * kRecBytes + kSRecRy;
+                if (q < 4) {
+                    const double t = tan_t(zc[q]);
+                    store_through(reinterpret_cast<double*>(sry + q * 16 + var * 8), var ? t : -t);
+                } else {
+                    const double P = tan_scale(zc), pc = P * zc[4].c, ps = P * zc[4].s;
+                    store_through(reinterpret_cast<double2*>(sry + 64 + var * 16), var ? make_double2(ps, pc) : make_double2(pc, -ps));
+                }
             }
         }
     }

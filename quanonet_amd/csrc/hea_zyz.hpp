@@ -323,6 +323,8 @@ __device__ __forceinline__ void zyz_forward(double (&re)[1], double (&im)[1], co
 // ---------------------------------------------------------------------------------------
 template <int K> using CtSlot = std::integral_constant<int, K>;
 struct RtSlot { int b; };
+template <class T> struct is_ct_slot : std::false_type {};
+template <int K> struct is_ct_slot<CtSlot<K>> : std::true_type {};
 constexpr int kBSlots = 4, kBDist = 2;         // block slots per ring; blocks in flight beyond the one being read
 constexpr int kPadRecs = 9;                    // >= (kBDist + 1) * 3 records of padding before record 0 and after record L
 constexpr int kBlockRingBytes = kBSlots * 3 * kRecBytes;     // per streaming wave (LD = 2)
@@ -512,7 +514,8 @@ __device__ __forceinline__ void zyz_forward_fast(double (&re)[1], double (&im)[1
 // in the all-lane layout every gate is paid twice, once for the real and once for the imaginary part of the wave's
 // two samples.  An RY gate has REAL coefficients: it acts on the real parts and on the imaginary parts separately.
 // So a wave may carry ONE sample with lane = k + 32 p  (k: basis index, p = 0: Re, 1: Im), one double per lane:
-//   RY on qubit q < 4   partner through DPP, x' = c x -/+ s x_partner           2 moves + 2 fp64 (was 4 + 4)
+//   RY on qubit q < 4   partner through DPP, x' = c x -/+ s x_partner           2 moves + 2 fp64 (was 4 + 4); ansatz
+//                       sub-layers: x' = x -/+ t x_partner, 2 moves + 1 fp64, the cosines folded into wire 4's gate
 //   RY on qubit 4       A = B = x; v_permlane16_swap(A, B) leaves the pair's bit-0 value in A and its bit-1 value in
 //                       B for both lanes: x' = u.x A + u.y B, u = (c, -s) / (s, c)    1 copy + 2 swaps + 2 fp64
 //   diagonal e^{i Phi}  the same through v_permlane32_swap (A = Re, B = Im): x' = alpha A + beta B with
@@ -527,7 +530,10 @@ __device__ __forceinline__ void zyz_forward_fast(double (&re)[1], double (&im)[1
 // Split records (prep_zyz_kernel), 1 KB per layer like the all-lane ones:
 //   bytes [0, 768)        per basis index k: [-sin, cos, sin] of Phi_l(k); lane (k, p) reads the 16 bytes at 24 k + 8 p
 //                         as (beta, alpha)
-//   bytes [768, 928)      ansatz layers: per wire 32 bytes, the lane-bit 0 / 1 variants (c, -s) / (c, +s); wire 4: (c, -s) / (s, c)
+//   bytes [768, 864)      ansatz layers, tangent form (SplitCoef below): wires 0..3 16 bytes each, the lane-bit 0 / 1 variants
+//                         -t / +t with t = s / c; then wire 4's 32 bytes, P (c, -s) / P (s, c) with P = c0 c1 c2 c3 of the
+//                         sub-layer (|c| < 2^-100 taken as +-2^-100: hea_api.hip, tan_cos).  RX chunks' records: the 15
+//                         chunk-gradient axes of the next sub-layer, bytes [768, 888)
 // (cos, sin) table of the encodings: 32 bytes per angle, wire = column % 5:
 //   wires 0..3 [c, -s | c, +s]   (the second half is what the all-lane reverse walk's native RX wants)
 //   wire 4     [s, c | c, -s]    (split: lane-bit 1 / 0 variants; all-lane reverse walk: (s, c), fields swapped)
@@ -556,14 +562,20 @@ __device__ __forceinline__ double2 cs32_packed(const double2* chunk /* entry of 
 
 template <bool HALVES>      // A, B <- the value of the lower / upper partner (rows of 16 lanes, or the wave's halves)
 __device__ __forceinline__ void swap_dup(double x, double& A, double& B) {
+    // Both swap operands must hold x, so x is copied once.  Handed the two halves of x the compiler copies them with two
+    // v_mov_b32; a 64-bit value it cannot see through (an empty asm statement tied to x, which stays live) it copies with ONE
+    // v_mov_b64.  The copy is the compiler's own instruction, so it also pads the swaps' two wait states after it itself.
+    double y;
+    asm("" : "=v"(y) : "0"(x));
     const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+    const unsigned lo2 = (unsigned)__double2loint(y), hi2 = (unsigned)__double2hiint(y);
     if constexpr (HALVES) {
-        const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        const auto l = __builtin_amdgcn_permlane32_swap(lo, lo2, false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap(hi, hi2, false, false);
         A = __hiloint2double((int)h[0], (int)l[0]); B = __hiloint2double((int)h[1], (int)l[1]);
     } else {
-        const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        const auto l = __builtin_amdgcn_permlane16_swap(lo, lo2, false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap(hi, hi2, false, false);
         A = __hiloint2double((int)h[0], (int)l[0]); B = __hiloint2double((int)h[1], (int)l[1]);
     }
 }
@@ -583,6 +595,24 @@ __device__ __forceinline__ void split_ry(double& x, const double2& u) {
         x = fma(u.y, xchg<(1 << Q)>(x), own);
     }
 }
+// Ansatz sub-layers, tangent form: RY = c (I -/+ t X~), t = s / c, so a gate on wire q < 4 is ONE fma, x' = x + t~ x_partner
+// with t~ this lane's signed entry (-t / +t by its bit q), and the layer's scalar c0 c1 c2 c3 rides in wire 4's swap-form
+// coefficients (prep_layer_records), whose gate costs what it did.  The inverse gate reads the entry's other variant.
+// Within a layer the state is off by the cosines not yet applied (forward: wire 4 runs last; reverse: first), at a layer's
+// ends -- where states are published, stored and gathered -- it is the state.
+struct SplitCoef { double2 dg; double t[4]; double2 g4; };
+template <int Q>
+__device__ __forceinline__ void split_ry_tan(double& x, double t) {
+    static_assert(Q < 4, "wire 4 keeps the swap form");
+    x = fma(t, xchg<(1 << Q)>(x), x);
+}
+__device__ __forceinline__ void split_gates(double& x, const LayerCoef<5>& c) {     // RX chunk: the table's (c, -/+s) entries
+    static_for<0, 5>([&](auto q) { split_ry<decltype(q)::value>(x, c.g[decltype(q)::value]); });
+}
+__device__ __forceinline__ void split_gates(double& x, const SplitCoef& c) {        // ansatz sub-layer
+    static_for<0, 4>([&](auto q) { split_ry_tan<decltype(q)::value>(x, c.t[decltype(q)::value]); });
+    split_ry<4>(x, c.g4);
+}
 
 template <int LD>
 struct SplitStream : BlockStream<5, LD, false> {
@@ -595,7 +625,7 @@ struct SplitStream : BlockStream<5, LD, false> {
         static_for<0, 5>([&](auto q) {
             constexpr int Q = decltype(q)::value;
             const unsigned bit = ((unsigned)lane >> Q) & 1u;
-            this->a_ry[Q] = kSRecRy + Q * 32 + bit * 16u;
+            this->a_ry[Q] = Q == 4 ? kSRecRy + 64 + bit * 16u : kSRecRy + Q * 16 + bit * 8u;     // (split-record layout above)
             a_cs[Q] = Q * 32 + (Q == 4 ? (1u - bit) : bit) * 16u;
         });
     }
@@ -603,15 +633,16 @@ struct SplitStream : BlockStream<5, LD, false> {
         const double* q = reinterpret_cast<const double*>(p + off);
         return make_double2(q[0], q[1]);
     }
-    __device__ __forceinline__ void load_records_split(const char* sl) {
-#pragma unroll
-        for (int i = 0; i < RPB; ++i) this->dg[i] = rd8(sl, i * kRecBytes + this->a_dg);
-#pragma unroll
-        for (int s = 0; s < LD; ++s)
-            static_for<0, 5>([&](auto q) { this->ry[s][decltype(q)::value] = Base::rd(sl, (1 + s) * kRecBytes + this->a_ry[decltype(q)::value]); });
-    }
-    __device__ __forceinline__ void load_cs_split(const char* chunk) {
-        static_for<0, 5>([&](auto q) { this->cs[decltype(q)::value] = Base::rd(chunk, a_cs[decltype(q)::value]); });
+    // an ansatz sub-layer's coefficients (record `rec` of the block in slot `sl`) behind the diagonal at `a_diag`; DAG: of
+    // its inverse -- wires 0..3 read the other variant (+t / -t), wire 4's swap form negates in the gate (split_ry_dag)
+    template <bool DAG = false>
+    __device__ __forceinline__ void read_ansatz(SplitCoef& c, const char* sl, int rec, unsigned a_diag) const {
+        c.dg = rd8(sl, rec * kRecBytes + a_diag);
+        static_for<0, 4>([&](auto q) {
+            constexpr int Q = decltype(q)::value;
+            c.t[Q] = *reinterpret_cast<const double*>(sl + rec * kRecBytes + (this->a_ry[Q] ^ (DAG ? 8u : 0u)));
+        });
+        c.g4 = Base::rd(sl, rec * kRecBytes + this->a_ry[4]);
     }
 };
 
@@ -626,12 +657,12 @@ __device__ __forceinline__ double zsplit_forward(SplitStream<LD>& bs, const char
     double x = lane == 0 ? 1.0 : 0.0;
     bs.template prime<1>(0, false);
     const char* cs_b = csrow;                            // entry of block b's first column
-    LayerCoef<5> ce, ca, cb;                             // coefficients one layer ahead (zyz_forward_fast)
+    LayerCoef<5> ce;                                     // coefficients one layer ahead (zyz_forward_fast)
+    SplitCoef ca, cb;
     ce.dg = bs.rd8(bs.slot(0), bs.a_dg);
     static_for<0, 5>([&](auto q) { ce.g[decltype(q)::value] = bs.rd(cs_b, bs.a_cs[decltype(q)::value]); });
-    auto read_layer = [&](LayerCoef<5>& c, const char* sl, int rec) {
-        c.dg = bs.rd8(sl, rec * kRecBytes + bs.a_dg);
-        static_for<0, 5>([&](auto q) { c.g[decltype(q)::value] = bs.rd(sl, rec * kRecBytes + bs.a_ry[decltype(q)::value]); });
+    auto read_layer = [&](SplitCoef& c, const char* sl, int rec) {
+        bs.read_ansatz(c, sl, rec, bs.a_dg);
         __builtin_amdgcn_sched_barrier(0);
     };
     auto read_chunk = [&](const char* nx, int kb) {
@@ -640,9 +671,9 @@ __device__ __forceinline__ double zsplit_forward(SplitStream<LD>& bs, const char
         static_for<0, 5>([&](auto q) { ce.g[decltype(q)::value] = bs.rd(cn, bs.a_cs[decltype(q)::value]); });
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto layer = [&](const LayerCoef<5>& c, bool ring, int pt) {
+    auto layer = [&](const auto& c, bool ring, int pt) {
         split_phase(x, c.dg);
-        static_for<0, 5>([&](auto q) { split_ry<decltype(q)::value>(x, c.g[decltype(q)::value]); });
+        split_gates(x, c);
         if constexpr (SNAP) {
             if (ring) {                                  // a global_store: a flat one would also count in lgkmcnt
                 typedef __attribute__((address_space(1))) double gdouble;
@@ -1452,6 +1483,25 @@ __device__ __forceinline__ void split_ry_dag(double& x, const double2& u, unsign
         x = fma(-u.y, xchg<(1 << Q)>(x), own);
     }
 }
+__device__ __forceinline__ void split_gates_dag(double& x, const LayerCoef<5>& c, unsigned mask4) {     // RX chunk
+    static_rfor<0, 5>([&](auto q) { split_ry_dag<decltype(q)::value>(x, c.g[decltype(q)::value], mask4); });
+}
+__device__ __forceinline__ void split_gates_dag(double& x, const SplitCoef& c /* read_ansatz<true> */, unsigned mask4) {
+    split_ry_dag<4>(x, c.g4, mask4);
+    static_rfor<0, 4>([&](auto q) { split_ry_tan<decltype(q)::value>(x, c.t[decltype(q)::value]); });
+}
+
+// Hand-off slots of the split-layout reverse walks.  Step t of a walk lives in ring slot (t + off) mod RING, chains and sigma
+// waves alike.  Where a pass of the chains' unrolled body (kBSlots blocks) publishes a whole number of times into the ring
+// (LD = 2: 8 publications, RING = 8 or 16), `off` makes the first publication of every pass land on a multiple of 8: the
+// slot of each publication of the pass is then a constant behind a base that moves once per pass (RING = 8: never), i.e. an
+// immediate offset of its store.  The blocks peeled in front of the unrolled body (nblocks mod kBSlots of them, 2 steps
+// each) are what `off` makes up for.  LD = 1: off = 0, slots computed per publication as before.
+template <int RING>
+__host__ __device__ __forceinline__ int zquad_slot_offset(int ld, int nblocks) {
+    static_assert(RING % (2 * kBSlots) == 0, "a pass of the LD = 2 body must divide the ring");
+    return ld == 2 ? (RING - 2 * (nblocks & (kBSlots - 1))) & (RING - 1) : 0;
+}
 
 // The sigma waves' walk over a block-unrolled shape (one full RX chunk + LD sub-layers per block), shared by the kernels whose
 // chains run in the split layout: steps drawn from a counter, the RX-chunk gradients read off the block's first sub-layer's
@@ -1490,6 +1540,7 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
         }
     };
     const int LDr = a.fast_ld, nsteps = a.nblocks * LDr;
+    const int slot_off = zquad_slot_offset<RING>(LDr, a.nblocks);     // step t lives in slot (t + slot_off) mod RING (zquad_chain)
     // snapshot of step t into slot `sl` (sc1: from L2, never a vector-L1 line of an earlier step's data at that address).  The
     // slots alternate per step of THIS wave (its steps are drawn, not consecutive)
     const unsigned snap_lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)(psi_ring[0]);
@@ -1531,11 +1582,11 @@ __device__ __forceinline__ void zsigma_walk(const A& a, int lane, int me, long w
 #pragma unroll
         for (int i = 0; i < NPROD; ++i) pair_wait_ge(&prod[i], t + 1, abort_flag, seen_c[i]);
         if constexpr (SNAP) wait_vmcnt<0>();              // this step's snapshot (issued a step ago) has landed
-        const double2* slot = SNAP ? psi_ring[cur] : psi_ring[t & (RING - 1)];
+        const double2* slot = SNAP ? psi_ring[cur] : psi_ring[(t + slot_off) & (RING - 1)];
         const double2 pv = slot[lane];
         double2 qv[N];
         static_for<0, N>([&](auto q) { qv[decltype(q)::value] = slot[lane ^ (1 << decltype(q)::value)]; });
-        const double2 lm = lam_ring[t & (RING - 1)][lane];
+        const double2 lm = lam_ring[(t + slot_off) & (RING - 1)][lane];
         double ax = 0.0;                                  // (read before the cursor moves on: it also frees the axis entry)
         if constexpr (CHUNK) ax = axis_ring[(bl & (kAxisRing - 1)) * (3 * N) + ax_slot];
         if (lane == 0) __hip_atomic_store(&cursor[me], after_v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1613,12 +1664,21 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
         if (!valid) gb = 0.0;
         x = gb * h * (p ? f.y : f.x);
     }
-    double* ring = reinterpret_cast<double*>(role == 0 ? psi_ring : lam_ring);
+    const int nb = a.nblocks;
+    // this lane's double in ring slot 0; in the slot of the first publication of the unrolled body's pass at hand
+    double* ring_lane = reinterpret_cast<double*>(role == 0 ? psi_ring : lam_ring) + slot_idx;
+    double* ring_pass = ring_lane;
+    const int slot_off = zquad_slot_offset<RING>(LD, nb);      // (zsigma_walk reads the slots with the same offset)
     int* prod = role == 0 ? &sync->psi_prod[smp] : &sync->lam_prod[smp];
     int step = 0;
-    auto publish_data = [&]() {                                // the state now, the counter after the layer's gates (ztri_chain)
+    // the state now, the counter after the layer's gates (ztri_chain); `sl`: the slot of the block at hand, `sub`: which of
+    // the block's publications.  LD = 2, unrolled body: block kBSlots - 1 - K of the pass, its slot an immediate.
+    auto publish_data = [&](auto sl, auto sub) {
         wait_slot_free<NSIG>(sync->cursor, step - RING + 1, &sync->abort, seen, safe);
-        ring[(step & (RING - 1)) * 128 + slot_idx] = x;
+        if constexpr (LD == 2 && is_ct_slot<decltype(sl)>::value)
+            ring_pass[(2 * (kBSlots - 1 - decltype(sl)::value) + decltype(sub)::value) * 128] = x;
+        else
+            ring_lane[((step + slot_off) & (RING - 1)) * 128] = x;
         ++step;
     };
     auto publish_flag = [&]() {
@@ -1626,7 +1686,6 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
         __hip_atomic_store(prod, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
     // ---- block-unrolled reverse walk in the split layout (the all-lane one: ztri_chain)
-    const int nb = a.nblocks;
     const unsigned a_dgd = (unsigned)k * 24u + (unsigned)(1 - p) * 8u;             // the inverse diagonal's two entries
     // (drains vmcnt: with SNAP every snapshot store has reached L2 before the first publication releases a sigma wave, whose
     // snapshot loads are ordered behind that publication -- zsigma_walk)
@@ -1634,10 +1693,10 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
     split_phase_dag(x, ss.rd8(ss.slot(nb), a_dgd));                                // block nb's slot: its record 0 is the final diagonal
     ss.template step<-1>(nb);
     const char* cs_b = row + (long)(nb - 1) * (N * 32);                            // chunk of the block at hand
-    LayerCoef<N> ct, cm, c0;
-    auto read_layer = [&](LayerCoef<N>& c, const char* sl, int rec) {
-        c.dg = ss.rd8(sl, rec * kRecBytes + a_dgd);
-        static_for<0, N>([&](auto q) { c.g[decltype(q)::value] = ss.rd(sl, rec * kRecBytes + ss.a_ry[decltype(q)::value]); });
+    SplitCoef ct, cm;
+    LayerCoef<N> c0;
+    auto read_layer = [&](SplitCoef& c, const char* sl, int rec) {
+        ss.template read_ansatz<true>(c, sl, rec, a_dgd);
         __builtin_amdgcn_sched_barrier(0);
     };
     auto read_chunk = [&](const char* sl, const char* chunk) {
@@ -1645,32 +1704,57 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
         static_for<0, N>([&](auto q) { c0.g[decltype(q)::value] = ss.rd(chunk, ss.a_cs[decltype(q)::value]); });
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto undo_gates = [&](const LayerCoef<N>& c) {
-        static_rfor<0, N>([&](auto q) { split_ry_dag<decltype(q)::value>(x, c.g[decltype(q)::value], mask4); });
+    auto undo_gates = [&](const auto& c) {
+        split_gates_dag(x, c, mask4);
         __builtin_amdgcn_sched_barrier(0);
     };
     read_layer(ct, ss.slot(nb - 1), LD);
-    auto block = [&](auto sl, int bl, int kb) {
+    // the chunk-gradient axes of a block (prep_zyz_kernel leaves them in the chunk's split record too) are handed to the
+    // sigma waves by the first sample's lambda wave before it publishes the block's first step: axis-ring row bl mod
+    // kAxisRing.  In the unrolled body that is row K of the pass's four (the block in ring slot K has bl = K mod kBSlots)
+    static_assert(kAxisRing % kBSlots == 0, "a pass of the unrolled body stays within the axis ring");
+    double* axis_lane = axis_ring + lane;
+    double* axis_pass = axis_lane;
+    // likewise the chunk of the block in slot K lies K chunks above the pass's lowest one: cs_pass[q] = this lane's LDS
+    // address of that chunk's wire-q entry, formed once per pass (DS offsets are unsigned: counted down from the pass's first
+    // block, each read would take an address add; the empty asm keeps the compiler from rewriting it that way)
+    typedef double vdouble2 __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) const vdouble2 lds_double2;
+    unsigned cs_pass[N];
+    auto read_chunk_pass = [&](const char* sl, auto k) {
+        c0.dg = ss.rd8(sl, a_dgd);
+        static_for<0, N>([&](auto q) {
+            const vdouble2 v = *(lds_double2*)(unsigned long)(cs_pass[decltype(q)::value] + decltype(k)::value * (N * 32));
+            c0.g[decltype(q)::value] = make_double2(v.x, v.y);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto block = [&](auto sl, int bl) {
         const char* cur = ss.template slot_rel<0>(sl);
         const char* nx = ss.template slot_rel<-1>(sl);
-        // the chunk-gradient axes of this block (prep_zyz_kernel leaves them in the chunk's split record too): handed to the
-        // sigma waves by the first sample's lambda wave before it publishes the block's first step
-        if (role == 1 && smp == 0 && lane < 3 * N)
-            axis_ring[(bl & (kAxisRing - 1)) * (3 * N) + lane] = reinterpret_cast<const double*>(cur + kSRecRy)[lane];
+        auto chunk_coefs = [&]() {
+            if constexpr (is_ct_slot<decltype(sl)>::value) read_chunk_pass(cur, sl);
+            else read_chunk(cur, cs_b);
+        };
+        if (role == 1 && smp == 0 && lane < 3 * N) {
+            const double ax = reinterpret_cast<const double*>(cur + kSRecRy)[lane];
+            if constexpr (is_ct_slot<decltype(sl)>::value) axis_pass[decltype(sl)::value * (3 * N)] = ax;
+            else axis_lane[(bl & (kAxisRing - 1)) * (3 * N)] = ax;
+        }
         if constexpr (LD == 2) read_layer(cm, cur, 1);
-        else read_chunk(cur, cs_b - kb * (N * 32));
+        else chunk_coefs();
         x = lane_gather(x, ring_rev);
         ss.template ahead_rel<-(kBDist + 1)>(sl, bl);          // in the gather's shadow
         __builtin_amdgcn_sched_barrier(0);
-        publish_data();
+        publish_data(sl, std::integral_constant<int, 0>{});
         undo_gates(ct);
         publish_flag();
         if constexpr (LD == 2) {
-            read_chunk(cur, cs_b - kb * (N * 32));
+            chunk_coefs();
             split_phase_dag(x, ct.dg);
             x = lane_gather(x, ring_rev);
             __builtin_amdgcn_sched_barrier(0);
-            publish_data();
+            publish_data(sl, std::integral_constant<int, 1>{});
             undo_gates(cm);
             publish_flag();
             split_phase_dag(x, cm.dg);
@@ -1684,14 +1768,22 @@ __device__ __forceinline__ void zquad_chain(const A& a, int role /* 0: psi, 1: l
     };
     int bl = nb - 1;
     for (; bl >= 0 && (bl & (kBSlots - 1)) != kBSlots - 1; --bl) {
-        block(RtSlot{bl}, bl, 0);
+        block(RtSlot{bl}, bl);
         cs_b -= N * 32;
     }
     for (; bl >= kBSlots - 1; bl -= kBSlots) {
-        block(CtSlot<3>{}, bl, 0);
-        block(CtSlot<2>{}, bl - 1, 1);
-        block(CtSlot<1>{}, bl - 2, 2);
-        block(CtSlot<0>{}, bl - 3, 3);
+        static_for<0, N>([&](auto q) {
+            constexpr int Q = decltype(q)::value;
+            cs_pass[Q] = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)(cs_b - (kBSlots - 1) * (N * 32)) + ss.a_cs[Q];
+            asm("" : "+v"(cs_pass[Q]));
+        });
+        // (step + slot_off is a multiple of 8 here when LD = 2: zquad_slot_offset; RING = 8: the base never moves)
+        if constexpr (LD == 2) ring_pass = ring_lane + ((step + slot_off) & (RING - 1) & ~(2 * kBSlots - 1)) * 128;
+        axis_pass = axis_lane + (bl & (kAxisRing - 1) & ~(kBSlots - 1)) * (3 * N);
+        block(CtSlot<3>{}, bl);
+        block(CtSlot<2>{}, bl - 1);
+        block(CtSlot<1>{}, bl - 2);
+        block(CtSlot<0>{}, bl - 3);
         cs_b -= kBSlots * (N * 32);
     }
 }
