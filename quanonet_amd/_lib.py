@@ -652,8 +652,11 @@ def model_depth_sweep_workspace_bytes(descs, batch):
 
 
 def depth_sweep_pmax(descs):
-    """Row length of a depth sweep's parameter / moment arrays: the largest member's model_param_count."""
+    """Row length of a depth or qubit sweep's parameter / moment arrays: the largest member's model_param_count."""
     return max(model_param_count(d) for d in descs)
+
+
+qubit_sweep_pmax = depth_sweep_pmax
 
 
 def model_depth_sweep_train_steps(descs, members, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
@@ -676,11 +679,6 @@ def model_qubit_sweep_workspace_bytes(descs, batch):
     """qhea_model_qubit_sweep_workspace_bytes for the members' descriptors; 0 if they cannot train as one qubit sweep."""
     arr, R = _desc_array(descs)
     return int(load().qhea_model_qubit_sweep_workspace_bytes(arr, R, int(batch)))
-
-
-def qubit_sweep_pmax(descs):
-    """Row length of a qubit sweep's parameter / moment arrays: the largest member's model_param_count."""
-    return max(model_param_count(d) for d in descs)
 
 
 def model_qubit_sweep_train_steps(descs, members, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
@@ -768,6 +766,25 @@ def model_forward_noisy_wide(desc, branch, trunk, params, noise, row0=0, ham_dia
     return _forward_noisy(True, desc, branch, trunk, params, noise, row0, ham_diag, out, stderr)
 
 
+def _forward_noisy_exact(device_model, desc, branch, trunk, params, noise, ham_diag, out, shot_std):
+    """The two exact entry points share one argument list: qhea_model_forward_noisy_exact (`noise` a NoiseParams) and
+    ..._noisy_device_exact (a DeviceNoiseParams)."""
+    lib = load()
+    entry = 'qhea_model_forward_noisy_device_exact' if device_model else 'qhea_model_forward_noisy_exact'
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
+    _dev_f64(shot_std, 'shot_std', (B,))
+    pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
+    ws = _sized_ws(branch.device, lib.qhea_model_exact_noisy_workspace_bytes, ctypes.byref(desc), int(B))
+    with torch.cuda.device(branch.device):
+        rc = getattr(lib, entry)(ctypes.byref(desc), int(B), _ptr(branch), _ptr(trunk), _ptr(params), _ptr(ham_diag),
+                                 ctypes.byref(noise), _ptr(pred), _ptr(shot_std), _ptr(ws), 0 if ws is None else ws.numel(),
+                                 _stream(branch.device))
+    if rc == -2:
+        raise Unsupported(f"{entry}: unsupported circuit (n >= 7)")
+    _check(rc, entry)
+    return pred, shot_std
+
+
 def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None, out=None, shot_std=None):
     """
     qhea_model_forward_noisy_exact on all rows of branch / trunk in ONE call: (pred[B], shot_std[B] or None) -- the exact
@@ -775,19 +792,7 @@ def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None,
     standard deviation of one shot.  Raises Unsupported for n >= 7 and QheaError for a bad noise setting -- in both cases before
     anything is launched.
     """
-    lib = load()
-    B = _model_inputs(desc, branch, trunk, params, ham_diag)
-    _dev_f64(shot_std, 'shot_std', (B,))
-    pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
-    ws = _sized_ws(branch.device, lib.qhea_model_exact_noisy_workspace_bytes, ctypes.byref(desc), int(B))
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_forward_noisy_exact(ctypes.byref(desc), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
-                                                _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(shot_std), _ptr(ws),
-                                                0 if ws is None else ws.numel(), _stream(branch.device))
-    if rc == -2:
-        raise Unsupported("qhea_model_forward_noisy_exact: unsupported circuit (n >= 7)")
-    _check(rc, 'qhea_model_forward_noisy_exact')
-    return pred, shot_std
+    return _forward_noisy_exact(False, desc, branch, trunk, params, noise, ham_diag, out, shot_std)
 
 
 def device_noise_tables(n, noise):
@@ -812,19 +817,7 @@ def model_forward_noisy_device_exact(desc, branch, trunk, params, noise, ham_dia
     DeviceNoiseParams (per-wire rates, T1 / T2, layer durations).  Raises Unsupported for n >= 7 and QheaError for a bad noise
     setting -- in both cases before anything is launched.
     """
-    lib = load()
-    B = _model_inputs(desc, branch, trunk, params, ham_diag)
-    _dev_f64(shot_std, 'shot_std', (B,))
-    pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
-    ws = _sized_ws(branch.device, lib.qhea_model_exact_noisy_workspace_bytes, ctypes.byref(desc), int(B))
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_forward_noisy_device_exact(ctypes.byref(desc), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
-                                                       _ptr(ham_diag), ctypes.byref(noise), _ptr(pred), _ptr(shot_std),
-                                                       _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    if rc == -2:
-        raise Unsupported("qhea_model_forward_noisy_device_exact: unsupported circuit (n >= 7)")
-    _check(rc, 'qhea_model_forward_noisy_device_exact')
-    return pred, shot_std
+    return _forward_noisy_exact(True, desc, branch, trunk, params, noise, ham_diag, out, shot_std)
 
 
 def model_exact_noisy_log10_amplification(desc, noise):

@@ -12,11 +12,11 @@ checkpoints and history.  The parameters of all members live in one [R, Pmax] de
 parameter count); member m's model parameters are views into the front of row m.
 """
 from .ensemble import check_shared, check_supported
-from .sweep import SWEEP_KEYS, SweepSolver, sweep_data, validate_sweep_configs
+from .solver import model_setting
+from .sweep import SWEEP_KEYS, SweepSolver, check_sweep_rules
 
 # keys in which the members of one depth sweep may differ (net_size only in its depth entries: _check_net_sizes)
 DEPTH_SWEEP_KEYS = SWEEP_KEYS + ('net_size',)
-_DEFAULT_NET = [20, 2, 10, 2]           # PTSolver's default net_size
 
 
 def _depth_entries(cfg):
@@ -25,10 +25,10 @@ def _depth_entries(cfg):
 
 
 def _check_net_sizes(configs):
-    ref = list(configs[0].get('net_size', _DEFAULT_NET))
+    ref = list(model_setting(configs[0], 'net_size'))
     free = _depth_entries(configs[0])
     for i, c in enumerate(configs):
-        net = list(c.get('net_size', _DEFAULT_NET))
+        net = list(model_setting(c, 'net_size'))
         if len(net) != len(ref):
             raise ValueError(f"config {i}'s net_size {net} has a different length than config 0's {ref}")
         for k, (a, b) in enumerate(zip(ref, net)):
@@ -45,36 +45,12 @@ def validate_depth_sweep_configs(configs, data_dicts=None):
     configs = check_supported(configs, who='DepthSweepSolver')
     check_shared(configs, DEPTH_SWEEP_KEYS, what='one depth sweep')
     _check_net_sizes(configs)
-    # everything else is SweepSolver's rule set, checked on the configs with net_size made equal
-    flat = [dict(c, net_size=list(configs[0].get('net_size', _DEFAULT_NET))) for c in configs]
-    validate_sweep_configs(flat, data_dicts)
+    check_sweep_rules(configs, data_dicts)
     return configs
 
 
 class DepthSweepSolver(SweepSolver):
     """R PTSolver runs that differ in circuit depth (and anything SweepSolver allows), trained together."""
-
-    def __init__(self, configs, data_dicts, device=None, log=print):
-        self.configs = validate_depth_sweep_configs(configs, data_dicts)
-        self._build(sweep_data(self.configs, data_dicts), device, log)
-        self.descs = [m.trainer.desc for m in self.members]
-        if any(d is None for d in self.descs):
-            raise RuntimeError("DepthSweepSolver needs the fused model-level training path (QuanONetPT / HEAQNNPT in fp64)")
-        diags = [m.trainer._ham_diag() for m in self.members]
-        self.ham_diag = None
-        if diags[0] is not None:
-            import torch
-            self.ham_diag = torch.stack([d.reshape(-1) for d in diags]).to(self.device, dtype=torch.float64).contiguous()
-
-    def _train_steps(self, bounds, gbs, inputs, out, rows, first_step):
-        """one epoch's steps of every member with its own depth, read-out, scale and CURRENT learning rate, one launch per
-        kernel and step"""
-        from . import _lib
-        hps = []
-        for m, d in zip(self.members, self.descs):
-            lr = m.trainer.optimizer.param_groups[0]['lr']
-            hps.append(_lib.member_hparams(d.scale_coeff, d.ham_offset, d.ham_coeff, lr, d.ham_pauli))
-        g = self.members[0].trainer.optimizer.param_groups[0]
-        _lib.model_depth_sweep_train_steps(self.descs, hps, bounds, gbs, inputs[0], inputs[1] if len(inputs) > 1 else None, out,
-                                           self.params, rows, self.exp_avg, self.exp_avg_sq, first_step, g['betas'][0],
-                                           g['betas'][1], g['eps'], g['weight_decay'], ham_diag=self.ham_diag)
+    validate = staticmethod(validate_depth_sweep_configs)
+    entry = 'model_depth_sweep_train_steps'
+    takes_descs = True

@@ -15,15 +15,11 @@ import os
 import numpy as np
 import torch
 
-from .solver import PTSolver
+from .solver import PTSolver, batch_plan, model_setting, run_epochs, split_inputs
 
 # keys in which the members of one ensemble may differ (scale_coeff too, for trainable-frequency models: there it only sets
 # the initial frequency weights, the descriptor the kernels see is shared)
 MEMBER_KEYS = ('seed', 'run_id', 'prefix')
-
-
-def _trainable(cfg):
-    return str(cfg.get('if_trainable_freq', 'true')).lower() == 'true'
 
 
 def check_supported(configs, who='EnsembleSolver'):
@@ -62,13 +58,35 @@ def check_shared(configs, free, what='one ensemble'):
 def validate_configs(configs):
     """Raise ValueError unless `configs` can train as one ensemble.  Touches no device."""
     configs = check_supported(configs)
-    free = set(MEMBER_KEYS) | ({'scale_coeff'} if _trainable(configs[0]) else set())
+    free = set(MEMBER_KEYS) | ({'scale_coeff'} if model_setting(configs[0], 'if_trainable_freq') else set())
     check_shared(configs, free)
     return configs
 
 
+def sweep_data(configs, data_dicts):
+    """One data dict per member: `data_dicts` is one dict (shared) or a list of len(configs).  Every member's train arrays
+    must have the same shapes (one schedule for all); test sets may differ."""
+    if isinstance(data_dicts, dict):
+        return [data_dicts] * len(configs)
+    datas = list(data_dicts)
+    if len(datas) != len(configs):
+        raise ValueError(f"{len(datas)} data dicts for {len(configs)} configs: give one dict, or one per config")
+    ref = datas[0]
+    for i, d in enumerate(datas[1:], 1):
+        keys = sorted(k for k in set(ref) | set(d) if k.startswith('train_'))
+        for k in keys:
+            if k not in ref or k not in d or np.shape(ref[k]) != np.shape(d[k]):
+                raise ValueError(f"data dict {i}'s {k!r} has shape {np.shape(d.get(k))}, data dict 0's "
+                                 f"{np.shape(ref.get(k))}: every member trains on arrays of one shape")
+    return datas
+
+
 class EnsembleSolver:
-    """R PTSolver runs of one configuration, trained together (see the module docstring)."""
+    """R PTSolver runs of one configuration, trained together (see the module docstring).  The member solver of every kind:
+    a kind is its validator, the _lib entry of one epoch and the form of that entry's arguments."""
+    entry = 'model_ensemble_train_steps'
+    per_member = False       # whether `entry` takes a MemberHParams and a ham_diag row per member (else one lr, one read-out)
+    takes_descs = False      # whether `entry` takes the members' descriptors (else one, self.desc)
 
     def __init__(self, configs, data_dict, device=None, log=print):
         self.configs = validate_configs(configs)
@@ -132,9 +150,7 @@ class EnsembleSolver:
         n = m0.train_output.shape[0]
         bs = min(int(m0.config.get('batch_size', 100)), n)
         epochs = int(m0.config['num_epochs'])
-        nb = max(1, int(np.ceil(n / bs)))
-        bounds = [min(i * bs, n) for i in range(nb)] + [n]
-        gbs = [min(bs, n - i * bs) for i in range(nb)]
+        nb, gbs, bounds = batch_plan(n, bs)
         nm = max(self.numels)
         histories = [{'loss_train': [], 'loss_test': []} for _ in range(R)]
         want_save = m0.config.get('if_save', True)
@@ -142,6 +158,9 @@ class EnsembleSolver:
             os.makedirs(m.out_dir, exist_ok=True)
             m.best_model_path = os.path.join(m.out_dir, 'best_model.pt')
         opt0 = m0.trainer.optimizer
+
+        def stage():
+            return self._stage_epoch(n, bs, nb)
 
         def issue(staged):
             """queue one epoch's steps of every member; returns the device rows of their [sse | sum y^2]"""
@@ -153,49 +172,39 @@ class EnsembleSolver:
             for m in self.members:
                 m.trainer.optimizer.t += nb
             if all(p == nm for p in self.numels):
-                return rows[:, :, nm:]
-            return torch.stack([rows[r, :, p:p + 2] for r, p in enumerate(self.numels)])   # member r's [sse | sum y^2]
+                return rows[:, :, nm:], None
+            return torch.stack([rows[r, :, p:p + 2] for r, p in enumerate(self.numels)]), None   # member r's [sse | sum y^2]
 
-        cur = issue(self._stage_epoch(n, bs, nb)) if epochs > 0 else None
-        for epoch in range(epochs):
-            tails = cur
-            staged = self._stage_epoch(n, bs, nb) if epoch + 1 < epochs else None
-            tl = tails.tolist()                                 # one host sync per epoch
-            _lib.check_status(self.device)                      # a kernel-side pipeline failure ends the run here
-            snap = self.params.detach().to('cpu', copy=True) if want_save else None
-            for m in self.members:                              # (the schedulers depend on the epoch count alone)
-                if m.lr_scheduler is not None:
-                    m.lr_scheduler.step()
-            cur = issue(staged) if staged is not None else None
-            for r, m in enumerate(self.members):
-                s = [0.0, 0.0, 0.0]                             # as PTSolver.train: batch MSE, sse, sum y^2 in step order
-                for i in range(nb):
-                    s[0] += tl[r][i][0] / gbs[i]
-                    s[1] += tl[r][i][0]
-                    s[2] += tl[r][i][1]
-                avg_loss = s[0] / nb
-                histories[r]['loss_train'].append(avg_loss)
-                if avg_loss < m.best_loss:
-                    m.best_loss = avg_loss
-                    if want_save:
-                        m._save(m.best_model_path, flat=snap[r])
-                if epoch % 10 == 0:
-                    avg_rel = np.sqrt(s[1]) / (np.sqrt(s[2]) + 1e-8)
-                    self.log(f"[{m.config.get('run_id', r)}] Epoch {epoch} | MSE: {avg_loss:.6e} | Rel_L2: {avg_rel:.4%}")
+        def record(epoch, tl, snap):
+            for r, m in enumerate(self.members):                # member r's accounting is its PTSolver's
+                m._record_epoch(epoch, histories[r], tl[r], gbs, snap[r] if want_save else None, want_save, self.log,
+                                tag=f"[{m.config.get('run_id', r)}] ")
+
+        run_epochs(epochs, stage() if epochs > 0 else None, stage, issue, lambda: _lib.check_status(self.device),
+                   lambda _: self.params.detach().to('cpu', copy=True) if want_save else None,
+                   [m.lr_scheduler for m in self.members if m.lr_scheduler is not None], record)
         if want_save:
             for m in self.members:
                 m._save(os.path.join(m.out_dir, 'final.pt'))
         return histories
 
+    def _hparam_rows(self):
+        """every member's read-out, scale and CURRENT learning rate (its scheduler has stepped)"""
+        from . import _lib
+        return [_lib.member_hparams(d.scale_coeff, d.ham_offset, d.ham_coeff, m.trainer.optimizer.hparams()[0], d.ham_pauli)
+                for m, d in zip(self.members, self.descs)]
+
     def _train_steps(self, bounds, gbs, inputs, out, rows, first_step):
         """one epoch's steps of every member, one launch per kernel and step"""
         from . import _lib
         m0 = self.members[0]
-        g = m0.trainer.optimizer.param_groups[0]
-        _lib.model_ensemble_train_steps(self.desc, bounds, gbs, inputs[0], inputs[1] if len(inputs) > 1 else None, out,
-                                        self.params, rows, self.exp_avg, self.exp_avg_sq, first_step, g['lr'],
-                                        g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'],
-                                        ham_diag=m0.trainer._ham_diag())
+        lr, *adam = m0.trainer.optimizer.hparams()
+        call = (bounds, gbs, *split_inputs(inputs), out, self.params, rows, self.exp_avg, self.exp_avg_sq, first_step)
+        if self.per_member:
+            getattr(_lib, self.entry)(self.descs if self.takes_descs else self.desc, self._hparam_rows(), *call, *adam,
+                                      ham_diag=self.ham_diag)
+        else:
+            getattr(_lib, self.entry)(self.desc, *call, lr, *adam, ham_diag=m0.trainer._ham_diag())
 
     def predict(self, inputs, batch_size=None):
         """Every member's predictions on the same inputs (the single-model forward path), as a list."""
@@ -212,3 +221,24 @@ class EnsembleSolver:
         not blurred by independent noise draws.  exact=True: every member's exact expectation instead (no draws at all); a
         quanonet_amd.noise.DeviceNoise is evaluated that way only (ValueError with exact=False)."""
         return [m.evaluate_noisy(noise, out_name, exact=exact) for m in self.members]
+
+
+class PerMemberSolver(EnsembleSolver):
+    """The kinds whose members carry hyper-parameters of their own: SweepSolver, DepthSweepSolver, QubitSweepSolver.  A kind
+    sets `validate` (its validate_*_configs), `entry` and `takes_descs`."""
+    per_member = True
+    validate = None
+
+    def __init__(self, configs, data_dicts, device=None, log=print):
+        self.configs = type(self).validate(configs, data_dicts)
+        self._build(sweep_data(self.configs, data_dicts), device, log)
+        self.descs = [m.trainer.desc for m in self.members]
+        if any(d is None for d in self.descs):
+            raise RuntimeError(f"{type(self).__name__} needs the fused model-level training path (QuanONetPT / HEAQNNPT in fp64)")
+        diags = [m.trainer._ham_diag() for m in self.members]
+        self.ham_diag = None
+        if diags[0] is not None:            # [R, 2^nmax]: member m's spectrum at the front of row m
+            width = max(d.numel() for d in diags)
+            self.ham_diag = torch.zeros(len(diags), width, dtype=torch.float64, device=self.device)
+            for i, d in enumerate(diags):
+                self.ham_diag[i, :d.numel()].copy_(d.reshape(-1))

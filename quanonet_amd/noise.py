@@ -12,6 +12,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from .solver import split_inputs
 
 
 @dataclass(frozen=True)
@@ -233,8 +234,7 @@ _GRADIENT_WHY = "the gradient's reverse walk inverts the uniform depolarizing ch
 
 def _model_inputs(model, inputs):
     ins = list(inputs) if isinstance(inputs, (tuple, list)) else [inputs]
-    ins = [t.contiguous() for t in ins]
-    return ins[0], (ins[1] if len(ins) > 1 else None)
+    return split_inputs([t.contiguous() for t in ins])
 
 
 def _call_args(model, inputs, who):

@@ -44,6 +44,71 @@ def shard_slice(n_items, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def split_inputs(inputs):
+    """(branch, trunk or None) of a model's input tuple: (branch, trunk) for QuanONet, (x,) for HEAQNN"""
+    return inputs[0], (inputs[1] if len(inputs) > 1 else None)
+
+
+def run_dir(config):
+    """The directory PTSolver(config) writes its checkpoints and metric.json to."""
+    return os.path.join(config.get('prefix') or 'outputs', config.get('operator', 'Op'), config.get('run_id', 'run'))
+
+
+# the model settings a config may leave out, and how a given value is read (PTSolver._create_model and the member validators)
+_MODEL_DEFAULTS = {'net_size': [20, 2, 10, 2], 'if_trainable_freq': 'true', 'scale_coeff': 0.01, 'ham_bound': [-5, 5]}
+_MODEL_PARSE = {'net_size': tuple, 'if_trainable_freq': lambda v: str(v).lower() == 'true', 'scale_coeff': float,
+                'ham_bound': tuple}
+
+
+def model_setting(config, key):
+    """config[key] as the model takes it, PTSolver's default where the config leaves it out"""
+    return _MODEL_PARSE[key](config.get(key, _MODEL_DEFAULTS[key]))
+
+
+def batch_plan(n, bs):
+    """(number of steps, global batch of each step, row bounds of the steps in an epoch's n gathered rows)"""
+    nb = max(1, int(np.ceil(n / bs)))
+    return nb, [min(bs, n - i * bs) for i in range(nb)], [min(i * bs, n) for i in range(nb)] + [n]
+
+
+def epoch_sums(tl, gbs):
+    """(mean batch MSE, sse, sum y^2, the steps' MSE) of one epoch from its [sse, sum y^2] rows, added in step order"""
+    step_mse = [t[0] / gb for t, gb in zip(tl, gbs)]
+    s = [0.0, 0.0, 0.0]
+    for t, mse in zip(tl, step_mse):
+        s[0] += mse
+        s[1] += t[0]
+        s[2] += t[1]
+    return s[0] / len(gbs), s[1], s[2], step_mse
+
+
+def run_epochs(epochs, first, stage, issue, check_status, snapshot, schedulers, record):
+    """
+    The epoch loop of PTSolver.train and EnsembleSolver.train, one epoch ahead of its bookkeeping.  `first`: the staged first
+    epoch; stage() draws the next epoch's order and gathers its rows; issue(staged) queues an epoch's steps and returns (the
+    device rows of its [sse | sum y^2], whatever snapshot needs of it); snapshot(that) copies to the host what the bookkeeping
+    needs from the END of the epoch (the parameters for the checkpoint); record(epoch, tails as lists, snapshot) does the sums,
+    the checkpoint and the log line.
+    """
+    cur = issue(first) if epochs > 0 else None
+    for epoch in range(epochs):
+        tails, extra = cur
+        # the next epoch's order and rows are drawn and gathered BEFORE the host waits for this epoch: the draw (a
+        # millisecond of host time at 10^5 rows) overlaps the steps still queued on the device
+        staged = stage() if epoch + 1 < epochs else None
+        tl = tails.tolist()                                 # one host sync per epoch
+        check_status()                                      # a kernel-side pipeline failure ends the run here
+        # What the bookkeeping needs from the END of this epoch is on the host after the snapshot -- the losses, and (19 KB)
+        # the parameters for the best-by-train-loss checkpoint -- so the NEXT epoch is queued first and the host does its
+        # sums, its checkpoint and its log line while the device already works (the schedulers offered are functions
+        # of the epoch count alone).
+        snap = snapshot(extra)
+        for sched in schedulers:
+            sched.step()
+        cur = issue(staged) if staged is not None else None
+        record(epoch, tl, snap)
+
+
 def regression_metrics(y_pred, y_true, dist=None, world=1):
     """
     MSE / MAE / Max_Error (utils/metrics.py:6-29) and relative L2 (solvers/solver_pt.py:316-321) of a test set that is
@@ -78,13 +143,16 @@ class FlatAdam(torch.optim.Optimizer):
         self.exp_avg_sq = torch.zeros_like(pflat)
         self.t = 0
 
+    def hparams(self):
+        """(lr, beta1, beta2, eps, weight_decay) of the param group: the tail of every _lib call with an Adam update"""
+        g = self.param_groups[0]
+        return g['lr'], g['betas'][0], g['betas'][1], g['eps'], g['weight_decay']
+
     @torch.no_grad()
     def step(self, closure=None):
         from . import _lib
-        g = self.param_groups[0]
         self.t += 1
-        _lib.adam_step(self.pflat, self.gflat, self.exp_avg, self.exp_avg_sq, self.t, g['lr'], g['betas'][0],
-                       g['betas'][1], g['eps'], g['weight_decay'])
+        _lib.adam_step(self.pflat, self.gflat, self.exp_avg, self.exp_avg_sq, self.t, *self.hparams())
 
     def state_dict(self):
         sd = super().state_dict()
@@ -199,12 +267,10 @@ class PeerExchange:
     def allreduce_adam(self, flat, pflat, opt):
         """flat <- sum over ranks of flat (rank order); FlatAdam `opt`'s update of pflat with it; one launch."""
         from . import _lib
-        g = opt.param_groups[0]
         opt.t += 1
         self.seq += 1
         _lib.dp_allreduce_adam(self.rank, self.world, self.bufs, self.seq, flat, flat, pflat, opt.exp_avg,
-                               opt.exp_avg_sq, opt.t, g['lr'], g['betas'][0], g['betas'][1], g['eps'],
-                               g['weight_decay'], timeout_ms=self.timeout_ms)
+                               opt.exp_avg_sq, opt.t, *opt.hparams(), timeout_ms=self.timeout_ms)
 
     def check_status(self):
         from . import _lib
@@ -349,14 +415,12 @@ class DataParallelTrainer:
         gb = float(global_batch if global_batch is not None else y.shape[0] * self.world)
         if self.desc is not None:
             from . import _lib
-            branch = inputs[0]
-            trunk = inputs[1] if len(inputs) > 1 else None
+            data = (self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat)
+            grad = self.flat if out is None else out
             if self.train_noise is not None:
-                _lib.model_loss_grad_noisy_exact(self.desc, branch, trunk, y.reshape(-1), self.pflat, self.train_noise.params(),
-                                                 1.0 / gb, self.flat if out is None else out, ham_diag=self._ham_diag())
+                _lib.model_loss_grad_noisy_exact(*data, self.train_noise.params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
             else:
-                _lib.model_loss_grad(self.desc, branch, trunk, y.reshape(-1), self.pflat, 1.0 / gb,
-                                     self.flat if out is None else out, ham_diag=self._ham_diag())
+                _lib.model_loss_grad(*data, 1.0 / gb, grad, ham_diag=self._ham_diag())
         else:
             self.flat.zero_()
             pred = self._forward(inputs)
@@ -380,19 +444,13 @@ class DataParallelTrainer:
             from . import _lib
             *inputs, y = batch
             gb = float(global_batch if global_batch is not None else y.shape[0])
-            opt, g = self.optimizer, self.optimizer.param_groups[0]
+            opt = self.optimizer
             opt.t += 1
-            if self.train_noise is not None:
-                _lib.model_train_steps_noisy_exact(self.desc, [0, y.shape[0]], [gb], inputs[0],
-                                                   inputs[1] if len(inputs) > 1 else None, y.reshape(-1), self.pflat,
-                                                   flat.view(1, -1), opt.exp_avg, opt.exp_avg_sq, opt.t, g['lr'], g['betas'][0],
-                                                   g['betas'][1], g['eps'], g['weight_decay'], self.train_noise.params(),
-                                                   ham_diag=self._ham_diag())
-                return flat
-            _lib.model_train_step(self.desc, inputs[0], inputs[1] if len(inputs) > 1 else None, y.reshape(-1),
-                                  self.pflat, 1.0 / gb, flat, opt.exp_avg, opt.exp_avg_sq, opt.t, g['lr'],
-                                  g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'],
-                                  ham_diag=self._ham_diag())
+            if self.train_noise is not None:                # (the noise-aware path has the steps entry only: one step of it)
+                self._steps(inputs, y, [0, y.shape[0]], [gb], flat.view(1, -1), opt.t)
+            else:
+                _lib.model_train_step(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat, 1.0 / gb, flat, opt.exp_avg,
+                                      opt.exp_avg_sq, opt.t, *opt.hparams(), ham_diag=self._ham_diag())
             return flat
         gb_all = float(global_batch if global_batch is not None else batch[-1].shape[0] * self.world)
         if self.peer_fused and gb_all >= self.world and batch[-1].shape[0] > 0:
@@ -419,13 +477,23 @@ class DataParallelTrainer:
         self.optimizer.step()
         return flat
 
+    def _steps(self, inputs, y, bounds, global_batches, rows, first_step):
+        """single device: the steps entry, ideal (qhea_model_train_steps) or under train_noise (..._noisy_exact)"""
+        from . import _lib
+        opt = self.optimizer
+        call = (self.desc, bounds, global_batches, *split_inputs(inputs), y.reshape(-1), self.pflat, rows, opt.exp_avg,
+                opt.exp_avg_sq, first_step, *opt.hparams())
+        if self.train_noise is not None:
+            _lib.model_train_steps_noisy_exact(*call, self.train_noise.params(), ham_diag=self._ham_diag())
+        else:
+            _lib.model_train_steps(*call, ham_diag=self._ham_diag())
+
     def _dp_steps(self, inputs, y, bounds, global_batches, rows):
         from . import _lib
-        opt, g, px = self.optimizer, self.optimizer.param_groups[0], self.peer
+        opt, px = self.optimizer, self.peer
         n_steps = len(bounds) - 1
-        _lib.model_dp_train_steps(self.desc, bounds, global_batches, inputs[0], inputs[1] if len(inputs) > 1 else None,
-                                  y.reshape(-1), self.pflat, rows, opt.exp_avg, opt.exp_avg_sq, opt.t + 1, g['lr'],
-                                  g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'], px.rank, px.world, px.bufs,
+        _lib.model_dp_train_steps(self.desc, bounds, global_batches, *split_inputs(inputs), y.reshape(-1), self.pflat, rows,
+                                  opt.exp_avg, opt.exp_avg_sq, opt.t + 1, *opt.hparams(), px.rank, px.world, px.bufs,
                                   px.n, px.seq + 1, timeout_ms=px.timeout_ms, ham_diag=self._ham_diag())
         opt.t += n_steps
         px.seq += n_steps
@@ -538,24 +606,12 @@ class DataParallelTrainer:
         train_step(..., out=rows[i]) in a loop, without the interpreter between launches.
         """
         assert self.epoch_call
-        from . import _lib
         n_steps = len(bounds) - 1
         if self.world > 1:
             self._dp_steps(inputs, y, bounds, global_batches, rows)
-            self._last = rows[n_steps - 1]
-            return rows
-        opt, g = self.optimizer, self.optimizer.param_groups[0]
-        if self.train_noise is not None:
-            _lib.model_train_steps_noisy_exact(self.desc, bounds, global_batches, inputs[0],
-                                               inputs[1] if len(inputs) > 1 else None, y.reshape(-1), self.pflat, rows,
-                                               opt.exp_avg, opt.exp_avg_sq, opt.t + 1, g['lr'], g['betas'][0], g['betas'][1],
-                                               g['eps'], g['weight_decay'], self.train_noise.params(),
-                                               ham_diag=self._ham_diag())
         else:
-            _lib.model_train_steps(self.desc, bounds, global_batches, inputs[0], inputs[1] if len(inputs) > 1 else None,
-                                   y.reshape(-1), self.pflat, rows, opt.exp_avg, opt.exp_avg_sq, opt.t + 1, g['lr'],
-                                   g['betas'][0], g['betas'][1], g['eps'], g['weight_decay'], ham_diag=self._ham_diag())
-        opt.t += n_steps
+            self._steps(inputs, y, bounds, global_batches, rows, self.optimizer.t + 1)
+            self.optimizer.t += n_steps
         self._last = rows[n_steps - 1]
         return rows
 
@@ -609,8 +665,7 @@ class PTSolver:
         # this very loop on the CPU); the solver never builds anything but the HIP modules itself
         if self.device.type != 'cuda' and model is None:
             raise RuntimeError("PTSolver runs on a HIP device only (no CPU fallback)")
-        self.out_dir = os.path.join(config.get('prefix') or 'outputs', config.get('operator', 'Op'),
-                                    config.get('run_id', 'run'))
+        self.out_dir = run_dir(config)
         self.model = (model if model is not None else self._create_model()).to(self.device)
         self.trainer = DataParallelTrainer(self.model, lr=config['learning_rate'], world_size=world_size,
                                            dist=dist, optimizer=config.get('optimizer', 'adam'),
@@ -626,10 +681,8 @@ class PTSolver:
     def _create_model(self):
         from .models import QuanONetPT, HEAQNNPT
         c = self.config
-        ham_bound = tuple(c.get('ham_bound', [-5, 5]))
-        net_size = tuple(c.get('net_size', [20, 2, 10, 2]))
-        if_tf = str(c.get('if_trainable_freq', 'true')).lower() == 'true'
-        scale = float(c.get('scale_coeff', 0.01))
+        ham_bound, net_size = model_setting(c, 'ham_bound'), model_setting(c, 'net_size')
+        if_tf, scale = model_setting(c, 'if_trainable_freq'), model_setting(c, 'scale_coeff')
         n = int(c['num_qubits'])
         # --ham_diag strictly overrides --ham_pauli (utils/common.py:84)
         ham_pauli = 'Z' if c.get('ham_diag') is not None else (c.get('ham_pauli') or 'Z')
@@ -721,6 +774,23 @@ class PTSolver:
             return idx
         return torch.as_tensor(np.random.permutation(n), device=self.device)
 
+    def _record_epoch(self, epoch, history, tl, gbs, snap, want_save, log, tag=''):
+        """
+        One epoch's loss accounting (solver_pt.py:243-262): its mean batch MSE into history['loss_train'], the best-by-train-loss
+        checkpoint from `snap` (the host copy of the parameters at the epoch's end) and a log line every 10 epochs.  tl: the
+        epoch's [sse, sum y^2] per step.  Returns the steps' MSE.
+        """
+        avg_loss, sse, sum_y2, step_mse = epoch_sums(tl, gbs)
+        history['loss_train'].append(avg_loss)
+        if avg_loss < self.best_loss:
+            self.best_loss = avg_loss
+            if want_save:
+                self._save(self.best_model_path, flat=snap)
+        if epoch % 10 == 0:
+            avg_rel = np.sqrt(sse) / (np.sqrt(sum_y2) + 1e-8)
+            log(f"{tag}Epoch {epoch} | MSE: {avg_loss:.6e} | Rel_L2: {avg_rel:.4%}")
+        return step_mse
+
     def is_completed(self):
         """Whether this run's directory already holds a metric.json -- the reference's "experiment already completed" test
         (utils/logger.py:182-185), on which its train() ends the process (solvers/solver_pt.py:192-194)."""
@@ -734,18 +804,18 @@ class PTSolver:
         n = self.train_output.shape[0]
         bs = min(int(self.config.get('batch_size', 100)), n)
         epochs = int(self.config['num_epochs'])
-        nb = max(1, int(np.ceil(n / bs)))
+        nb, gbs, _ = batch_plan(n, bs)                          # (the row bounds are this rank's: _stage_epoch)
         history = {'loss_train': [], 'loss_test': []}
         trace = bool(self.config.get('trace_steps', False))     # parity tests: per-step MSE and the epoch orders
         if trace:
             history['loss_steps'], history['indices'] = [], []
         os.makedirs(self.out_dir, exist_ok=True)
         self.best_model_path = os.path.join(self.out_dir, 'best_model.pt')
-        staged = self._stage_epoch(n, bs, nb) if epochs > 0 else None
-        if staged is not None and self.world > 1 and self.config.get('dp_calibrate', True):
+        first = self._stage_epoch(n, bs, nb) if epochs > 0 else None
+        if first is not None and self.world > 1 and self.config.get('dp_calibrate', True):
             # both forms of the peer exchange timed on the first batch, the faster one kept (state restored afterwards)
-            _, b0, in0, out0 = staged
-            r = self.trainer.calibrate_exchange(*[t[b0[0]:b0[1]] for t in in0], out0[b0[0]:b0[1]], global_batch=min(bs, n))
+            _, b0, in0, out0 = first
+            r = self.trainer.calibrate_exchange(*[t[b0[0]:b0[1]] for t in in0], out0[b0[0]:b0[1]], global_batch=gbs[0])
             if r is not None:
                 self.log("data-parallel exchange: " + self.trainer.dp_exchange_reason)
         want_save = self.config.get('if_save', True) and self.rank == 0
@@ -764,56 +834,30 @@ class PTSolver:
             # False keeps one host call per step).  Several ranks: every rank must take the same path, so the choice rests on
             # what all of them know -- no global batch smaller than the world size (an empty shard somewhere)
             one_call = (rows is not None and self.trainer.epoch_call and self.config.get('epoch_call', True) and
-                        min(bs, n - (nb - 1) * bs) >= self.world)
+                        gbs[-1] >= self.world)
             if one_call:
-                self.trainer.train_steps(ep_inputs, ep_output, bounds, [min(bs, n - i * bs) for i in range(nb)], rows)
+                self.trainer.train_steps(ep_inputs, ep_output, bounds, gbs, rows)
             else:
                 for i in range(nb):
                     a, b = bounds[i], bounds[i + 1]
-                    gb = min(bs, n - i * bs)
-                    flat = self.trainer.train_step(*[t[a:b] for t in ep_inputs], ep_output[a:b], global_batch=gb,
+                    flat = self.trainer.train_step(*[t[a:b] for t in ep_inputs], ep_output[a:b], global_batch=gbs[i],
                                                    out=None if rows is None else rows[i])
                     if rows is None:
                         tails[i].copy_(flat[nm:])
             return tails, idx_dev
 
-        cur = issue(staged) if epochs > 0 else None
-        for epoch in range(epochs):
-            tails, idx_dev = cur
-            # the next epoch's order and rows are drawn and gathered BEFORE the host waits for this epoch: the draw (a
-            # millisecond of host time at 10^5 rows) overlaps the steps still queued on the device
-            staged = self._stage_epoch(n, bs, nb) if epoch + 1 < epochs else None
-            tl = tails.tolist()                                 # one host sync per epoch
-            self.trainer.check_status()                         # a kernel-side pipeline failure ends the run here
-            # What the bookkeeping below needs from the END of this epoch is on the host now -- the losses, and (19 KB) the
-            # parameters for the best-by-train-loss checkpoint -- so the NEXT epoch is queued first and the host does its
-            # sums, its checkpoint and its log line while the device already works (the schedulers offered are functions
-            # of the epoch count alone).
-            snap = self.trainer.pflat.detach().to('cpu', copy=True) if want_save else None
-            idx_host = idx_dev.cpu().numpy() if trace else None
-            if self.lr_scheduler is not None:
-                self.lr_scheduler.step()
-            cur = issue(staged) if staged is not None else None
-            s = [0.0, 0.0, 0.0]                                 # sum of batch MSE, sse, sum y^2 -- added in step order
-            step_mse = []
-            for i in range(nb):
-                gb = min(bs, n - i * bs)
-                step_mse.append(tl[i][0] / gb)
-                s[0] += tl[i][0] / gb
-                s[1] += tl[i][0]
-                s[2] += tl[i][1]
+        def snapshot(idx_dev):
+            return (self.trainer.pflat.detach().to('cpu', copy=True) if want_save else None,
+                    idx_dev.cpu().numpy() if trace else None)
+
+        def record(epoch, tl, snap):
+            step_mse = self._record_epoch(epoch, history, tl, gbs, snap[0], want_save, self.log)
             if trace:
                 history['loss_steps'].extend(step_mse)
-                history['indices'].append(idx_host)
-            avg_loss = s[0] / nb
-            avg_rel = np.sqrt(s[1]) / (np.sqrt(s[2]) + 1e-8)
-            history['loss_train'].append(avg_loss)
-            if avg_loss < self.best_loss:
-                self.best_loss = avg_loss
-                if want_save:
-                    self._save(self.best_model_path, flat=snap)
-            if epoch % 10 == 0:
-                self.log(f"Epoch {epoch} | MSE: {avg_loss:.6e} | Rel_L2: {avg_rel:.4%}")
+                history['indices'].append(snap[1])
+
+        run_epochs(epochs, first, lambda: self._stage_epoch(n, bs, nb), issue, self.trainer.check_status, snapshot,
+                   [self.lr_scheduler] if self.lr_scheduler is not None else [], record)
         if self.config.get('if_save', True) and self.rank == 0:
             self._save(os.path.join(self.out_dir, 'final.pt'))                 # logger.py:174-177 + solver_pt.py:266-272: final.pt / final.npz
         return history
@@ -830,8 +874,7 @@ class PTSolver:
                 # all chunks from one host call: the layer records are prepared once for the whole set (the parameters
                 # do not change during an evaluation)
                 from . import _lib
-                ins = [t.contiguous() for t in inputs]
-                o = _lib.model_forward_chunks(tr.desc, ins[0], ins[1] if len(ins) > 1 else None, tr.pflat, bs,
+                o = _lib.model_forward_chunks(tr.desc, *split_inputs([t.contiguous() for t in inputs]), tr.pflat, bs,
                                               ham_diag=tr._ham_diag())
                 return o.unsqueeze(-1)
             for s in range(0, n, bs):
@@ -841,13 +884,18 @@ class PTSolver:
             return torch.empty((0, 1), dtype=torch.float64, device=inputs[0].device)
         return torch.cat(outs, dim=0)
 
+    def _load_best(self):
+        """the best-by-train-loss checkpoint into the model, where train() wrote one"""
+        if self.best_model_path and os.path.exists(self.best_model_path):
+            sd = torch.load(self.best_model_path, map_location=self.device, weights_only=True)
+            self.model.load_state_dict(sd)
+
     def evaluate(self, history=None):
         # rank 0 alone wrote best_model.pt (train()) and alone reads it back; the other ranks receive the weights by
         # broadcast (parameters are views into the trainer's flat vector), so no rank can read a half-written file
         # or, on node-local storage, silently evaluate different weights
-        if self.rank == 0 and self.best_model_path and os.path.exists(self.best_model_path):
-            sd = torch.load(self.best_model_path, map_location=self.device, weights_only=True)
-            self.model.load_state_dict(sd)
+        if self.rank == 0:
+            self._load_best()
         if self.world > 1:
             self.trainer.broadcast_parameters()
         # every rank evaluates its contiguous slice of the test set (10-100x a training batch: SURVEY.md 8(f)-2) in
@@ -880,9 +928,7 @@ class PTSolver:
             raise RuntimeError("evaluate_noisy runs on one rank (world_size == 1)")
         if not exact:
             _uniform_only(noise, 'evaluate_noisy(exact=False)', _TRAJECTORY_WHY)
-        if self.best_model_path and os.path.exists(self.best_model_path):
-            sd = torch.load(self.best_model_path, map_location=self.device, weights_only=True)
-            self.model.load_state_dict(sd)
+        self._load_best()
         predict = exact_noisy_predict if exact else noisy_predict
         y_pred, stderr = predict(self.model, self.test_input, noise, chunk_rows=self.config.get('eval_batch_size', 16384))
         y_true = torch.as_tensor(np.asarray(self.test_output), dtype=torch.float64).to(y_pred.device)

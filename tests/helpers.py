@@ -448,3 +448,12 @@ def member_lossgrad(kind, n, net, ham_bound=(-5.0, 5.0), ham_pauli='Z', ham_diag
             loss, grads, _ = O.heaqnn_loss_and_grads(sd, ins[0], y, n, net, **kw)
         return loss, grads
     return f
+
+
+def assert_checkpoints_bitwise(dir_a, dir_b, what=None):
+    """best_model.npz and final.npz of two runs (their output directories) hold the same arrays, bit for bit"""
+    for f in ('best_model.npz', 'final.npz'):
+        with np.load(os.path.join(dir_a, f)) as a, np.load(os.path.join(dir_b, f)) as b:
+            assert sorted(a.files) == sorted(b.files), (what, f)
+            for k in a.files:
+                assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), (what, f, k)

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import run_members
+from tests.helpers import assert_checkpoints_bitwise, run_members
 from tests.test_ensemble import _data, _flat, _heaqnn, _oracle_adam, _quanonet, _run_single, _schedule
 
 pytestmark = pytest.mark.gpu
@@ -170,6 +170,7 @@ def test_depth_sweep_solver_matches_ptsolver_runs(dev, tmp_path, variant):
                 assert torch.equal(p_sw, p_solo), c
                 assert h['loss_train'] == hs['loss_train'], c
                 assert mt['rel_l2'] == ms['rel_l2'], c
+                assert_checkpoints_bitwise(m.out_dir, solo.out_dir, c)
             else:                                 # AUTO: the single run may take the ZYZ kernels
                 assert float((p_sw - p_solo).abs().max()) < 1e-10, c
                 assert np.allclose(h['loss_train'], hs['loss_train'], rtol=1e-10, atol=0), c

@@ -19,7 +19,7 @@ import torch
 from oracle import hea_oracle as O
 from oracle import c_oracle as C
 from tests.helpers import flat as _flat, heaqnn as _heaqnn, member_data as _data, oracle_adam as _oracle_adam
-from tests.helpers import quanonet as _quanonet, run_members, run_single as _run_single, schedule as _schedule
+from tests.helpers import assert_checkpoints_bitwise, quanonet as _quanonet, run_members, run_single as _run_single, schedule as _schedule
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -179,6 +179,7 @@ def test_ensemble_solver_matches_ptsolver_runs(dev, tmp_path, variant):
             else:                                    # the same variant forced for both: bitwise
                 assert torch.equal(p_ens, p_solo), s
                 assert h['loss_train'] == hs['loss_train'], s
+                assert_checkpoints_bitwise(m.out_dir, solo.out_dir, s)
             for f in ('best_model.pt', 'final.pt', 'final.npz'):
                 assert os.path.exists(os.path.join(m.out_dir, f)), (s, f)
         metrics = ens.evaluate(hists)

@@ -17,7 +17,7 @@ import torch
 from tests.test_ensemble import _antideriv, _data, _flat, _heaqnn, _oracle_adam, _quanonet, _run_single, _schedule
 from tests.test_depth_sweep import _run_depth
 from tests.test_qubit_sweep import SENTINEL, _run_qubit
-from tests.helpers import kernels_launched as _kernels_launched, member_call
+from tests.helpers import assert_checkpoints_bitwise, kernels_launched as _kernels_launched, member_call
 
 pytestmark = pytest.mark.gpu
 
@@ -240,6 +240,7 @@ def test_q2_q10_qubit_sweep_solver_matches_ptsolver_runs(dev, tmp_path, variant)
                 assert torch.equal(p_sw, p_solo), c
                 assert h['loss_train'] == hs['loss_train'], c
                 assert mt['rel_l2'] == ms['rel_l2'], c
+                assert_checkpoints_bitwise(m.out_dir, solo.out_dir, c)
             else:
                 assert float((p_sw - p_solo).abs().max()) < 1e-10, c
                 assert np.allclose(h['loss_train'], hs['loss_train'], rtol=1e-10, atol=0), c

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import run_members
+from tests.helpers import assert_checkpoints_bitwise, run_members
 from tests.test_depth_sweep import _run_depth
 from tests.test_ensemble import _data, _flat, _heaqnn, _oracle_adam, _quanonet, _run_single, _schedule
 
@@ -177,6 +177,7 @@ def test_qubit_sweep_solver_matches_ptsolver_runs(dev, tmp_path, variant):
                 assert torch.equal(p_sw, p_solo), c
                 assert h['loss_train'] == hs['loss_train'], c
                 assert mt['rel_l2'] == ms['rel_l2'], c
+                assert_checkpoints_bitwise(m.out_dir, solo.out_dir, c)
             else:                                 # AUTO: the single run may take other backward kernels
                 assert float((p_sw - p_solo).abs().max()) < 1e-10, c
                 assert np.allclose(h['loss_train'], hs['loss_train'], rtol=1e-10, atol=0), c

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import run_members
+from tests.helpers import assert_checkpoints_bitwise, run_members
 from tests.test_ensemble import _antideriv, _data, _flat, _oracle_adam, _quanonet, _run_ensemble, _run_single, _schedule
 
 pytestmark = pytest.mark.gpu
@@ -240,6 +240,7 @@ def test_sweep_solver_matches_ptsolver_runs(dev, tmp_path, variant, cell):
             else:                                    # the same variant forced for both: bitwise
                 assert torch.equal(p_sw, p_solo), c
                 assert h['loss_train'] == hs['loss_train'], c
+                assert_checkpoints_bitwise(m.out_dir, solo.out_dir, c)
             assert m.trainer.optimizer.param_groups[0]['lr'] == solo.trainer.optimizer.param_groups[0]['lr'], c
             assert m.out_dir.startswith(str(tmp_path / 'sweep')) and m.out_dir not in dirs
             dirs.add(m.out_dir)
