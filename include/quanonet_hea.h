@@ -456,7 +456,8 @@ int    qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n
  * qhea_model_forward_noisy_exact.  With p1[q] = p1, p2[j] = p2, readout01 = readout10 = readout, infinite t1 / t2 it computes
  * that call's quantity (to rounding; the channels are evaluated in the triple form), with all rates 0 the ideal model.
  * Scope: n = 2..6, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.  Out of scope: thermal
- * excited-state population, crosstalk, routing (the ring is taken to be native on the chosen wires), gradients.
+ * excited-state population, crosstalk, routing (the ring is taken to be native on the chosen wires).  Gradients and training
+ * under the model: qhea_model_loss_grad_noisy_device_exact below.
  * Errors, all before anything is launched or any device is touched, outputs untouched: QHEA_EINVAL for a NULL setting or a NULL
  * array in it, n_wires != n, a probability outside [0, 1] or NaN, a duration that is negative, NaN or infinite, t1 or t2 <= 0 or
  * NaN, t2 > 2 t1; then QHEA_EUNSUPPORTED for n >= 7; then the errors of qhea_model_forward_noisy_exact.
@@ -475,6 +476,83 @@ int qhea_model_forward_noisy_device_exact(const qhea_model_desc* desc, int64_t b
                                           const qhea_device_noise* dn /*HOST*/,
                                           double* pred /*DEVICE [B]*/, double* shot_std /*DEVICE [B] or NULL*/,
                                           void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Training under the calibrated device noise model: the MSE loss of qhea_model_forward_noisy_device_exact and its exact
+ * gradient, so that a model scored under a qhea_device_noise can be trained against it.  Replaces nothing in the reference.
+ *
+ * The quantity is qhea_model_loss_grad_noisy_exact's with pred_b = what qhea_model_forward_noisy_device_exact returns for row b;
+ * the [P+2] buffer has the same layout (gradients, sum_b (pred_b - y_b)^2, sum_b y_b^2), so the data-parallel SUM and
+ * qhea_adam_step take it as is, and the chain rule around the circuit is the same.
+ *
+ * The reverse walk.  It is the walk stated for qhea_model_loss_grad_noisy_exact (d pred / d theta = Im Tr(O_k sigma_q rho_k) at
+ * every rotation, rho walked back through inverses, O through Heisenberg adjoints) over the channel sites of the device model.
+ * A one-wire site is a phase-covariant triple (off, a, b): off-diagonals times `off`, z -> a z + b tr.
+ *   - rho walks back through the inverse, the triple (1 / off, 1 / a, -b / a); it exists whenever off > 0 and a > 0;
+ *   - O walks back through the adjoint.  Relaxation is non-unital (b != 0), so this is no longer the channel itself:
+ *     off-diagonals times `off`, and on the diagonal pair the TRANSPOSED weight matrix,
+ *         O00' = (1 + a + b)/2 O00 + (1 - a - b)/2 O11,     O11' = (1 - a + b)/2 O00 + (1 + a - b)/2 O11;
+ *   - the two-qubit depolarizing channel of slot j stays self-adjoint; its inverse is the closed form stated there with the
+ *     slot's own lam_j = 16 p2[j] / 15;
+ *   - order: slot J applies CNOT, D2(lam_J), the TGT site of wire J, the CTL site of wire J + 1 mod n, so the reverse pass undoes
+ *     the two one-wire sites first, then D2, then the CNOT (the sites do not commute with D2 once b != 0); a wire's pending
+ *     gates are followed by their ENC / ROT site, so in reverse: the site's inverse on rho and adjoint on O, then the trace,
+ *     then the un-rotation;
+ *   - read-out: O_N = diag h' behind the H / H S^dagger of an X / Y read-out, h' mixed per bit by readout01 / readout10 as in
+ *     the forward call.
+ *
+ * Conditioning and the guard.  With the sums over what the circuit applies -- the ENC site of a wire once per encoding layer,
+ * its ROT, CTL and TGT sites once per sub-layer, every CNOT slot once per sub-layer --
+ *     log10 A_dev = - sum log10 min(off, a) - sum log10 (1 - lam_j).
+ * For p1[q] = p1, p2[j] = p2 and no relaxation this is log10 A of qhea_model_exact_noisy_log10_amplification.
+ * qhea_model_device_noisy_log10_amplification returns it (host only, no device needed; NaN for a bad descriptor or a setting the
+ * forward call refuses with QHEA_EINVAL, +inf for a singular channel).  The calls refuse -- QHEA_EUNSUPPORTED, before anything
+ * is launched, outputs untouched -- p1[q] >= 3/4, p2[j] >= 15/16, a site the circuit applies whose min(off, a) is 0 (a decay
+ * that underflows), n >= 7, and log10 A_dev > 7.
+ *   The bound is 7, not the uniform call's 12.  Once b != 0 the observable no longer shrinks by the factor rho grows by, and
+ *   the numpy probe (tests/test_device_noise_training_abi.py: inverse walk against a walk over stored forward states, device
+ *   settings with relaxation on every wire but one; n = 5 with 60 and 120 sub-layers, n = 6 with 20; the largest difference of
+ *   the three circuits) shows
+ *       log10 A_dev      0        4        5        6        7        8        10       11.99
+ *       difference    6.1e-15  2.1e-15  1.3e-14  4.5e-14  2.4e-13  1.5e-12  3.7e-11  1.1e-9
+ *   The criterion is the uniform bound's -- no probe at or below the bound above 1e-12 -- and 7 is the largest probed value that
+ *   meets it.
+ *
+ * Scope: n = 2..6, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.
+ * Arguments: those of qhea_model_loss_grad_noisy_exact / qhea_model_train_steps_noisy_exact with `dn` in place of `noise`.
+ * Workspace: qhea_model_device_noisy_grad_workspace_bytes (0 on a bad descriptor): the uniform call's plus the table below.
+ * Errors, all before anything is launched and with the outputs untouched, in this order: a bad descriptor and the setting's
+ * QHEA_EINVAL cases (those of qhea_model_forward_noisy_device_exact, by the same code); QHEA_EUNSUPPORTED for n >= 7 and for
+ * the guard; then the errors of qhea_model_loss_grad_noisy_exact (read-out, negative batch, NULL arrays, QHEA_EWORKSPACE).
+ * An empty batch (or n_steps = 0) returns QHEA_OK.
+ * Launches: a table kernel once per call (one workgroup: the three forms -- forward, inverse, adjoint -- of every site, the
+ * slots' factors and the readout probabilities, 66 doubles per wire, from its by-value argument into the workspace; the
+ * backward kernel reads a site's constants where it uses them), then three per step: the prep kernel, the density-matrix
+ * backward kernel (density_dev_bwd_kernel: layout, passes, LDS budget and trace sums of the uniform call's kernel) and that
+ * call's reduce kernel.  No allocation, no synchronisation (hipGraph-capturable), no atomics, fixed summation orders: results
+ * are bitwise reproducible, and a row's pred and its record do not depend on the batch, the grid or the rows beside it.  pred
+ * agrees with qhea_model_forward_noisy_device_exact to rounding (1e-13).
+ * qhea_model_train_steps_noisy_device_exact is bitwise a loop of qhea_model_loss_grad_noisy_device_exact + qhea_adam_step.  The
+ * workspace must fit the largest step.
+ */
+size_t qhea_model_device_noisy_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+double qhea_model_device_noisy_log10_amplification(const qhea_model_desc* desc, const qhea_device_noise* dn /*HOST*/);
+int    qhea_model_loss_grad_noisy_device_exact(const qhea_model_desc* desc, int64_t batch,
+                                               const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                               const double* params, const double* ham_diag,
+                                               const qhea_device_noise* dn /*HOST*/, double inv_batch_total,
+                                               double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                               void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_device_exact(const qhea_model_desc* desc, int64_t n_steps,
+                                                 const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                                 const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                                 const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                                 const double* ham_diag, const qhea_device_noise* dn /*HOST*/,
+                                                 const double* inv_batch_total /*HOST [n_steps]*/,
+                                                 double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                                 double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                                 double beta2, double eps, double weight_decay, void* workspace,
+                                                 size_t workspace_bytes, void* stream);
 
 /*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the

@@ -39,7 +39,9 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_exact_noisy_workspace_bytes', 'qhea_model_forward_noisy_exact',
            'qhea_model_exact_noisy_grad_workspace_bytes', 'qhea_model_exact_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact',
-           'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact']
+           'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact',
+           'qhea_model_device_noisy_grad_workspace_bytes', 'qhea_model_device_noisy_log10_amplification',
+           'qhea_model_loss_grad_noisy_device_exact', 'qhea_model_train_steps_noisy_device_exact']
 
 
 class ModelDesc(ctypes.Structure):
@@ -71,7 +73,7 @@ class DeviceNoiseParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 540           # 0.5.4: + qhea_model_forward_noisy_device_exact (exact evaluation under a device noise model)
+MIN_LIB_VERSION = 550           # 0.5.5: + qhea_model_loss_grad / train_steps_noisy_device_exact (training under a device noise model)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -233,6 +235,15 @@ def load():
     lib.qhea_device_noise_tables.argtypes = [ctypes.c_int, dnp, f64p, f64p]
     lib.qhea_model_forward_noisy_device_exact.restype = ctypes.c_int
     lib.qhea_model_forward_noisy_device_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, dnp, dp, dp, vp, ctypes.c_size_t, vp]
+    lib.qhea_model_device_noisy_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_device_noisy_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
+    lib.qhea_model_device_noisy_log10_amplification.restype = ctypes.c_double
+    lib.qhea_model_device_noisy_log10_amplification.argtypes = [mdp, dnp]
+    lib.qhea_model_loss_grad_noisy_device_exact.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_device_exact.argtypes = [dnp if t is npp else t for t in lib.qhea_model_loss_grad_noisy_exact.argtypes]
+    lib.qhea_model_train_steps_noisy_device_exact.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_device_exact.argtypes = [dnp if t is npp else t
+                                                              for t in lib.qhea_model_train_steps_noisy_exact.argtypes]
     _lib = lib
     return lib
 
@@ -829,15 +840,56 @@ def model_exact_noisy_log10_amplification(desc, noise):
     return float(load().qhea_model_exact_noisy_log10_amplification(ctypes.byref(desc), ctypes.byref(noise)))
 
 
-def _noisy_grad_ws(lib, desc, B, device):
-    return _sized_ws(device, lib.qhea_model_exact_noisy_grad_workspace_bytes, ctypes.byref(desc), int(B))
+def _noisy_grad_ws(lib, desc, B, device, device_model=False):
+    size_fn = lib.qhea_model_device_noisy_grad_workspace_bytes if device_model else lib.qhea_model_exact_noisy_grad_workspace_bytes
+    return _sized_ws(device, size_fn, ctypes.byref(desc), int(B))
 
 
 def _check_noisy_grad(rc, who):
     if rc == -2:
         raise Unsupported(f"{who}: n >= 7, or rates and depth whose inverse walk is ill-conditioned (log10 amplification > 12, "
-                          "or a singular channel)")
+                          "a lower bound under a DeviceNoise -- include/quanonet_hea.h --, or a singular channel)")
     _check(rc, who)
+
+
+def _loss_grad_noisy(device_model, desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred):
+    """The two gradient entry points share one argument list: qhea_model_loss_grad_noisy_exact (`noise` a NoiseParams) and
+    ..._noisy_device_exact (a DeviceNoiseParams)."""
+    lib = load()
+    entry = 'qhea_model_loss_grad_noisy_device_exact' if device_model else 'qhea_model_loss_grad_noisy_exact'
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
+    _dev_f64(y, 'y')
+    if y.numel() != B:
+        raise QheaError(f"y has {y.numel()} elements, expected {B}")
+    _dev_f64(grad, 'grad')
+    if grad.numel() < params.numel() + 2:
+        raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
+    _dev_f64(pred, 'pred', (B,))
+    ws = _noisy_grad_ws(lib, desc, B, branch.device, device_model)
+    with torch.cuda.device(branch.device):
+        rc = getattr(lib, entry)(ctypes.byref(desc), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params), _ptr(ham_diag),
+                                 ctypes.byref(noise), float(inv_batch_total), _ptr(grad), _ptr(pred), _ptr(ws),
+                                 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_noisy_grad(rc, entry)
+    return grad
+
+
+def _train_steps_noisy(device_model, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                       first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag):
+    lib = load()
+    entry = 'qhea_model_train_steps_noisy_device_exact' if device_model else 'qhea_model_train_steps_noisy_exact'
+    if len(bounds) - 1 <= 0:
+        return rows
+    n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
+                                                    exp_avg, exp_avg_sq, ham_diag)
+    ws = _noisy_grad_ws(lib, desc, biggest, branch.device, device_model)
+    with torch.cuda.device(branch.device):
+        rc = getattr(lib, entry)(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+                                 _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows), int(rows.stride(0)), _ptr(exp_avg),
+                                 _ptr(exp_avg_sq), int(first_step), float(lr), float(beta1), float(beta2), float(eps),
+                                 float(weight_decay), _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_noisy_grad(rc, entry)
+    return rows
 
 
 def model_loss_grad_noisy_exact(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None, pred=None):
@@ -846,23 +898,7 @@ def model_loss_grad_noisy_exact(desc, branch, trunk, y, params, noise, inv_batch
     of the exact noisy prediction for this shard (qhea_model_loss_grad_noisy_exact); returns grad.  Raises Unsupported for
     n >= 7 or a refused conditioning and QheaError for a bad noise setting, in both cases before anything is launched.
     """
-    lib = load()
-    B = _model_inputs(desc, branch, trunk, params, ham_diag)
-    _dev_f64(y, 'y')
-    if y.numel() != B:
-        raise QheaError(f"y has {y.numel()} elements, expected {B}")
-    _dev_f64(grad, 'grad')
-    if grad.numel() < params.numel() + 2:
-        raise QheaError("model_loss_grad_noisy_exact: grad needs P + 2 entries")
-    _dev_f64(pred, 'pred', (B,))
-    ws = _noisy_grad_ws(lib, desc, B, branch.device)
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_loss_grad_noisy_exact(ctypes.byref(desc), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
-                                                  _ptr(ham_diag), ctypes.byref(noise), float(inv_batch_total), _ptr(grad),
-                                                  _ptr(pred), _ptr(ws), 0 if ws is None else ws.numel(),
-                                                  _stream(branch.device))
-    _check_noisy_grad(rc, 'qhea_model_loss_grad_noisy_exact')
-    return grad
+    return _loss_grad_noisy(False, desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred)
 
 
 def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
@@ -872,20 +908,51 @@ def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y
     bounds[i]:bounds[i+1] under `noise` with residual weight 1 / global_batches[i], leaves [grads | sse | sum y^2] in rows[i]
     and applies Adam update first_step + i.  Bitwise a loop of model_loss_grad_noisy_exact + adam_step.
     """
-    lib = load()
-    if len(bounds) - 1 <= 0:
-        return rows
-    n_steps, rb, ib, biggest = _flat_train_schedule('model_train_steps_noisy_exact', desc, bounds, global_batches, branch, trunk, y, params,
-                                                    rows, exp_avg, exp_avg_sq, ham_diag)
-    ws = _noisy_grad_ws(lib, desc, biggest, branch.device)
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_train_steps_noisy_exact(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
-                                                    _ptr(params), _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows),
-                                                    int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
-                                                    float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                                    _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_noisy_grad(rc, 'qhea_model_train_steps_noisy_exact')
-    return rows
+    return _train_steps_noisy(False, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                              first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+
+
+def model_device_noisy_log10_amplification(desc, noise):
+    """
+    qhea_model_device_noisy_log10_amplification (host only): log10 A_dev of this shape under `noise` (a DeviceNoiseParams) --
+    what the inverse walk of the device-noise gradient amplifies the traceless part of rho by; inf for a singular channel,
+    NaN for a bad descriptor or a setting the library refuses.  The gradient calls refuse values above their bound
+    (model_device_noisy_refused answers for a model and a setting).
+    """
+    return float(load().qhea_model_device_noisy_log10_amplification(ctypes.byref(desc), ctypes.byref(noise)))
+
+
+def model_device_noisy_refused(desc, noise):
+    """
+    Whether the device-noise gradient calls refuse this model under `noise` (a DeviceNoiseParams) with QHEA_EUNSUPPORTED --
+    n >= 7, a singular channel, or log10 A_dev above the library's bound.  Asked of the library itself: the call on an empty
+    batch runs every check in front of the batch and launches nothing (host only, no device needed).  Raises QheaError for a
+    setting the library refuses as invalid.
+    """
+    rc = load().qhea_model_loss_grad_noisy_device_exact(ctypes.byref(desc), 0, None, None, None, None, None, ctypes.byref(noise),
+                                                        1.0, None, None, None, 0, None)
+    if rc == -2:
+        return True
+    _check(rc, 'qhea_model_loss_grad_noisy_device_exact')
+    return False
+
+
+def model_loss_grad_noisy_device_exact(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None, pred=None):
+    """
+    model_loss_grad_noisy_exact with `noise` a DeviceNoiseParams (qhea_model_loss_grad_noisy_device_exact): loss and exact
+    gradient of the prediction of model_forward_noisy_device_exact.  Same errors.
+    """
+    return _loss_grad_noisy(True, desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred)
+
+
+def model_train_steps_noisy_device_exact(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                         first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag=None):
+    """
+    model_train_steps_noisy_exact with `noise` a DeviceNoiseParams (qhea_model_train_steps_noisy_device_exact).  Bitwise a loop
+    of model_loss_grad_noisy_device_exact + adam_step.
+    """
+    return _train_steps_noisy(True, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                              first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
 
 
 def clock_probe(device, n_workgroups=1024, iters=200000):

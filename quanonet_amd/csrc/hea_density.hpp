@@ -1,7 +1,8 @@
 // hea_density.hpp -- what the density-matrix kernels share: the exact noisy forward (hea_density.hip) and its adjoint gradient
-// (hea_density_grad.hip).  Element layout, bank fold, the pass over two wires, the gates and the depolarizing channels in their
+// (hea_density_grad.hip), and their counterparts under a device noise model (hea_density_device.hip,
+// hea_density_device_grad.hip).  Element layout, bank fold, the pass over two wires, the gates and the depolarizing channels in their
 // closed forms, and the forward sweep's passes; hea_density.hip describes the layout.  Everything sits in an unnamed namespace:
-// each of the two translation units compiles its own copy into its own kernels.
+// each translation unit compiles its own copy into its own kernels.
 #pragma once
 #include <cmath>
 #include <cstdint>

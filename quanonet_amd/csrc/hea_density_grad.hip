@@ -17,27 +17,16 @@
 // workspace; reduce_density_kernel adds the rows of one parameter in a fixed order (lane l takes rows l, l + 64, ...; the 64
 // lane sums by the same butterfly), applies the frequency chain rule and -- train_steps -- the Adam update of hea_adam.hpp.
 // No atomics; nothing depends on the grid, and a row's record and pred do not depend on the batch or on other rows.
-#include "hea_density.hpp"
-#include "hea_adam.hpp"
+// What the walk shares with hea_density_device_grad.hip (the same walk over the channel sites of a device noise model) is in
+// hea_density_grad.hpp; launch_density_reduce at the end of this file serves both units.
+#include "hea_density_grad.hpp"
 #include "hea_train.hpp"
 #include "hea_sincos.hpp"
 
 namespace qhea {
 namespace {
 
-constexpr int kTracesPerPass = 8;                                        // two wires x (three angles + the encoding)
 constexpr int kRedWaves = 4;                                             // reduce kernel: one parameter per wave
-// Threads of a density_bwd_kernel workgroup: a row's 4^(n-2) threads, at least QHEA_DENS_BWD_THREADS.  A workgroup's rows are
-// independent (they meet only at the pass barriers), so the choice changes no result; it decides how many CUs a small batch
-// spreads over and how many rows share a CU's LDS.  Measured at 64 and 256: one wave per workgroup is faster
-// at every batch measured (n = 5, batch 100: 1.55 against 1.93 ms per step), so that is what is built.
-#ifndef QHEA_DENS_BWD_THREADS
-#define QHEA_DENS_BWD_THREADS 64
-#endif
-template <int N> constexpr int bwd_threads() {
-    return (1 << (2 * N - 4)) > QHEA_DENS_BWD_THREADS ? (1 << (2 * N - 4)) : QHEA_DENS_BWD_THREADS;
-}
-
 struct DensGradArgs {
     DensArgs f;                             // the forward's arguments (f.pred: the caller's pred or NULL; f.sd = NULL)
     const double* w;                        // ansatz angles [blk, 3, n]
@@ -47,44 +36,6 @@ struct DensGradArgs {
     double* pred_ws;                        // [B]
     double* rec;                            // [E + 3 n blk][B]: d pred_b / d x[b, e], then d pred_b / d w[s, k, q]
 };
-
-// A pass' 32 LDS addresses depend on the thread alone, so the compiler computes those of every pass once, ahead of the loop
-// over the sub-layers, and keeps 32 n values alive through it (up to 198 AGPRs at n = 6, beside the 256 VGPRs the elements and
-// their arithmetic take).  A zero it cannot see through, taken inside the pass, makes it form them where they are used.
-__device__ __forceinline__ int opaque_zero() {
-    int z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-}
-
-// A trace is needed only when the pass ends, and the compiler would move its arithmetic down to there -- keeping the 32 elements
-// it reads alive past the un-rotation that replaces them, once per trace.  This pins the value where it is computed.
-__device__ __forceinline__ double pinned(double t) {
-    asm volatile("" : "+v"(t));
-    return t;
-}
-
-__device__ __forceinline__ double im_cj(double2 a, double2 b) { return a.x * b.y - a.y * b.x; }     // Im(conj(a) b)
-__device__ __forceinline__ double re_cj(double2 a, double2 b) { return a.x * b.x + a.y * b.y; }     // Re(conj(a) b)
-
-// this thread's share of Im Tr(O sigma_AX rho) for the wire of stride S (AX: 0 X, 1 Y, 2 Z)
-template <int S, int AX>
-__device__ __forceinline__ double trace16(const double2 (&o)[16], const double2 (&e)[16]) {
-    double t = 0.0;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int b = S == 1 ? 4 * m : m;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {                                    // column bit; elements (row bit 0, row bit 1)
-            const double2 o0 = o[b + S * (2 * c)], o1 = o[b + S * (2 * c + 1)];
-            const double2 r0 = e[b + S * (2 * c)], r1 = e[b + S * (2 * c + 1)];
-            if (AX == 0) t += im_cj(o0, r1) + im_cj(o1, r0);
-            else if (AX == 1) t += re_cj(o1, r0) - re_cj(o0, r1);
-            else t += im_cj(o0, r0) - im_cj(o1, r1);
-        }
-    }
-    return t;
-}
 
 // one-qubit channel with given coefficients (the forward's on O, the inverse's on rho)
 template <int S>
@@ -98,71 +49,6 @@ __device__ __forceinline__ void channel1(double2 (&e)[16], double keep, double m
         e[b + S].x *= off; e[b + S].y *= off;
         e[b + 2 * S].x *= off; e[b + 2 * S].y *= off;
     }
-}
-
-// e <- R e R^T with R = RY(theta)^dagger = [[c, s], [-s, c]]
-template <int S>
-__device__ __forceinline__ void unrotate_y(double2 (&e)[16], double c, double s) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int b = S == 1 ? 4 * m : m;
-        const double2 x00 = e[b], x10 = e[b + S], x01 = e[b + 2 * S], x11 = e[b + 3 * S];
-        const double2 r00 = make_double2(c * x00.x + s * x10.x, c * x00.y + s * x10.y);
-        const double2 r10 = make_double2(c * x10.x - s * x00.x, c * x10.y - s * x00.y);
-        const double2 r01 = make_double2(c * x01.x + s * x11.x, c * x01.y + s * x11.y);
-        const double2 r11 = make_double2(c * x11.x - s * x01.x, c * x11.y - s * x01.y);
-        e[b] = make_double2(c * r00.x + s * r01.x, c * r00.y + s * r01.y);
-        e[b + 2 * S] = make_double2(c * r01.x - s * r00.x, c * r01.y - s * r00.y);
-        e[b + S] = make_double2(c * r10.x + s * r11.x, c * r10.y + s * r11.y);
-        e[b + 3 * S] = make_double2(c * r11.x - s * r10.x, c * r11.y - s * r10.y);
-    }
-}
-
-// e <- U e U^dagger with U = RX(theta)^dagger = [[c, i s], [i s, c]]
-template <int S>
-__device__ __forceinline__ void unrotate_x(double2 (&e)[16], double c, double s) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int b = S == 1 ? 4 * m : m;
-        const double2 x00 = e[b], x10 = e[b + S], x01 = e[b + 2 * S], x11 = e[b + 3 * S];
-        // U on the row index: i s (x + i y) = (-s y, s x)
-        const double2 r00 = make_double2(c * x00.x - s * x10.y, c * x00.y + s * x10.x);
-        const double2 r10 = make_double2(c * x10.x - s * x00.y, c * x10.y + s * x00.x);
-        const double2 r01 = make_double2(c * x01.x - s * x11.y, c * x01.y + s * x11.x);
-        const double2 r11 = make_double2(c * x11.x - s * x01.y, c * x11.y + s * x01.x);
-        // U* on the column index: -i s (x + i y) = (s y, -s x)
-        e[b] = make_double2(c * r00.x + s * r01.y, c * r00.y - s * r01.x);
-        e[b + 2 * S] = make_double2(c * r01.x + s * r00.y, c * r01.y - s * r00.x);
-        e[b + S] = make_double2(c * r10.x + s * r11.y, c * r10.y - s * r11.x);
-        e[b + 3 * S] = make_double2(c * r11.x + s * r10.y, c * r11.y - s * r10.x);
-    }
-}
-
-// e <- D e D^dagger with D = RZ(theta)^dagger: rho10 *= exp(-i theta), rho01 *= exp(i theta); (c, s) = (cos, sin)(theta / 2)
-template <int S>
-__device__ __forceinline__ void unrotate_z(double2 (&e)[16], double c, double s) {
-    const double C = c * c - s * s, Sn = 2.0 * s * c;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int b = S == 1 ? 4 * m : m;
-        const double2 x10 = e[b + S], x01 = e[b + 2 * S];
-        e[b + S] = make_double2(C * x10.x + Sn * x10.y, C * x10.y - Sn * x10.x);
-        e[b + 2 * S] = make_double2(C * x01.x - Sn * x01.y, C * x01.y + Sn * x01.x);
-    }
-}
-
-// channel (inverse on rho), then CNOT(c -> t) on both indices: the reverse of cnot_depolarize2
-__device__ __forceinline__ void undo_cnot2(double2 (&e)[16], double keep, double mix) {
-    const double sx = (e[0].x + e[3].x) + (e[12].x + e[15].x), sy = (e[0].y + e[3].y) + (e[12].y + e[15].y);
-    double2 r[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const bool eq = k == 0 || k == 3 || k == 12 || k == 15;
-        r[k].x = eq ? keep * e[k].x + mix * sx : keep * e[k].x;
-        r[k].y = eq ? keep * e[k].y + mix * sy : keep * e[k].y;
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k) e[k] = r[k ^ ((k >> 2) & 1) ^ (((k >> 3) & 1) << 1)];
 }
 
 // encoding of wire q: channel, trace (slot 3 of the wire's four), RX^dagger
@@ -196,57 +82,6 @@ __device__ __forceinline__ void undo_wire(double2 (&e)[16], double2 (&o)[16], co
     unrotate_y<S>(o, cn, sn);
     tr[3] = 0.0;
     if (enc) undo_encoding<S>(e, o, a, csr[col + q], tr);
-}
-
-// What the passes need of the workgroup: the row's rho and O, its rank and fold, where its record goes
-template <int N> struct RowCtx {
-    static constexpr int TPR = 1 << (2 * N - 4), WPR = TPR > 64 ? TPR / 64 : 1;
-    double2* rho; double2* obs;
-    double* red;                            // [2][WPR][kTracesPerPass], n = 6 only
-    int rank, sf, parity;
-    long r, B;
-    bool live;
-};
-
-// Adds tr[0 .. 8) over the row's threads and stores the sums whose record index idx[i] is >= 0.  Called by every thread of the
-// workgroup after a reverse pass has stored its elements, with the pass' closing barrier inside.
-template <int N>
-__device__ __forceinline__ void flush_traces(RowCtx<N>& cx, const DensGradArgs& a, double (&tr)[kTracesPerPass],
-                                             const int (&idx)[kTracesPerPass]) {
-    using C = RowCtx<N>;
-    constexpr int W = C::TPR < 64 ? C::TPR : 64;
-#pragma unroll
-    for (int i = 0; i < kTracesPerPass; ++i) {
-#pragma unroll
-        for (int o = W / 2; o >= 1; o >>= 1) tr[i] += __shfl_xor(tr[i], o);
-    }
-    if constexpr (C::WPR == 1) {
-        __syncthreads();
-        if (cx.rank == 0 && cx.live) {
-#pragma unroll
-            for (int i = 0; i < kTracesPerPass; ++i)
-                if (idx[i] >= 0) a.rec[(long)idx[i] * cx.B + cx.r] = tr[i];
-        }
-    } else {
-        double* red = cx.red + cx.parity * (C::WPR * kTracesPerPass);
-        const int tid = (int)threadIdx.x;
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int i = 0; i < kTracesPerPass; ++i) red[(tid >> 6) * kTracesPerPass + i] = tr[i];
-        }
-        __syncthreads();
-        if (tid < kTracesPerPass && cx.live) {
-            int my = -1;
-#pragma unroll
-            for (int i = 0; i < kTracesPerPass; ++i) my = tid == i ? idx[i] : my;
-            if (my >= 0) {
-                double t = red[tid];
-                for (int wv = 1; wv < C::WPR; ++wv) t += red[wv * kTracesPerPass + tid];
-                a.rec[(long)my * cx.B + cx.r] = t;
-            }
-        }
-        cx.parity ^= 1;                                                  // the next pass' partials go to the other buffer
-    }
 }
 
 // the reverse of ring_passes: passes J = N - 1 .. 0 of sub-layer s
@@ -305,24 +140,6 @@ __device__ __forceinline__ void encoding_passes_back(RowCtx<N>& cx, const DensGr
         P::store(o, cx.obs, b);
         flush_traces<N>(cx, a, tr, idx);
         encoding_passes_back<N, J + 2>(cx, a, csr, col);
-    }
-}
-
-// U on every wire of one matrix in LDS (no noise): KIND 3 = H, 4 = S H (the daggers of the read-out basis changes)
-template <int N, int J, int KIND>
-__device__ __forceinline__ void basis_passes_back(double2* row, int rank, int sf) {
-    if constexpr (J < N) {
-        using P = Pass<N, J>;
-        const int i0 = P::base(rank | opaque_zero()), b = i0 ^ fold(i0) ^ sf;
-        double2 e[16];
-        P::load(e, row, b);
-        const U2 h = KIND == 3 ? U2{{M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {-M_SQRT1_2, 0.0}}
-                               : U2{{M_SQRT1_2, 0.0}, {M_SQRT1_2, 0.0}, {0.0, M_SQRT1_2}, {0.0, -M_SQRT1_2}};
-        apply_gate<1>(e, h);
-        if (J + 1 < N) apply_gate<4>(e, h);
-        P::store(e, row, b);
-        __syncthreads();
-        basis_passes_back<N, J + 2, KIND>(row, rank, sf);
     }
 }
 
@@ -486,19 +303,6 @@ __global__ __launch_bounds__(64 * kRedWaves) void reduce_density_kernel(DensRed 
     }
 }
 
-struct DensGradLayout { size_t off_gates, off_cs, off_pred, off_rec, total; };
-
-DensGradLayout dens_grad_layout(const ModelInfo& mi, int64_t B) {
-    DensGradLayout L{};
-    const DensLayout F = dens_layout(mi, B);
-    L.off_gates = F.off_gates; L.off_cs = F.off_cs;
-    size_t p = F.total;
-    L.off_pred = p; p = align256(p + (size_t)B * sizeof(double));
-    L.off_rec = p;  p = align256(p + (size_t)B * ((size_t)mi.sh.E + (size_t)3 * mi.n * mi.sh.blk) * sizeof(double));
-    L.total = p;
-    return L;
-}
-
 template <int N>
 int launch_density_bwd(const DensGradArgs& a, hipStream_t st) {
     constexpr int T = bwd_threads<N>(), TPR = 1 << (2 * N - 4), RPW = T / TPR, WPR = TPR > 64 ? TPR / 64 : 1;
@@ -544,8 +348,16 @@ int loss_grad_launch(const qhea_model_desc* desc, const ModelInfo& mi, int64_t b
     }
     if (rc != QHEA_OK) return rc;
 
+    return launch_density_reduce(desc, mi, batch, branch, trunk, y, a.rec, a.pred_ws, inv_bt, grad, adam, st);
+}
+
+}  // namespace
+
+int launch_density_reduce(const qhea_model_desc* desc, const ModelInfo& mi, int64_t batch, const double* branch,
+                          const double* trunk, const double* y, const double* rec, const double* pred, double inv_bt,
+                          double* grad, const AdamArgs& adam, hipStream_t st) {
     DensRed d{};
-    d.rec = a.rec; d.pred = a.pred_ws; d.y = y;
+    d.rec = rec; d.pred = pred; d.y = y;
     d.in[0] = desc->model == QHEA_MODEL_QUANONET ? trunk : branch; d.in[1] = branch;
     d.B = batch; d.P = mi.P; d.off_ans = mi.off_ans; d.off_bias = mi.off_bias;
     for (int s = 0; s < 2; ++s) {
@@ -557,8 +369,6 @@ int loss_grad_launch(const qhea_model_desc* desc, const ModelInfo& mi, int64_t b
                        st, d);
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
-
-}  // namespace
 }  // namespace qhea
 
 using namespace qhea;

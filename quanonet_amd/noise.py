@@ -225,11 +225,12 @@ class DeviceNoise:
 def _uniform_only(noise, who, why):
     if isinstance(noise, DeviceNoise):
         raise ValueError(f"{who} takes a NoiseModel, not a DeviceNoise: {why}; exact_noisy_predict and "
-                         "evaluate_noisy(exact=True) evaluate a DeviceNoise")
+                         "evaluate_noisy(exact=True) evaluate a DeviceNoise, device_noisy_loss_and_grad, device_amplification "
+                         "and the config key train_device_noise differentiate and train under one")
 
 
 _TRAJECTORY_WHY = "the trajectory kernels sample Pauli errors only and relaxation is not a Pauli channel"
-_GRADIENT_WHY = "the gradient's reverse walk inverts the uniform depolarizing channels only"
+_GRADIENT_WHY = "this call's reverse walk inverts the uniform depolarizing channels only"
 
 
 def _model_inputs(model, inputs):
@@ -332,3 +333,42 @@ def exact_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
         return grad
     inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
     return _lib.model_loss_grad_noisy_exact(desc, branch, trunk, y, flat, noise.params(), inv, grad, ham_diag=ham_diag)
+
+
+def _device_noise(noise, who):
+    if not isinstance(noise, DeviceNoise):
+        raise ValueError(f"{who} takes a DeviceNoise (got {type(noise).__name__}); a NoiseModel goes to its uniform "
+                         "counterpart, or through DeviceNoise.uniform")
+
+
+def device_amplification(model, noise):
+    """
+    log10 A_dev of this model's circuit under `noise` (a DeviceNoise): what the inverse walk of the device-noise gradient
+    multiplies the traceless part of rho by, - sum log10 min(off, a) over the one-wire channel sites the circuit applies
+    - sum log10 (1 - 16 p2[j] / 15) over its CNOT slots.  For DeviceNoise.uniform(nm) it is amplification(model, nm).  The
+    training calls refuse values above 7 (and singular channels, inf): the bound is lower than the uniform walk's 12 because
+    relaxation is not self-adjoint.  No device is needed.
+    """
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("device_amplification takes a QuanONetPT or HEAQNNPT model")
+    _device_noise(noise, 'device_amplification')
+    desc = model.fused_desc()
+    return _lib.model_device_noisy_log10_amplification(desc, noise.params(desc.n_qubits))
+
+
+def device_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
+    """
+    exact_noisy_loss_and_grad under a DeviceNoise: the MSE loss of exact_noisy_predict(model, inputs, noise) and its exact
+    gradient, as the flat [P + 2] tensor of qhea_model_loss_grad_noisy_device_exact (same layout, same inv_batch_total).  The
+    adjoint walk through the density matrix with the device's channel sites: no sampling, n <= 6.
+    """
+    _device_noise(noise, 'device_noisy_loss_and_grad')
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'device_noisy_loss_and_grad')
+    B = branch.shape[0]
+    y = y.detach().to(torch.float64).reshape(-1).contiguous()
+    grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
+    if B == 0:
+        return grad
+    inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
+    return _lib.model_loss_grad_noisy_device_exact(desc, branch, trunk, y, flat, noise.params(desc.n_qubits), inv, grad,
+                                                   ham_diag=ham_diag)

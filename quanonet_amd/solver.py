@@ -305,6 +305,22 @@ def _train_noise(v):
     raise ValueError(f"train_noise must be a quanonet_amd.noise.NoiseModel or a dict of its fields (got {type(v).__name__})")
 
 
+def _train_device_noise(v, train_noise=None):
+    """config value / argument `train_device_noise` -> DeviceNoise or None (a DeviceNoise, or its asdict() form); a key of its
+    own because the dict forms of the two noise records have different fields.  Both keys together are refused."""
+    if v is None:
+        return None
+    from .noise import DeviceNoise
+    if train_noise is not None:
+        raise ValueError("train_noise and train_device_noise are both set: a run trains under one noise model")
+    if isinstance(v, DeviceNoise):
+        return v
+    if isinstance(v, dict):
+        return DeviceNoise.fromdict(v)
+    raise ValueError("train_device_noise must be a quanonet_amd.noise.DeviceNoise or its asdict() form "
+                     f"(got {type(v).__name__}); a NoiseModel goes to train_noise")
+
+
 class DataParallelTrainer:
     """
     fused='auto': when the model is one of this package's QuanONetPT / HEAQNNPT (fp64, on a HIP
@@ -314,9 +330,10 @@ class DataParallelTrainer:
     """
 
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
-                 fused='auto', peer_exchange=True, log=None, train_noise=None):
+                 fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None):
         self.model = model
         self.train_noise = _train_noise(train_noise)
+        self.train_device_noise = _train_device_noise(train_device_noise, train_noise)
         self.world = int(world_size)
         self.dist = dist
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -390,6 +407,37 @@ class DataParallelTrainer:
                 log(f"noise-aware training: the loss and 'loss_train' are the exact noisy MSE under p1={self.train_noise.p1:g} "
                     f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g} (log10 amplification {amp:.2f})")
 
+        if self.train_device_noise is not None:
+            # the loss is the exact one under the device model (qhea_model_loss_grad_noisy_device_exact): the same refusals
+            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+                raise ValueError("train_device_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP "
+                                 "device, Adam with betas / eps / weight_decay only)")
+            from . import _lib
+            n = self.desc.n_qubits
+            try:
+                rec = self.train_device_noise.params(n)
+                amp = _lib.model_device_noisy_log10_amplification(self.desc, rec)
+                refused = _lib.model_device_noisy_refused(self.desc, rec)     # the library's own checks and bound
+            except _lib.QheaError as e:
+                raise ValueError(f"train_device_noise: {e}") from e
+            if refused:
+                raise ValueError(f"train_device_noise: the library refuses this model under this DeviceNoise (n = {n}, log10 "
+                                 f"amplification {amp:.2f}): n <= 6 and a log10 amplification within the bound of "
+                                 "include/quanonet_hea.h are needed; see quanonet_amd.noise.device_amplification")
+            if self.peer_fused:
+                self.peer_fused = False
+                self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
+                                           "with the exchange inside")
+            if log is not None:
+                log("device-noise training: the loss and 'loss_train' are the exact noisy MSE under the DeviceNoise of "
+                    f"train_device_noise (log10 amplification {amp:.2f})")
+
+    def _noise_params(self):
+        """the noise record of the training loss as the C ABI takes it, or None (the ideal loss)"""
+        if self.train_device_noise is not None:
+            return self.train_device_noise.params(self.desc.n_qubits)
+        return None if self.train_noise is None else self.train_noise.params()
+
     def broadcast_parameters(self):
         self.dist.broadcast(self.pflat, src=0)
 
@@ -417,7 +465,9 @@ class DataParallelTrainer:
             from . import _lib
             data = (self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat)
             grad = self.flat if out is None else out
-            if self.train_noise is not None:
+            if self.train_device_noise is not None:
+                _lib.model_loss_grad_noisy_device_exact(*data, self._noise_params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
+            elif self.train_noise is not None:
                 _lib.model_loss_grad_noisy_exact(*data, self.train_noise.params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
             else:
                 _lib.model_loss_grad(*data, 1.0 / gb, grad, ham_diag=self._ham_diag())
@@ -446,7 +496,7 @@ class DataParallelTrainer:
             gb = float(global_batch if global_batch is not None else y.shape[0])
             opt = self.optimizer
             opt.t += 1
-            if self.train_noise is not None:                # (the noise-aware path has the steps entry only: one step of it)
+            if self._noise_params() is not None:            # (the noise-aware paths have the steps entry only: one step of it)
                 self._steps(inputs, y, [0, y.shape[0]], [gb], flat.view(1, -1), opt.t)
             else:
                 _lib.model_train_step(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat, 1.0 / gb, flat, opt.exp_avg,
@@ -478,12 +528,15 @@ class DataParallelTrainer:
         return flat
 
     def _steps(self, inputs, y, bounds, global_batches, rows, first_step):
-        """single device: the steps entry, ideal (qhea_model_train_steps) or under train_noise (..._noisy_exact)"""
+        """single device: the steps entry, ideal (qhea_model_train_steps), under train_noise (..._noisy_exact) or under
+        train_device_noise (..._noisy_device_exact)"""
         from . import _lib
         opt = self.optimizer
         call = (self.desc, bounds, global_batches, *split_inputs(inputs), y.reshape(-1), self.pflat, rows, opt.exp_avg,
                 opt.exp_avg_sq, first_step, *opt.hparams())
-        if self.train_noise is not None:
+        if self.train_device_noise is not None:
+            _lib.model_train_steps_noisy_device_exact(*call, self._noise_params(), ham_diag=self._ham_diag())
+        elif self.train_noise is not None:
             _lib.model_train_steps_noisy_exact(*call, self.train_noise.params(), ham_diag=self._ham_diag())
         else:
             _lib.model_train_steps(*call, ham_diag=self._ham_diag())
@@ -671,7 +724,8 @@ class PTSolver:
                                            dist=dist, optimizer=config.get('optimizer', 'adam'),
                                            optimizer_kwargs=config.get('optimizer_kwargs', {}),
                                            peer_exchange=str(config.get('dp_exchange', 'peer')).lower() == 'peer',
-                                           log=self.log, train_noise=config.get('train_noise'))
+                                           log=self.log, train_noise=config.get('train_noise'),
+                                           train_device_noise=config.get('train_device_noise'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None
