@@ -555,6 +555,85 @@ int    qhea_model_train_steps_noisy_device_exact(const qhea_model_desc* desc, in
                                                  size_t workspace_bytes, void* stream);
 
 /*
+ * Noisy forward under the calibrated device noise model by quantum-jump (Monte-Carlo wave-function) trajectories: an unbiased
+ * estimate of pred of qhea_model_forward_noisy_device_exact, for the qubit counts that call cannot reach (n = 7..9) and for
+ * finite shots at any n = 2..9 -- what an Estimator with default_shots = S returns on that device.  Arguments, estimators and
+ * stderr_out are those of qhea_model_forward_noisy with the noise setting split in two: `dn` (the device) and `sampling`.
+ *
+ * Model.  Exactly the qhea_device_noise model above, timeline and the four folded sites per wire included.  Folding the idle
+ * slots into the sites is exact as a channel, so a trajectory sees one relaxation R(tau) per site with the folded duration:
+ *   ENC t_rx;  ROT t_rot, or t_rot + (q - 1) t_cx for q >= 1 with idle;  CTL t_cx;  TGT (n - 1) t_cx for wire 0 and
+ *   (n - q) t_cx for q >= 1;  with idle = 0: t_cx for CTL and TGT, t_rot for ROT.
+ * Unravelling of R(tau) on wire q:  gamma = 1 - exp(-tau / t1[q]);  f = exp(-tau / t2[q]) / sqrt(1 - gamma), clipped to <= 1,
+ *   f = 0 when gamma = 1;  pz = (1 - f) / 2.  Two events, in this order:
+ *     1. dephasing: Z on wire q with probability pz (state-independent);
+ *     2. damping: with P1 the population of wire q in |1> of the current normalised state, with probability gamma P1 the state
+ *        becomes |0><1|_q psi / sqrt(P1), otherwise diag(1, sqrt(1 - gamma))_q psi / sqrt(1 - gamma P1).
+ *   An infinite t1 or a zero duration gives gamma = 0 and the damping event is the identity, bit for bit.  (Amplitude damping
+ *   followed by phase damping: the Kraus pair of the exact call's relaxation.)  Depolarizing stays the sampled Pauli of
+ *   qhea_noise, with p1[q] per wire and p2[j] per slot.  qhea_device_noise_jump_tables (host only, no device needed, n = 2..12
+ *   like qhea_device_noise_tables) returns jump[site][q] = (gamma, pz) as [4][n][2] doubles.
+ * Events in circuit order, which is also the order random numbers are consumed in:
+ *   - per block: for q = 0..n-1 the encoding RX on q, then site ENC_q;
+ *   - per sub-layer: for q = 0..n-1 the fused rotation on q, then site ROT_q; then for j = 0..n-1: CNOT((j+1) mod n -> j), the
+ *     pair Pauli with p2[j], relaxation TGT of wire j, relaxation CTL of wire (j+1) mod n.
+ *   A site ENC_q or ROT_q is: Pauli with p1[q], then dephasing, then damping.
+ * Random numbers: Philox4x32-10, key = seed, counter = (call, trajectory, row_lo, row_hi) with the GLOBAL row index row0 + b.
+ *   Every event group is one whole call: words 0 and 1 pick the Pauli by the rule of qhea_noise (error iff w0 < floor(p 2^32);
+ *   one qubit (w1 * 3) >> 32, two qubits 1 + ((w1 * 15) >> 32) with control = code >> 2, target = code & 3); word 2 is the
+ *   dephasing, Z iff w2 < floor(pz 2^32); word 3 is the damping, which jumps iff (w3 + 0.5) 2^-32 < gamma P1 in fp64.  The
+ *   kernels carry the state unnormalised with its squared norm N2 beside it and evaluate that as u N2 < gamma M, M the masked
+ *   sum below (P1 = M / N2; a jump leaves N2 = M, no jump N2 - gamma M); a replay that normalises at every site agrees except
+ *   where u lies within a few ulps of the edge.
+ *   ENC_q and ROT_q take one call each; slot j takes two: the first gives the pair Pauli (words 0, 1) and TGT's words 2, 3, the
+ *   second CTL's words 2, 3 (its words 0, 1 are unused).  A block with linear depth ld has n + 3 n ld calls; C = the circuit's
+ *   total.  Shot mode continues from call C as qhea_noise continues from call m: u from words 0, 1 of call C; bit i uses word
+ *   (2 + i) mod 4 of call C + (2 + i) / 4; a bit that is 0 flips iff its word is < floor(readout01[i] 2^32), a bit that is 1 iff
+ *   it is < floor(readout10[i] 2^32).
+ * Estimators: expectation mode (sampling.shots = 0, T = sampling.trajectories) and shot mode (S = sampling.shots) of
+ *   qhea_noise; stderr_out = sample deviation / sqrt(count).  The asymmetric readout is folded into expectation mode as
+ *     h(k) = offset + coeff sum_i (bit_i(k) ? -(1 - 2 readout10[i]) : 1 - 2 readout01[i]),  or with ham_diag
+ *     diag'[k] = sum_j prod_i c_i(bit_i(j) | bit_i(k)) diag[j],  c_i = bit i's 2 x 2 confusion matrix, k the true string.
+ * Summation, each order a function of n and the number of values per row only:
+ *   1. tiles of 64 trajectories, a row's tile sums added in tile order; inside a tile, n = 2..6: slot j of the 64 / 2^n slots
+ *      adds trajectories j, j + slots, .. in that order and the slots are added in slot order; n = 7..9: trajectory order;
+ *   2. the masked sum M of a damping site (|psi_k|^2 over the k whose wire is |1>, zero elsewhere): n = 2..6 the xor butterfly
+ *      over the trajectory's 2^n lanes, offsets 2^(n-1), .., 1; n = 7..9 per lane the terms k = l + 64 r in the order
+ *      r = 0, 1, .., then the butterfly over the 64 lanes, offsets 32, .., 1 (wires 6..8 select registers, not lanes);
+ *   3. read-out: value = (sum_k p_k h'(k)) / (sum_k p_k) + offset term, p_k = |psi_k|^2 of the unnormalised final state, both
+ *      sums in the order of 2 (unmasked); h' is built by one launch: the sum over i in the order i = 0..n-1 times coeff, or
+ *      diag' bit by bit, h <- (1 - e) h + e h[k ^ 2^i] for i = 0..n-1 with e = readout01[i] where bit i of k is 0 and
+ *      readout10[i] where it is 1;
+ *   4. shot mode: the first k with u sum_k p_k < cdf[k] (the total as in 3); cdf in index order for n = 2..6, and for n = 7..9
+ *      the blocks-of-64 Hillis-Steele scan of qhea_model_forward_noisy_wide; if there is none, the last k with p_k > 0.
+ * No floating-point atomics; results are bitwise reproducible and independent of the batch, the grid and the chunking.
+ * Scope: n = 2..9, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.  Out of scope: n = 10..12
+ * (QHEA_EUNSUPPORTED: with the state in LDS every damping site would cost a workgroup-wide reduction and a pass; an LDS variant
+ * can be added later); gradients and training through trajectories; thermal population, crosstalk and routing, as above.
+ * Errors, all before anything is launched, outputs untouched: QHEA_EINVAL for the cases of
+ * qhea_model_forward_noisy_device_exact (by the same code) and for a bad sampling record (NULL, shots < 0, trajectories < 1 in
+ * expectation mode, more than 2^32 - 1 values per row); then QHEA_EUNSUPPORTED for n >= 10; then the errors of
+ * qhea_model_forward_noisy (and QHEA_EINVAL for batch * ceil(values / 64) > 2^31 - 1).
+ * Launches: the prep kernel, one kernel that writes the per-site constants (and expectation mode's h') into the workspace, the
+ * trajectory kernel, the finishing kernel of qhea_model_forward_noisy; no allocation, no synchronisation (hipGraph-capturable).
+ */
+typedef struct qhea_sampling {
+    int64_t  shots;             /* 0: expectation mode; S >= 1: shot mode (one trajectory per shot) */
+    int64_t  trajectories;      /* expectation mode: T >= 1 (ignored in shot mode)                  */
+    uint64_t seed;
+} qhea_sampling;
+
+int    qhea_device_noise_jump_tables(int n, const qhea_device_noise* dn /*HOST*/, double* jump /*HOST [4][n][2] = (gamma, pz)*/);
+/* DEVICE scratch bytes for qhea_model_forward_noisy_device on `batch` rows (0 on a bad descriptor or sampling record, or n >= 10). */
+size_t qhea_model_noisy_device_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling);
+int    qhea_model_forward_noisy_device(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                       const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                       const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                       const qhea_device_noise* dn /*HOST*/, const qhea_sampling* sampling /*HOST*/,
+                                       double* pred /*DEVICE [B]*/, double* stderr_out /*DEVICE [B] or NULL*/,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the
  * SAME parameters -- the chunk loop of PTSolver.evaluate / infer.predict (solvers/solver_pt.py:299-310, infer.py:274-289) in
  * one host call.  The layer records depend on the parameters alone, so one preparation launch serves all chunks of

@@ -41,7 +41,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact',
            'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact',
            'qhea_model_device_noisy_grad_workspace_bytes', 'qhea_model_device_noisy_log10_amplification',
-           'qhea_model_loss_grad_noisy_device_exact', 'qhea_model_train_steps_noisy_device_exact']
+           'qhea_model_loss_grad_noisy_device_exact', 'qhea_model_train_steps_noisy_device_exact',
+           'qhea_device_noise_jump_tables', 'qhea_model_noisy_device_workspace_bytes', 'qhea_model_forward_noisy_device']
 
 
 class ModelDesc(ctypes.Structure):
@@ -72,8 +73,13 @@ class DeviceNoiseParams(ctypes.Structure):
                [('t_rx', ctypes.c_double), ('t_rot', ctypes.c_double), ('t_cx', ctypes.c_double)]
 
 
+class SamplingParams(ctypes.Structure):
+    """Mirror of `qhea_sampling` (include/quanonet_hea.h): the estimator of the device-noise trajectory call."""
+    _fields_ = [('shots', ctypes.c_int64), ('trajectories', ctypes.c_int64), ('seed', ctypes.c_uint64)]
+
+
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 550           # 0.5.5: + qhea_model_loss_grad / train_steps_noisy_device_exact (training under a device noise model)
+MIN_LIB_VERSION = 560           # 0.5.6: + qhea_model_forward_noisy_device (quantum-jump trajectories under a device noise model)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -235,6 +241,14 @@ def load():
     lib.qhea_device_noise_tables.argtypes = [ctypes.c_int, dnp, f64p, f64p]
     lib.qhea_model_forward_noisy_device_exact.restype = ctypes.c_int
     lib.qhea_model_forward_noisy_device_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, dnp, dp, dp, vp, ctypes.c_size_t, vp]
+    spp = ctypes.POINTER(SamplingParams)
+    lib.qhea_device_noise_jump_tables.restype = ctypes.c_int
+    lib.qhea_device_noise_jump_tables.argtypes = [ctypes.c_int, dnp, ctypes.POINTER(ctypes.c_double)]
+    lib.qhea_model_noisy_device_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_device_workspace_bytes.argtypes = [mdp, ctypes.c_int64, spp]
+    lib.qhea_model_forward_noisy_device.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy_device.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, dp, dp, dp, dp, dnp, spp, dp, dp, vp,
+                                                    ctypes.c_size_t, vp]
     lib.qhea_model_device_noisy_grad_workspace_bytes.restype = ctypes.c_size_t
     lib.qhea_model_device_noisy_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
     lib.qhea_model_device_noisy_log10_amplification.restype = ctypes.c_double
@@ -829,6 +843,48 @@ def model_forward_noisy_device_exact(desc, branch, trunk, params, noise, ham_dia
     setting -- in both cases before anything is launched.
     """
     return _forward_noisy_exact(True, desc, branch, trunk, params, noise, ham_diag, out, shot_std)
+
+
+def device_noise_jump_tables(n, noise):
+    """
+    qhea_device_noise_jump_tables (host only, no device needed): jump [4, n, 2] as a numpy array -- (gamma, pz) of the relaxation
+    of every channel site (ENC, ROT, CTL, TGT) and wire at its folded duration, as the trajectory call unravels it, for `noise`,
+    a DeviceNoiseParams.  Raises QheaError for a setting the library refuses.
+    """
+    import numpy as np
+    n = int(n)
+    jump = np.zeros((4, max(n, 0), 2), dtype=np.float64)
+    _check(load().qhea_device_noise_jump_tables(n, ctypes.byref(noise), jump.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+           'qhea_device_noise_jump_tables')
+    return jump
+
+
+def model_noisy_device_workspace_bytes(desc, batch, sampling):
+    """qhea_model_noisy_device_workspace_bytes: 0 for a bad descriptor or sampling record (a SamplingParams), or n >= 10."""
+    return int(load().qhea_model_noisy_device_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(sampling)))
+
+
+def model_forward_noisy_device(desc, branch, trunk, params, noise, sampling, row0=0, ham_diag=None, out=None, stderr=None):
+    """
+    qhea_model_forward_noisy_device on all rows of branch / trunk in ONE call: (pred[B], stderr[B] or None) from quantum-jump
+    trajectories under `noise` (a DeviceNoiseParams) with the estimator `sampling` (a SamplingParams); row0 is the global index
+    of the first row (the random streams are keyed by it).  n = 2..9: raises Unsupported for n >= 10 and QheaError for a bad
+    noise setting or sampling record -- in both cases before anything is launched.
+    """
+    lib = load()
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
+    _dev_f64(stderr, 'stderr', (B,))
+    pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
+    ws = _sized_ws(branch.device, lib.qhea_model_noisy_device_workspace_bytes, ctypes.byref(desc), int(B), ctypes.byref(sampling))
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_forward_noisy_device(ctypes.byref(desc), int(row0), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
+                                                 _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling), _ptr(pred),
+                                                 _ptr(stderr), _ptr(ws), 0 if ws is None else ws.numel(),
+                                                 _stream(branch.device))
+    if rc == -2:
+        raise Unsupported("qhea_model_forward_noisy_device: unsupported circuit (n >= 10)")
+    _check(rc, 'qhea_model_forward_noisy_device')
+    return pred, stderr
 
 
 def model_exact_noisy_log10_amplification(desc, noise):

@@ -1,0 +1,702 @@
+// hea_noise_device.hip -- qhea_model_forward_noisy_device: the model forward under the calibrated device noise model
+// (qhea_device_noise) estimated from quantum-jump (Monte-Carlo wave-function) trajectories, n = 2..9, expectation mode and shot
+// mode.  The quantity, the unravelling, the random stream and the summation orders are the contract stated in
+// include/quanonet_hea.h; tests/device_traj_reference.py replays them gate by gate.
+//
+// Two kernels, in the layouts of the uniform trajectory units:
+//   n = 2..6   one amplitude per lane, 64 / 2^n trajectories of one row per wave (hea_noise.hip);
+//   n = 7..9   one wave per trajectory in Cfg<N>'s register layout (hea_noise_wide.hip): wires 0..5 on lane bits, 6..8 in registers.
+// A work item is a (row, tile of kTile trajectories) pair as there; noisy_finish_kernel adds a row's tiles.
+//
+// What relaxation changes against the Pauli kernels:
+//   * The state is carried UNNORMALISED with its squared norm beside it (nrm2).  A damping site needs M, the masked sum of
+//     |psi_k|^2 over the amplitudes whose wire is |1>: the jump fires iff u nrm2 < gamma M (u < gamma P1 with P1 = M / nrm2), a
+//     jump leaves nrm2 = M, no jump scales the |1> half by sqrt(1 - gamma) and leaves nrm2 - gamma M.  So a site costs no
+//     division and no square root; the read-out divides by the state's own sum of squares once per trajectory.  A power-of-two
+//     rescale behind a segment keeps the numbers in range (exact, so invisible in the result).
+//   * The Pauli frame (X mask, Z mask) stays unapplied across the sites of a segment: Z bits change no population, an X bit on
+//     the wire swaps which stored bit value is |1> (the polarity of the mask above), the lowering operator acts on the stored
+//     state with that polarity up to a global sign, and dephasing toggles a Z bit.
+//   * A jump sits behind every CNOT slot, so the ring is applied CNOT by CNOT (a one-bit exchange and a select each) and not as
+//     one gather; the frame is conjugated through each as before.
+//   * A fired jump is rare: its exchange is guarded by __any.
+// Philox calls are shared as in segment_codes: lane c of a slot (or of the wave) computes call c of the segment -- the encoding
+// sites of a block, the rotation sites of a sub-layer, or the 2 n calls of its ring -- and reduces it to a code (Pauli in bits
+// 0..3, dephasing in bit 4) and the jump's word; every site reads the two from that lane.  The per-call thresholds and the
+// per-site (gamma, sqrt(1 - gamma)) come from a small table in the workspace that one prep launch fills from its arguments: the
+// trajectory kernels read it by wave-uniform addresses, so the constants live in scalar registers only while a site uses them.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "hea_device_noise.hpp"
+#include "hea_noise_traj.hpp"
+
+namespace qhea {
+namespace {
+
+constexpr int kJumpMaxWires = 9;            // n = 10..12: the state would live in LDS and every site would cost a workgroup pass
+constexpr int kJumpWaves = 4;               // waves per workgroup (independent; no LDS, no barrier)
+
+struct DevTable {                           // 8-byte words only: device_tables_kernel copies it word by word
+    unsigned long long cthr[4 * kJumpMaxWires][2];  // call c of a block's template (ENC 0..n-1, ROT n..2n-1, slot j: 2n + 2j, + 1):
+                                                    // (Pauli threshold, dephasing threshold)
+    double gs[4][kJumpMaxWires][2];                 // [site][wire] (gamma, sqrt(1 - gamma))
+    unsigned long long rthr[kJumpMaxWires][2];      // readout thresholds (01, 10) per bit
+    double rd[kJumpMaxWires][2];                    // readout01, readout10 per bit
+    // what the read-out of a trajectory needs of the call's arguments; the wave kernel reads it there (readout_args)
+    double off, co;
+    const double* diag;
+    unsigned L, pauli;
+};
+constexpr int kTableWords = (int)(sizeof(DevTable) / 8);
+
+// folded duration of site `site` on wire q (the table of the header)
+inline double site_duration(int n, const qhea_device_noise* dn, int site, int q) {
+    const bool idle = dn->idle != 0;
+    switch (site) {
+        case kEnc: return dn->t_rx;
+        case kRot: return dn->t_rot + (idle && q >= 1 ? (q - 1) * dn->t_cx : 0.0);
+        case kCtl: return dn->t_cx;
+        default:   return idle ? (q == 0 ? n - 1 : n - q) * dn->t_cx : dn->t_cx;
+    }
+}
+
+// (gamma, pz) of relaxation for time t: amplitude damping gamma, then Z with probability pz so that the off-diagonals end at
+// exp(-t / T2) in total
+inline void jump_pair(double t, double T1, double T2, double& gamma, double& pz) {
+    const double x1 = std::isinf(T1) ? 0.0 : t / T1, x2 = std::isinf(T2) ? 0.0 : t / T2;
+    gamma = 1.0 - exp(-x1);
+    double f = gamma < 1.0 ? exp(-x2) / sqrt(1.0 - gamma) : 0.0;
+    if (f > 1.0) f = 1.0;                                                // T2 = 2 T1 to rounding
+    pz = 0.5 * (1.0 - f);
+}
+
+inline void jump_tables(int n, const qhea_device_noise* dn, double* jump) {
+    for (int site = 0; site < 4; ++site)
+        for (int q = 0; q < n; ++q)
+            jump_pair(site_duration(n, dn, site, q), dn->t1[q], dn->t2[q], jump[((size_t)site * n + q) * 2],
+                      jump[((size_t)site * n + q) * 2 + 1]);
+}
+
+// ---- device helpers (the file-local ones of hea_noise.hip / hea_noise_wide.hip, which stay as they are) ---------------------------
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// psi <- X^x Z^z psi (up to a global phase): psi'[k] = (-1)^popcount((k ^ x) & z) psi[k ^ x]
+__device__ __forceinline__ void apply_frame(double& re, double& im, int x, int z, int k, int base) {
+    if (__any(x | z)) {
+        const int src = k ^ x;
+        const double pr = __shfl(re, base + src), pi = __shfl(im, base + src);
+        const bool neg = __popc(src & z) & 1;
+        re = neg ? -pr : pr;
+        im = neg ? -pi : pi;
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void frame_regs(double (&re)[Cfg<N>::R], double (&im)[Cfg<N>::R], int x, int z, int lane) {
+    using C = Cfg<N>;
+    if ((x | z) == 0) return;
+    if (x & 63) {
+        const int src = (lane ^ (x & 63)) << 2;
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) { re[r] = lane_gather(re[r], src); im[r] = lane_gather(im[r], src); }
+    }
+    static_for<0, C::RB>([&](auto b) {
+        constexpr int J = 1 << decltype(b)::value;
+        if ((x >> 6) & J) {
+#pragma unroll
+            for (int r = 0; r < C::R; ++r) {
+                if (r & J) continue;
+                double t = re[r]; re[r] = re[r | J]; re[r | J] = t;
+                t = im[r]; im[r] = im[r | J]; im[r | J] = t;
+            }
+        }
+    });
+    if (z) {
+        const int lp = __popc((unsigned)(lane & z & 63));
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) {
+            const bool neg = (lp + __popc((unsigned)(r & (z >> 6)))) & 1;
+            re[r] = neg ? -re[r] : re[r];
+            im[r] = neg ? -im[r] : im[r];
+        }
+    }
+}
+
+// inclusive sum over the lanes 0 .. lane of a wave (Hillis-Steele, distances 1, 2, .. 32: a fixed order)
+__device__ __forceinline__ double wave_scan(double c, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double t = __shfl_up(c, d);
+        if (lane >= d) c += t;
+    }
+    return c;
+}
+
+// This lane's call of a segment: call0 + c for c < cnt, template entry tbase + c of the table.  code = the sampled Pauli
+// (0 none; one qubit 1..3; RING, even calls: the pair 1..15) | dephasing << 4; w3 = the jump's word.  a.thr1 == 0: an ideal
+// setting, nothing is drawn.
+template <bool RING>
+__device__ __forceinline__ void site_draws(const NoiseArgs& a, const DevTable* __restrict__ tab, unsigned call0, int tbase, int cnt,
+                                           int c, unsigned traj, unsigned long long row, unsigned& code, unsigned& w3) {
+    code = 0; w3 = 0;
+    if (a.thr1 == 0 || c >= cnt) return;
+    const uint4 w = philox(make_uint4(call0 + (unsigned)c, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
+    const unsigned long long tp = tab->cthr[tbase + c][0], tz = tab->cthr[tbase + c][1];
+    const unsigned kinds = (RING && !(c & 1)) ? 15u : 3u;
+    if ((unsigned long long)w.x < tp) code = 1u + (unsigned)(((unsigned long long)w.y * kinds) >> 32);
+    if ((unsigned long long)w.z < tz) code |= 16u;
+    w3 = w.w;
+}
+
+// (gamma, sqrt(1 - gamma)) of a site, read where the site uses it.  The addresses are loop-invariant, so without the (empty)
+// fence on the offset every load of the circuit loop is hoisted in front of it and the constants are kept in scalar registers
+// that spill into vector lanes (9 wires: 72 doubles); behind it the pair is one scalar load that lives for the length of its
+// site.  (A fence on the pointer itself would lose its address space: flat vector loads.)
+__device__ __forceinline__ double2 site_pair(const DevTable* __restrict__ tab, int site, int q) {
+    int fence = 0;
+    asm volatile("" : "+s"(fence));
+    const double* p = &tab->gs[site][q][0] + fence;
+    return make_double2(p[0], p[1]);
+}
+
+// v summed over the lanes that differ in bits 0 .. BITS-1, offsets 2^(BITS-1), .., 1; every lane of a group ends with the same sum
+template <int BITS>
+__device__ __forceinline__ double group_sum(double v) {
+    static_rfor<0, BITS>([&](auto b) { v = pair_sum<(1 << decltype(b)::value)>(v); });
+    return v;
+}
+
+__device__ __forceinline__ double jump_u(unsigned w3) { return ((double)w3 + 0.5) * 0x1p-32; }
+
+template <int N>
+__device__ __forceinline__ double shot_value(const double* __restrict__ diag, double off, double co, int out) {
+#pragma clang fp contract(off)              // a product and a sum, each rounded: a shot's value is the same number on any host
+    return diag ? diag[out] : off + co * (double)(N - 2 * (int)__popc((unsigned)out));
+}
+
+// The read-out's arguments from the table, behind the fence of site_pair: with one wave per trajectory the circuit loop leaves no
+// scalar registers for values that are only used behind it, and kernel arguments would be parked in vector lanes meanwhile.
+struct ReadoutArgs { double off, co; const double* diag; unsigned L, pauli; };
+__device__ __forceinline__ ReadoutArgs readout_args(const DevTable* __restrict__ tab) {
+    int fence = 0;
+    asm volatile("" : "+s"(fence));
+    const DevTable* t = reinterpret_cast<const DevTable*>(reinterpret_cast<const char*>(tab) + fence);
+    return {t->off, t->co, t->diag, t->L, t->pauli};
+}
+
+// ---- n = 2..6: one amplitude per lane ----------------------------------------------------------------------------------------------
+
+// dephasing and damping of one site on wire q; c, w3: the site's code and jump word, (g, s) = (gamma, sqrt(1 - gamma))
+template <int N>
+__device__ __forceinline__ void relax_lane(double& re, double& im, double& nrm2, int x, int& z, int q, unsigned c, unsigned w3,
+                                           double2 gs, int k, int lane) {
+    const double g = gs.x, s = gs.y;
+    z ^= (int)((c >> 4) & 1u) << q;
+    if (g > 0.0) {                                                       // wave-uniform: a table entry
+        const bool one = ((k ^ x) >> q) & 1;                             // this amplitude has the wire in |1>
+        const double M = group_sum<N>(one ? re * re + im * im : 0.0);
+        const bool fire = jump_u(w3) * nrm2 < g * M;
+        if (__any(fire)) {
+            const double pr = __shfl(re, lane ^ (1 << q)), pi = __shfl(im, lane ^ (1 << q));
+            if (fire) { re = one ? 0.0 : pr; im = one ? 0.0 : pi; nrm2 = M; }
+        }
+        if (!fire) {
+            const double f = one ? s : 1.0;
+            re *= f; im *= f;
+            nrm2 -= g * M;
+        }
+    }
+}
+
+__device__ __forceinline__ void rescale_lane(double& re, double& im, double& nrm2) {
+    if (__any(nrm2 < 0x1p-200)) {
+        const double f = nrm2 < 0x1p-200 ? 0x1p100 : 1.0;
+        re *= f; im *= f; nrm2 *= f * f;
+    }
+}
+
+template <int N>
+__global__ __launch_bounds__(64 * kJumpWaves) void device_traj_lane_kernel(NoiseArgs a, const DevTable* __restrict__ tab,
+                                                                           const double* __restrict__ hd) {
+    constexpr int D = 1 << N, SL = 64 / D;
+    const int lane = threadIdx.x & 63;
+    const long item = (long)blockIdx.x * kJumpWaves + (threadIdx.x >> 6);
+    if (item >= a.B * a.tiles) return;                                   // whole waves
+    const long r = item / a.tiles;
+    const long t0 = (item - r * a.tiles) * (long)kTile;
+    const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
+    const int k = lane & (D - 1), base = lane - k, slot = lane / D;
+    const unsigned long long row = (unsigned long long)(a.row0 + r);
+    const double2* csr = a.cs + r * a.E;
+    const double hk = a.shots ? 0.0 : hd[k];
+    const double off_term = (a.shots || a.diag) ? 0.0 : a.off;
+
+    double sum = 0.0, sq = 0.0;
+    for (int it = 0; it < tcount; it += SL) {
+        const int tj = it + slot;
+        const unsigned traj = (unsigned)(t0 + tj);
+        double re = k == 0 ? 1.0 : 0.0, im = 0.0, nrm2 = 1.0;
+        unsigned call = 0, code, w3;
+        int s = 0, col = 0;
+        for (int g = 0; g < 2; ++g) {
+            for (int b = 0; b < a.nb[g]; ++b) {
+                // per wire: encoding RX, then site ENC (Pauli, dephasing, jump)
+                site_draws<false>(a, tab, call, 0, N, k, traj, row, code, w3);
+                int x = 0, z = 0;
+#pragma unroll
+                for (int q = 0; q < N; ++q) {
+                    const double2 c = csr[col + q];
+                    const double pr = __shfl(re, lane ^ (1 << q)), pi = __shfl(im, lane ^ (1 << q));
+                    const double nr = c.x * re + c.y * pi, ni = c.x * im - c.y * pr;
+                    re = nr; im = ni;
+                    const unsigned cq = __shfl(code, base + q);
+                    x ^= pauli_x(cq & 3u, q); z ^= pauli_z(cq & 3u, q);
+                    relax_lane<N>(re, im, nrm2, x, z, q, cq, __shfl(w3, base + q), site_pair(tab, kEnc, q), k, lane);
+                }
+                apply_frame(re, im, x, z, k, base);
+                rescale_lane(re, im, nrm2);
+                col += N; call += N;
+                for (int l = 0; l < a.ld[g]; ++l, ++s) {
+                    site_draws<false>(a, tab, call, N, N, k, traj, row, code, w3);
+                    x = 0; z = 0;
+#pragma unroll
+                    for (int q = 0; q < N; ++q) {                        // fused RY RZ RY per wire, then site ROT
+                        const double4 v = a.gates[2 * (s * N + q + N) + ((k >> q) & 1)];
+                        const double pr = __shfl(re, lane ^ (1 << q)), pi = __shfl(im, lane ^ (1 << q));
+                        const double nr = v.x * re - v.y * im + v.z * pr - v.w * pi;
+                        const double ni = v.x * im + v.y * re + v.z * pi + v.w * pr;
+                        re = nr; im = ni;
+                        const unsigned cq = __shfl(code, base + q);
+                        x ^= pauli_x(cq & 3u, q); z ^= pauli_z(cq & 3u, q);
+                        relax_lane<N>(re, im, nrm2, x, z, q, cq, __shfl(w3, base + q), site_pair(tab, kRot, q), k,
+                                      lane);
+                    }
+                    call += N;
+                    site_draws<true>(a, tab, call, 2 * N, 2 * N, k, traj, row, code, w3);
+#pragma unroll
+                    for (int j = 0; j < N; ++j) {                        // slot j: CNOT(c -> t), pair Pauli, TGT of t, CTL of c
+                        const int c = (j + 1) % N, t = j;
+                        const double pr = __shfl(re, lane ^ (1 << t)), pi = __shfl(im, lane ^ (1 << t));
+                        const bool on = (k >> c) & 1;
+                        re = on ? pr : re; im = on ? pi : im;
+                        x ^= ((x >> c) & 1) << t;
+                        z ^= ((z >> t) & 1) << c;
+                        const unsigned c0 = __shfl(code, base + 2 * j), c1 = __shfl(code, base + 2 * j + 1);
+                        const unsigned p = c0 & 15u;
+                        x ^= pauli_x(p >> 2, c) | pauli_x(p & 3u, t);
+                        z ^= pauli_z(p >> 2, c) | pauli_z(p & 3u, t);
+                        relax_lane<N>(re, im, nrm2, x, z, t, c0, __shfl(w3, base + 2 * j), site_pair(tab, kTgt, t), k,
+                                      lane);
+                        relax_lane<N>(re, im, nrm2, x, z, c, c1, __shfl(w3, base + 2 * j + 1), site_pair(tab, kCtl, c), k, lane);
+                    }
+                    call += 2 * N;
+                    apply_frame(re, im, x, z, k, base);
+                    rescale_lane(re, im, nrm2);
+                }
+            }
+        }
+        // the lane index behind a fence: what the read-out derives from it (bit masks, shot-mode selects) is computed here, per
+        // trajectory, and not kept in scalar registers across the circuit loop
+        int rl = lane;
+        asm volatile("" : "+v"(rl));
+        const int rk = rl & (D - 1), rbase = rl - rk;
+        // noiseless basis change of the X / Y read-outs: H, or H S^dagger, on every wire
+        if (a.pauli != QHEA_PAULI_Z) {
+#pragma unroll
+            for (int q = 0; q < N; ++q) {
+                const int bit = (rk >> q) & 1;
+                if (a.pauli == QHEA_PAULI_Y && bit) { const double t = re; re = im; im = -t; }
+                const double pr = __shfl(re, rl ^ (1 << q)), pi = __shfl(im, rl ^ (1 << q));
+                re = M_SQRT1_2 * (bit ? pr - re : re + pr);
+                im = M_SQRT1_2 * (bit ? pi - im : im + pi);
+            }
+        }
+        const double pk = re * re + im * im;
+        const double tot = group_sum<N>(pk);
+        double v;
+        if (!a.shots) {
+            v = group_sum<N>(pk * hk) / tot + off_term;
+        } else {
+            // one measured bitstring: u against the cdf in index order, then the n readout flips of its own bits
+            const uint4 w0 = philox(make_uint4(a.L, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
+            const uint4 w1 = philox(make_uint4(a.L + 1, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
+            const double u = ((double)(w0.x >> 5) * 67108864.0 + (double)(w0.y >> 6)) * 0x1p-53;
+            const double ut = u * tot;
+            double acc = 0.0;
+            int out = -1, last = 0;
+            for (int j = 0; j < D; ++j) {
+                const double pj = __shfl(pk, rbase + j);
+                acc += pj;
+                if (out < 0 && ut < acc) out = j;
+                if (pj > 0.0) last = j;
+            }
+            if (out < 0) out = last;
+            const unsigned rw[6] = {w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+            int flips = 0;
+#pragma unroll
+            for (int i = 0; i < N; ++i)
+                flips |= (unsigned long long)rw[i] < tab->rthr[i][(out >> i) & 1] ? 1 << i : 0;
+            v = shot_value<N>(a.diag, a.off, a.co, out ^ flips);
+        }
+        if (tj < tcount) { sum += v; sq += v * v; }
+    }
+    double S = 0.0, Q = 0.0;
+#pragma unroll
+    for (int j = 0; j < SL; ++j) { S += __shfl(sum, j * D); Q += __shfl(sq, j * D); }
+    if (lane == 0) a.partial[item] = make_double2(S, Q);
+}
+
+// ---- n = 7..9: one wave, 2^(n-6) amplitudes per lane ---------------------------------------------------------------------------------
+
+// dephasing and damping of one site on wire Q; x, z, c, w3 wave-uniform
+template <int N, int Q>
+__device__ __forceinline__ void relax_regs(double (&re)[Cfg<N>::R], double (&im)[Cfg<N>::R], double& nrm2, int x, int& z, unsigned c,
+                                           unsigned w3, double2 gs, int lane) {
+    using C = Cfg<N>;
+    const double g = gs.x, s = gs.y;
+    constexpr int R = C::R;
+    z ^= (int)((c >> 4) & 1u) << Q;
+    if (g > 0.0) {
+        const int xq = (x >> Q) & 1;
+        bool one[R];
+        double M = 0.0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            one[r] = ((Q < C::LB ? (lane >> Q) : (r >> (Q >= C::LB ? Q - C::LB : 0))) & 1) != xq;
+            M += one[r] ? re[r] * re[r] + im[r] * im[r] : 0.0;
+        }
+        M = group_sum<6>(M);
+        const bool fire = jump_u(w3) * nrm2 < g * M;                     // the same in every lane
+        if (__any(fire)) {
+            if constexpr (Q < C::LB) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double pr = xchg<(1 << Q)>(re[r]), pi = xchg<(1 << Q)>(im[r]);
+                    re[r] = one[r] ? 0.0 : pr; im[r] = one[r] ? 0.0 : pi;
+                }
+            } else {
+                constexpr int J = 1 << (Q - C::LB);
+#pragma unroll
+                for (int r0 = 0; r0 < R; ++r0) {
+                    if (r0 & J) continue;
+                    const int r1 = r0 | J;
+                    const double lr = xq ? 0.0 : re[r1], li = xq ? 0.0 : im[r1];
+                    const double hr = xq ? re[r0] : 0.0, hi = xq ? im[r0] : 0.0;
+                    re[r0] = lr; im[r0] = li; re[r1] = hr; im[r1] = hi;
+                }
+            }
+            nrm2 = M;
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double f = one[r] ? s : 1.0;
+                re[r] *= f; im[r] *= f;
+            }
+            nrm2 -= g * M;
+        }
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void rescale_regs(double (&re)[Cfg<N>::R], double (&im)[Cfg<N>::R], double& nrm2) {
+    if (__any(nrm2 < 0x1p-200)) {
+#pragma unroll
+        for (int r = 0; r < Cfg<N>::R; ++r) { re[r] *= 0x1p100; im[r] *= 0x1p100; }
+        nrm2 *= 0x1p200;
+    }
+}
+
+__device__ __forceinline__ unsigned lane_word(unsigned v, int l) { return (unsigned)__builtin_amdgcn_readlane((int)v, l); }
+
+template <int N>
+__global__ __launch_bounds__(64 * kJumpWaves) void device_traj_wave_kernel(NoiseArgs a, const DevTable* __restrict__ tab,
+                                                                           const double* __restrict__ hd) {
+    using C = Cfg<N>;
+    constexpr int R = C::R;
+    const int lane = threadIdx.x & 63;
+    const long item = (long)blockIdx.x * kJumpWaves + (threadIdx.x >> 6);
+    if (item >= a.B * a.tiles) return;                                   // whole waves
+    const long r = item / a.tiles;
+    const long t0 = (item - r * a.tiles) * (long)kTile;
+    const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
+    const unsigned long long row = (unsigned long long)(a.row0 + r);
+    const double2* csr = a.cs + r * a.E;
+
+    double hk[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) hk[i] = a.shots ? 0.0 : hd[lane | (i << 6)];
+    const double off_term = (a.shots || a.diag) ? 0.0 : a.off;
+
+    double sum = 0.0, sq = 0.0;
+    for (int tj = 0; tj < tcount; ++tj) {
+        const unsigned traj = (unsigned)(t0 + tj);
+        double re[R], im[R], nrm2 = 1.0;
+#pragma unroll
+        for (int i = 0; i < R; ++i) { re[i] = 0.0; im[i] = 0.0; }
+        re[0] = lane == 0 ? 1.0 : 0.0;
+        unsigned call = 0, code, w3;
+        int s = 0, col = 0;
+        for (int g = 0; g < 2; ++g) {
+            for (int b = 0; b < a.nb[g]; ++b) {
+                site_draws<false>(a, tab, call, 0, N, lane, traj, row, code, w3);
+                int x = 0, z = 0;
+                static_for<0, N>([&](auto q) {                           // encoding RX, then site ENC
+                    constexpr int Q = decltype(q)::value;
+                    const double2 c = csr[col + Q];
+                    apply_rx<N, Q>(re, im, c.x, c.y);
+                    const unsigned cq = lane_word(code, Q);
+                    x ^= pauli_x(cq & 3u, Q); z ^= pauli_z(cq & 3u, Q);
+                    relax_regs<N, Q>(re, im, nrm2, x, z, cq, lane_word(w3, Q), site_pair(tab, kEnc, Q), lane);
+                });
+                frame_regs<N>(re, im, x, z, lane);
+                rescale_regs<N>(re, im, nrm2);
+                col += N; call += N;
+                for (int l = 0; l < a.ld[g]; ++l, ++s) {
+                    site_draws<false>(a, tab, call, N, N, lane, traj, row, code, w3);
+                    x = 0; z = 0;
+                    static_for<0, N>([&](auto q) {                       // fused RY RZ RY, then site ROT
+                        constexpr int Q = decltype(q)::value;
+                        constexpr bool kSigned = Q < C::LB && !kSwapQubit<N, Q>;   // the lane's variant of the gate table
+                        const double4 v = a.gates[2 * (s * N + Q + N) + (kSigned ? (lane >> Q) & 1 : 0)];
+                        apply_su2<N, Q>(re, im, v.x, v.y, v.z, v.w);
+                        const unsigned cq = lane_word(code, Q);
+                        x ^= pauli_x(cq & 3u, Q); z ^= pauli_z(cq & 3u, Q);
+                        relax_regs<N, Q>(re, im, nrm2, x, z, cq, lane_word(w3, Q), site_pair(tab, kRot, Q), lane);
+                    });
+                    call += N;
+                    site_draws<true>(a, tab, call, 2 * N, 2 * N, lane, traj, row, code, w3);
+                    static_for<0, N>([&](auto jj) {                      // slot j: CNOT(c -> t), pair Pauli, TGT of t, CTL of c
+                        constexpr int J = decltype(jj)::value, CQ = (J + 1) % N, TQ = J;
+                        apply_cnot<N, CQ, TQ>(re, im, lane);
+                        x ^= ((x >> CQ) & 1) << TQ;
+                        z ^= ((z >> TQ) & 1) << CQ;
+                        const unsigned c0 = lane_word(code, 2 * J), c1 = lane_word(code, 2 * J + 1);
+                        const unsigned p = c0 & 15u;
+                        x ^= pauli_x(p >> 2, CQ) | pauli_x(p & 3u, TQ);
+                        z ^= pauli_z(p >> 2, CQ) | pauli_z(p & 3u, TQ);
+                        relax_regs<N, TQ>(re, im, nrm2, x, z, c0, lane_word(w3, 2 * J), site_pair(tab, kTgt, TQ),
+                                          lane);
+                        relax_regs<N, CQ>(re, im, nrm2, x, z, c1, lane_word(w3, 2 * J + 1), site_pair(tab, kCtl, CQ), lane);
+                    });
+                    call += 2 * N;
+                    frame_regs<N>(re, im, x, z, lane);
+                    rescale_regs<N>(re, im, nrm2);
+                }
+            }
+        }
+        int rl = lane;                                                   // behind a fence, as in the lane kernel's read-out
+        asm volatile("" : "+v"(rl));
+        const ReadoutArgs ro = readout_args(tab);
+        basis_change<N, false>(re, im, (int)ro.pauli, rl);               // same probabilities as H / H S^dagger
+        double pk[R], tot = 0.0;
+#pragma unroll
+        for (int i = 0; i < R; ++i) { pk[i] = re[i] * re[i] + im[i] * im[i]; tot += pk[i]; }
+        tot = group_sum<6>(tot);
+        double v;
+        if (!a.shots) {
+            v = 0.0;
+#pragma unroll
+            for (int i = 0; i < R; ++i) v += pk[i] * hk[i];
+            v = group_sum<6>(v) / tot + off_term;
+        } else {
+            // calls L .. L + 2: u, then per bit the flip words against both thresholds (the outcome picks the direction)
+            const int j = rl & 3;
+            const uint4 w = philox(make_uint4(ro.L + (unsigned)j, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
+            const unsigned wd[4] = {w.x, w.y, w.z, w.w};
+            int m01 = 0, m10 = 0;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const int i = 4 * j + h - 2;
+                if (i >= 0 && i < N) {
+                    if ((unsigned long long)wd[h] < tab->rthr[i][0]) m01 |= 1 << i;
+                    if ((unsigned long long)wd[h] < tab->rthr[i][1]) m10 |= 1 << i;
+                }
+            }
+            m01 = uniform(__shfl(m01, 0) | __shfl(m01, 1) | __shfl(m01, 2) | __shfl(m01, 3));
+            m10 = uniform(__shfl(m10, 0) | __shfl(m10, 1) | __shfl(m10, 2) | __shfl(m10, 3));
+            const double ut = __shfl(((double)(w.x >> 5) * 67108864.0 + (double)(w.y >> 6)) * 0x1p-53, 0) * tot;
+            int out = -1, last = 0;
+            double below = 0.0;                                          // cdf of the blocks of 64 before this one
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const double c = wave_scan(pk[i], rl);
+                const unsigned long long hit = __ballot(ut < below + c), pos = __ballot(pk[i] > 0.0);
+                if (out < 0 && hit) out = (i << 6) | (__ffsll(hit) - 1);
+                if (pos) last = (i << 6) | (63 - __clzll(pos));
+                below += __shfl(c, 63);
+            }
+            if (out < 0) out = last;
+            v = shot_value<N>(ro.diag, ro.off, ro.co, out ^ ((out & m10) | (~out & m01)));
+        }
+        sum += v; sq += v * v;
+    }
+    if (lane == 0) a.partial[item] = make_double2(sum, sq);
+}
+
+// ---- prep: the table, and expectation mode's read-out weights -------------------------------------------------------------------------
+
+// One workgroup.  Copies the table into the workspace and, with `buf`, builds h[k] of expectation mode in half (n - 1) & 1 of
+// buf[2 * 2^n]: co sum_i (bit_i(k) ? -(1 - 2 r10_i) : 1 - 2 r01_i) in the order i = 0..n-1, or ham_diag under the readout
+// confusion, bit by bit: stage i writes half i & 1, h'[k] = (1 - e) h[k] + e h[k ^ 2^i] with e = r01_i where bit i of k is 0 and
+// r10_i where it is 1.
+__global__ __launch_bounds__(256) void device_tables_kernel(DevTable t, DevTable* __restrict__ out, const double* __restrict__ diag,
+                                                            double co, int n, double* __restrict__ buf) {
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&t);
+    if ((int)threadIdx.x < kTableWords) reinterpret_cast<unsigned long long*>(out)[threadIdx.x] = src[threadIdx.x];
+    if (!buf) return;
+    const int D = 1 << n;
+    if (!diag) {
+        double* dst = buf + (size_t)((n - 1) & 1) * D;
+        for (int k = threadIdx.x; k < D; k += 256) {
+            double h = 0.0;
+            for (int i = 0; i < n; ++i) h += (k >> i) & 1 ? -(1.0 - 2.0 * t.rd[i][1]) : 1.0 - 2.0 * t.rd[i][0];
+            dst[k] = co * h;
+        }
+        return;
+    }
+    const double* from = diag;
+    for (int i = 0; i < n; ++i) {
+        double* dst = buf + (size_t)(i & 1) * D;
+        for (int k = threadIdx.x; k < D; k += 256) {
+            const double e = (k >> i) & 1 ? t.rd[i][1] : t.rd[i][0];
+            dst[k] = (1.0 - e) * from[k] + e * from[k ^ (1 << i)];
+        }
+        __syncthreads();
+        from = dst;
+    }
+}
+
+int launch_device_traj(const NoiseArgs& a, int n, const DevTable* tab, const double* hd, hipStream_t st) {
+    const long items = a.B * a.tiles;
+    const dim3 grid((unsigned)((items + kJumpWaves - 1) / kJumpWaves)), block(64 * kJumpWaves);
+    switch (n) {
+        case 2: hipLaunchKernelGGL(device_traj_lane_kernel<2>, grid, block, 0, st, a, tab, hd); break;
+        case 3: hipLaunchKernelGGL(device_traj_lane_kernel<3>, grid, block, 0, st, a, tab, hd); break;
+        case 4: hipLaunchKernelGGL(device_traj_lane_kernel<4>, grid, block, 0, st, a, tab, hd); break;
+        case 5: hipLaunchKernelGGL(device_traj_lane_kernel<5>, grid, block, 0, st, a, tab, hd); break;
+        case 6: hipLaunchKernelGGL(device_traj_lane_kernel<6>, grid, block, 0, st, a, tab, hd); break;
+        case 7: hipLaunchKernelGGL(device_traj_wave_kernel<7>, grid, block, 0, st, a, tab, hd); break;
+        case 8: hipLaunchKernelGGL(device_traj_wave_kernel<8>, grid, block, 0, st, a, tab, hd); break;
+        case 9: hipLaunchKernelGGL(device_traj_wave_kernel<9>, grid, block, 0, st, a, tab, hd); break;
+        default: return QHEA_EUNSUPPORTED;
+    }
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
+// the uniform units' layout with the read-out region of the wide ones, then the table
+constexpr TrajUnit kJumpUnit{QHEA_MIN_QUBITS, kJumpMaxWires, true, nullptr};
+struct JumpLayout { TrajLayout t; size_t off_tab, total; };
+inline JumpLayout jump_layout(const ModelInfo& mi, int64_t B, int64_t T) {
+    JumpLayout L{};
+    L.t = traj_layout(kJumpUnit, mi, B, T);
+    L.off_tab = L.t.total;
+    L.total = align256(L.off_tab + sizeof(DevTable));
+    return L;
+}
+
+inline qhea_noise sampling_as_noise(const qhea_sampling* s) {
+    qhea_noise nz{};
+    nz.shots = s->shots; nz.trajectories = s->trajectories; nz.seed = s->seed;
+    return nz;
+}
+
+void fill_table(int n, const qhea_device_noise* dn, DevTable& t, bool& any) {
+    double flat[4 * kJumpMaxWires * 2];                                  // [4][n][2]
+    jump_tables(n, dn, flat);
+    auto jump = [&](int site, int q, int k) { return flat[((size_t)site * n + q) * 2 + k]; };
+    any = false;
+    for (int q = 0; q < n; ++q) {
+        t.cthr[q][0] = threshold(dn->p1[q]);         t.cthr[q][1] = threshold(jump(kEnc, q, 1));
+        t.cthr[n + q][0] = threshold(dn->p1[q]);     t.cthr[n + q][1] = threshold(jump(kRot, q, 1));
+        t.cthr[2 * n + 2 * q][0] = threshold(dn->p2[q]);                 // slot q: the pair, and TGT of wire q
+        t.cthr[2 * n + 2 * q][1] = threshold(jump(kTgt, q, 1));
+        t.cthr[2 * n + 2 * q + 1][0] = 0;                                // ... CTL of wire (q + 1) mod n
+        t.cthr[2 * n + 2 * q + 1][1] = threshold(jump(kCtl, (q + 1) % n, 1));
+        for (int site = 0; site < 4; ++site) {
+            t.gs[site][q][0] = jump(site, q, 0);
+            t.gs[site][q][1] = sqrt(1.0 - jump(site, q, 0));
+            any = any || jump(site, q, 0) > 0.0;
+        }
+        t.rthr[q][0] = threshold(dn->readout01[q]); t.rthr[q][1] = threshold(dn->readout10[q]);
+        t.rd[q][0] = dn->readout01[q]; t.rd[q][1] = dn->readout10[q];
+    }
+    for (int c = 0; c < 4 * n; ++c) any = any || t.cthr[c][0] || t.cthr[c][1];
+}
+
+}  // namespace
+}  // namespace qhea
+
+using namespace qhea;
+
+extern "C" {
+
+int qhea_device_noise_jump_tables(int n, const qhea_device_noise* dn, double* jump) {
+    const int rc = device_noise_check(n, dn);
+    if (rc != QHEA_OK) return rc;
+    if (!jump) return QHEA_EINVAL;
+    jump_tables(n, dn, jump);
+    return QHEA_OK;
+}
+
+size_t qhea_model_noisy_device_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling) {
+    ModelInfo mi;
+    if (!sampling || batch < 0 || model_info(desc, mi) != QHEA_OK || mi.n > kJumpMaxWires) return 0;
+    const qhea_noise nz = sampling_as_noise(sampling);
+    const int64_t T = noise_values(&nz);
+    if (T < 1) return 0;
+    return jump_layout(mi, batch, T).total;
+}
+
+int qhea_model_forward_noisy_device(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
+                                    const double* trunk, const double* params, const double* ham_diag,
+                                    const qhea_device_noise* dn, const qhea_sampling* sampling, double* pred, double* stderr_out,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    // the device setting is checked against the model's n before the shared checks, which read the model themselves: the first
+    // reading goes into a record of its own (model_info appends to the record's block list)
+    ModelInfo probe;
+    int rc = model_info(desc, probe);
+    if (rc != QHEA_OK) return rc;
+    rc = device_noise_check(probe.n, dn);
+    if (rc != QHEA_OK) return rc;
+    if (!sampling) return QHEA_EINVAL;
+    const qhea_noise nz = sampling_as_noise(sampling);
+    NoisyCall c;
+    rc = noisy_call_check({QHEA_MIN_QUBITS, kJumpMaxWires, true, false}, desc, ham_diag, &nz, row0, batch, trunk,
+                          {branch, params, pred}, workspace, stream, c);
+    if (rc != QHEA_OK || c.empty) return rc;
+    const JumpLayout L = jump_layout(c.mi, batch, c.T);
+    if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
+    if ((int64_t)batch * L.t.tiles > (int64_t)INT_MAX) return QHEA_EINVAL;
+    const int n = c.mi.n;
+    double4* gates = reinterpret_cast<double4*>(c.ws + L.t.off_gates);
+    double2* cs = reinterpret_cast<double2*>(c.ws + L.t.off_cs);
+    double2* part = reinterpret_cast<double2*>(c.ws + L.t.off_part);
+    double* mix = reinterpret_cast<double*>(c.ws + L.t.off_mix);
+    DevTable* tab = reinterpret_cast<DevTable*>(c.ws + L.off_tab);
+    rc = launch_prep_model(desc, c.mi, batch, branch, trunk, params, gates, cs, c.ws, c.st);
+    if (rc != QHEA_OK) return rc;
+
+    NoiseArgs a = noise_args(desc, c.mi, &nz, params, ham_diag, row0, batch, c.T);
+    a.gates = gates; a.cs = cs; a.partial = part;
+    unsigned calls = 0;                                                  // C of the header: n + 3 n ld per block
+    for (int g = 0; g < 2; ++g) calls += (unsigned)c.mi.nb[g] * (unsigned)(n + 3 * n * c.mi.ld[g]);
+    a.L = calls;                                                         // shot mode continues from call C
+    DevTable t{};
+    bool any;
+    fill_table(n, dn, t, any);
+    t.off = a.off; t.co = a.co; t.diag = ham_diag; t.L = a.L; t.pauli = (unsigned)a.pauli;
+    a.thr1 = any ? 1 : 0;                                                // an ideal setting draws nothing
+    const bool expect = !a.shots;
+    hipLaunchKernelGGL(device_tables_kernel, dim3(1), dim3(256), 0, c.st, t, tab, ham_diag, a.co, n,
+                       expect ? mix : static_cast<double*>(nullptr));
+    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    const double* hd = expect ? mix + ((size_t)((n - 1) & 1) << n) : nullptr;
+    rc = launch_device_traj(a, n, tab, hd, c.st);
+    if (rc != QHEA_OK) return rc;
+    return launch_noisy_finish(part, L.t.tiles, batch, c.T, a.bias, pred, stderr_out, c.st);
+}
+
+}  // extern "C"

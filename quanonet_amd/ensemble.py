@@ -218,12 +218,13 @@ class EnsembleSolver:
         histories = histories if histories is not None else [None] * len(self.members)
         return [m.evaluate(h) for m, h in zip(self.members, histories)]
 
-    def evaluate_noisy(self, noise, out_name=None, exact=False):
+    def evaluate_noisy(self, noise, out_name=None, exact=False, sampling=None):
         """PTSolver.evaluate_noisy for every member (its best checkpoint; out_dir/out_name when given, never metric.json); returns
         the list of results.  Every member uses noise.seed, so the members see common random numbers: member differences are
         not blurred by independent noise draws.  exact=True: every member's exact expectation instead (no draws at all); a
-        quanonet_amd.noise.DeviceNoise is evaluated that way only (ValueError with exact=False)."""
-        return [m.evaluate_noisy(noise, out_name, exact=exact) for m in self.members]
+        quanonet_amd.noise.DeviceNoise is evaluated that way, or sampled with sampling= (one Sampling, so one seed, for every
+        member: common random numbers again); ValueError with neither."""
+        return [m.evaluate_noisy(noise, out_name, exact=exact, sampling=sampling) for m in self.members]
 
 
 class PerMemberSolver(EnsembleSolver):

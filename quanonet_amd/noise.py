@@ -55,6 +55,37 @@ class NoiseModel:
         return dataclasses.asdict(self)
 
 
+@dataclass(frozen=True)
+class Sampling:
+    """
+    The estimator of device_noisy_predict (qhea_sampling): shots = 0 is expectation mode, the mean over `trajectories`
+    quantum-jump runs of their exact read-outs (readout error folded in); shots = S >= 1 draws S bitstrings per row, what an
+    Estimator with default_shots = S estimates.  seed: key of the counter-based random streams; a row's draws depend on
+    (seed, global row index, trajectory) only.
+    """
+    shots: int = 0
+    trajectories: int = 1
+    seed: int = 0
+
+    def __post_init__(self):
+        for name in ('shots', 'trajectories', 'seed'):
+            if not isinstance(getattr(self, name), int) or isinstance(getattr(self, name), bool):
+                raise ValueError(f"Sampling.{name} must be an int (got {getattr(self, name)!r})")
+        if self.shots < 0:
+            raise ValueError(f"Sampling.shots must be >= 0 (got {self.shots})")
+        if self.shots == 0 and self.trajectories < 1:
+            raise ValueError(f"Sampling.trajectories must be >= 1 in expectation mode (got {self.trajectories})")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"Sampling.seed must fit in 64 unsigned bits (got {self.seed})")
+
+    def params(self):
+        """The C ABI's qhea_sampling."""
+        return _lib.SamplingParams(int(self.shots), int(self.trajectories), int(self.seed))
+
+    def asdict(self):
+        return dataclasses.asdict(self)
+
+
 _PER_WIRE = ('p1', 'p2', 'readout01', 'readout10', 't1', 't2')
 _DURATIONS = ('t_rx', 't_rot', 't_cx')
 
@@ -67,7 +98,8 @@ def _number(v):
 class DeviceNoise:
     """
     The calibrated device noise model of qhea_device_noise (include/quanonet_hea.h), for the exact evaluation
-    (exact_noisy_predict, evaluate_noisy(exact=True)); n <= 6.
+    (exact_noisy_predict, evaluate_noisy(exact=True)); n <= 6, and for quantum-jump trajectories (device_noisy_predict,
+    evaluate_noisy(sampling=...)); n <= 9.
     p1[q]: depolarizing probability after every single-qubit gate on wire q; p2[j]: two-qubit depolarizing probability after
     the CNOT of ring slot j (control (j+1) mod n -> target j); readout01[q] / readout10[q]: probability that bit q reads 1
     given 0 / 0 given 1; t1[q], t2[q]: relaxation times of wire q (math.inf: no decay; t2 <= 2 t1).  Each of the six is one
@@ -147,6 +179,12 @@ class DeviceNoise:
         TGT) and wire, with the idle decay folded in, and 16 p2[j] / 15 per CNOT slot.  No device needed."""
         return _lib.device_noise_tables(n, self.params(n))
 
+    def jump_tables(self, n):
+        """jump [4, n, 2] of qhea_device_noise_jump_tables: (gamma, pz) of the relaxation of every channel site (ENC, ROT, CTL,
+        TGT) and wire at its folded duration -- damping probability and dephasing probability of the trajectory unravelling.
+        No device needed."""
+        return _lib.device_noise_jump_tables(n, self.params(n))
+
     def asdict(self):
         """JSON-serialisable (json.dumps(..., allow_nan=False) accepts it): per-wire sequences as lists, an infinite t1 / t2
         as the string 'Infinity' -- what float() reads back, so DeviceNoise.fromdict(json.loads(...)) restores the setting."""
@@ -224,12 +262,14 @@ class DeviceNoise:
 
 def _uniform_only(noise, who, why):
     if isinstance(noise, DeviceNoise):
-        raise ValueError(f"{who} takes a NoiseModel, not a DeviceNoise: {why}; exact_noisy_predict and "
-                         "evaluate_noisy(exact=True) evaluate a DeviceNoise, device_noisy_loss_and_grad, device_amplification "
-                         "and the config key train_device_noise differentiate and train under one")
+        raise ValueError(f"{who} takes a NoiseModel, not a DeviceNoise: {why}; device_noisy_predict and "
+                         "evaluate_noisy(noise, sampling=Sampling(...)) sample a DeviceNoise by quantum-jump trajectories, "
+                         "exact_noisy_predict and evaluate_noisy(exact=True) evaluate one exactly, device_noisy_loss_and_grad, "
+                         "device_amplification and the config key train_device_noise differentiate and train under one")
 
 
-_TRAJECTORY_WHY = "the trajectory kernels sample Pauli errors only and relaxation is not a Pauli channel"
+_TRAJECTORY_WHY = ("this call's trajectory kernels sample Pauli errors only and relaxation is not a Pauli channel: a DeviceNoise "
+                   "goes to device_noisy_predict, or to evaluate_noisy with the sampling= argument")
 _GRADIENT_WHY = "this call's reverse walk inverts the uniform depolarizing channels only"
 
 
@@ -277,6 +317,32 @@ def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
         e = min(N, s + chunk)
         forward(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, row0=int(row0) + s, ham_diag=ham_diag,
                 out=pred[s:e], stderr=stderr[s:e])
+    return pred.unsqueeze(-1), stderr
+
+
+def device_noisy_predict(model, inputs, noise, sampling, chunk_rows=16384, row0=0):
+    """
+    noisy_predict under a DeviceNoise (qhea_model_forward_noisy_device): (pred [N, 1], stderr [N]) from quantum-jump trajectories
+    -- sampled Paulis for the gate errors, dephasing and norm-dependent damping jumps for T1 / T2 with the ring's idle decay,
+    the asymmetric readout -- with the estimator `sampling` (a Sampling: expectation mode or shots, and the seed).  Unbiased for
+    exact_noisy_predict(model, inputs, noise); n = 2..9.  Rows go in chunks of `chunk_rows`; chunk i passes its global index
+    row0 + i * chunk_rows, so the result is bitwise the same for any chunking.
+    """
+    if not isinstance(noise, DeviceNoise):
+        raise ValueError(f"device_noisy_predict takes a DeviceNoise (got {type(noise).__name__}); a NoiseModel goes to "
+                         "noisy_predict, or through DeviceNoise.uniform")
+    if not isinstance(sampling, Sampling):
+        raise ValueError(f"device_noisy_predict takes a Sampling (got {type(sampling).__name__})")
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'device_noisy_predict')
+    N = branch.shape[0]
+    pred = torch.empty(N, dtype=torch.float64, device=branch.device)
+    stderr = torch.empty(N, dtype=torch.float64, device=branch.device)
+    chunk = max(1, int(chunk_rows))
+    nz, sp = noise.params(desc.n_qubits), sampling.params()
+    for s in range(0, N, chunk):
+        e = min(N, s + chunk)
+        _lib.model_forward_noisy_device(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, sp,
+                                        row0=int(row0) + s, ham_diag=ham_diag, out=pred[s:e], stderr=stderr[s:e])
     return pred.unsqueeze(-1), stderr
 
 

@@ -967,7 +967,7 @@ class PTSolver:
         self.log(f"Test Relative L2 Error: {metrics['rel_l2']:.6f}")
         return metrics
 
-    def evaluate_noisy(self, noise, out_name=None, exact=False):
+    def evaluate_noisy(self, noise, out_name=None, exact=False, sampling=None):
         """
         The test set of `evaluate` predicted under `noise` (a quanonet_amd.noise.NoiseModel) from the best checkpoint:
         regression_metrics plus 'mean_stderr' (the rows' mean standard error) and 'noise' (the settings).  Writes
@@ -975,21 +975,32 @@ class PTSolver:
         exact=True: the metrics of the exact expectation under the noise channels (exact_noisy_predict; no sampling error,
         noise.shots / trajectories / seed ignored), with 'exact': True and 'mean_shot_std' (the rows' mean one-shot standard
         deviation) in place of 'mean_stderr'.  A quanonet_amd.noise.DeviceNoise (per-wire rates, T1 / T2, the ring's idle
-        decay) is evaluated with exact=True only.
+        decay) is evaluated with exact=True, or sampled with sampling= (a quanonet_amd.noise.Sampling: quantum-jump trajectories,
+        device_noisy_predict; 'mean_stderr', and 'sampling' beside 'noise').  sampling belongs to a DeviceNoise without exact.
         """
-        from .noise import _TRAJECTORY_WHY, _uniform_only, exact_noisy_predict, noisy_predict
+        from .noise import (DeviceNoise, _TRAJECTORY_WHY, _uniform_only, device_noisy_predict, exact_noisy_predict,
+                            noisy_predict)
         if self.world > 1:
             raise RuntimeError("evaluate_noisy runs on one rank (world_size == 1)")
-        if not exact:
+        if sampling is not None and (exact or not isinstance(noise, DeviceNoise)):
+            raise ValueError("evaluate_noisy: sampling= is the estimator of a DeviceNoise's trajectories; exact=True draws "
+                             "nothing and a NoiseModel carries its own shots, trajectories and seed")
+        if not exact and sampling is None:
             _uniform_only(noise, 'evaluate_noisy(exact=False)', _TRAJECTORY_WHY)
         self._load_best()
-        predict = exact_noisy_predict if exact else noisy_predict
-        y_pred, stderr = predict(self.model, self.test_input, noise, chunk_rows=self.config.get('eval_batch_size', 16384))
+        chunk_rows = self.config.get('eval_batch_size', 16384)
+        if sampling is not None:
+            y_pred, stderr = device_noisy_predict(self.model, self.test_input, noise, sampling, chunk_rows=chunk_rows)
+        else:
+            predict = exact_noisy_predict if exact else noisy_predict
+            y_pred, stderr = predict(self.model, self.test_input, noise, chunk_rows=chunk_rows)
         y_true = torch.as_tensor(np.asarray(self.test_output), dtype=torch.float64).to(y_pred.device)
         metrics = regression_metrics(y_pred, y_true)
         spread = 'mean_shot_std' if exact else 'mean_stderr'
         metrics[spread] = float(stderr.mean().item()) if stderr.numel() else 0.0
         metrics['noise'] = noise.asdict()
+        if sampling is not None:
+            metrics['sampling'] = sampling.asdict()
         if exact:
             metrics['exact'] = True
         if out_name:
