@@ -15,6 +15,10 @@
 // (skipped when no slot of the wave drew one).  Philox calls are shared by the lanes of a slot: at each segment (the encoding of
 // a block, or one sub-layer) lane k of the slot computes the segment's call k and turns its four words into the error codes of
 // its two locations; every location then reads its code from that lane.
+//
+// The stream, the frame (apply_frame) and u of the cdf search are hea_noise_traj.hpp's, shared with hea_noise_wide.hip and
+// hea_noise_device.hip.  Where the kernel below still spells out what those units also hold, the shared form changed its device
+// code (profiles/r25_device_code_identity.txt).
 #include <cmath>
 #include <cstdint>
 
@@ -25,23 +29,13 @@ namespace {
 
 constexpr int kNoiseWaves = 4;              // waves per workgroup (independent; no LDS, no barrier)
 
-// psi <- X^x Z^z psi (up to a global phase): psi'[k] = (-1)^popcount((k ^ x) & z) psi[k ^ x]
-__device__ __forceinline__ void apply_frame(double& re, double& im, int x, int z, int k, int base) {
-    if (__any(x | z)) {
-        const int src = k ^ x;
-        const double pr = __shfl(re, base + src), pi = __shfl(im, base + src);
-        const bool neg = __popc(src & z) & 1;
-        re = neg ? -pr : pr;
-        im = neg ? -pi : pi;
-    }
-}
-
 template <int N>
 __global__ __launch_bounds__(64 * kNoiseWaves) void noisy_fwd_kernel(NoiseArgs a) {
     constexpr int D = 1 << N, SL = 64 / D;
     const int lane = threadIdx.x & 63;
     const long item = (long)blockIdx.x * kNoiseWaves + (threadIdx.x >> 6);
     if (item >= a.B * a.tiles) return;                                   // whole waves
+    // (written out, not work_item(): with it this kernel's device code changes)
     const long r = item / a.tiles;
     const long t0 = (item - r * a.tiles) * (long)kTile;
     const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(64 * kNoiseWaves) void noisy_fwd_kernel(NoiseArgs a
             const unsigned cm = (a.L + 1) >> 1;
             const uint4 w0 = philox(make_uint4(cm, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
             const uint4 w1 = philox(make_uint4(cm + 1, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
-            const double u = ((double)(w0.x >> 5) * 67108864.0 + (double)(w0.y >> 6)) * 0x1p-53;
+            const double u = unit_double(w0.x, w0.y);
             double acc = 0.0;
             int out = -1, last = 0;
             for (int j = 0; j < D; ++j) {
@@ -155,6 +149,7 @@ __global__ __launch_bounds__(64 * kNoiseWaves) void noisy_fwd_kernel(NoiseArgs a
             const unsigned rw[6] = {w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
 #pragma unroll
             for (int i = 0; i < N; ++i) out ^= (unsigned long long)rw[i] < a.thrq ? 1 << i : 0;
+            // (written out, not shot_value<N>: this kernel is built without that function's contraction pragma)
             v = a.diag ? a.diag[out] : a.off + a.co * (double)(N - 2 * (int)__popc(out));
         }
         if (tj < tcount) { sum += v; sq += v * v; }
@@ -184,7 +179,7 @@ __global__ __launch_bounds__(256) void noisy_finish_kernel(const double2* __rest
     }
 }
 
-int launch_noisy(const NoiseArgs& a, int n, double*, hipStream_t st) {
+int launch_noisy(const NoiseArgs& a, int n, hipStream_t st) {
     const long items = a.B * a.tiles;
     const dim3 grid((unsigned)((items + kNoiseWaves - 1) / kNoiseWaves)), block(64 * kNoiseWaves);
     switch (n) {
@@ -197,7 +192,7 @@ int launch_noisy(const NoiseArgs& a, int n, double*, hipStream_t st) {
     }
     return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
-constexpr TrajUnit kLaneUnit{QHEA_MIN_QUBITS, 6, false, launch_noisy};      // lane-resident states only
+constexpr TrajUnit kLaneUnit{QHEA_MIN_QUBITS, 6, false, 0};                 // lane-resident states only
 
 }  // namespace
 
@@ -221,8 +216,11 @@ size_t qhea_model_noisy_workspace_bytes(const qhea_model_desc* desc, int64_t bat
 int qhea_model_forward_noisy(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch, const double* trunk,
                              const double* params, const double* ham_diag, const qhea_noise* noise, double* pred,
                              double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return traj_forward(kLaneUnit, desc, row0, batch, branch, trunk, params, ham_diag, noise, pred, stderr_out, workspace,
-                        workspace_bytes, stream);
+    TrajCall t;
+    const int rc = traj_open(kLaneUnit, desc, row0, batch, branch, trunk, params, ham_diag, noise, pred, workspace, workspace_bytes,
+                             stream, t);
+    if (rc != QHEA_OK || t.c.empty) return rc;
+    return traj_finish(t, launch_noisy(t.a, t.c.mi.n, t.c.st), pred, stderr_out);
 }
 
 }  // extern "C"

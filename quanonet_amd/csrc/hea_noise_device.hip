@@ -25,6 +25,12 @@
 // 0..3, dephasing in bit 4) and the jump's word; every site reads the two from that lane.  The per-call thresholds and the
 // per-site (gamma, sqrt(1 - gamma)) come from a small table in the workspace that one prep launch fills from its arguments: the
 // trajectory kernels read it by wave-uniform addresses, so the constants live in scalar registers only while a site uses them.
+//
+// The work item, apply_frame, frame_regs, wave_scan, uniform, u of the cdf search and shot_value are hea_noise_traj.hpp's, shared
+// with the uniform units, and so is the entry point around the table fill (traj_open, traj_finish).  Where a kernel below still
+// spells out what hea_noise.hip or hea_noise_wide.hip also hold (the lane butterflies, the basis change, the cdf searches, the
+// slot fold, the wave kernel's work item and shot words), the shared form changed its device code
+// (profiles/r25_device_code_identity.txt).
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -79,61 +85,7 @@ inline void jump_tables(int n, const qhea_device_noise* dn, double* jump) {
                       jump[((size_t)site * n + q) * 2 + 1]);
 }
 
-// ---- device helpers (the file-local ones of hea_noise.hip / hea_noise_wide.hip, which stay as they are) ---------------------------
-
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// psi <- X^x Z^z psi (up to a global phase): psi'[k] = (-1)^popcount((k ^ x) & z) psi[k ^ x]
-__device__ __forceinline__ void apply_frame(double& re, double& im, int x, int z, int k, int base) {
-    if (__any(x | z)) {
-        const int src = k ^ x;
-        const double pr = __shfl(re, base + src), pi = __shfl(im, base + src);
-        const bool neg = __popc(src & z) & 1;
-        re = neg ? -pr : pr;
-        im = neg ? -pi : pi;
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void frame_regs(double (&re)[Cfg<N>::R], double (&im)[Cfg<N>::R], int x, int z, int lane) {
-    using C = Cfg<N>;
-    if ((x | z) == 0) return;
-    if (x & 63) {
-        const int src = (lane ^ (x & 63)) << 2;
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) { re[r] = lane_gather(re[r], src); im[r] = lane_gather(im[r], src); }
-    }
-    static_for<0, C::RB>([&](auto b) {
-        constexpr int J = 1 << decltype(b)::value;
-        if ((x >> 6) & J) {
-#pragma unroll
-            for (int r = 0; r < C::R; ++r) {
-                if (r & J) continue;
-                double t = re[r]; re[r] = re[r | J]; re[r | J] = t;
-                t = im[r]; im[r] = im[r | J]; im[r | J] = t;
-            }
-        }
-    });
-    if (z) {
-        const int lp = __popc((unsigned)(lane & z & 63));
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) {
-            const bool neg = (lp + __popc((unsigned)(r & (z >> 6)))) & 1;
-            re[r] = neg ? -re[r] : re[r];
-            im[r] = neg ? -im[r] : im[r];
-        }
-    }
-}
-
-// inclusive sum over the lanes 0 .. lane of a wave (Hillis-Steele, distances 1, 2, .. 32: a fixed order)
-__device__ __forceinline__ double wave_scan(double c, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double t = __shfl_up(c, d);
-        if (lane >= d) c += t;
-    }
-    return c;
-}
+// ---- device helpers of this unit ----------------------------------------------------------------------------------------------------
 
 // This lane's call of a segment: call0 + c for c < cnt, template entry tbase + c of the table.  code = the sampled Pauli
 // (0 none; one qubit 1..3; RING, even calls: the pair 1..15) | dephasing << 4; w3 = the jump's word.  a.thr1 == 0: an ideal
@@ -170,12 +122,6 @@ __device__ __forceinline__ double group_sum(double v) {
 }
 
 __device__ __forceinline__ double jump_u(unsigned w3) { return ((double)w3 + 0.5) * 0x1p-32; }
-
-template <int N>
-__device__ __forceinline__ double shot_value(const double* __restrict__ diag, double off, double co, int out) {
-#pragma clang fp contract(off)              // a product and a sum, each rounded: a shot's value is the same number on any host
-    return diag ? diag[out] : off + co * (double)(N - 2 * (int)__popc((unsigned)out));
-}
 
 // The read-out's arguments from the table, behind the fence of site_pair: with one wave per trajectory the circuit loop leaves no
 // scalar registers for values that are only used behind it, and kernel arguments would be parked in vector lanes meanwhile.
@@ -225,30 +171,26 @@ __global__ __launch_bounds__(64 * kJumpWaves) void device_traj_lane_kernel(Noise
     const int lane = threadIdx.x & 63;
     const long item = (long)blockIdx.x * kJumpWaves + (threadIdx.x >> 6);
     if (item >= a.B * a.tiles) return;                                   // whole waves
-    const long r = item / a.tiles;
-    const long t0 = (item - r * a.tiles) * (long)kTile;
-    const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
+    const WorkItem wi = work_item(a, item);
     const int k = lane & (D - 1), base = lane - k, slot = lane / D;
-    const unsigned long long row = (unsigned long long)(a.row0 + r);
-    const double2* csr = a.cs + r * a.E;
     const double hk = a.shots ? 0.0 : hd[k];
     const double off_term = (a.shots || a.diag) ? 0.0 : a.off;
 
     double sum = 0.0, sq = 0.0;
-    for (int it = 0; it < tcount; it += SL) {
+    for (int it = 0; it < wi.tcount; it += SL) {
         const int tj = it + slot;
-        const unsigned traj = (unsigned)(t0 + tj);
+        const unsigned traj = (unsigned)(wi.t0 + tj);
         double re = k == 0 ? 1.0 : 0.0, im = 0.0, nrm2 = 1.0;
         unsigned call = 0, code, w3;
         int s = 0, col = 0;
         for (int g = 0; g < 2; ++g) {
             for (int b = 0; b < a.nb[g]; ++b) {
                 // per wire: encoding RX, then site ENC (Pauli, dephasing, jump)
-                site_draws<false>(a, tab, call, 0, N, k, traj, row, code, w3);
+                site_draws<false>(a, tab, call, 0, N, k, traj, wi.row, code, w3);
                 int x = 0, z = 0;
 #pragma unroll
                 for (int q = 0; q < N; ++q) {
-                    const double2 c = csr[col + q];
+                    const double2 c = wi.csr[col + q];
                     const double pr = __shfl(re, lane ^ (1 << q)), pi = __shfl(im, lane ^ (1 << q));
                     const double nr = c.x * re + c.y * pi, ni = c.x * im - c.y * pr;
                     re = nr; im = ni;
@@ -260,7 +202,7 @@ __global__ __launch_bounds__(64 * kJumpWaves) void device_traj_lane_kernel(Noise
                 rescale_lane(re, im, nrm2);
                 col += N; call += N;
                 for (int l = 0; l < a.ld[g]; ++l, ++s) {
-                    site_draws<false>(a, tab, call, N, N, k, traj, row, code, w3);
+                    site_draws<false>(a, tab, call, N, N, k, traj, wi.row, code, w3);
                     x = 0; z = 0;
 #pragma unroll
                     for (int q = 0; q < N; ++q) {                        // fused RY RZ RY per wire, then site ROT
@@ -275,7 +217,7 @@ __global__ __launch_bounds__(64 * kJumpWaves) void device_traj_lane_kernel(Noise
                                       lane);
                     }
                     call += N;
-                    site_draws<true>(a, tab, call, 2 * N, 2 * N, k, traj, row, code, w3);
+                    site_draws<true>(a, tab, call, 2 * N, 2 * N, k, traj, wi.row, code, w3);
 #pragma unroll
                     for (int j = 0; j < N; ++j) {                        // slot j: CNOT(c -> t), pair Pauli, TGT of t, CTL of c
                         const int c = (j + 1) % N, t = j;
@@ -321,9 +263,9 @@ __global__ __launch_bounds__(64 * kJumpWaves) void device_traj_lane_kernel(Noise
             v = group_sum<N>(pk * hk) / tot + off_term;
         } else {
             // one measured bitstring: u against the cdf in index order, then the n readout flips of its own bits
-            const uint4 w0 = philox(make_uint4(a.L, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
-            const uint4 w1 = philox(make_uint4(a.L + 1, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
-            const double u = ((double)(w0.x >> 5) * 67108864.0 + (double)(w0.y >> 6)) * 0x1p-53;
+            const uint4 w0 = philox(make_uint4(a.L, traj, (unsigned)wi.row, (unsigned)(wi.row >> 32)), a.key0, a.key1);
+            const uint4 w1 = philox(make_uint4(a.L + 1, traj, (unsigned)wi.row, (unsigned)(wi.row >> 32)), a.key0, a.key1);
+            const double u = unit_double(w0.x, w0.y);
             const double ut = u * tot;
             double acc = 0.0;
             int out = -1, last = 0;
@@ -341,7 +283,7 @@ __global__ __launch_bounds__(64 * kJumpWaves) void device_traj_lane_kernel(Noise
                 flips |= (unsigned long long)rw[i] < tab->rthr[i][(out >> i) & 1] ? 1 << i : 0;
             v = shot_value<N>(a.diag, a.off, a.co, out ^ flips);
         }
-        if (tj < tcount) { sum += v; sq += v * v; }
+        if (tj < wi.tcount) { sum += v; sq += v * v; }
     }
     double S = 0.0, Q = 0.0;
 #pragma unroll
@@ -419,6 +361,7 @@ __global__ __launch_bounds__(64 * kJumpWaves) void device_traj_wave_kernel(Noise
     const int lane = threadIdx.x & 63;
     const long item = (long)blockIdx.x * kJumpWaves + (threadIdx.x >> 6);
     if (item >= a.B * a.tiles) return;                                   // whole waves
+    // (written out, not work_item(): with it this kernel's device code changes; the same holds for u of the cdf search below)
     const long r = item / a.tiles;
     const long t0 = (item - r * a.tiles) * (long)kTile;
     const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
@@ -587,15 +530,7 @@ int launch_device_traj(const NoiseArgs& a, int n, const DevTable* tab, const dou
 }
 
 // the uniform units' layout with the read-out region of the wide ones, then the table
-constexpr TrajUnit kJumpUnit{QHEA_MIN_QUBITS, kJumpMaxWires, true, nullptr};
-struct JumpLayout { TrajLayout t; size_t off_tab, total; };
-inline JumpLayout jump_layout(const ModelInfo& mi, int64_t B, int64_t T) {
-    JumpLayout L{};
-    L.t = traj_layout(kJumpUnit, mi, B, T);
-    L.off_tab = L.t.total;
-    L.total = align256(L.off_tab + sizeof(DevTable));
-    return L;
-}
+constexpr TrajUnit kJumpUnit{QHEA_MIN_QUBITS, kJumpMaxWires, true, sizeof(DevTable)};
 
 inline qhea_noise sampling_as_noise(const qhea_sampling* s) {
     qhea_noise nz{};
@@ -642,12 +577,9 @@ int qhea_device_noise_jump_tables(int n, const qhea_device_noise* dn, double* ju
 }
 
 size_t qhea_model_noisy_device_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling) {
-    ModelInfo mi;
-    if (!sampling || batch < 0 || model_info(desc, mi) != QHEA_OK || mi.n > kJumpMaxWires) return 0;
+    if (!sampling) return 0;
     const qhea_noise nz = sampling_as_noise(sampling);
-    const int64_t T = noise_values(&nz);
-    if (T < 1) return 0;
-    return jump_layout(mi, batch, T).total;
+    return traj_workspace_bytes(kJumpUnit, desc, batch, &nz);
 }
 
 int qhea_model_forward_noisy_device(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
@@ -663,40 +595,26 @@ int qhea_model_forward_noisy_device(const qhea_model_desc* desc, int64_t row0, i
     if (rc != QHEA_OK) return rc;
     if (!sampling) return QHEA_EINVAL;
     const qhea_noise nz = sampling_as_noise(sampling);
-    NoisyCall c;
-    rc = noisy_call_check({QHEA_MIN_QUBITS, kJumpMaxWires, true, false}, desc, ham_diag, &nz, row0, batch, trunk,
-                          {branch, params, pred}, workspace, stream, c);
-    if (rc != QHEA_OK || c.empty) return rc;
-    const JumpLayout L = jump_layout(c.mi, batch, c.T);
-    if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
-    if ((int64_t)batch * L.t.tiles > (int64_t)INT_MAX) return QHEA_EINVAL;
-    const int n = c.mi.n;
-    double4* gates = reinterpret_cast<double4*>(c.ws + L.t.off_gates);
-    double2* cs = reinterpret_cast<double2*>(c.ws + L.t.off_cs);
-    double2* part = reinterpret_cast<double2*>(c.ws + L.t.off_part);
-    double* mix = reinterpret_cast<double*>(c.ws + L.t.off_mix);
-    DevTable* tab = reinterpret_cast<DevTable*>(c.ws + L.off_tab);
-    rc = launch_prep_model(desc, c.mi, batch, branch, trunk, params, gates, cs, c.ws, c.st);
-    if (rc != QHEA_OK) return rc;
-
-    NoiseArgs a = noise_args(desc, c.mi, &nz, params, ham_diag, row0, batch, c.T);
-    a.gates = gates; a.cs = cs; a.partial = part;
+    TrajCall t;
+    rc = traj_open(kJumpUnit, desc, row0, batch, branch, trunk, params, ham_diag, &nz, pred, workspace, workspace_bytes, stream, t);
+    if (rc != QHEA_OK || t.c.empty) return rc;
+    const int n = t.c.mi.n;
+    NoiseArgs& a = t.a;
     unsigned calls = 0;                                                  // C of the header: n + 3 n ld per block
-    for (int g = 0; g < 2; ++g) calls += (unsigned)c.mi.nb[g] * (unsigned)(n + 3 * n * c.mi.ld[g]);
+    for (int g = 0; g < 2; ++g) calls += (unsigned)t.c.mi.nb[g] * (unsigned)(n + 3 * n * t.c.mi.ld[g]);
     a.L = calls;                                                         // shot mode continues from call C
-    DevTable t{};
+    DevTable tb{};
     bool any;
-    fill_table(n, dn, t, any);
-    t.off = a.off; t.co = a.co; t.diag = ham_diag; t.L = a.L; t.pauli = (unsigned)a.pauli;
+    fill_table(n, dn, tb, any);
+    tb.off = a.off; tb.co = a.co; tb.diag = ham_diag; tb.L = a.L; tb.pauli = (unsigned)a.pauli;
     a.thr1 = any ? 1 : 0;                                                // an ideal setting draws nothing
+    DevTable* tab = reinterpret_cast<DevTable*>(t.extra);
     const bool expect = !a.shots;
-    hipLaunchKernelGGL(device_tables_kernel, dim3(1), dim3(256), 0, c.st, t, tab, ham_diag, a.co, n,
-                       expect ? mix : static_cast<double*>(nullptr));
+    hipLaunchKernelGGL(device_tables_kernel, dim3(1), dim3(256), 0, t.c.st, tb, tab, ham_diag, a.co, n,
+                       expect ? t.mix : static_cast<double*>(nullptr));
     if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    const double* hd = expect ? mix + ((size_t)((n - 1) & 1) << n) : nullptr;
-    rc = launch_device_traj(a, n, tab, hd, c.st);
-    if (rc != QHEA_OK) return rc;
-    return launch_noisy_finish(part, L.t.tiles, batch, c.T, a.bias, pred, stderr_out, c.st);
+    const double* hd = expect ? t.mix + ((size_t)((n - 1) & 1) << n) : nullptr;
+    return traj_finish(t, launch_device_traj(a, n, tab, hd, t.c.st), pred, stderr_out);
 }
 
 }  // extern "C"

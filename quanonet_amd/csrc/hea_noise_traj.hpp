@@ -1,7 +1,9 @@
-// hea_noise_traj.hpp -- what the noisy entry points share.  All four units (hea_noise.hip, hea_noise_wide.hip, hea_density.hip,
-// hea_density_grad.hip): the checks of a qhea_noise and the argument checks that open every call (noisy_call_check).  The two
-// trajectory units (n = 2..6, one amplitude per lane; n = 7..12, registers or LDS): the argument record, the Philox stream and
-// its error codes, the Pauli frame bits, the workspace layout and the body of the entry point around a unit's kernels.
+// hea_noise_traj.hpp -- what the noisy entry points share.  All units (hea_noise.hip, hea_noise_wide.hip, hea_noise_device.hip
+// and the density-matrix ones): the checks of a qhea_noise and the argument checks that open every call (noisy_call_check).  The
+// three trajectory units (uniform noise at n = 2..6, one amplitude per lane, and at n = 7..12, registers or LDS; device noise at
+// n = 2..9 in both layouts): the argument record, the Philox stream and its error codes, the Pauli frame bits and the frame's
+// application in either layout (apply_frame, frame_regs), the work item, wave_scan, u and the value of a shot, the workspace
+// layout, and the head and tail of the entry point around a unit's kernels (traj_open, traj_finish).
 #pragma once
 #include <climits>
 #include <cmath>
@@ -70,6 +72,86 @@ __device__ __forceinline__ unsigned code_at(unsigned codes, unsigned l0, unsigne
 // Pauli p (0 I, 1 X, 2 Y, 3 Z) on wire w as (X mask, Z mask) bits, up to phase
 __device__ __forceinline__ int pauli_x(unsigned p, int w) { return (p == 1u || p == 2u) ? 1 << w : 0; }
 __device__ __forceinline__ int pauli_z(unsigned p, int w) { return p >= 2u ? 1 << w : 0; }
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// u in [0, 1) of shot mode's cdf search: 53 bits from two words
+__device__ __forceinline__ double unit_double(unsigned w0, unsigned w1) {
+    return ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) * 0x1p-53;
+}
+
+template <int N>
+__device__ __forceinline__ double shot_value(const double* __restrict__ diag, double off, double co, int out) {
+#pragma clang fp contract(off)              // a product and a sum, each rounded: a shot's value is the same number on any host
+    return diag ? diag[out] : off + co * (double)(N - 2 * (int)__popc((unsigned)out));
+}
+
+// A work item of the wave kernels and the LDS kernel: row r of the call (global row `row`, its encoding table csr) and the
+// tcount <= kTile trajectories from t0 on
+struct WorkItem {
+    long r, t0;
+    int tcount;
+    unsigned long long row;
+    const double2* csr;
+};
+__device__ __forceinline__ WorkItem work_item(const NoiseArgs& a, long item) {
+    const long r = item / a.tiles, t0 = (item - r * a.tiles) * (long)kTile;
+    return {r, t0, (int)(a.T - t0 < kTile ? a.T - t0 : kTile), (unsigned long long)(a.row0 + r), a.cs + r * a.E};
+}
+
+// one amplitude per lane (n = 2..6), basis state k of a slot on lane base + k: psi <- X^x Z^z psi (up to a global phase),
+// psi'[k] = (-1)^popcount((k ^ x) & z) psi[k ^ x]
+__device__ __forceinline__ void apply_frame(double& re, double& im, int x, int z, int k, int base) {
+    if (__any(x | z)) {
+        const int src = k ^ x;
+        const double pr = __shfl(re, base + src), pi = __shfl(im, base + src);
+        const bool neg = __popc(src & z) & 1;
+        re = neg ? -pr : pr;
+        im = neg ? -pi : pi;
+    }
+}
+
+// inclusive sum over the lanes 0 .. lane of a wave (Hillis-Steele, distances 1, 2, .. 32: a fixed order)
+__device__ __forceinline__ double wave_scan(double c, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double t = __shfl_up(c, d);
+        if (lane >= d) c += t;
+    }
+    return c;
+}
+
+// Cfg<N>'s register layout (n = 7..9), k = lane | r << 6: psi'[k] = (-1)^parity(k & z) psi[k ^ x]; x, z wave-uniform
+template <int N>
+__device__ __forceinline__ void frame_regs(double (&re)[Cfg<N>::R], double (&im)[Cfg<N>::R], int x, int z, int lane) {
+    using C = Cfg<N>;
+    if ((x | z) == 0) return;
+    if (x & 63) {
+        const int src = (lane ^ (x & 63)) << 2;
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) { re[r] = lane_gather(re[r], src); im[r] = lane_gather(im[r], src); }
+    }
+    static_for<0, C::RB>([&](auto b) {
+        constexpr int J = 1 << decltype(b)::value;
+        if ((x >> 6) & J) {
+#pragma unroll
+            for (int r = 0; r < C::R; ++r) {
+                if (r & J) continue;
+                double t = re[r]; re[r] = re[r | J]; re[r | J] = t;
+                t = im[r]; im[r] = im[r | J]; im[r | J] = t;
+            }
+        }
+    });
+    if (z) {
+        const int lp = __popc((unsigned)(lane & z & 63));
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) {
+            const bool neg = (lp + __popc((unsigned)(r & (z >> 6)))) & 1;
+            re[r] = neg ? -re[r] : re[r];
+            im[r] = neg ? -im[r] : im[r];
+        }
+    }
+}
 
 inline bool rates_ok(const qhea_noise* nz) {
     if (!nz) return false;
@@ -158,14 +240,14 @@ int launch_noisy_finish(const double2* partial, int tiles, int64_t B, int64_t T,
                         hipStream_t st);
 
 // A trajectory unit: the qubit counts of its kernels, whether it keeps ham_diag under the readout confusion in a region of its
-// own (`mix`: 2 x 2^n doubles, NULL without one), and its launch of the trajectory kernel for a.B * a.tiles work items
+// own (`wide`: 2 x 2^n doubles), and the bytes of a last region of its own (0: none)
 struct TrajUnit {
     int nmin, nmax;
     bool wide;
-    int (*launch)(const NoiseArgs& a, int n, double* mix, hipStream_t st);
+    size_t extra;
 };
 
-struct TrajLayout { size_t off_gates, off_cs, off_part, off_mix /* wide units */, total; int tiles; };
+struct TrajLayout { size_t off_gates, off_cs, off_part, off_mix /* wide units */, off_extra, total; int tiles; };
 inline TrajLayout traj_layout(const TrajUnit& u, const ModelInfo& mi, int64_t B, int64_t T) {
     TrajLayout L{};
     L.tiles = (int)((T + kTile - 1) / kTile);
@@ -174,40 +256,54 @@ inline TrajLayout traj_layout(const TrajUnit& u, const ModelInfo& mi, int64_t B,
     size_t p = t.end;
     L.off_part = p; p = align256(p + (size_t)B * L.tiles * sizeof(double2));
     if (u.wide) { L.off_mix = p; p = align256(p + ((size_t)2 << mi.n) * sizeof(double)); }
+    if (u.extra) { L.off_extra = p; p = align256(p + u.extra); }
     L.total = p;
     return L;
 }
 
-// qhea_model_noisy_workspace_bytes answers for every qubit count, ..._noisy_wide_workspace_bytes for its own from nmin on
+// qhea_model_noisy_workspace_bytes answers for every qubit count, the wide units' calls for their own counts only
 inline size_t traj_workspace_bytes(const TrajUnit& u, const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise) {
     ModelInfo mi;
     const int64_t T = noise_values(noise);
-    if (T < 1 || batch < 0 || model_info(desc, mi) != QHEA_OK || (u.wide && mi.n < u.nmin)) return 0;
+    if (T < 1 || batch < 0 || model_info(desc, mi) != QHEA_OK || (u.wide && (mi.n < u.nmin || mi.n > u.nmax))) return 0;
     return traj_layout(u, mi, batch, T).total;
 }
 
-// qhea_model_forward_noisy and qhea_model_forward_noisy_wide: checks, prep, the unit's trajectories, finish
-inline int traj_forward(const TrajUnit& u, const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
-                        const double* trunk, const double* params, const double* ham_diag, const qhea_noise* noise, double* pred,
-                        double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
+// What a trajectory call holds once traj_open has passed it: the regions of its workspace and its kernels' arguments
+struct TrajCall {
     NoisyCall c;
+    TrajLayout L;
+    NoiseArgs a;
+    double* mix = nullptr;                  // wide units
+    char* extra = nullptr;                  // units with a region of their own
+};
+
+// The head of the three trajectory entry points: checks, layout, prep.  QHEA_OK with t.c.empty set: nothing to do.
+inline int traj_open(const TrajUnit& u, const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
+                     const double* trunk, const double* params, const double* ham_diag, const qhea_noise* noise, double* pred,
+                     void* workspace, size_t workspace_bytes, void* stream, TrajCall& t) {
+    NoisyCall& c = t.c;
     int rc = noisy_call_check({u.nmin, u.nmax, true, false}, desc, ham_diag, noise, row0, batch, trunk, {branch, params, pred},
                               workspace, stream, c);
     if (rc != QHEA_OK || c.empty) return rc;
-    const TrajLayout L = traj_layout(u, c.mi, batch, c.T);
+    const TrajLayout& L = t.L = traj_layout(u, c.mi, batch, c.T);
     if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
     if (u.wide && (int64_t)batch * L.tiles > (int64_t)INT_MAX) return QHEA_EINVAL;      // one workgroup per (row, tile)
     double4* gates = reinterpret_cast<double4*>(c.ws + L.off_gates);
     double2* cs = reinterpret_cast<double2*>(c.ws + L.off_cs);
-    double2* part = reinterpret_cast<double2*>(c.ws + L.off_part);
     rc = launch_prep_model(desc, c.mi, batch, branch, trunk, params, gates, cs, c.ws, c.st);
     if (rc != QHEA_OK) return rc;
+    t.a = noise_args(desc, c.mi, noise, params, ham_diag, row0, batch, c.T);
+    t.a.gates = gates; t.a.cs = cs; t.a.partial = reinterpret_cast<double2*>(c.ws + L.off_part);
+    if (u.wide) t.mix = reinterpret_cast<double*>(c.ws + L.off_mix);
+    if (u.extra) t.extra = c.ws + L.off_extra;
+    return QHEA_OK;
+}
 
-    NoiseArgs a = noise_args(desc, c.mi, noise, params, ham_diag, row0, batch, c.T);
-    a.gates = gates; a.cs = cs; a.partial = part;
-    rc = u.launch(a, c.mi.n, u.wide ? reinterpret_cast<double*>(c.ws + L.off_mix) : nullptr, c.st);
+// ... and their tail, behind the unit's launch (rc): row r's tiles added in tile order, mean (+ bias) and standard error
+inline int traj_finish(const TrajCall& t, int rc, double* pred, double* stderr_out) {
     if (rc != QHEA_OK) return rc;
-    return launch_noisy_finish(part, L.tiles, batch, c.T, a.bias, pred, stderr_out, c.st);
+    return launch_noisy_finish(t.a.partial, t.L.tiles, t.a.B, t.c.T, t.a.bias, pred, stderr_out, t.c.st);
 }
 
 }  // namespace qhea

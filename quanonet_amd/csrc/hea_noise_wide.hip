@@ -24,6 +24,9 @@
 // readout_mix_kernel builds by n two-point mixes (the O(4^n) loop of hea_noise.hip is out of reach here).  Shot mode scans
 // |psi_k|^2 into a cdf (block offsets in order, a Hillis-Steele scan over lanes inside a block) and locates the first k with
 // u < cdf[k] by ballots or a workgroup minimum.  Nothing depends on the batch, the grid or the chunking; no atomics.
+//
+// The work item, frame_regs, wave_scan, uniform, u of the cdf search and shot_value are hea_noise_traj.hpp's, shared with
+// hea_noise_device.hip; the frames of a segment, the shot words, the LDS kernel and the readout mix are this unit's.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -36,8 +39,6 @@ namespace {
 
 constexpr int kWideWaves = 4;               // n = 7..9: waves per workgroup (independent; no LDS, no barrier)
 constexpr int kWideLG = 4;                  // n = 10..12: gate qubits per pass, as the ideal forward (hea_lds.hip)
-
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // (X mask, Z mask) of the errors behind a block's n encoding RX gates; codes: segment_codes of the wave's lanes
 template <int N>
@@ -87,63 +88,16 @@ __device__ __forceinline__ void shot_words(const NoiseArgs& a, unsigned traj, un
         if (i >= 0 && i < N && (unsigned long long)wd[h] < a.thrq) mask |= 1 << i;
     }
     flips = uniform(__shfl(mask, 0) | __shfl(mask, 1) | __shfl(mask, 2) | __shfl(mask, 3));
-    u = __shfl(((double)(w.x >> 5) * 67108864.0 + (double)(w.y >> 6)) * 0x1p-53, 0);
+    u = __shfl(unit_double(w.x, w.y), 0);
 }
 
-template <int N>
-__device__ __forceinline__ double shot_value(const NoiseArgs& a, int out) {
-#pragma clang fp contract(off)              // a product and a sum, each rounded: a shot's value is the same number on any host
-    return a.diag ? a.diag[out] : a.off + a.co * (double)(N - 2 * (int)__popc((unsigned)out));
-}
 // expectation mode's weight of basis state k (hd: the readout-confused ham_diag, or NULL)
 template <int N>
 __device__ __forceinline__ double readout_weight(const NoiseArgs& a, const double* __restrict__ hd, int k) {
     return hd ? hd[k] : a.co * (1.0 - 2.0 * a.q) * (double)(N - 2 * (int)__popc((unsigned)k));
 }
 
-// inclusive sum over the lanes 0 .. lane of a wave (Hillis-Steele, distances 1, 2, .. 32: a fixed order)
-__device__ __forceinline__ double wave_scan(double c, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double t = __shfl_up(c, d);
-        if (lane >= d) c += t;
-    }
-    return c;
-}
-
 // ---- n = 7..9: one wave, 2^(n-6) amplitudes per lane -------------------------------------------------------------------------
-
-// psi'[k] = (-1)^parity(k & z) psi[k ^ x], k = lane | r << 6; x, z wave-uniform
-template <int N>
-__device__ __forceinline__ void frame_regs(double (&re)[Cfg<N>::R], double (&im)[Cfg<N>::R], int x, int z, int lane) {
-    using C = Cfg<N>;
-    if ((x | z) == 0) return;
-    if (x & 63) {
-        const int src = (lane ^ (x & 63)) << 2;
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) { re[r] = lane_gather(re[r], src); im[r] = lane_gather(im[r], src); }
-    }
-    static_for<0, C::RB>([&](auto b) {
-        constexpr int J = 1 << decltype(b)::value;
-        if ((x >> 6) & J) {
-#pragma unroll
-            for (int r = 0; r < C::R; ++r) {
-                if (r & J) continue;
-                double t = re[r]; re[r] = re[r | J]; re[r | J] = t;
-                t = im[r]; im[r] = im[r | J]; im[r | J] = t;
-            }
-        }
-    });
-    if (z) {
-        const int lp = __popc((unsigned)(lane & z & 63));
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) {
-            const bool neg = (lp + __popc((unsigned)(r & (z >> 6)))) & 1;
-            re[r] = neg ? -re[r] : re[r];
-            im[r] = neg ? -im[r] : im[r];
-        }
-    }
-}
 
 template <int N>
 __global__ __launch_bounds__(64 * kWideWaves) void noisy_wide_wave_kernel(NoiseArgs a, const double* __restrict__ hd) {
@@ -152,11 +106,7 @@ __global__ __launch_bounds__(64 * kWideWaves) void noisy_wide_wave_kernel(NoiseA
     const int lane = threadIdx.x & 63;
     const long item = (long)blockIdx.x * kWideWaves + (threadIdx.x >> 6);
     if (item >= a.B * a.tiles) return;                                   // whole waves
-    const long r = item / a.tiles;
-    const long t0 = (item - r * a.tiles) * (long)kTile;
-    const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
-    const unsigned long long row = (unsigned long long)(a.row0 + r);
-    const double2* csr = a.cs + r * a.E;
+    const WorkItem wi = work_item(a, item);
     const int ring_src = ring_source<N>(lane, false);
 
     double hk[R];
@@ -165,8 +115,8 @@ __global__ __launch_bounds__(64 * kWideWaves) void noisy_wide_wave_kernel(NoiseA
     const double off_term = (a.shots || hd) ? 0.0 : a.off;
 
     double sum = 0.0, sq = 0.0;
-    for (int tj = 0; tj < tcount; ++tj) {
-        const unsigned traj = (unsigned)(t0 + tj);
+    for (int tj = 0; tj < wi.tcount; ++tj) {
+        const unsigned traj = (unsigned)(wi.t0 + tj);
         double re[R], im[R];
 #pragma unroll
         for (int i = 0; i < R; ++i) { re[i] = 0.0; im[i] = 0.0; }
@@ -176,17 +126,17 @@ __global__ __launch_bounds__(64 * kWideWaves) void noisy_wide_wave_kernel(NoiseA
         for (int g = 0; g < 2; ++g) {
             for (int b = 0; b < a.nb[g]; ++b) {
                 // encoding RX on every wire, then one-qubit depolarizing noise on every wire
-                unsigned codes = segment_codes(a, loc, N, N, traj, row, lane);
+                unsigned codes = segment_codes(a, loc, N, N, traj, wi.row, lane);
                 static_for<0, N>([&](auto q) {
                     constexpr int Q = decltype(q)::value;
-                    const double2 c = csr[col + Q];
+                    const double2 c = wi.csr[col + Q];
                     apply_rx<N, Q>(re, im, c.x, c.y);
                 });
                 enc_frame<N>(codes, loc, x, z);
                 frame_regs<N>(re, im, x, z, lane);
                 col += N; loc += N;
                 for (int l = 0; l < a.ld[g]; ++l, ++s, loc += 2 * N) {
-                    codes = segment_codes(a, loc, 2 * N, N, traj, row, lane);
+                    codes = segment_codes(a, loc, 2 * N, N, traj, wi.row, lane);
                     static_for<0, N>([&](auto q) {                       // fused RY RZ RY per wire
                         constexpr int Q = decltype(q)::value;
                         constexpr bool kSigned = Q < C::LB && !kSwapQubit<N, Q>;   // the lane's variant of the gate table
@@ -214,7 +164,7 @@ __global__ __launch_bounds__(64 * kWideWaves) void noisy_wide_wave_kernel(NoiseA
         } else {
             double u;
             int flips, out = -1, last = 0;
-            shot_words<N>(a, traj, row, lane, u, flips);
+            shot_words<N>(a, traj, wi.row, lane, u, flips);
             double below = 0.0;                                          // cdf of the blocks of 64 before this one
 #pragma unroll
             for (int i = 0; i < R; ++i) {
@@ -225,7 +175,7 @@ __global__ __launch_bounds__(64 * kWideWaves) void noisy_wide_wave_kernel(NoiseA
                 below += __shfl(c, 63);
             }
             if (out < 0) out = last;
-            v = shot_value<N>(a, out ^ flips);
+            v = shot_value<N>(a.diag, a.off, a.co, out ^ flips);
         }
         sum += v; sq += v * v;
     }
@@ -308,19 +258,15 @@ __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(N
     WideScratch* sc = reinterpret_cast<WideScratch*>(wide_lds + L::STATE_BYTES);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const long item = blockIdx.x;
-    const long r = item / a.tiles;
-    const long t0 = (item - r * a.tiles) * (long)kTile;
-    const int tcount = (int)(a.T - t0 < kTile ? a.T - t0 : kTile);
-    const unsigned long long row = (unsigned long long)(a.row0 + r);
-    const double2* csr = a.cs + r * a.E;
+    const WorkItem wi = work_item(a, item);
     Bases<N, LG> bs;
     bs.init(t);
     const int tpl = thread_part<Pass<N, L::NP - 1, LG>::A, LG>(t);
     const double off_term = (a.shots || hd) ? 0.0 : a.off;
 
     double sum = 0.0, sq = 0.0;
-    for (int tj = 0; tj < tcount; ++tj) {
-        const unsigned traj = (unsigned)(t0 + tj);
+    for (int tj = 0; tj < wi.tcount; ++tj) {
+        const unsigned traj = (unsigned)(wi.t0 + tj);
 #pragma unroll
         for (int j = 0; j < M; ++j) {
             const int p = t + j * L::T;
@@ -333,15 +279,15 @@ __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(N
             for (int b = 0; b < a.nb[g]; ++b) {
                 if (wave == 0) {
                     int x, z;
-                    enc_frame<N>(segment_codes(a, loc, N, N, traj, row, lane), loc, x, z);
+                    enc_frame<N>(segment_codes(a, loc, N, N, traj, wi.row, lane), loc, x, z);
                     if (t == 0) { sc->frame[0] = phys<LG>(x); sc->frame[1] = z; }
                 }
-                noisy_layer<N, false>(psi, bs, tpl, sc, [&](int q) { return rx_su2(csr[col + q]); });
+                noisy_layer<N, false>(psi, bs, tpl, sc, [&](int q) { return rx_su2(wi.csr[col + q]); });
                 col += N; loc += N;
                 for (int l = 0; l < a.ld[g]; ++l, ++s, loc += 2 * N) {
                     if (wave == 0) {
                         int x, z;
-                        sub_frame<N>(segment_codes(a, loc, 2 * N, N, traj, row, lane), loc, x, z);
+                        sub_frame<N>(segment_codes(a, loc, 2 * N, N, traj, wi.row, lane), loc, x, z);
                         if (t == 0) { sc->frame[0] = phys<LG>(x); sc->frame[1] = ring_pull<N>(z); }
                     }
                     noisy_layer<N, true>(psi, bs, tpl, sc, [&](int q) { return a.gates[2 * ((s + 1) * N + q)]; });
@@ -357,7 +303,7 @@ __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(N
         if (a.shots && wave == 0) {
             double u;
             int flips;
-            shot_words<N>(a, traj, row, lane, u, flips);
+            shot_words<N>(a, traj, wi.row, lane, u, flips);
             if (t == 0) { sc->u = u; sc->flips = flips; }
         }
         // thread t reads the 16 consecutive basis states 16 t .. 16 t + 15
@@ -405,7 +351,7 @@ __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(N
                 hi = sc->hi[w] > hi ? sc->hi[w] : hi;
             }
             const int out = lo != INT_MAX ? lo : (hi < 0 ? 0 : hi);
-            val = shot_value<N>(a, out ^ sc->flips);
+            val = shot_value<N>(a.diag, a.off, a.co, out ^ sc->flips);
         }
         sum += val; sq += val * val;
         __syncthreads();                                                 // psi and the scratch are rewritten
@@ -462,7 +408,7 @@ int launch_noisy_wide(const NoiseArgs& a, int n, double* mix, hipStream_t st) {
         default: return QHEA_EUNSUPPORTED;
     }
 }
-constexpr TrajUnit kWideUnit{7, QHEA_MAX_QUBITS, true, launch_noisy_wide};   // qhea_model_forward_noisy is the path below 7
+constexpr TrajUnit kWideUnit{7, QHEA_MAX_QUBITS, true, 0};                   // qhea_model_forward_noisy is the path below 7
 
 }  // namespace
 }  // namespace qhea
@@ -478,8 +424,11 @@ size_t qhea_model_noisy_wide_workspace_bytes(const qhea_model_desc* desc, int64_
 int qhea_model_forward_noisy_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
                                   const double* trunk, const double* params, const double* ham_diag, const qhea_noise* noise,
                                   double* pred, double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return traj_forward(kWideUnit, desc, row0, batch, branch, trunk, params, ham_diag, noise, pred, stderr_out, workspace,
-                        workspace_bytes, stream);
+    TrajCall t;
+    const int rc = traj_open(kWideUnit, desc, row0, batch, branch, trunk, params, ham_diag, noise, pred, workspace, workspace_bytes,
+                             stream, t);
+    if (rc != QHEA_OK || t.c.empty) return rc;
+    return traj_finish(t, launch_noisy_wide(t.a, t.c.mi.n, t.mix, t.c.st), pred, stderr_out);
 }
 
 }  // extern "C"

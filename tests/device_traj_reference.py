@@ -6,7 +6,7 @@ include/quanonet_hea.h):
   * readout_weights -- h(k) / diag' of expectation mode under the asymmetric readout;
   * replay_values -- a gate-by-gate fp64 statevector replay of every (row, trajectory) on the header's random stream, the state
     normalised at every damping event exactly as the header words it.  It also counts the events that fired.
-Circuit conventions are oracle.hea_oracle's; gates, Philox and thresholds are tests/noise_oracle.py's.
+Circuit conventions are oracle.hea_oracle's; gates, the stream, thresholds and shot mode's tail are tests/noise_oracle.py's.
 """
 import numpy as np
 
@@ -86,14 +86,9 @@ def replay_values(n, cfgs, x, w, nz, shots, trajectories, seed, offset=0.0, coef
     w = np.asarray(w, np.float64)
     B = x.shape[0]
     T = int(shots) if shots > 0 else int(trajectories)
-    rows = np.repeat(np.arange(B, dtype=np.uint64) + np.uint64(row0), T)
-    trajs = np.tile(np.arange(T, dtype=np.uint64), B)
-    key = (int(seed) & 0xFFFFFFFF, int(seed) >> 32)
+    words = NO.stream(B, T, row0, seed)
     jp = jump_pairs(n, nz)
     fired = {'pauli': 0, 'dephasing': 0, 'jump': 0}
-
-    def words(c):
-        return NO.philox4x32((np.uint64(c), trajs, rows & NO.M32, rows >> np.uint64(32)), key)
 
     M = B * T
     psi = np.zeros((M, 1 << n), dtype=np.complex128)
@@ -173,24 +168,9 @@ def replay_values(n, cfgs, x, w, nz, shots, trajectories, seed, offset=0.0, coef
         off, h = readout_weights(n, offset, coeff, ham_diag, r01, r10)
         vals = off + prob @ h
     else:
-        wm = words(call)
-        u = ((wm[0] >> np.uint64(5)).astype(np.float64) * 67108864.0 + (wm[1] >> np.uint64(6)).astype(np.float64)) * 2.0 ** -53
-        cdf = np.cumsum(prob, axis=1)
-        hit = u[:, None] < cdf
-        last = (1 << n) - 1 - np.argmax((prob > 0)[:, ::-1], axis=1)
-        out = np.where(hit.any(axis=1), np.argmax(hit, axis=1), last)
-        true = out.copy()
-        for i in range(n):
-            m = 2 + i
-            wd = words(call + m // 4)[m % 4]
-            bit = (true >> i) & 1
-            thr = np.where(bit == 1, np.uint64(NO.threshold(r10[i])), np.uint64(NO.threshold(r01[i])))
-            out = out ^ ((wd < thr).astype(np.int64) << i)
-        if ham_diag is not None:
-            vals = np.asarray(ham_diag, np.float64)[out]
-        else:
-            pop = sum((out >> i) & 1 for i in range(n))
-            vals = offset + coeff * (n - 2.0 * pop)
+        thr = [(np.uint64(NO.threshold(r01[i])), np.uint64(NO.threshold(r10[i]))) for i in range(n)]
+        vals = NO.shot_values(prob, words, call, n, lambda i, bit: np.where(bit == 1, thr[i][1], thr[i][0]), offset, coeff,
+                              ham_diag)
     return vals.reshape(B, T)
 
 

@@ -1,6 +1,8 @@
 """
 numpy checker for the noisy forward (qhea_model_forward_noisy, include/quanonet_hea.h):
   * philox4x32 -- Philox4x32-10, vectorised over counters;
+  * stream, shot_values -- the random stream of a call's (row, trajectory) pairs and the tail of shot mode, shared with
+    tests/device_traj_reference.py;
   * replay_values -- a gate-by-gate fp64 statevector replay of every (row, trajectory) that consumes the header's random
     stream: a trajectory's value (expectation mode: its exact read-out with readout error folded in; shot mode: one sampled,
     readout-flipped bitstring);
@@ -94,6 +96,41 @@ def _readout_weights(n, offset, coeff, ham_diag, q):
     return float(offset), coeff * (1.0 - 2.0 * q) * (n - 2.0 * pop)
 
 
+def stream(B, T, row0, seed):
+    """words(c) of a call's B * T values, row-major: the four word arrays of Philox call c for every (row, trajectory)."""
+    rows = np.repeat(np.arange(B, dtype=np.uint64) + np.uint64(row0), T)
+    trajs = np.tile(np.arange(T, dtype=np.uint64), B)
+    key = (int(seed) & 0xFFFFFFFF, int(seed) >> 32)
+    cache = {}
+
+    def words(c):
+        if c not in cache:
+            cache[c] = philox4x32((np.uint64(c), trajs, rows & M32, rows >> np.uint64(32)), key)
+        return cache[c]
+
+    return words
+
+
+def shot_values(prob, words, call0, n, thr, offset, coeff, ham_diag):
+    """Shot mode's tail.  u (53 bits of call0's first two words) picks the first k with u < cdf[k] (prob as given, index order,
+    fp64), or the last k of positive weight; bit i of it flips iff word 2 + i of the calls from call0 on is below thr(i, the
+    bit's true value); the value of the string that is read."""
+    wm = words(call0)
+    u = ((wm[0] >> np.uint64(5)).astype(np.float64) * 67108864.0 + (wm[1] >> np.uint64(6)).astype(np.float64)) * 2.0 ** -53
+    hit = u[:, None] < np.cumsum(prob, axis=1)
+    last = (1 << n) - 1 - np.argmax((prob > 0)[:, ::-1], axis=1)
+    true = np.where(hit.any(axis=1), np.argmax(hit, axis=1), last)
+    out = true.copy()
+    for i in range(n):
+        m = 2 + i
+        flip = words(call0 + m // 4)[m % 4] < thr(i, (true >> i) & 1)
+        out = out ^ (flip.astype(np.int64) << i)
+    if ham_diag is not None:
+        return np.asarray(ham_diag, np.float64)[out]
+    pop = sum((out >> i) & 1 for i in range(n))
+    return offset + coeff * (n - 2.0 * pop)
+
+
 def replay_values(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0):
     """
     values[B, T]: trajectory t of row b (global row row0 + b) replayed gate by gate on the header's random stream (no bias).
@@ -103,15 +140,7 @@ def replay_values(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ha
     w = np.asarray(w, np.float64)
     B = x.shape[0]
     T = int(noise.shots) if noise.shots > 0 else int(noise.trajectories)
-    rows = np.repeat(np.arange(B, dtype=np.uint64) + np.uint64(row0), T)
-    trajs = np.tile(np.arange(T, dtype=np.uint64), B)
-    key = (int(noise.seed) & 0xFFFFFFFF, int(noise.seed) >> 32)
-    cache = {}
-
-    def words(c):
-        if c not in cache:
-            cache[c] = philox4x32((np.uint64(c), trajs, rows & M32, rows >> np.uint64(32)), key)
-        return cache[c]
+    words = stream(B, T, row0, noise.seed)
 
     def draw(loc, p, two):
         wd = words(loc // 2)
@@ -160,23 +189,8 @@ def replay_values(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ha
         off, h = _readout_weights(n, offset, coeff, ham_diag, float(noise.readout))
         vals = off + prob @ h
     else:
-        cm = (loc + 1) // 2
-        wm = words(cm)
-        u = ((wm[0] >> np.uint64(5)).astype(np.float64) * 67108864.0 + (wm[1] >> np.uint64(6)).astype(np.float64)) * 2.0 ** -53
-        cdf = np.cumsum(prob, axis=1)                        # index order, fp64
-        hit = u[:, None] < cdf
-        last = (1 << n) - 1 - np.argmax((prob > 0)[:, ::-1], axis=1)
-        out = np.where(hit.any(axis=1), np.argmax(hit, axis=1), last)
         thr = np.uint64(threshold(noise.readout))
-        for i in range(n):
-            m = 2 + i
-            flip = words(cm + m // 4)[m % 4] < thr
-            out = out ^ (flip.astype(np.int64) << i)
-        if ham_diag is not None:
-            vals = np.asarray(ham_diag, np.float64)[out]
-        else:
-            pop = sum((out >> i) & 1 for i in range(n))
-            vals = offset + coeff * (n - 2.0 * pop)
+        vals = shot_values(prob, words, (loc + 1) // 2, n, lambda i, bit: thr, offset, coeff, ham_diag)    # prob as it is
     return vals.reshape(B, T)
 
 
