@@ -608,8 +608,9 @@ int    qhea_model_train_steps_noisy_device_exact(const qhea_model_desc* desc, in
  *      the blocks-of-64 Hillis-Steele scan of qhea_model_forward_noisy_wide; if there is none, the last k with p_k > 0.
  * No floating-point atomics; results are bitwise reproducible and independent of the batch, the grid and the chunking.
  * Scope: n = 2..9, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.  Out of scope: n = 10..12
- * (QHEA_EUNSUPPORTED: with the state in LDS every damping site would cost a workgroup-wide reduction and a pass; an LDS variant
- * can be added later); gradients and training through trajectories; thermal population, crosstalk and routing, as above.
+ * (QHEA_EUNSUPPORTED here: with the state in LDS the sites are laid out differently, and that range is
+ * qhea_model_forward_noisy_device_wide below); gradients and training through trajectories; thermal population, crosstalk and
+ * routing, as above.
  * Errors, all before anything is launched, outputs untouched: QHEA_EINVAL for the cases of
  * qhea_model_forward_noisy_device_exact (by the same code) and for a bad sampling record (NULL, shots < 0, trajectories < 1 in
  * expectation mode, more than 2^32 - 1 values per row); then QHEA_EUNSUPPORTED for n >= 10; then the errors of
@@ -632,6 +633,42 @@ int    qhea_model_forward_noisy_device(const qhea_model_desc* desc, int64_t row0
                                        const qhea_device_noise* dn /*HOST*/, const qhea_sampling* sampling /*HOST*/,
                                        double* pred /*DEVICE [B]*/, double* stderr_out /*DEVICE [B] or NULL*/,
                                        void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * qhea_model_forward_noisy_device for n = 10..12, where the state lives in LDS (one workgroup of 2^(n-4) threads per tile of 64
+ * trajectories, the layout of qhea_model_forward_noisy_wide).  Model, unravelling, random stream (calls, words, counter, shot
+ * mode's continuation from call C), estimators and stderr_out are those of qhea_model_forward_noisy_device, word for word; the
+ * two calls answer for disjoint qubit counts.  What differs:
+ * Scope: n = 10..12; n <= 9 returns QHEA_EUNSUPPORTED (qhea_model_noisy_device_wide_workspace_bytes: 0).
+ * Errors: those of qhea_model_forward_noisy_device in its order, with "n <= 9" in the place of "n >= 10".
+ * Summation, each order a function of n and the number of values per row only:
+ *   1. tiles of 64 trajectories in trajectory order, a row's tile sums added in tile order (the finishing kernel);
+ *   2. the masked sum M of a damping site.  Thread t of the 2^(n-4) holds, in the pass where the site sits, the 16 amplitudes
+ *      k = (t >> A) << (A + 4) | (t & (2^A - 1)) | J << A, J = 0..15, of the state as it is stored (a sub-layer's state keeps
+ *      the labels it had before the CNOT ring until the ring's last slot; sampled Paulis and fired jumps are carried as a
+ *      frame): A = 4 floor(q / 4) for site ENC_q / ROT_q, except in the last pass of n = 10 and n = 11, which holds bits
+ *      n - 4 .. n - 1 (A = 6: q = 8, 9; A = 7: q = 8, 9, 10); A = n - 4 for the 2 n sites of the ring.  The masked terms are
+ *      added in the order J = 0..15 (zero where the wire reads |0>), then over the 64 lanes of a wave by the xor butterfly,
+ *      offsets 32, .., 1, then the n = 11: 2, n = 12: 4 waves in wave order.  Every site has its own sum: the TGT / CTL pair
+ *      of a slot shares none;
+ *   3. read-out: value = (sum_k p_k h'(k)) / (sum_k p_k) + offset term; thread t adds the 16 basis states 16 t .. 16 t + 15 in
+ *      index order, then the butterfly and the waves as in 2, both sums; h' is built as for n = 2..9;
+ *   4. shot mode: the first k with u S < cdf[k], S = sum_k p_k as in 3, else the last k with p_k > 0; cdf[k]: chunks of 16
+ *      summed in index order, a Hillis-Steele scan of the chunk sums over each wave (distances 1, 2, .., 32), wave totals added
+ *      in wave order -- the cdf of qhea_model_forward_noisy_wide for n = 10..12.
+ * No floating-point atomics; results are bitwise reproducible and independent of the batch, the grid and the chunking.
+ * Launches: the prep kernel, one kernel that writes this call's table of per-site constants (and expectation mode's h') into the
+ * workspace, the trajectory kernel, the finishing kernel of qhea_model_forward_noisy; a linear chain, no allocation, no
+ * synchronisation (hipGraph-capturable).
+ */
+/* DEVICE scratch bytes for qhea_model_forward_noisy_device_wide on `batch` rows (0 on a bad descriptor or sampling record, or n <= 9). */
+size_t qhea_model_noisy_device_wide_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling);
+int    qhea_model_forward_noisy_device_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                            const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                            const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                            const qhea_device_noise* dn /*HOST*/, const qhea_sampling* sampling /*HOST*/,
+                                            double* pred /*DEVICE [B]*/, double* stderr_out /*DEVICE [B] or NULL*/,
+                                            void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the

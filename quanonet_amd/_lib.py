@@ -42,7 +42,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact',
            'qhea_model_device_noisy_grad_workspace_bytes', 'qhea_model_device_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_device_exact', 'qhea_model_train_steps_noisy_device_exact',
-           'qhea_device_noise_jump_tables', 'qhea_model_noisy_device_workspace_bytes', 'qhea_model_forward_noisy_device']
+           'qhea_device_noise_jump_tables', 'qhea_model_noisy_device_workspace_bytes', 'qhea_model_forward_noisy_device',
+           'qhea_model_noisy_device_wide_workspace_bytes', 'qhea_model_forward_noisy_device_wide']
 
 
 class ModelDesc(ctypes.Structure):
@@ -79,7 +80,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 560           # 0.5.6: + qhea_model_forward_noisy_device (quantum-jump trajectories under a device noise model)
+MIN_LIB_VERSION = 570           # 0.5.7: + qhea_model_forward_noisy_device_wide (device-noise trajectories at n = 10..12)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -249,6 +250,10 @@ def load():
     lib.qhea_model_forward_noisy_device.restype = ctypes.c_int
     lib.qhea_model_forward_noisy_device.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, dp, dp, dp, dp, dnp, spp, dp, dp, vp,
                                                     ctypes.c_size_t, vp]
+    lib.qhea_model_noisy_device_wide_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_device_wide_workspace_bytes.argtypes = lib.qhea_model_noisy_device_workspace_bytes.argtypes
+    lib.qhea_model_forward_noisy_device_wide.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy_device_wide.argtypes = lib.qhea_model_forward_noisy_device.argtypes
     lib.qhea_model_device_noisy_grad_workspace_bytes.restype = ctypes.c_size_t
     lib.qhea_model_device_noisy_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
     lib.qhea_model_device_noisy_log10_amplification.restype = ctypes.c_double
@@ -864,27 +869,47 @@ def model_noisy_device_workspace_bytes(desc, batch, sampling):
     return int(load().qhea_model_noisy_device_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(sampling)))
 
 
-def model_forward_noisy_device(desc, branch, trunk, params, noise, sampling, row0=0, ham_diag=None, out=None, stderr=None):
-    """
-    qhea_model_forward_noisy_device on all rows of branch / trunk in ONE call: (pred[B], stderr[B] or None) from quantum-jump
-    trajectories under `noise` (a DeviceNoiseParams) with the estimator `sampling` (a SamplingParams); row0 is the global index
-    of the first row (the random streams are keyed by it).  n = 2..9: raises Unsupported for n >= 10 and QheaError for a bad
-    noise setting or sampling record -- in both cases before anything is launched.
-    """
+def _forward_noisy_device(entry, sizer, why, desc, branch, trunk, params, noise, sampling, row0, ham_diag, out, stderr):
     lib = load()
     B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(stderr, 'stderr', (B,))
     pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
-    ws = _sized_ws(branch.device, lib.qhea_model_noisy_device_workspace_bytes, ctypes.byref(desc), int(B), ctypes.byref(sampling))
+    ws = _sized_ws(branch.device, getattr(lib, sizer), ctypes.byref(desc), int(B), ctypes.byref(sampling))
     with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_forward_noisy_device(ctypes.byref(desc), int(row0), int(B), _ptr(branch), _ptr(trunk), _ptr(params),
-                                                 _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling), _ptr(pred),
-                                                 _ptr(stderr), _ptr(ws), 0 if ws is None else ws.numel(),
-                                                 _stream(branch.device))
+        rc = getattr(lib, entry)(ctypes.byref(desc), int(row0), int(B), _ptr(branch), _ptr(trunk), _ptr(params), _ptr(ham_diag),
+                                 ctypes.byref(noise), ctypes.byref(sampling), _ptr(pred), _ptr(stderr), _ptr(ws),
+                                 0 if ws is None else ws.numel(), _stream(branch.device))
     if rc == -2:
-        raise Unsupported("qhea_model_forward_noisy_device: unsupported circuit (n >= 10)")
-    _check(rc, 'qhea_model_forward_noisy_device')
+        raise Unsupported(f"{entry}: unsupported circuit ({why})")
+    _check(rc, entry)
     return pred, stderr
+
+
+def model_forward_noisy_device(desc, branch, trunk, params, noise, sampling, row0=0, ham_diag=None, out=None, stderr=None):
+    """
+    qhea_model_forward_noisy_device on all rows of branch / trunk in ONE call: (pred[B], stderr[B] or None) from quantum-jump
+    trajectories under `noise` (a DeviceNoiseParams) with the estimator `sampling` (a SamplingParams); row0 is the global index
+    of the first row (the random streams are keyed by it).  n = 2..9: raises Unsupported for n >= 10 (that range is
+    model_forward_noisy_device_wide's) and QheaError for a bad noise setting or sampling record -- in both cases before anything
+    is launched.
+    """
+    return _forward_noisy_device('qhea_model_forward_noisy_device', 'qhea_model_noisy_device_workspace_bytes', 'n >= 10', desc,
+                                 branch, trunk, params, noise, sampling, row0, ham_diag, out, stderr)
+
+
+def model_noisy_device_wide_workspace_bytes(desc, batch, sampling):
+    """qhea_model_noisy_device_wide_workspace_bytes: 0 for a bad descriptor or sampling record (a SamplingParams), or n <= 9."""
+    return int(load().qhea_model_noisy_device_wide_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(sampling)))
+
+
+def model_forward_noisy_device_wide(desc, branch, trunk, params, noise, sampling, row0=0, ham_diag=None, out=None, stderr=None):
+    """
+    model_forward_noisy_device for n = 10..12 (qhea_model_forward_noisy_device_wide: the same model, unravelling and random
+    stream, the state in LDS).  Raises Unsupported for n <= 9 and QheaError for a bad noise setting or sampling record -- in both
+    cases before anything is launched.
+    """
+    return _forward_noisy_device('qhea_model_forward_noisy_device_wide', 'qhea_model_noisy_device_wide_workspace_bytes', 'n <= 9',
+                                 desc, branch, trunk, params, noise, sampling, row0, ham_diag, out, stderr)
 
 
 def model_exact_noisy_log10_amplification(desc, noise):

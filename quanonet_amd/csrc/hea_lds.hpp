@@ -1,6 +1,7 @@
 // hea_lds.hpp -- the pass machinery of the workgroup-resident kernels (n = 10..12, state in LDS): the per-pass thread layout,
 // the LDS index swizzle, the CNOT ring as an index map and the load / gate / store of a thread's 2^LG amplitudes.  Shared by
-// hea_lds.hip (forward and backward sweeps) and hea_noise_wide.hip (noisy trajectories); hea_lds.hip explains the scheme.
+// hea_lds.hip (forward and backward sweeps), hea_noise_wide.hip and hea_noise_device_wide.hip (noisy trajectories); hea_lds.hip
+// explains the scheme.
 #pragma once
 #include "hea_device.hpp"
 

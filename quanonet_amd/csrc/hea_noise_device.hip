@@ -41,7 +41,7 @@
 namespace qhea {
 namespace {
 
-constexpr int kJumpMaxWires = 9;            // n = 10..12: the state would live in LDS and every site would cost a workgroup pass
+constexpr int kJumpMaxWires = 9;            // n = 10..12: the state lives in LDS, hea_noise_device_wide.hip
 constexpr int kJumpWaves = 4;               // waves per workgroup (independent; no LDS, no barrier)
 
 struct DevTable {                           // 8-byte words only: device_tables_kernel copies it word by word
@@ -56,34 +56,6 @@ struct DevTable {                           // 8-byte words only: device_tables_
     unsigned L, pauli;
 };
 constexpr int kTableWords = (int)(sizeof(DevTable) / 8);
-
-// folded duration of site `site` on wire q (the table of the header)
-inline double site_duration(int n, const qhea_device_noise* dn, int site, int q) {
-    const bool idle = dn->idle != 0;
-    switch (site) {
-        case kEnc: return dn->t_rx;
-        case kRot: return dn->t_rot + (idle && q >= 1 ? (q - 1) * dn->t_cx : 0.0);
-        case kCtl: return dn->t_cx;
-        default:   return idle ? (q == 0 ? n - 1 : n - q) * dn->t_cx : dn->t_cx;
-    }
-}
-
-// (gamma, pz) of relaxation for time t: amplitude damping gamma, then Z with probability pz so that the off-diagonals end at
-// exp(-t / T2) in total
-inline void jump_pair(double t, double T1, double T2, double& gamma, double& pz) {
-    const double x1 = std::isinf(T1) ? 0.0 : t / T1, x2 = std::isinf(T2) ? 0.0 : t / T2;
-    gamma = 1.0 - exp(-x1);
-    double f = gamma < 1.0 ? exp(-x2) / sqrt(1.0 - gamma) : 0.0;
-    if (f > 1.0) f = 1.0;                                                // T2 = 2 T1 to rounding
-    pz = 0.5 * (1.0 - f);
-}
-
-inline void jump_tables(int n, const qhea_device_noise* dn, double* jump) {
-    for (int site = 0; site < 4; ++site)
-        for (int q = 0; q < n; ++q)
-            jump_pair(site_duration(n, dn, site, q), dn->t1[q], dn->t2[q], jump[((size_t)site * n + q) * 2],
-                      jump[((size_t)site * n + q) * 2 + 1]);
-}
 
 // ---- device helpers of this unit ----------------------------------------------------------------------------------------------------
 
@@ -538,29 +510,6 @@ inline qhea_noise sampling_as_noise(const qhea_sampling* s) {
     return nz;
 }
 
-void fill_table(int n, const qhea_device_noise* dn, DevTable& t, bool& any) {
-    double flat[4 * kJumpMaxWires * 2];                                  // [4][n][2]
-    jump_tables(n, dn, flat);
-    auto jump = [&](int site, int q, int k) { return flat[((size_t)site * n + q) * 2 + k]; };
-    any = false;
-    for (int q = 0; q < n; ++q) {
-        t.cthr[q][0] = threshold(dn->p1[q]);         t.cthr[q][1] = threshold(jump(kEnc, q, 1));
-        t.cthr[n + q][0] = threshold(dn->p1[q]);     t.cthr[n + q][1] = threshold(jump(kRot, q, 1));
-        t.cthr[2 * n + 2 * q][0] = threshold(dn->p2[q]);                 // slot q: the pair, and TGT of wire q
-        t.cthr[2 * n + 2 * q][1] = threshold(jump(kTgt, q, 1));
-        t.cthr[2 * n + 2 * q + 1][0] = 0;                                // ... CTL of wire (q + 1) mod n
-        t.cthr[2 * n + 2 * q + 1][1] = threshold(jump(kCtl, (q + 1) % n, 1));
-        for (int site = 0; site < 4; ++site) {
-            t.gs[site][q][0] = jump(site, q, 0);
-            t.gs[site][q][1] = sqrt(1.0 - jump(site, q, 0));
-            any = any || jump(site, q, 0) > 0.0;
-        }
-        t.rthr[q][0] = threshold(dn->readout01[q]); t.rthr[q][1] = threshold(dn->readout10[q]);
-        t.rd[q][0] = dn->readout01[q]; t.rd[q][1] = dn->readout10[q];
-    }
-    for (int c = 0; c < 4 * n; ++c) any = any || t.cthr[c][0] || t.cthr[c][1];
-}
-
 }  // namespace
 }  // namespace qhea
 
@@ -600,12 +549,10 @@ int qhea_model_forward_noisy_device(const qhea_model_desc* desc, int64_t row0, i
     if (rc != QHEA_OK || t.c.empty) return rc;
     const int n = t.c.mi.n;
     NoiseArgs& a = t.a;
-    unsigned calls = 0;                                                  // C of the header: n + 3 n ld per block
-    for (int g = 0; g < 2; ++g) calls += (unsigned)t.c.mi.nb[g] * (unsigned)(n + 3 * n * t.c.mi.ld[g]);
-    a.L = calls;                                                         // shot mode continues from call C
+    a.L = jump_calls(n, t.c.mi.nb, t.c.mi.ld);                           // shot mode continues from call C
     DevTable tb{};
     bool any;
-    fill_table(n, dn, tb, any);
+    fill_jump_table(n, dn, tb, any);
     tb.off = a.off; tb.co = a.co; tb.diag = ham_diag; tb.L = a.L; tb.pauli = (unsigned)a.pauli;
     a.thr1 = any ? 1 : 0;                                                // an ideal setting draws nothing
     DevTable* tab = reinterpret_cast<DevTable*>(t.extra);

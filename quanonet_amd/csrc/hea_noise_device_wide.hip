@@ -1,0 +1,517 @@
+// hea_noise_device_wide.hip -- qhea_model_forward_noisy_device_wide: the quantum-jump trajectories of hea_noise_device.hip under
+// the calibrated device noise model for n = 10..12, where the state lives in LDS.  Same quantity, same unravelling, same random
+// stream (include/quanonet_hea.h); what differs is where the state lives and, with it, the order of the floating-point sums,
+// which the header states.  tests/device_traj_wide_reference.py restates the formulation in numpy and
+// tests/test_device_traj_wide_abi.py proves it against the gate-by-gate replay without a GPU.
+//
+// Layout: that of noisy_wide_lds_kernel (hea_noise_wide.hip).  One workgroup of 2^(n-4) threads per (row, tile of kTile
+// trajectories) work item, the trajectories one after another, the state in LDS behind phys<4>, a gate layer in the three passes
+// of hea_lds.hpp (16 amplitudes per thread and pass) with the ring folded into the last pass's scatter.
+//
+// Every relaxation site is a DIAGONAL operation on the 16 amplitudes a thread holds in a pass that exists anyway:
+//   * Jumps go into the frame.  |0><1|_w = X_w Pi1_w: a fired jump zeroes the amplitudes whose wire w reads |0>, sets N2 = M and
+//     toggles bit w of the frame's X mask; no exchange, no pass.  No jump scales the |1> half by sqrt(1 - gamma), N2 -= gamma M.
+//     Dephasing toggles a Z bit.  The frame therefore depends on the jump decisions: every thread evolves it (the values are
+//     workgroup-uniform and live in scalar registers), wave 0 cannot build it ahead of the layer as in hea_noise_wide.hip.
+//   * The stored state keeps its pre-ring labels for the whole sub-layer.  Behind CNOT slot j the logical bit of a wire is a
+//     parity of at most three stored index bits (ring_site_mask below), XORed with the frame's X bit of the wire: "reads |1>" is
+//     parity(tp & m) ^ parity(J & (m >> A)) ^ x_w for local index J, the middle term a compile-time constant per J.
+//   * ENC_q and ROT_q run inside the pass that holds qubit q in registers, right behind gate q; the 2 n ring sites run in the
+//     last pass behind its rotations and before the scatter store, on the same registers.  The frame is pushed through each CNOT
+//     (x_t ^= x_c, z_c ^= z_t) and applied by the store: an XOR of phys(x) on the store base, a sign from the pulled-back z.
+// A site with gamma > 0 costs one masked sum over the thread's 16 |v|^2, one workgroup reduction and one select-scale; gamma = 0
+// skips it by a scalar branch (a table entry), so the default setting runs the ideal circuit bit for bit.
+//
+// Choices:
+//   * |v|^2 is recomputed at every site, not kept beside v: 16 more doubles would not fit beside the 64 of v and the gate.
+//   * Every site has its own reduction; the TGT / CTL pair of a slot does not share one.  The summation order of a site is then
+//     one rule for all four kinds of site.
+//   * The butterfly is pair_sum (DPP and permlane swaps, hea_device.hpp), offsets 32 .. 1, as in hea_noise_device.hip.
+// Reduction: the thread's masked terms in local-index order, the butterfly over the wave, then the waves in order through LDS
+// slots.  n = 10 is one wave and needs no barrier; n = 11, 12 write one of two alternating slot sets, so a site costs ONE
+// barrier: a wave can only reach the site after next -- which writes this set again -- through the next site's barrier, which
+// every wave passes after it has read this one.  The wave-local relaxation between the first two passes (wave_local_passes,
+// hea_lds.hpp) stays in the code but cannot hold where those passes contain sites with gamma > 0 at n = 11, 12: the site's
+// reduction is a workgroup barrier anyway.
+//
+// Philox: lane c of wave 0 computes call c of the segment -- the n ENC calls of a block, or the 3 n calls of a sub-layer (ROT
+// 0..n-1, then the ring's 2 n) -- and reduces it to a code (Pauli in bits 0..3, dephasing in bit 4) and the jump's word, as
+// site_draws of hea_noise_device.hip; both go to LDS scratch in front of a barrier that opens the layer.  The per-call thresholds
+// and per-site (gamma, sqrt(1 - gamma)) live in a table of this unit's own in the workspace (WideDevTable, 12 wires), filled by
+// one prep launch and read by wave-uniform addresses where a site uses them.
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "hea_device_noise.hpp"
+#include "hea_lds.hpp"
+#include "hea_noise_traj.hpp"
+
+namespace qhea {
+namespace {
+
+constexpr int kLG = 4;                      // gate qubits per pass, as noisy_wide_lds_kernel
+constexpr int kWideWires = QHEA_MAX_QUBITS; // 12
+
+struct WideDevTable {                       // 8-byte words only: wide_tables_kernel copies it word by word
+    unsigned long long cthr[4 * kWideWires][2];     // call c of a block's template: (Pauli threshold, dephasing threshold)
+    double gs[4][kWideWires][2];                    // [site][wire] (gamma, sqrt(1 - gamma))
+    unsigned long long rthr[kWideWires][2];         // readout thresholds (01, 10) per bit
+    double rd[kWideWires][2];                       // readout01, readout10 per bit
+    double off, co;
+    const double* diag;
+    unsigned L, pauli;
+};
+constexpr int kWideTableWords = (int)(sizeof(WideDevTable) / 8);
+static_assert(kWideTableWords <= 256, "wide_tables_kernel copies one word per thread");
+
+// In FRONT of the state: at n = 12 the state alone fills the 64 KiB an LDS instruction's immediate offset reaches, and behind it
+// every scratch word would need its address in a register (36 draws: scalar registers that spill inside the sub-layer loop)
+struct JumpScratch {
+    double red[2][4];                       // a site's per-wave sums, two alternating sets
+    double rsum[2][4];                      // the read-out's per-wave sums (numerator / cdf, total)
+    int lo[4], hi[4];                       // per-wave first hit / last positive index
+    unsigned code[3 * kWideWires], w3[3 * kWideWires];   // the segment's draws
+    int m01, m10;                           // shot mode: the bits that flip when read as 0 / as 1
+    double u;
+};
+constexpr size_t kScratchBytes = 512;       // a multiple of the LDS bank period: the swizzle of phys<4> sees the same banks
+static_assert(sizeof(JumpScratch) <= kScratchBytes, "the state starts behind the scratch");
+
+// The stored-bit mask of the wire of a ring site behind slot J, the state in pre-ring labels (CNOT(c = J + 1 -> t = J) applied
+// for slots 0..J): TGT is wire J, CTL wire (J + 1) mod N
+template <int N, int J, bool TGT>
+constexpr int ring_site_mask() {
+    if (TGT) return J < N - 1 ? (1 << J) | (1 << (J + 1)) : (1 << (N - 1)) | 3;
+    return J < N - 1 ? 1 << (J + 1) : 3;
+}
+
+__device__ __forceinline__ double jump_u(unsigned w3) { return ((double)w3 + 0.5) * 0x1p-32; }
+
+// (gamma, sqrt(1 - gamma)) of a site, read where the site uses it (the fence: site_pair of hea_noise_device.hip)
+__device__ __forceinline__ double2 site_pair(const WideDevTable* __restrict__ tab, int site, int q) {
+    int fence = 0;
+    asm volatile("" : "+s"(fence));
+    const double* p = &tab->gs[site][q][0] + fence;
+    return make_double2(p[0], p[1]);
+}
+
+// What every thread carries along a trajectory; all values are the same in every thread of the workgroup
+struct JumpState {
+    double n2;                              // squared norm of the stored state
+    int x, z;                               // the frame, in the labels of the circuit point reached
+    int par;                                // which slot set the next reduction writes
+};
+
+// v summed over the workgroup: the butterfly over the wave, offsets 32 .. 1, then the waves in order
+template <int NW>
+__device__ __forceinline__ double site_sum(double v, JumpScratch* sc, int& par) {
+    static_rfor<0, 6>([&](auto b) { v = pair_sum<(1 << decltype(b)::value)>(v); });
+    if constexpr (NW == 1) {
+        return v;
+    } else {
+        if ((threadIdx.x & 63) == 0) sc->red[par][threadIdx.x >> 6] = v;
+        __syncthreads();
+        double tot = sc->red[par][0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) tot += sc->red[par][w];
+        par ^= 1;
+        return tot;
+    }
+}
+
+// Dephasing and damping of one site on wire W, whose |1> is the parity of the stored bits MASK; the thread holds the amplitudes
+// tp | J << A.  c, w3: the site's code and jump word; gs = (gamma, sqrt(1 - gamma)).
+template <int N, int A, int W, int MASK>
+__device__ __forceinline__ void relax_site(c2 (&v)[1 << kLG], JumpState& js, int tp, unsigned c, unsigned w3, double2 gs,
+                                           JumpScratch* sc) {
+    constexpr int M16 = 1 << kLG, ML = (MASK >> A) & (M16 - 1);
+    const double g = gs.x, s = gs.y;
+    js.z ^= (int)((c >> 4) & 1u) << W;
+    if (g > 0.0) {                                                       // workgroup-uniform: a table entry
+        const int pol = (__popc((unsigned)(tp & MASK)) + ((js.x >> W) & 1)) & 1;
+        double m = 0.0;
+        static_for<0, M16>([&](auto jj) {
+            constexpr int J = decltype(jj)::value;
+            const bool one = pol != (__builtin_popcount(J & ML) & 1);
+            m += one ? v[J].x * v[J].x + v[J].y * v[J].y : 0.0;
+        });
+        m = site_sum<LCfg<N, kLG>::NW>(m, sc, js.par);
+        const bool fire = uniform(jump_u(w3) * js.n2 < g * m);           // the same in every thread
+        if (fire) {
+            static_for<0, M16>([&](auto jj) {
+                constexpr int J = decltype(jj)::value;
+                const bool one = pol != (__builtin_popcount(J & ML) & 1);
+                v[J].x = one ? v[J].x : 0.0; v[J].y = one ? v[J].y : 0.0;
+            });
+            js.n2 = m;
+            js.x ^= 1 << W;
+        } else {
+            static_for<0, M16>([&](auto jj) {
+                constexpr int J = decltype(jj)::value;
+                const bool one = pol != (__builtin_popcount(J & ML) & 1);
+                const double f = one ? s : 1.0;
+                v[J].x *= f; v[J].y *= f;
+            });
+            js.n2 -= g * m;
+        }
+    }
+}
+
+// z' with parity(ring(k) & z) = parity(k & z'): the transposed ring, last CNOT first
+template <int N>
+__device__ __forceinline__ int ring_pull(int z) {
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) z ^= ((z >> i) & 1) << ((i + 1) % N);
+    return z;
+}
+
+// Wave 0's lanes draw the segment's calls call0 .. call0 + cnt - 1 (template entries tbase ..; RING: the calls from `ring0` on
+// alternate pair Pauli / none) into the scratch; the barrier behind it opens the layer.  a.thr1 == 0: an ideal setting.
+__device__ __forceinline__ void segment_draws(const NoiseArgs& a, const WideDevTable* __restrict__ tab, JumpScratch* sc,
+                                              unsigned call0, int tbase, int cnt, int ring0, unsigned traj, unsigned long long row) {
+    const int c = threadIdx.x;
+    if (c < cnt) {
+        unsigned code = 0, w3 = 0;
+        if (a.thr1 != 0) {
+            // the key behind a fence: without it the ten round keys of each word are loop invariants that the compiler keeps in
+            // scalar registers across the circuit loop, where they spill; behind it they are nine scalar adds per call
+            unsigned k0 = a.key0, k1 = a.key1;
+            asm volatile("" : "+s"(k0), "+s"(k1));
+            const uint4 w = philox(make_uint4(call0 + (unsigned)c, traj, (unsigned)row, (unsigned)(row >> 32)), k0, k1);
+            const unsigned long long tp = tab->cthr[tbase + c][0], tz = tab->cthr[tbase + c][1];
+            const unsigned kinds = (c >= ring0 && !((c - ring0) & 1)) ? 15u : 3u;
+            if ((unsigned long long)w.x < tp) code = 1u + (unsigned)(((unsigned long long)w.y * kinds) >> 32);
+            if ((unsigned long long)w.z < tz) code |= 16u;
+            w3 = w.w;
+        }
+        sc->code[c] = code; sc->w3[c] = w3;
+    }
+    __syncthreads();
+}
+
+// One gate layer with its sites.  SITE: kEnc (a block's encoding layer, no ring) or kRot (a sub-layer: its ring's 2 n sites sit
+// in the last pass and the ring is that pass's scatter).  The frame, the power-of-two rescale and the ring go into the last
+// pass's store.
+template <int N, int SITE, class G>
+__device__ __forceinline__ void jump_layer(double2* s, const Bases<N, kLG>& bs, int t, JumpScratch* sc,
+                                           const WideDevTable* __restrict__ tab, JumpState& js, G gate) {
+    constexpr int LG = kLG, NP = LCfg<N, LG>::NP;
+    constexpr bool RING = SITE == kRot;
+    static_for<0, NP>([&](auto p) {
+        constexpr int P = decltype(p)::value;
+        using PS = Pass<N, P, LG>;
+        const int tp = thread_part<PS::A, LG>(t);
+        c2 v[1 << LG];
+        load_group<N, PS::A, false, LG>(s, bs.plain[P], v);
+        static_for<PS::Q0, PS::Q1>([&](auto q) {
+            constexpr int Q = decltype(q)::value;
+            apply_group<Q - PS::A, LG>(v, gate(Q));
+            const unsigned c = (unsigned)uniform((int)sc->code[Q]), w3 = (unsigned)uniform((int)sc->w3[Q]);
+            js.x ^= pauli_x(c & 3u, Q); js.z ^= pauli_z(c & 3u, Q);
+            relax_site<N, PS::A, Q, (1 << Q)>(v, js, tp, c, w3, site_pair(tab, SITE, Q), sc);
+        });
+        if constexpr (P < NP - 1) {
+            store_group<N, PS::A, false, LG>(s, bs.plain[P], v);
+            pass_sync<wave_local_passes<N, LG, P, P + 1>()>();
+        } else {
+            if constexpr (RING) {
+                static_for<0, N>([&](auto jj) {                          // slot j: CNOT(c -> t), pair Pauli, TGT of t, CTL of c
+                    constexpr int J = decltype(jj)::value, CQ = (J + 1) % N, TQ = J;
+                    js.x ^= ((js.x >> CQ) & 1) << TQ;
+                    js.z ^= ((js.z >> TQ) & 1) << CQ;
+                    const unsigned c0 = (unsigned)uniform((int)sc->code[N + 2 * J]), c1 = (unsigned)uniform((int)sc->code[N + 2 * J + 1]);
+                    const unsigned u0 = (unsigned)uniform((int)sc->w3[N + 2 * J]), u1 = (unsigned)uniform((int)sc->w3[N + 2 * J + 1]);
+                    const unsigned pp = c0 & 15u;
+                    js.x ^= pauli_x(pp >> 2, CQ) | pauli_x(pp & 3u, TQ);
+                    js.z ^= pauli_z(pp >> 2, CQ) | pauli_z(pp & 3u, TQ);
+                    relax_site<N, PS::A, TQ, ring_site_mask<N, J, true>()>(v, js, tp, c0, u0, site_pair(tab, kTgt, TQ), sc);
+                    relax_site<N, PS::A, CQ, ring_site_mask<N, J, false>()>(v, js, tp, c1, u1, site_pair(tab, kCtl, CQ), sc);
+                });
+            }
+            if (js.n2 < 0x1p-200) {                                      // exact, so invisible in the result
+                static_for<0, (1 << LG)>([&](auto jj) {
+                    constexpr int J = decltype(jj)::value;
+                    v[J].x *= 0x1p100; v[J].y *= 0x1p100;
+                });
+                js.n2 *= 0x1p200;
+            }
+            __syncthreads();                               // every thread holds its amplitudes: safe to permute
+            const int px = phys<LG>(js.x), z = RING ? ring_pull<N>(js.z) : js.z;
+            if (z) {
+                const int sb = __popc((unsigned)(tp & z)), zl = (z >> PS::A) & ((1 << LG) - 1);
+                static_for<0, (1 << LG)>([&](auto jj) {
+                    constexpr int J = decltype(jj)::value;
+                    const bool neg = (sb + __popc((unsigned)(J & zl))) & 1;
+                    v[J].x = neg ? -v[J].x : v[J].x;
+                    v[J].y = neg ? -v[J].y : v[J].y;
+                });
+            }
+            store_group<N, PS::A, RING, LG>(s, (RING ? bs.ring : bs.plain[P]) ^ px, v);
+            js.x = 0; js.z = 0;
+            __syncthreads();
+        }
+    });
+}
+
+// One gate layer without sites: the X / Y basis change
+template <int N, class G>
+__device__ __forceinline__ void plain_layer(double2* s, const Bases<N, kLG>& bs, G gate) {
+    constexpr int LG = kLG, NP = LCfg<N, LG>::NP;
+    static_for<0, NP>([&](auto p) {
+        constexpr int P = decltype(p)::value;
+        using PS = Pass<N, P, LG>;
+        c2 v[1 << LG];
+        load_group<N, PS::A, false, LG>(s, bs.plain[P], v);
+        static_for<PS::Q0, PS::Q1>([&](auto q) { apply_group<decltype(q)::value - PS::A, LG>(v, gate(decltype(q)::value)); });
+        store_group<N, PS::A, false, LG>(s, bs.plain[P], v);
+        __syncthreads();
+    });
+}
+
+// the read-out's sums over a wave: the butterfly, offsets 32 .. 1 (the waves are added in order behind the caller's barrier)
+__device__ __forceinline__ double readout_butterfly(double v) {
+    static_rfor<0, 6>([&](auto b) { v = pair_sum<(1 << decltype(b)::value)>(v); });
+    return v;
+}
+
+template <int N>
+__global__ __launch_bounds__((LCfg<N, kLG>::T)) void device_traj_lds_kernel(NoiseArgs a, const WideDevTable* __restrict__ tab,
+                                                                            const double* __restrict__ hd) {
+    constexpr int LG = kLG, M = 1 << LG;
+    using L = LCfg<N, LG>;
+    extern __shared__ __attribute__((aligned(16))) char jump_lds[];
+    JumpScratch* sc = reinterpret_cast<JumpScratch*>(jump_lds);
+    double2* psi = reinterpret_cast<double2*>(jump_lds + kScratchBytes);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const long item = blockIdx.x;
+    const WorkItem wi = work_item(a, item);
+    Bases<N, LG> bs;
+    bs.init(t);
+    const double off_term = (a.shots || a.diag) ? 0.0 : a.off;
+
+    double sum = 0.0, sq = 0.0;
+    for (int tj = 0; tj < wi.tcount; ++tj) {
+        const unsigned traj = (unsigned)(wi.t0 + tj);
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            const int p = t + j * L::T;
+            psi[p] = make_double2(p == 0 ? 1.0 : 0.0, 0.0);              // |0..0>: phys(0) = 0
+        }
+        JumpState js{1.0, 0, 0, 0};
+        unsigned call = 0;
+        int s = 0, col = 0;
+        for (int g = 0; g < 2; ++g) {
+            for (int b = 0; b < a.nb[g]; ++b) {
+                segment_draws(a, tab, sc, call, 0, N, N, traj, wi.row);  // its barrier also covers the initial state
+                jump_layer<N, kEnc>(psi, bs, t, sc, tab, js, [&](int q) { return rx_su2(wi.csr[col + q]); });
+                col += N; call += N;
+                for (int l = 0; l < a.ld[g]; ++l, ++s) {
+                    segment_draws(a, tab, sc, call, N, 3 * N, N, traj, wi.row);
+                    jump_layer<N, kRot>(psi, bs, t, sc, tab, js, [&](int q) { return a.gates[2 * ((s + 1) * N + q)]; });
+                    call += 3 * N;
+                }
+            }
+        }
+        if (a.pauli != QHEA_PAULI_Z) {                                   // same probabilities as H / H S^dagger
+            constexpr double kR = 0.70710678118654752440;
+            const double4 ub = a.pauli == QHEA_PAULI_X ? make_double4(kR, 0.0, kR, 0.0) : make_double4(kR, 0.0, 0.0, -kR);
+            plain_layer<N>(psi, bs, [&](int) { return ub; });
+        }
+        if (a.shots && wave == 0) {
+            // calls L .. L + 3: u, then per bit the flip words against both thresholds (the outcome picks the direction)
+            const int j = lane & 3;
+            const uint4 w = philox(make_uint4(a.L + (unsigned)j, traj, (unsigned)wi.row, (unsigned)(wi.row >> 32)), a.key0, a.key1);
+            const unsigned wd[4] = {w.x, w.y, w.z, w.w};
+            int m01 = 0, m10 = 0;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const int i = 4 * j + h - 2;
+                if (i >= 0 && i < N) {
+                    if ((unsigned long long)wd[h] < tab->rthr[i][0]) m01 |= 1 << i;
+                    if ((unsigned long long)wd[h] < tab->rthr[i][1]) m10 |= 1 << i;
+                }
+            }
+            m01 = __shfl(m01, 0) | __shfl(m01, 1) | __shfl(m01, 2) | __shfl(m01, 3);
+            m10 = __shfl(m10, 0) | __shfl(m10, 1) | __shfl(m10, 2) | __shfl(m10, 3);
+            if (t == 0) { sc->m01 = m01; sc->m10 = m10; sc->u = unit_double(w.x, w.y); }
+        }
+        // thread t reads the 16 consecutive basis states 16 t .. 16 t + 15
+        c2 v[M];
+        load_group<N, 0, false, LG>(psi, bs.plain[0], v);
+        double pk[M], part = 0.0;
+#pragma unroll
+        for (int j = 0; j < M; ++j) { pk[j] = v[j].x * v[j].x + v[j].y * v[j].y; part += pk[j]; }
+        double val;
+        if (!a.shots) {
+            double num = 0.0;
+#pragma unroll
+            for (int j = 0; j < M; ++j) num += pk[j] * hd[(t << LG) | j];
+            num = readout_butterfly(num);
+            double tot = readout_butterfly(part);
+            if constexpr (L::NW > 1) {
+                if (lane == 0) { sc->rsum[0][wave] = num; sc->rsum[1][wave] = tot; }
+                __syncthreads();
+                num = sc->rsum[0][0]; tot = sc->rsum[1][0];
+#pragma unroll
+                for (int w = 1; w < L::NW; ++w) { num += sc->rsum[0][w]; tot += sc->rsum[1][w]; }
+            }
+            val = num / tot + off_term;
+        } else {
+            double c[M];
+            c[0] = pk[0];
+#pragma unroll
+            for (int j = 1; j < M; ++j) c[j] = c[j - 1] + pk[j];
+            const double inc = wave_scan(c[M - 1], lane);
+            double before = __shfl_up(inc, 1);
+            if (lane == 0) before = 0.0;
+            double tot = readout_butterfly(part);
+            if (lane == 63) sc->rsum[0][wave] = inc;
+            if (lane == 0) sc->rsum[1][wave] = tot;
+            __syncthreads();                                             // rsum, u, the flip masks
+            double below = 0.0;
+            for (int w = 0; w < wave; ++w) below += sc->rsum[0][w];
+            below += before;
+            if constexpr (L::NW > 1) {
+                tot = sc->rsum[1][0];
+#pragma unroll
+                for (int w = 1; w < L::NW; ++w) tot += sc->rsum[1][w];
+            }
+            const double ut = sc->u * tot;
+            int lo = INT_MAX, hi = -1;
+#pragma unroll
+            for (int j = M - 1; j >= 0; --j) {
+                if (ut < below + c[j]) lo = (t << LG) | j;
+                if (pk[j] > 0.0 && hi < 0) hi = (t << LG) | j;
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const int l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+                lo = l2 < lo ? l2 : lo;
+                hi = h2 > hi ? h2 : hi;
+            }
+            if (lane == 0) { sc->lo[wave] = lo; sc->hi[wave] = hi; }
+            __syncthreads();
+            for (int w = 0; w < L::NW; ++w) {
+                lo = sc->lo[w] < lo ? sc->lo[w] : lo;
+                hi = sc->hi[w] > hi ? sc->hi[w] : hi;
+            }
+            const int out = lo != INT_MAX ? lo : (hi < 0 ? 0 : hi);
+            val = shot_value<N>(a.diag, a.off, a.co, out ^ ((out & sc->m10) | (~out & sc->m01 & (L::DIM - 1))));
+        }
+        sum += val; sq += val * val;
+        __syncthreads();                                                 // psi and the scratch are rewritten
+    }
+    if (t == 0) a.partial[item] = make_double2(sum, sq);
+}
+
+// ---- prep: the table, and expectation mode's read-out weights ------------------------------------------------------------------
+
+// One workgroup.  Copies the table into the workspace and, with `buf`, builds h[k] of expectation mode in half (n - 1) & 1 of
+// buf[2 * 2^n] exactly as device_tables_kernel of hea_noise_device.hip does: co sum_i (bit_i(k) ? -(1 - 2 r10_i) : 1 - 2 r01_i)
+// in the order i = 0..n-1, or ham_diag under the readout confusion bit by bit, stage i writing half i & 1.
+__global__ __launch_bounds__(256) void wide_tables_kernel(WideDevTable t, WideDevTable* __restrict__ out,
+                                                          const double* __restrict__ diag, double co, int n,
+                                                          double* __restrict__ buf) {
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&t);
+    if ((int)threadIdx.x < kWideTableWords) reinterpret_cast<unsigned long long*>(out)[threadIdx.x] = src[threadIdx.x];
+    if (!buf) return;
+    const int D = 1 << n;
+    if (!diag) {
+        double* dst = buf + (size_t)((n - 1) & 1) * D;
+        for (int k = threadIdx.x; k < D; k += 256) {
+            double h = 0.0;
+            for (int i = 0; i < n; ++i) h += (k >> i) & 1 ? -(1.0 - 2.0 * t.rd[i][1]) : 1.0 - 2.0 * t.rd[i][0];
+            dst[k] = co * h;
+        }
+        return;
+    }
+    const double* from = diag;
+    for (int i = 0; i < n; ++i) {
+        double* dst = buf + (size_t)(i & 1) * D;
+        for (int k = threadIdx.x; k < D; k += 256) {
+            const double e = (k >> i) & 1 ? t.rd[i][1] : t.rd[i][0];
+            dst[k] = (1.0 - e) * from[k] + e * from[k ^ (1 << i)];
+        }
+        __syncthreads();
+        from = dst;
+    }
+}
+
+template <int N>
+int launch_traj_lds(const NoiseArgs& a, const WideDevTable* tab, const double* hd, hipStream_t st) {
+    using L = LCfg<N, kLG>;
+    constexpr size_t smem = kScratchBytes + L::STATE_BYTES;
+    // every launch: the attribute is per device, and a process may drive more than one
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(device_traj_lds_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)smem) != hipSuccess)
+        return QHEA_ELAUNCH;
+    hipLaunchKernelGGL(device_traj_lds_kernel<N>, dim3((unsigned)(a.B * a.tiles)), dim3(L::T), smem, st, a, tab, hd);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
+int launch_device_traj_wide(const NoiseArgs& a, int n, const WideDevTable* tab, const double* hd, hipStream_t st) {
+    switch (n) {
+        case 10: return launch_traj_lds<10>(a, tab, hd, st);
+        case 11: return launch_traj_lds<11>(a, tab, hd, st);
+        case 12: return launch_traj_lds<12>(a, tab, hd, st);
+        default: return QHEA_EUNSUPPORTED;
+    }
+}
+
+// the uniform units' layout with the read-out region of the wide ones, then the table
+constexpr TrajUnit kJumpWideUnit{10, QHEA_MAX_QUBITS, true, sizeof(WideDevTable)};
+
+inline qhea_noise sampling_as_noise(const qhea_sampling* s) {
+    qhea_noise nz{};
+    nz.shots = s->shots; nz.trajectories = s->trajectories; nz.seed = s->seed;
+    return nz;
+}
+
+}  // namespace
+}  // namespace qhea
+
+using namespace qhea;
+
+extern "C" {
+
+size_t qhea_model_noisy_device_wide_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling) {
+    if (!sampling) return 0;
+    const qhea_noise nz = sampling_as_noise(sampling);
+    return traj_workspace_bytes(kJumpWideUnit, desc, batch, &nz);
+}
+
+int qhea_model_forward_noisy_device_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
+                                         const double* trunk, const double* params, const double* ham_diag,
+                                         const qhea_device_noise* dn, const qhea_sampling* sampling, double* pred,
+                                         double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
+    // as qhea_model_forward_noisy_device: the device setting against the model's n, then the shared checks
+    ModelInfo probe;
+    int rc = model_info(desc, probe);
+    if (rc != QHEA_OK) return rc;
+    rc = device_noise_check(probe.n, dn);
+    if (rc != QHEA_OK) return rc;
+    if (!sampling) return QHEA_EINVAL;
+    const qhea_noise nz = sampling_as_noise(sampling);
+    TrajCall t;
+    rc = traj_open(kJumpWideUnit, desc, row0, batch, branch, trunk, params, ham_diag, &nz, pred, workspace, workspace_bytes, stream,
+                   t);
+    if (rc != QHEA_OK || t.c.empty) return rc;
+    const int n = t.c.mi.n;
+    NoiseArgs& a = t.a;
+    a.L = jump_calls(n, t.c.mi.nb, t.c.mi.ld);                           // shot mode continues from call C
+    WideDevTable tb{};
+    bool any;
+    fill_jump_table(n, dn, tb, any);
+    tb.off = a.off; tb.co = a.co; tb.diag = ham_diag; tb.L = a.L; tb.pauli = (unsigned)a.pauli;
+    a.thr1 = any ? 1 : 0;                                                // an ideal setting draws nothing
+    WideDevTable* tab = reinterpret_cast<WideDevTable*>(t.extra);
+    const bool expect = !a.shots;
+    hipLaunchKernelGGL(wide_tables_kernel, dim3(1), dim3(256), 0, t.c.st, tb, tab, ham_diag, a.co, n,
+                       expect ? t.mix : static_cast<double*>(nullptr));
+    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    const double* hd = expect ? t.mix + ((size_t)((n - 1) & 1) << n) : nullptr;
+    return traj_finish(t, launch_device_traj_wide(a, n, tab, hd, t.c.st), pred, stderr_out);
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
-// hea_noise_traj.hpp -- what the noisy entry points share.  All units (hea_noise.hip, hea_noise_wide.hip, hea_noise_device.hip
-// and the density-matrix ones): the checks of a qhea_noise and the argument checks that open every call (noisy_call_check).  The
-// three trajectory units (uniform noise at n = 2..6, one amplitude per lane, and at n = 7..12, registers or LDS; device noise at
-// n = 2..9 in both layouts): the argument record, the Philox stream and its error codes, the Pauli frame bits and the frame's
+// hea_noise_traj.hpp -- what the noisy entry points share.  All units (hea_noise.hip, hea_noise_wide.hip, hea_noise_device.hip,
+// hea_noise_device_wide.hip and the density-matrix ones): the checks of a qhea_noise and the argument checks that open every call
+// (noisy_call_check).  The four trajectory units (uniform noise at n = 2..6, one amplitude per lane, and at n = 7..12, registers
+// or LDS; device noise at n = 2..9 in both register layouts and at n = 10..12 in LDS): the argument record, the Philox stream and its error codes, the Pauli frame bits and the frame's
 // application in either layout (apply_frame, frame_regs), the work item, wave_scan, u and the value of a shot, the workspace
 // layout, and the head and tail of the entry point around a unit's kernels (traj_open, traj_finish).
 #pragma once
@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <initializer_list>
 
+#include "hea_device_noise.hpp"
 #include "hea_model.hpp"
 #include "hea_train.hpp"
 
@@ -212,8 +213,6 @@ inline int noisy_call_check(const NoisyKind& k, const qhea_model_desc* desc, con
     c.ws = static_cast<char*>(workspace);
     return QHEA_OK;
 }
-
-inline unsigned long long threshold(double p) { return (unsigned long long)(p * 4294967296.0); }
 
 // everything of NoiseArgs that the descriptor and the noise setting fix; the caller adds the workspace pointers
 inline NoiseArgs noise_args(const qhea_model_desc* desc, const ModelInfo& mi, const qhea_noise* noise, const double* params,

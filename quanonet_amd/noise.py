@@ -99,7 +99,7 @@ class DeviceNoise:
     """
     The calibrated device noise model of qhea_device_noise (include/quanonet_hea.h), for the exact evaluation
     (exact_noisy_predict, evaluate_noisy(exact=True)); n <= 6, and for quantum-jump trajectories (device_noisy_predict,
-    evaluate_noisy(sampling=...)); n <= 9.
+    evaluate_noisy(sampling=...)); n <= 12.
     p1[q]: depolarizing probability after every single-qubit gate on wire q; p2[j]: two-qubit depolarizing probability after
     the CNOT of ring slot j (control (j+1) mod n -> target j); readout01[q] / readout10[q]: probability that bit q reads 1
     given 0 / 0 given 1; t1[q], t2[q]: relaxation times of wire q (math.inf: no decay; t2 <= 2 t1).  Each of the six is one
@@ -322,10 +322,11 @@ def noisy_predict(model, inputs, noise, chunk_rows=16384, row0=0):
 
 def device_noisy_predict(model, inputs, noise, sampling, chunk_rows=16384, row0=0):
     """
-    noisy_predict under a DeviceNoise (qhea_model_forward_noisy_device): (pred [N, 1], stderr [N]) from quantum-jump trajectories
+    noisy_predict under a DeviceNoise (qhea_model_forward_noisy_device for n = 2..9, qhea_model_forward_noisy_device_wide for
+    n = 10..12; the same model, unravelling and random stream): (pred [N, 1], stderr [N]) from quantum-jump trajectories
     -- sampled Paulis for the gate errors, dephasing and norm-dependent damping jumps for T1 / T2 with the ring's idle decay,
     the asymmetric readout -- with the estimator `sampling` (a Sampling: expectation mode or shots, and the seed).  Unbiased for
-    exact_noisy_predict(model, inputs, noise); n = 2..9.  Rows go in chunks of `chunk_rows`; chunk i passes its global index
+    exact_noisy_predict(model, inputs, noise); n = 2..12.  Rows go in chunks of `chunk_rows`; chunk i passes its global index
     row0 + i * chunk_rows, so the result is bitwise the same for any chunking.
     """
     if not isinstance(noise, DeviceNoise):
@@ -339,10 +340,11 @@ def device_noisy_predict(model, inputs, noise, sampling, chunk_rows=16384, row0=
     stderr = torch.empty(N, dtype=torch.float64, device=branch.device)
     chunk = max(1, int(chunk_rows))
     nz, sp = noise.params(desc.n_qubits), sampling.params()
+    forward = _lib.model_forward_noisy_device_wide if desc.n_qubits >= 10 else _lib.model_forward_noisy_device
     for s in range(0, N, chunk):
         e = min(N, s + chunk)
-        _lib.model_forward_noisy_device(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, sp,
-                                        row0=int(row0) + s, ham_diag=ham_diag, out=pred[s:e], stderr=stderr[s:e])
+        forward(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, sp, row0=int(row0) + s, ham_diag=ham_diag,
+                out=pred[s:e], stderr=stderr[s:e])
     return pred.unsqueeze(-1), stderr
 
 
