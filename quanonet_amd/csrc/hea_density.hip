@@ -100,12 +100,7 @@ template <int N>
 int launch_density(const DensArgs& a, hipStream_t st) {
     constexpr int RPW = kDensThreads / (1 << (2 * N - 4));
     constexpr size_t smem = kDensStateBytes + 2 * (1 << N) * sizeof(double);
-    // every launch: the attribute is per device, and a process may drive more than one
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(density_fwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-        return QHEA_ELAUNCH;
-    hipLaunchKernelGGL(density_fwd_kernel<N>, dim3((unsigned)((a.B + RPW - 1) / RPW)), dim3(kDensThreads), smem, st, a);
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+    return launch_dynamic_lds(density_fwd_kernel<N>, dim3((unsigned)((a.B + RPW - 1) / RPW)), dim3(kDensThreads), smem, st, a);
 }
 
 }  // namespace

@@ -308,12 +308,7 @@ int launch_density_bwd(const DensGradArgs& a, hipStream_t st) {
     constexpr int T = bwd_threads<N>(), TPR = 1 << (2 * N - 4), RPW = T / TPR, WPR = TPR > 64 ? TPR / 64 : 1;
     constexpr size_t smem = 2 * (size_t)RPW * (1 << (2 * N)) * sizeof(double2) + (1 << N) * sizeof(double) +
                             2 * WPR * kTracesPerPass * sizeof(double);
-    // every launch: the attribute is per device, and a process may drive more than one
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(density_bwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-        return QHEA_ELAUNCH;
-    hipLaunchKernelGGL(density_bwd_kernel<N>, dim3((unsigned)((a.f.B + RPW - 1) / RPW)), dim3(T), smem, st, a);
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+    return launch_dynamic_lds(density_bwd_kernel<N>, dim3((unsigned)((a.f.B + RPW - 1) / RPW)), dim3(T), smem, st, a);
 }
 
 constexpr NoisyKind kGradKind{QHEA_MIN_QUBITS, 6 /* 2 x 4^n elements per row in LDS */, false, true};

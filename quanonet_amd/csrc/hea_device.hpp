@@ -1824,4 +1824,14 @@ bool lds_supported(int n);
 int launch_lds_fwd(int n, long B, hipStream_t st, const FwdArgs& a);
 int launch_lds_bwd(int n, long B, hipStream_t st, const BwdArgs& a);
 
+// Launch of a kernel that needs more dynamic LDS than the default limit.  The limit is raised on every launch (microseconds
+// against a kernel of a millisecond): the attribute is per device, and a process may drive more than one.
+template <class... P, class... A>
+int launch_dynamic_lds(void (*k)(P...), dim3 grid, dim3 block, size_t smem, hipStream_t st, A&&... a) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        return QHEA_ELAUNCH;
+    hipLaunchKernelGGL(k, grid, block, smem, st, std::forward<A>(a)...);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
 }  // namespace qhea

@@ -92,8 +92,8 @@ inline void jump_tables(int n, const qhea_device_noise* dn, double* jump) {
                       jump[((size_t)site * n + q) * 2 + 1]);
 }
 
-// A trajectory unit's table (DevTable of hea_noise_device.hip, WideDevTable of hea_noise_device_wide.hip; they differ in the
-// wires they are sized for) from a checked setting: cthr[c] = (Pauli threshold, dephasing threshold) of call c of a block's
+// A trajectory unit's table (DevTable, WideDevTable: JumpTable<W> of hea_noise_jump.hpp, which differ in the wires they are
+// sized for) from a checked setting: cthr[c] = (Pauli threshold, dephasing threshold) of call c of a block's
 // template (ENC 0..n-1, ROT n..2n-1, slot j: 2n + 2j, + 1), gs[site][q] = (gamma, sqrt(1 - gamma)), the readout thresholds and
 // rates per bit.  any: some event can fire.
 template <class Table>

@@ -407,27 +407,16 @@ template <int N>
 int launch_fwd_n(long B, hipStream_t st, const FwdArgs& a) {
     using L = LCfg<N, kFwdLG>;
     constexpr size_t smem = L::STATE_BYTES + L::SCRATCH_BYTES;
-    // every launch (microseconds against a millisecond kernel): the attribute is per device, and a process may
-    // drive more than one
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(lds_fwd_kernel<N>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return QHEA_ELAUNCH;
-    hipLaunchKernelGGL(lds_fwd_kernel<N>, dim3((unsigned)B), dim3(L::T), smem, st, a.runs, a.B, a.E, a.cs, a.gates,
-                       a.off, a.co, a.diag, a.pauli, a.out, a.state_out, a.bias);
-    return QHEA_OK;
+    return launch_dynamic_lds(lds_fwd_kernel<N>, dim3((unsigned)B), dim3(L::T), smem, st, a.runs, a.B, a.E, a.cs, a.gates, a.off,
+                              a.co, a.diag, a.pauli, a.out, a.state_out, a.bias);
 }
 
 template <int N>
 int launch_bwd_n(long B, hipStream_t st, const BwdArgs& a) {
     using L = LCfg<N, kBwdLG>;
     constexpr size_t smem = 2 * L::STATE_BYTES + L::SCRATCH_BYTES;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(lds_bwd_kernel<N>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return QHEA_ELAUNCH;
-    hipLaunchKernelGGL(lds_bwd_kernel<N>, dim3((unsigned)B), dim3(L::T), smem, st, a.runs, a.B, a.E, a.blk, a.cs,
-                       a.gates, a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x,
-                       a.partial);
-    return QHEA_OK;
+    return launch_dynamic_lds(lds_bwd_kernel<N>, dim3((unsigned)B), dim3(L::T), smem, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates,
+                              a.off, a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x, a.partial);
 }
 
 // member launches: grid (samples, members); A = DepthArgs or QubitArgs
@@ -435,12 +424,8 @@ template <int N, class A>
 int launch_bwd_member_n(dim3 grid, hipStream_t st, const BwdArgs& a, const A& m) {
     using L = LCfg<N, kBwdLG>;
     constexpr size_t smem = 2 * L::STATE_BYTES + L::SCRATCH_BYTES;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(lds_bwd_kernel<N, A>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return QHEA_ELAUNCH;
-    hipLaunchKernelGGL((lds_bwd_kernel<N, A>), grid, dim3(L::T), smem, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates, a.off,
-                       a.co, a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x, a.partial, m);
-    return QHEA_OK;
+    return launch_dynamic_lds(lds_bwd_kernel<N, A>, grid, dim3(L::T), smem, st, a.runs, a.B, a.E, a.blk, a.cs, a.gates, a.off, a.co,
+                              a.diag, a.pauli, a.g, a.state_in, a.y, a.bias, a.inv_bt, a.out, a.grad_x, a.partial, m);
 }
 template <class A>
 int launch_bwd_member(int n, dim3 grid, hipStream_t st, const BwdArgs& a, const A& m) {

@@ -1,7 +1,8 @@
 // hea_lds.hpp -- the pass machinery of the workgroup-resident kernels (n = 10..12, state in LDS): the per-pass thread layout,
 // the LDS index swizzle, the CNOT ring as an index map and the load / gate / store of a thread's 2^LG amplitudes.  Shared by
 // hea_lds.hip (forward and backward sweeps), hea_noise_wide.hip and hea_noise_device_wide.hip (noisy trajectories); hea_lds.hip
-// explains the scheme.
+// explains the scheme.  For the two trajectory units also the Pauli frame of a segment in this layout: ring_pull (Z through the
+// ring) and store_framed (the last pass's store with the frame applied).
 #pragma once
 #include "hea_device.hpp"
 
@@ -74,6 +75,13 @@ __host__ __device__ constexpr int ring_dst(int k) {
     for (int i = 0; i < N; ++i) k ^= ((k >> ((i + 1) % N)) & 1) << i;
     return k;
 }
+// z' with parity(ring(k) & z) = parity(k & z'): the transposed ring, last CNOT first
+template <int N>
+__device__ __forceinline__ int ring_pull(int z) {
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) z ^= ((z >> i) & 1) << ((i + 1) % N);
+    return z;
+}
 // index bits of thread t for a pass with base bit A (the LG bits A..A+LG-1 are the per-thread local index j)
 template <int A, int LG>
 __device__ __forceinline__ int thread_part(int t) { return ((t >> A) << (A + LG)) | (t & ((1 << A) - 1)); }
@@ -109,6 +117,22 @@ __device__ __forceinline__ void store_group(double2* s, int base, const c2 (&v)[
         constexpr int CJ = RING ? phys<LG>(ring_dst<N>(J << A)) : phys<LG>(J << A);
         s[base ^ CJ] = make_double2(v[J].x, v[J].y);
     });
+}
+// store_group behind a Pauli frame, psi'[k] = (-1)^parity(k & z) psi[k ^ x]: px = phys(x) moves the base (k -> k ^ x is linear
+// like the ring and the swizzle), z signs the values (pulled back through the ring by the caller where RING); tp = the thread's
+// index bits in this pass (thread_part)
+template <int N, int A, bool RING, int LG>
+__device__ __forceinline__ void store_framed(double2* s, int base, int px, int z, int tp, c2 (&v)[1 << LG]) {
+    if (z) {
+        const int sb = __popc((unsigned)(tp & z)), zl = (z >> A) & ((1 << LG) - 1);
+        static_for<0, (1 << LG)>([&](auto jj) {
+            constexpr int J = decltype(jj)::value;
+            const bool neg = (sb + __popc((unsigned)(J & zl))) & 1;
+            v[J].x = neg ? -v[J].x : v[J].x;
+            v[J].y = neg ? -v[J].y : v[J].y;
+        });
+    }
+    store_group<N, A, RING, LG>(s, base ^ px, v);
 }
 template <int LBIT, int LG>
 __device__ __forceinline__ void apply_group(c2 (&v)[1 << LG], const double4& u) {

@@ -27,35 +27,21 @@
 // trajectory kernels read it by wave-uniform addresses, so the constants live in scalar registers only while a site uses them.
 //
 // The work item, apply_frame, frame_regs, wave_scan, uniform, u of the cdf search and shot_value are hea_noise_traj.hpp's, shared
-// with the uniform units, and so is the entry point around the table fill (traj_open, traj_finish).  Where a kernel below still
-// spells out what hea_noise.hip or hea_noise_wide.hip also hold (the lane butterflies, the basis change, the cdf searches, the
-// slot fold, the wave kernel's work item and shot words), the shared form changed its device code
-// (profiles/r25_device_code_identity.txt).
+// with the uniform units.  The table (DevTable), the body of the prep kernel that writes it, site_pair, group_sum, jump_u,
+// draw_code and the body of the entry point (jump_forward, around traj_open and traj_finish) are hea_noise_jump.hpp's, shared
+// with hea_noise_device_wide.hip.  Where a kernel below still spells out what hea_noise.hip or hea_noise_wide.hip also hold (the
+// lane butterflies, the basis change, the cdf searches, the slot fold, the wave kernel's work item and shot words), the shared
+// form changed its device code (profiles/r25_device_code_identity.txt).
 #include <climits>
 #include <cmath>
 #include <cstdint>
 
-#include "hea_device_noise.hpp"
-#include "hea_noise_traj.hpp"
+#include "hea_noise_jump.hpp"
 
 namespace qhea {
 namespace {
 
-constexpr int kJumpMaxWires = 9;            // n = 10..12: the state lives in LDS, hea_noise_device_wide.hip
 constexpr int kJumpWaves = 4;               // waves per workgroup (independent; no LDS, no barrier)
-
-struct DevTable {                           // 8-byte words only: device_tables_kernel copies it word by word
-    unsigned long long cthr[4 * kJumpMaxWires][2];  // call c of a block's template (ENC 0..n-1, ROT n..2n-1, slot j: 2n + 2j, + 1):
-                                                    // (Pauli threshold, dephasing threshold)
-    double gs[4][kJumpMaxWires][2];                 // [site][wire] (gamma, sqrt(1 - gamma))
-    unsigned long long rthr[kJumpMaxWires][2];      // readout thresholds (01, 10) per bit
-    double rd[kJumpMaxWires][2];                    // readout01, readout10 per bit
-    // what the read-out of a trajectory needs of the call's arguments; the wave kernel reads it there (readout_args)
-    double off, co;
-    const double* diag;
-    unsigned L, pauli;
-};
-constexpr int kTableWords = (int)(sizeof(DevTable) / 8);
 
 // ---- device helpers of this unit ----------------------------------------------------------------------------------------------------
 
@@ -68,32 +54,8 @@ __device__ __forceinline__ void site_draws(const NoiseArgs& a, const DevTable* _
     code = 0; w3 = 0;
     if (a.thr1 == 0 || c >= cnt) return;
     const uint4 w = philox(make_uint4(call0 + (unsigned)c, traj, (unsigned)row, (unsigned)(row >> 32)), a.key0, a.key1);
-    const unsigned long long tp = tab->cthr[tbase + c][0], tz = tab->cthr[tbase + c][1];
-    const unsigned kinds = (RING && !(c & 1)) ? 15u : 3u;
-    if ((unsigned long long)w.x < tp) code = 1u + (unsigned)(((unsigned long long)w.y * kinds) >> 32);
-    if ((unsigned long long)w.z < tz) code |= 16u;
-    w3 = w.w;
+    draw_code(tab, tbase + c, w, (RING && !(c & 1)) ? 15u : 3u, code, w3);
 }
-
-// (gamma, sqrt(1 - gamma)) of a site, read where the site uses it.  The addresses are loop-invariant, so without the (empty)
-// fence on the offset every load of the circuit loop is hoisted in front of it and the constants are kept in scalar registers
-// that spill into vector lanes (9 wires: 72 doubles); behind it the pair is one scalar load that lives for the length of its
-// site.  (A fence on the pointer itself would lose its address space: flat vector loads.)
-__device__ __forceinline__ double2 site_pair(const DevTable* __restrict__ tab, int site, int q) {
-    int fence = 0;
-    asm volatile("" : "+s"(fence));
-    const double* p = &tab->gs[site][q][0] + fence;
-    return make_double2(p[0], p[1]);
-}
-
-// v summed over the lanes that differ in bits 0 .. BITS-1, offsets 2^(BITS-1), .., 1; every lane of a group ends with the same sum
-template <int BITS>
-__device__ __forceinline__ double group_sum(double v) {
-    static_rfor<0, BITS>([&](auto b) { v = pair_sum<(1 << decltype(b)::value)>(v); });
-    return v;
-}
-
-__device__ __forceinline__ double jump_u(unsigned w3) { return ((double)w3 + 0.5) * 0x1p-32; }
 
 // The read-out's arguments from the table, behind the fence of site_pair: with one wave per trajectory the circuit loop leaves no
 // scalar registers for values that are only used behind it, and kernel arguments would be parked in vector lanes meanwhile.
@@ -453,35 +415,9 @@ __global__ __launch_bounds__(64 * kJumpWaves) void device_traj_wave_kernel(Noise
 
 // ---- prep: the table, and expectation mode's read-out weights -------------------------------------------------------------------------
 
-// One workgroup.  Copies the table into the workspace and, with `buf`, builds h[k] of expectation mode in half (n - 1) & 1 of
-// buf[2 * 2^n]: co sum_i (bit_i(k) ? -(1 - 2 r10_i) : 1 - 2 r01_i) in the order i = 0..n-1, or ham_diag under the readout
-// confusion, bit by bit: stage i writes half i & 1, h'[k] = (1 - e) h[k] + e h[k ^ 2^i] with e = r01_i where bit i of k is 0 and
-// r10_i where it is 1.
 __global__ __launch_bounds__(256) void device_tables_kernel(DevTable t, DevTable* __restrict__ out, const double* __restrict__ diag,
                                                             double co, int n, double* __restrict__ buf) {
-    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&t);
-    if ((int)threadIdx.x < kTableWords) reinterpret_cast<unsigned long long*>(out)[threadIdx.x] = src[threadIdx.x];
-    if (!buf) return;
-    const int D = 1 << n;
-    if (!diag) {
-        double* dst = buf + (size_t)((n - 1) & 1) * D;
-        for (int k = threadIdx.x; k < D; k += 256) {
-            double h = 0.0;
-            for (int i = 0; i < n; ++i) h += (k >> i) & 1 ? -(1.0 - 2.0 * t.rd[i][1]) : 1.0 - 2.0 * t.rd[i][0];
-            dst[k] = co * h;
-        }
-        return;
-    }
-    const double* from = diag;
-    for (int i = 0; i < n; ++i) {
-        double* dst = buf + (size_t)(i & 1) * D;
-        for (int k = threadIdx.x; k < D; k += 256) {
-            const double e = (k >> i) & 1 ? t.rd[i][1] : t.rd[i][0];
-            dst[k] = (1.0 - e) * from[k] + e * from[k ^ (1 << i)];
-        }
-        __syncthreads();
-        from = dst;
-    }
+    jump_tables_body(t, out, diag, co, n, buf);
 }
 
 int launch_device_traj(const NoiseArgs& a, int n, const DevTable* tab, const double* hd, hipStream_t st) {
@@ -504,12 +440,6 @@ int launch_device_traj(const NoiseArgs& a, int n, const DevTable* tab, const dou
 // the uniform units' layout with the read-out region of the wide ones, then the table
 constexpr TrajUnit kJumpUnit{QHEA_MIN_QUBITS, kJumpMaxWires, true, sizeof(DevTable)};
 
-inline qhea_noise sampling_as_noise(const qhea_sampling* s) {
-    qhea_noise nz{};
-    nz.shots = s->shots; nz.trajectories = s->trajectories; nz.seed = s->seed;
-    return nz;
-}
-
 }  // namespace
 }  // namespace qhea
 
@@ -526,42 +456,15 @@ int qhea_device_noise_jump_tables(int n, const qhea_device_noise* dn, double* ju
 }
 
 size_t qhea_model_noisy_device_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling) {
-    if (!sampling) return 0;
-    const qhea_noise nz = sampling_as_noise(sampling);
-    return traj_workspace_bytes(kJumpUnit, desc, batch, &nz);
+    return jump_workspace_bytes(kJumpUnit, desc, batch, sampling);
 }
 
 int qhea_model_forward_noisy_device(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
                                     const double* trunk, const double* params, const double* ham_diag,
                                     const qhea_device_noise* dn, const qhea_sampling* sampling, double* pred, double* stderr_out,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    // the device setting is checked against the model's n before the shared checks, which read the model themselves: the first
-    // reading goes into a record of its own (model_info appends to the record's block list)
-    ModelInfo probe;
-    int rc = model_info(desc, probe);
-    if (rc != QHEA_OK) return rc;
-    rc = device_noise_check(probe.n, dn);
-    if (rc != QHEA_OK) return rc;
-    if (!sampling) return QHEA_EINVAL;
-    const qhea_noise nz = sampling_as_noise(sampling);
-    TrajCall t;
-    rc = traj_open(kJumpUnit, desc, row0, batch, branch, trunk, params, ham_diag, &nz, pred, workspace, workspace_bytes, stream, t);
-    if (rc != QHEA_OK || t.c.empty) return rc;
-    const int n = t.c.mi.n;
-    NoiseArgs& a = t.a;
-    a.L = jump_calls(n, t.c.mi.nb, t.c.mi.ld);                           // shot mode continues from call C
-    DevTable tb{};
-    bool any;
-    fill_jump_table(n, dn, tb, any);
-    tb.off = a.off; tb.co = a.co; tb.diag = ham_diag; tb.L = a.L; tb.pauli = (unsigned)a.pauli;
-    a.thr1 = any ? 1 : 0;                                                // an ideal setting draws nothing
-    DevTable* tab = reinterpret_cast<DevTable*>(t.extra);
-    const bool expect = !a.shots;
-    hipLaunchKernelGGL(device_tables_kernel, dim3(1), dim3(256), 0, t.c.st, tb, tab, ham_diag, a.co, n,
-                       expect ? t.mix : static_cast<double*>(nullptr));
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    const double* hd = expect ? t.mix + ((size_t)((n - 1) & 1) << n) : nullptr;
-    return traj_finish(t, launch_device_traj(a, n, tab, hd, t.c.st), pred, stderr_out);
+    return jump_forward(kJumpUnit, device_tables_kernel, launch_device_traj, desc, row0, batch, branch, trunk, params, ham_diag, dn,
+                        sampling, pred, stderr_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

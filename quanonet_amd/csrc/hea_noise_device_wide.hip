@@ -37,34 +37,25 @@
 // Philox: lane c of wave 0 computes call c of the segment -- the n ENC calls of a block, or the 3 n calls of a sub-layer (ROT
 // 0..n-1, then the ring's 2 n) -- and reduces it to a code (Pauli in bits 0..3, dephasing in bit 4) and the jump's word, as
 // site_draws of hea_noise_device.hip; both go to LDS scratch in front of a barrier that opens the layer.  The per-call thresholds
-// and per-site (gamma, sqrt(1 - gamma)) live in a table of this unit's own in the workspace (WideDevTable, 12 wires), filled by
-// one prep launch and read by wave-uniform addresses where a site uses them.
+// and per-site (gamma, sqrt(1 - gamma)) live in a table in the workspace (WideDevTable, 12 wires), filled by one prep launch and
+// read by wave-uniform addresses where a site uses them.
+//
+// Shared, not this unit's: the table, the body of its prep kernel, site_pair, group_sum, jump_u, draw_code and the body of the
+// entry point are hea_noise_jump.hpp's (with hea_noise_device.hip); ring_pull and the framed store of the last pass
+// (store_framed) are hea_lds.hpp's (with hea_noise_wide.hip).  The ground-state fill, the basis-change gate, the cdf prefix and
+// pick of the read-out and plain_layer are spelt out here and in hea_noise_wide.hip: every shared form tried changed the device
+// code of a kernel (profiles/r27_device_code_identity.txt).
 #include <climits>
 #include <cmath>
 #include <cstdint>
 
-#include "hea_device_noise.hpp"
 #include "hea_lds.hpp"
-#include "hea_noise_traj.hpp"
+#include "hea_noise_jump.hpp"
 
 namespace qhea {
 namespace {
 
 constexpr int kLG = 4;                      // gate qubits per pass, as noisy_wide_lds_kernel
-constexpr int kWideWires = QHEA_MAX_QUBITS; // 12
-
-struct WideDevTable {                       // 8-byte words only: wide_tables_kernel copies it word by word
-    unsigned long long cthr[4 * kWideWires][2];     // call c of a block's template: (Pauli threshold, dephasing threshold)
-    double gs[4][kWideWires][2];                    // [site][wire] (gamma, sqrt(1 - gamma))
-    unsigned long long rthr[kWideWires][2];         // readout thresholds (01, 10) per bit
-    double rd[kWideWires][2];                       // readout01, readout10 per bit
-    double off, co;
-    const double* diag;
-    unsigned L, pauli;
-};
-constexpr int kWideTableWords = (int)(sizeof(WideDevTable) / 8);
-static_assert(kWideTableWords <= 256, "wide_tables_kernel copies one word per thread");
-
 // In FRONT of the state: at n = 12 the state alone fills the 64 KiB an LDS instruction's immediate offset reaches, and behind it
 // every scratch word would need its address in a register (36 draws: scalar registers that spill inside the sub-layer loop)
 struct JumpScratch {
@@ -86,16 +77,6 @@ constexpr int ring_site_mask() {
     return J < N - 1 ? 1 << (J + 1) : 3;
 }
 
-__device__ __forceinline__ double jump_u(unsigned w3) { return ((double)w3 + 0.5) * 0x1p-32; }
-
-// (gamma, sqrt(1 - gamma)) of a site, read where the site uses it (the fence: site_pair of hea_noise_device.hip)
-__device__ __forceinline__ double2 site_pair(const WideDevTable* __restrict__ tab, int site, int q) {
-    int fence = 0;
-    asm volatile("" : "+s"(fence));
-    const double* p = &tab->gs[site][q][0] + fence;
-    return make_double2(p[0], p[1]);
-}
-
 // What every thread carries along a trajectory; all values are the same in every thread of the workgroup
 struct JumpState {
     double n2;                              // squared norm of the stored state
@@ -106,7 +87,7 @@ struct JumpState {
 // v summed over the workgroup: the butterfly over the wave, offsets 32 .. 1, then the waves in order
 template <int NW>
 __device__ __forceinline__ double site_sum(double v, JumpScratch* sc, int& par) {
-    static_rfor<0, 6>([&](auto b) { v = pair_sum<(1 << decltype(b)::value)>(v); });
+    v = group_sum<6>(v);
     if constexpr (NW == 1) {
         return v;
     } else {
@@ -158,14 +139,6 @@ __device__ __forceinline__ void relax_site(c2 (&v)[1 << kLG], JumpState& js, int
     }
 }
 
-// z' with parity(ring(k) & z) = parity(k & z'): the transposed ring, last CNOT first
-template <int N>
-__device__ __forceinline__ int ring_pull(int z) {
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) z ^= ((z >> i) & 1) << ((i + 1) % N);
-    return z;
-}
-
 // Wave 0's lanes draw the segment's calls call0 .. call0 + cnt - 1 (template entries tbase ..; RING: the calls from `ring0` on
 // alternate pair Pauli / none) into the scratch; the barrier behind it opens the layer.  a.thr1 == 0: an ideal setting.
 __device__ __forceinline__ void segment_draws(const NoiseArgs& a, const WideDevTable* __restrict__ tab, JumpScratch* sc,
@@ -179,11 +152,7 @@ __device__ __forceinline__ void segment_draws(const NoiseArgs& a, const WideDevT
             unsigned k0 = a.key0, k1 = a.key1;
             asm volatile("" : "+s"(k0), "+s"(k1));
             const uint4 w = philox(make_uint4(call0 + (unsigned)c, traj, (unsigned)row, (unsigned)(row >> 32)), k0, k1);
-            const unsigned long long tp = tab->cthr[tbase + c][0], tz = tab->cthr[tbase + c][1];
-            const unsigned kinds = (c >= ring0 && !((c - ring0) & 1)) ? 15u : 3u;
-            if ((unsigned long long)w.x < tp) code = 1u + (unsigned)(((unsigned long long)w.y * kinds) >> 32);
-            if ((unsigned long long)w.z < tz) code |= 16u;
-            w3 = w.w;
+            draw_code(tab, tbase + c, w, (c >= ring0 && !((c - ring0) & 1)) ? 15u : 3u, code, w3);
         }
         sc->code[c] = code; sc->w3[c] = w3;
     }
@@ -238,16 +207,7 @@ __device__ __forceinline__ void jump_layer(double2* s, const Bases<N, kLG>& bs, 
             }
             __syncthreads();                               // every thread holds its amplitudes: safe to permute
             const int px = phys<LG>(js.x), z = RING ? ring_pull<N>(js.z) : js.z;
-            if (z) {
-                const int sb = __popc((unsigned)(tp & z)), zl = (z >> PS::A) & ((1 << LG) - 1);
-                static_for<0, (1 << LG)>([&](auto jj) {
-                    constexpr int J = decltype(jj)::value;
-                    const bool neg = (sb + __popc((unsigned)(J & zl))) & 1;
-                    v[J].x = neg ? -v[J].x : v[J].x;
-                    v[J].y = neg ? -v[J].y : v[J].y;
-                });
-            }
-            store_group<N, PS::A, RING, LG>(s, (RING ? bs.ring : bs.plain[P]) ^ px, v);
+            store_framed<N, PS::A, RING, LG>(s, RING ? bs.ring : bs.plain[P], px, z, tp, v);
             js.x = 0; js.z = 0;
             __syncthreads();
         }
@@ -267,12 +227,6 @@ __device__ __forceinline__ void plain_layer(double2* s, const Bases<N, kLG>& bs,
         store_group<N, PS::A, false, LG>(s, bs.plain[P], v);
         __syncthreads();
     });
-}
-
-// the read-out's sums over a wave: the butterfly, offsets 32 .. 1 (the waves are added in order behind the caller's barrier)
-__device__ __forceinline__ double readout_butterfly(double v) {
-    static_rfor<0, 6>([&](auto b) { v = pair_sum<(1 << decltype(b)::value)>(v); });
-    return v;
 }
 
 template <int N>
@@ -347,8 +301,8 @@ __global__ __launch_bounds__((LCfg<N, kLG>::T)) void device_traj_lds_kernel(Nois
             double num = 0.0;
 #pragma unroll
             for (int j = 0; j < M; ++j) num += pk[j] * hd[(t << LG) | j];
-            num = readout_butterfly(num);
-            double tot = readout_butterfly(part);
+            num = group_sum<6>(num);
+            double tot = group_sum<6>(part);
             if constexpr (L::NW > 1) {
                 if (lane == 0) { sc->rsum[0][wave] = num; sc->rsum[1][wave] = tot; }
                 __syncthreads();
@@ -365,7 +319,7 @@ __global__ __launch_bounds__((LCfg<N, kLG>::T)) void device_traj_lds_kernel(Nois
             const double inc = wave_scan(c[M - 1], lane);
             double before = __shfl_up(inc, 1);
             if (lane == 0) before = 0.0;
-            double tot = readout_butterfly(part);
+            double tot = group_sum<6>(part);
             if (lane == 63) sc->rsum[0][wave] = inc;
             if (lane == 0) sc->rsum[1][wave] = tot;
             __syncthreads();                                             // rsum, u, the flip masks
@@ -407,47 +361,17 @@ __global__ __launch_bounds__((LCfg<N, kLG>::T)) void device_traj_lds_kernel(Nois
 
 // ---- prep: the table, and expectation mode's read-out weights ------------------------------------------------------------------
 
-// One workgroup.  Copies the table into the workspace and, with `buf`, builds h[k] of expectation mode in half (n - 1) & 1 of
-// buf[2 * 2^n] exactly as device_tables_kernel of hea_noise_device.hip does: co sum_i (bit_i(k) ? -(1 - 2 r10_i) : 1 - 2 r01_i)
-// in the order i = 0..n-1, or ham_diag under the readout confusion bit by bit, stage i writing half i & 1.
 __global__ __launch_bounds__(256) void wide_tables_kernel(WideDevTable t, WideDevTable* __restrict__ out,
                                                           const double* __restrict__ diag, double co, int n,
                                                           double* __restrict__ buf) {
-    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&t);
-    if ((int)threadIdx.x < kWideTableWords) reinterpret_cast<unsigned long long*>(out)[threadIdx.x] = src[threadIdx.x];
-    if (!buf) return;
-    const int D = 1 << n;
-    if (!diag) {
-        double* dst = buf + (size_t)((n - 1) & 1) * D;
-        for (int k = threadIdx.x; k < D; k += 256) {
-            double h = 0.0;
-            for (int i = 0; i < n; ++i) h += (k >> i) & 1 ? -(1.0 - 2.0 * t.rd[i][1]) : 1.0 - 2.0 * t.rd[i][0];
-            dst[k] = co * h;
-        }
-        return;
-    }
-    const double* from = diag;
-    for (int i = 0; i < n; ++i) {
-        double* dst = buf + (size_t)(i & 1) * D;
-        for (int k = threadIdx.x; k < D; k += 256) {
-            const double e = (k >> i) & 1 ? t.rd[i][1] : t.rd[i][0];
-            dst[k] = (1.0 - e) * from[k] + e * from[k ^ (1 << i)];
-        }
-        __syncthreads();
-        from = dst;
-    }
+    jump_tables_body(t, out, diag, co, n, buf);
 }
 
 template <int N>
 int launch_traj_lds(const NoiseArgs& a, const WideDevTable* tab, const double* hd, hipStream_t st) {
     using L = LCfg<N, kLG>;
     constexpr size_t smem = kScratchBytes + L::STATE_BYTES;
-    // every launch: the attribute is per device, and a process may drive more than one
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(device_traj_lds_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-        return QHEA_ELAUNCH;
-    hipLaunchKernelGGL(device_traj_lds_kernel<N>, dim3((unsigned)(a.B * a.tiles)), dim3(L::T), smem, st, a, tab, hd);
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+    return launch_dynamic_lds(device_traj_lds_kernel<N>, dim3((unsigned)(a.B * a.tiles)), dim3(L::T), smem, st, a, tab, hd);
 }
 
 int launch_device_traj_wide(const NoiseArgs& a, int n, const WideDevTable* tab, const double* hd, hipStream_t st) {
@@ -462,12 +386,6 @@ int launch_device_traj_wide(const NoiseArgs& a, int n, const WideDevTable* tab, 
 // the uniform units' layout with the read-out region of the wide ones, then the table
 constexpr TrajUnit kJumpWideUnit{10, QHEA_MAX_QUBITS, true, sizeof(WideDevTable)};
 
-inline qhea_noise sampling_as_noise(const qhea_sampling* s) {
-    qhea_noise nz{};
-    nz.shots = s->shots; nz.trajectories = s->trajectories; nz.seed = s->seed;
-    return nz;
-}
-
 }  // namespace
 }  // namespace qhea
 
@@ -476,42 +394,15 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_noisy_device_wide_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling) {
-    if (!sampling) return 0;
-    const qhea_noise nz = sampling_as_noise(sampling);
-    return traj_workspace_bytes(kJumpWideUnit, desc, batch, &nz);
+    return jump_workspace_bytes(kJumpWideUnit, desc, batch, sampling);
 }
 
 int qhea_model_forward_noisy_device_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
                                          const double* trunk, const double* params, const double* ham_diag,
                                          const qhea_device_noise* dn, const qhea_sampling* sampling, double* pred,
                                          double* stderr_out, void* workspace, size_t workspace_bytes, void* stream) {
-    // as qhea_model_forward_noisy_device: the device setting against the model's n, then the shared checks
-    ModelInfo probe;
-    int rc = model_info(desc, probe);
-    if (rc != QHEA_OK) return rc;
-    rc = device_noise_check(probe.n, dn);
-    if (rc != QHEA_OK) return rc;
-    if (!sampling) return QHEA_EINVAL;
-    const qhea_noise nz = sampling_as_noise(sampling);
-    TrajCall t;
-    rc = traj_open(kJumpWideUnit, desc, row0, batch, branch, trunk, params, ham_diag, &nz, pred, workspace, workspace_bytes, stream,
-                   t);
-    if (rc != QHEA_OK || t.c.empty) return rc;
-    const int n = t.c.mi.n;
-    NoiseArgs& a = t.a;
-    a.L = jump_calls(n, t.c.mi.nb, t.c.mi.ld);                           // shot mode continues from call C
-    WideDevTable tb{};
-    bool any;
-    fill_jump_table(n, dn, tb, any);
-    tb.off = a.off; tb.co = a.co; tb.diag = ham_diag; tb.L = a.L; tb.pauli = (unsigned)a.pauli;
-    a.thr1 = any ? 1 : 0;                                                // an ideal setting draws nothing
-    WideDevTable* tab = reinterpret_cast<WideDevTable*>(t.extra);
-    const bool expect = !a.shots;
-    hipLaunchKernelGGL(wide_tables_kernel, dim3(1), dim3(256), 0, t.c.st, tb, tab, ham_diag, a.co, n,
-                       expect ? t.mix : static_cast<double*>(nullptr));
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    const double* hd = expect ? t.mix + ((size_t)((n - 1) & 1) << n) : nullptr;
-    return traj_finish(t, launch_device_traj_wide(a, n, tab, hd, t.c.st), pred, stderr_out);
+    return jump_forward(kJumpWideUnit, wide_tables_kernel, launch_device_traj_wide, desc, row0, batch, branch, trunk, params,
+                        ham_diag, dn, sampling, pred, stderr_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,9 @@
 // (noisy_call_check).  The four trajectory units (uniform noise at n = 2..6, one amplitude per lane, and at n = 7..12, registers
 // or LDS; device noise at n = 2..9 in both register layouts and at n = 10..12 in LDS): the argument record, the Philox stream and its error codes, the Pauli frame bits and the frame's
 // application in either layout (apply_frame, frame_regs), the work item, wave_scan, u and the value of a shot, the workspace
-// layout, and the head and tail of the entry point around a unit's kernels (traj_open, traj_finish).
+// layout, and the head and tail of the entry point around a unit's kernels (traj_open, traj_finish).  What only the two
+// device-noise units share (their table, its prep kernel's body, the site helpers, the entry point's body) is
+// hea_noise_jump.hpp's; the frame in the LDS layout (ring_pull, store_framed) is hea_lds.hpp's.
 #pragma once
 #include <climits>
 #include <cmath>

@@ -26,7 +26,8 @@
 // u < cdf[k] by ballots or a workgroup minimum.  Nothing depends on the batch, the grid or the chunking; no atomics.
 //
 // The work item, frame_regs, wave_scan, uniform, u of the cdf search and shot_value are hea_noise_traj.hpp's, shared with
-// hea_noise_device.hip; the frames of a segment, the shot words, the LDS kernel and the readout mix are this unit's.
+// hea_noise_device.hip; ring_pull and the last pass's store behind the frame (store_framed) are hea_lds.hpp's, shared with
+// hea_noise_device_wide.hip; the frames of a segment, the shot words, the LDS kernel and the readout mix are this unit's.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -192,14 +193,6 @@ struct WideScratch {                        // behind the state
     double u;
 };
 
-// z' with parity(ring(k) & z) = parity(k & z'): the transposed ring, last CNOT first
-template <int N>
-__device__ __forceinline__ int ring_pull(int z) {
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) z ^= ((z >> i) & 1) << ((i + 1) % N);
-    return z;
-}
-
 // One gate layer with the segment's frame behind it.  The last pass stores every amplitude where the ring (RING) and the X mask
 // send it, with the Z mask's sign; `tpl` = the thread's index bits in that pass.  sc->frame is written by thread 0 before the
 // layer's last barrier pair and read between the two.
@@ -221,16 +214,7 @@ __device__ __forceinline__ void noisy_layer(double2* s, const Bases<N, kWideLG>&
         } else {
             __syncthreads();                               // every thread holds its amplitudes: safe to permute
             const int px = uniform(sc->frame[0]), z = uniform(sc->frame[1]);
-            if (z) {
-                const int sb = __popc((unsigned)(tpl & z)), zl = (z >> PS::A) & ((1 << LG) - 1);
-                static_for<0, (1 << LG)>([&](auto jj) {
-                    constexpr int J = decltype(jj)::value;
-                    const bool neg = (sb + __popc((unsigned)(J & zl))) & 1;
-                    v[J].x = neg ? -v[J].x : v[J].x;
-                    v[J].y = neg ? -v[J].y : v[J].y;
-                });
-            }
-            store_group<N, PS::A, RING, LG>(s, (RING ? bs.ring : bs.plain[P]) ^ px, v);
+            store_framed<N, PS::A, RING, LG>(s, RING ? bs.ring : bs.plain[P], px, z, tpl, v);
             __syncthreads();
         }
     });
@@ -378,16 +362,12 @@ int launch_wide(const NoiseArgs& a, const double* hd, hipStream_t st) {
     if constexpr (N <= 9) {
         hipLaunchKernelGGL(noisy_wide_wave_kernel<N>, dim3((unsigned)((items + kWideWaves - 1) / kWideWaves)), dim3(64 * kWideWaves),
                            0, st, a, hd);
+        return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
     } else {
         using L = LCfg<N, kWideLG>;
         constexpr size_t smem = L::STATE_BYTES + sizeof(WideScratch);
-        // every launch: the attribute is per device, and a process may drive more than one
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(noisy_wide_lds_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return QHEA_ELAUNCH;
-        hipLaunchKernelGGL(noisy_wide_lds_kernel<N>, dim3((unsigned)items), dim3(L::T), smem, st, a, hd);
+        return launch_dynamic_lds(noisy_wide_lds_kernel<N>, dim3((unsigned)items), dim3(L::T), smem, st, a, hd);
     }
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
 
 // ham_diag goes through readout_mix_kernel first where the kernels read it mixed (expectation mode)

@@ -1,10 +1,11 @@
 """
-Parity record of the three trajectory calls (qhea_model_forward_noisy, ..._noisy_wide, ..._noisy_device) for the library that
-QHEA_LIB names (default: the tree's own): SHA-256 of `pred` and `stderr` over a small grid, and the three workspace sizes per
-shape.  Run it once per library and compare the outputs line by line.
-  grid: QuanONet and HEAQNN; n = 2, 6, 7, 9 for the uniform calls (2, 6: lane call; 7, 9: wide call) and the device call, n = 10,
-  12 for the wide call; 3 rows x 70 values (a full and a partial tile); expectation and shot mode; Z and diag read-outs; row0 = 0
-  and 2^32 + 5.
+Parity record of the four trajectory calls (qhea_model_forward_noisy, ..._noisy_wide, ..._noisy_device, ..._noisy_device_wide)
+for the library that QHEA_LIB names (default: the tree's own): SHA-256 of `pred` and `stderr` over a small grid, and the
+workspace sizes per shape (lane, wide, device; for n >= 10 also device_wide).  Run it once per library and compare the outputs
+line by line.
+  grid: QuanONet and HEAQNN; n = 2, 6 (uniform lane call, device call), 7, 9 (uniform wide call, device call), 10, 12 (uniform wide
+  call, device wide call: device_noisy_predict picks it there); 3 rows x 70 values (a full and a partial tile); expectation and
+  shot mode; Z and diag read-outs; row0 = 0 and 2^32 + 5.
     QHEA_LIB=/path/to/libquanonet_hea.so python scripts/traj_parity.py > out.txt
 """
 import ctypes
@@ -69,13 +70,13 @@ def main():
                              int(lib.qhea_model_noisy_wide_workspace_bytes(ctypes.byref(desc), ROWS, ctypes.byref(nm.params()))),
                              _lib.model_noisy_device_workspace_bytes(desc, ROWS, sp.params())]
                     tag = f'{kind} n={n} {readout} shots={shots}'
-                    print(f'{tag} workspace_bytes lane={sizes[0]} wide={sizes[1]} device={sizes[2]}')
+                    wide = f' device_wide={_lib.model_noisy_device_wide_workspace_bytes(desc, ROWS, sp.params())}' if n >= 10 else ''
+                    print(f'{tag} workspace_bytes lane={sizes[0]} wide={sizes[1]} device={sizes[2]}{wide}')
                     for row0 in (0, (1 << 32) + 5):
                         pred, se = noisy_predict(m, ins, nm, row0=row0)
                         print(f'{tag} row0={row0} {"wide" if n >= 7 else "lane"} pred={_sha(pred)} stderr={_sha(se)}')
-                        if n <= 9:
-                            pred, se = device_noisy_predict(m, ins, _device_noise(n), sp, row0=row0)
-                            print(f'{tag} row0={row0} device pred={_sha(pred)} stderr={_sha(se)}')
+                        pred, se = device_noisy_predict(m, ins, _device_noise(n), sp, row0=row0)
+                        print(f'{tag} row0={row0} device pred={_sha(pred)} stderr={_sha(se)}')
     torch.cuda.synchronize()
 
 
