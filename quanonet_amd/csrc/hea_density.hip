@@ -96,13 +96,6 @@ __global__ __launch_bounds__(kDensThreads) void density_fwd_kernel(DensArgs a) {
     }
 }
 
-template <int N>
-int launch_density(const DensArgs& a, hipStream_t st) {
-    constexpr int RPW = kDensThreads / (1 << (2 * N - 4));
-    constexpr size_t smem = kDensStateBytes + 2 * (1 << N) * sizeof(double);
-    return launch_dynamic_lds(density_fwd_kernel<N>, dim3((unsigned)((a.B + RPW - 1) / RPW)), dim3(kDensThreads), smem, st, a);
-}
-
 }  // namespace
 }  // namespace qhea
 
@@ -132,14 +125,7 @@ int qhea_model_forward_noisy_exact(const qhea_model_desc* desc, int64_t batch, c
 
     DensArgs a = dens_args(desc, c.mi, noise, params, ham_diag, batch, gates, cs);
     a.pred = pred; a.sd = shot_std;
-    switch (c.mi.n) {
-        case 2: return launch_density<2>(a, c.st);
-        case 3: return launch_density<3>(a, c.st);
-        case 4: return launch_density<4>(a, c.st);
-        case 5: return launch_density<5>(a, c.st);
-        case 6: return launch_density<6>(a, c.st);
-        default: return QHEA_EUNSUPPORTED;
-    }
+    return dispatch_n(c.mi.n, [&](auto n) { return launch_density_fwd<n()>(density_fwd_kernel<n()>, a, c.st); });
 }
 
 }  // extern "C"

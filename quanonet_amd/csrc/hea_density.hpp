@@ -1,11 +1,13 @@
 // hea_density.hpp -- what the density-matrix kernels share: the exact noisy forward (hea_density.hip) and its adjoint gradient
 // (hea_density_grad.hip), and their counterparts under a device noise model (hea_density_device.hip,
 // hea_density_device_grad.hip).  Element layout, bank fold, the pass over two wires, the gates and the depolarizing channels in their
-// closed forms, and the forward sweep's passes; hea_density.hip describes the layout.  Everything sits in an unnamed namespace:
+// closed forms, and the forward sweep's passes; hea_density.hip describes the layout.  Host side: the dispatch on the qubit count,
+// the forward launcher and the fill of what every argument record holds of the circuit.  Everything sits in an unnamed namespace:
 // each translation unit compiles its own copy into its own kernels.
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "hea_noise_traj.hpp"
 
@@ -59,6 +61,9 @@ __device__ __forceinline__ void apply_gate(double2 (&e)[16], const U2& u) {
     }
 }
 
+// the encoding gate RX(x) of a wire from (cos, sin)(x / 2)
+__device__ __forceinline__ U2 encoding_rx(double2 c) { return U2{{c.x, 0.0}, {0.0, -c.y}, {0.0, -c.y}, {c.x, 0.0}}; }
+
 // one-qubit depolarizing channel on the same blocks
 template <int S>
 __device__ __forceinline__ void depolarize1(double2 (&e)[16], const DensArgs& a) {
@@ -73,13 +78,30 @@ __device__ __forceinline__ void depolarize1(double2 (&e)[16], const DensArgs& a)
     }
 }
 
+// a phase-covariant one-wire channel in its element form (element_form of hea_device_noise.hpp) on the same blocks:
+// rho00' = k00 rho00 + k01 rho11, rho11' = k10 rho00 + k11 rho11, the off-diagonal elements times off.  The device units fetch
+// the five constants their own way.  depolarize1 above is the case k00 = k11, k01 = k10 but keeps its text: written through
+// this body, the uniform kernels' code changes (profiles/r28_device_code_identity.txt).
+template <int S>
+__device__ __forceinline__ void phase_covariant(double2 (&e)[16], double off, double k00, double k01, double k10, double k11) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        const double2 d0 = e[b], d1 = e[b + 3 * S];
+        e[b] = make_double2(k00 * d0.x + k01 * d1.x, k00 * d0.y + k01 * d1.y);
+        e[b + 3 * S] = make_double2(k10 * d0.x + k11 * d1.x, k10 * d0.y + k11 * d1.y);
+        e[b + S].x *= off; e[b + S].y *= off;
+        e[b + 2 * S].x *= off; e[b + 2 * S].y *= off;
+    }
+}
+
 // wire q's pending gates of sub-layer s: (encoding RX, channel), fused RY RZ RY, channel
 template <int N, int S>
 __device__ __forceinline__ void wire_gates(double2 (&e)[16], const DensArgs& a, const double2* csr, int s, int col, bool enc,
                                            int q) {
     if (enc) {
         const double2 c = csr[col + q];
-        apply_gate<S>(e, U2{{c.x, 0.0}, {0.0, -c.y}, {0.0, -c.y}, {c.x, 0.0}});
+        apply_gate<S>(e, encoding_rx(c));
         depolarize1<S>(e, a);
     }
     const double4 v = a.gates[2 * (s * N + q + N)];                      // (u00, u01); u10 = -conj(u01), u11 = conj(u00)
@@ -88,7 +110,8 @@ __device__ __forceinline__ void wire_gates(double2 (&e)[16], const DensArgs& a, 
 }
 
 // CNOT(c -> t) on both indices (local bits: 0 / 1 = t's row / column bit, 2 / 3 = c's), then the two-qubit channel
-__device__ __forceinline__ void cnot_depolarize2(double2 (&e)[16], const DensArgs& a) {
+// (keep, mix) = (1 - lam, lam / 4): the uniform one, or a slot's own under a device noise model
+__device__ __forceinline__ void cnot_depolarize2(double2 (&e)[16], double keep, double mix) {
     double2 r[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) r[k] = e[k ^ ((k >> 2) & 1) ^ (((k >> 3) & 1) << 1)];
@@ -96,8 +119,8 @@ __device__ __forceinline__ void cnot_depolarize2(double2 (&e)[16], const DensArg
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const bool eq = k == 0 || k == 3 || k == 12 || k == 15;          // row bits (c, t) = column bits
-        e[k].x = eq ? a.d2_keep * r[k].x + a.d2_mix * sx : a.d2_keep * r[k].x;
-        e[k].y = eq ? a.d2_keep * r[k].y + a.d2_mix * sy : a.d2_keep * r[k].y;
+        e[k].x = eq ? keep * r[k].x + mix * sx : keep * r[k].x;
+        e[k].y = eq ? keep * r[k].y + mix * sy : keep * r[k].y;
     }
 }
 
@@ -142,7 +165,7 @@ __device__ __forceinline__ void ring_passes(double2* row, int rank, int sf, cons
         }
         if (J == 0) wire_gates<N, 1>(e, a, csr, s, col, enc, P::t);
         if (J <= N - 2) wire_gates<N, 4>(e, a, csr, s, col, enc, P::c);
-        cnot_depolarize2(e, a);
+        cnot_depolarize2(e, a.d2_keep, a.d2_mix);
         P::store(e, row, b);
         __syncthreads();
         ring_passes<N, J + 1>(row, rank, sf, a, csr, s, col, enc, false);
@@ -168,11 +191,11 @@ __device__ __forceinline__ void wire_passes(double2* row, int rank, int sf, cons
                                : U2{{M_SQRT1_2, 0.0}, {0.0, -M_SQRT1_2}, {M_SQRT1_2, 0.0}, {0.0, M_SQRT1_2}};
         if (KIND == 0) {
             const double2 c0 = csr[col + P::t];
-            apply_gate<1>(e, U2{{c0.x, 0.0}, {0.0, -c0.y}, {0.0, -c0.y}, {c0.x, 0.0}});
+            apply_gate<1>(e, encoding_rx(c0));
             depolarize1<1>(e, a);
             if (J + 1 < N) {
                 const double2 c1 = csr[col + P::c];
-                apply_gate<4>(e, U2{{c1.x, 0.0}, {0.0, -c1.y}, {0.0, -c1.y}, {c1.x, 0.0}});
+                apply_gate<4>(e, encoding_rx(c1));
                 depolarize1<4>(e, a);
             }
         } else {
@@ -185,6 +208,29 @@ __device__ __forceinline__ void wire_passes(double2* row, int rank, int sf, cons
     }
 }
 
+// ---- host --------------------------------------------------------------------------------------------------------------------
+
+// The family's kernels exist for n = 2..6 (4^n elements per row in LDS): f(std::integral_constant<int, n>) for the call's n
+template <class F>
+int dispatch_n(int n, F&& f) {
+    switch (n) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        default: return QHEA_EUNSUPPORTED;
+    }
+}
+
+// a forward kernel (density_fwd_kernel<N>, density_dev_fwd_kernel<N>): 256 / 4^(n-2) rows per workgroup; the state, h'[D], h2'[D]
+template <int N, class Args>
+int launch_density_fwd(void (*kernel)(Args), const Args& a, hipStream_t st) {
+    constexpr int RPW = kDensThreads / (1 << (2 * N - 4));
+    constexpr size_t smem = kDensStateBytes + 2 * (1 << N) * sizeof(double);
+    return launch_dynamic_lds(kernel, dim3((unsigned)((a.B + RPW - 1) / RPW)), dim3(kDensThreads), smem, st, a);
+}
+
 struct DensLayout { size_t off_gates, off_cs, total; };
 
 DensLayout dens_layout(const ModelInfo& mi, int64_t B) {
@@ -192,18 +238,27 @@ DensLayout dens_layout(const ModelInfo& mi, int64_t B) {
     return DensLayout{t.off_gates, t.off_cs, t.end};
 }
 
+// what every argument record of the family holds of the circuit, its read-out and the prep tables (DensArgs, and the device
+// units' DensDevArgs and DevGradArgs, which name these members alike)
+template <class Args>
+void circuit_args(Args& a, const qhea_model_desc* desc, const ModelInfo& mi, const double* params, const double* ham_diag,
+                  int64_t batch, const double4* gates, const double2* cs) {
+    a.gates = gates; a.cs = cs; a.diag = ham_diag;
+    a.bias = mi.has_bias ? params + mi.off_bias : nullptr;
+    a.off = desc->ham_offset; a.co = desc->ham_coeff;
+    a.B = batch; a.E = (int)mi.sh.E; a.pauli = desc->ham_pauli;
+    for (int g = 0; g < 2; ++g) { a.nb[g] = mi.nb[g]; a.ld[g] = mi.ld[g]; }
+}
+
 // everything of DensArgs but the outputs (pred, sd)
 DensArgs dens_args(const qhea_model_desc* desc, const ModelInfo& mi, const qhea_noise* noise, const double* params,
                    const double* ham_diag, int64_t batch, const double4* gates, const double2* cs) {
     DensArgs a{};
-    a.gates = gates; a.cs = cs; a.diag = ham_diag;
-    a.bias = mi.has_bias ? params + mi.off_bias : nullptr;
-    a.off = desc->ham_offset; a.co = desc->ham_coeff; a.q = noise->readout;
+    circuit_args(a, desc, mi, params, ham_diag, batch, gates, cs);
+    a.q = noise->readout;
     a.d1_off = 1.0 - 4.0 * noise->p1 / 3.0; a.d1_keep = 1.0 - 2.0 * noise->p1 / 3.0; a.d1_mix = 2.0 * noise->p1 / 3.0;
     const double lam = 16.0 * noise->p2 / 15.0;
     a.d2_keep = 1.0 - lam; a.d2_mix = lam / 4.0;
-    a.B = batch; a.E = (int)mi.sh.E; a.pauli = desc->ham_pauli;
-    for (int g = 0; g < 2; ++g) { a.nb[g] = mi.nb[g]; a.ld[g] = mi.ld[g]; }
     return a;
 }
 }  // namespace

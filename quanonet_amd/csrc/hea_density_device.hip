@@ -36,22 +36,11 @@ struct DensDevArgs {
     double* sd;                             // or NULL
 };
 
-// the phase-covariant channel (off, a, b) of site SITE, wire Q on the 2 x 2 blocks of that wire (apply_gate's element order):
-// rho00' = k00 rho00 + k01 rho11, rho11' = k10 rho00 + k11 rho11.  The host forms the four k: arithmetic on launch constants
-// would be fp64 vector work whose results the compiler keeps in vector registers across the whole circuit loop.
+// the phase-covariant channel (off, a, b) of site SITE, wire Q on the 2 x 2 blocks of that wire (phase_covariant of
+// hea_density.hpp), its constants scalars of the launch
 template <int S, int SITE, int Q>
 __device__ __forceinline__ void channel1(double2 (&e)[16], const DensDevArgs& a) {
-    const double off = a.chan[SITE][Q][0];
-    const double k00 = a.chan[SITE][Q][1], k01 = a.chan[SITE][Q][2], k10 = a.chan[SITE][Q][3], k11 = a.chan[SITE][Q][4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int b = S == 1 ? 4 * m : m;
-        const double2 d0 = e[b], d1 = e[b + 3 * S];
-        e[b] = make_double2(k00 * d0.x + k01 * d1.x, k00 * d0.y + k01 * d1.y);
-        e[b + 3 * S] = make_double2(k10 * d0.x + k11 * d1.x, k10 * d0.y + k11 * d1.y);
-        e[b + S].x *= off; e[b + S].y *= off;
-        e[b + 2 * S].x *= off; e[b + 2 * S].y *= off;
-    }
+    phase_covariant<S>(e, a.chan[SITE][Q][0], a.chan[SITE][Q][1], a.chan[SITE][Q][2], a.chan[SITE][Q][3], a.chan[SITE][Q][4]);
 }
 
 // wire Q's pending gates of sub-layer s: (encoding RX, its site), fused RY RZ RY, its site
@@ -60,28 +49,12 @@ __device__ __forceinline__ void dev_wire_gates(double2 (&e)[16], const DensDevAr
                                                bool enc) {
     if (enc) {
         const double2 c = csr[col + Q];
-        apply_gate<S>(e, U2{{c.x, 0.0}, {0.0, -c.y}, {0.0, -c.y}, {c.x, 0.0}});
+        apply_gate<S>(e, encoding_rx(c));
         channel1<S, kEnc, Q>(e, a);
     }
     const double4 v = a.gates[2 * (s * N + Q + N)];                      // (u00, u01); u10 = -conj(u01), u11 = conj(u00)
     apply_gate<S>(e, U2{{v.x, v.y}, {v.z, v.w}, {-v.z, v.w}, {v.x, -v.y}});
     channel1<S, kRot, Q>(e, a);
-}
-
-// CNOT(c -> t) on both indices, then slot J's two-qubit channel (cnot_depolarize2 with the slot's own lam)
-template <int J>
-__device__ __forceinline__ void dev_cnot_depolarize2(double2 (&e)[16], const DensDevArgs& a) {
-    const double keep = a.keep2[J], mix = a.mix2[J];
-    double2 r[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r[k] = e[k ^ ((k >> 2) & 1) ^ (((k >> 3) & 1) << 1)];
-    const double sx = (r[0].x + r[3].x) + (r[12].x + r[15].x), sy = (r[0].y + r[3].y) + (r[12].y + r[15].y);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const bool eq = k == 0 || k == 3 || k == 12 || k == 15;          // row bits (c, t) = column bits
-        e[k].x = eq ? keep * r[k].x + mix * sx : keep * r[k].x;
-        e[k].y = eq ? keep * r[k].y + mix * sy : keep * r[k].y;
-    }
 }
 
 // ring_passes of hea_density.hpp with the device channels: slot J's CNOT, its two-qubit channel, then the target site of
@@ -101,7 +74,7 @@ __device__ __forceinline__ void dev_ring_passes(double2* row, int rank, int sf, 
         }
         if (J == 0) dev_wire_gates<N, 1, P::t>(e, a, csr, s, col, enc);
         if (J <= N - 2) dev_wire_gates<N, 4, P::c>(e, a, csr, s, col, enc);
-        dev_cnot_depolarize2<J>(e, a);
+        cnot_depolarize2(e, a.keep2[J], a.mix2[J]);
         channel1<1, kTgt, P::t>(e, a);
         channel1<4, kCtl, P::c>(e, a);
         P::store(e, row, b);
@@ -125,11 +98,11 @@ __device__ __forceinline__ void dev_enc_passes(double2* row, int rank, int sf, c
             P::load(e, row, b);
         }
         const double2 c0 = csr[col + P::t];
-        apply_gate<1>(e, U2{{c0.x, 0.0}, {0.0, -c0.y}, {0.0, -c0.y}, {c0.x, 0.0}});
+        apply_gate<1>(e, encoding_rx(c0));
         channel1<1, kEnc, P::t>(e, a);
         if (J + 1 < N) {
             const double2 c1 = csr[col + P::c];
-            apply_gate<4>(e, U2{{c1.x, 0.0}, {0.0, -c1.y}, {0.0, -c1.y}, {c1.x, 0.0}});
+            apply_gate<4>(e, encoding_rx(c1));
             channel1<4, kEnc, P::c>(e, a);
         }
         P::store(e, row, b);
@@ -214,13 +187,6 @@ __global__ __launch_bounds__(kDensThreads) void density_dev_fwd_kernel(DensDevAr
     }
 }
 
-template <int N>
-int launch_density_dev(const DensDevArgs& a, hipStream_t st) {
-    constexpr int RPW = kDensThreads / (1 << (2 * N - 4));
-    constexpr size_t smem = kDensStateBytes + 2 * (1 << N) * sizeof(double);
-    return launch_dynamic_lds(density_dev_fwd_kernel<N>, dim3((unsigned)((a.B + RPW - 1) / RPW)), dim3(kDensThreads), smem, st, a);
-}
-
 }  // namespace
 }  // namespace qhea
 
@@ -240,20 +206,9 @@ int qhea_model_forward_noisy_device_exact(const qhea_model_desc* desc, int64_t b
                                           const double* params, const double* ham_diag, const qhea_device_noise* dn,
                                           double* pred, double* shot_std, void* workspace, size_t workspace_bytes,
                                           void* stream) {
-    // noisy_call_check (hea_noise_traj.hpp, shared with the uniform calls and left as it is) reads the model itself and wants a
-    // qhea_noise to check; the device setting has to be checked against the model's n before it, so the model is read twice
-    // (host arithmetic on the descriptor) and the shared checks get an all-zero qhea_noise.  model_info appends to the record's
-    // block list, so the first reading goes into a record of its own: filling c.mi twice would double the sub-layer count,
-    // and with it the gate table of the workspace and what prep_model_kernel reads of `params`.
-    ModelInfo probe;
-    int rc = model_info(desc, probe);
-    if (rc != QHEA_OK) return rc;
-    rc = device_noise_check(probe.n, dn);
-    if (rc != QHEA_OK) return rc;
     NoisyCall c;
-    const qhea_noise none{};
-    rc = noisy_call_check({QHEA_MIN_QUBITS, kDevMaxWires /* 4^n elements per row in LDS */, false, false}, desc, ham_diag, &none,
-                          0, batch, trunk, {branch, params, pred}, workspace, stream, c);
+    int rc = device_call_check({QHEA_MIN_QUBITS, kDevMaxWires /* 4^n elements per row in LDS */, false, false}, desc, ham_diag, dn,
+                               nullptr, batch, trunk, {branch, params, pred}, workspace, stream, c);
     if (rc != QHEA_OK || c.empty) return rc;
     const DensLayout L = dens_layout(c.mi, batch);
     if (!workspace || workspace_bytes < L.total) return QHEA_EWORKSPACE;
@@ -264,32 +219,15 @@ int qhea_model_forward_noisy_device_exact(const qhea_model_desc* desc, int64_t b
 
     const int n = c.mi.n;
     DensDevArgs a{};
-    a.gates = gates; a.cs = cs; a.diag = ham_diag;
-    a.bias = c.mi.has_bias ? params + c.mi.off_bias : nullptr;
-    a.off = desc->ham_offset; a.co = desc->ham_coeff;
-    double chan[4][kDevMaxWires][3] = {}, lam2[kDevMaxWires] = {};
-    device_noise_compose(n, dn, &chan[0][0][0], kDevMaxWires, lam2);
+    circuit_args(a, desc, c.mi, params, ham_diag, batch, gates, cs);
+    const DevSites sites(n, dn);
     for (int q = 0; q < n; ++q) {
-        for (int k = 0; k < 4; ++k) {
-            const double ca = chan[k][q][1], cb = chan[k][q][2];
-            a.chan[k][q][0] = chan[k][q][0];
-            a.chan[k][q][1] = 0.5 * (1.0 + ca + cb); a.chan[k][q][2] = 0.5 * (1.0 - ca + cb);
-            a.chan[k][q][3] = 0.5 * (1.0 - ca - cb); a.chan[k][q][4] = 0.5 * (1.0 + ca - cb);
-        }
-        a.keep2[q] = 1.0 - lam2[q]; a.mix2[q] = 0.25 * lam2[q];
+        for (int k = 0; k < 4; ++k) element_form(sites.at(k, q), a.chan[k][q]);
+        slot_form(sites.lam2[q], a.keep2[q], a.mix2[q]);
         a.r01[q] = dn->readout01[q]; a.r10[q] = dn->readout10[q];
     }
-    a.B = batch; a.E = (int)c.mi.sh.E; a.pauli = desc->ham_pauli;
-    for (int g = 0; g < 2; ++g) { a.nb[g] = c.mi.nb[g]; a.ld[g] = c.mi.ld[g]; }
     a.pred = pred; a.sd = shot_std;
-    switch (n) {
-        case 2: return launch_density_dev<2>(a, c.st);
-        case 3: return launch_density_dev<3>(a, c.st);
-        case 4: return launch_density_dev<4>(a, c.st);
-        case 5: return launch_density_dev<5>(a, c.st);
-        case 6: return launch_density_dev<6>(a, c.st);
-        default: return QHEA_EUNSUPPORTED;
-    }
+    return dispatch_n(n, [&](auto nn) { return launch_density_fwd<nn()>(density_dev_fwd_kernel<nn()>, a, c.st); });
 }
 
 }  // extern "C"

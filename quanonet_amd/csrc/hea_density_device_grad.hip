@@ -25,8 +25,6 @@
 
 #include "hea_density_grad.hpp"
 #include "hea_device_noise.hpp"
-#include "hea_train.hpp"
-#include "hea_sincos.hpp"
 
 namespace qhea {
 namespace {
@@ -78,15 +76,7 @@ template <int S>
 __device__ __forceinline__ void channel5(double2 (&e)[16], const double* c) {
     const double off = uniform_load(c), k00 = uniform_load(c + 1), k01 = uniform_load(c + 2), k10 = uniform_load(c + 3),
                  k11 = uniform_load(c + 4);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int b = S == 1 ? 4 * m : m;
-        const double2 d0 = e[b], d1 = e[b + 3 * S];
-        e[b] = make_double2(k00 * d0.x + k01 * d1.x, k00 * d0.y + k01 * d1.y);
-        e[b + 3 * S] = make_double2(k10 * d0.x + k11 * d1.x, k10 * d0.y + k11 * d1.y);
-        e[b + S].x *= off; e[b + S].y *= off;
-        e[b + 2 * S].x *= off; e[b + 2 * S].y *= off;
-    }
+    phase_covariant<S>(e, off, k00, k01, k10, k11);
 }
 
 __device__ __forceinline__ const double* site_at(const double* tab, int q, int site, int form) {
@@ -94,36 +84,24 @@ __device__ __forceinline__ const double* site_at(const double* tab, int q, int s
 }
 
 // ---- forward sweep: the passes of density_dev_fwd_kernel with the constants read from the table ----
-// dev_wire_gates, dev_cnot_depolarize2, dev_ring_passes and dev_enc_passes below are hea_density_device.hip's functions of the
-// same names, statement for statement; only where a site's constants come from differs (there: members of the by-value
-// argument indexed at compile time; here: the workspace table, loaded inside the pass).  A change to the forward model is
-// made in both; tests/test_device_noise_training.py holds this sweep's pred to the forward call's within 1e-13.
+// dev_wire_gates, dev_ring_passes and dev_enc_passes below are hea_density_device.hip's functions of the same names, statement
+// for statement (the channel bodies they call, phase_covariant and cnot_depolarize2 of hea_density.hpp, are shared); only where a
+// site's constants come from differs (there: members of the by-value argument indexed at compile time; here: the workspace
+// table, loaded inside the pass).  Templated over that source they changed this unit's code (profiles/
+// r28_device_code_identity.txt), so a change to the forward model is made in both; tests/test_device_noise_training.py holds
+// this sweep's pred to the forward call's within 1e-13.
 
 template <int N, int S>
 __device__ __forceinline__ void dev_wire_gates(double2 (&e)[16], const DevGradArgs& a, const double* tab, const double2* csr,
                                                int s, int col, bool enc, int q) {
     if (enc) {
         const double2 c = csr[col + q];
-        apply_gate<S>(e, U2{{c.x, 0.0}, {0.0, -c.y}, {0.0, -c.y}, {c.x, 0.0}});
+        apply_gate<S>(e, encoding_rx(c));
         channel5<S>(e, site_at(tab, q, kEnc, kFormFwd));
     }
     const double4 v = a.gates[2 * (s * N + q + N)];                      // (u00, u01); u10 = -conj(u01), u11 = conj(u00)
     apply_gate<S>(e, U2{{v.x, v.y}, {v.z, v.w}, {-v.z, v.w}, {v.x, -v.y}});
     channel5<S>(e, site_at(tab, q, kRot, kFormFwd));
-}
-
-// CNOT(c -> t) on both indices, then the two-qubit channel (keep, mix)
-__device__ __forceinline__ void dev_cnot_depolarize2(double2 (&e)[16], double keep, double mix) {
-    double2 r[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r[k] = e[k ^ ((k >> 2) & 1) ^ (((k >> 3) & 1) << 1)];
-    const double sx = (r[0].x + r[3].x) + (r[12].x + r[15].x), sy = (r[0].y + r[3].y) + (r[12].y + r[15].y);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const bool eq = k == 0 || k == 3 || k == 12 || k == 15;          // row bits (c, t) = column bits
-        e[k].x = eq ? keep * r[k].x + mix * sx : keep * r[k].x;
-        e[k].y = eq ? keep * r[k].y + mix * sy : keep * r[k].y;
-    }
 }
 
 template <int N, int J>
@@ -142,7 +120,7 @@ __device__ __forceinline__ void dev_ring_passes(double2* row, int rank, int sf, 
         }
         if (J == 0) dev_wire_gates<N, 1>(e, a, tab, csr, s, col, enc, P::t);
         if (J <= N - 2) dev_wire_gates<N, 4>(e, a, tab, csr, s, col, enc, P::c);
-        dev_cnot_depolarize2(e, uniform_load(tab + J * kTabWire + kTabSlot), uniform_load(tab + J * kTabWire + kTabSlot + 1));
+        cnot_depolarize2(e, uniform_load(tab + J * kTabWire + kTabSlot), uniform_load(tab + J * kTabWire + kTabSlot + 1));
         channel5<1>(e, site_at(tab, P::t, kTgt, kFormFwd));
         channel5<4>(e, site_at(tab, P::c, kCtl, kFormFwd));
         P::store(e, row, b);
@@ -166,11 +144,11 @@ __device__ __forceinline__ void dev_enc_passes(double2* row, int rank, int sf, c
             P::load(e, row, b);
         }
         const double2 c0 = csr[col + P::t];
-        apply_gate<1>(e, U2{{c0.x, 0.0}, {0.0, -c0.y}, {0.0, -c0.y}, {c0.x, 0.0}});
+        apply_gate<1>(e, encoding_rx(c0));
         channel5<1>(e, site_at(tab, P::t, kEnc, kFormFwd));
         if (J + 1 < N) {
             const double2 c1 = csr[col + P::c];
-            apply_gate<4>(e, U2{{c1.x, 0.0}, {0.0, -c1.y}, {0.0, -c1.y}, {c1.x, 0.0}});
+            apply_gate<4>(e, encoding_rx(c1));
             channel5<4>(e, site_at(tab, P::c, kEnc, kFormFwd));
         }
         P::store(e, row, b);
@@ -203,20 +181,7 @@ template <int N, int S>
 __device__ __forceinline__ void dev_undo_wire(double2 (&e)[16], double2 (&o)[16], const DevGradArgs& a, const double* tab,
                                               const double2* csr, int s, int col, bool enc, int q, double* tr) {
     undo_site<S>(e, o, tab, q, kRot);
-    const double* ws = a.w + (long)s * 3 * N + q;
-    double sn, cn;
-    tr[2] = pinned(trace16<S, 1>(o, e));
-    fast_sincos(0.5 * ws[2 * N], &sn, &cn);
-    unrotate_y<S>(e, cn, sn);
-    unrotate_y<S>(o, cn, sn);
-    tr[1] = pinned(trace16<S, 2>(o, e));
-    fast_sincos(0.5 * ws[N], &sn, &cn);
-    unrotate_z<S>(e, cn, sn); unrotate_z<S>(o, cn, sn);
-    tr[0] = pinned(trace16<S, 1>(o, e));
-    fast_sincos(0.5 * ws[0], &sn, &cn);
-    unrotate_y<S>(e, cn, sn);
-    unrotate_y<S>(o, cn, sn);
-    tr[3] = 0.0;
+    undo_rotations<N, S>(e, o, a.w, s, q, tr);
     if (enc) dev_undo_encoding<S>(e, o, tab, q, csr[col + q], tr);
 }
 
@@ -394,32 +359,16 @@ __global__ __launch_bounds__(bwd_threads<N>()) void density_dev_bwd_kernel(DevGr
     }
 }
 
-template <int N>
-int launch_density_dev_bwd(const DevGradArgs& a, hipStream_t st) {
-    constexpr int T = bwd_threads<N>(), TPR = 1 << (2 * N - 4), RPW = T / TPR, WPR = TPR > 64 ? TPR / 64 : 1;
-    constexpr size_t smem = 2 * (size_t)RPW * (1 << (2 * N)) * sizeof(double2) + (1 << N) * sizeof(double) +
-                            2 * WPR * kTracesPerPass * sizeof(double);
-    return launch_dynamic_lds(density_dev_bwd_kernel<N>, dim3((unsigned)((a.B + RPW - 1) / RPW)), dim3(T), smem, st, a);
-}
-
 // ---- host ----
-
-// the element form (off, k00, k01, k10, k11) of a triple
-void element_form(const Triple& t, double* c) {
-    c[0] = t.off;
-    c[1] = 0.5 * (1.0 + t.a + t.b); c[2] = 0.5 * (1.0 - t.a + t.b);
-    c[3] = 0.5 * (1.0 - t.a - t.b); c[4] = 0.5 * (1.0 + t.a - t.b);
-}
 
 // the kernel's table for a checked setting whose channels are all invertible
 void fill_table(int n, const qhea_device_noise* dn, DevTable& t) {
-    double chan[4][kDevMaxWires][3] = {}, lam2[kDevMaxWires] = {};
-    device_noise_compose(n, dn, &chan[0][0][0], kDevMaxWires, lam2);
+    const DevSites sites(n, dn);
     for (int i = 0; i < kTabDoubles; ++i) t.v[i] = 0.0;
     for (int q = 0; q < n; ++q) {
         double* w = t.v + q * kTabWire;
         for (int k = 0; k < 4; ++k) {
-            const Triple f{chan[k][q][0], chan[k][q][1], chan[k][q][2]};
+            const Triple f = sites.at(k, q);
             double* c = w + k * kTabSite;
             element_form(f, c + 5 * kFormFwd);
             element_form(Triple{1.0 / f.off, 1.0 / f.a, -f.b / f.a}, c + 5 * kFormInv);
@@ -427,9 +376,8 @@ void fill_table(int n, const qhea_device_noise* dn, DevTable& t) {
             const double k01 = c[5 * kFormAdj + 2];                      // the adjoint's weight matrix is the transposed one
             c[5 * kFormAdj + 2] = c[5 * kFormAdj + 3]; c[5 * kFormAdj + 3] = k01;
         }
-        const double keep = 1.0 - lam2[q];
-        w[kTabSlot] = keep; w[kTabSlot + 1] = 0.25 * lam2[q];
-        w[kTabSlot + 2] = 1.0 / keep; w[kTabSlot + 3] = -0.25 * lam2[q] / keep;
+        slot_form(sites.lam2[q], w[kTabSlot], w[kTabSlot + 1]);
+        w[kTabSlot + 2] = 1.0 / w[kTabSlot]; w[kTabSlot + 3] = -w[kTabSlot + 1] / w[kTabSlot];
         w[kTabRead] = dn->readout01[q]; w[kTabRead + 1] = dn->readout10[q];
     }
 }
@@ -464,76 +412,41 @@ double device_log10_amplification(const ModelInfo& mi, const qhea_device_noise* 
 // largest probed value that stays under the 1e-12 the uniform bound was held to.
 constexpr double kMaxLog10AmplificationDevice = 7.0;
 
-struct DevGradLayout { DensGradLayout g; size_t off_tab, total; };
-
-DevGradLayout dev_grad_layout(const ModelInfo& mi, int64_t B) {
-    DevGradLayout L{};
-    L.g = dens_grad_layout(mi, B);
-    L.off_tab = L.g.total;
-    L.total = align256(L.off_tab + kTabDoubles * sizeof(double));
-    return L;
-}
-
-constexpr NoisyKind kDevGradKind{QHEA_MIN_QUBITS, kDevMaxWires /* 2 x 4^n elements per row in LDS */, false, false};
-
-// What opens both calls, in the order the ABI reports it: the descriptor, the setting's QHEA_EINVAL cases (the forward device
-// call's checking code), QHEA_EUNSUPPORTED for n >= 7 and the guard, then the shared checks of the uniform gradient call (which
-// get an all-zero qhea_noise: the guard has been answered here).  The model is read into a record of its own first, as in
-// hea_density_device.hip: model_info appends to the record's block list.
-int dev_grad_check(const qhea_model_desc* desc, const double* ham_diag, const qhea_device_noise* dn, int64_t count,
-                   const double* trunk, std::initializer_list<const void*> required, void* workspace, void* stream,
-                   NoisyCall& c) {
-    ModelInfo probe;
-    int rc = model_info(desc, probe);
-    if (rc != QHEA_OK) return rc;
-    rc = device_noise_check(probe.n, dn);
-    if (rc != QHEA_OK) return rc;
-    if (probe.n > kDevMaxWires) return QHEA_EUNSUPPORTED;
-    if (!(device_log10_amplification(probe, dn) <= kMaxLog10AmplificationDevice)) return QHEA_EUNSUPPORTED;
-    const qhea_noise none{};
-    return noisy_call_check(kDevGradKind, desc, ham_diag, &none, 0, count, trunk, required, workspace, stream, c);
-}
-
-int launch_dev_table(const ModelInfo& mi, const qhea_device_noise* dn, char* ws, int64_t bmax, hipStream_t st) {
-    DevTable t;
-    fill_table(mi.n, dn, t);
-    hipLaunchKernelGGL(dev_table_kernel, dim3(1), dim3(64), 0, st, t, reinterpret_cast<double*>(ws + dev_grad_layout(mi, bmax).off_tab));
-    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
-}
-
-// prep, density backward, reduce (+ Adam when adam.p) for one batch; the arguments have been checked and the table (at the
-// offset of a workspace for `bmax` rows) written
-int dev_loss_grad_launch(const qhea_model_desc* desc, const ModelInfo& mi, int64_t batch, int64_t bmax, const double* branch,
-                         const double* trunk, const double* y, const double* params, const double* ham_diag, double inv_bt,
-                         double* grad, double* pred, char* ws, hipStream_t st, const AdamArgs& adam) {
-    const DensGradLayout L = dens_grad_layout(mi, batch);
-    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
-    int rc = launch_prep_model(desc, mi, batch, branch, trunk, params, gates, cs, ws, st);
-    if (rc != QHEA_OK) return rc;
-
-    DevGradArgs a{};
-    a.gates = gates; a.cs = cs; a.diag = ham_diag;
-    a.bias = mi.has_bias ? params + mi.off_bias : nullptr;
-    a.tab = reinterpret_cast<const double*>(ws + dev_grad_layout(mi, bmax).off_tab);
-    a.w = params + mi.off_ans;
-    a.off = desc->ham_offset; a.co = desc->ham_coeff;
-    a.B = batch; a.E = (int)mi.sh.E; a.pauli = desc->ham_pauli;
-    for (int g = 0; g < 2; ++g) { a.nb[g] = mi.nb[g]; a.ld[g] = mi.ld[g]; }
-    a.pred = pred;
-    a.pred_ws = reinterpret_cast<double*>(ws + L.off_pred);
-    a.rec = reinterpret_cast<double*>(ws + L.off_rec);
-    switch (mi.n) {
-        case 2: rc = launch_density_dev_bwd<2>(a, st); break;
-        case 3: rc = launch_density_dev_bwd<3>(a, st); break;
-        case 4: rc = launch_density_dev_bwd<4>(a, st); break;
-        case 5: rc = launch_density_dev_bwd<5>(a, st); break;
-        case 6: rc = launch_density_dev_bwd<6>(a, st); break;
-        default: rc = QHEA_EUNSUPPORTED;
+// The unit record of grad_loss_grad / grad_train_steps (hea_density_grad.hpp): the channel sites of a qhea_device_noise.  Its
+// workspace is the uniform unit's with the table behind it.
+struct DevGradUnit {
+    using Noise = qhea_device_noise;
+    static constexpr bool kStepCheckFirst = false;
+    static size_t off_tab(const ModelInfo& mi, int64_t B) { return dens_grad_layout(mi, B).total; }
+    static size_t workspace_bytes(const ModelInfo& mi, int64_t B) { return align256(off_tab(mi, B) + kTabDoubles * sizeof(double)); }
+    // QHEA_EUNSUPPORTED for n >= 7 and for what the guard refuses, between the setting's checks and the shared ones (which get
+    // an all-zero qhea_noise: the guard has been answered here)
+    static int refuse(const ModelInfo& mi, const qhea_device_noise* dn) {
+        if (mi.n > kDevMaxWires) return QHEA_EUNSUPPORTED;
+        return device_log10_amplification(mi, dn) <= kMaxLog10AmplificationDevice ? QHEA_OK : QHEA_EUNSUPPORTED;
     }
-    if (rc != QHEA_OK) return rc;
-    return launch_density_reduce(desc, mi, batch, branch, trunk, y, a.rec, a.pred_ws, inv_bt, grad, adam, st);
-}
+    static int check(const qhea_model_desc* desc, const double* ham_diag, const qhea_device_noise* dn, int64_t count,
+                     const double* trunk, std::initializer_list<const void*> required, void* workspace, void* stream,
+                     NoisyCall& c) {
+        return device_call_check({QHEA_MIN_QUBITS, kDevMaxWires /* 2 x 4^n elements per row in LDS */, false, false}, desc,
+                                 ham_diag, dn, refuse, count, trunk, required, workspace, stream, c);
+    }
+    // the table, at its offset in a workspace for `bmax` rows
+    static int once(const ModelInfo& mi, const qhea_device_noise* dn, char* ws, int64_t bmax, hipStream_t st) {
+        DevTable t;
+        fill_table(mi.n, dn, t);
+        hipLaunchKernelGGL(dev_table_kernel, dim3(1), dim3(64), 0, st, t, reinterpret_cast<double*>(ws + off_tab(mi, bmax)));
+        return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+    }
+    static int launch_bwd(const GradBatch& b, const qhea_device_noise*) {
+        DevGradArgs a{};
+        circuit_args(a, b.desc, b.mi, b.params, b.ham_diag, b.batch, b.gates, b.cs);
+        a.tab = reinterpret_cast<const double*>(b.ws + off_tab(b.mi, b.bmax));
+        a.w = b.params + b.mi.off_ans;
+        a.pred = b.pred; a.pred_ws = b.pred_ws; a.rec = b.rec;
+        return dispatch_n(b.mi.n, [&](auto n) { return launch_density_bwd<n()>(density_dev_bwd_kernel<n()>, a.B, a, b.st); });
+    }
+};
 
 }  // namespace
 }  // namespace qhea
@@ -543,9 +456,7 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_device_noisy_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch) {
-    ModelInfo mi;
-    if (batch < 0 || model_info(desc, mi) != QHEA_OK) return 0;
-    return dev_grad_layout(mi, batch).total;
+    return grad_workspace_bytes<DevGradUnit>(desc, batch);
 }
 
 double qhea_model_device_noisy_log10_amplification(const qhea_model_desc* desc, const qhea_device_noise* dn) {
@@ -558,14 +469,8 @@ int qhea_model_loss_grad_noisy_device_exact(const qhea_model_desc* desc, int64_t
                                             const double* trunk, const double* y, const double* params, const double* ham_diag,
                                             const qhea_device_noise* dn, double inv_batch_total, double* grad, double* pred,
                                             void* workspace, size_t workspace_bytes, void* stream) {
-    NoisyCall c;
-    int rc = dev_grad_check(desc, ham_diag, dn, batch, trunk, {branch, y, params, grad}, workspace, stream, c);
-    if (rc != QHEA_OK || c.empty) return rc;
-    if (!workspace || workspace_bytes < dev_grad_layout(c.mi, batch).total) return QHEA_EWORKSPACE;
-    rc = launch_dev_table(c.mi, dn, c.ws, batch, c.st);
-    if (rc != QHEA_OK) return rc;
-    return dev_loss_grad_launch(desc, c.mi, batch, batch, branch, trunk, y, params, ham_diag, inv_batch_total, grad, pred, c.ws,
-                                c.st, AdamArgs{});
+    return grad_loss_grad<DevGradUnit>(desc, batch, branch, trunk, y, params, ham_diag, dn, inv_batch_total, grad, pred, workspace,
+                                       workspace_bytes, stream);
 }
 
 int qhea_model_train_steps_noisy_device_exact(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
@@ -575,26 +480,9 @@ int qhea_model_train_steps_noisy_device_exact(const qhea_model_desc* desc, int64
                                               double* exp_avg_sq, int64_t first_step, double lr, double beta1, double beta2,
                                               double eps, double weight_decay, void* workspace, size_t workspace_bytes,
                                               void* stream) {
-    NoisyCall c;
-    int rc = dev_grad_check(desc, ham_diag, dn, n_steps, trunk,
-                            {row_begin, inv_batch_total, branch, y, grad, params, exp_avg, exp_avg_sq}, workspace, stream, c);
-    if (rc != QHEA_OK) return rc;
-    if (first_step < 1) return QHEA_EINVAL;
-    if (c.empty) return QHEA_OK;
     const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
                          first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
-    const int64_t bmax = call_max_batch(call, c.mi.P, *desc);
-    if (bmax < 0) return QHEA_EINVAL;
-    if (!workspace || workspace_bytes < dev_grad_layout(c.mi, bmax).total) return QHEA_EWORKSPACE;     // (every region grows with the batch)
-    rc = launch_dev_table(c.mi, dn, c.ws, bmax, c.st);
-    if (rc != QHEA_OK) return rc;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const StepView v = step_view(call, i, *desc);
-        rc = dev_loss_grad_launch(desc, c.mi, v.nb, bmax, v.branch, v.trunk, v.y, params, ham_diag, v.inv_bt, v.grad, nullptr,
-                                  c.ws, c.st, adam_step(call, i, lr).adam);
-        if (rc != QHEA_OK) return rc;
-    }
-    return QHEA_OK;
+    return grad_train_steps<DevGradUnit>(desc, call, ham_diag, dn, lr);
 }
 
 }  // extern "C"

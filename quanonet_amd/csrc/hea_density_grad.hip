@@ -18,10 +18,9 @@
 // lane sums by the same butterfly), applies the frequency chain rule and -- train_steps -- the Adam update of hea_adam.hpp.
 // No atomics; nothing depends on the grid, and a row's record and pred do not depend on the batch or on other rows.
 // What the walk shares with hea_density_device_grad.hip (the same walk over the channel sites of a device noise model) is in
-// hea_density_grad.hpp; launch_density_reduce at the end of this file serves both units.
+// hea_density_grad.hpp, the body of both units' entry points included (this unit's record is DensGradUnit below);
+// launch_density_reduce at the end of this file serves both units.
 #include "hea_density_grad.hpp"
-#include "hea_train.hpp"
-#include "hea_sincos.hpp"
 
 namespace qhea {
 namespace {
@@ -67,20 +66,7 @@ __device__ __forceinline__ void undo_wire(double2 (&e)[16], double2 (&o)[16], co
                                           int col, bool enc, int q, double* tr) {
     channel1<S>(e, a.r1_keep, a.r1_mix, a.r1_off);
     channel1<S>(o, a.o1_keep, a.o1_mix, a.o1_off);
-    const double* ws = a.w + (long)s * 3 * N + q;
-    double sn, cn;
-    tr[2] = pinned(trace16<S, 1>(o, e));
-    fast_sincos(0.5 * ws[2 * N], &sn, &cn);
-    unrotate_y<S>(e, cn, sn);
-    unrotate_y<S>(o, cn, sn);
-    tr[1] = pinned(trace16<S, 2>(o, e));
-    fast_sincos(0.5 * ws[N], &sn, &cn);
-    unrotate_z<S>(e, cn, sn); unrotate_z<S>(o, cn, sn);
-    tr[0] = pinned(trace16<S, 1>(o, e));
-    fast_sincos(0.5 * ws[0], &sn, &cn);
-    unrotate_y<S>(e, cn, sn);
-    unrotate_y<S>(o, cn, sn);
-    tr[3] = 0.0;
+    undo_rotations<N, S>(e, o, a.w, s, q, tr);
     if (enc) undo_encoding<S>(e, o, a, csr[col + q], tr);
 }
 
@@ -303,48 +289,31 @@ __global__ __launch_bounds__(64 * kRedWaves) void reduce_density_kernel(DensRed 
     }
 }
 
-template <int N>
-int launch_density_bwd(const DensGradArgs& a, hipStream_t st) {
-    constexpr int T = bwd_threads<N>(), TPR = 1 << (2 * N - 4), RPW = T / TPR, WPR = TPR > 64 ? TPR / 64 : 1;
-    constexpr size_t smem = 2 * (size_t)RPW * (1 << (2 * N)) * sizeof(double2) + (1 << N) * sizeof(double) +
-                            2 * WPR * kTracesPerPass * sizeof(double);
-    return launch_dynamic_lds(density_bwd_kernel<N>, dim3((unsigned)((a.f.B + RPW - 1) / RPW)), dim3(T), smem, st, a);
-}
-
-constexpr NoisyKind kGradKind{QHEA_MIN_QUBITS, 6 /* 2 x 4^n elements per row in LDS */, false, true};
-
-// prep, density backward, reduce (+ Adam when adam.p) for one batch; the arguments have been checked
-int loss_grad_launch(const qhea_model_desc* desc, const ModelInfo& mi, int64_t batch, const double* branch, const double* trunk,
-                     const double* y, const double* params, const double* ham_diag, const qhea_noise* noise, double inv_bt,
-                     double* grad, double* pred, char* ws, hipStream_t st, const AdamArgs& adam) {
-    const DensGradLayout L = dens_grad_layout(mi, batch);
-    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
-    int rc = launch_prep_model(desc, mi, batch, branch, trunk, params, gates, cs, ws, st);
-    if (rc != QHEA_OK) return rc;
-
-    DensGradArgs a{};
-    a.f = dens_args(desc, mi, noise, params, ham_diag, batch, gates, cs);
-    a.f.pred = pred; a.f.sd = nullptr;
-    a.w = params + mi.off_ans;
-    a.o1_keep = a.f.d1_keep; a.o1_mix = a.f.d1_mix; a.o1_off = a.f.d1_off;
-    a.r1_off = 1.0 / a.f.d1_off; a.r1_keep = a.f.d1_keep * a.r1_off; a.r1_mix = -a.f.d1_mix * a.r1_off;
-    a.o2_keep = a.f.d2_keep; a.o2_mix = a.f.d2_mix;
-    a.r2_keep = 1.0 / a.f.d2_keep; a.r2_mix = -a.f.d2_mix * a.r2_keep;
-    a.pred_ws = reinterpret_cast<double*>(ws + L.off_pred);
-    a.rec = reinterpret_cast<double*>(ws + L.off_rec);
-    switch (mi.n) {
-        case 2: rc = launch_density_bwd<2>(a, st); break;
-        case 3: rc = launch_density_bwd<3>(a, st); break;
-        case 4: rc = launch_density_bwd<4>(a, st); break;
-        case 5: rc = launch_density_bwd<5>(a, st); break;
-        case 6: rc = launch_density_bwd<6>(a, st); break;
-        default: rc = QHEA_EUNSUPPORTED;
+// The unit record of grad_loss_grad / grad_train_steps (hea_density_grad.hpp): the uniform channels of a qhea_noise
+struct DensGradUnit {
+    using Noise = qhea_noise;
+    static constexpr bool kStepCheckFirst = true;
+    static size_t workspace_bytes(const ModelInfo& mi, int64_t B) { return dens_grad_layout(mi, B).total; }
+    static int check(const qhea_model_desc* desc, const double* ham_diag, const qhea_noise* noise, int64_t count,
+                     const double* trunk, std::initializer_list<const void*> required, void* workspace, void* stream,
+                     NoisyCall& c) {
+        return noisy_call_check({QHEA_MIN_QUBITS, 6 /* 2 x 4^n elements per row in LDS */, false, true}, desc, ham_diag, noise, 0,
+                                count, trunk, required, workspace, stream, c);
     }
-    if (rc != QHEA_OK) return rc;
-
-    return launch_density_reduce(desc, mi, batch, branch, trunk, y, a.rec, a.pred_ws, inv_bt, grad, adam, st);
-}
+    static int once(const ModelInfo&, const qhea_noise*, char*, int64_t, hipStream_t) { return QHEA_OK; }
+    static int launch_bwd(const GradBatch& b, const qhea_noise* noise) {
+        DensGradArgs a{};
+        a.f = dens_args(b.desc, b.mi, noise, b.params, b.ham_diag, b.batch, b.gates, b.cs);
+        a.f.pred = b.pred; a.f.sd = nullptr;
+        a.w = b.params + b.mi.off_ans;
+        a.o1_keep = a.f.d1_keep; a.o1_mix = a.f.d1_mix; a.o1_off = a.f.d1_off;
+        a.r1_off = 1.0 / a.f.d1_off; a.r1_keep = a.f.d1_keep * a.r1_off; a.r1_mix = -a.f.d1_mix * a.r1_off;
+        a.o2_keep = a.f.d2_keep; a.o2_mix = a.f.d2_mix;
+        a.r2_keep = 1.0 / a.f.d2_keep; a.r2_mix = -a.f.d2_mix * a.r2_keep;
+        a.pred_ws = b.pred_ws; a.rec = b.rec;
+        return dispatch_n(b.mi.n, [&](auto n) { return launch_density_bwd<n()>(density_bwd_kernel<n()>, a.f.B, a, b.st); });
+    }
+};
 
 }  // namespace
 
@@ -371,9 +340,7 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_exact_noisy_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch) {
-    ModelInfo mi;
-    if (batch < 0 || model_info(desc, mi) != QHEA_OK) return 0;
-    return dens_grad_layout(mi, batch).total;
+    return grad_workspace_bytes<DensGradUnit>(desc, batch);
 }
 
 double qhea_model_exact_noisy_log10_amplification(const qhea_model_desc* desc, const qhea_noise* noise) {
@@ -386,12 +353,8 @@ int qhea_model_loss_grad_noisy_exact(const qhea_model_desc* desc, int64_t batch,
                                      const double* y, const double* params, const double* ham_diag, const qhea_noise* noise,
                                      double inv_batch_total, double* grad, double* pred, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    NoisyCall c;
-    const int rc = noisy_call_check(kGradKind, desc, ham_diag, noise, 0, batch, trunk, {branch, y, params, grad}, workspace, stream, c);
-    if (rc != QHEA_OK || c.empty) return rc;
-    if (!workspace || workspace_bytes < dens_grad_layout(c.mi, batch).total) return QHEA_EWORKSPACE;
-    return loss_grad_launch(desc, c.mi, batch, branch, trunk, y, params, ham_diag, noise, inv_batch_total, grad, pred, c.ws, c.st,
-                            AdamArgs{});
+    return grad_loss_grad<DensGradUnit>(desc, batch, branch, trunk, y, params, ham_diag, noise, inv_batch_total, grad, pred,
+                                        workspace, workspace_bytes, stream);
 }
 
 int qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
@@ -400,23 +363,9 @@ int qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n_st
                                        double* grad, int64_t grad_stride, double* exp_avg, double* exp_avg_sq,
                                        int64_t first_step, double lr, double beta1, double beta2, double eps,
                                        double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!desc || n_steps < 0 || first_step < 1) return QHEA_EINVAL;
-    NoisyCall c;
-    const int rc0 = noisy_call_check(kGradKind, desc, ham_diag, noise, 0, n_steps, trunk,
-                                     {row_begin, inv_batch_total, branch, y, grad, params, exp_avg, exp_avg_sq}, workspace, stream, c);
-    if (rc0 != QHEA_OK || c.empty) return rc0;
     const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
                          first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
-    const int64_t bmax = call_max_batch(call, c.mi.P, *desc);
-    if (bmax < 0) return QHEA_EINVAL;
-    if (!workspace || workspace_bytes < dens_grad_layout(c.mi, bmax).total) return QHEA_EWORKSPACE;    // (every region grows with the batch)
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const StepView v = step_view(call, i, *desc);
-        const int rc = loss_grad_launch(desc, c.mi, v.nb, v.branch, v.trunk, v.y, params, ham_diag, noise, v.inv_bt, v.grad,
-                                        nullptr, c.ws, c.st, adam_step(call, i, lr).adam);
-        if (rc != QHEA_OK) return rc;
-    }
-    return QHEA_OK;
+    return grad_train_steps<DensGradUnit>(desc, call, ham_diag, noise, lr);
 }
 
 }  // extern "C"

@@ -2,10 +2,12 @@
 // the uniform channels of qhea_noise; hea_density_device_grad.hip: the channel sites of qhea_device_noise): the two compiler
 // pins, a thread's share of a trace, the un-rotations, the reverse of the CNOT with its two-qubit channel, the row context with
 // the sum of a pass' traces over the row, the read-out basis passes, the workspace layout and the reduce launch.  The device
-// code sits in an unnamed namespace like hea_density.hpp's: each unit compiles its own copy into its own kernels.
+// code sits in an unnamed namespace like hea_density.hpp's: each unit compiles its own copy into its own kernels.  Host side:
+// the backward launcher and the one body of the units' entry points (grad_loss_grad, grad_train_steps over a unit record).
 #pragma once
 #include "hea_density.hpp"
 #include "hea_adam.hpp"
+#include "hea_sincos.hpp"
 
 namespace qhea {
 
@@ -28,6 +30,12 @@ constexpr int kTracesPerPass = 8;                                        // two 
 #endif
 template <int N> constexpr int bwd_threads() {
     return (1 << (2 * N - 4)) > QHEA_DENS_BWD_THREADS ? (1 << (2 * N - 4)) : QHEA_DENS_BWD_THREADS;
+}
+
+// LDS of a backward workgroup: rho and O of its rows, h'[D], and two buffers of the waves' trace partials (n = 6)
+template <int N> constexpr size_t bwd_lds_bytes() {
+    constexpr int TPR = 1 << (2 * N - 4), RPW = bwd_threads<N>() / TPR, WPR = TPR > 64 ? TPR / 64 : 1;
+    return 2 * (size_t)RPW * (1 << (2 * N)) * sizeof(double2) + (1 << N) * sizeof(double) + 2 * WPR * kTracesPerPass * sizeof(double);
 }
 
 // A pass' 32 LDS addresses depend on the thread alone, so the compiler computes those of every pass once, ahead of the loop
@@ -117,6 +125,26 @@ __device__ __forceinline__ void unrotate_z(double2 (&e)[16], double c, double s)
         e[b + S] = make_double2(C * x10.x + Sn * x10.y, C * x10.y - Sn * x10.x);
         e[b + 2 * S] = make_double2(C * x01.x - Sn * x01.y, C * x01.y + Sn * x01.x);
     }
+}
+
+// The fused rotation of wire q in sub-layer s in reverse, behind the unit's own channel: for RY(w2), RZ(w1), RY(w0) in turn the
+// trace, then the un-rotation of rho and O.  tr[k] = this thread's share of d pred / d w[s, k, q]; tr[3] (the encoding's) = 0.
+template <int N, int S>
+__device__ __forceinline__ void undo_rotations(double2 (&e)[16], double2 (&o)[16], const double* w, int s, int q, double* tr) {
+    const double* ws = w + (long)s * 3 * N + q;
+    double sn, cn;
+    tr[2] = pinned(trace16<S, 1>(o, e));
+    fast_sincos(0.5 * ws[2 * N], &sn, &cn);
+    unrotate_y<S>(e, cn, sn);
+    unrotate_y<S>(o, cn, sn);
+    tr[1] = pinned(trace16<S, 2>(o, e));
+    fast_sincos(0.5 * ws[N], &sn, &cn);
+    unrotate_z<S>(e, cn, sn); unrotate_z<S>(o, cn, sn);
+    tr[0] = pinned(trace16<S, 1>(o, e));
+    fast_sincos(0.5 * ws[0], &sn, &cn);
+    unrotate_y<S>(e, cn, sn);
+    unrotate_y<S>(o, cn, sn);
+    tr[3] = 0.0;
 }
 
 // channel (inverse on rho), then CNOT(c -> t) on both indices: the reverse of cnot_depolarize2
@@ -213,6 +241,101 @@ DensGradLayout dens_grad_layout(const ModelInfo& mi, int64_t B) {
     L.off_rec = p;  p = align256(p + (size_t)B * ((size_t)mi.sh.E + (size_t)3 * mi.n * mi.sh.blk) * sizeof(double));
     L.total = p;
     return L;
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+
+// a backward kernel (density_bwd_kernel<N>, density_dev_bwd_kernel<N>) over B rows
+template <int N, class Args>
+int launch_density_bwd(void (*kernel)(Args), long B, const Args& a, hipStream_t st) {
+    constexpr int T = bwd_threads<N>(), RPW = T / (1 << (2 * N - 4));
+    return launch_dynamic_lds(kernel, dim3((unsigned)((B + RPW - 1) / RPW)), dim3(T), bwd_lds_bytes<N>(), st, a);
+}
+
+// One batch of a gradient call as a unit's backward launch sees it: the checked call, the prep tables and the regions of the
+// workspace (laid out for `batch` rows; bmax: the rows the call's workspace was sized for)
+struct GradBatch {
+    const qhea_model_desc* desc; const ModelInfo& mi;
+    const double* params; const double* ham_diag;
+    int64_t batch, bmax;
+    const double4* gates; const double2* cs;
+    double* pred;                           // the caller's pred or NULL
+    double* pred_ws; double* rec;
+    char* ws; hipStream_t st;
+};
+
+// The body of the gradient units' entry points.  A unit record U (DensGradUnit of hea_density_grad.hip, DevGradUnit of
+// hea_density_device_grad.hip) gives
+//   Noise                              the call's noise setting (qhea_noise, qhea_device_noise)
+//   kStepCheckFirst                    where train_steps reports first_step < 1: true: with the descriptor and n_steps < 0, ahead
+//                                      of every other check; false: after U::check and before the return of a call without steps
+//   workspace_bytes(mi, B)             the call's workspace for B rows
+//   check(desc, ham_diag, noise, count, trunk, required, workspace, stream, c)      what opens the call
+//   once(mi, noise, ws, bmax, st)      what is launched once per call, or nothing
+//   launch_bwd(b, noise)               its argument record's fill and its backward kernel for b.mi.n
+
+// prep, density backward, reduce (+ Adam when adam.p) for one batch; the arguments have been checked and U::once has run
+template <class U>
+int grad_launch(const qhea_model_desc* desc, const ModelInfo& mi, int64_t batch, int64_t bmax, const double* branch,
+                const double* trunk, const double* y, const double* params, const double* ham_diag,
+                const typename U::Noise* noise, double inv_bt, double* grad, double* pred, char* ws, hipStream_t st,
+                const AdamArgs& adam) {
+    const DensGradLayout L = dens_grad_layout(mi, batch);
+    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
+    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
+    int rc = launch_prep_model(desc, mi, batch, branch, trunk, params, gates, cs, ws, st);
+    if (rc != QHEA_OK) return rc;
+    const GradBatch b{desc, mi, params, ham_diag, batch, bmax, gates, cs, pred, reinterpret_cast<double*>(ws + L.off_pred),
+                      reinterpret_cast<double*>(ws + L.off_rec), ws, st};
+    rc = U::launch_bwd(b, noise);
+    if (rc != QHEA_OK) return rc;
+    return launch_density_reduce(desc, mi, batch, branch, trunk, y, b.rec, b.pred_ws, inv_bt, grad, adam, st);
+}
+
+template <class U>
+size_t grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch) {
+    ModelInfo mi;
+    if (batch < 0 || model_info(desc, mi) != QHEA_OK) return 0;
+    return U::workspace_bytes(mi, batch);
+}
+
+template <class U>
+int grad_loss_grad(const qhea_model_desc* desc, int64_t batch, const double* branch, const double* trunk, const double* y,
+                   const double* params, const double* ham_diag, const typename U::Noise* noise, double inv_batch_total,
+                   double* grad, double* pred, void* workspace, size_t workspace_bytes, void* stream) {
+    NoisyCall c;
+    int rc = U::check(desc, ham_diag, noise, batch, trunk, {branch, y, params, grad}, workspace, stream, c);
+    if (rc != QHEA_OK || c.empty) return rc;
+    if (!workspace || workspace_bytes < U::workspace_bytes(c.mi, batch)) return QHEA_EWORKSPACE;
+    rc = U::once(c.mi, noise, c.ws, batch, c.st);
+    if (rc != QHEA_OK) return rc;
+    return grad_launch<U>(desc, c.mi, batch, batch, branch, trunk, y, params, ham_diag, noise, inv_batch_total, grad, pred, c.ws,
+                          c.st, AdamArgs{});
+}
+
+template <class U>
+int grad_train_steps(const qhea_model_desc* desc, const TrainCall& call, const double* ham_diag, const typename U::Noise* noise,
+                     double lr) {
+    if (U::kStepCheckFirst && (!desc || call.n_steps < 0 || call.first_step < 1)) return QHEA_EINVAL;
+    NoisyCall c;
+    int rc = U::check(desc, ham_diag, noise, call.n_steps, call.trunk,
+                      {call.row_begin, call.inv_batch_total, call.branch, call.y, call.grad, call.params, call.exp_avg,
+                       call.exp_avg_sq}, call.workspace, call.stream, c);
+    if (rc != QHEA_OK) return rc;
+    if (call.first_step < 1) return QHEA_EINVAL;
+    if (c.empty) return QHEA_OK;
+    const int64_t bmax = call_max_batch(call, c.mi.P, *desc);
+    if (bmax < 0) return QHEA_EINVAL;
+    if (!call.workspace || call.workspace_bytes < U::workspace_bytes(c.mi, bmax)) return QHEA_EWORKSPACE;    // (every region grows with the batch)
+    rc = U::once(c.mi, noise, c.ws, bmax, c.st);
+    if (rc != QHEA_OK) return rc;
+    for (int64_t i = 0; i < call.n_steps; ++i) {
+        const StepView v = step_view(call, i, *desc);
+        rc = grad_launch<U>(desc, c.mi, v.nb, bmax, v.branch, v.trunk, v.y, call.params, ham_diag, noise, v.inv_bt, v.grad, nullptr,
+                            c.ws, c.st, adam_step(call, i, lr).adam);
+        if (rc != QHEA_OK) return rc;
+    }
+    return QHEA_OK;
 }
 
 }  // namespace

@@ -1,11 +1,13 @@
 // hea_device_noise.hpp -- host side of the calibrated device noise model (qhea_device_noise, include/quanonet_hea.h) for the
 // units that evaluate it (hea_density_device.hip, hea_density_device_grad.hip; the trajectory units hea_noise_device.hip and
-// hea_noise_device_wide.hip): the checks of a setting, the composition of its channels into the four sites per wire, and for the
-// trajectories the (gamma, pz) of every site and the fill of a unit's table of per-call thresholds.  No device code.
+// hea_noise_device_wide.hip): the checks of a setting and what opens a density-matrix call under one, the composition of its
+// channels into the four sites per wire and their form in the kernels' tables, and for the trajectories the (gamma, pz) of every
+// site and the fill of a unit's table of per-call thresholds.  No device code.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include "../../include/quanonet_hea.h"
+#include "hea_noise_traj.hpp"
 
 namespace qhea {
 
@@ -41,6 +43,29 @@ inline int device_noise_check(int n, const qhea_device_noise* dn) {
     return QHEA_OK;
 }
 
+// What opens the three density-matrix calls under a device setting (the exact forward, loss_grad, train_steps), in the order the
+// ABI reports it: the descriptor, the setting's QHEA_EINVAL cases, what the unit itself refuses (`refuse`, or none: the gradient
+// unit's qubit limit and guard), then the shared checks of the uniform calls.
+// noisy_call_check (hea_noise_traj.hpp, shared with the uniform calls and left as it is) reads the model itself and wants a
+// qhea_noise to check; the device setting has to be checked against the model's n before it, so the model is read twice
+// (host arithmetic on the descriptor) and the shared checks get an all-zero qhea_noise.  model_info appends to the record's
+// block list, so the first reading goes into a record of its own: filling c.mi twice would double the sub-layer count,
+// and with it the gate table of the workspace and what prep_model_kernel reads of `params`.
+// (The quantum-jump entry body, jump_forward of hea_noise_jump.hpp, opens in another order -- the sampling record is refused
+// between the setting and the shared checks, which get its value count, not zeros -- and keeps its own text.)
+inline int device_call_check(const NoisyKind& k, const qhea_model_desc* desc, const double* ham_diag, const qhea_device_noise* dn,
+                             int (*refuse)(const ModelInfo&, const qhea_device_noise*), int64_t count, const double* trunk,
+                             std::initializer_list<const void*> required, void* workspace, void* stream, NoisyCall& c) {
+    ModelInfo probe;
+    int rc = model_info(desc, probe);
+    if (rc != QHEA_OK) return rc;
+    rc = device_noise_check(probe.n, dn);
+    if (rc != QHEA_OK) return rc;
+    if (refuse && (rc = refuse(probe, dn)) != QHEA_OK) return rc;
+    const qhea_noise none{};
+    return noisy_call_check(k, desc, ham_diag, &none, 0, count, trunk, required, workspace, stream, c);
+}
+
 // chan[site][q] for a checked setting (stride: wires per site in `chan`), lam2[j]
 inline void device_noise_compose(int n, const qhea_device_noise* dn, double* chan, int stride, double* lam2) {
     const bool idle = dn->idle != 0;
@@ -59,10 +84,25 @@ inline void device_noise_compose(int n, const qhea_device_noise* dn, double* cha
     }
 }
 
-// ---- quantum-jump trajectories: one relaxation per site at its folded duration ------------------------------------------------
+// The forms the density-matrix kernels multiply with.  A triple's element form (off, k00, k01, k10, k11): rho00' = k00 rho00 +
+// k01 rho11, rho11' = k10 rho00 + k11 rho11, the off-diagonal elements times off.  The host forms the four k: arithmetic on
+// launch constants would be fp64 vector work whose results the compiler keeps in vector registers across the whole circuit loop.
+inline void element_form(const Triple& t, double* c) {
+    c[0] = t.off;
+    c[1] = 0.5 * (1.0 + t.a + t.b); c[2] = 0.5 * (1.0 - t.a + t.b);
+    c[3] = 0.5 * (1.0 - t.a - t.b); c[4] = 0.5 * (1.0 + t.a - t.b);
+}
+// ... and the two-qubit channel of a slot with lam = 16 p2 / 15: (keep, mix) = (1 - lam, lam / 4)
+inline void slot_form(double lam, double& keep, double& mix) { keep = 1.0 - lam; mix = 0.25 * lam; }
 
-// an event happens iff its 32-bit word is < threshold(p) (p 2^32, floored)
-inline unsigned long long threshold(double p) { return (unsigned long long)(p * 4294967296.0); }
+// A checked setting's sites and slots for up to kDevMaxWires wires
+struct DevSites {
+    double chan[4][kDevMaxWires][3] = {}, lam2[kDevMaxWires] = {};
+    DevSites(int n, const qhea_device_noise* dn) { device_noise_compose(n, dn, &chan[0][0][0], kDevMaxWires, lam2); }
+    Triple at(int site, int q) const { return {chan[site][q][0], chan[site][q][1], chan[site][q][2]}; }
+};
+
+// ---- quantum-jump trajectories: one relaxation per site at its folded duration ------------------------------------------------
 
 // folded duration of site `site` on wire q (the table of the header)
 inline double site_duration(int n, const qhea_device_noise* dn, int site, int q) {

@@ -12,7 +12,6 @@
 #include <cstdint>
 #include <initializer_list>
 
-#include "hea_device_noise.hpp"
 #include "hea_model.hpp"
 #include "hea_train.hpp"
 
@@ -155,6 +154,9 @@ __device__ __forceinline__ void frame_regs(double (&re)[Cfg<N>::R], double (&im)
         }
     }
 }
+
+// an event happens iff its 32-bit word is < threshold(p) (p 2^32, floored)
+inline unsigned long long threshold(double p) { return (unsigned long long)(p * 4294967296.0); }
 
 inline bool rates_ok(const qhea_noise* nz) {
     if (!nz) return false;

@@ -26,29 +26,33 @@ from quanonet_amd.noise import DeviceNoise, NoiseModel, Sampling, device_noisy_p
 ROWS, VALUES = 3, 70
 
 
-def _model(kind, n, readout, dev):
+def _model(kind, n, readout, dev, net=None):
+    """readout: 'Z', 'X', 'Y' or 'diag'; net: the net_size, by default (2, 1, 1, 2) / (3, 1)"""
     torch.manual_seed(10 * n + (kind == 'heaqnn'))
     kw = dict(scale_coeff=0.7, if_trainable_freq=True)
     if readout == 'diag':
         kw['ham_diag'] = np.random.default_rng(n).normal(size=1 << n)
+    else:
+        kw['ham_pauli'] = readout
     if kind == 'quanonet':
-        return QuanONetPT(n, 3, 2, (2, 1, 1, 2), **kw).double().to(dev)
-    return HEAQNNPT(n, 4, (3, 1), **kw).double().to(dev)
+        return QuanONetPT(n, 3, 2, net or (2, 1, 1, 2), **kw).double().to(dev)
+    return HEAQNNPT(n, 4, net or (3, 1), **kw).double().to(dev)
 
 
-def _inputs(kind, dev):
+def _inputs(kind, dev, rows=ROWS):
     rng = np.random.default_rng(1)
     if kind == 'quanonet':
-        return (torch.tensor(rng.uniform(-1, 1, (ROWS, 3)), device=dev), torch.tensor(rng.uniform(0, 1, (ROWS, 2)), device=dev))
-    return (torch.tensor(rng.uniform(-1, 1, (ROWS, 4)), device=dev),)
+        return (torch.tensor(rng.uniform(-1, 1, (rows, 3)), device=dev), torch.tensor(rng.uniform(0, 1, (rows, 2)), device=dev))
+    return (torch.tensor(rng.uniform(-1, 1, (rows, 4)), device=dev),)
 
 
-def _device_noise(n):
+def _device_noise(n, scale=1.0):
+    """scale multiplies the durations (the gradient calls refuse the setting at scale 1: scripts/density_parity.py)"""
     rng = np.random.default_rng(100 + n)
     t1 = rng.uniform(1.0, 2.0, n)
     return DeviceNoise(p1=rng.uniform(0.02, 0.05, n), p2=rng.uniform(0.05, 0.1, n), readout01=rng.uniform(0.01, 0.05, n),
-                       readout10=rng.uniform(0.04, 0.09, n), t1=t1, t2=t1 * rng.uniform(0.5, 2.0, n), t_rx=0.05, t_rot=0.1,
-                       t_cx=0.3, idle=True)
+                       readout10=rng.uniform(0.04, 0.09, n), t1=t1, t2=t1 * rng.uniform(0.5, 2.0, n), t_rx=0.05 * scale,
+                       t_rot=0.1 * scale, t_cx=0.3 * scale, idle=True)
 
 
 def _sha(t):

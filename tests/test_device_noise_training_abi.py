@@ -195,6 +195,30 @@ def test_abi_argument_checks_without_gpu(lib):
     assert _loss_grad(lib, dx, 10, _record(3), ham_diag=ctypes.cast(ctypes.c_void_p(256), ctypes.POINTER(ctypes.c_double))) == -1
 
 
+def test_train_steps_two_faults_at_once(lib):
+    """which code wins: unlike the uniform call, first_step = 0 is reported after the setting, the qubit count, the guard and
+    the shared checks, and before the return of a call without steps (the codes are those of the library before its entry
+    points shared one body)"""
+    from quanonet_amd import _lib
+    from quanonet_amd.noise import DeviceNoise
+    from tests.test_noise_aware_abi import full_train_steps
+    n = 5
+    d = _lib.make_model_desc(_lib.MODEL_QUANONET, n, (2, 1, 2, 1), 4, 1, True, 0.1, 0.0, 1.0)
+    d7 = _lib.make_model_desc(_lib.MODEL_HEAQNN, 7, (2, 1), 3, 0, False, 0.1, 0.0, 1.0)
+    ok, bad = _record(n), _record(n, t_cx=-1.0)
+    singular = DeviceNoise(p1=[0.01] * n, p2=[0.02] * n, t1=[1.0] * n, t2=[1.5] * n, t_rx=0.01, t_rot=0.02, t_cx=1e4).params(n)
+    name = 'qhea_model_train_steps_noisy_device_exact'
+    table = [('first_step 0, no row_begin', dict(d=d, nz=ok, first_step=0, row_begin=False), -1),
+             ('first_step 0, invalid setting', dict(d=d, nz=bad, first_step=0), -1),
+             ('first_step 0, n = 7', dict(d=d7, nz=_record(7), first_step=0), -2),
+             ('first_step 0, refused amplification', dict(d=d, nz=singular, first_step=0), -2),
+             ('first_step 0, no steps', dict(d=d, nz=ok, first_step=0, n_steps=0), -1),
+             ('no steps alone', dict(d=d, nz=ok, n_steps=0), 0),
+             ('no workspace, a valid call of two steps', dict(d=d, nz=ok), -3)]
+    for what, kw, want in table:
+        assert full_train_steps(lib, name, **kw) == want, what
+
+
 def _circuit_case(n, kind, readout, seed):
     """(cfgs, x, w, read-out kwargs) of a small circuit with blocks of depth 0, 1 and 2"""
     rng = np.random.default_rng(seed)

@@ -92,6 +92,38 @@ def test_abi_argument_checks_without_gpu(lib):
     assert _loss_grad(lib, dx, 10, ok, ham_diag=ctypes.cast(ctypes.c_void_p(256), ctypes.POINTER(ctypes.c_double))) == -1
 
 
+def full_train_steps(lib, name, d, nz, n_steps=2, first_step=1, row_begin=True):
+    """train-steps call `name` with every array present (host memory: the checks read row_begin and nothing else) and no
+    workspace, so nothing is launched: the code that wins when the call has more than one fault"""
+    from quanonet_amd import _lib
+    P, rows = _lib.model_param_count(d), 5
+    buf = lambda k: (ctypes.c_double * k)()
+    rb = (ctypes.c_int64 * 3)(0, 3, rows) if row_begin else None
+    return getattr(lib, name)(ctypes.byref(d), n_steps, rb, buf(rows * 8), buf(rows * 8), buf(rows), buf(P), None,
+                              ctypes.byref(nz), buf(2), buf(2 * (P + 2)), P + 2, buf(P), buf(P), first_step, 1e-3, 0.9, 0.999,
+                              1e-8, 0.0, None, 0, None)
+
+
+def test_train_steps_two_faults_at_once(lib):
+    """which code wins: first_step = 0 is refused with the descriptor, ahead of every other check of the call (the codes are
+    those of the library before its entry points shared one body)"""
+    from quanonet_amd import _lib
+    d = _lib.make_model_desc(_lib.MODEL_QUANONET, 5, (2, 1, 2, 1), 4, 1, True, 0.1, 0.0, 1.0)
+    d7 = _lib.make_model_desc(_lib.MODEL_HEAQNN, 7, (2, 1), 3, 0, False, 0.1, 0.0, 1.0)
+    ok, bad, singular = _lib.NoiseParams(0.01, 0.02, 0.03, 0, 1, 0), _lib.NoiseParams(0, 1.01, 0, 0, 1, 0), _lib.NoiseParams(0.75, 0, 0, 0, 1, 0)
+    name = 'qhea_model_train_steps_noisy_exact'
+    table = [('first_step 0, no row_begin', dict(d=d, nz=ok, first_step=0, row_begin=False), -1),
+             ('first_step 0, invalid rate', dict(d=d, nz=bad, first_step=0), -1),
+             ('first_step 0, n = 7', dict(d=d7, nz=ok, first_step=0), -1),
+             ('first_step 0, refused amplification', dict(d=d, nz=singular, first_step=0), -1),
+             ('first_step 0, no steps', dict(d=d, nz=ok, first_step=0, n_steps=0), -1),
+             ('n = 7 alone', dict(d=d7, nz=ok), -2),
+             ('refused amplification alone', dict(d=d, nz=singular), -2),
+             ('no workspace, a valid call of two steps', dict(d=d, nz=ok), -3)]
+    for what, kw, want in table:
+        assert full_train_steps(lib, name, **kw) == want, what
+
+
 def _closed_form(n, E, blk, p1, p2):
     return -((E + n * blk) * math.log10(1 - 4 * p1 / 3) + n * blk * math.log10(1 - 16 * p2 / 15))
 
