@@ -413,6 +413,74 @@ int    qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n
                                           size_t workspace_bytes, void* stream);
 
 /*
+ * Noise-aware training at n = 7..9, where a density matrix no longer fits: the MSE loss of the SAMPLED noisy forward
+ * (qhea_model_forward_noisy_wide, expectation mode) and its gradient with the random stream held fixed.
+ *
+ * The quantity.  A depolarizing channel is a mixture of Pauli insertions whose probabilities do not depend on the parameters,
+ * so for fixed draws a trajectory is an ideal circuit with fixed Pauli strings in it and its value is smooth in the parameters.
+ *   pred_b       = what qhea_model_forward_noisy_wide returns for global row row0 + b under the same `noise` (shots = 0, its
+ *                  trajectories T and seed): the mean of the T trajectory values + bias.  Agreement is to rounding, not bitwise:
+ *                  the summation order below is this call's own;
+ *   loss         = sum_b (pred_b - y_b)^2 * inv_batch_total;
+ *   grad[0..P)   = the exact derivative of that loss with the random stream held fixed, in the flat layout of
+ *                  qhea_model_loss_grad;  grad[P] = sum_b (pred_b - y_b)^2;  grad[P+1] = sum_b y_b^2, as in the exact call.
+ * The estimator.  With Var_b the variance of one trajectory's value of row b, the expectation of the sampled loss over the
+ * stream is the exact noisy MSE (the loss of qhea_model_loss_grad_noisy_exact) + inv_batch_total sum_b Var_b / T.  Hence
+ * d pred_b / d theta is an unbiased estimate of the exact noisy derivative, and the loss gradient is the exact noisy one plus
+ * sampling noise plus the derivative of that variance term, which is of order 1 / T.  Nothing is done about the latter: the
+ * estimator is stated here, not corrected.
+ * The walk.  Per trajectory the forward of qhea_model_forward_noisy_wide, then lambda = h' psi in the read-out basis (h' the
+ * folded read-out weight, with ham_diag the table diag'; no residual weight), then the adjoint walk of qhea_backward with the
+ * sampled Pauli strings in it (each is its own inverse up to a sign psi and lambda share): per fused RY RZ RY the sums
+ * Im<lambda|sigma|psi>, sigma = X, Y, Z, behind the gate; per encoding RX the X sum behind it.
+ * Random numbers: exactly those of the forward call -- the same Philox words for the same (seed, global row, trajectory,
+ * location).
+ * Summation, each order a function of n, the shape and T only:
+ *   1. a trajectory's value: as in qhea_model_forward_noisy_wide (3., n = 7..9); its inner products: per lane in register
+ *      order, then over the 64 lanes by a fixed transposing butterfly (lane bits 4, 5, 3, 2, 1, 0 for a sub-layer's 3n sums,
+ *      0, 1, .. 5 for a block's n encoding sums);
+ *   2. a row's trajectories go in tiles of 4; inside a tile values and inner products are added in trajectory order;
+ *   3. a row's tiles are added in tile order and divided by T; then a gate's (X, Y, Z) become its three angles' derivatives
+ *      (g_c = Y, g_b = cos(c) Z + sin(c) X, g_a = cos(b) Y - sin(b) cos(c) X + sin(b) sin(c) Z for RY(a) RZ(b) RY(c));
+ *   4. the rows per parameter as in qhea_model_loss_grad_noisy_exact (lane l adds rows l, l + 64, ..; the 64 lane sums by
+ *      the xor butterfly), with the weight 2 (pred_b - y_b) inv_batch_total and the frequency chain rule stated there.
+ * qhea_model_train_steps_noisy_wide: arguments and semantics of qhea_model_train_steps_noisy_exact.  Step i has the Adam count
+ * t = first_step + i, draws from the stream keyed noise->seed + t (mod 2^64) with global rows row_begin[i] + r, and is bitwise
+ * qhea_model_loss_grad_noisy_wide with that seed and row0 = row_begin[i] followed by qhea_adam_step: fresh noise every step,
+ * and a run resumed at first_step reproduces an uninterrupted one.  The workspace must fit the largest step.
+ * Scope: n = 7..9, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs; the uniform model of qhea_noise
+ * only (relaxation jumps of a device noise model depend on the state, hence on the parameters).
+ * Errors, all before anything is launched and with the outputs untouched, in the order of the forward call: a bad descriptor;
+ * QHEA_EINVAL for rates outside [0, 1] (NaN included), a NULL noise, trajectories < 1 and shots > 0 (shot mode has no such
+ * gradient); QHEA_EUNSUPPORTED for n <= 6 (the exact calls above) and n >= 10; QHEA_EINVAL for a bad read-out, a negative
+ * batch or row0, first_step < 1, NULL arrays, batch * ceil(T / 4) > 2^31 - 1; QHEA_EWORKSPACE.  An empty batch (or
+ * n_steps = 0) returns QHEA_OK.  There is no conditioning guard: no channel is inverted.
+ * Launches: four per step -- the prep kernel, the trajectory kernel (one wave per row and tile), the fold kernel (tiles -> pred
+ * and the per-row record), the reduce kernel of the exact call (with Adam in train_steps) -- and with ham_diag one more per
+ * CALL in front, the kernel that builds diag'.  No allocation, no synchronisation (hipGraph-capturable).  No atomics and fixed
+ * orders: results are bitwise reproducible, and a row's pred and record do not depend on the batch, the grid or the rows
+ * beside it.  Cost per trajectory: one forward walk, two reverse walks and 3 n inner products per sub-layer.
+ */
+/* DEVICE scratch bytes for the two calls on (at most) `batch` rows (0 on a bad descriptor or noise setting, shots > 0, or n
+ * outside 7..9): the forward's tables, and (E + 3 n blk) doubles per (row, tile) and per row. */
+size_t qhea_model_noisy_wide_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise);
+int    qhea_model_loss_grad_noisy_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                       const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                       const double* params, const double* ham_diag,
+                                       const qhea_noise* noise /*HOST: shots = 0*/, double inv_batch_total,
+                                       double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_wide(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                         const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                         const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                         const double* ham_diag, const qhea_noise* noise /*HOST*/,
+                                         const double* inv_batch_total /*HOST [n_steps]*/,
+                                         double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                         double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                         double beta2, double eps, double weight_decay, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+
+/*
  * Exact noisy forward under a calibrated device noise model: pred and shot_std of qhea_model_forward_noisy_exact, with the three
  * numbers of qhea_noise replaced by what a backend's calibration reports -- a gate error per wire and per coupled pair, a
  * readout error per qubit and direction, T1 and T2 per qubit -- and with the time the sequential CNOT ring takes.  Replaces the

@@ -43,7 +43,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_device_noisy_grad_workspace_bytes', 'qhea_model_device_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_device_exact', 'qhea_model_train_steps_noisy_device_exact',
            'qhea_device_noise_jump_tables', 'qhea_model_noisy_device_workspace_bytes', 'qhea_model_forward_noisy_device',
-           'qhea_model_noisy_device_wide_workspace_bytes', 'qhea_model_forward_noisy_device_wide']
+           'qhea_model_noisy_device_wide_workspace_bytes', 'qhea_model_forward_noisy_device_wide',
+           'qhea_model_noisy_wide_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_wide', 'qhea_model_train_steps_noisy_wide']
 
 
 class ModelDesc(ctypes.Structure):
@@ -80,7 +81,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 570           # 0.5.7: + qhea_model_forward_noisy_device_wide (device-noise trajectories at n = 10..12)
+MIN_LIB_VERSION = 580           # 0.5.8: + qhea_model_loss_grad_noisy_wide / ..._train_steps_noisy_wide (sampled-trajectory gradients, n = 7..9)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -237,6 +238,12 @@ def load():
     lib.qhea_model_train_steps_noisy_exact.argtypes = [mdp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), dp, dp, dp, dp, dp, npp,
                                                        ctypes.POINTER(ctypes.c_double), dp, ctypes.c_int64, dp, dp,
                                                        ctypes.c_int64] + [ctypes.c_double] * 5 + [vp, ctypes.c_size_t, vp]
+    lib.qhea_model_noisy_wide_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_wide_grad_workspace_bytes.argtypes = lib.qhea_model_noisy_workspace_bytes.argtypes
+    lib.qhea_model_loss_grad_noisy_wide.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_wide.argtypes = [mdp, ctypes.c_int64] + lib.qhea_model_loss_grad_noisy_exact.argtypes[1:]
+    lib.qhea_model_train_steps_noisy_wide.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_wide.argtypes = lib.qhea_model_train_steps_noisy_exact.argtypes
     dnp = ctypes.POINTER(DeviceNoiseParams)
     lib.qhea_device_noise_tables.restype = ctypes.c_int
     lib.qhea_device_noise_tables.argtypes = [ctypes.c_int, dnp, f64p, f64p]
@@ -991,6 +998,70 @@ def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y
     """
     return _train_steps_noisy(False, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
                               first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+
+
+def model_noisy_wide_grad_workspace_bytes(desc, batch, noise):
+    """qhea_model_noisy_wide_grad_workspace_bytes: 0 for a bad descriptor or noise setting (shot mode included) or n outside 7..9."""
+    return int(load().qhea_model_noisy_wide_grad_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(noise)))
+
+
+def _check_noisy_wide_grad(rc, who):
+    if rc == -2:
+        raise Unsupported(f"{who}: n outside 7..9 (n <= 6: the exact calls; n >= 10: not built)")
+    _check(rc, who)
+
+
+def model_loss_grad_noisy_wide(desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0=0, ham_diag=None, pred=None):
+    """
+    model_loss_grad of the SAMPLED noisy prediction (qhea_model_loss_grad_noisy_wide, n = 7..9): fills grad[P+2] =
+    [d loss/d params | sse | sum y^2] where pred is what model_forward_noisy_wide returns for the same `noise` (a NoiseParams in
+    expectation mode: trajectories and seed are used) and global rows row0 + b, differentiated with the random stream held
+    fixed; returns grad.  Raises Unsupported for n outside 7..9 and QheaError for a bad noise setting (shots > 0 included), in
+    both cases before anything is launched.
+    """
+    lib = load()
+    entry = 'qhea_model_loss_grad_noisy_wide'
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
+    _dev_f64(y, 'y')
+    if y.numel() != B:
+        raise QheaError(f"y has {y.numel()} elements, expected {B}")
+    _dev_f64(grad, 'grad')
+    if grad.numel() < params.numel() + 2:
+        raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
+    _dev_f64(pred, 'pred', (B,))
+    ws = _sized_ws(branch.device, lib.qhea_model_noisy_wide_grad_workspace_bytes, ctypes.byref(desc), int(B), ctypes.byref(noise))
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_loss_grad_noisy_wide(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+                                                 _ptr(ham_diag), ctypes.byref(noise), float(inv_batch_total), _ptr(grad),
+                                                 _ptr(pred), _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_noisy_wide_grad(rc, entry)
+    return grad
+
+
+def model_train_steps_noisy_wide(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                                 lr, beta1, beta2, eps, weight_decay, noise, ham_diag=None):
+    """
+    model_train_steps with the sampled noisy loss (qhea_model_train_steps_noisy_wide, n = 7..9): step i trains on rows
+    bounds[i]:bounds[i+1] (their global row indices key the random stream) under `noise` with the seed noise.seed +
+    first_step + i, leaves [grads | sse | sum y^2] in rows[i] and applies Adam update first_step + i.  Bitwise a loop of
+    model_loss_grad_noisy_wide (that seed, row0 = bounds[i]) + adam_step.
+    """
+    lib = load()
+    entry = 'qhea_model_train_steps_noisy_wide'
+    if len(bounds) - 1 <= 0:
+        return rows
+    n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
+                                                    exp_avg, exp_avg_sq, ham_diag)
+    ws = _sized_ws(branch.device, lib.qhea_model_noisy_wide_grad_workspace_bytes, ctypes.byref(desc), int(biggest),
+                   ctypes.byref(noise))
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_train_steps_noisy_wide(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
+                                                   _ptr(params), _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows),
+                                                   int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
+                                                   float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                                   _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_noisy_wide_grad(rc, entry)
+    return rows
 
 
 def model_device_noisy_log10_amplification(desc, noise):

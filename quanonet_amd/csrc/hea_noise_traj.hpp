@@ -3,7 +3,9 @@
 // (noisy_call_check).  The four trajectory units (uniform noise at n = 2..6, one amplitude per lane, and at n = 7..12, registers
 // or LDS; device noise at n = 2..9 in both register layouts and at n = 10..12 in LDS): the argument record, the Philox stream and its error codes, the Pauli frame bits and the frame's
 // application in either layout (apply_frame, frame_regs), the work item, wave_scan, u and the value of a shot, the workspace
-// layout, and the head and tail of the entry point around a unit's kernels (traj_open, traj_finish).  What only the two
+// layout, and the head and tail of the entry point around a unit's kernels (traj_open, traj_finish); the uniform model's segment
+// frames (enc_frame, sub_frame), readout_weight and the launch of the readout mix, which hea_noise_wide.hip shares with the
+// sampled-trajectory gradient unit (hea_noise_grad.hip).  What only the two
 // device-noise units share (their table, its prep kernel's body, the site helpers, the entry point's body) is
 // hea_noise_jump.hpp's; the frame in the LDS layout (ring_pull, store_framed) is hea_lds.hpp's.
 #pragma once
@@ -154,6 +156,51 @@ __device__ __forceinline__ void frame_regs(double (&re)[Cfg<N>::R], double (&im)
         }
     }
 }
+
+// The frames of the uniform model's segments (hea_noise_wide.hip's forward walk, hea_noise_grad.hip's walk both ways).
+// (X mask, Z mask) of the errors behind a block's n encoding RX gates; codes: segment_codes of the wave's lanes
+template <int N>
+__device__ __forceinline__ void enc_frame(unsigned codes, unsigned loc, int& x, int& z) {
+    x = 0; z = 0;
+    if (!__any(codes != 0u)) return;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        const unsigned p = code_at(codes, loc, loc + q, 0);
+        x |= pauli_x(p, q); z |= pauli_z(p, q);
+    }
+    x = uniform(x); z = uniform(z);
+}
+// ... of a sub-layer, as one frame behind its ring: the rotations' errors, then per CNOT(c -> t) the conjugation and its own
+template <int N>
+__device__ __forceinline__ void sub_frame(unsigned codes, unsigned loc, int& x, int& z) {
+    x = 0; z = 0;
+    if (!__any(codes != 0u)) return;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        const unsigned p = code_at(codes, loc, loc + q, 0);
+        x |= pauli_x(p, q); z |= pauli_z(p, q);
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const int c = (j + 1) % N, t = j;
+        x ^= ((x >> c) & 1) << t;
+        z ^= ((z >> t) & 1) << c;
+        const unsigned p = code_at(codes, loc, loc + N + j, 0);
+        x ^= pauli_x(p >> 2, c) | pauli_x(p & 3u, t);
+        z ^= pauli_z(p >> 2, c) | pauli_z(p & 3u, t);
+    }
+    x = uniform(x); z = uniform(z);
+}
+
+// expectation mode's weight of basis state k (hd: the readout-confused ham_diag, or NULL)
+template <int N>
+__device__ __forceinline__ double readout_weight(const NoiseArgs& a, const double* __restrict__ hd, int k) {
+    return hd ? hd[k] : a.co * (1.0 - 2.0 * a.q) * (double)(N - 2 * (int)__popc((unsigned)k));
+}
+
+// readout_mix_kernel (hea_noise_wide.hip) on `st`: ham_diag under the readout confusion, built bit by bit in mix[2 * 2^n];
+// *hd = where the table ends up (the half (n - 1) & 1)
+int launch_readout_mix(const double* diag, double q, int n, double* mix, hipStream_t st, const double** hd);
 
 // an event happens iff its 32-bit word is < threshold(p) (p 2^32, floored)
 inline unsigned long long threshold(double p) { return (unsigned long long)(p * 4294967296.0); }

@@ -27,7 +27,8 @@
 //
 // The work item, frame_regs, wave_scan, uniform, u of the cdf search and shot_value are hea_noise_traj.hpp's, shared with
 // hea_noise_device.hip; ring_pull and the last pass's store behind the frame (store_framed) are hea_lds.hpp's, shared with
-// hea_noise_device_wide.hip; the frames of a segment, the shot words, the LDS kernel and the readout mix are this unit's.
+// hea_noise_device_wide.hip; the frames of a segment (enc_frame, sub_frame), readout_weight and the readout mix's launcher are
+// hea_noise_traj.hpp's too, shared with hea_noise_grad.hip; the shot words, the LDS kernel and the mix kernel are this unit's.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -40,40 +41,6 @@ namespace {
 
 constexpr int kWideWaves = 4;               // n = 7..9: waves per workgroup (independent; no LDS, no barrier)
 constexpr int kWideLG = 4;                  // n = 10..12: gate qubits per pass, as the ideal forward (hea_lds.hip)
-
-// (X mask, Z mask) of the errors behind a block's n encoding RX gates; codes: segment_codes of the wave's lanes
-template <int N>
-__device__ __forceinline__ void enc_frame(unsigned codes, unsigned loc, int& x, int& z) {
-    x = 0; z = 0;
-    if (!__any(codes != 0u)) return;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        const unsigned p = code_at(codes, loc, loc + q, 0);
-        x |= pauli_x(p, q); z |= pauli_z(p, q);
-    }
-    x = uniform(x); z = uniform(z);
-}
-// ... of a sub-layer, as one frame behind its ring: the rotations' errors, then per CNOT(c -> t) the conjugation and its own
-template <int N>
-__device__ __forceinline__ void sub_frame(unsigned codes, unsigned loc, int& x, int& z) {
-    x = 0; z = 0;
-    if (!__any(codes != 0u)) return;
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-        const unsigned p = code_at(codes, loc, loc + q, 0);
-        x |= pauli_x(p, q); z |= pauli_z(p, q);
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const int c = (j + 1) % N, t = j;
-        x ^= ((x >> c) & 1) << t;
-        z ^= ((z >> t) & 1) << c;
-        const unsigned p = code_at(codes, loc, loc + N + j, 0);
-        x ^= pauli_x(p >> 2, c) | pauli_x(p & 3u, t);
-        z ^= pauli_z(p >> 2, c) | pauli_z(p & 3u, t);
-    }
-    x = uniform(x); z = uniform(z);
-}
 
 // shot mode's words (header: calls m .. m + 3): u of the cdf search and the n readout flips as a bit mask; whole wave
 template <int N>
@@ -90,12 +57,6 @@ __device__ __forceinline__ void shot_words(const NoiseArgs& a, unsigned traj, un
     }
     flips = uniform(__shfl(mask, 0) | __shfl(mask, 1) | __shfl(mask, 2) | __shfl(mask, 3));
     u = __shfl(unit_double(w.x, w.y), 0);
-}
-
-// expectation mode's weight of basis state k (hd: the readout-confused ham_diag, or NULL)
-template <int N>
-__device__ __forceinline__ double readout_weight(const NoiseArgs& a, const double* __restrict__ hd, int k) {
-    return hd ? hd[k] : a.co * (1.0 - 2.0 * a.q) * (double)(N - 2 * (int)__popc((unsigned)k));
 }
 
 // ---- n = 7..9: one wave, 2^(n-6) amplitudes per lane -------------------------------------------------------------------------
@@ -373,11 +334,7 @@ int launch_wide(const NoiseArgs& a, const double* hd, hipStream_t st) {
 // ham_diag goes through readout_mix_kernel first where the kernels read it mixed (expectation mode)
 int launch_noisy_wide(const NoiseArgs& a, int n, double* mix, hipStream_t st) {
     const double* hd = nullptr;
-    if (a.diag && !a.shots) {
-        hipLaunchKernelGGL(readout_mix_kernel, dim3(1), dim3(256), 0, st, a.diag, a.q, n, mix);
-        if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-        hd = mix + ((size_t)((n - 1) & 1) << n);
-    }
+    if (a.diag && !a.shots && launch_readout_mix(a.diag, a.q, n, mix, st, &hd) != QHEA_OK) return QHEA_ELAUNCH;
     switch (n) {
         case 7: return launch_wide<7>(a, hd, st);
         case 8: return launch_wide<8>(a, hd, st);
@@ -391,6 +348,13 @@ int launch_noisy_wide(const NoiseArgs& a, int n, double* mix, hipStream_t st) {
 constexpr TrajUnit kWideUnit{7, QHEA_MAX_QUBITS, true, 0};                   // qhea_model_forward_noisy is the path below 7
 
 }  // namespace
+
+int launch_readout_mix(const double* diag, double q, int n, double* mix, hipStream_t st, const double** hd) {
+    hipLaunchKernelGGL(readout_mix_kernel, dim3(1), dim3(256), 0, st, diag, q, n, mix);
+    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
+    *hd = mix + ((size_t)((n - 1) & 1) << n);
+    return QHEA_OK;
+}
 }  // namespace qhea
 
 using namespace qhea;

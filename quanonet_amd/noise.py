@@ -403,6 +403,36 @@ def exact_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
     return _lib.model_loss_grad_noisy_exact(desc, branch, trunk, y, flat, noise.params(), inv, grad, ham_diag=ham_diag)
 
 
+def noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, row0=0):
+    """
+    The MSE loss of the SAMPLED noisy prediction -- noisy_predict(model, inputs, noise, row0=row0) in expectation mode, the mean
+    of noise.trajectories runs on the stream keyed noise.seed -- and its gradient with that stream held fixed, as the flat
+    [P + 2] tensor of qhea_model_loss_grad_noisy_wide (the layout of exact_noisy_loss_and_grad).  d pred / d params is an
+    unbiased estimate of the exact noisy derivative; the loss also carries the trajectories' variance / T (the header states
+    the estimator).  n = 7..9, where no density matrix fits; for n <= 6 exact_noisy_loss_and_grad is the call.
+    """
+    _uniform_only(noise, 'noisy_loss_and_grad',
+                  "relaxation jumps depend on the state, so a sampled DeviceNoise has no fixed-stream gradient")
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("noisy_loss_and_grad takes a QuanONetPT or HEAQNNPT model")
+    if noise.shots > 0:
+        raise ValueError("noisy_loss_and_grad differentiates expectation mode (shots = 0); a sampled bitstring has no gradient")
+    n = int(model.fused_desc().n_qubits)
+    if n <= 6:
+        raise ValueError(f"noisy_loss_and_grad covers n = 7..9 (got n = {n}); exact_noisy_loss_and_grad is the call for n <= 6")
+    if n >= 10:
+        raise ValueError(f"noisy_loss_and_grad covers n = 7..9 (got n = {n})")
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'noisy_loss_and_grad')
+    B = branch.shape[0]
+    y = y.detach().to(torch.float64).reshape(-1).contiguous()
+    grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
+    if B == 0:
+        return grad
+    inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
+    return _lib.model_loss_grad_noisy_wide(desc, branch, trunk, y, flat, noise.params(), inv, grad, row0=int(row0),
+                                           ham_diag=ham_diag)
+
+
 def _device_noise(noise, who):
     if not isinstance(noise, DeviceNoise):
         raise ValueError(f"{who} takes a DeviceNoise (got {type(noise).__name__}); a NoiseModel goes to its uniform "

@@ -321,6 +321,18 @@ def _train_device_noise(v, train_noise=None):
                      f"(got {type(v).__name__}); a NoiseModel goes to train_noise")
 
 
+def _train_sampling(v):
+    """config value / argument `train_sampling` -> Sampling or None (a Sampling, or its asdict() form)"""
+    if v is None:
+        return None
+    from .noise import Sampling
+    if isinstance(v, Sampling):
+        return v
+    if isinstance(v, dict):
+        return Sampling(**v)
+    raise ValueError(f"train_sampling must be a quanonet_amd.noise.Sampling or its asdict() form (got {type(v).__name__})")
+
+
 class DataParallelTrainer:
     """
     fused='auto': when the model is one of this package's QuanONetPT / HEAQNNPT (fp64, on a HIP
@@ -330,10 +342,24 @@ class DataParallelTrainer:
     """
 
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
-                 fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None):
+                 fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None,
+                 train_sampling=None):
         self.model = model
         self.train_noise = _train_noise(train_noise)
         self.train_device_noise = _train_device_noise(train_device_noise, train_noise)
+        self.train_sampling = _train_sampling(train_sampling)
+        if self.train_sampling is not None:
+            # sampled-trajectory training (qhea_model_train_steps_noisy_wide): what it cannot combine with
+            if self.train_device_noise is not None:
+                raise ValueError("train_sampling does not combine with train_device_noise: relaxation jumps depend on the state, "
+                                 "so a sampled DeviceNoise has no fixed-stream gradient")
+            if self.train_noise is None:
+                raise ValueError("train_sampling needs train_noise: it says how the NoiseModel of train_noise is sampled")
+            if self.train_sampling.shots > 0:
+                raise ValueError("train_sampling: training differentiates expectation mode (Sampling.shots = 0, trajectories "
+                                 "= T); a sampled bitstring has no gradient")
+            if int(world_size) > 1:
+                raise ValueError("train_sampling: sampled-trajectory training runs on one device (world_size = 1)")
         self.world = int(world_size)
         self.dist = dist
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -389,7 +415,19 @@ class DataParallelTrainer:
                 self.peer, self.dp_exchange_reason = PeerExchange.create(dist, dist.get_rank(), self.world, self.numel + 2,
                                                                          p0.device, log=log)
                 self.peer_fused = self.peer is not None and self.desc is not None
-        if self.train_noise is not None:
+        if self.train_sampling is not None:
+            # the loss is the sampled noisy one (qhea_model_loss_grad_noisy_wide): refuse here what the call would refuse
+            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+                raise ValueError("train_sampling needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
+                                 "Adam with betas / eps / weight_decay only)")
+            if not 7 <= self.desc.n_qubits <= 9:
+                raise ValueError(f"train_sampling: sampled-trajectory training takes n = 7..9 (this model: n = "
+                                 f"{self.desc.n_qubits}); for n <= 6 train_noise alone trains on the exact noisy loss")
+            if log is not None:
+                log(f"noise-aware training: the loss and 'loss_train' are the sampled noisy MSE under p1={self.train_noise.p1:g} "
+                    f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g}, {self.train_sampling.trajectories} "
+                    f"trajectories per row, stream seed {self.train_sampling.seed} + step count")
+        elif self.train_noise is not None:
             # the loss is the exact noisy one (qhea_model_loss_grad_noisy_exact): refuse here what the call would refuse
             if self.desc is None or not isinstance(self.optimizer, FlatAdam):
                 raise ValueError("train_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
@@ -438,6 +476,14 @@ class DataParallelTrainer:
             return self.train_device_noise.params(self.desc.n_qubits)
         return None if self.train_noise is None else self.train_noise.params()
 
+    def _sampled_noise(self, step):
+        """train_noise's rates with train_sampling's trajectories and seed + step (mod 2^64): `step` = 0 is the record the
+        steps entry takes (it adds the step count itself), the Adam count that of one step's own call"""
+        tn, sp = self.train_noise, self.train_sampling
+        from . import _lib
+        return _lib.NoiseParams(float(tn.p1), float(tn.p2), float(tn.readout), 0, int(sp.trajectories),
+                                (int(sp.seed) + int(step)) & ((1 << 64) - 1))
+
     def broadcast_parameters(self):
         self.dist.broadcast(self.pflat, src=0)
 
@@ -465,7 +511,10 @@ class DataParallelTrainer:
             from . import _lib
             data = (self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat)
             grad = self.flat if out is None else out
-            if self.train_device_noise is not None:
+            if self.train_sampling is not None:          # (the stream of the NEXT update, global rows from 0)
+                _lib.model_loss_grad_noisy_wide(*data, self._sampled_noise(self.optimizer.t + 1), 1.0 / gb, grad,
+                                                ham_diag=self._ham_diag())
+            elif self.train_device_noise is not None:
                 _lib.model_loss_grad_noisy_device_exact(*data, self._noise_params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
             elif self.train_noise is not None:
                 _lib.model_loss_grad_noisy_exact(*data, self.train_noise.params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
@@ -482,10 +531,12 @@ class DataParallelTrainer:
                 self.flat[self.numel + 1] = (y * y).sum()
         return self.flat
 
-    def train_step(self, *batch, global_batch=None, out=None):
+    def train_step(self, *batch, global_batch=None, out=None, row0=0):
         """batch = (branch, trunk, y) or (x, y): this rank's shard.  Returns the flat buffer (device): self.flat, or
         `out` -- a caller's [numel + 2] fp64 buffer, honoured where accepts_out says so (PTSolver hands in one row per
-        step of an epoch, so that the two logging scalars of every step stay on the device without a copy)."""
+        step of an epoch, so that the two logging scalars of every step stay on the device without a copy).
+        row0 (train_sampling only): the global index of the batch's first row, which keys its random streams -- a step of
+        train_steps has its bounds[i] there."""
         if out is not None and not self.accepts_out:
             out = None
         flat = self._last = self.flat if out is None else out
@@ -496,7 +547,14 @@ class DataParallelTrainer:
             gb = float(global_batch if global_batch is not None else y.shape[0])
             opt = self.optimizer
             opt.t += 1
-            if self._noise_params() is not None:            # (the noise-aware paths have the steps entry only: one step of it)
+            if self.train_sampling is not None:
+                # the steps entry reads a step's global rows off its schedule; one step with rows of its own is the loop the
+                # entry is bitwise equal to: the single call under seed + step count, then the Adam launch
+                _lib.model_loss_grad_noisy_wide(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat,
+                                                self._sampled_noise(opt.t), 1.0 / gb, flat, row0=int(row0),
+                                                ham_diag=self._ham_diag())
+                _lib.adam_step(self.pflat, flat, opt.exp_avg, opt.exp_avg_sq, opt.t, *opt.hparams())
+            elif self._noise_params() is not None:          # (the noise-aware paths have the steps entry only: one step of it)
                 self._steps(inputs, y, [0, y.shape[0]], [gb], flat.view(1, -1), opt.t)
             else:
                 _lib.model_train_step(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat, 1.0 / gb, flat, opt.exp_avg,
@@ -528,13 +586,15 @@ class DataParallelTrainer:
         return flat
 
     def _steps(self, inputs, y, bounds, global_batches, rows, first_step):
-        """single device: the steps entry, ideal (qhea_model_train_steps), under train_noise (..._noisy_exact) or under
-        train_device_noise (..._noisy_device_exact)"""
+        """single device: the steps entry, ideal (qhea_model_train_steps), under train_noise (..._noisy_exact; with
+        train_sampling ..._noisy_wide) or under train_device_noise (..._noisy_device_exact)"""
         from . import _lib
         opt = self.optimizer
         call = (self.desc, bounds, global_batches, *split_inputs(inputs), y.reshape(-1), self.pflat, rows, opt.exp_avg,
                 opt.exp_avg_sq, first_step, *opt.hparams())
-        if self.train_device_noise is not None:
+        if self.train_sampling is not None:
+            _lib.model_train_steps_noisy_wide(*call, self._sampled_noise(0), ham_diag=self._ham_diag())
+        elif self.train_device_noise is not None:
             _lib.model_train_steps_noisy_device_exact(*call, self._noise_params(), ham_diag=self._ham_diag())
         elif self.train_noise is not None:
             _lib.model_train_steps_noisy_exact(*call, self.train_noise.params(), ham_diag=self._ham_diag())
@@ -725,7 +785,8 @@ class PTSolver:
                                            optimizer_kwargs=config.get('optimizer_kwargs', {}),
                                            peer_exchange=str(config.get('dp_exchange', 'peer')).lower() == 'peer',
                                            log=self.log, train_noise=config.get('train_noise'),
-                                           train_device_noise=config.get('train_device_noise'))
+                                           train_device_noise=config.get('train_device_noise'),
+                                           train_sampling=config.get('train_sampling'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None
@@ -895,7 +956,7 @@ class PTSolver:
                 for i in range(nb):
                     a, b = bounds[i], bounds[i + 1]
                     flat = self.trainer.train_step(*[t[a:b] for t in ep_inputs], ep_output[a:b], global_batch=gbs[i],
-                                                   out=None if rows is None else rows[i])
+                                                   out=None if rows is None else rows[i], row0=a)
                     if rows is None:
                         tails[i].copy_(flat[nm:])
             return tails, idx_dev
