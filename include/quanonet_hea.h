@@ -481,6 +481,52 @@ int    qhea_model_train_steps_noisy_wide(const qhea_model_desc* desc, int64_t n_
                                          size_t workspace_bytes, void* stream);
 
 /*
+ * The same at n = 10..12, where psi and lambda rest in LDS: quantity, estimator, random stream, record, arguments, launches and
+ * error order of the _wide pair above, under names of their own because the _wide pair's answers at n >= 10 are part of its
+ * contract.  One workgroup per (row, tile): 2^(n-LG) threads, LG = 3 gate qubits per pass at n = 10 and 11, 4 at n = 12 (128 /
+ * 256 / 256 threads), thread t holding in a pass the 2^LG amplitudes that differ in the pass's index bits.
+ * Summation, each order a function of n, the shape and T only, so that a row's pred and record depend on (seed, global row, T)
+ * and on nothing else -- not on the batch, the grid or the rows beside it:
+ *   1. within a thread: a trajectory's value over the thread's 2^LG consecutive basis states 2^LG t + j, j ascending (at
+ *      n = 12 the order of qhea_model_forward_noisy_wide, 3.; at n = 10 and 11 groups of 8 where that call has 16); an inner
+ *      product over the passes of a reverse layer from the highest index bits down and, inside a pass, over the amplitude pairs
+ *      in ascending local index, each pair one chain of fused multiply-adds;
+ *   2. over the wave: the value by the xor butterfly (offsets 32, 16, .. 1); the 3n sums of a sub-layer and the n of a block's
+ *      encoding by the transposing butterfly of qhea_backward at n = 10..12 (lane bits 0, 1, .. 5);
+ *   3. over the waves: in wave order;
+ *   4. within a tile of 2 trajectories: values and inner products in trajectory order;
+ *   5. over the tiles: in tile order, divided by T, then a gate's (X, Y, Z) to its angles and the rows per parameter exactly as
+ *      3. and 4. of the _wide pair.
+ * pred agrees with qhea_model_forward_noisy_wide for the same noise and row0 to rounding, not bitwise (other tiles).
+ * Scope: n = 10..12; QHEA_EUNSUPPORTED for n <= 9 (the _wide pair and the exact calls), reported where the _wide pair reports its
+ * qubit range: after a bad descriptor and a bad noise setting (rates outside [0, 1], NaN, NULL, trajectories < 1, shots > 0),
+ * before QHEA_EINVAL for a bad read-out, a negative batch or row0, first_step < 1, NULL arrays and batch * ceil(T / 2) >
+ * 2^31 - 1, and before QHEA_EWORKSPACE.  All errors come before anything is launched and leave the outputs untouched.  An empty
+ * batch (or n_steps = 0) returns QHEA_OK.  Step i of train_steps has the stream key noise->seed + first_step + i (mod 2^64) and
+ * the global rows row_begin[i] + r and is bitwise the single call with that seed and row0 = row_begin[i] followed by
+ * qhea_adam_step.  Four launches per step and with ham_diag one more per CALL in front, no allocation, no synchronisation
+ * (hipGraph-capturable), no atomics.
+ */
+/* DEVICE scratch bytes for the two calls on (at most) `batch` rows (0 on a bad descriptor or noise setting, shots > 0, or n
+ * outside 10..12): the forward's tables, and (E + 3 n blk) doubles per (row, tile of 2) and per row. */
+size_t qhea_model_noisy_lds_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise);
+int    qhea_model_loss_grad_noisy_lds(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                      const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                      const double* params, const double* ham_diag,
+                                      const qhea_noise* noise /*HOST: shots = 0*/, double inv_batch_total,
+                                      double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_lds(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                        const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                        const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                        const double* ham_diag, const qhea_noise* noise /*HOST*/,
+                                        const double* inv_batch_total /*HOST [n_steps]*/,
+                                        double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                        double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                        double beta2, double eps, double weight_decay, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+
+/*
  * Exact noisy forward under a calibrated device noise model: pred and shot_std of qhea_model_forward_noisy_exact, with the three
  * numbers of qhea_noise replaced by what a backend's calibration reports -- a gate error per wire and per coupled pair, a
  * readout error per qubit and direction, T1 and T2 per qubit -- and with the time the sequential CNOT ring takes.  Replaces the

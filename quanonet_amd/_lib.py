@@ -44,7 +44,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_loss_grad_noisy_device_exact', 'qhea_model_train_steps_noisy_device_exact',
            'qhea_device_noise_jump_tables', 'qhea_model_noisy_device_workspace_bytes', 'qhea_model_forward_noisy_device',
            'qhea_model_noisy_device_wide_workspace_bytes', 'qhea_model_forward_noisy_device_wide',
-           'qhea_model_noisy_wide_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_wide', 'qhea_model_train_steps_noisy_wide']
+           'qhea_model_noisy_wide_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_wide', 'qhea_model_train_steps_noisy_wide',
+           'qhea_model_noisy_lds_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_lds', 'qhea_model_train_steps_noisy_lds']
 
 
 class ModelDesc(ctypes.Structure):
@@ -81,7 +82,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 580           # 0.5.8: + qhea_model_loss_grad_noisy_wide / ..._train_steps_noisy_wide (sampled-trajectory gradients, n = 7..9)
+MIN_LIB_VERSION = 590           # 0.5.9: + qhea_model_loss_grad_noisy_lds / ..._train_steps_noisy_lds (sampled-trajectory gradients, n = 10..12)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -244,6 +245,12 @@ def load():
     lib.qhea_model_loss_grad_noisy_wide.argtypes = [mdp, ctypes.c_int64] + lib.qhea_model_loss_grad_noisy_exact.argtypes[1:]
     lib.qhea_model_train_steps_noisy_wide.restype = ctypes.c_int
     lib.qhea_model_train_steps_noisy_wide.argtypes = lib.qhea_model_train_steps_noisy_exact.argtypes
+    lib.qhea_model_noisy_lds_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_lds_grad_workspace_bytes.argtypes = lib.qhea_model_noisy_wide_grad_workspace_bytes.argtypes
+    lib.qhea_model_loss_grad_noisy_lds.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_lds.argtypes = lib.qhea_model_loss_grad_noisy_wide.argtypes
+    lib.qhea_model_train_steps_noisy_lds.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_lds.argtypes = lib.qhea_model_train_steps_noisy_wide.argtypes
     dnp = ctypes.POINTER(DeviceNoiseParams)
     lib.qhea_device_noise_tables.restype = ctypes.c_int
     lib.qhea_device_noise_tables.argtypes = [ctypes.c_int, dnp, f64p, f64p]
@@ -1005,10 +1012,56 @@ def model_noisy_wide_grad_workspace_bytes(desc, batch, noise):
     return int(load().qhea_model_noisy_wide_grad_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(noise)))
 
 
-def _check_noisy_wide_grad(rc, who):
+# The two sampled-trajectory gradient pairs share their arguments: `kind` is 'wide' (n = 7..9) or 'lds' (n = 10..12)
+_SAMPLED_RANGE = {'wide': "n outside 7..9 (n <= 6: the exact calls; n >= 10: the _lds calls)",
+                  'lds': "n outside 10..12 (n = 7..9: the _wide calls; n <= 6: the exact calls)"}
+
+
+def _check_noisy_wide_grad(rc, who, kind='wide'):
     if rc == -2:
-        raise Unsupported(f"{who}: n outside 7..9 (n <= 6: the exact calls; n >= 10: not built)")
+        raise Unsupported(f"{who}: {_SAMPLED_RANGE[kind]}")
     _check(rc, who)
+
+
+def _loss_grad_sampled(kind, desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0, ham_diag, pred):
+    lib = load()
+    entry = f'qhea_model_loss_grad_noisy_{kind}'
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
+    _dev_f64(y, 'y')
+    if y.numel() != B:
+        raise QheaError(f"y has {y.numel()} elements, expected {B}")
+    _dev_f64(grad, 'grad')
+    if grad.numel() < params.numel() + 2:
+        raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
+    _dev_f64(pred, 'pred', (B,))
+    ws = _sized_ws(branch.device, getattr(lib, f'qhea_model_noisy_{kind}_grad_workspace_bytes'), ctypes.byref(desc), int(B),
+                   ctypes.byref(noise))
+    with torch.cuda.device(branch.device):
+        rc = getattr(lib, entry)(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+                                 _ptr(ham_diag), ctypes.byref(noise), float(inv_batch_total), _ptr(grad),
+                                 _ptr(pred), _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_noisy_wide_grad(rc, entry, kind)
+    return grad
+
+
+def _train_steps_sampled(kind, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                         lr, beta1, beta2, eps, weight_decay, noise, ham_diag):
+    lib = load()
+    entry = f'qhea_model_train_steps_noisy_{kind}'
+    if len(bounds) - 1 <= 0:
+        return rows
+    n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
+                                                    exp_avg, exp_avg_sq, ham_diag)
+    ws = _sized_ws(branch.device, getattr(lib, f'qhea_model_noisy_{kind}_grad_workspace_bytes'), ctypes.byref(desc),
+                   int(biggest), ctypes.byref(noise))
+    with torch.cuda.device(branch.device):
+        rc = getattr(lib, entry)(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
+                                 _ptr(params), _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows),
+                                 int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
+                                 float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                 _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_noisy_wide_grad(rc, entry, kind)
+    return rows
 
 
 def model_loss_grad_noisy_wide(desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0=0, ham_diag=None, pred=None):
@@ -1019,23 +1072,7 @@ def model_loss_grad_noisy_wide(desc, branch, trunk, y, params, noise, inv_batch_
     fixed; returns grad.  Raises Unsupported for n outside 7..9 and QheaError for a bad noise setting (shots > 0 included), in
     both cases before anything is launched.
     """
-    lib = load()
-    entry = 'qhea_model_loss_grad_noisy_wide'
-    B = _model_inputs(desc, branch, trunk, params, ham_diag)
-    _dev_f64(y, 'y')
-    if y.numel() != B:
-        raise QheaError(f"y has {y.numel()} elements, expected {B}")
-    _dev_f64(grad, 'grad')
-    if grad.numel() < params.numel() + 2:
-        raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
-    _dev_f64(pred, 'pred', (B,))
-    ws = _sized_ws(branch.device, lib.qhea_model_noisy_wide_grad_workspace_bytes, ctypes.byref(desc), int(B), ctypes.byref(noise))
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_loss_grad_noisy_wide(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
-                                                 _ptr(ham_diag), ctypes.byref(noise), float(inv_batch_total), _ptr(grad),
-                                                 _ptr(pred), _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_noisy_wide_grad(rc, entry)
-    return grad
+    return _loss_grad_sampled('wide', desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0, ham_diag, pred)
 
 
 def model_train_steps_noisy_wide(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
@@ -1046,22 +1083,27 @@ def model_train_steps_noisy_wide(desc, bounds, global_batches, branch, trunk, y,
     first_step + i, leaves [grads | sse | sum y^2] in rows[i] and applies Adam update first_step + i.  Bitwise a loop of
     model_loss_grad_noisy_wide (that seed, row0 = bounds[i]) + adam_step.
     """
-    lib = load()
-    entry = 'qhea_model_train_steps_noisy_wide'
-    if len(bounds) - 1 <= 0:
-        return rows
-    n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
-                                                    exp_avg, exp_avg_sq, ham_diag)
-    ws = _sized_ws(branch.device, lib.qhea_model_noisy_wide_grad_workspace_bytes, ctypes.byref(desc), int(biggest),
-                   ctypes.byref(noise))
-    with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_train_steps_noisy_wide(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
-                                                   _ptr(params), _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows),
-                                                   int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
-                                                   float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                                   _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_noisy_wide_grad(rc, entry)
-    return rows
+    return _train_steps_sampled('wide', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+
+
+def model_noisy_lds_grad_workspace_bytes(desc, batch, noise):
+    """qhea_model_noisy_lds_grad_workspace_bytes: 0 for a bad descriptor or noise setting (shot mode included) or n outside 10..12."""
+    return int(load().qhea_model_noisy_lds_grad_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(noise)))
+
+
+def model_loss_grad_noisy_lds(desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0=0, ham_diag=None, pred=None):
+    """model_loss_grad_noisy_wide at n = 10..12 (qhea_model_loss_grad_noisy_lds): same arguments, same quantity, psi and lambda
+    in LDS.  Raises Unsupported for n outside 10..12."""
+    return _loss_grad_sampled('lds', desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0, ham_diag, pred)
+
+
+def model_train_steps_noisy_lds(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                                lr, beta1, beta2, eps, weight_decay, noise, ham_diag=None):
+    """model_train_steps_noisy_wide at n = 10..12 (qhea_model_train_steps_noisy_lds): bitwise a loop of
+    model_loss_grad_noisy_lds (seed noise.seed + first_step + i, row0 = bounds[i]) + adam_step."""
+    return _train_steps_sampled('lds', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
 
 
 def model_device_noisy_log10_amplification(desc, noise):

@@ -46,18 +46,6 @@ __device__ __forceinline__ void set_gates(double4* gtab, F f) {
     if (threadIdx.x < N) gtab[threadIdx.x] = f((int)threadIdx.x);
     __syncthreads();
 }
-// Im<l|sigma|p> contributions of one pair (p0,p1),(l0,l1), accumulated as FMA chains: 4 fp64 instructions per product
-// (written as sums of differences the compiler may not reassociate: mul, fma, mul, fma, add, add)
-__device__ __forceinline__ void inner_x(const c2& p0, const c2& p1, const c2& l0, const c2& l1, double& X) {
-    X = fma(l0.x, p1.y, X); X = fma(-l0.y, p1.x, X); X = fma(l1.x, p0.y, X); X = fma(-l1.y, p0.x, X);
-}
-__device__ __forceinline__ void inner(const c2& p0, const c2& p1, const c2& l0, const c2& l1, double& X, double& Y,
-                                      double& Z) {
-    inner_x(p0, p1, l0, l1, X);
-    Y = fma(-l0.x, p1.x, Y); Y = fma(-l0.y, p1.y, Y); Y = fma(l1.x, p0.x, Y); Y = fma(l1.y, p0.y, Y);
-    Z = fma(l0.x, p0.y, Z); Z = fma(-l0.y, p0.x, Z); Z = fma(-l1.x, p1.y, Z); Z = fma(l1.y, p1.x, Z);
-}
-
 // One forward gate layer.  gate(q, u) fills u and returns whether qubit q has a gate (wave-uniform).
 // RING: the last pass scatters through the CNOT ring.
 template <int N, int LG, bool RING, class G>
@@ -85,47 +73,7 @@ __device__ __forceinline__ void fwd_layer(double2* s, const Bases<N, LG>& bs, G 
     });
 }
 
-// One reverse layer on psi and lambda: (ring^-1 via a gather in the first pass when RING), then per qubit the
-// inner products Im<lam|sigma|psi> (XYZ: all three, else X only) followed by the adjoint gate on both states.
-// gate(q, u) returns the ADJOINT coefficients.  acc: XYZ ? [3q..3q+2] : [q].
-template <int N, int LG, bool RING, bool XYZ, class G, int NA>
-__device__ __forceinline__ void bwd_layer(double2* psi, double2* lam, const Bases<N, LG>& bs, G gate, double (&acc)[NA]) {
-    constexpr int NP = LCfg<N, LG>::NP;
-    static_rfor<0, NP>([&](auto p) {
-        constexpr int P = decltype(p)::value;
-        using PS = Pass<N, P, LG>;
-        c2 v[1 << LG], l[1 << LG];
-        if constexpr (RING && P == NP - 1) {
-            load_group<N, PS::A, true, LG>(psi, bs.ring, v);
-            load_group<N, PS::A, true, LG>(lam, bs.ring, l);
-            __syncthreads();                               // all gathers done before anything is overwritten
-        } else {
-            load_group<N, PS::A, false, LG>(psi, bs.plain[P], v);
-            load_group<N, PS::A, false, LG>(lam, bs.plain[P], l);
-        }
-        static_for<PS::Q0, PS::Q1>([&](auto q) {
-            constexpr int Q = decltype(q)::value;
-            constexpr int LBIT = Q - PS::A;
-            double4 u;
-            if (gate(Q, u)) {
-                static_for<0, (1 << LG)>([&](auto jj) {
-                    constexpr int J = decltype(jj)::value;
-                    if constexpr (!(J & (1 << LBIT))) {
-                        constexpr int J1 = J | (1 << LBIT);
-                        if constexpr (XYZ) inner(v[J], v[J1], l[J], l[J1], acc[3 * Q], acc[3 * Q + 1], acc[3 * Q + 2]);
-                        else inner_x(v[J], v[J1], l[J], l[J1], acc[Q]);
-                        su2(v[J], v[J1], u);
-                        su2(l[J], l[J1], u);
-                    }
-                });
-            }
-        });
-        store_group<N, PS::A, false, LG>(psi, bs.plain[P], v);
-        store_group<N, PS::A, false, LG>(lam, bs.plain[P], l);
-        // the next pass: P - 1, or the last pass of the following (earlier) layer
-        pass_sync<(P > 0) && wave_local_passes<N, LG, P, (P > 0 ? P - 1 : 0)>()>();
-    });
-}
+// inner / inner_x and the reverse layer on psi and lambda (bwd_layer): hea_lds.hpp, shared with hea_noise_grad_lds.hip
 
 __device__ __forceinline__ double4 gate_u(const char* gates, int n, int sub, int q) {   // base variant of gate (sub,q)
     return *reinterpret_cast<const double4*>(gates + ((long)(sub + 1) * n + q) * kGateBytes);

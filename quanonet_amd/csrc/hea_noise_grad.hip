@@ -22,9 +22,9 @@
 // ones read, add and store, the same lane every time, so program order is all the ordering there is.  No atomics.
 // noisy_grad_fold_kernel: a row's tiles added in tile order and divided by T: pred (+ bias, as noisy_finish_kernel) and the
 // record rec[E + 3 n blk][B] that launch_density_reduce (hea_density_grad.hip) reads; that launch does the weights, the
-// frequency chain rule, grad[P], grad[P + 1] and Adam.
-#include "hea_density_grad.hpp"
-#include "hea_noise_traj.hpp"
+// frequency chain rule, grad[P], grad[P + 1] and Adam.  launch_noisy_grad_fold puts it behind hea_noise_grad_lds.hip's kernel
+// (n = 10..12) too; what the two units share on the host is hea_noise_grad.hpp.
+#include "hea_noise_grad.hpp"
 
 namespace qhea {
 namespace {
@@ -40,16 +40,8 @@ constexpr int kGradWaves = 4;               // waves per workgroup (independent;
 constexpr int kGradTile = QHEA_NOISE_GRAD_TILE;
 constexpr int kFoldThreads = 256;
 
-struct NoisyGradArgs {
-    NoiseArgs f;                            // the forward's record; f.tiles and f.partial are this unit's (tiles of kGradTile)
-    const double* hd;                       // the readout-confused ham_diag, or NULL
-    const double* w;                        // ansatz angles [blk, 3, n]
-    int blk, width;                         // sub-layers; width = E + 3 n blk
-    double* items;                          // [B * tiles][width]: d sum_t v / d x[e], then per (s, q) the (X, Y, Z) sums
-    double* pred;                           // the caller's [B] or NULL
-    double* pred_ws;                        // [B]
-    double* rec;                            // [width][B]: d pred_b / d x[b, e], then d pred_b / d w[s, k, q]
-};
+// NoisyGradArgs, the workspace layout, the checks and the entry points' bodies: hea_noise_grad.hpp, shared with
+// hea_noise_grad_lds.hip (n = 10..12)
 
 template <int N>
 __global__ __launch_bounds__(64 * kGradWaves) void noisy_grad_wave_kernel(NoisyGradArgs g) {
@@ -211,86 +203,29 @@ __global__ __launch_bounds__(kFoldThreads) void noisy_grad_fold_kernel(NoisyGrad
     out[(long)2 * n * a.B] = Y;
 }
 
-struct WideGradLayout { size_t off_gates, off_cs, off_part, off_mix, off_items, off_pred, off_rec, total; int tiles; long width; };
-WideGradLayout wide_grad_layout(const ModelInfo& mi, int64_t B, int64_t T) {
-    WideGradLayout L{};
-    L.tiles = (int)((T + kGradTile - 1) / kGradTile);
-    L.width = mi.sh.E + 3L * mi.n * mi.sh.blk;
-    const TableLayout t = table_layout(mi, B);
-    L.off_gates = t.off_gates; L.off_cs = t.off_cs;
-    size_t p = t.end;
-    L.off_part = p;  p = align256(p + (size_t)B * L.tiles * sizeof(double2));
-    L.off_mix = p;   p = align256(p + ((size_t)2 << mi.n) * sizeof(double));
-    L.off_items = p; p = align256(p + (size_t)B * L.tiles * L.width * sizeof(double));
-    L.off_pred = p;  p = align256(p + (size_t)B * sizeof(double));
-    L.off_rec = p;   p = align256(p + (size_t)B * L.width * sizeof(double));
-    L.total = p;
-    return L;
-}
-
-// What opens both calls: noisy_call_check's order for a trajectory call at n = 7..9, with shots > 0 refused as part of the
-// noise setting (the gradient is of expectation mode)
-int wide_grad_check(const qhea_model_desc* desc, const double* ham_diag, const qhea_noise* noise, int64_t row0, int64_t count,
-                    const double* trunk, std::initializer_list<const void*> required, void* workspace, void* stream,
-                    NoisyCall& c) {
-    ModelInfo mi;                                                        // (c.mi is noisy_call_check's to fill)
-    const int rc = model_info(desc, mi);
-    if (rc != QHEA_OK) return rc;
-    if (noise_values(noise) < 1 || noise->shots > 0) return QHEA_EINVAL;
-    return noisy_call_check({7, 9, true, false}, desc, ham_diag, noise, row0, count, trunk, required, workspace, stream, c);
-}
-
-// The regions of a checked call's workspace, laid out once for its largest batch
-struct WideGradCall {
-    const qhea_model_desc* desc; const ModelInfo& mi;
-    WideGradLayout L;
-    const double* ham_diag; const double* hd;       // hd: the mixed table (launched once per call), or NULL
-    char* ws; hipStream_t st;
-};
-
-int wide_grad_open(const qhea_model_desc* desc, const NoisyCall& c, int64_t bmax, const double* ham_diag, const qhea_noise* noise,
-                   size_t workspace_bytes, WideGradCall& w) {
-    w.L = wide_grad_layout(c.mi, bmax, c.T);
-    if (!c.ws || workspace_bytes < w.L.total) return QHEA_EWORKSPACE;
-    if (bmax * w.L.tiles > (int64_t)INT_MAX) return QHEA_EINVAL;         // one wave per (row, tile)
-    w.hd = nullptr;
-    if (ham_diag) return launch_readout_mix(ham_diag, noise->readout, c.mi.n, reinterpret_cast<double*>(c.ws + w.L.off_mix), c.st, &w.hd);
-    return QHEA_OK;
-}
-
-// prep, trajectories, fold, reduce (+ Adam when adam.p) for one batch under `noise` (its seed: the step's)
-int wide_grad_launch(const WideGradCall& w, const qhea_noise* noise, int64_t T, int64_t row0, int64_t batch, const double* branch,
-                     const double* trunk, const double* y, const double* params, double inv_bt, double* grad, double* pred,
-                     const AdamArgs& adam) {
-    double4* gates = reinterpret_cast<double4*>(w.ws + w.L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(w.ws + w.L.off_cs);
-    int rc = launch_prep_model(w.desc, w.mi, batch, branch, trunk, params, gates, cs, w.ws, w.st);
-    if (rc != QHEA_OK) return rc;
-    NoisyGradArgs g{};
-    g.f = noise_args(w.desc, w.mi, noise, params, w.ham_diag, row0, batch, T);
-    g.f.gates = gates; g.f.cs = cs; g.f.tiles = w.L.tiles;
-    g.f.partial = reinterpret_cast<double2*>(w.ws + w.L.off_part);
-    g.hd = w.hd; g.w = params + w.mi.off_ans; g.blk = (int)w.mi.sh.blk; g.width = (int)w.L.width;
-    g.items = reinterpret_cast<double*>(w.ws + w.L.off_items);
-    g.pred = pred; g.pred_ws = reinterpret_cast<double*>(w.ws + w.L.off_pred);
-    g.rec = reinterpret_cast<double*>(w.ws + w.L.off_rec);
-    const long items = batch * w.L.tiles;
+// one wave per (row, tile)
+int launch_wave(int n, const NoisyGradArgs& g, hipStream_t st) {
+    const long items = g.f.B * g.f.tiles;
     const dim3 grid((unsigned)((items + kGradWaves - 1) / kGradWaves)), block(64 * kGradWaves);
-    switch (w.mi.n) {
-        case 7: hipLaunchKernelGGL(noisy_grad_wave_kernel<7>, grid, block, 0, w.st, g); break;
-        case 8: hipLaunchKernelGGL(noisy_grad_wave_kernel<8>, grid, block, 0, w.st, g); break;
-        case 9: hipLaunchKernelGGL(noisy_grad_wave_kernel<9>, grid, block, 0, w.st, g); break;
+    switch (n) {
+        case 7: hipLaunchKernelGGL(noisy_grad_wave_kernel<7>, grid, block, 0, st, g); break;
+        case 8: hipLaunchKernelGGL(noisy_grad_wave_kernel<8>, grid, block, 0, st, g); break;
+        case 9: hipLaunchKernelGGL(noisy_grad_wave_kernel<9>, grid, block, 0, st, g); break;
         default: return QHEA_EUNSUPPORTED;
     }
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    const int units = g.f.E + w.mi.n * g.blk + 1;
-    hipLaunchKernelGGL(noisy_grad_fold_kernel, dim3((unsigned)((units + kFoldThreads - 1) / kFoldThreads), (unsigned)batch),
-                       dim3(kFoldThreads), 0, w.st, g, w.mi.n);
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    return launch_density_reduce(w.desc, w.mi, batch, branch, trunk, y, g.rec, g.pred_ws, inv_bt, grad, adam, w.st);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
 }
+constexpr GradUnit kWaveUnit{7, 9, kGradTile, launch_wave};
 
 }  // namespace
+
+int launch_noisy_grad_fold(const NoisyGradArgs& g, int n, int64_t batch, hipStream_t st) {
+    const int units = g.f.E + n * g.blk + 1;
+    hipLaunchKernelGGL(noisy_grad_fold_kernel, dim3((unsigned)((units + kFoldThreads - 1) / kFoldThreads), (unsigned)batch),
+                       dim3(kFoldThreads), 0, st, g, n);
+    return hipGetLastError() == hipSuccess ? QHEA_OK : QHEA_ELAUNCH;
+}
+
 }  // namespace qhea
 
 using namespace qhea;
@@ -298,23 +233,15 @@ using namespace qhea;
 extern "C" {
 
 size_t qhea_model_noisy_wide_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_noise* noise) {
-    ModelInfo mi;
-    const int64_t T = noise_values(noise);
-    if (T < 1 || noise->shots > 0 || batch < 0 || model_info(desc, mi) != QHEA_OK || mi.n < 7 || mi.n > 9) return 0;
-    return wide_grad_layout(mi, batch, T).total;
+    return wide_grad_workspace_bytes(kWaveUnit, desc, batch, noise);
 }
 
 int qhea_model_loss_grad_noisy_wide(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
                                     const double* trunk, const double* y, const double* params, const double* ham_diag,
                                     const qhea_noise* noise, double inv_batch_total, double* grad, double* pred, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    NoisyCall c;
-    int rc = wide_grad_check(desc, ham_diag, noise, row0, batch, trunk, {branch, y, params, grad}, workspace, stream, c);
-    if (rc != QHEA_OK || c.empty) return rc;
-    WideGradCall w{desc, c.mi, {}, ham_diag, nullptr, c.ws, c.st};
-    rc = wide_grad_open(desc, c, batch, ham_diag, noise, workspace_bytes, w);
-    if (rc != QHEA_OK) return rc;
-    return wide_grad_launch(w, noise, c.T, row0, batch, branch, trunk, y, params, inv_batch_total, grad, pred, AdamArgs{});
+    return wide_grad_loss_grad(kWaveUnit, desc, row0, batch, branch, trunk, y, params, ham_diag, noise, inv_batch_total, grad, pred,
+                               workspace, workspace_bytes, stream);
 }
 
 int qhea_model_train_steps_noisy_wide(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
@@ -325,25 +252,7 @@ int qhea_model_train_steps_noisy_wide(const qhea_model_desc* desc, int64_t n_ste
                                       double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
     const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
                          first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
-    if (!desc || n_steps < 0 || first_step < 1) return QHEA_EINVAL;
-    NoisyCall c;
-    int rc = wide_grad_check(desc, ham_diag, noise, 0, n_steps, trunk,
-                             {row_begin, inv_batch_total, branch, y, grad, params, exp_avg, exp_avg_sq}, workspace, stream, c);
-    if (rc != QHEA_OK || c.empty) return rc;
-    const int64_t bmax = call_max_batch(call, c.mi.P, *desc);
-    if (bmax < 0) return QHEA_EINVAL;
-    WideGradCall w{desc, c.mi, {}, ham_diag, nullptr, c.ws, c.st};
-    rc = wide_grad_open(desc, c, bmax, ham_diag, noise, workspace_bytes, w);
-    if (rc != QHEA_OK) return rc;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const StepView v = step_view(call, i, *desc);
-        qhea_noise nz = *noise;
-        nz.seed = noise->seed + (uint64_t)(first_step + i);              // fresh noise every step; a resumed run continues it
-        rc = wide_grad_launch(w, &nz, c.T, v.r0, v.nb, v.branch, v.trunk, v.y, params, v.inv_bt, v.grad, nullptr,
-                              adam_step(call, i, lr).adam);
-        if (rc != QHEA_OK) return rc;
-    }
-    return QHEA_OK;
+    return wide_grad_train_steps(kWaveUnit, desc, call, ham_diag, noise, lr);
 }
 
 }  // extern "C"

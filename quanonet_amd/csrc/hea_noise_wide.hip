@@ -154,45 +154,8 @@ struct WideScratch {                        // behind the state
     double u;
 };
 
-// One gate layer with the segment's frame behind it.  The last pass stores every amplitude where the ring (RING) and the X mask
-// send it, with the Z mask's sign; `tpl` = the thread's index bits in that pass.  sc->frame is written by thread 0 before the
-// layer's last barrier pair and read between the two.
-template <int N, bool RING, class G>
-__device__ __forceinline__ void noisy_layer(double2* s, const Bases<N, kWideLG>& bs, int tpl, const WideScratch* sc, G gate) {
-    constexpr int LG = kWideLG, NP = LCfg<N, LG>::NP;
-    static_for<0, NP>([&](auto p) {
-        constexpr int P = decltype(p)::value;
-        using PS = Pass<N, P, LG>;
-        c2 v[1 << LG];
-        load_group<N, PS::A, false, LG>(s, bs.plain[P], v);
-        static_for<PS::Q0, PS::Q1>([&](auto q) {
-            constexpr int Q = decltype(q)::value;
-            apply_group<Q - PS::A, LG>(v, gate(Q));
-        });
-        if constexpr (P < NP - 1) {
-            store_group<N, PS::A, false, LG>(s, bs.plain[P], v);
-            pass_sync<wave_local_passes<N, LG, P, P + 1>()>();
-        } else {
-            __syncthreads();                               // every thread holds its amplitudes: safe to permute
-            const int px = uniform(sc->frame[0]), z = uniform(sc->frame[1]);
-            store_framed<N, PS::A, RING, LG>(s, RING ? bs.ring : bs.plain[P], px, z, tpl, v);
-            __syncthreads();
-        }
-    });
-}
-
-template <int NW>
-__device__ __forceinline__ double wide_block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    if constexpr (NW == 1) return v;
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double tot = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) tot += red[w];
-    return tot;
-}
+// the gate layer with a segment's frame behind it (noisy_layer) and the workgroup sum (wide_block_sum): hea_lds.hpp, shared
+// with hea_noise_grad_lds.hip; the frame is sc->frame, written by thread 0 before the layer
 
 template <int N>
 __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(NoiseArgs a, const double* __restrict__ hd) {
@@ -227,7 +190,7 @@ __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(N
                     enc_frame<N>(segment_codes(a, loc, N, N, traj, wi.row, lane), loc, x, z);
                     if (t == 0) { sc->frame[0] = phys<LG>(x); sc->frame[1] = z; }
                 }
-                noisy_layer<N, false>(psi, bs, tpl, sc, [&](int q) { return rx_su2(wi.csr[col + q]); });
+                noisy_layer<N, false, LG>(psi, bs, tpl, sc->frame, [&](int q) { return rx_su2(wi.csr[col + q]); });
                 col += N; loc += N;
                 for (int l = 0; l < a.ld[g]; ++l, ++s, loc += 2 * N) {
                     if (wave == 0) {
@@ -235,7 +198,7 @@ __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(N
                         sub_frame<N>(segment_codes(a, loc, 2 * N, N, traj, wi.row, lane), loc, x, z);
                         if (t == 0) { sc->frame[0] = phys<LG>(x); sc->frame[1] = ring_pull<N>(z); }
                     }
-                    noisy_layer<N, true>(psi, bs, tpl, sc, [&](int q) { return a.gates[2 * ((s + 1) * N + q)]; });
+                    noisy_layer<N, true, LG>(psi, bs, tpl, sc->frame, [&](int q) { return a.gates[2 * ((s + 1) * N + q)]; });
                 }
             }
         }
@@ -243,7 +206,7 @@ __global__ __launch_bounds__((LCfg<N, kWideLG>::T)) void noisy_wide_lds_kernel(N
             constexpr double kR = 0.70710678118654752440;
             const double4 ub = a.pauli == QHEA_PAULI_X ? make_double4(kR, 0.0, kR, 0.0) : make_double4(kR, 0.0, 0.0, -kR);
             if (t == 0) { sc->frame[0] = 0; sc->frame[1] = 0; }
-            noisy_layer<N, false>(psi, bs, tpl, sc, [&](int) { return ub; });
+            noisy_layer<N, false, LG>(psi, bs, tpl, sc->frame, [&](int) { return ub; });
         }
         if (a.shots && wave == 0) {
             double u;

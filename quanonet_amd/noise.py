@@ -433,6 +433,36 @@ def noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, row0=0):
                                            ham_diag=ham_diag)
 
 
+def sampled_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, row0=0):
+    """
+    noisy_loss_and_grad for every qubit count a sampled gradient exists for, n = 7..12: at n = 7..9 it IS noisy_loss_and_grad
+    (qhea_model_loss_grad_noisy_wide, bitwise), at n = 10..12 the same quantity from qhea_model_loss_grad_noisy_lds (psi and
+    lambda in LDS).  For n <= 6 exact_noisy_loss_and_grad is the call.
+    """
+    _uniform_only(noise, 'sampled_noisy_loss_and_grad',
+                  "relaxation jumps depend on the state, so a sampled DeviceNoise has no fixed-stream gradient")
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("sampled_noisy_loss_and_grad takes a QuanONetPT or HEAQNNPT model")
+    if noise.shots > 0:
+        raise ValueError("sampled_noisy_loss_and_grad differentiates expectation mode (shots = 0); a sampled bitstring has no "
+                         "gradient")
+    n = int(model.fused_desc().n_qubits)
+    if n <= 6:
+        raise ValueError(f"sampled_noisy_loss_and_grad covers n = 7..12 (got n = {n}); exact_noisy_loss_and_grad is the call "
+                         "for n <= 6")
+    if n <= 9:
+        return noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=inv_batch_total, row0=row0)
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'sampled_noisy_loss_and_grad')
+    B = branch.shape[0]
+    y = y.detach().to(torch.float64).reshape(-1).contiguous()
+    grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
+    if B == 0:
+        return grad
+    inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
+    return _lib.model_loss_grad_noisy_lds(desc, branch, trunk, y, flat, noise.params(), inv, grad, row0=int(row0),
+                                          ham_diag=ham_diag)
+
+
 def _device_noise(noise, who):
     if not isinstance(noise, DeviceNoise):
         raise ValueError(f"{who} takes a DeviceNoise (got {type(noise).__name__}); a NoiseModel goes to its uniform "

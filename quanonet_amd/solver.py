@@ -321,8 +321,8 @@ def _train_device_noise(v, train_noise=None):
                      f"(got {type(v).__name__}); a NoiseModel goes to train_noise")
 
 
-def _train_sampling(v):
-    """config value / argument `train_sampling` -> Sampling or None (a Sampling, or its asdict() form)"""
+def _train_sampling(v, key='train_sampling'):
+    """config value / argument `train_sampling` or `train_trajectories` -> Sampling or None (a Sampling, or its asdict() form)"""
     if v is None:
         return None
     from .noise import Sampling
@@ -330,7 +330,7 @@ def _train_sampling(v):
         return v
     if isinstance(v, dict):
         return Sampling(**v)
-    raise ValueError(f"train_sampling must be a quanonet_amd.noise.Sampling or its asdict() form (got {type(v).__name__})")
+    raise ValueError(f"{key} must be a quanonet_amd.noise.Sampling or its asdict() form (got {type(v).__name__})")
 
 
 class DataParallelTrainer:
@@ -343,23 +343,30 @@ class DataParallelTrainer:
 
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
                  fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None,
-                 train_sampling=None):
+                 train_sampling=None, train_trajectories=None):
         self.model = model
         self.train_noise = _train_noise(train_noise)
         self.train_device_noise = _train_device_noise(train_device_noise, train_noise)
-        self.train_sampling = _train_sampling(train_sampling)
+        # Two keys, one meaning: train_sampling keeps the range it was introduced with (n = 7..9, and its refusal beyond),
+        # train_trajectories is the same request for every n a sampled gradient exists for (7..12).  self.train_sampling is the
+        # Sampling in force under either key, self.sampling_key the key it came by.
+        if train_sampling is not None and train_trajectories is not None:
+            raise ValueError("train_sampling and train_trajectories say the same thing: set one of them (train_trajectories "
+                             "covers n = 7..12, train_sampling n = 7..9)")
+        self.sampling_key = key = 'train_sampling' if train_trajectories is None else 'train_trajectories'
+        self.train_sampling = _train_sampling(train_sampling if train_trajectories is None else train_trajectories, key)
         if self.train_sampling is not None:
-            # sampled-trajectory training (qhea_model_train_steps_noisy_wide): what it cannot combine with
+            # sampled-trajectory training (qhea_model_train_steps_noisy_wide / _lds): what it cannot combine with
             if self.train_device_noise is not None:
-                raise ValueError("train_sampling does not combine with train_device_noise: relaxation jumps depend on the state, "
+                raise ValueError(f"{key} does not combine with train_device_noise: relaxation jumps depend on the state, "
                                  "so a sampled DeviceNoise has no fixed-stream gradient")
             if self.train_noise is None:
-                raise ValueError("train_sampling needs train_noise: it says how the NoiseModel of train_noise is sampled")
+                raise ValueError(f"{key} needs train_noise: it says how the NoiseModel of train_noise is sampled")
             if self.train_sampling.shots > 0:
-                raise ValueError("train_sampling: training differentiates expectation mode (Sampling.shots = 0, trajectories "
+                raise ValueError(f"{key}: training differentiates expectation mode (Sampling.shots = 0, trajectories "
                                  "= T); a sampled bitstring has no gradient")
             if int(world_size) > 1:
-                raise ValueError("train_sampling: sampled-trajectory training runs on one device (world_size = 1)")
+                raise ValueError(f"{key}: sampled-trajectory training runs on one device (world_size = 1)")
         self.world = int(world_size)
         self.dist = dist
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -416,13 +423,19 @@ class DataParallelTrainer:
                                                                          p0.device, log=log)
                 self.peer_fused = self.peer is not None and self.desc is not None
         if self.train_sampling is not None:
-            # the loss is the sampled noisy one (qhea_model_loss_grad_noisy_wide): refuse here what the call would refuse
+            # the loss is the sampled noisy one (qhea_model_loss_grad_noisy_wide / _lds): refuse here what the call would refuse
+            key, nmax = self.sampling_key, 9 if self.sampling_key == 'train_sampling' else 12
             if self.desc is None or not isinstance(self.optimizer, FlatAdam):
-                raise ValueError("train_sampling needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
+                raise ValueError(f"{key} needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
                                  "Adam with betas / eps / weight_decay only)")
-            if not 7 <= self.desc.n_qubits <= 9:
-                raise ValueError(f"train_sampling: sampled-trajectory training takes n = 7..9 (this model: n = "
+            if not 7 <= self.desc.n_qubits <= nmax:
+                raise ValueError(f"{key}: sampled-trajectory training takes n = 7..{nmax} (this model: n = "
                                  f"{self.desc.n_qubits}); for n <= 6 train_noise alone trains on the exact noisy loss")
+            from . import _lib
+            # the pair of calls for this qubit count: the wave-resident kernels at n = 7..9, the LDS-resident one at n = 10..12
+            self._sampled_loss_grad, self._sampled_steps = (
+                (_lib.model_loss_grad_noisy_wide, _lib.model_train_steps_noisy_wide) if self.desc.n_qubits <= 9 else
+                (_lib.model_loss_grad_noisy_lds, _lib.model_train_steps_noisy_lds))
             if log is not None:
                 log(f"noise-aware training: the loss and 'loss_train' are the sampled noisy MSE under p1={self.train_noise.p1:g} "
                     f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g}, {self.train_sampling.trajectories} "
@@ -512,8 +525,8 @@ class DataParallelTrainer:
             data = (self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat)
             grad = self.flat if out is None else out
             if self.train_sampling is not None:          # (the stream of the NEXT update, global rows from 0)
-                _lib.model_loss_grad_noisy_wide(*data, self._sampled_noise(self.optimizer.t + 1), 1.0 / gb, grad,
-                                                ham_diag=self._ham_diag())
+                self._sampled_loss_grad(*data, self._sampled_noise(self.optimizer.t + 1), 1.0 / gb, grad,
+                                        ham_diag=self._ham_diag())
             elif self.train_device_noise is not None:
                 _lib.model_loss_grad_noisy_device_exact(*data, self._noise_params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
             elif self.train_noise is not None:
@@ -535,8 +548,8 @@ class DataParallelTrainer:
         """batch = (branch, trunk, y) or (x, y): this rank's shard.  Returns the flat buffer (device): self.flat, or
         `out` -- a caller's [numel + 2] fp64 buffer, honoured where accepts_out says so (PTSolver hands in one row per
         step of an epoch, so that the two logging scalars of every step stay on the device without a copy).
-        row0 (train_sampling only): the global index of the batch's first row, which keys its random streams -- a step of
-        train_steps has its bounds[i] there."""
+        row0 (train_sampling / train_trajectories only): the global index of the batch's first row, which keys its random
+        streams -- a step of train_steps has its bounds[i] there."""
         if out is not None and not self.accepts_out:
             out = None
         flat = self._last = self.flat if out is None else out
@@ -550,9 +563,9 @@ class DataParallelTrainer:
             if self.train_sampling is not None:
                 # the steps entry reads a step's global rows off its schedule; one step with rows of its own is the loop the
                 # entry is bitwise equal to: the single call under seed + step count, then the Adam launch
-                _lib.model_loss_grad_noisy_wide(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat,
-                                                self._sampled_noise(opt.t), 1.0 / gb, flat, row0=int(row0),
-                                                ham_diag=self._ham_diag())
+                self._sampled_loss_grad(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat,
+                                        self._sampled_noise(opt.t), 1.0 / gb, flat, row0=int(row0),
+                                        ham_diag=self._ham_diag())
                 _lib.adam_step(self.pflat, flat, opt.exp_avg, opt.exp_avg_sq, opt.t, *opt.hparams())
             elif self._noise_params() is not None:          # (the noise-aware paths have the steps entry only: one step of it)
                 self._steps(inputs, y, [0, y.shape[0]], [gb], flat.view(1, -1), opt.t)
@@ -587,13 +600,14 @@ class DataParallelTrainer:
 
     def _steps(self, inputs, y, bounds, global_batches, rows, first_step):
         """single device: the steps entry, ideal (qhea_model_train_steps), under train_noise (..._noisy_exact; with
-        train_sampling ..._noisy_wide) or under train_device_noise (..._noisy_device_exact)"""
+        train_sampling / train_trajectories ..._noisy_wide or ..._noisy_lds) or under train_device_noise
+        (..._noisy_device_exact)"""
         from . import _lib
         opt = self.optimizer
         call = (self.desc, bounds, global_batches, *split_inputs(inputs), y.reshape(-1), self.pflat, rows, opt.exp_avg,
                 opt.exp_avg_sq, first_step, *opt.hparams())
         if self.train_sampling is not None:
-            _lib.model_train_steps_noisy_wide(*call, self._sampled_noise(0), ham_diag=self._ham_diag())
+            self._sampled_steps(*call, self._sampled_noise(0), ham_diag=self._ham_diag())
         elif self.train_device_noise is not None:
             _lib.model_train_steps_noisy_device_exact(*call, self._noise_params(), ham_diag=self._ham_diag())
         elif self.train_noise is not None:
@@ -786,7 +800,8 @@ class PTSolver:
                                            peer_exchange=str(config.get('dp_exchange', 'peer')).lower() == 'peer',
                                            log=self.log, train_noise=config.get('train_noise'),
                                            train_device_noise=config.get('train_device_noise'),
-                                           train_sampling=config.get('train_sampling'))
+                                           train_sampling=config.get('train_sampling'),
+                                           train_trajectories=config.get('train_trajectories'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None
