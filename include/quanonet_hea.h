@@ -785,6 +785,90 @@ int    qhea_model_forward_noisy_device_wide(const qhea_model_desc* desc, int64_t
                                             void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Training under the calibrated device noise model at n = 7..9, where qhea_model_loss_grad_noisy_device_exact's density matrix
+ * no longer fits: the MSE loss of the quantum-jump estimate (qhea_model_forward_noisy_device, expectation mode) and an unbiased
+ * gradient of it.
+ *
+ * The estimator.  Fix a row and a random stream.  Trajectory k applies, in circuit order, the gates, the sampled Paulis, the
+ * dephasing flips and at every damping site one of two fixed linear operators, the unnormalised ones of the forward call:
+ * K0 = diag(1, sqrt(1 - gamma)) (no jump) or L = |0><1| (jump).  With psi~_k the unnormalised final state, N2_k = <psi~_k|psi~_k>
+ * and num_k = <psi~_k|h'|psi~_k> (h' the read-out weights with the asymmetric readout folded in), the probability of pattern k is
+ * c_k N2_k with c_k free of the parameters, the trajectory's value is num_k / N2_k, and the exact value is sum_k c_k num_k.  Hence
+ * d pred / d theta = sum_k c_k d num_k = E_k[ d num_k / N2_k ]:
+ *   the gradient of the unnormalised numerator is taken with the fired pattern held fixed and divided by the final N2.  The
+ *   norm is not differentiated, and the jump decisions are not differentiated.  (The score-function term of the pattern's
+ *   probability and the derivative of 1 / N2 cancel exactly; differentiating the normalised value with the pattern fixed is
+ *   biased.)
+ *   pred_b       = what qhea_model_forward_noisy_device returns for global row row0 + b under the same dn and sampling (to
+ *                  rounding, not bitwise: the tiles below are this call's own): the mean of the T trajectory values + bias;
+ *   loss         = sum_b (pred_b - y_b)^2 * inv_batch_total;
+ *   grad[0..P)   = sum_b 2 (pred_b - y_b) inv_batch_total * (the unbiased d pred_b / d params above), in the flat layout of
+ *                  qhea_model_loss_grad;  grad[P] = sum_b (pred_b - y_b)^2;  grad[P+1] = sum_b y_b^2.
+ *   As in qhea_model_loss_grad_noisy_wide the expectation of the sampled loss is the exact MSE + inv_batch_total sum_b Var_b / T,
+ *   and pred_b and d pred_b are taken from the same trajectories: the loss gradient is the exact one plus sampling noise plus a
+ *   term of order 1 / T.  The estimator is stated here, not corrected.
+ * The walk.  Per trajectory the forward walk of qhea_model_forward_noisy_device (n = 7..9), word for word; then
+ * lambda = h' psi~ / N2 behind the read-out's basis change; then lambda goes back through the ADJOINTS of the fixed operators
+ * (K0^dagger = K0, L^dagger = |1><0|, each with the polarity of the Pauli frame at its site; a segment's frame X^x Z^z is its own
+ * inverse up to the sign (-1)^parity(x & z), which is applied) and psi goes back beside it -- by the gates' inverses and K0^-1, and at a fired
+ * site, where L has no inverse, from a snapshot: the forward walk keeps psi~ at the start of every block, and the state before
+ * the jump is that snapshot walked forward again to the site (at most one block per fired jump).  Per fused RY RZ RY the sums
+ * Im<lambda|sigma|psi>, sigma = X, Y, Z, behind the gate; per encoding RX the X sum behind it.  The exact power-of-two rescale
+ * of the forward walk is crossed by both (psi 2^-100, lambda 2^100), so psi is always in the scale the forward walk had there
+ * and every product is unchanged; lambda stays finite while fewer than 9 rescales lie behind a point of the circuit (N2 of a
+ * pattern below 2^-1800, which no supported shape reaches).
+ * Random numbers: exactly those of the forward call (Philox calls, words, thresholds, the rule u N2 < gamma M) and only in the
+ * forward walk.  It records per segment (a block's encoding sites, or a sub-layer) four 32-bit words: which of its <= 27
+ * damping sites fired (and whether the rescale behind it did), the frame's polarity at each site, and the segment's final
+ * frame (X mask, Z mask).  The reverse walk and the re-walks read these words: no jump is decided twice.
+ * Summation, each order a function of n, the shape and T only:
+ *   1. a trajectory's value, the masked sums and N2: as in qhea_model_forward_noisy_device (2., 3., n = 7..9); its inner products
+ *      as in qhea_model_loss_grad_noisy_wide (1.);
+ *   2. a row's trajectories go in tiles of 4; inside a tile values and inner products are added in trajectory order;
+ *   3., 4. the tiles, the angles' derivatives and the rows as in qhea_model_loss_grad_noisy_wide (3., 4.).
+ * Workspace: a function of the shape, the batch and T only, never of how many jumps fire: the tables, (E + 3 n blk) doubles per
+ * (row, tile) and per row, and per launched wave -- min(batch * ceil(T / 4), 2048) of them, which take the (row, tile) items in
+ * a grid-stride loop -- one state per block and 1 KiB per segment.  An item's result does not depend on the wave that walks it.
+ * No trajectory is dropped, truncated or capped.
+ * qhea_model_train_steps_noisy_device: the arguments of qhea_model_train_steps_noisy_wide with dn and sampling in the place of
+ * noise.  Step i has the Adam count t = first_step + i, draws from the stream keyed sampling->seed + t (mod 2^64) with global rows
+ * row_begin[i] + r, and is bitwise qhea_model_loss_grad_noisy_device with that seed and row0 = row_begin[i] followed by
+ * qhea_adam_step; a run resumed at first_step reproduces an uninterrupted one.  The workspace must fit the largest step.
+ * Scope: n = 7..9, one device, sampling.shots = 0, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs.
+ * Errors, all before anything is launched and with the outputs untouched, in the order of qhea_model_forward_noisy_device: a bad
+ * descriptor; QHEA_EINVAL for a bad device setting, a NULL sampling, shots != 0 (shot mode has no such gradient) and
+ * trajectories < 1; QHEA_EUNSUPPORTED for n <= 6 (qhea_model_loss_grad_noisy_device_exact) and n >= 10; QHEA_EINVAL for a bad
+ * read-out, a negative batch or row0, first_step < 1, NULL arrays; QHEA_EINVAL for a site with 1 - gamma == 0 in fp64, which no
+ * inverse undoes (qhea_device_noise_singular_site names it: 1 and *site (0 ENC, 1 ROT, 2 CTL, 3 TGT), *wire for the first such
+ * site, 0 if there is none); QHEA_EINVAL for batch * ceil(T / 4) > 2^31 - 1; QHEA_EWORKSPACE.  An empty batch (or n_steps = 0)
+ * returns QHEA_OK.  There is no amplification guard: K0^-1 is a relative scaling of one half of the state by
+ * 1 / sqrt(1 - gamma), which lambda's K0 takes back in every product.
+ * Launches: per CALL the kernel that writes the per-site constants and h'; per step the prep kernel, the trajectory kernel, the
+ * fold kernel and the reduce kernel (with Adam in train_steps) of qhea_model_loss_grad_noisy_wide.  A linear chain, no
+ * allocation, no synchronisation (hipGraph-capturable).  No atomics and fixed orders: results are bitwise reproducible.
+ */
+int    qhea_device_noise_singular_site(int n, const qhea_device_noise* dn /*HOST*/, int* site /*HOST or NULL*/, int* wire /*HOST or NULL*/);
+/* DEVICE scratch bytes for the two calls on (at most) `batch` rows (0 on a bad descriptor or sampling record, shots != 0, or n
+ * outside 7..9). */
+size_t qhea_model_noisy_device_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling);
+int    qhea_model_loss_grad_noisy_device(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                         const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                         const double* params, const double* ham_diag,
+                                         const qhea_device_noise* dn /*HOST*/, const qhea_sampling* sampling /*HOST: shots = 0*/,
+                                         double inv_batch_total, double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_device(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                           const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                           const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                           const double* ham_diag, const qhea_device_noise* dn /*HOST*/,
+                                           const qhea_sampling* sampling /*HOST*/,
+                                           const double* inv_batch_total /*HOST [n_steps]*/,
+                                           double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                           double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                           double beta2, double eps, double weight_decay, void* workspace,
+                                           size_t workspace_bytes, void* stream);
+
+/*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the
  * SAME parameters -- the chunk loop of PTSolver.evaluate / infer.predict (solvers/solver_pt.py:299-310, infer.py:274-289) in
  * one host call.  The layer records depend on the parameters alone, so one preparation launch serves all chunks of

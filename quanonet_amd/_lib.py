@@ -45,7 +45,9 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_device_noise_jump_tables', 'qhea_model_noisy_device_workspace_bytes', 'qhea_model_forward_noisy_device',
            'qhea_model_noisy_device_wide_workspace_bytes', 'qhea_model_forward_noisy_device_wide',
            'qhea_model_noisy_wide_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_wide', 'qhea_model_train_steps_noisy_wide',
-           'qhea_model_noisy_lds_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_lds', 'qhea_model_train_steps_noisy_lds']
+           'qhea_model_noisy_lds_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_lds', 'qhea_model_train_steps_noisy_lds',
+           'qhea_device_noise_singular_site', 'qhea_model_noisy_device_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_device',
+           'qhea_model_train_steps_noisy_device']
 
 
 class ModelDesc(ctypes.Structure):
@@ -82,7 +84,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 590           # 0.5.9: + qhea_model_loss_grad_noisy_lds / ..._train_steps_noisy_lds (sampled-trajectory gradients, n = 10..12)
+MIN_LIB_VERSION = 600           # 0.6.0: + qhea_model_loss_grad_noisy_device / ..._train_steps_noisy_device (quantum-jump trajectory gradients, n = 7..9)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -277,6 +279,17 @@ def load():
     lib.qhea_model_train_steps_noisy_device_exact.restype = ctypes.c_int
     lib.qhea_model_train_steps_noisy_device_exact.argtypes = [dnp if t is npp else t
                                                               for t in lib.qhea_model_train_steps_noisy_exact.argtypes]
+    lib.qhea_device_noise_singular_site.restype = ctypes.c_int
+    lib.qhea_device_noise_singular_site.argtypes = [ctypes.c_int, dnp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.qhea_model_noisy_device_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_device_grad_workspace_bytes.argtypes = lib.qhea_model_noisy_device_workspace_bytes.argtypes
+    lib.qhea_model_loss_grad_noisy_device.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_device.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, dp, dp, dp, dp, dp, dnp, spp, ctypes.c_double,
+                                                      dp, dp, vp, ctypes.c_size_t, vp]
+    lib.qhea_model_train_steps_noisy_device.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_device.argtypes = [mdp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), dp, dp, dp, dp, dp, dnp,
+                                                        spp, ctypes.POINTER(ctypes.c_double), dp, ctypes.c_int64, dp, dp,
+                                                        ctypes.c_int64] + [ctypes.c_double] * 5 + [vp, ctypes.c_size_t, vp]
     _lib = lib
     return lib
 
@@ -1104,6 +1117,95 @@ def model_train_steps_noisy_lds(desc, bounds, global_batches, branch, trunk, y, 
     model_loss_grad_noisy_lds (seed noise.seed + first_step + i, row0 = bounds[i]) + adam_step."""
     return _train_steps_sampled('lds', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
                                 first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+
+
+def model_noisy_device_grad_workspace_bytes(desc, batch, sampling):
+    """qhea_model_noisy_device_grad_workspace_bytes: 0 for a bad descriptor or sampling record (shot mode included) or n outside 7..9."""
+    return int(load().qhea_model_noisy_device_grad_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(sampling)))
+
+
+SITE_NAMES = ('ENC', 'ROT', 'CTL', 'TGT')
+
+
+def device_noise_singular_site(n, noise):
+    """qhea_device_noise_singular_site (host only): (site name, wire) of the first relaxation site of `noise` (a DeviceNoiseParams)
+    with 1 - gamma == 0, which the trajectory gradient cannot walk back, or None."""
+    site, wire = ctypes.c_int(0), ctypes.c_int(0)
+    rc = load().qhea_device_noise_singular_site(int(n), ctypes.byref(noise), ctypes.byref(site), ctypes.byref(wire))
+    if rc < 0:
+        _check(rc, 'qhea_device_noise_singular_site')
+    return (SITE_NAMES[site.value], wire.value) if rc == 1 else None
+
+
+def _check_device_sampled(rc, who, desc, noise):
+    if rc == -2:
+        raise Unsupported(f"{who}: n outside 7..9 (n <= 6: the exact calls under a device noise model; n >= 10: not built)")
+    if rc == -1:
+        hit = None
+        try:
+            hit = device_noise_singular_site(desc.n_qubits, noise)
+        except QheaError:
+            pass
+        if hit:
+            raise QheaError(f"{who}: relaxation site {hit[0]} on wire {hit[1]} has gamma = 1 (1 - gamma == 0 in fp64): the "
+                            "trajectory gradient cannot walk it back")
+    _check(rc, who)
+
+
+def model_loss_grad_noisy_device(desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0=0, ham_diag=None,
+                                 pred=None):
+    """
+    model_loss_grad of the quantum-jump estimate under `noise` (a DeviceNoiseParams) with the estimator `sampling` (a
+    SamplingParams in expectation mode), n = 7..9 (qhea_model_loss_grad_noisy_device): fills grad[P+2] = [d loss/d params | sse |
+    sum y^2] where pred is what model_forward_noisy_device returns for the same arguments and global rows row0 + b, and
+    d pred / d params is the unbiased estimate stated in include/quanonet_hea.h (the unnormalised numerator's gradient with the
+    fired pattern fixed, over the final norm); returns grad.  Raises Unsupported for n outside 7..9 and QheaError for a bad
+    setting (shots != 0 and a site with gamma = 1 included), in both cases before anything is launched.
+    """
+    lib = load()
+    entry = 'qhea_model_loss_grad_noisy_device'
+    B = _model_inputs(desc, branch, trunk, params, ham_diag)
+    _dev_f64(y, 'y')
+    if y.numel() != B:
+        raise QheaError(f"y has {y.numel()} elements, expected {B}")
+    _dev_f64(grad, 'grad')
+    if grad.numel() < params.numel() + 2:
+        raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
+    _dev_f64(pred, 'pred', (B,))
+    ws = _sized_ws(branch.device, lib.qhea_model_noisy_device_grad_workspace_bytes, ctypes.byref(desc), int(B), ctypes.byref(sampling))
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_loss_grad_noisy_device(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+                                                   _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling),
+                                                   float(inv_batch_total), _ptr(grad), _ptr(pred), _ptr(ws),
+                                                   0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_device_sampled(rc, entry, desc, noise)
+    return grad
+
+
+def model_train_steps_noisy_device(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                                   lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag=None):
+    """
+    model_train_steps with the quantum-jump loss under a device noise model (qhea_model_train_steps_noisy_device, n = 7..9): step
+    i trains on rows bounds[i]:bounds[i+1] (their global row indices key the random stream) with the stream key sampling.seed +
+    first_step + i, leaves [grads | sse | sum y^2] in rows[i] and applies Adam update first_step + i.  Bitwise a loop of
+    model_loss_grad_noisy_device (that seed, row0 = bounds[i]) + adam_step.
+    """
+    lib = load()
+    entry = 'qhea_model_train_steps_noisy_device'
+    if len(bounds) - 1 <= 0:
+        return rows
+    n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
+                                                    exp_avg, exp_avg_sq, ham_diag)
+    ws = _sized_ws(branch.device, lib.qhea_model_noisy_device_grad_workspace_bytes, ctypes.byref(desc), int(biggest),
+                   ctypes.byref(sampling))
+    with torch.cuda.device(branch.device):
+        rc = lib.qhea_model_train_steps_noisy_device(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+                                                     _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling), ib, _ptr(rows),
+                                                     int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
+                                                     float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                                                     _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    _check_device_sampled(rc, entry, desc, noise)
+    return rows
 
 
 def model_device_noisy_log10_amplification(desc, noise):

@@ -500,3 +500,40 @@ def device_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
     inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
     return _lib.model_loss_grad_noisy_device_exact(desc, branch, trunk, y, flat, noise.params(desc.n_qubits), inv, grad,
                                                    ham_diag=ham_diag)
+
+
+def device_sampled_loss_and_grad(model, inputs, y, device_noise, sampling, inv_batch_total=None, row0=0):
+    """
+    The MSE loss of the quantum-jump estimate under a DeviceNoise -- device_noisy_predict(model, inputs, device_noise, sampling,
+    row0=row0) in expectation mode -- and an unbiased gradient of it: (flat [P + 2] tensor of qhea_model_loss_grad_noisy_device,
+    pred[B]).  Per trajectory the gradient of the UNNORMALISED numerator is taken with the fired jump pattern held fixed and
+    divided by the final norm; neither the norm nor the jump decisions are differentiated (the two terms cancel: the header
+    states the estimator).  The loss also carries the trajectories' variance / T.  n = 7..9, where no density matrix fits; for
+    n <= 6 device_noisy_loss_and_grad is the exact call.
+    """
+    _device_noise(device_noise, 'device_sampled_loss_and_grad')
+    if not isinstance(sampling, Sampling):
+        raise ValueError(f"device_sampled_loss_and_grad takes a Sampling (got {type(sampling).__name__})")
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("device_sampled_loss_and_grad takes a QuanONetPT or HEAQNNPT model")
+    if sampling.shots != 0:
+        raise ValueError("device_sampled_loss_and_grad differentiates expectation mode (Sampling.shots = 0, trajectories = T); a "
+                         "sampled bitstring has no gradient")
+    n = int(model.fused_desc().n_qubits)
+    if n <= 6:
+        raise ValueError(f"device_sampled_loss_and_grad covers n = 7..9 (got n = {n}); device_noisy_loss_and_grad is the exact "
+                         "call for n <= 6")
+    if n >= 10:
+        raise ValueError(f"device_sampled_loss_and_grad covers n = 7..9 (got n = {n}); device_noisy_predict evaluates n = 10..12, "
+                         "no gradient is built there")
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'device_sampled_loss_and_grad')
+    B = branch.shape[0]
+    y = y.detach().to(torch.float64).reshape(-1).contiguous()
+    grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
+    pred = torch.empty(B, dtype=torch.float64, device=branch.device)
+    if B == 0:
+        return grad, pred
+    inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
+    _lib.model_loss_grad_noisy_device(desc, branch, trunk, y, flat, device_noise.params(desc.n_qubits), sampling.params(), inv,
+                                      grad, row0=int(row0), ham_diag=ham_diag, pred=pred)
+    return grad, pred

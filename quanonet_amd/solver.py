@@ -357,10 +357,13 @@ class DataParallelTrainer:
         self.train_sampling = _train_sampling(train_sampling if train_trajectories is None else train_trajectories, key)
         if self.train_sampling is not None:
             # sampled-trajectory training (qhea_model_train_steps_noisy_wide / _lds): what it cannot combine with
-            if self.train_device_noise is not None:
-                raise ValueError(f"{key} does not combine with train_device_noise: relaxation jumps depend on the state, "
-                                 "so a sampled DeviceNoise has no fixed-stream gradient")
-            if self.train_noise is None:
+            # ... or quantum-jump training under a device model (qhea_model_train_steps_noisy_device): train_trajectories beside
+            # train_device_noise
+            if self.train_device_noise is not None and key == 'train_sampling':
+                raise ValueError("train_sampling does not combine with train_device_noise: train_trajectories is the key that "
+                                 "says how the DeviceNoise of train_device_noise is sampled (quantum-jump trajectories, "
+                                 "n = 7..9)")
+            if self.train_device_noise is None and self.train_noise is None:
                 raise ValueError(f"{key} needs train_noise: it says how the NoiseModel of train_noise is sampled")
             if self.train_sampling.shots > 0:
                 raise ValueError(f"{key}: training differentiates expectation mode (Sampling.shots = 0, trajectories "
@@ -422,7 +425,43 @@ class DataParallelTrainer:
                 self.peer, self.dp_exchange_reason = PeerExchange.create(dist, dist.get_rank(), self.world, self.numel + 2,
                                                                          p0.device, log=log)
                 self.peer_fused = self.peer is not None and self.desc is not None
-        if self.train_sampling is not None:
+        self.device_sampled = self.train_sampling is not None and self.train_device_noise is not None
+        if self.device_sampled:
+            # the loss is the quantum-jump estimate under the device model (qhea_model_loss_grad_noisy_device)
+            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+                raise ValueError("train_device_noise with train_trajectories needs the fused model-level path (a fp64 QuanONetPT "
+                                 "/ HEAQNNPT on a HIP device, Adam with betas / eps / weight_decay only)")
+            from . import _lib
+            n = self.desc.n_qubits
+            if n <= 6:
+                raise ValueError(f"train_device_noise with train_trajectories: quantum-jump training takes n = 7..9 (this model: "
+                                 f"n = {n}); for n <= 6 train_device_noise alone trains on the exact loss under the device model")
+            if n >= 10:
+                raise ValueError(f"train_device_noise with train_trajectories: quantum-jump training takes n = 7..9 (this model: "
+                                 f"n = {n}); at n = 10..12 a DeviceNoise can be evaluated (device_noisy_predict), and train_noise "
+                                 "with train_trajectories trains under uniform gate noise")
+            try:
+                hit = _lib.device_noise_singular_site(n, self.train_device_noise.params(n))
+            except _lib.QheaError as e:
+                raise ValueError(f"train_device_noise: {e}") from e
+            if hit:
+                raise ValueError(f"train_device_noise with train_trajectories: relaxation site {hit[0]} on wire {hit[1]} has "
+                                 "gamma = 1, which the trajectory gradient cannot walk back")
+
+            def loss_grad(desc, branch, trunk, y, params, sampling, inv, grad, row0=0, ham_diag=None):
+                return _lib.model_loss_grad_noisy_device(desc, branch, trunk, y, params, self.train_device_noise.params(n),
+                                                         sampling, inv, grad, row0=row0, ham_diag=ham_diag)
+
+            def steps(*call, ham_diag=None):
+                *head, sampling = call
+                return _lib.model_train_steps_noisy_device(*head, self.train_device_noise.params(n), sampling, ham_diag=ham_diag)
+
+            self._sampled_loss_grad, self._sampled_steps = loss_grad, steps
+            if log is not None:
+                log("device-noise training: the loss and 'loss_train' are the quantum-jump estimate of the MSE under the "
+                    f"DeviceNoise of train_device_noise, {self.train_sampling.trajectories} trajectories per row, stream seed "
+                    f"{self.train_sampling.seed} + step count")
+        elif self.train_sampling is not None:
             # the loss is the sampled noisy one (qhea_model_loss_grad_noisy_wide / _lds): refuse here what the call would refuse
             key, nmax = self.sampling_key, 9 if self.sampling_key == 'train_sampling' else 12
             if self.desc is None or not isinstance(self.optimizer, FlatAdam):
@@ -458,7 +497,7 @@ class DataParallelTrainer:
                 log(f"noise-aware training: the loss and 'loss_train' are the exact noisy MSE under p1={self.train_noise.p1:g} "
                     f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g} (log10 amplification {amp:.2f})")
 
-        if self.train_device_noise is not None:
+        if self.train_device_noise is not None and not self.device_sampled:
             # the loss is the exact one under the device model (qhea_model_loss_grad_noisy_device_exact): the same refusals
             if self.desc is None or not isinstance(self.optimizer, FlatAdam):
                 raise ValueError("train_device_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP "
@@ -474,7 +513,8 @@ class DataParallelTrainer:
             if refused:
                 raise ValueError(f"train_device_noise: the library refuses this model under this DeviceNoise (n = {n}, log10 "
                                  f"amplification {amp:.2f}): n <= 6 and a log10 amplification within the bound of "
-                                 "include/quanonet_hea.h are needed; see quanonet_amd.noise.device_amplification")
+                                 "include/quanonet_hea.h are needed; see quanonet_amd.noise.device_amplification.  At "
+                                 "n = 7..9 train_trajectories beside train_device_noise trains on quantum-jump trajectories")
             if self.peer_fused:
                 self.peer_fused = False
                 self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
@@ -494,6 +534,8 @@ class DataParallelTrainer:
         steps entry takes (it adds the step count itself), the Adam count that of one step's own call"""
         tn, sp = self.train_noise, self.train_sampling
         from . import _lib
+        if self.device_sampled:                 # the device record travels beside it: the qhea_sampling of that step
+            return _lib.SamplingParams(0, int(sp.trajectories), (int(sp.seed) + int(step)) & ((1 << 64) - 1))
         return _lib.NoiseParams(float(tn.p1), float(tn.p2), float(tn.readout), 0, int(sp.trajectories),
                                 (int(sp.seed) + int(step)) & ((1 << 64) - 1))
 
