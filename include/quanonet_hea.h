@@ -869,6 +869,65 @@ int    qhea_model_train_steps_noisy_device(const qhea_model_desc* desc, int64_t 
                                            size_t workspace_bytes, void* stream);
 
 /*
+ * qhea_model_loss_grad_noisy_device_lds / qhea_model_train_steps_noisy_device_lds (library version 610): the two calls above for
+ * n = 10, 11 and 12, where psi and lambda live in LDS (hea_noise_device_grad_lds.hip).  The arguments, the quantity, the
+ * estimator (d pred_b = E_k[d num_k / N2_k] with the fired pattern held fixed; neither the norm nor the jump decisions are
+ * differentiated), the loss's Var / T term (stated, not corrected), the errors and their order, train_steps' stream keys
+ * (sampling->seed + first_step + i, mod 2^64, global rows row_begin[i] + r; bitwise the single call followed by qhea_adam_step)
+ * and the launch chain are those of qhea_model_loss_grad_noisy_device; qhea_model_loss_grad_noisy_device itself keeps returning
+ * QHEA_EUNSUPPORTED at n >= 10, and these return it at n <= 9.
+ *   pred_b = what qhea_model_forward_noisy_device_wide returns for global row row0 + b under the same dn and sampling, to
+ *   rounding (the tiles below are this call's own).
+ * Random numbers: exactly those of qhea_model_forward_noisy_device_wide (Philox calls, words, thresholds, u N2 < gamma M), drawn
+ * only in the forward walk, which is that call's code.  Per segment it records eight 32-bit words in the workspace: which of
+ * the segment's <= 36 sites fired (site q < n the segment's own site of wire q, n + 2 j the TGT and n + 2 j + 1 the CTL site of
+ * slot j: bits 0..31 in word 0, 32..35 in word 1, whose bit 31 says that the rescale behind the segment fired), the frame's X
+ * bit on the site's wire when the site was reached (words 2, 3), and the frame the segment's last store applied (word 4 the X
+ * mask in LDS slot bits, word 5 the Z mask pulled back through the ring); words 6, 7 are unused.  The reverse walk and the
+ * re-walks read them: nothing is decided or drawn twice.
+ * The walk is that of qhea_model_loss_grad_noisy_device in the LDS layout: 2^(n-4) threads, 16 amplitudes per thread and pass at
+ * every n and in both directions; a site is a diagonal step on those 16 with the forward's stored-bit masks and the recorded
+ * polarity (no jump: psi by 1 / sqrt(1 - gamma), lambda by sqrt(1 - gamma); jump: lambda by the projector, its X sits in the
+ * recorded frame, psi from the block's snapshot walked forward to the site).  A segment's last store and the reverse walk's
+ * first gather are exact inverses (both drop the frame's sign (-1)^parity(x & z), and so does every re-walk), so no sign is
+ * applied here.
+ * Summation, each order a function of n, the shape and T only:
+ *   1. a site's masked sum and a trajectory's num and N2: as in qhea_model_forward_noisy_device_wide (the thread's 16 terms in
+ *      local-index order, the wave by the butterfly with offsets 32 .. 1, the waves in wave order);
+ *   2. an inner product: the thread's pairs in local-index order as FMA chains, the wave by the transposing butterfly over lane
+ *      bits 0 .. 5, the waves in wave order (as qhea_model_loss_grad_noisy_lds, 1., with 16 amplitudes per thread at every n);
+ *   3. a row's trajectories go in tiles of 2; inside a tile values and inner products are added in trajectory order;
+ *   4., 5. the tiles, the angles' derivatives and the rows as in qhea_model_loss_grad_noisy_wide (3., 4.).
+ * Workspace: a function of the shape, the batch and T only, never of how many jumps fire: the tables, (E + 3 n blk) doubles per
+ * (row, tile) and per row, and per launched workgroup -- min(batch * ceil(T / 2), qhea_noisy_device_lds_grad_max_workgroups(n))
+ * of them, which take the (row, tile) items in a grid-stride loop -- 2^n * 16 bytes per block and 32 bytes per segment.  An
+ * item's result does not depend on the workgroup that walks it, so results do not depend on batch, grid or chunking.  No
+ * trajectory is dropped, truncated or capped.
+ * qhea_noisy_device_lds_grad_max_workgroups: the launch cap (1024 / 512 / 256 at n = 10 / 11 / 12: what 256 compute units keep
+ * resident), 0 outside 10..12.
+ */
+/* DEVICE scratch bytes for the two calls on (at most) `batch` rows (0 on a bad descriptor or sampling record, shots != 0, or n
+ * outside 10..12). */
+size_t qhea_model_noisy_device_lds_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling);
+int    qhea_noisy_device_lds_grad_max_workgroups(int n);
+int    qhea_model_loss_grad_noisy_device_lds(const qhea_model_desc* desc, int64_t row0, int64_t batch,
+                                             const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                             const double* params, const double* ham_diag,
+                                             const qhea_device_noise* dn /*HOST*/, const qhea_sampling* sampling /*HOST: shots = 0*/,
+                                             double inv_batch_total, double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                             void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_device_lds(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                               const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                               const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                               const double* ham_diag, const qhea_device_noise* dn /*HOST*/,
+                                               const qhea_sampling* sampling /*HOST*/,
+                                               const double* inv_batch_total /*HOST [n_steps]*/,
+                                               double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                               double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                               double beta2, double eps, double weight_decay, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+
+/*
  * qhea_model_forward over `n_chunks` consecutive row ranges [row_begin[i], row_begin[i+1]) of the same arrays with the
  * SAME parameters -- the chunk loop of PTSolver.evaluate / infer.predict (solvers/solver_pt.py:299-310, infer.py:274-289) in
  * one host call.  The layer records depend on the parameters alone, so one preparation launch serves all chunks of

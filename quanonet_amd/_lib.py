@@ -47,7 +47,9 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_noisy_wide_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_wide', 'qhea_model_train_steps_noisy_wide',
            'qhea_model_noisy_lds_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_lds', 'qhea_model_train_steps_noisy_lds',
            'qhea_device_noise_singular_site', 'qhea_model_noisy_device_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_device',
-           'qhea_model_train_steps_noisy_device']
+           'qhea_model_train_steps_noisy_device',
+           'qhea_model_noisy_device_lds_grad_workspace_bytes', 'qhea_noisy_device_lds_grad_max_workgroups',
+           'qhea_model_loss_grad_noisy_device_lds', 'qhea_model_train_steps_noisy_device_lds']
 
 
 class ModelDesc(ctypes.Structure):
@@ -84,7 +86,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 600           # 0.6.0: + qhea_model_loss_grad_noisy_device / ..._train_steps_noisy_device (quantum-jump trajectory gradients, n = 7..9)
+MIN_LIB_VERSION = 610           # 0.6.1: + qhea_model_loss_grad_noisy_device_lds / ..._train_steps_noisy_device_lds (quantum-jump trajectory gradients, n = 10..12)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -286,10 +288,18 @@ def load():
     lib.qhea_model_loss_grad_noisy_device.restype = ctypes.c_int
     lib.qhea_model_loss_grad_noisy_device.argtypes = [mdp, ctypes.c_int64, ctypes.c_int64, dp, dp, dp, dp, dp, dnp, spp, ctypes.c_double,
                                                       dp, dp, vp, ctypes.c_size_t, vp]
+    lib.qhea_model_noisy_device_lds_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_noisy_device_lds_grad_workspace_bytes.argtypes = lib.qhea_model_noisy_device_workspace_bytes.argtypes
+    lib.qhea_noisy_device_lds_grad_max_workgroups.restype = ctypes.c_int
+    lib.qhea_noisy_device_lds_grad_max_workgroups.argtypes = [ctypes.c_int]
     lib.qhea_model_train_steps_noisy_device.restype = ctypes.c_int
     lib.qhea_model_train_steps_noisy_device.argtypes = [mdp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), dp, dp, dp, dp, dp, dnp,
                                                         spp, ctypes.POINTER(ctypes.c_double), dp, ctypes.c_int64, dp, dp,
                                                         ctypes.c_int64] + [ctypes.c_double] * 5 + [vp, ctypes.c_size_t, vp]
+    lib.qhea_model_loss_grad_noisy_device_lds.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_device_lds.argtypes = lib.qhea_model_loss_grad_noisy_device.argtypes
+    lib.qhea_model_train_steps_noisy_device_lds.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_device_lds.argtypes = lib.qhea_model_train_steps_noisy_device.argtypes
     _lib = lib
     return lib
 
@@ -1137,9 +1147,24 @@ def device_noise_singular_site(n, noise):
     return (SITE_NAMES[site.value], wire.value) if rc == 1 else None
 
 
+def model_noisy_device_lds_grad_workspace_bytes(desc, batch, sampling):
+    """qhea_model_noisy_device_lds_grad_workspace_bytes: 0 for a bad descriptor or sampling record (shot mode included) or n outside
+    10..12."""
+    return int(load().qhea_model_noisy_device_lds_grad_workspace_bytes(ctypes.byref(desc), int(batch), ctypes.byref(sampling)))
+
+
+def noisy_device_lds_grad_max_workgroups(n):
+    """qhea_noisy_device_lds_grad_max_workgroups: the workgroups one launch of the n = 10..12 quantum-jump gradient kernel has at
+    most (more (row, tile) items go round its grid-stride loop); 0 outside 10..12."""
+    return int(load().qhea_noisy_device_lds_grad_max_workgroups(int(n)))
+
+
 def _check_device_sampled(rc, who, desc, noise):
     if rc == -2:
-        raise Unsupported(f"{who}: n outside 7..9 (n <= 6: the exact calls under a device noise model; n >= 10: not built)")
+        if who.endswith('_lds'):
+            raise Unsupported(f"{who}: n outside 10..12 (n <= 6: the exact calls under a device noise model; n = 7..9: "
+                              f"{who[:-4]})")
+        raise Unsupported(f"{who}: n outside 7..9 (n <= 6: the exact calls under a device noise model; n >= 10: {who}_lds)")
     if rc == -1:
         hit = None
         try:
@@ -1162,8 +1187,22 @@ def model_loss_grad_noisy_device(desc, branch, trunk, y, params, noise, sampling
     fired pattern fixed, over the final norm); returns grad.  Raises Unsupported for n outside 7..9 and QheaError for a bad
     setting (shots != 0 and a site with gamma = 1 included), in both cases before anything is launched.
     """
+    return _loss_grad_noisy_device('', desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0, ham_diag, pred)
+
+
+def model_loss_grad_noisy_device_lds(desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0=0, ham_diag=None,
+                                     pred=None):
+    """model_loss_grad_noisy_device for n = 10..12 (qhea_model_loss_grad_noisy_device_lds: the same quantity, estimator and
+    random stream with psi and lambda in LDS; pred is what model_forward_noisy_device_wide returns).  Same errors, with the
+    qubit range 10..12."""
+    return _loss_grad_noisy_device('_lds', desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0, ham_diag,
+                                   pred)
+
+
+def _loss_grad_noisy_device(unit, desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0, ham_diag, pred):
     lib = load()
-    entry = 'qhea_model_loss_grad_noisy_device'
+    entry = 'qhea_model_loss_grad_noisy_device' + unit
+    sizer = getattr(lib, f'qhea_model_noisy_device{unit}_grad_workspace_bytes')
     B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(y, 'y')
     if y.numel() != B:
@@ -1172,9 +1211,9 @@ def model_loss_grad_noisy_device(desc, branch, trunk, y, params, noise, sampling
     if grad.numel() < params.numel() + 2:
         raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
     _dev_f64(pred, 'pred', (B,))
-    ws = _sized_ws(branch.device, lib.qhea_model_noisy_device_grad_workspace_bytes, ctypes.byref(desc), int(B), ctypes.byref(sampling))
+    ws = _sized_ws(branch.device, sizer, ctypes.byref(desc), int(B), ctypes.byref(sampling))
     with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_loss_grad_noisy_device(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+        rc = getattr(lib, entry)(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
                                                    _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling),
                                                    float(inv_batch_total), _ptr(grad), _ptr(pred), _ptr(ws),
                                                    0 if ws is None else ws.numel(), _stream(branch.device))
@@ -1190,16 +1229,30 @@ def model_train_steps_noisy_device(desc, bounds, global_batches, branch, trunk, 
     first_step + i, leaves [grads | sse | sum y^2] in rows[i] and applies Adam update first_step + i.  Bitwise a loop of
     model_loss_grad_noisy_device (that seed, row0 = bounds[i]) + adam_step.
     """
+    return _train_steps_noisy_device('', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                     first_step, lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag)
+
+
+def model_train_steps_noisy_device_lds(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                       first_step, lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag=None):
+    """model_train_steps_noisy_device for n = 10..12 (qhea_model_train_steps_noisy_device_lds).  Bitwise a loop of
+    model_loss_grad_noisy_device_lds (seed sampling.seed + first_step + i, row0 = bounds[i]) + adam_step."""
+    return _train_steps_noisy_device('_lds', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                     first_step, lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag)
+
+
+def _train_steps_noisy_device(unit, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
+                              lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag):
     lib = load()
-    entry = 'qhea_model_train_steps_noisy_device'
+    entry = 'qhea_model_train_steps_noisy_device' + unit
+    sizer = getattr(lib, f'qhea_model_noisy_device{unit}_grad_workspace_bytes')
     if len(bounds) - 1 <= 0:
         return rows
     n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
                                                     exp_avg, exp_avg_sq, ham_diag)
-    ws = _sized_ws(branch.device, lib.qhea_model_noisy_device_grad_workspace_bytes, ctypes.byref(desc), int(biggest),
-                   ctypes.byref(sampling))
+    ws = _sized_ws(branch.device, sizer, ctypes.byref(desc), int(biggest), ctypes.byref(sampling))
     with torch.cuda.device(branch.device):
-        rc = lib.qhea_model_train_steps_noisy_device(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
+        rc = getattr(lib, entry)(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
                                                      _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling), ib, _ptr(rows),
                                                      int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
                                                      float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),

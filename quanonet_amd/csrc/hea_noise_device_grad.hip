@@ -29,12 +29,13 @@
 // Records, fold and reduce are hea_noise_grad.hip's and hea_density_grad.hip's, unchanged; the tables kernel's body is
 // hea_noise_jump.hpp's.  The forward pieces below (site_draws, the relaxation of a site, the rescale) restate
 // hea_noise_device.hip's, which keeps its own text: its device code is pinned (profiles/r31_device_code_identity.txt).
+// The fenced read of 1 / sqrt(1 - gamma), the checks that open the calls and the workspace query are hea_noise_jump_grad.hpp's,
+// shared with the LDS form of this unit (hea_noise_device_grad_lds.hip, n = 10..12).
 #include <climits>
 #include <cmath>
 #include <cstdint>
 
-#include "hea_noise_jump.hpp"
-#include "hea_noise_grad.hpp"
+#include "hea_noise_jump_grad.hpp"
 
 namespace qhea {
 namespace {
@@ -62,12 +63,6 @@ struct DevGradArgs {
 };
 
 // ---- device helpers -------------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ double site_inv(const DevGradTable* __restrict__ tab, int site, int q) {
-    int fence = 0;
-    asm volatile("" : "+s"(fence));
-    return (&tab->inv[site][q])[fence];
-}
 
 template <bool RING>
 __device__ __forceinline__ void site_draws(const NoiseArgs& a, const DevGradTable* __restrict__ tab, unsigned call0, int tbase,
@@ -540,26 +535,6 @@ inline DevGradLayout device_grad_layout(const ModelInfo& mi, int64_t B, int64_t 
     return L;
 }
 
-// the checks of qhea_model_forward_noisy_device in its order, shots != 0 refused with the sampling record, then the site that
-// cannot be walked back (1 - gamma == 0)
-inline int device_grad_check(const qhea_model_desc* desc, const double* ham_diag, const qhea_device_noise* dn,
-                             const qhea_sampling* sampling, int64_t row0, int64_t count, const double* trunk,
-                             std::initializer_list<const void*> required, void* workspace, void* stream, NoisyCall& c, qhea_noise& nz) {
-    ModelInfo probe;
-    int rc = model_info(desc, probe);
-    if (rc != QHEA_OK) return rc;
-    rc = device_noise_check(probe.n, dn);
-    if (rc != QHEA_OK) return rc;
-    if (!sampling || sampling->shots != 0) return QHEA_EINVAL;
-    nz = sampling_as_noise(sampling);
-    rc = noisy_call_check({kDevGradUnit.nmin, kDevGradUnit.nmax, true, false}, desc, ham_diag, &nz, row0, count, trunk, required,
-                          workspace, stream, c);
-    if (rc != QHEA_OK) return rc;
-    int site, wire;
-    if (qhea_device_noise_singular_site(probe.n, dn, &site, &wire) == 1) return QHEA_EINVAL;
-    return QHEA_OK;
-}
-
 struct DevGradCall {
     const qhea_model_desc* desc; const ModelInfo& mi;
     DevGradLayout L;
@@ -576,8 +551,7 @@ inline int device_grad_open(const NoisyCall& c, int64_t bmax, const qhea_device_
     const int n = c.mi.n;
     w.tb = DevGradTable{};
     fill_jump_table(n, dn, w.tb, w.any);
-    for (int site = 0; site < 4; ++site)
-        for (int q = 0; q < n; ++q) w.tb.inv[site][q] = 1.0 / w.tb.gs[site][q][1];
+    fill_site_inv(n, w.tb.gs, w.tb.inv);
     w.tb.off = w.desc->ham_offset; w.tb.co = w.desc->ham_coeff; w.tb.diag = w.ham_diag;
     w.tb.L = jump_calls(n, c.mi.nb, c.mi.ld); w.tb.pauli = (unsigned)w.desc->ham_pauli;
     double* mix = reinterpret_cast<double*>(c.ws + w.L.w.off_mix);
@@ -644,12 +618,7 @@ int qhea_device_noise_singular_site(int n, const qhea_device_noise* dn, int* sit
 }
 
 size_t qhea_model_noisy_device_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling) {
-    if (!sampling || sampling->shots != 0) return 0;
-    const qhea_noise nz = sampling_as_noise(sampling);
-    ModelInfo mi;
-    const int64_t T = noise_values(&nz);
-    if (T < 1 || batch < 0 || model_info(desc, mi) != QHEA_OK || mi.n < kDevGradUnit.nmin || mi.n > kDevGradUnit.nmax) return 0;
-    return device_grad_layout(mi, batch, T).total;
+    return device_grad_workspace_bytes(kDevGradUnit, device_grad_layout, desc, batch, sampling);
 }
 
 int qhea_model_loss_grad_noisy_device(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
@@ -658,7 +627,7 @@ int qhea_model_loss_grad_noisy_device(const qhea_model_desc* desc, int64_t row0,
                                       double* grad, double* pred, void* workspace, size_t workspace_bytes, void* stream) {
     NoisyCall c;
     qhea_noise nz{};
-    int rc = device_grad_check(desc, ham_diag, dn, sampling, row0, batch, trunk, {branch, y, params, grad}, workspace, stream, c, nz);
+    int rc = device_grad_check(kDevGradUnit, desc, ham_diag, dn, sampling, row0, batch, trunk, {branch, y, params, grad}, workspace, stream, c, nz);
     if (rc != QHEA_OK || c.empty) return rc;
     DevGradCall w{desc, c.mi, {}, ham_diag, nullptr, {}, false, c.ws, c.st};
     rc = device_grad_open(c, batch, dn, workspace_bytes, w);
@@ -677,7 +646,7 @@ int qhea_model_train_steps_noisy_device(const qhea_model_desc* desc, int64_t n_s
     if (!desc || n_steps < 0 || first_step < 1) return QHEA_EINVAL;
     NoisyCall c;
     qhea_noise nz{};
-    int rc = device_grad_check(desc, ham_diag, dn, sampling, 0, n_steps, trunk,
+    int rc = device_grad_check(kDevGradUnit, desc, ham_diag, dn, sampling, 0, n_steps, trunk,
                                {row_begin, inv_batch_total, branch, y, grad, params, exp_avg, exp_avg_sq}, workspace, stream, c, nz);
     if (rc != QHEA_OK || c.empty) return rc;
     const int64_t bmax = call_max_batch(call, c.mi.P, *desc);

@@ -110,6 +110,9 @@ class EnsembleSolver:
         if any(c.get('train_trajectories') is not None for c in self.configs):
             raise ValueError(f"{type(self).__name__}: config key train_trajectories is not supported in member launches "
                              "(sampled-trajectory training runs one model per PTSolver)")
+        if any(c.get('train_jump_trajectories') is not None for c in self.configs):
+            raise ValueError(f"{type(self).__name__}: config key train_jump_trajectories is not supported in member launches "
+                             "(quantum-jump training runs one model per PTSolver)")
         self.log = log
         self.members = []
         for c, d in zip(self.configs, data_dicts):

@@ -524,9 +524,13 @@ def device_sampled_loss_and_grad(model, inputs, y, device_noise, sampling, inv_b
         raise ValueError(f"device_sampled_loss_and_grad covers n = 7..9 (got n = {n}); device_noisy_loss_and_grad is the exact "
                          "call for n <= 6")
     if n >= 10:
-        raise ValueError(f"device_sampled_loss_and_grad covers n = 7..9 (got n = {n}); device_noisy_predict evaluates n = 10..12, "
-                         "no gradient is built there")
-    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'device_sampled_loss_and_grad')
+        raise ValueError(f"device_sampled_loss_and_grad covers n = 7..9 (got n = {n}); device_trajectory_loss_and_grad is the "
+                         "same call for n = 7..12")
+    return _device_trajectory_call('device_sampled_loss_and_grad', model, inputs, y, device_noise, sampling, inv_batch_total, row0)
+
+
+def _device_trajectory_call(who, model, inputs, y, device_noise, sampling, inv_batch_total, row0):
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, who)
     B = branch.shape[0]
     y = y.detach().to(torch.float64).reshape(-1).contiguous()
     grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
@@ -534,6 +538,31 @@ def device_sampled_loss_and_grad(model, inputs, y, device_noise, sampling, inv_b
     if B == 0:
         return grad, pred
     inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
-    _lib.model_loss_grad_noisy_device(desc, branch, trunk, y, flat, device_noise.params(desc.n_qubits), sampling.params(), inv,
-                                      grad, row0=int(row0), ham_diag=ham_diag, pred=pred)
+    call = _lib.model_loss_grad_noisy_device if desc.n_qubits <= 9 else _lib.model_loss_grad_noisy_device_lds
+    call(desc, branch, trunk, y, flat, device_noise.params(desc.n_qubits), sampling.params(), inv, grad, row0=int(row0),
+         ham_diag=ham_diag, pred=pred)
     return grad, pred
+
+
+def device_trajectory_loss_and_grad(model, inputs, y, device_noise, sampling, inv_batch_total=None, row0=0):
+    """
+    device_sampled_loss_and_grad for every n a quantum-jump gradient exists for, n = 7..12: the MSE loss of the quantum-jump
+    estimate under a DeviceNoise and the unbiased gradient of it (the same estimator and random stream at every n).  At
+    n = 7..9 it is device_sampled_loss_and_grad, bitwise (qhea_model_loss_grad_noisy_device); at n = 10..12 psi and lambda live
+    in LDS (qhea_model_loss_grad_noisy_device_lds) and pred is what device_noisy_predict returns there.  For n <= 6
+    device_noisy_loss_and_grad is the exact call.
+    """
+    _device_noise(device_noise, 'device_trajectory_loss_and_grad')
+    if not isinstance(sampling, Sampling):
+        raise ValueError(f"device_trajectory_loss_and_grad takes a Sampling (got {type(sampling).__name__})")
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("device_trajectory_loss_and_grad takes a QuanONetPT or HEAQNNPT model")
+    if sampling.shots != 0:
+        raise ValueError("device_trajectory_loss_and_grad differentiates expectation mode (Sampling.shots = 0, trajectories = T); "
+                         "a sampled bitstring has no gradient")
+    n = int(model.fused_desc().n_qubits)
+    if n <= 6:
+        raise ValueError(f"device_trajectory_loss_and_grad covers n = 7..12 (got n = {n}); device_noisy_loss_and_grad is the "
+                         "exact call for n <= 6")
+    return _device_trajectory_call('device_trajectory_loss_and_grad', model, inputs, y, device_noise, sampling, inv_batch_total,
+                                   row0)

@@ -343,18 +343,31 @@ class DataParallelTrainer:
 
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
                  fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None,
-                 train_sampling=None, train_trajectories=None):
+                 train_sampling=None, train_trajectories=None, train_jump_trajectories=None):
         self.model = model
         self.train_noise = _train_noise(train_noise)
         self.train_device_noise = _train_device_noise(train_device_noise, train_noise)
+        # train_jump_trajectories beside train_device_noise: what train_trajectories means there, for every n a quantum-jump
+        # gradient exists for (7..12); train_trajectories there keeps the range it was introduced with (7..9)
+        if train_jump_trajectories is not None:
+            if train_trajectories is not None or train_sampling is not None:
+                other = 'train_trajectories' if train_trajectories is not None else 'train_sampling'
+                raise ValueError(f"train_jump_trajectories and {other} are both set: set one of them (beside train_device_noise "
+                                 "train_jump_trajectories covers n = 7..12, train_trajectories n = 7..9)")
+            if self.train_device_noise is None:
+                raise ValueError("train_jump_trajectories needs train_device_noise: it says how the DeviceNoise of "
+                                 "train_device_noise is sampled (quantum-jump trajectories, n = 7..12); train_trajectories is "
+                                 "the key beside train_noise")
         # Two keys, one meaning: train_sampling keeps the range it was introduced with (n = 7..9, and its refusal beyond),
         # train_trajectories is the same request for every n a sampled gradient exists for (7..12).  self.train_sampling is the
         # Sampling in force under either key, self.sampling_key the key it came by.
         if train_sampling is not None and train_trajectories is not None:
             raise ValueError("train_sampling and train_trajectories say the same thing: set one of them (train_trajectories "
                              "covers n = 7..12, train_sampling n = 7..9)")
-        self.sampling_key = key = 'train_sampling' if train_trajectories is None else 'train_trajectories'
-        self.train_sampling = _train_sampling(train_sampling if train_trajectories is None else train_trajectories, key)
+        self.sampling_key = key = ('train_jump_trajectories' if train_jump_trajectories is not None else
+                                   'train_sampling' if train_trajectories is None else 'train_trajectories')
+        self.train_sampling = _train_sampling(train_jump_trajectories if train_jump_trajectories is not None else
+                                              train_sampling if train_trajectories is None else train_trajectories, key)
         if self.train_sampling is not None:
             # sampled-trajectory training (qhea_model_train_steps_noisy_wide / _lds): what it cannot combine with
             # ... or quantum-jump training under a device model (qhea_model_train_steps_noisy_device): train_trajectories beside
@@ -362,7 +375,7 @@ class DataParallelTrainer:
             if self.train_device_noise is not None and key == 'train_sampling':
                 raise ValueError("train_sampling does not combine with train_device_noise: train_trajectories is the key that "
                                  "says how the DeviceNoise of train_device_noise is sampled (quantum-jump trajectories, "
-                                 "n = 7..9)")
+                                 "n = 7..9; train_jump_trajectories: n = 7..12)")
             if self.train_device_noise is None and self.train_noise is None:
                 raise ValueError(f"{key} needs train_noise: it says how the NoiseModel of train_noise is sampled")
             if self.train_sampling.shots > 0:
@@ -427,34 +440,39 @@ class DataParallelTrainer:
                 self.peer_fused = self.peer is not None and self.desc is not None
         self.device_sampled = self.train_sampling is not None and self.train_device_noise is not None
         if self.device_sampled:
-            # the loss is the quantum-jump estimate under the device model (qhea_model_loss_grad_noisy_device)
+            # the loss is the quantum-jump estimate under the device model (qhea_model_loss_grad_noisy_device at n = 7..9,
+            # ..._noisy_device_lds at n = 10..12)
+            key, nmax = self.sampling_key, 12 if self.sampling_key == 'train_jump_trajectories' else 9
             if self.desc is None or not isinstance(self.optimizer, FlatAdam):
-                raise ValueError("train_device_noise with train_trajectories needs the fused model-level path (a fp64 QuanONetPT "
+                raise ValueError(f"train_device_noise with {key} needs the fused model-level path (a fp64 QuanONetPT "
                                  "/ HEAQNNPT on a HIP device, Adam with betas / eps / weight_decay only)")
             from . import _lib
             n = self.desc.n_qubits
             if n <= 6:
-                raise ValueError(f"train_device_noise with train_trajectories: quantum-jump training takes n = 7..9 (this model: "
+                raise ValueError(f"train_device_noise with {key}: quantum-jump training takes n = 7..{nmax} (this model: "
                                  f"n = {n}); for n <= 6 train_device_noise alone trains on the exact loss under the device model")
-            if n >= 10:
-                raise ValueError(f"train_device_noise with train_trajectories: quantum-jump training takes n = 7..9 (this model: "
-                                 f"n = {n}); at n = 10..12 a DeviceNoise can be evaluated (device_noisy_predict), and train_noise "
-                                 "with train_trajectories trains under uniform gate noise")
+            if n > nmax:
+                raise ValueError(f"train_device_noise with {key}: quantum-jump training takes n = 7..9 under this key (this "
+                                 f"model: n = {n}); train_jump_trajectories is the key that trains n = 7..12 on quantum-jump "
+                                 "trajectories under the DeviceNoise")
             try:
                 hit = _lib.device_noise_singular_site(n, self.train_device_noise.params(n))
             except _lib.QheaError as e:
                 raise ValueError(f"train_device_noise: {e}") from e
             if hit:
-                raise ValueError(f"train_device_noise with train_trajectories: relaxation site {hit[0]} on wire {hit[1]} has "
+                raise ValueError(f"train_device_noise with {key}: relaxation site {hit[0]} on wire {hit[1]} has "
                                  "gamma = 1, which the trajectory gradient cannot walk back")
+            # the pair of calls for this qubit count: the wave-resident kernel at n = 7..9, the LDS-resident one at n = 10..12
+            call_loss_grad, call_steps = ((_lib.model_loss_grad_noisy_device, _lib.model_train_steps_noisy_device) if n <= 9 else
+                                          (_lib.model_loss_grad_noisy_device_lds, _lib.model_train_steps_noisy_device_lds))
 
             def loss_grad(desc, branch, trunk, y, params, sampling, inv, grad, row0=0, ham_diag=None):
-                return _lib.model_loss_grad_noisy_device(desc, branch, trunk, y, params, self.train_device_noise.params(n),
-                                                         sampling, inv, grad, row0=row0, ham_diag=ham_diag)
+                return call_loss_grad(desc, branch, trunk, y, params, self.train_device_noise.params(n), sampling, inv, grad,
+                                      row0=row0, ham_diag=ham_diag)
 
             def steps(*call, ham_diag=None):
                 *head, sampling = call
-                return _lib.model_train_steps_noisy_device(*head, self.train_device_noise.params(n), sampling, ham_diag=ham_diag)
+                return call_steps(*head, self.train_device_noise.params(n), sampling, ham_diag=ham_diag)
 
             self._sampled_loss_grad, self._sampled_steps = loss_grad, steps
             if log is not None:
@@ -514,7 +532,8 @@ class DataParallelTrainer:
                 raise ValueError(f"train_device_noise: the library refuses this model under this DeviceNoise (n = {n}, log10 "
                                  f"amplification {amp:.2f}): n <= 6 and a log10 amplification within the bound of "
                                  "include/quanonet_hea.h are needed; see quanonet_amd.noise.device_amplification.  At "
-                                 "n = 7..9 train_trajectories beside train_device_noise trains on quantum-jump trajectories")
+                                 "n = 7..9 train_trajectories beside train_device_noise trains on quantum-jump trajectories, "
+                                 "and train_jump_trajectories there does at n = 7..12")
             if self.peer_fused:
                 self.peer_fused = False
                 self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
@@ -843,7 +862,8 @@ class PTSolver:
                                            log=self.log, train_noise=config.get('train_noise'),
                                            train_device_noise=config.get('train_device_noise'),
                                            train_sampling=config.get('train_sampling'),
-                                           train_trajectories=config.get('train_trajectories'))
+                                           train_trajectories=config.get('train_trajectories'),
+                                           train_jump_trajectories=config.get('train_jump_trajectories'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None
