@@ -669,6 +669,52 @@ int    qhea_model_train_steps_noisy_device_exact(const qhea_model_desc* desc, in
                                                  size_t workspace_bytes, void* stream);
 
 /*
+ * The same two calls past the guard: rho replayed from stored states (library version 620).
+ *
+ * qhea_model_loss_grad_noisy_device_exact_stored / qhea_model_train_steps_noisy_device_exact_stored compute what the two calls
+ * above compute -- same arguments, same [P+2] buffer, same status codes in the same order -- for settings whose log10 A_dev is
+ * past 7.  Call one sub-layer a unit (a block's first sub-layer carries the block's encoding gates; a block without sub-layers
+ * is one encoding-only unit), U = sub-layers + blocks without sub-layers.  The forward sweep of the backward kernel writes the
+ * row's rho after unit u to snap[u][row] in the workspace (16 * 4^n bytes, fp64 complex, not compressed); the reverse walk
+ * replaces rho by the stored rho_u before it undoes unit u.  Within a unit nothing differs from the walk above: rho through
+ * the inverse sites and un-rotations, O through the adjoints, the traces where they are.  So rho never carries more than one
+ * unit's worth of inverse walk, and the guard is asked of one unit:
+ *     qhea_model_device_noisy_log10_layer_amplification (host only) = log10 A_dev of the largest single unit: one sub-layer's
+ *     ROT, CTL and TGT sites and CNOT slots, plus the ENC sites once if the circuit has encoding layers; the ENC sites alone
+ *     for a circuit without sub-layers.  NaN and +inf exactly where qhea_model_device_noisy_log10_amplification returns them;
+ *     never above it, and equal to it for a circuit of one unit.
+ * The calls refuse -- QHEA_EUNSUPPORTED, before anything is launched, outputs untouched, at the place in the order where the
+ * calls above refuse -- n >= 7, a singular channel (+inf), and a layer amplification above 7: the bound above was measured for
+ * the inverse walk of a whole circuit, and one unit is such a circuit.  The total log10 A_dev is no reason to refuse.
+ * Workspace: qhea_model_device_noisy_stored_grad_workspace_bytes = qhea_model_device_noisy_grad_workspace_bytes plus the
+ * snapshot region behind it, U * batch * 16 * 4^n bytes rounded up to 256 (it passes 4 GiB at sizes people run: Q6 with 20
+ * units at 3300 rows; every index is 64-bit).
+ * Launches: those of the calls above with density_dev_stored_bwd_kernel in place of density_dev_bwd_kernel; the snapshot of a
+ * unit is the row's image in LDS, stored and loaded by the same thread with 16-byte vector accesses (the load is issued one
+ * unit ahead and waits in registers), a tail slot of the last workgroup stores and loads none.  No allocation, no synchronisation, no atomics, fixed summation orders: bitwise reproducible,
+ * a row's pred and record independent of batch and grid; pred is the same sweep's as above (it agrees to 1e-13).
+ * qhea_model_train_steps_noisy_device_exact_stored is bitwise a loop of the loss_grad call + qhea_adam_step.
+ */
+size_t qhea_model_device_noisy_stored_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+double qhea_model_device_noisy_log10_layer_amplification(const qhea_model_desc* desc, const qhea_device_noise* dn /*HOST*/);
+int    qhea_model_loss_grad_noisy_device_exact_stored(const qhea_model_desc* desc, int64_t batch,
+                                                      const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                                      const double* params, const double* ham_diag,
+                                                      const qhea_device_noise* dn /*HOST*/, double inv_batch_total,
+                                                      double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                                      void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_device_exact_stored(const qhea_model_desc* desc, int64_t n_steps,
+                                                        const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                                        const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                                        const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                                        const double* ham_diag, const qhea_device_noise* dn /*HOST*/,
+                                                        const double* inv_batch_total /*HOST [n_steps]*/,
+                                                        double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                                        double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr,
+                                                        double beta1, double beta2, double eps, double weight_decay,
+                                                        void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Noisy forward under the calibrated device noise model by quantum-jump (Monte-Carlo wave-function) trajectories: an unbiased
  * estimate of pred of qhea_model_forward_noisy_device_exact, for the qubit counts that call cannot reach (n = 7..9) and for
  * finite shots at any n = 2..9 -- what an Estimator with default_shots = S returns on that device.  Arguments, estimators and

@@ -49,7 +49,9 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_device_noise_singular_site', 'qhea_model_noisy_device_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_device',
            'qhea_model_train_steps_noisy_device',
            'qhea_model_noisy_device_lds_grad_workspace_bytes', 'qhea_noisy_device_lds_grad_max_workgroups',
-           'qhea_model_loss_grad_noisy_device_lds', 'qhea_model_train_steps_noisy_device_lds']
+           'qhea_model_loss_grad_noisy_device_lds', 'qhea_model_train_steps_noisy_device_lds',
+           'qhea_model_device_noisy_stored_grad_workspace_bytes', 'qhea_model_device_noisy_log10_layer_amplification',
+           'qhea_model_loss_grad_noisy_device_exact_stored', 'qhea_model_train_steps_noisy_device_exact_stored']
 
 
 class ModelDesc(ctypes.Structure):
@@ -86,7 +88,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 610           # 0.6.1: + qhea_model_loss_grad_noisy_device_lds / ..._train_steps_noisy_device_lds (quantum-jump trajectory gradients, n = 10..12)
+MIN_LIB_VERSION = 620           # 0.6.2: + qhea_model_loss_grad_noisy_device_exact_stored / ..._train_steps_..._stored (device-noise training past the guard: rho from stored states)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -278,9 +280,17 @@ def load():
     lib.qhea_model_device_noisy_log10_amplification.argtypes = [mdp, dnp]
     lib.qhea_model_loss_grad_noisy_device_exact.restype = ctypes.c_int
     lib.qhea_model_loss_grad_noisy_device_exact.argtypes = [dnp if t is npp else t for t in lib.qhea_model_loss_grad_noisy_exact.argtypes]
+    lib.qhea_model_device_noisy_stored_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_device_noisy_stored_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
+    lib.qhea_model_device_noisy_log10_layer_amplification.restype = ctypes.c_double
+    lib.qhea_model_device_noisy_log10_layer_amplification.argtypes = [mdp, dnp]
+    lib.qhea_model_loss_grad_noisy_device_exact_stored.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_device_exact_stored.argtypes = lib.qhea_model_loss_grad_noisy_device_exact.argtypes
     lib.qhea_model_train_steps_noisy_device_exact.restype = ctypes.c_int
     lib.qhea_model_train_steps_noisy_device_exact.argtypes = [dnp if t is npp else t
                                                               for t in lib.qhea_model_train_steps_noisy_exact.argtypes]
+    lib.qhea_model_train_steps_noisy_device_exact_stored.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_device_exact_stored.argtypes = lib.qhea_model_train_steps_noisy_device_exact.argtypes
     lib.qhea_device_noise_singular_site.restype = ctypes.c_int
     lib.qhea_device_noise_singular_site.argtypes = [ctypes.c_int, dnp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.qhea_model_noisy_device_grad_workspace_bytes.restype = ctypes.c_size_t
@@ -958,9 +968,15 @@ def model_exact_noisy_log10_amplification(desc, noise):
     return float(load().qhea_model_exact_noisy_log10_amplification(ctypes.byref(desc), ctypes.byref(noise)))
 
 
+# the exact gradient units by what `device_model` says: False the uniform NoiseParams, True a DeviceNoiseParams with rho walked
+# back through inverses, 'stored' a DeviceNoiseParams with rho replayed from stored states: (name in the entry points, sizing call)
+_NOISY_GRAD_UNITS = {False: ('noisy_exact', 'qhea_model_exact_noisy_grad_workspace_bytes'),
+                     True: ('noisy_device_exact', 'qhea_model_device_noisy_grad_workspace_bytes'),
+                     'stored': ('noisy_device_exact_stored', 'qhea_model_device_noisy_stored_grad_workspace_bytes')}
+
+
 def _noisy_grad_ws(lib, desc, B, device, device_model=False):
-    size_fn = lib.qhea_model_device_noisy_grad_workspace_bytes if device_model else lib.qhea_model_exact_noisy_grad_workspace_bytes
-    return _sized_ws(device, size_fn, ctypes.byref(desc), int(B))
+    return _sized_ws(device, getattr(lib, _NOISY_GRAD_UNITS[device_model][1]), ctypes.byref(desc), int(B))
 
 
 def _check_noisy_grad(rc, who):
@@ -972,9 +988,9 @@ def _check_noisy_grad(rc, who):
 
 def _loss_grad_noisy(device_model, desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred):
     """The two gradient entry points share one argument list: qhea_model_loss_grad_noisy_exact (`noise` a NoiseParams) and
-    ..._noisy_device_exact (a DeviceNoiseParams)."""
+    ..._noisy_device_exact and ..._noisy_device_exact_stored (a DeviceNoiseParams)."""
     lib = load()
-    entry = 'qhea_model_loss_grad_noisy_device_exact' if device_model else 'qhea_model_loss_grad_noisy_exact'
+    entry = 'qhea_model_loss_grad_' + _NOISY_GRAD_UNITS[device_model][0]
     B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(y, 'y')
     if y.numel() != B:
@@ -995,7 +1011,7 @@ def _loss_grad_noisy(device_model, desc, branch, trunk, y, params, noise, inv_ba
 def _train_steps_noisy(device_model, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
                        first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag):
     lib = load()
-    entry = 'qhea_model_train_steps_noisy_device_exact' if device_model else 'qhea_model_train_steps_noisy_exact'
+    entry = 'qhea_model_train_steps_' + _NOISY_GRAD_UNITS[device_model][0]
     if len(bounds) - 1 <= 0:
         return rows
     n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
@@ -1271,6 +1287,40 @@ def model_device_noisy_log10_amplification(desc, noise):
     return float(load().qhea_model_device_noisy_log10_amplification(ctypes.byref(desc), ctypes.byref(noise)))
 
 
+def model_device_noisy_log10_layer_amplification(desc, noise):
+    """
+    qhea_model_device_noisy_log10_layer_amplification (host only): log10 A_dev of the largest single unit of this shape under
+    `noise` (a DeviceNoiseParams) -- one sub-layer's sites and slots with the encoding sites -- which is what the stored-state
+    gradient calls are bounded by; inf and NaN where model_device_noisy_log10_amplification returns them.
+    """
+    return float(load().qhea_model_device_noisy_log10_layer_amplification(ctypes.byref(desc), ctypes.byref(noise)))
+
+
+def model_device_noisy_stored_grad_workspace_bytes(desc, batch, snapshots_only=False):
+    """qhea_model_device_noisy_stored_grad_workspace_bytes (host only): the inverse walk's workspace plus the snapshot region
+    (units x batch x 16 x 4^n bytes, rounded up to 256); snapshots_only: the region alone."""
+    lib = load()
+    total = int(lib.qhea_model_device_noisy_stored_grad_workspace_bytes(ctypes.byref(desc), int(batch)))
+    return total - int(lib.qhea_model_device_noisy_grad_workspace_bytes(ctypes.byref(desc), int(batch))) if snapshots_only else total
+
+
+def _device_noisy_refused(entry, desc, noise):
+    rc = getattr(load(), entry)(ctypes.byref(desc), 0, None, None, None, None, None, ctypes.byref(noise), 1.0, None, None, None, 0,
+                                None)
+    if rc == -2:
+        return True
+    _check(rc, entry)
+    return False
+
+
+def model_device_noisy_stored_refused(desc, noise):
+    """
+    model_device_noisy_refused for the stored-state calls (qhea_model_loss_grad_noisy_device_exact_stored): n >= 7, a singular
+    channel, or a layer amplification above the library's bound -- the total amplification is no reason.  Host only.
+    """
+    return _device_noisy_refused('qhea_model_loss_grad_noisy_device_exact_stored', desc, noise)
+
+
 def model_device_noisy_refused(desc, noise):
     """
     Whether the device-noise gradient calls refuse this model under `noise` (a DeviceNoiseParams) with QHEA_EUNSUPPORTED --
@@ -1278,12 +1328,7 @@ def model_device_noisy_refused(desc, noise):
     batch runs every check in front of the batch and launches nothing (host only, no device needed).  Raises QheaError for a
     setting the library refuses as invalid.
     """
-    rc = load().qhea_model_loss_grad_noisy_device_exact(ctypes.byref(desc), 0, None, None, None, None, None, ctypes.byref(noise),
-                                                        1.0, None, None, None, 0, None)
-    if rc == -2:
-        return True
-    _check(rc, 'qhea_model_loss_grad_noisy_device_exact')
-    return False
+    return _device_noisy_refused('qhea_model_loss_grad_noisy_device_exact', desc, noise)
 
 
 def model_loss_grad_noisy_device_exact(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None, pred=None):
@@ -1301,6 +1346,26 @@ def model_train_steps_noisy_device_exact(desc, bounds, global_batches, branch, t
     of model_loss_grad_noisy_device_exact + adam_step.
     """
     return _train_steps_noisy(True, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                              first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+
+
+def model_loss_grad_noisy_device_exact_stored(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None,
+                                              pred=None):
+    """
+    model_loss_grad_noisy_device_exact with rho replayed from stored states (qhea_model_loss_grad_noisy_device_exact_stored):
+    the same quantity for settings past that call's guard; Unsupported for n >= 7, a singular channel or a single unit whose
+    log10 A_dev is above the bound.  The workspace grows by units x rows x 16 x 4^n bytes.
+    """
+    return _loss_grad_noisy('stored', desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred)
+
+
+def model_train_steps_noisy_device_exact_stored(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                                first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag=None):
+    """
+    model_train_steps_noisy_device_exact with rho replayed from stored states
+    (qhea_model_train_steps_noisy_device_exact_stored).  Bitwise a loop of model_loss_grad_noisy_device_exact_stored + adam_step.
+    """
+    return _train_steps_noisy('stored', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
                               first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
 
 

@@ -21,6 +21,13 @@
 // copies them from its by-value argument into the workspace; the backward kernel reads a site's constants where it uses them,
 // from an address it forms behind a scalar zero the compiler cannot see through (so the loads stay inside their pass), and
 // moves them to scalar registers (the address is wave-uniform).
+//
+// Stored states.  The inverse walk amplifies the traceless part of rho by A_dev, so the calls above refuse log10 A_dev > 7.
+// qhea_model_loss_grad_noisy_device_exact_stored / ..._train_steps_..._stored run density_dev_stored_bwd_kernel<N>: the same
+// kernel, except that its forward sweep writes rho after every unit -- a sub-layer, or the encoding gates of a block without
+// sub-layers -- to the workspace and its reverse walk starts every unit from the stored state (fetched into registers one
+// unit ahead, so that the loads land while the unit in front is walked).  Within a unit nothing differs, so the guard is
+// asked of one unit only.
 #include <vector>
 
 #include "hea_density_grad.hpp"
@@ -54,6 +61,11 @@ struct DevGradArgs {
     double* pred;                           // the caller's pred or NULL
     double* pred_ws;                        // [B]
     double* rec;                            // [E + 3 n blk][B]: d pred_b / d x[b, e], then d pred_b / d w[s, k, q]
+};
+
+// ... of the stored-state kernel: the record above and where the forward sweep leaves rho after every unit
+struct DevStoredArgs : DevGradArgs {
+    double2* snap;                          // [U][B][4^n]: snap[u][row] = the row's rho after unit u, as its image in LDS
 };
 
 // A scalar zero the compiler cannot see through: a table address formed behind it belongs to the pass that forms it, so the
@@ -359,6 +371,168 @@ __global__ __launch_bounds__(bwd_threads<N>()) void density_dev_bwd_kernel(DevGr
     }
 }
 
+// ---- stored states ----
+// A unit is one sub-layer (a block's first carries its encoding) or the encoding gates of a block without sub-layers.  The row's
+// image in LDS is copied as it lies (fold and slot fold included: the thread that stored an element is the one that loads it),
+// element i by the row's thread i mod TPR: 16 bytes per lane, contiguous over the row's lanes.  A tail slot copies nothing.
+// Called by every thread of the workgroup behind a pass' closing barrier; the barrier inside closes the copy.
+template <int N>
+__device__ __forceinline__ void store_snapshot(const double2* row, int rank, bool live, double2* dst) {
+    constexpr int TPR = RowCtx<N>::TPR, NE = 1 << (2 * N);
+    if (live)
+        for (int i = rank; i < NE; i += TPR) dst[i] = row[i];
+    __syncthreads();
+}
+
+// The way back in two halves: a thread's 16 elements of a snapshot into registers (issued one unit ahead: the loads land
+// while the unit in front of them is walked), and from there into the row's rho.
+template <int N>
+__device__ __forceinline__ void fetch_snapshot(double2 (&pf)[16], int rank, bool live, const double2* src) {
+    constexpr int TPR = RowCtx<N>::TPR;
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) pf[k] = src[rank + k * TPR];
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void place_snapshot(double2* row, int rank, bool live, const double2 (&pf)[16]) {
+    constexpr int TPR = RowCtx<N>::TPR;
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) row[rank + k * TPR] = pf[k];
+    }
+    __syncthreads();
+}
+
+// density_dev_bwd_kernel with stored states: the forward sweep writes rho after every unit to a.snap and the reverse walk
+// starts every unit from the stored state, so rho carries one unit's worth of inverse walk at most.  The text between the
+// snapshot lines is that kernel's.  (As one body templated over `bool Stored` the inverse kernel's instantiations changed --
+// one more scalar spill at n = 2, 3, 4, 6, profiles/r33_resource_usage.txt -- so the two kernels share the device functions
+// above and nothing else.)
+template <int N>
+__global__ __launch_bounds__(bwd_threads<N>()) void density_dev_stored_bwd_kernel(DevStoredArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char dens_lds[];      // rho, O, h'[D], the waves' trace partials
+    using C = RowCtx<N>;
+    constexpr int TPR = C::TPR, RPW = bwd_threads<N>() / TPR, D = 1 << N, NE = 1 << (2 * N);
+    double2* state = reinterpret_cast<double2*>(dens_lds);
+    double* hv = reinterpret_cast<double*>(dens_lds + 2 * RPW * NE * sizeof(double2));
+    const int tid = threadIdx.x, slot = tid / TPR, rank = tid % TPR;
+    long r = (long)blockIdx.x * RPW + slot;
+    const bool live = r < a.B;
+    if (!live) r = a.B - 1;                                              // a tail slot repeats the last row and stores nothing
+    const double2* csr = a.cs + r * a.E;
+    C cx;
+    cx.rho = state + slot * NE;
+    cx.obs = state + RPW * NE + slot * NE;
+    cx.red = hv + D;
+    cx.rank = rank; cx.sf = slot_fold<N>(slot); cx.parity = 0;
+    cx.r = r; cx.B = a.B; cx.live = live;
+    double2* row = cx.rho;
+    const int sf = cx.sf;
+    const long ustride = a.B * (long)NE;
+    double2* snap = a.snap + r * (long)NE;                               // the row's snapshot of the unit the walk stands at
+    int units = 0;
+
+    // value table under the readout confusion: per bit, h'[k] = (1 - f) h[k] + f h[k ^ bit], f = P(the bit of k is misread)
+    double h = 0.0;
+    if (tid < D) h = a.diag ? a.diag[tid] : a.off + a.co * (double)(N - 2 * (int)__popc(tid));
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (tid < D) hv[tid] = h;
+        __syncthreads();
+        if (tid < D) {
+            const double f = a.tab[i * kTabWire + kTabRead + ((tid >> i) & 1)];
+            h = (1.0 - f) * h + f * hv[tid ^ (1 << i)];
+        }
+        __syncthreads();
+    }
+    if (tid < D) hv[tid] = h;
+
+    // forward sweep: the passes of density_dev_fwd_kernel
+    int s = 0, col = 0;
+    bool first = true;
+    for (int g = 0; g < 2; ++g) {
+        for (int b = 0; b < a.nb[g]; ++b) {
+            if (a.ld[g] == 0) {
+                dev_enc_passes<N, 0>(row, rank, sf, a, csr, col, first);
+                first = false;
+                store_snapshot<N>(row, rank, live, snap); snap += ustride; ++units;
+            }
+            for (int l = 0; l < a.ld[g]; ++l, ++s) {
+                dev_ring_passes<N, 0>(row, rank, sf, a, csr, s, col, l == 0, first);
+                first = false;
+                store_snapshot<N>(row, rank, live, snap); snap += ustride; ++units;
+            }
+            col += N;
+        }
+    }
+    if (first) {                                                         // no block at all: rho = |0><0|
+        for (int i = rank; i < NE; i += TPR) row[i] = make_double2(0.0, 0.0);
+        __syncthreads();
+        if (rank == 0) row[fold(0) ^ sf] = make_double2(1.0, 0.0);
+        __syncthreads();
+    }
+    const DensArgs none{};                                               // the basis-change passes read nothing of it
+    if (a.pauli == QHEA_PAULI_X) wire_passes<N, 0, 1>(row, rank, sf, none, csr, 0, false);
+    else if (a.pauli == QHEA_PAULI_Y) wire_passes<N, 0, 2>(row, rank, sf, none, csr, 0, false);
+
+    if (rank == 0 && live) {
+        double m1 = 0.0;
+        for (int k = 0; k < D; ++k) {
+            int i = 0;
+#pragma unroll
+            for (int w = 0; w < N; ++w) i |= ((k >> w) & 1) * (3 << (2 * w));
+            m1 += row[i ^ fold(i) ^ sf].x * hv[k];
+        }
+        const double p = m1 + (a.bias ? a.bias[0] : 0.0);
+        a.pred_ws[r] = p;
+        if (a.pred) a.pred[r] = p;
+    }
+
+    // O = diag h' in the read-out basis
+    for (int i = rank; i < NE; i += TPR) {
+        int k = 0;
+        bool diag = true;
+#pragma unroll
+        for (int w = 0; w < N; ++w) {
+            const int rb = (i >> (2 * w)) & 1, cb = (i >> (2 * w + 1)) & 1;
+            diag = diag && rb == cb;
+            k |= rb << w;
+        }
+        cx.obs[i ^ fold(i) ^ sf] = make_double2(diag ? hv[k] : 0.0, 0.0);
+    }
+    __syncthreads();
+    // back to the computational basis: O through the daggers of the basis change (rho is reloaded)
+    if (a.pauli == QHEA_PAULI_X) basis_passes_back<N, 0, 3>(cx.obs, rank, sf);
+    else if (a.pauli == QHEA_PAULI_Y) basis_passes_back<N, 0, 4>(cx.obs, rank, sf);
+
+    // reverse walk: blocks, sub-layers and passes in reverse order; every unit starts from its stored state, fetched while
+    // the unit behind it was walked
+    double2 pf[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) pf[k] = make_double2(0.0, 0.0);
+    if (units > 0) { snap -= ustride; fetch_snapshot<N>(pf, rank, live, snap); }
+    auto open_unit = [&]() {
+        place_snapshot<N>(cx.rho, rank, live, pf);
+        if (--units > 0) { snap -= ustride; fetch_snapshot<N>(pf, rank, live, snap); }
+    };
+    for (int g = 1; g >= 0; --g) {
+        for (int b = a.nb[g] - 1; b >= 0; --b) {
+            col -= N;
+            for (int l = a.ld[g] - 1; l >= 0; --l) {
+                --s;
+                open_unit();
+                dev_ring_passes_back<N, N - 1>(cx, a, csr, s, col, l == 0);
+            }
+            if (a.ld[g] == 0) {
+                open_unit();
+                dev_enc_passes_back<N, 0>(cx, a, csr, col);
+            }
+        }
+    }
+}
+
 // ---- host ----
 
 // the kernel's table for a checked setting whose channels are all invertible
@@ -384,13 +558,17 @@ void fill_table(int n, const qhea_device_noise* dn, DevTable& t) {
 
 // log10 A_dev of a checked setting: - sum log10 min(off, a) over the one-wire sites the circuit applies (ENC once per block,
 // ROT / CTL / TGT once per sub-layer) - sum log10 (1 - lam_j) over its CNOT slots; +inf for a singular channel
-double device_log10_amplification(const ModelInfo& mi, const qhea_device_noise* dn) {
+// `layer`: of the largest single unit instead -- one sub-layer's sites and slots, with the ENC sites if the circuit encodes at
+// all (every block does, so some first sub-layer carries them); the ENC sites alone for a circuit without sub-layers
+double device_log10_amplification(const ModelInfo& mi, const qhea_device_noise* dn, bool layer = false) {
     const int n = mi.n;
     for (int q = 0; q < n; ++q)
         if (!(dn->p1[q] < 0.75) || !(dn->p2[q] < 15.0 / 16.0)) return INFINITY;
     std::vector<double> chan((size_t)4 * n * 3), lam2((size_t)n);
     device_noise_compose(n, dn, chan.data(), n, lam2.data());
-    const double count[4] = {(double)(mi.sh.E / n), (double)mi.sh.blk, (double)mi.sh.blk, (double)mi.sh.blk};
+    const double enc = (double)(mi.sh.E / n), sub = (double)mi.sh.blk;
+    const double slots = layer && sub > 1.0 ? 1.0 : sub;
+    const double count[4] = {layer && enc > 1.0 ? 1.0 : enc, slots, slots, slots};
     double sum = 0.0;
     for (int k = 0; k < 4; ++k) {
         if (count[k] == 0.0) continue;
@@ -401,7 +579,7 @@ double device_log10_amplification(const ModelInfo& mi, const qhea_device_noise* 
             sum -= count[k] * log10(m);
         }
     }
-    for (int j = 0; j < n && mi.sh.blk > 0; ++j) sum -= (double)mi.sh.blk * log10(1.0 - lam2[j]);
+    for (int j = 0; j < n && mi.sh.blk > 0; ++j) sum -= slots * log10(1.0 - lam2[j]);
     return sum;
 }
 
@@ -448,6 +626,41 @@ struct DevGradUnit {
     }
 };
 
+// The unit record of the stored-state calls: DevGradUnit with the snapshot region behind its workspace, the guard asked of the
+// largest single unit (between two stored states rho walks back through one unit, and one unit is a circuit of the kind the
+// bound was measured on), and the stored-state kernel.  Table, prep and reduce launches are the inverse unit's.
+struct DevStoredGradUnit : DevGradUnit {
+    // U: sub-layers, plus the blocks without any (one encoding-only unit each)
+    static size_t units(const ModelInfo& mi) {
+        size_t u = 0;
+        for (int g = 0; g < 2; ++g) u += (size_t)mi.nb[g] * (size_t)(mi.ld[g] == 0 ? 1 : mi.ld[g]);
+        return u;
+    }
+    static size_t off_snap(const ModelInfo& mi, int64_t B) { return DevGradUnit::workspace_bytes(mi, B); }
+    static size_t workspace_bytes(const ModelInfo& mi, int64_t B) {
+        return off_snap(mi, B) + align256(units(mi) * (size_t)B * (sizeof(double2) << (2 * mi.n)));
+    }
+    static int refuse(const ModelInfo& mi, const qhea_device_noise* dn) {
+        if (mi.n > kDevMaxWires) return QHEA_EUNSUPPORTED;
+        return device_log10_amplification(mi, dn, true) <= kMaxLog10AmplificationDevice ? QHEA_OK : QHEA_EUNSUPPORTED;
+    }
+    static int check(const qhea_model_desc* desc, const double* ham_diag, const qhea_device_noise* dn, int64_t count,
+                     const double* trunk, std::initializer_list<const void*> required, void* workspace, void* stream,
+                     NoisyCall& c) {
+        return device_call_check({QHEA_MIN_QUBITS, kDevMaxWires, false, false}, desc, ham_diag, dn, refuse, count, trunk, required,
+                                 workspace, stream, c);
+    }
+    static int launch_bwd(const GradBatch& b, const qhea_device_noise*) {
+        DevStoredArgs a{};
+        circuit_args(a, b.desc, b.mi, b.params, b.ham_diag, b.batch, b.gates, b.cs);
+        a.tab = reinterpret_cast<const double*>(b.ws + off_tab(b.mi, b.bmax));
+        a.w = b.params + b.mi.off_ans;
+        a.pred = b.pred; a.pred_ws = b.pred_ws; a.rec = b.rec;
+        a.snap = reinterpret_cast<double2*>(b.ws + off_snap(b.mi, b.bmax));
+        return dispatch_n(b.mi.n, [&](auto n) { return launch_density_bwd<n()>(density_dev_stored_bwd_kernel<n()>, a.B, a, b.st); });
+    }
+};
+
 }  // namespace
 }  // namespace qhea
 
@@ -483,6 +696,37 @@ int qhea_model_train_steps_noisy_device_exact(const qhea_model_desc* desc, int64
     const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
                          first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
     return grad_train_steps<DevGradUnit>(desc, call, ham_diag, dn, lr);
+}
+
+size_t qhea_model_device_noisy_stored_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch) {
+    return grad_workspace_bytes<DevStoredGradUnit>(desc, batch);
+}
+
+double qhea_model_device_noisy_log10_layer_amplification(const qhea_model_desc* desc, const qhea_device_noise* dn) {
+    ModelInfo mi;
+    if (model_info(desc, mi) != QHEA_OK || device_noise_check(mi.n, dn) != QHEA_OK) return NAN;
+    return device_log10_amplification(mi, dn, true);
+}
+
+int qhea_model_loss_grad_noisy_device_exact_stored(const qhea_model_desc* desc, int64_t batch, const double* branch,
+                                                   const double* trunk, const double* y, const double* params,
+                                                   const double* ham_diag, const qhea_device_noise* dn, double inv_batch_total,
+                                                   double* grad, double* pred, void* workspace, size_t workspace_bytes,
+                                                   void* stream) {
+    return grad_loss_grad<DevStoredGradUnit>(desc, batch, branch, trunk, y, params, ham_diag, dn, inv_batch_total, grad, pred,
+                                             workspace, workspace_bytes, stream);
+}
+
+int qhea_model_train_steps_noisy_device_exact_stored(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
+                                                     const double* branch, const double* trunk, const double* y, double* params,
+                                                     const double* ham_diag, const qhea_device_noise* dn,
+                                                     const double* inv_batch_total, double* grad, int64_t grad_stride,
+                                                     double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr,
+                                                     double beta1, double beta2, double eps, double weight_decay, void* workspace,
+                                                     size_t workspace_bytes, void* stream) {
+    const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
+                         first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
+    return grad_train_steps<DevStoredGradUnit>(desc, call, ham_diag, dn, lr);
 }
 
 }  // extern "C"

@@ -484,13 +484,36 @@ def device_amplification(model, noise):
     return _lib.model_device_noisy_log10_amplification(desc, noise.params(desc.n_qubits))
 
 
-def device_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
+def device_layer_amplification(model, noise):
+    """
+    device_amplification of the largest single unit of this model's circuit (qhea_model_device_noisy_log10_layer_amplification):
+    one sub-layer's channel sites and CNOT slots with the encoding sites in front of it.  It bounds
+    device_noisy_loss_and_grad(states='stored') and the config key train_noise_states='stored', which replay rho from the
+    state stored after every unit, the way device_amplification bounds the inverse walk (values above 7 and inf are refused).
+    No device is needed.
+    """
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("device_layer_amplification takes a QuanONetPT or HEAQNNPT model")
+    _device_noise(noise, 'device_layer_amplification')
+    desc = model.fused_desc()
+    return _lib.model_device_noisy_log10_layer_amplification(desc, noise.params(desc.n_qubits))
+
+
+NOISE_STATES = ('inverse', 'stored')
+
+
+def device_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, states='inverse'):
     """
     exact_noisy_loss_and_grad under a DeviceNoise: the MSE loss of exact_noisy_predict(model, inputs, noise) and its exact
     gradient, as the flat [P + 2] tensor of qhea_model_loss_grad_noisy_device_exact (same layout, same inv_batch_total).  The
     adjoint walk through the density matrix with the device's channel sites: no sampling, n <= 6.
+    states='inverse' walks rho back through the inverse of every channel and is refused above device_amplification 7;
+    states='stored' (qhea_model_loss_grad_noisy_device_exact_stored) replays rho from the state the forward sweep stored after
+    every sub-layer, is bounded by device_layer_amplification instead, and takes units x rows x 16 x 4^n more bytes.
     """
     _device_noise(noise, 'device_noisy_loss_and_grad')
+    if states not in NOISE_STATES:
+        raise ValueError(f"device_noisy_loss_and_grad: states must be 'inverse' or 'stored' (got {states!r})")
     desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'device_noisy_loss_and_grad')
     B = branch.shape[0]
     y = y.detach().to(torch.float64).reshape(-1).contiguous()
@@ -498,8 +521,8 @@ def device_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
     if B == 0:
         return grad
     inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
-    return _lib.model_loss_grad_noisy_device_exact(desc, branch, trunk, y, flat, noise.params(desc.n_qubits), inv, grad,
-                                                   ham_diag=ham_diag)
+    call = _lib.model_loss_grad_noisy_device_exact_stored if states == 'stored' else _lib.model_loss_grad_noisy_device_exact
+    return call(desc, branch, trunk, y, flat, noise.params(desc.n_qubits), inv, grad, ham_diag=ham_diag)
 
 
 def device_sampled_loss_and_grad(model, inputs, y, device_noise, sampling, inv_batch_total=None, row0=0):

@@ -321,6 +321,29 @@ def _train_device_noise(v, train_noise=None):
                      f"(got {type(v).__name__}); a NoiseModel goes to train_noise")
 
 
+def _train_noise_states(v, train_noise=None, train_device_noise=None, sampling_keys=()):
+    """config value / argument `train_noise_states` -> 'inverse' (the default: rho walked back through the inverse channels) or
+    'stored' (rho replayed from the states the forward sweep stored, qhea_model_train_steps_noisy_device_exact_stored).
+    `sampling_keys`: the sampling keys that are set.  'stored' belongs to the exact loss under train_device_noise alone."""
+    if v is None or v == 'inverse':
+        return 'inverse'
+    if v != 'stored':
+        raise ValueError(f"train_noise_states must be 'inverse' (rho walked back through the inverse channels, the default) or "
+                         f"'stored' (rho replayed from stored forward states) (got {v!r})")
+    if train_noise is not None:
+        raise ValueError("train_noise_states='stored' does not combine with train_noise: under a uniform NoiseModel every "
+                         "gradient entry shrinks by the amplification the guard bounds, so past the guard there is nothing left "
+                         "to train; stored states are the walk of train_device_noise")
+    for key in sampling_keys:
+        raise ValueError(f"train_noise_states='stored' does not combine with {key}: a sampled-trajectory gradient walks pure "
+                         "states back through unitaries and has no inverse channel to replace; stored states belong to the "
+                         "exact loss of train_device_noise alone (n <= 6)")
+    if train_device_noise is None:
+        raise ValueError("train_noise_states='stored' needs train_device_noise: it says how the exact gradient under that "
+                         "DeviceNoise carries rho back")
+    return 'stored'
+
+
 def _train_sampling(v, key='train_sampling'):
     """config value / argument `train_sampling` or `train_trajectories` -> Sampling or None (a Sampling, or its asdict() form)"""
     if v is None:
@@ -343,10 +366,14 @@ class DataParallelTrainer:
 
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
                  fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None,
-                 train_sampling=None, train_trajectories=None, train_jump_trajectories=None):
+                 train_sampling=None, train_trajectories=None, train_jump_trajectories=None, train_noise_states=None):
         self.model = model
         self.train_noise = _train_noise(train_noise)
         self.train_device_noise = _train_device_noise(train_device_noise, train_noise)
+        self.noise_states = _train_noise_states(
+            train_noise_states, self.train_noise, self.train_device_noise,
+            [k for k, v in (('train_sampling', train_sampling), ('train_trajectories', train_trajectories),
+                            ('train_jump_trajectories', train_jump_trajectories)) if v is not None])
         # train_jump_trajectories beside train_device_noise: what train_trajectories means there, for every n a quantum-jump
         # gradient exists for (7..12); train_trajectories there keeps the range it was introduced with (7..9)
         if train_jump_trajectories is not None:
@@ -522,12 +549,20 @@ class DataParallelTrainer:
                                  "device, Adam with betas / eps / weight_decay only)")
             from . import _lib
             n = self.desc.n_qubits
+            stored = self.noise_states == 'stored'
             try:
                 rec = self.train_device_noise.params(n)
                 amp = _lib.model_device_noisy_log10_amplification(self.desc, rec)
-                refused = _lib.model_device_noisy_refused(self.desc, rec)     # the library's own checks and bound
+                # the library's own checks and bound
+                refused = (_lib.model_device_noisy_stored_refused if stored else _lib.model_device_noisy_refused)(self.desc, rec)
+                layer = _lib.model_device_noisy_log10_layer_amplification(self.desc, rec) if stored else None
             except _lib.QheaError as e:
                 raise ValueError(f"train_device_noise: {e}") from e
+            if refused and stored:
+                raise ValueError(f"train_device_noise with train_noise_states='stored': the library refuses this model under "
+                                 f"this DeviceNoise (n = {n}, log10 amplification {amp:.2f}, of one layer {layer:.2f}): n <= 6 "
+                                 "and a layer amplification within the bound of include/quanonet_hea.h are needed; see "
+                                 "quanonet_amd.noise.device_layer_amplification")
             if refused:
                 raise ValueError(f"train_device_noise: the library refuses this model under this DeviceNoise (n = {n}, log10 "
                                  f"amplification {amp:.2f}): n <= 6 and a log10 amplification within the bound of "
@@ -541,6 +576,11 @@ class DataParallelTrainer:
             if log is not None:
                 log("device-noise training: the loss and 'loss_train' are the exact noisy MSE under the DeviceNoise of "
                     f"train_device_noise (log10 amplification {amp:.2f})")
+                if stored:
+                    per_row = _lib.model_device_noisy_stored_grad_workspace_bytes(self.desc, 1, snapshots_only=True)
+                    log(f"device-noise training: rho is replayed from stored states (train_noise_states='stored'; log10 "
+                        f"amplification {amp:.2f} in total, {layer:.2f} for one layer, which is what the bound is asked of; "
+                        f"{per_row} snapshot bytes per row)")
 
     def _noise_params(self):
         """the noise record of the training loss as the C ABI takes it, or None (the ideal loss)"""
@@ -589,7 +629,9 @@ class DataParallelTrainer:
                 self._sampled_loss_grad(*data, self._sampled_noise(self.optimizer.t + 1), 1.0 / gb, grad,
                                         ham_diag=self._ham_diag())
             elif self.train_device_noise is not None:
-                _lib.model_loss_grad_noisy_device_exact(*data, self._noise_params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
+                call = (_lib.model_loss_grad_noisy_device_exact_stored if self.noise_states == 'stored' else
+                        _lib.model_loss_grad_noisy_device_exact)
+                call(*data, self._noise_params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
             elif self.train_noise is not None:
                 _lib.model_loss_grad_noisy_exact(*data, self.train_noise.params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
             else:
@@ -662,7 +704,7 @@ class DataParallelTrainer:
     def _steps(self, inputs, y, bounds, global_batches, rows, first_step):
         """single device: the steps entry, ideal (qhea_model_train_steps), under train_noise (..._noisy_exact; with
         train_sampling / train_trajectories ..._noisy_wide or ..._noisy_lds) or under train_device_noise
-        (..._noisy_device_exact)"""
+        (..._noisy_device_exact, with train_noise_states='stored' ..._noisy_device_exact_stored)"""
         from . import _lib
         opt = self.optimizer
         call = (self.desc, bounds, global_batches, *split_inputs(inputs), y.reshape(-1), self.pflat, rows, opt.exp_avg,
@@ -670,7 +712,9 @@ class DataParallelTrainer:
         if self.train_sampling is not None:
             self._sampled_steps(*call, self._sampled_noise(0), ham_diag=self._ham_diag())
         elif self.train_device_noise is not None:
-            _lib.model_train_steps_noisy_device_exact(*call, self._noise_params(), ham_diag=self._ham_diag())
+            steps = (_lib.model_train_steps_noisy_device_exact_stored if self.noise_states == 'stored' else
+                     _lib.model_train_steps_noisy_device_exact)
+            steps(*call, self._noise_params(), ham_diag=self._ham_diag())
         elif self.train_noise is not None:
             _lib.model_train_steps_noisy_exact(*call, self.train_noise.params(), ham_diag=self._ham_diag())
         else:
@@ -863,7 +907,8 @@ class PTSolver:
                                            train_device_noise=config.get('train_device_noise'),
                                            train_sampling=config.get('train_sampling'),
                                            train_trajectories=config.get('train_trajectories'),
-                                           train_jump_trajectories=config.get('train_jump_trajectories'))
+                                           train_jump_trajectories=config.get('train_jump_trajectories'),
+                                           train_noise_states=config.get('train_noise_states'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None
