@@ -5,6 +5,7 @@ ctypes binding of the C ABI in include/quanonet_hea.h (libquanonet_hea.so, built
 There is deliberately NO CPU fallback: if the shared library is missing, or a tensor is not on
 a HIP device, the calls raise.  torch is used only for device memory and streams.
 """
+import collections
 import ctypes
 import os
 
@@ -968,17 +969,6 @@ def model_exact_noisy_log10_amplification(desc, noise):
     return float(load().qhea_model_exact_noisy_log10_amplification(ctypes.byref(desc), ctypes.byref(noise)))
 
 
-# the exact gradient units by what `device_model` says: False the uniform NoiseParams, True a DeviceNoiseParams with rho walked
-# back through inverses, 'stored' a DeviceNoiseParams with rho replayed from stored states: (name in the entry points, sizing call)
-_NOISY_GRAD_UNITS = {False: ('noisy_exact', 'qhea_model_exact_noisy_grad_workspace_bytes'),
-                     True: ('noisy_device_exact', 'qhea_model_device_noisy_grad_workspace_bytes'),
-                     'stored': ('noisy_device_exact_stored', 'qhea_model_device_noisy_stored_grad_workspace_bytes')}
-
-
-def _noisy_grad_ws(lib, desc, B, device, device_model=False):
-    return _sized_ws(device, getattr(lib, _NOISY_GRAD_UNITS[device_model][1]), ctypes.byref(desc), int(B))
-
-
 def _check_noisy_grad(rc, who):
     if rc == -2:
         raise Unsupported(f"{who}: n >= 7, or rates and depth whose inverse walk is ill-conditioned (log10 amplification > 12, "
@@ -986,11 +976,46 @@ def _check_noisy_grad(rc, who):
     _check(rc, who)
 
 
-def _loss_grad_noisy(device_model, desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred):
-    """The two gradient entry points share one argument list: qhea_model_loss_grad_noisy_exact (`noise` a NoiseParams) and
-    ..._noisy_device_exact and ..._noisy_device_exact_stored (a DeviceNoiseParams)."""
+# The noisy gradient units by the name in their entry points (qhea_model_loss_grad_<name>, qhea_model_train_steps_<name>):
+#   size, size_rec   the workspace query: called with (desc, batch) and then the record `size_rec` by reference (None: no record)
+#   row0             whether loss_grad takes row0 in front of the batch
+#   records          the records that go in by reference behind ham_diag, in their order
+#   check            how a non-zero return code is reported: check(rc, entry, desc, records)
+_GradUnit = collections.namedtuple('_GradUnit', 'size size_rec row0 records check')
+
+
+def _exact_unit(size):
+    return _GradUnit(size, None, False, ('noise',), lambda rc, who, desc, records: _check_noisy_grad(rc, who))
+
+
+def _sampled_unit(kind):
+    return _GradUnit(f'qhea_model_noisy_{kind}_grad_workspace_bytes', 'noise', True, ('noise',),
+                     lambda rc, who, desc, records: _check_noisy_wide_grad(rc, who, kind))
+
+
+def _jump_unit(size):
+    return _GradUnit(size, 'sampling', True, ('noise', 'sampling'),
+                     lambda rc, who, desc, records: _check_device_sampled(rc, who, desc, records['noise']))
+
+
+_GRAD_UNITS = {'noisy_exact': _exact_unit('qhea_model_exact_noisy_grad_workspace_bytes'),
+               'noisy_device_exact': _exact_unit('qhea_model_device_noisy_grad_workspace_bytes'),
+               'noisy_device_exact_stored': _exact_unit('qhea_model_device_noisy_stored_grad_workspace_bytes'),
+               'noisy_wide': _sampled_unit('wide'),
+               'noisy_lds': _sampled_unit('lds'),
+               'noisy_device': _jump_unit('qhea_model_noisy_device_grad_workspace_bytes'),
+               'noisy_device_lds': _jump_unit('qhea_model_noisy_device_lds_grad_workspace_bytes')}
+
+
+def _grad_unit_ws(lib, unit, desc, B, records, device):
+    rec = () if unit.size_rec is None else (ctypes.byref(records[unit.size_rec]),)
+    return _sized_ws(device, getattr(lib, unit.size), ctypes.byref(desc), int(B), *rec)
+
+
+def _loss_grad_call(name, desc, branch, trunk, y, params, records, inv_batch_total, grad, row0, ham_diag, pred):
+    """qhea_model_loss_grad_<name> of a unit of _GRAD_UNITS; `records`: its records by name"""
     lib = load()
-    entry = 'qhea_model_loss_grad_' + _NOISY_GRAD_UNITS[device_model][0]
+    unit, entry = _GRAD_UNITS[name], 'qhea_model_loss_grad_' + name
     B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(y, 'y')
     if y.numel() != B:
@@ -999,30 +1024,33 @@ def _loss_grad_noisy(device_model, desc, branch, trunk, y, params, noise, inv_ba
     if grad.numel() < params.numel() + 2:
         raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
     _dev_f64(pred, 'pred', (B,))
-    ws = _noisy_grad_ws(lib, desc, B, branch.device, device_model)
+    ws = _grad_unit_ws(lib, unit, desc, B, records, branch.device)
+    rows = (int(row0), B) if unit.row0 else (B,)
     with torch.cuda.device(branch.device):
-        rc = getattr(lib, entry)(ctypes.byref(desc), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params), _ptr(ham_diag),
-                                 ctypes.byref(noise), float(inv_batch_total), _ptr(grad), _ptr(pred), _ptr(ws),
-                                 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_noisy_grad(rc, entry)
+        rc = getattr(lib, entry)(ctypes.byref(desc), *rows, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params), _ptr(ham_diag),
+                                 *(ctypes.byref(records[k]) for k in unit.records), float(inv_batch_total), _ptr(grad),
+                                 _ptr(pred), _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
+    unit.check(rc, entry, desc, records)
     return grad
 
 
-def _train_steps_noisy(device_model, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                       first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag):
+def _train_steps_call(name, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step, lr,
+                      beta1, beta2, eps, weight_decay, records, ham_diag):
+    """qhea_model_train_steps_<name> of a unit of _GRAD_UNITS; `records`: its records by name"""
     lib = load()
-    entry = 'qhea_model_train_steps_' + _NOISY_GRAD_UNITS[device_model][0]
+    unit, entry = _GRAD_UNITS[name], 'qhea_model_train_steps_' + name
     if len(bounds) - 1 <= 0:
         return rows
     n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
                                                     exp_avg, exp_avg_sq, ham_diag)
-    ws = _noisy_grad_ws(lib, desc, biggest, branch.device, device_model)
+    ws = _grad_unit_ws(lib, unit, desc, biggest, records, branch.device)
     with torch.cuda.device(branch.device):
         rc = getattr(lib, entry)(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
-                                 _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows), int(rows.stride(0)), _ptr(exp_avg),
-                                 _ptr(exp_avg_sq), int(first_step), float(lr), float(beta1), float(beta2), float(eps),
-                                 float(weight_decay), _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_noisy_grad(rc, entry)
+                                 _ptr(ham_diag), *(ctypes.byref(records[k]) for k in unit.records), ib, _ptr(rows),
+                                 int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step), float(lr), float(beta1),
+                                 float(beta2), float(eps), float(weight_decay), _ptr(ws), 0 if ws is None else ws.numel(),
+                                 _stream(branch.device))
+    unit.check(rc, entry, desc, records)
     return rows
 
 
@@ -1032,7 +1060,8 @@ def model_loss_grad_noisy_exact(desc, branch, trunk, y, params, noise, inv_batch
     of the exact noisy prediction for this shard (qhea_model_loss_grad_noisy_exact); returns grad.  Raises Unsupported for
     n >= 7 or a refused conditioning and QheaError for a bad noise setting, in both cases before anything is launched.
     """
-    return _loss_grad_noisy(False, desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred)
+    return _loss_grad_call('noisy_exact', desc, branch, trunk, y, params, dict(noise=noise), inv_batch_total, grad, 0, ham_diag,
+                           pred)
 
 
 def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
@@ -1042,8 +1071,8 @@ def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y
     bounds[i]:bounds[i+1] under `noise` with residual weight 1 / global_batches[i], leaves [grads | sse | sum y^2] in rows[i]
     and applies Adam update first_step + i.  Bitwise a loop of model_loss_grad_noisy_exact + adam_step.
     """
-    return _train_steps_noisy(False, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                              first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+    return _train_steps_call('noisy_exact', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                             first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
 
 
 def model_noisy_wide_grad_workspace_bytes(desc, batch, noise):
@@ -1062,47 +1091,6 @@ def _check_noisy_wide_grad(rc, who, kind='wide'):
     _check(rc, who)
 
 
-def _loss_grad_sampled(kind, desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0, ham_diag, pred):
-    lib = load()
-    entry = f'qhea_model_loss_grad_noisy_{kind}'
-    B = _model_inputs(desc, branch, trunk, params, ham_diag)
-    _dev_f64(y, 'y')
-    if y.numel() != B:
-        raise QheaError(f"y has {y.numel()} elements, expected {B}")
-    _dev_f64(grad, 'grad')
-    if grad.numel() < params.numel() + 2:
-        raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
-    _dev_f64(pred, 'pred', (B,))
-    ws = _sized_ws(branch.device, getattr(lib, f'qhea_model_noisy_{kind}_grad_workspace_bytes'), ctypes.byref(desc), int(B),
-                   ctypes.byref(noise))
-    with torch.cuda.device(branch.device):
-        rc = getattr(lib, entry)(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
-                                 _ptr(ham_diag), ctypes.byref(noise), float(inv_batch_total), _ptr(grad),
-                                 _ptr(pred), _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_noisy_wide_grad(rc, entry, kind)
-    return grad
-
-
-def _train_steps_sampled(kind, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
-                         lr, beta1, beta2, eps, weight_decay, noise, ham_diag):
-    lib = load()
-    entry = f'qhea_model_train_steps_noisy_{kind}'
-    if len(bounds) - 1 <= 0:
-        return rows
-    n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
-                                                    exp_avg, exp_avg_sq, ham_diag)
-    ws = _sized_ws(branch.device, getattr(lib, f'qhea_model_noisy_{kind}_grad_workspace_bytes'), ctypes.byref(desc),
-                   int(biggest), ctypes.byref(noise))
-    with torch.cuda.device(branch.device):
-        rc = getattr(lib, entry)(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y),
-                                 _ptr(params), _ptr(ham_diag), ctypes.byref(noise), ib, _ptr(rows),
-                                 int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
-                                 float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                 _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_noisy_wide_grad(rc, entry, kind)
-    return rows
-
-
 def model_loss_grad_noisy_wide(desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0=0, ham_diag=None, pred=None):
     """
     model_loss_grad of the SAMPLED noisy prediction (qhea_model_loss_grad_noisy_wide, n = 7..9): fills grad[P+2] =
@@ -1111,7 +1099,8 @@ def model_loss_grad_noisy_wide(desc, branch, trunk, y, params, noise, inv_batch_
     fixed; returns grad.  Raises Unsupported for n outside 7..9 and QheaError for a bad noise setting (shots > 0 included), in
     both cases before anything is launched.
     """
-    return _loss_grad_sampled('wide', desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0, ham_diag, pred)
+    return _loss_grad_call('noisy_wide', desc, branch, trunk, y, params, dict(noise=noise), inv_batch_total, grad, row0, ham_diag,
+                           pred)
 
 
 def model_train_steps_noisy_wide(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
@@ -1122,8 +1111,8 @@ def model_train_steps_noisy_wide(desc, bounds, global_batches, branch, trunk, y,
     first_step + i, leaves [grads | sse | sum y^2] in rows[i] and applies Adam update first_step + i.  Bitwise a loop of
     model_loss_grad_noisy_wide (that seed, row0 = bounds[i]) + adam_step.
     """
-    return _train_steps_sampled('wide', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                                first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+    return _train_steps_call('noisy_wide', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                             first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
 
 
 def model_noisy_lds_grad_workspace_bytes(desc, batch, noise):
@@ -1134,15 +1123,16 @@ def model_noisy_lds_grad_workspace_bytes(desc, batch, noise):
 def model_loss_grad_noisy_lds(desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0=0, ham_diag=None, pred=None):
     """model_loss_grad_noisy_wide at n = 10..12 (qhea_model_loss_grad_noisy_lds): same arguments, same quantity, psi and lambda
     in LDS.  Raises Unsupported for n outside 10..12."""
-    return _loss_grad_sampled('lds', desc, branch, trunk, y, params, noise, inv_batch_total, grad, row0, ham_diag, pred)
+    return _loss_grad_call('noisy_lds', desc, branch, trunk, y, params, dict(noise=noise), inv_batch_total, grad, row0, ham_diag,
+                           pred)
 
 
 def model_train_steps_noisy_lds(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
                                 lr, beta1, beta2, eps, weight_decay, noise, ham_diag=None):
     """model_train_steps_noisy_wide at n = 10..12 (qhea_model_train_steps_noisy_lds): bitwise a loop of
     model_loss_grad_noisy_lds (seed noise.seed + first_step + i, row0 = bounds[i]) + adam_step."""
-    return _train_steps_sampled('lds', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                                first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+    return _train_steps_call('noisy_lds', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                             first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
 
 
 def model_noisy_device_grad_workspace_bytes(desc, batch, sampling):
@@ -1203,7 +1193,8 @@ def model_loss_grad_noisy_device(desc, branch, trunk, y, params, noise, sampling
     fired pattern fixed, over the final norm); returns grad.  Raises Unsupported for n outside 7..9 and QheaError for a bad
     setting (shots != 0 and a site with gamma = 1 included), in both cases before anything is launched.
     """
-    return _loss_grad_noisy_device('', desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0, ham_diag, pred)
+    return _loss_grad_call('noisy_device', desc, branch, trunk, y, params, dict(noise=noise, sampling=sampling), inv_batch_total,
+                           grad, row0, ham_diag, pred)
 
 
 def model_loss_grad_noisy_device_lds(desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0=0, ham_diag=None,
@@ -1211,30 +1202,8 @@ def model_loss_grad_noisy_device_lds(desc, branch, trunk, y, params, noise, samp
     """model_loss_grad_noisy_device for n = 10..12 (qhea_model_loss_grad_noisy_device_lds: the same quantity, estimator and
     random stream with psi and lambda in LDS; pred is what model_forward_noisy_device_wide returns).  Same errors, with the
     qubit range 10..12."""
-    return _loss_grad_noisy_device('_lds', desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0, ham_diag,
-                                   pred)
-
-
-def _loss_grad_noisy_device(unit, desc, branch, trunk, y, params, noise, sampling, inv_batch_total, grad, row0, ham_diag, pred):
-    lib = load()
-    entry = 'qhea_model_loss_grad_noisy_device' + unit
-    sizer = getattr(lib, f'qhea_model_noisy_device{unit}_grad_workspace_bytes')
-    B = _model_inputs(desc, branch, trunk, params, ham_diag)
-    _dev_f64(y, 'y')
-    if y.numel() != B:
-        raise QheaError(f"y has {y.numel()} elements, expected {B}")
-    _dev_f64(grad, 'grad')
-    if grad.numel() < params.numel() + 2:
-        raise QheaError(f"{entry[5:]}: grad needs P + 2 entries")
-    _dev_f64(pred, 'pred', (B,))
-    ws = _sized_ws(branch.device, sizer, ctypes.byref(desc), int(B), ctypes.byref(sampling))
-    with torch.cuda.device(branch.device):
-        rc = getattr(lib, entry)(ctypes.byref(desc), int(row0), B, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
-                                                   _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling),
-                                                   float(inv_batch_total), _ptr(grad), _ptr(pred), _ptr(ws),
-                                                   0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_device_sampled(rc, entry, desc, noise)
-    return grad
+    return _loss_grad_call('noisy_device_lds', desc, branch, trunk, y, params, dict(noise=noise, sampling=sampling),
+                           inv_batch_total, grad, row0, ham_diag, pred)
 
 
 def model_train_steps_noisy_device(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
@@ -1245,36 +1214,30 @@ def model_train_steps_noisy_device(desc, bounds, global_batches, branch, trunk, 
     first_step + i, leaves [grads | sse | sum y^2] in rows[i] and applies Adam update first_step + i.  Bitwise a loop of
     model_loss_grad_noisy_device (that seed, row0 = bounds[i]) + adam_step.
     """
-    return _train_steps_noisy_device('', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                                     first_step, lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag)
+    return _train_steps_call('noisy_device', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                             first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise, sampling=sampling), ham_diag)
 
 
 def model_train_steps_noisy_device_lds(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
                                        first_step, lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag=None):
     """model_train_steps_noisy_device for n = 10..12 (qhea_model_train_steps_noisy_device_lds).  Bitwise a loop of
     model_loss_grad_noisy_device_lds (seed sampling.seed + first_step + i, row0 = bounds[i]) + adam_step."""
-    return _train_steps_noisy_device('_lds', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                                     first_step, lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag)
+    return _train_steps_call('noisy_device_lds', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                             first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise, sampling=sampling), ham_diag)
 
 
-def _train_steps_noisy_device(unit, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq, first_step,
-                              lr, beta1, beta2, eps, weight_decay, noise, sampling, ham_diag):
-    lib = load()
-    entry = 'qhea_model_train_steps_noisy_device' + unit
-    sizer = getattr(lib, f'qhea_model_noisy_device{unit}_grad_workspace_bytes')
-    if len(bounds) - 1 <= 0:
-        return rows
-    n_steps, rb, ib, biggest = _flat_train_schedule(entry[5:], desc, bounds, global_batches, branch, trunk, y, params, rows,
-                                                    exp_avg, exp_avg_sq, ham_diag)
-    ws = _sized_ws(branch.device, sizer, ctypes.byref(desc), int(biggest), ctypes.byref(sampling))
-    with torch.cuda.device(branch.device):
-        rc = getattr(lib, entry)(ctypes.byref(desc), n_steps, rb, _ptr(branch), _ptr(trunk), _ptr(y), _ptr(params),
-                                                     _ptr(ham_diag), ctypes.byref(noise), ctypes.byref(sampling), ib, _ptr(rows),
-                                                     int(rows.stride(0)), _ptr(exp_avg), _ptr(exp_avg_sq), int(first_step),
-                                                     float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                                     _ptr(ws), 0 if ws is None else ws.numel(), _stream(branch.device))
-    _check_device_sampled(rc, entry, desc, noise)
-    return rows
+def sampled_grad_calls(n):
+    """(loss_grad, train_steps) of the sampled-trajectory gradient for n qubits: the wave-resident unit (model_*_noisy_wide,
+    n = 7..9) or the LDS-resident one (model_*_noisy_lds, n = 10..12); the calls themselves refuse an n outside their range"""
+    return ((model_loss_grad_noisy_wide, model_train_steps_noisy_wide) if n <= 9 else
+            (model_loss_grad_noisy_lds, model_train_steps_noisy_lds))
+
+
+def device_sampled_grad_calls(n):
+    """sampled_grad_calls for the quantum-jump gradient under a device noise model: model_*_noisy_device (n = 7..9) or
+    model_*_noisy_device_lds (n = 10..12)"""
+    return ((model_loss_grad_noisy_device, model_train_steps_noisy_device) if n <= 9 else
+            (model_loss_grad_noisy_device_lds, model_train_steps_noisy_device_lds))
 
 
 def model_device_noisy_log10_amplification(desc, noise):
@@ -1336,7 +1299,8 @@ def model_loss_grad_noisy_device_exact(desc, branch, trunk, y, params, noise, in
     model_loss_grad_noisy_exact with `noise` a DeviceNoiseParams (qhea_model_loss_grad_noisy_device_exact): loss and exact
     gradient of the prediction of model_forward_noisy_device_exact.  Same errors.
     """
-    return _loss_grad_noisy(True, desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred)
+    return _loss_grad_call('noisy_device_exact', desc, branch, trunk, y, params, dict(noise=noise), inv_batch_total, grad, 0,
+                           ham_diag, pred)
 
 
 def model_train_steps_noisy_device_exact(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
@@ -1345,8 +1309,8 @@ def model_train_steps_noisy_device_exact(desc, bounds, global_batches, branch, t
     model_train_steps_noisy_exact with `noise` a DeviceNoiseParams (qhea_model_train_steps_noisy_device_exact).  Bitwise a loop
     of model_loss_grad_noisy_device_exact + adam_step.
     """
-    return _train_steps_noisy(True, desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                              first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+    return _train_steps_call('noisy_device_exact', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg,
+                             exp_avg_sq, first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
 
 
 def model_loss_grad_noisy_device_exact_stored(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None,
@@ -1356,7 +1320,8 @@ def model_loss_grad_noisy_device_exact_stored(desc, branch, trunk, y, params, no
     the same quantity for settings past that call's guard; Unsupported for n >= 7, a singular channel or a single unit whose
     log10 A_dev is above the bound.  The workspace grows by units x rows x 16 x 4^n bytes.
     """
-    return _loss_grad_noisy('stored', desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag, pred)
+    return _loss_grad_call('noisy_device_exact_stored', desc, branch, trunk, y, params, dict(noise=noise), inv_batch_total, grad, 0,
+                           ham_diag, pred)
 
 
 def model_train_steps_noisy_device_exact_stored(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
@@ -1365,8 +1330,8 @@ def model_train_steps_noisy_device_exact_stored(desc, bounds, global_batches, br
     model_train_steps_noisy_device_exact with rho replayed from stored states
     (qhea_model_train_steps_noisy_device_exact_stored).  Bitwise a loop of model_loss_grad_noisy_device_exact_stored + adam_step.
     """
-    return _train_steps_noisy('stored', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
-                              first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag)
+    return _train_steps_call('noisy_device_exact_stored', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg,
+                             exp_avg_sq, first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
 
 
 def clock_probe(device, n_workgroups=1024, iters=200000):

@@ -35,6 +35,9 @@
 // over the wave by lane_reduce, the waves in wave order through LDS, and thread i adds value i to the item's record in global
 // memory -- the first trajectory of the tile stores, later ones read, add and store, the same thread every time.  No atomics.
 // Records, fold and reduce are hea_noise_grad.hip's and hea_density_grad.hip's; the tables kernel's body is hea_noise_jump.hpp's.
+// The host side of the calls (checks, workspace layout and query, call record, open, launch, the bodies of loss_grad and
+// train_steps) is hea_noise_jump_grad.hpp's, shared with the wave form of this unit.  Here: the kernel and its device helpers, the
+// tables kernel and the launcher, the unit record (JumpLdsUnit) and the extern "C" shells.
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -497,91 +500,25 @@ int launch_device_grad_lds(int n, const NoisyGradArgs& g, const LdsDevGradArgs& 
     }
 }
 
-// ---- host: layout, the three entry points' bodies ---------------------------------------------------------------------------------------
+// ---- the unit of hea_noise_jump_grad.hpp's host body ------------------------------------------------------------------------------------
 
-constexpr GradUnit kLdsDevGradUnit{10, 12, kLdsDevGradTile, nullptr};    // the layout's qubit range and tile
-
-inline int lds_grad_groups(int n, int64_t items) {
-    const int cap = lds_grad_max_groups(n);
-    return (int)(items < cap ? items : cap);
-}
-
-// hea_noise_grad.hpp's layout, then the table, the segments' words and the snapshots of min(items, cap) workgroups: a function
-// of the shape, the batch and T only
-struct LdsDevGradLayout { WideGradLayout w; size_t off_tab, off_words, off_snap, total; long words_stride, snap_stride; };
-inline LdsDevGradLayout device_grad_lds_layout(const ModelInfo& mi, int64_t B, int64_t T) {
-    LdsDevGradLayout L{};
-    L.w = wide_grad_layout(kLdsDevGradUnit, mi, B, T);
-    const int groups = lds_grad_groups(mi.n, B * L.w.tiles);
-    const long blocks = mi.nb[0] + mi.nb[1], segs = blocks + mi.sh.blk;
-    L.words_stride = segs * kSegWords;
-    L.snap_stride = blocks << mi.n;                                      // double2 per LDS slot and block
-    size_t p = L.w.total;
-    L.off_tab = p;   p = align256(p + sizeof(LdsDevGradTable));
-    L.off_words = p; p = align256(p + (size_t)groups * L.words_stride * sizeof(unsigned));
-    L.off_snap = p;  p = align256(p + (size_t)groups * L.snap_stride * sizeof(double2));
-    L.total = p;
-    return L;
-}
-
-struct LdsDevGradCall {
-    const qhea_model_desc* desc; const ModelInfo& mi;
-    LdsDevGradLayout L;
-    const double* ham_diag; const double* hd;
-    LdsDevGradTable tb; bool any;
-    char* ws; hipStream_t st;
+struct JumpLdsUnit {
+    using Table = LdsDevGradTable;
+    using Args = LdsDevGradArgs;
+    using Snap = double2;
+    static constexpr GradUnit unit{10, 12, kLdsDevGradTile, nullptr};    // the layout's qubit range and tile
+    static WideDevTable& jump(Table& t) { return t.t; }
+    static const WideDevTable& jump(const Table& t) { return t.t; }
+    static constexpr int cap(int n) { return lds_grad_max_groups(n); }
+    static long words_stride(long segs) { return segs * kSegWords; }
+    static long snap_stride(long blocks, int n) { return blocks << n; }  // double2 per LDS slot and block
+    static void launch_tables(const Table& tb, Table* out, const double* diag, double co, int n, double* buf, hipStream_t st) {
+        hipLaunchKernelGGL(device_grad_lds_tables_kernel, dim3(1), dim3(256), 0, st, tb, out, diag, co, n, buf);
+    }
+    static int launch(int n, const NoisyGradArgs& g, const Args& d, int groups, hipStream_t st) {
+        return launch_device_grad_lds(n, g, d, groups, st);
+    }
 };
-
-// layout for the call's largest batch, and the once-per-call launch: the table and h'
-inline int device_grad_lds_open(const NoisyCall& c, int64_t bmax, const qhea_device_noise* dn, size_t workspace_bytes,
-                                LdsDevGradCall& w) {
-    w.L = device_grad_lds_layout(c.mi, bmax, c.T);
-    if (!c.ws || workspace_bytes < w.L.total) return QHEA_EWORKSPACE;
-    if (bmax * w.L.w.tiles > (int64_t)INT_MAX) return QHEA_EINVAL;
-    const int n = c.mi.n;
-    w.tb = LdsDevGradTable{};
-    fill_jump_table(n, dn, w.tb.t, w.any);
-    fill_site_inv(n, w.tb.t.gs, w.tb.inv);
-    w.tb.t.off = w.desc->ham_offset; w.tb.t.co = w.desc->ham_coeff; w.tb.t.diag = w.ham_diag;
-    w.tb.t.L = jump_calls(n, c.mi.nb, c.mi.ld); w.tb.t.pauli = (unsigned)w.desc->ham_pauli;
-    double* mix = reinterpret_cast<double*>(c.ws + w.L.w.off_mix);
-    hipLaunchKernelGGL(device_grad_lds_tables_kernel, dim3(1), dim3(256), 0, c.st, w.tb,
-                       reinterpret_cast<LdsDevGradTable*>(c.ws + w.L.off_tab), w.ham_diag, w.desc->ham_coeff, n, mix);
-    if (hipGetLastError() != hipSuccess) return QHEA_ELAUNCH;
-    w.hd = mix + ((size_t)((n - 1) & 1) << n);
-    return QHEA_OK;
-}
-
-// prep, trajectories, fold, reduce (+ Adam when adam.p) for one batch under the stream key `nz.seed`
-inline int device_grad_lds_launch(const LdsDevGradCall& w, const qhea_noise& nz, int64_t T, int64_t row0, int64_t batch,
-                                  const double* branch, const double* trunk, const double* y, const double* params, double inv_bt,
-                                  double* grad, double* pred, const AdamArgs& adam) {
-    const WideGradLayout& L = w.L.w;
-    double4* gates = reinterpret_cast<double4*>(w.ws + L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(w.ws + L.off_cs);
-    int rc = launch_prep_model(w.desc, w.mi, batch, branch, trunk, params, gates, cs, w.ws, w.st);
-    if (rc != QHEA_OK) return rc;
-    NoisyGradArgs g{};
-    g.f = noise_args(w.desc, w.mi, &nz, params, w.ham_diag, row0, batch, T);
-    g.f.gates = gates; g.f.cs = cs; g.f.tiles = L.tiles;
-    g.f.L = w.tb.t.L;
-    g.f.thr1 = w.any ? 1 : 0;                                            // an ideal setting draws nothing
-    g.f.partial = reinterpret_cast<double2*>(w.ws + L.off_part);
-    g.hd = w.hd; g.w = params + w.mi.off_ans; g.blk = (int)w.mi.sh.blk; g.width = (int)L.width;
-    g.items = reinterpret_cast<double*>(w.ws + L.off_items);
-    g.pred = pred; g.pred_ws = reinterpret_cast<double*>(w.ws + L.off_pred);
-    g.rec = reinterpret_cast<double*>(w.ws + L.off_rec);
-    LdsDevGradArgs d{};
-    d.tab = reinterpret_cast<const LdsDevGradTable*>(w.ws + w.L.off_tab);
-    d.words = reinterpret_cast<unsigned*>(w.ws + w.L.off_words);
-    d.snap = reinterpret_cast<double2*>(w.ws + w.L.off_snap);
-    d.words_stride = w.L.words_stride; d.snap_stride = w.L.snap_stride;
-    rc = launch_device_grad_lds(w.mi.n, g, d, lds_grad_groups(w.mi.n, batch * L.tiles), w.st);
-    if (rc != QHEA_OK) return rc;
-    rc = launch_noisy_grad_fold(g, w.mi.n, batch, w.st);
-    if (rc != QHEA_OK) return rc;
-    return launch_density_reduce(w.desc, w.mi, batch, branch, trunk, y, g.rec, g.pred_ws, inv_bt, grad, adam, w.st);
-}
 
 }  // namespace
 }  // namespace qhea
@@ -593,22 +530,15 @@ extern "C" {
 int qhea_noisy_device_lds_grad_max_workgroups(int n) { return lds_grad_max_groups(n); }
 
 size_t qhea_model_noisy_device_lds_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch, const qhea_sampling* sampling) {
-    return device_grad_workspace_bytes(kLdsDevGradUnit, device_grad_lds_layout, desc, batch, sampling);
+    return jump_grad_workspace_bytes<JumpLdsUnit>(desc, batch, sampling);
 }
 
 int qhea_model_loss_grad_noisy_device_lds(const qhea_model_desc* desc, int64_t row0, int64_t batch, const double* branch,
                                           const double* trunk, const double* y, const double* params, const double* ham_diag,
                                           const qhea_device_noise* dn, const qhea_sampling* sampling, double inv_batch_total,
                                           double* grad, double* pred, void* workspace, size_t workspace_bytes, void* stream) {
-    NoisyCall c;
-    qhea_noise nz{};
-    int rc = device_grad_check(kLdsDevGradUnit, desc, ham_diag, dn, sampling, row0, batch, trunk, {branch, y, params, grad}, workspace,
-                               stream, c, nz);
-    if (rc != QHEA_OK || c.empty) return rc;
-    LdsDevGradCall w{desc, c.mi, {}, ham_diag, nullptr, {}, false, c.ws, c.st};
-    rc = device_grad_lds_open(c, batch, dn, workspace_bytes, w);
-    if (rc != QHEA_OK) return rc;
-    return device_grad_lds_launch(w, nz, c.T, row0, batch, branch, trunk, y, params, inv_batch_total, grad, pred, AdamArgs{});
+    return jump_grad_loss_grad<JumpLdsUnit>(desc, row0, batch, branch, trunk, y, params, ham_diag, dn, sampling, inv_batch_total,
+                                            grad, pred, workspace, workspace_bytes, stream);
 }
 
 int qhea_model_train_steps_noisy_device_lds(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin,
@@ -619,26 +549,7 @@ int qhea_model_train_steps_noisy_device_lds(const qhea_model_desc* desc, int64_t
                                             double eps, double weight_decay, void* workspace, size_t workspace_bytes, void* stream) {
     const TrainCall call{n_steps, row_begin, branch, trunk, y, params, inv_batch_total, grad, grad_stride, exp_avg, exp_avg_sq,
                          first_step, beta1, beta2, eps, weight_decay, workspace, workspace_bytes, stream};
-    if (!desc || n_steps < 0 || first_step < 1) return QHEA_EINVAL;
-    NoisyCall c;
-    qhea_noise nz{};
-    int rc = device_grad_check(kLdsDevGradUnit, desc, ham_diag, dn, sampling, 0, n_steps, trunk,
-                               {row_begin, inv_batch_total, branch, y, grad, params, exp_avg, exp_avg_sq}, workspace, stream, c, nz);
-    if (rc != QHEA_OK || c.empty) return rc;
-    const int64_t bmax = call_max_batch(call, c.mi.P, *desc);
-    if (bmax < 0) return QHEA_EINVAL;
-    LdsDevGradCall w{desc, c.mi, {}, ham_diag, nullptr, {}, false, c.ws, c.st};
-    rc = device_grad_lds_open(c, bmax, dn, workspace_bytes, w);
-    if (rc != QHEA_OK) return rc;
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const StepView v = step_view(call, i, *desc);
-        qhea_noise step = nz;
-        step.seed = nz.seed + (uint64_t)(first_step + i);                // fresh draws every step; a resumed run continues them
-        rc = device_grad_lds_launch(w, step, c.T, v.r0, v.nb, v.branch, v.trunk, v.y, params, v.inv_bt, v.grad, nullptr,
-                                    adam_step(call, i, lr).adam);
-        if (rc != QHEA_OK) return rc;
-    }
-    return QHEA_OK;
+    return jump_grad_train_steps<JumpLdsUnit>(desc, call, ham_diag, dn, sampling, lr);
 }
 
 }  // extern "C"

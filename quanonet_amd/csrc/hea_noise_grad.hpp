@@ -90,22 +90,32 @@ inline int wide_grad_open(const NoisyCall& c, int64_t bmax, const qhea_noise* no
     return QHEA_OK;
 }
 
+// The prep launch for one batch and the kernels' record from a call's layout (also the quantum-jump units', which set g.f.L and
+// g.f.thr1 on top: hea_noise_jump_grad.hpp)
+inline int wide_grad_prep(const qhea_model_desc* desc, const ModelInfo& mi, const WideGradLayout& L, char* ws, hipStream_t st,
+                          const double* ham_diag, const double* hd, const qhea_noise* noise, int64_t T, int64_t row0, int64_t batch,
+                          const double* branch, const double* trunk, const double* params, double* pred, NoisyGradArgs& g) {
+    double4* gates = reinterpret_cast<double4*>(ws + L.off_gates);
+    double2* cs = reinterpret_cast<double2*>(ws + L.off_cs);
+    const int rc = launch_prep_model(desc, mi, batch, branch, trunk, params, gates, cs, ws, st);
+    if (rc != QHEA_OK) return rc;
+    g.f = noise_args(desc, mi, noise, params, ham_diag, row0, batch, T);
+    g.f.gates = gates; g.f.cs = cs; g.f.tiles = L.tiles;
+    g.f.partial = reinterpret_cast<double2*>(ws + L.off_part);
+    g.hd = hd; g.w = params + mi.off_ans; g.blk = (int)mi.sh.blk; g.width = (int)L.width;
+    g.items = reinterpret_cast<double*>(ws + L.off_items);
+    g.pred = pred; g.pred_ws = reinterpret_cast<double*>(ws + L.off_pred);
+    g.rec = reinterpret_cast<double*>(ws + L.off_rec);
+    return QHEA_OK;
+}
+
 // prep, trajectories, fold, reduce (+ Adam when adam.p) for one batch under `noise` (its seed: the step's)
 inline int wide_grad_launch(const WideGradCall& w, const qhea_noise* noise, int64_t T, int64_t row0, int64_t batch,
                             const double* branch, const double* trunk, const double* y, const double* params, double inv_bt,
                             double* grad, double* pred, const AdamArgs& adam) {
-    double4* gates = reinterpret_cast<double4*>(w.ws + w.L.off_gates);
-    double2* cs = reinterpret_cast<double2*>(w.ws + w.L.off_cs);
-    int rc = launch_prep_model(w.desc, w.mi, batch, branch, trunk, params, gates, cs, w.ws, w.st);
-    if (rc != QHEA_OK) return rc;
     NoisyGradArgs g{};
-    g.f = noise_args(w.desc, w.mi, noise, params, w.ham_diag, row0, batch, T);
-    g.f.gates = gates; g.f.cs = cs; g.f.tiles = w.L.tiles;
-    g.f.partial = reinterpret_cast<double2*>(w.ws + w.L.off_part);
-    g.hd = w.hd; g.w = params + w.mi.off_ans; g.blk = (int)w.mi.sh.blk; g.width = (int)w.L.width;
-    g.items = reinterpret_cast<double*>(w.ws + w.L.off_items);
-    g.pred = pred; g.pred_ws = reinterpret_cast<double*>(w.ws + w.L.off_pred);
-    g.rec = reinterpret_cast<double*>(w.ws + w.L.off_rec);
+    int rc = wide_grad_prep(w.desc, w.mi, w.L, w.ws, w.st, w.ham_diag, w.hd, noise, T, row0, batch, branch, trunk, params, pred, g);
+    if (rc != QHEA_OK) return rc;
     rc = w.u.launch(w.mi.n, g, w.st);
     if (rc != QHEA_OK) return rc;
     rc = launch_noisy_grad_fold(g, w.mi.n, batch, w.st);

@@ -422,15 +422,19 @@ def noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, row0=0):
         raise ValueError(f"noisy_loss_and_grad covers n = 7..9 (got n = {n}); exact_noisy_loss_and_grad is the call for n <= 6")
     if n >= 10:
         raise ValueError(f"noisy_loss_and_grad covers n = 7..9 (got n = {n})")
-    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'noisy_loss_and_grad')
+    return _sampled_trajectory_call('noisy_loss_and_grad', model, inputs, y, noise, inv_batch_total, row0)
+
+
+def _sampled_trajectory_call(who, model, inputs, y, noise, inv_batch_total, row0):
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, who)
     B = branch.shape[0]
     y = y.detach().to(torch.float64).reshape(-1).contiguous()
     grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
     if B == 0:
         return grad
     inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
-    return _lib.model_loss_grad_noisy_wide(desc, branch, trunk, y, flat, noise.params(), inv, grad, row0=int(row0),
-                                           ham_diag=ham_diag)
+    call, _ = _lib.sampled_grad_calls(desc.n_qubits)
+    return call(desc, branch, trunk, y, flat, noise.params(), inv, grad, row0=int(row0), ham_diag=ham_diag)
 
 
 def sampled_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, row0=0):
@@ -450,17 +454,7 @@ def sampled_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, r
     if n <= 6:
         raise ValueError(f"sampled_noisy_loss_and_grad covers n = 7..12 (got n = {n}); exact_noisy_loss_and_grad is the call "
                          "for n <= 6")
-    if n <= 9:
-        return noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=inv_batch_total, row0=row0)
-    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'sampled_noisy_loss_and_grad')
-    B = branch.shape[0]
-    y = y.detach().to(torch.float64).reshape(-1).contiguous()
-    grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
-    if B == 0:
-        return grad
-    inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
-    return _lib.model_loss_grad_noisy_lds(desc, branch, trunk, y, flat, noise.params(), inv, grad, row0=int(row0),
-                                          ham_diag=ham_diag)
+    return _sampled_trajectory_call('sampled_noisy_loss_and_grad', model, inputs, y, noise, inv_batch_total, row0)
 
 
 def _device_noise(noise, who):
@@ -561,7 +555,7 @@ def _device_trajectory_call(who, model, inputs, y, device_noise, sampling, inv_b
     if B == 0:
         return grad, pred
     inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
-    call = _lib.model_loss_grad_noisy_device if desc.n_qubits <= 9 else _lib.model_loss_grad_noisy_device_lds
+    call, _ = _lib.device_sampled_grad_calls(desc.n_qubits)
     call(desc, branch, trunk, y, flat, device_noise.params(desc.n_qubits), sampling.params(), inv, grad, row0=int(row0),
          ham_diag=ham_diag, pred=pred)
     return grad, pred

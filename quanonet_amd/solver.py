@@ -14,6 +14,7 @@ reference's ``solvers/solver_pt.py`` (PTSolver) plus the data-parallel step the 
   as ``.pt`` + ``.npz`` with the reference's state_dict keys, final checkpoint, evaluate() with
   rel-L2 / MSE / MAE / max-error.  Training data stay resident on the device.
 """
+import collections
 import json
 import os
 import random
@@ -356,6 +357,34 @@ def _train_sampling(v, key='train_sampling'):
     raise ValueError(f"{key} must be a quanonet_amd.noise.Sampling or its asdict() form (got {type(v).__name__})")
 
 
+# The loss a DataParallelTrainer trains on, chosen once in __init__ by one function per family (_ideal_loss, _exact_loss,
+# _exact_device_loss, _sampled_loss, _jump_loss):
+#   loss_grad(data, inv, grad, step, row0, ham_diag)    behind loss_and_grad; data = (desc, branch, trunk, y, params), step the
+#                                                       Adam count of the update the gradient is for, row0 its first global row
+#   steps(call, ham_diag)                               behind _steps; call = a steps entry's arguments up to weight_decay
+#   single                                              one train_step on a single device: 'loss_grad+adam' (loss_grad under the
+#                                                       step's record, then the Adam launch), 'steps' (one step of the steps
+#                                                       entry) or 'train_step' (model_train_step)
+#   step_record(step)                                   the record of a sampled loss with seed + step (mod 2^64), or None: `step`
+#                                                       = 0 is the record the steps entry takes (it adds the step count itself)
+TrainLoss = collections.namedtuple('TrainLoss', 'loss_grad steps single step_record')
+
+
+def _exact_train_loss(loss_grad, steps, record):
+    """an exact noisy loss: its two calls with record() behind the data; the steps entry is its only fused step"""
+    return TrainLoss(lambda data, inv, grad, step, row0, ham_diag: loss_grad(*data, record(), inv, grad, ham_diag=ham_diag),
+                     lambda call, ham_diag: steps(*call, record(), ham_diag=ham_diag), 'steps', None)
+
+
+def _sampled_train_loss(loss_grad, steps, step_record):
+    """a sampled loss: its two calls with the step's record behind the data.  The steps entry reads a step's global rows off its
+    schedule; one step with rows of its own is the loop the entry is bitwise equal to: the single call under seed + step count,
+    then the Adam launch"""
+    return TrainLoss(lambda data, inv, grad, step, row0, ham_diag: loss_grad(*data, step_record(step), inv, grad, row0=row0,
+                                                                             ham_diag=ham_diag),
+                     lambda call, ham_diag: steps(*call, step_record(0), ham_diag=ham_diag), 'loss_grad+adam', step_record)
+
+
 class DataParallelTrainer:
     """
     fused='auto': when the model is one of this package's QuanONetPT / HEAQNNPT (fp64, on a HIP
@@ -466,137 +495,145 @@ class DataParallelTrainer:
                                                                          p0.device, log=log)
                 self.peer_fused = self.peer is not None and self.desc is not None
         self.device_sampled = self.train_sampling is not None and self.train_device_noise is not None
-        if self.device_sampled:
-            # the loss is the quantum-jump estimate under the device model (qhea_model_loss_grad_noisy_device at n = 7..9,
-            # ..._noisy_device_lds at n = 10..12)
-            key, nmax = self.sampling_key, 12 if self.sampling_key == 'train_jump_trajectories' else 9
-            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
-                raise ValueError(f"train_device_noise with {key} needs the fused model-level path (a fp64 QuanONetPT "
-                                 "/ HEAQNNPT on a HIP device, Adam with betas / eps / weight_decay only)")
-            from . import _lib
-            n = self.desc.n_qubits
-            if n <= 6:
-                raise ValueError(f"train_device_noise with {key}: quantum-jump training takes n = 7..{nmax} (this model: "
-                                 f"n = {n}); for n <= 6 train_device_noise alone trains on the exact loss under the device model")
-            if n > nmax:
-                raise ValueError(f"train_device_noise with {key}: quantum-jump training takes n = 7..9 under this key (this "
-                                 f"model: n = {n}); train_jump_trajectories is the key that trains n = 7..12 on quantum-jump "
-                                 "trajectories under the DeviceNoise")
-            try:
-                hit = _lib.device_noise_singular_site(n, self.train_device_noise.params(n))
-            except _lib.QheaError as e:
-                raise ValueError(f"train_device_noise: {e}") from e
-            if hit:
-                raise ValueError(f"train_device_noise with {key}: relaxation site {hit[0]} on wire {hit[1]} has "
-                                 "gamma = 1, which the trajectory gradient cannot walk back")
-            # the pair of calls for this qubit count: the wave-resident kernel at n = 7..9, the LDS-resident one at n = 10..12
-            call_loss_grad, call_steps = ((_lib.model_loss_grad_noisy_device, _lib.model_train_steps_noisy_device) if n <= 9 else
-                                          (_lib.model_loss_grad_noisy_device_lds, _lib.model_train_steps_noisy_device_lds))
+        # the loss the run trains on, chosen once: loss_and_grad, train_step and _steps go through this record
+        self.train_loss = (self._jump_loss(log) if self.device_sampled else
+                           self._sampled_loss(log) if self.train_sampling is not None else
+                           self._exact_loss(log) if self.train_noise is not None else
+                           self._exact_device_loss(log) if self.train_device_noise is not None else self._ideal_loss())
 
-            def loss_grad(desc, branch, trunk, y, params, sampling, inv, grad, row0=0, ham_diag=None):
-                return call_loss_grad(desc, branch, trunk, y, params, self.train_device_noise.params(n), sampling, inv, grad,
-                                      row0=row0, ham_diag=ham_diag)
-
-            def steps(*call, ham_diag=None):
-                *head, sampling = call
-                return call_steps(*head, self.train_device_noise.params(n), sampling, ham_diag=ham_diag)
-
-            self._sampled_loss_grad, self._sampled_steps = loss_grad, steps
-            if log is not None:
-                log("device-noise training: the loss and 'loss_train' are the quantum-jump estimate of the MSE under the "
-                    f"DeviceNoise of train_device_noise, {self.train_sampling.trajectories} trajectories per row, stream seed "
-                    f"{self.train_sampling.seed} + step count")
-        elif self.train_sampling is not None:
-            # the loss is the sampled noisy one (qhea_model_loss_grad_noisy_wide / _lds): refuse here what the call would refuse
-            key, nmax = self.sampling_key, 9 if self.sampling_key == 'train_sampling' else 12
-            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
-                raise ValueError(f"{key} needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
-                                 "Adam with betas / eps / weight_decay only)")
-            if not 7 <= self.desc.n_qubits <= nmax:
-                raise ValueError(f"{key}: sampled-trajectory training takes n = 7..{nmax} (this model: n = "
-                                 f"{self.desc.n_qubits}); for n <= 6 train_noise alone trains on the exact noisy loss")
-            from . import _lib
-            # the pair of calls for this qubit count: the wave-resident kernels at n = 7..9, the LDS-resident one at n = 10..12
-            self._sampled_loss_grad, self._sampled_steps = (
-                (_lib.model_loss_grad_noisy_wide, _lib.model_train_steps_noisy_wide) if self.desc.n_qubits <= 9 else
-                (_lib.model_loss_grad_noisy_lds, _lib.model_train_steps_noisy_lds))
-            if log is not None:
-                log(f"noise-aware training: the loss and 'loss_train' are the sampled noisy MSE under p1={self.train_noise.p1:g} "
-                    f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g}, {self.train_sampling.trajectories} "
-                    f"trajectories per row, stream seed {self.train_sampling.seed} + step count")
-        elif self.train_noise is not None:
-            # the loss is the exact noisy one (qhea_model_loss_grad_noisy_exact): refuse here what the call would refuse
-            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
-                raise ValueError("train_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
-                                 "Adam with betas / eps / weight_decay only)")
-            from . import _lib
-            amp = _lib.model_exact_noisy_log10_amplification(self.desc, self.train_noise.params())
-            if self.desc.n_qubits > 6 or not amp <= 12.0:
-                raise ValueError(f"train_noise: noise-aware training takes n <= 6 and log10 amplification <= 12 (this model: "
-                                 f"n = {self.desc.n_qubits}, {amp:.2f}); see quanonet_amd.noise.amplification")
-            if self.peer_fused:
-                self.peer_fused = False
-                self.dp_exchange_reason = ("peer exchange as a separate kernel: the noise-aware step has no reduce kernel with "
-                                           "the exchange inside")
-            if log is not None:
-                log(f"noise-aware training: the loss and 'loss_train' are the exact noisy MSE under p1={self.train_noise.p1:g} "
-                    f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g} (log10 amplification {amp:.2f})")
-
-        if self.train_device_noise is not None and not self.device_sampled:
-            # the loss is the exact one under the device model (qhea_model_loss_grad_noisy_device_exact): the same refusals
-            if self.desc is None or not isinstance(self.optimizer, FlatAdam):
-                raise ValueError("train_device_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP "
-                                 "device, Adam with betas / eps / weight_decay only)")
-            from . import _lib
-            n = self.desc.n_qubits
-            stored = self.noise_states == 'stored'
-            try:
-                rec = self.train_device_noise.params(n)
-                amp = _lib.model_device_noisy_log10_amplification(self.desc, rec)
-                # the library's own checks and bound
-                refused = (_lib.model_device_noisy_stored_refused if stored else _lib.model_device_noisy_refused)(self.desc, rec)
-                layer = _lib.model_device_noisy_log10_layer_amplification(self.desc, rec) if stored else None
-            except _lib.QheaError as e:
-                raise ValueError(f"train_device_noise: {e}") from e
-            if refused and stored:
-                raise ValueError(f"train_device_noise with train_noise_states='stored': the library refuses this model under "
-                                 f"this DeviceNoise (n = {n}, log10 amplification {amp:.2f}, of one layer {layer:.2f}): n <= 6 "
-                                 "and a layer amplification within the bound of include/quanonet_hea.h are needed; see "
-                                 "quanonet_amd.noise.device_layer_amplification")
-            if refused:
-                raise ValueError(f"train_device_noise: the library refuses this model under this DeviceNoise (n = {n}, log10 "
-                                 f"amplification {amp:.2f}): n <= 6 and a log10 amplification within the bound of "
-                                 "include/quanonet_hea.h are needed; see quanonet_amd.noise.device_amplification.  At "
-                                 "n = 7..9 train_trajectories beside train_device_noise trains on quantum-jump trajectories, "
-                                 "and train_jump_trajectories there does at n = 7..12")
-            if self.peer_fused:
-                self.peer_fused = False
-                self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
-                                           "with the exchange inside")
-            if log is not None:
-                log("device-noise training: the loss and 'loss_train' are the exact noisy MSE under the DeviceNoise of "
-                    f"train_device_noise (log10 amplification {amp:.2f})")
-                if stored:
-                    per_row = _lib.model_device_noisy_stored_grad_workspace_bytes(self.desc, 1, snapshots_only=True)
-                    log(f"device-noise training: rho is replayed from stored states (train_noise_states='stored'; log10 "
-                        f"amplification {amp:.2f} in total, {layer:.2f} for one layer, which is what the bound is asked of; "
-                        f"{per_row} snapshot bytes per row)")
-
-    def _noise_params(self):
-        """the noise record of the training loss as the C ABI takes it, or None (the ideal loss)"""
-        if self.train_device_noise is not None:
-            return self.train_device_noise.params(self.desc.n_qubits)
-        return None if self.train_noise is None else self.train_noise.params()
-
-    def _sampled_noise(self, step):
-        """train_noise's rates with train_sampling's trajectories and seed + step (mod 2^64): `step` = 0 is the record the
-        steps entry takes (it adds the step count itself), the Adam count that of one step's own call"""
-        tn, sp = self.train_noise, self.train_sampling
+    def _ideal_loss(self):
+        """the ideal loss (qhea_model_loss_grad / _train_step / _train_steps)"""
         from . import _lib
-        if self.device_sampled:                 # the device record travels beside it: the qhea_sampling of that step
-            return _lib.SamplingParams(0, int(sp.trajectories), (int(sp.seed) + int(step)) & ((1 << 64) - 1))
-        return _lib.NoiseParams(float(tn.p1), float(tn.p2), float(tn.readout), 0, int(sp.trajectories),
-                                (int(sp.seed) + int(step)) & ((1 << 64) - 1))
+        return TrainLoss(lambda data, inv, grad, step, row0, ham_diag: _lib.model_loss_grad(*data, inv, grad, ham_diag=ham_diag),
+                         lambda call, ham_diag: _lib.model_train_steps(*call, ham_diag=ham_diag), 'train_step', None)
+
+    def _jump_loss(self, log):
+        """train_device_noise with train_trajectories / train_jump_trajectories"""
+        # the loss is the quantum-jump estimate under the device model (qhea_model_loss_grad_noisy_device at n = 7..9,
+        # ..._noisy_device_lds at n = 10..12)
+        key, nmax = self.sampling_key, 12 if self.sampling_key == 'train_jump_trajectories' else 9
+        if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+            raise ValueError(f"train_device_noise with {key} needs the fused model-level path (a fp64 QuanONetPT "
+                             "/ HEAQNNPT on a HIP device, Adam with betas / eps / weight_decay only)")
+        from . import _lib
+        n = self.desc.n_qubits
+        if n <= 6:
+            raise ValueError(f"train_device_noise with {key}: quantum-jump training takes n = 7..{nmax} (this model: "
+                             f"n = {n}); for n <= 6 train_device_noise alone trains on the exact loss under the device model")
+        if n > nmax:
+            raise ValueError(f"train_device_noise with {key}: quantum-jump training takes n = 7..9 under this key (this "
+                             f"model: n = {n}); train_jump_trajectories is the key that trains n = 7..12 on quantum-jump "
+                             "trajectories under the DeviceNoise")
+        try:
+            hit = _lib.device_noise_singular_site(n, self.train_device_noise.params(n))
+        except _lib.QheaError as e:
+            raise ValueError(f"train_device_noise: {e}") from e
+        if hit:
+            raise ValueError(f"train_device_noise with {key}: relaxation site {hit[0]} on wire {hit[1]} has "
+                             "gamma = 1, which the trajectory gradient cannot walk back")
+        # the pair of calls for this qubit count: the wave-resident kernel at n = 7..9, the LDS-resident one at n = 10..12
+        call_loss_grad, call_steps = _lib.device_sampled_grad_calls(n)
+
+        def loss_grad(desc, branch, trunk, y, params, sampling, inv, grad, row0=0, ham_diag=None):
+            return call_loss_grad(desc, branch, trunk, y, params, self.train_device_noise.params(n), sampling, inv, grad,
+                                  row0=row0, ham_diag=ham_diag)
+
+        def steps(*call, ham_diag=None):
+            *head, sampling = call
+            return call_steps(*head, self.train_device_noise.params(n), sampling, ham_diag=ham_diag)
+
+        step_record = lambda step: _lib.SamplingParams(0, int(self.train_sampling.trajectories),
+                                                       (int(self.train_sampling.seed) + int(step)) & ((1 << 64) - 1))
+        if log is not None:
+            log("device-noise training: the loss and 'loss_train' are the quantum-jump estimate of the MSE under the "
+                f"DeviceNoise of train_device_noise, {self.train_sampling.trajectories} trajectories per row, stream seed "
+                f"{self.train_sampling.seed} + step count")
+        return _sampled_train_loss(loss_grad, steps, step_record)
+
+    def _sampled_loss(self, log):
+        """train_noise with train_sampling / train_trajectories"""
+        # the loss is the sampled noisy one (qhea_model_loss_grad_noisy_wide / _lds): refuse here what the call would refuse
+        key, nmax = self.sampling_key, 9 if self.sampling_key == 'train_sampling' else 12
+        if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+            raise ValueError(f"{key} needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
+                             "Adam with betas / eps / weight_decay only)")
+        if not 7 <= self.desc.n_qubits <= nmax:
+            raise ValueError(f"{key}: sampled-trajectory training takes n = 7..{nmax} (this model: n = "
+                             f"{self.desc.n_qubits}); for n <= 6 train_noise alone trains on the exact noisy loss")
+        from . import _lib
+        tn, sp = self.train_noise, self.train_sampling
+        # train_noise's rates with train_sampling's trajectories and seed + step (mod 2^64)
+        step_record = lambda step: _lib.NoiseParams(float(tn.p1), float(tn.p2), float(tn.readout), 0, int(sp.trajectories),
+                                                    (int(sp.seed) + int(step)) & ((1 << 64) - 1))
+        if log is not None:
+            log(f"noise-aware training: the loss and 'loss_train' are the sampled noisy MSE under p1={self.train_noise.p1:g} "
+                f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g}, {self.train_sampling.trajectories} "
+                f"trajectories per row, stream seed {self.train_sampling.seed} + step count")
+        return _sampled_train_loss(*_lib.sampled_grad_calls(self.desc.n_qubits), step_record)
+
+    def _exact_loss(self, log):
+        """train_noise alone"""
+        # the loss is the exact noisy one (qhea_model_loss_grad_noisy_exact): refuse here what the call would refuse
+        if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+            raise ValueError("train_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
+                             "Adam with betas / eps / weight_decay only)")
+        from . import _lib
+        amp = _lib.model_exact_noisy_log10_amplification(self.desc, self.train_noise.params())
+        if self.desc.n_qubits > 6 or not amp <= 12.0:
+            raise ValueError(f"train_noise: noise-aware training takes n <= 6 and log10 amplification <= 12 (this model: "
+                             f"n = {self.desc.n_qubits}, {amp:.2f}); see quanonet_amd.noise.amplification")
+        if self.peer_fused:
+            self.peer_fused = False
+            self.dp_exchange_reason = ("peer exchange as a separate kernel: the noise-aware step has no reduce kernel with "
+                                       "the exchange inside")
+        if log is not None:
+            log(f"noise-aware training: the loss and 'loss_train' are the exact noisy MSE under p1={self.train_noise.p1:g} "
+                f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g} (log10 amplification {amp:.2f})")
+        return _exact_train_loss(_lib.model_loss_grad_noisy_exact, _lib.model_train_steps_noisy_exact, self.train_noise.params)
+
+    def _exact_device_loss(self, log):
+        """train_device_noise alone, rho walked back through inverses or replayed from stored states (train_noise_states)"""
+        # the loss is the exact one under the device model (qhea_model_loss_grad_noisy_device_exact): the same refusals
+        if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+            raise ValueError("train_device_noise needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP "
+                             "device, Adam with betas / eps / weight_decay only)")
+        from . import _lib
+        n = self.desc.n_qubits
+        stored = self.noise_states == 'stored'
+        try:
+            rec = self.train_device_noise.params(n)
+            amp = _lib.model_device_noisy_log10_amplification(self.desc, rec)
+            # the library's own checks and bound
+            refused = (_lib.model_device_noisy_stored_refused if stored else _lib.model_device_noisy_refused)(self.desc, rec)
+            layer = _lib.model_device_noisy_log10_layer_amplification(self.desc, rec) if stored else None
+        except _lib.QheaError as e:
+            raise ValueError(f"train_device_noise: {e}") from e
+        if refused and stored:
+            raise ValueError(f"train_device_noise with train_noise_states='stored': the library refuses this model under "
+                             f"this DeviceNoise (n = {n}, log10 amplification {amp:.2f}, of one layer {layer:.2f}): n <= 6 "
+                             "and a layer amplification within the bound of include/quanonet_hea.h are needed; see "
+                             "quanonet_amd.noise.device_layer_amplification")
+        if refused:
+            raise ValueError(f"train_device_noise: the library refuses this model under this DeviceNoise (n = {n}, log10 "
+                             f"amplification {amp:.2f}): n <= 6 and a log10 amplification within the bound of "
+                             "include/quanonet_hea.h are needed; see quanonet_amd.noise.device_amplification.  At "
+                             "n = 7..9 train_trajectories beside train_device_noise trains on quantum-jump trajectories, "
+                             "and train_jump_trajectories there does at n = 7..12")
+        if self.peer_fused:
+            self.peer_fused = False
+            self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
+                                       "with the exchange inside")
+        if log is not None:
+            log("device-noise training: the loss and 'loss_train' are the exact noisy MSE under the DeviceNoise of "
+                f"train_device_noise (log10 amplification {amp:.2f})")
+            if stored:
+                per_row = _lib.model_device_noisy_stored_grad_workspace_bytes(self.desc, 1, snapshots_only=True)
+                log(f"device-noise training: rho is replayed from stored states (train_noise_states='stored'; log10 "
+                    f"amplification {amp:.2f} in total, {layer:.2f} for one layer, which is what the bound is asked of; "
+                    f"{per_row} snapshot bytes per row)")
+        calls = ((_lib.model_loss_grad_noisy_device_exact_stored, _lib.model_train_steps_noisy_device_exact_stored) if stored else
+                 (_lib.model_loss_grad_noisy_device_exact, _lib.model_train_steps_noisy_device_exact))
+        return _exact_train_loss(*calls, lambda: self.train_device_noise.params(n))
 
     def broadcast_parameters(self):
         self.dist.broadcast(self.pflat, src=0)
@@ -622,20 +659,10 @@ class DataParallelTrainer:
         *inputs, y = batch
         gb = float(global_batch if global_batch is not None else y.shape[0] * self.world)
         if self.desc is not None:
-            from . import _lib
             data = (self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat)
             grad = self.flat if out is None else out
-            if self.train_sampling is not None:          # (the stream of the NEXT update, global rows from 0)
-                self._sampled_loss_grad(*data, self._sampled_noise(self.optimizer.t + 1), 1.0 / gb, grad,
-                                        ham_diag=self._ham_diag())
-            elif self.train_device_noise is not None:
-                call = (_lib.model_loss_grad_noisy_device_exact_stored if self.noise_states == 'stored' else
-                        _lib.model_loss_grad_noisy_device_exact)
-                call(*data, self._noise_params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
-            elif self.train_noise is not None:
-                _lib.model_loss_grad_noisy_exact(*data, self.train_noise.params(), 1.0 / gb, grad, ham_diag=self._ham_diag())
-            else:
-                _lib.model_loss_grad(*data, 1.0 / gb, grad, ham_diag=self._ham_diag())
+            # (a sampled loss: the stream of the NEXT update, global rows from 0)
+            self.train_loss.loss_grad(data, 1.0 / gb, grad, self.optimizer.t + 1, 0, self._ham_diag())
         else:
             self.flat.zero_()
             pred = self._forward(inputs)
@@ -663,14 +690,11 @@ class DataParallelTrainer:
             gb = float(global_batch if global_batch is not None else y.shape[0])
             opt = self.optimizer
             opt.t += 1
-            if self.train_sampling is not None:
-                # the steps entry reads a step's global rows off its schedule; one step with rows of its own is the loop the
-                # entry is bitwise equal to: the single call under seed + step count, then the Adam launch
-                self._sampled_loss_grad(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat,
-                                        self._sampled_noise(opt.t), 1.0 / gb, flat, row0=int(row0),
-                                        ham_diag=self._ham_diag())
+            if self.train_loss.single == 'loss_grad+adam':
+                self.train_loss.loss_grad((self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat), 1.0 / gb, flat, opt.t,
+                                          int(row0), self._ham_diag())
                 _lib.adam_step(self.pflat, flat, opt.exp_avg, opt.exp_avg_sq, opt.t, *opt.hparams())
-            elif self._noise_params() is not None:          # (the noise-aware paths have the steps entry only: one step of it)
+            elif self.train_loss.single == 'steps':         # (the exact noisy losses have the steps entry only: one step of it)
                 self._steps(inputs, y, [0, y.shape[0]], [gb], flat.view(1, -1), opt.t)
             else:
                 _lib.model_train_step(self.desc, *split_inputs(inputs), y.reshape(-1), self.pflat, 1.0 / gb, flat, opt.exp_avg,
@@ -705,20 +729,10 @@ class DataParallelTrainer:
         """single device: the steps entry, ideal (qhea_model_train_steps), under train_noise (..._noisy_exact; with
         train_sampling / train_trajectories ..._noisy_wide or ..._noisy_lds) or under train_device_noise
         (..._noisy_device_exact, with train_noise_states='stored' ..._noisy_device_exact_stored)"""
-        from . import _lib
         opt = self.optimizer
         call = (self.desc, bounds, global_batches, *split_inputs(inputs), y.reshape(-1), self.pflat, rows, opt.exp_avg,
                 opt.exp_avg_sq, first_step, *opt.hparams())
-        if self.train_sampling is not None:
-            self._sampled_steps(*call, self._sampled_noise(0), ham_diag=self._ham_diag())
-        elif self.train_device_noise is not None:
-            steps = (_lib.model_train_steps_noisy_device_exact_stored if self.noise_states == 'stored' else
-                     _lib.model_train_steps_noisy_device_exact)
-            steps(*call, self._noise_params(), ham_diag=self._ham_diag())
-        elif self.train_noise is not None:
-            _lib.model_train_steps_noisy_exact(*call, self.train_noise.params(), ham_diag=self._ham_diag())
-        else:
-            _lib.model_train_steps(*call, ham_diag=self._ham_diag())
+        self.train_loss.steps(call, self._ham_diag())
 
     def _dp_steps(self, inputs, y, bounds, global_batches, rows):
         from . import _lib
