@@ -101,36 +101,43 @@ def _ops(n, cfgs):
     return ops
 
 
-def value_table(n, readout, offset=0.0, coeff=1.0, ham_diag=None):
+def value_table(n, readout, offset=0.0, coeff=1.0, ham_diag=None, dtype=np.complex128):
     """h'[k]: the read value of bitstring k, mixed over the readout flips"""
+    real = DR.real_of(dtype)
+    readout = real(readout)
     D = 1 << n
     kk = np.arange(D)
     if ham_diag is not None:
-        hv = np.asarray(ham_diag, np.float64)
+        hv = np.asarray(ham_diag, np.float64).astype(real)
     else:
-        hv = offset + coeff * (n - 2.0 * sum((kk >> i) & 1 for i in range(n)))
-    conf = np.ones((D, D))
+        hv = real(offset) + real(coeff) * (n - 2.0 * sum((kk >> i) & 1 for i in range(n)))
+    conf = np.ones((D, D), dtype=real)
     for i in range(n):
         diff = ((kk[:, None] ^ kk[None, :]) >> i) & 1
         conf *= np.where(diff, readout, 1.0 - readout)
     return conf @ hv
 
 
-def circuit_grad(n, cfgs, x, w, p1, p2, readout, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', inverse=False):
+def circuit_grad(n, cfgs, x, w, p1, p2, readout, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', inverse=False,
+                 dtype=np.complex128):
     """
     (value[B], d value / d x [B, E], d value / d w [B, blk, 3, n]) of the exact noisy expectation (no bias).
     inverse=False: rho after every rotation is kept from the forward sweep; True: rho is walked back through inverse channels.
+    dtype: np.complex128, or np.clongdouble for the walk in extended precision (density_reference.real_of); the results come
+    back in its real type.
     """
     pauli = O._check_pauli(ham_pauli, ham_diag)
-    x = np.asarray(x, np.float64)
-    w = np.asarray(w, np.float64)
+    real = DR.real_of(dtype)
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
+    p1, p2, sq = real(p1), real(p2), DR.sq_of(dtype)
     B = x.shape[0]
     ops = _ops(n, cfgs)
 
     def angle(key):
         return x[:, key[1]] if key[0] == 'x' else np.full(B, w[key[1], key[2], key[3]])
 
-    rho = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     rho[(slice(None),) + (0,) * (2 * n)] = 1.0
     keep = {}
     for k, op in enumerate(ops):
@@ -143,17 +150,17 @@ def circuit_grad(n, cfgs, x, w, p1, p2, readout, offset=0.0, coeff=1.0, ham_diag
             if not inverse:
                 keep[k] = rho
     # O_N = B^dagger diag(h') B
-    hv = value_table(n, readout, offset, coeff, ham_diag)
-    obs = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    hv = value_table(n, readout, offset, coeff, ham_diag, dtype)
+    obs = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     obs.reshape(B, 1 << n, 1 << n)[:, np.arange(1 << n), np.arange(1 << n)] = hv
     if pauli != 'Z':
         for q in range(n):
-            obs = DR._gate(obs, n, q, (DR.SQ, DR.SQ, DR.SQ, -DR.SQ))                 # H is its own dagger
+            obs = DR._gate(obs, n, q, (sq, sq, sq, -sq))                             # H is its own dagger
             if pauli == 'Y':
                 obs = DR._gate(obs, n, q, (1.0, 0.0, 0.0, 1j))                       # S = (S^dagger)^dagger
     value = np.real(_trace(obs, rho, n))
-    gx = np.zeros((B, x.shape[1]))
-    gw = np.zeros((B,) + w.shape)
+    gx = np.zeros((B, x.shape[1]), dtype=real)
+    gw = np.zeros((B,) + w.shape, dtype=real)
     for k in range(len(ops) - 1, -1, -1):
         op = ops[k]
         if op[0] == 'd1':
@@ -203,19 +210,22 @@ def spec_of(model):
                 ham_pauli=('Z', 'X', 'Y')[q.ham_pauli])
 
 
-def _tiled(v, cols):
-    v = np.asarray(v, np.float64)
+def _tiled(v, cols, real=np.float64):
+    v = np.asarray(v, np.float64).astype(real)
     return np.tile(v, (1, -(-cols // v.shape[1])))[:, :cols]
 
 
-def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_total, inverse=False):
+def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_total, inverse=False, dtype=np.complex128):
     """
     ([P + 2] buffer, pred[B]) of the header's qhea_model_loss_grad_noisy_exact: gradients of sum_b (pred_b - y_b)^2 *
-    inv_batch_total in the flat parameter layout, then sum (pred - y)^2 and sum y^2.
+    inv_batch_total in the flat parameter layout, then sum (pred - y)^2 and sum y^2.  dtype: as in circuit_grad; with
+    np.clongdouble the frequency layers, the bias, the residual, the sums and the chain rule are done in the wide type too.
     """
     n, net = spec['n'], spec['net']
-    flat = np.asarray(flat, np.float64)
-    y = np.asarray(y, np.float64).reshape(-1)
+    real = DR.real_of(dtype)
+    flat = np.asarray(flat, np.float64).astype(real)
+    y = np.asarray(y, np.float64).reshape(-1).astype(real)
+    inv_batch_total = real(inv_batch_total)
     quanonet = spec['kind'] == 'quanonet'
     if quanonet:
         cfgs = O.block_configs_quanonet(n, net)
@@ -236,20 +246,20 @@ def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_tot
     assert flat.size == P, (flat.size, P)
     xs, tiles = [], []
     for name, v, cols in segs:
-        t = _tiled(v, cols)
+        t = _tiled(v, cols, real)
         tiles.append(t)
         if spec['trainable']:
             ow, ob = off[name]
             xs.append(t * flat[ow:ow + cols] + flat[ob:ob + cols])
         else:
-            xs.append(t * spec['scale'])
+            xs.append(t * real(spec['scale']))
     x = np.concatenate(xs, axis=1)
     w = flat[off_ans:].reshape(blk, 3, n)
     value, gx, gw = circuit_grad(n, cfgs, x, w, p1, p2, readout, spec['offset'], spec['coeff'], spec['ham_diag'],
-                                 spec['ham_pauli'], inverse=inverse)
+                                 spec['ham_pauli'], inverse=inverse, dtype=dtype)
     pred = value + (flat[0] if quanonet else 0.0)
     g = 2.0 * (pred - y) * inv_batch_total
-    out = np.zeros(P + 2)
+    out = np.zeros(P + 2, dtype=real)
     if quanonet:
         out[0] = g.sum()
     out[off_ans:P] = np.einsum('b,bskq->skq', g, gw).reshape(-1)

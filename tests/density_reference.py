@@ -19,6 +19,19 @@ from oracle import hea_oracle as O
 SQ = 1.0 / np.sqrt(2.0)
 
 
+def real_of(dtype):
+    """the real scalar type of a complex dtype (np.complex128 -> np.float64, np.clongdouble -> np.longdouble).  Every routine
+    here and in the gradient helpers takes dtype=np.complex128 by default; with np.clongdouble the inputs stay the float64 data
+    they are and everything computed from them -- half angles, sin / cos / exp, channel coefficients, sums -- is done in the
+    wide type (tests/density_precision_cases.py)."""
+    return np.finfo(dtype).dtype.type
+
+
+def sq_of(dtype):
+    """1 / sqrt 2 in the real type of dtype (SQ for complex128)"""
+    return 1.0 / np.sqrt(real_of(dtype)(2.0))
+
+
 def _row_axis(n, q):
     return 1 + (n - 1 - q)
 
@@ -30,7 +43,7 @@ def _col_axis(n, q):
 def _gate(rho, n, q, m):
     """rho <- M_q rho M_q^dagger; m = (m00, m01, m10, m11), each a scalar or a (B,) array"""
     B = rho.shape[0]
-    u = np.empty((B, 2, 2), dtype=np.complex128)
+    u = np.empty((B, 2, 2), dtype=rho.dtype)
     u[:, 0, 0], u[:, 0, 1], u[:, 1, 0], u[:, 1, 1] = m
     r = np.moveaxis(rho, _row_axis(n, q), 1)
     r = np.einsum('bij,bj...->bi...', u, r)
@@ -69,12 +82,14 @@ def _cnot_depolarize2(rho, n, c, t, p):
     return np.moveaxis(r, (1, 2, 3, 4), axes)
 
 
-def final_rho(n, cfgs, x, w, p1, p2, ham_pauli='Z'):
+def final_rho(n, cfgs, x, w, p1, p2, ham_pauli='Z', dtype=np.complex128):
     """rho[B, D, D] after the circuit, its channels and the noiseless basis change of the X / Y read-outs"""
-    x = np.asarray(x, np.float64)
-    w = np.asarray(w, np.float64)
+    real = real_of(dtype)
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
+    p1, p2, sq = real(p1), real(p2), sq_of(dtype)
     B, D = x.shape[0], 1 << n
-    rho = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     rho[(slice(None),) + (0,) * (2 * n)] = 1.0
     col, s = 0, 0
     for n_enc, ld in cfgs:
@@ -100,27 +115,29 @@ def final_rho(n, cfgs, x, w, p1, p2, ham_pauli='Z'):
         for q in range(n):
             if ham_pauli == 'Y':
                 rho = _gate(rho, n, q, (1.0, 0.0, 0.0, -1j))
-            rho = _gate(rho, n, q, (SQ, SQ, SQ, -SQ))
+            rho = _gate(rho, n, q, (sq, sq, sq, -sq))
     return np.ascontiguousarray(rho).reshape(B, D, D)
 
 
-def exact_moments(n, cfgs, x, w, p1, p2, readout, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z'):
+def exact_moments(n, cfgs, x, w, p1, p2, readout, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', dtype=np.complex128):
     """(mean, var) per row, no bias: the exact expectation of a read value and the variance of one shot's value"""
     pauli = O._check_pauli(ham_pauli, ham_diag)
-    rho = final_rho(n, cfgs, x, w, float(p1), float(p2), pauli)
+    real = real_of(dtype)
+    rho = final_rho(n, cfgs, x, w, float(p1), float(p2), pauli, dtype)
+    readout = real(readout)
     D = 1 << n
     prob = np.real(np.einsum('bkk->bk', rho))
     kk = np.arange(D)
-    conf = np.ones((D, D))
+    conf = np.ones((D, D), dtype=real)
     for i in range(n):
         diff = ((kk[:, None] ^ kk[None, :]) >> i) & 1
         conf *= np.where(diff, readout, 1.0 - readout)
     pread = prob @ conf
     if ham_diag is not None:
-        hv = np.asarray(ham_diag, np.float64)
+        hv = np.asarray(ham_diag, np.float64).astype(real)
     else:
         pop = sum((kk >> i) & 1 for i in range(n))
-        hv = offset + coeff * (n - 2.0 * pop)
+        hv = real(offset) + real(coeff) * (n - 2.0 * pop)
     mean = pread @ hv
     var = pread @ (hv * hv) - mean ** 2
     return mean, var

@@ -27,8 +27,9 @@ def _pairs():
     return [np.kron(a, b) for a in (DNR.I2,) + DNR.PAULIS for b in (DNR.I2,) + DNR.PAULIS]
 
 
-def depolarizing2_kraus(p):
+def depolarizing2_kraus(p, dtype=np.complex128):
     """on (control, target): identity with weight 1 - p, each of the 15 other Pauli pairs p / 15"""
+    p = DR.real_of(dtype)(p)
     ks = _pairs()
     return [np.sqrt(1.0 - p) * ks[0]] + [np.sqrt(p / 15.0) * k for k in ks[1:]]
 
@@ -54,20 +55,20 @@ def _inverse_on(rho, n, wires, kraus):
     return _superoperator_on(rho, n, wires, np.linalg.inv(sum(np.kron(K, K.conj()) for K in kraus)))
 
 
-def _relax_kraus(t, T1, T2):
+def _relax_kraus(t, T1, T2, dtype=np.complex128):
     """amplitude damping then phase damping as one Kraus set (the products)"""
-    return [P @ A for P in DNR.phase_damping_kraus(t, T1, T2) for A in DNR.amplitude_damping_kraus(t, T1)]
+    return [P @ A for P in DNR.phase_damping_kraus(t, T1, T2, dtype) for A in DNR.amplitude_damping_kraus(t, T1, dtype)]
 
 
-def _ops(n, cfgs, nz):
+def _ops(n, cfgs, nz, dtype=np.complex128):
     """the timeline as a list: ('x' | 'y' | 'z', wire, angle key), ('ch', wires, kraus), ('cnot', control, target)"""
     ops, col, s = [], 0, 0
 
     def relax(q, t):
-        return [('ch', (q,), _relax_kraus(t, nz['t1'][q], nz['t2'][q]))] if t != 0.0 else []
+        return [('ch', (q,), _relax_kraus(t, nz['t1'][q], nz['t2'][q], dtype))] if t != 0.0 else []
 
     def dep1(q):
-        return [('ch', (q,), DNR.depolarizing_kraus(nz['p1'][q]))] if nz['p1'][q] != 0.0 else []
+        return [('ch', (q,), DNR.depolarizing_kraus(nz['p1'][q], dtype))] if nz['p1'][q] != 0.0 else []
 
     for n_enc, ld in cfgs:
         assert n_enc == n
@@ -82,7 +83,7 @@ def _ops(n, cfgs, nz):
                 ctl, tgt = (j + 1) % n, j
                 ops.append(('cnot', ctl, tgt))
                 if nz['p2'][j] != 0.0:
-                    ops.append(('ch', (ctl, tgt), depolarizing2_kraus(nz['p2'][j])))
+                    ops.append(('ch', (ctl, tgt), depolarizing2_kraus(nz['p2'][j], dtype)))
                 for q in range(n):
                     if q in (ctl, tgt) or nz['idle']:
                         ops += relax(q, nz['t_cx'])
@@ -90,28 +91,34 @@ def _ops(n, cfgs, nz):
     return ops
 
 
-def value_table(n, nz, offset=0.0, coeff=1.0, ham_diag=None):
+def value_table(n, nz, offset=0.0, coeff=1.0, ham_diag=None, dtype=np.complex128):
     """h'[k] = sum_k' P(read k' | true k) h[k']: the expected read value of the true bitstring k"""
-    hv = DNR.value_table(n, offset, coeff, ham_diag)
-    eye = np.eye(1 << n)
+    real = DR.real_of(dtype)
+    hv = DNR.value_table(n, offset, coeff, ham_diag, real)
+    eye = np.eye(1 << n, dtype=real)
     return DNR.confuse(eye, n, nz['readout01'], nz['readout10']) @ hv
 
 
-def circuit_grad(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', inverse=False):
+def circuit_grad(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', inverse=False, dtype=np.complex128):
     """
     (value[B], d value / d x [B, E], d value / d w [B, blk, 3, n]) of the exact expectation under the device noise (no bias).
     inverse=False: rho after every rotation is kept from the forward sweep; True: rho is walked back through inverse channels.
+    dtype: np.complex128, or np.clongdouble for the stored walk in extended precision (density_reference.real_of; the inverse
+    walk inverts its superoperators with LAPACK and stays fp64); the results come back in its real type.
     """
     pauli = O._check_pauli(ham_pauli, ham_diag)
-    x = np.asarray(x, np.float64)
-    w = np.asarray(w, np.float64)
+    assert not inverse or np.dtype(dtype) == np.complex128, 'the inverse walk is fp64 only'
+    real = DR.real_of(dtype)
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
+    sq = DR.sq_of(dtype)
     B = x.shape[0]
-    ops = _ops(n, cfgs, nz)
+    ops = _ops(n, cfgs, nz, dtype)
 
     def angle(key):
         return x[:, key[1]] if key[0] == 'x' else np.full(B, w[key[1], key[2], key[3]])
 
-    rho = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     rho[(slice(None),) + (0,) * (2 * n)] = 1.0
     keep = {}
     for k, op in enumerate(ops):
@@ -123,17 +130,17 @@ def circuit_grad(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pa
             rho = DR._gate(rho, n, op[1], DGR._rot(op[0], angle(op[2])))
             if not inverse:
                 keep[k] = rho
-    hv = value_table(n, nz, offset, coeff, ham_diag)
-    obs = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    hv = value_table(n, nz, offset, coeff, ham_diag, dtype)
+    obs = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     obs.reshape(B, 1 << n, 1 << n)[:, np.arange(1 << n), np.arange(1 << n)] = hv
     if pauli != 'Z':
         for q in range(n):
-            obs = DR._gate(obs, n, q, (DR.SQ, DR.SQ, DR.SQ, -DR.SQ))                 # H is its own dagger
+            obs = DR._gate(obs, n, q, (sq, sq, sq, -sq))                             # H is its own dagger
             if pauli == 'Y':
                 obs = DR._gate(obs, n, q, (1.0, 0.0, 0.0, 1j))                       # S = (S^dagger)^dagger
     value = np.real(DGR._trace(obs, rho, n))
-    gx = np.zeros((B, x.shape[1]))
-    gw = np.zeros((B,) + w.shape)
+    gx = np.zeros((B, x.shape[1]), dtype=real)
+    gw = np.zeros((B,) + w.shape, dtype=real)
     for k in range(len(ops) - 1, -1, -1):
         op = ops[k]
         if op[0] == 'ch':
@@ -182,15 +189,18 @@ def shift_grad(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_paul
     return value, gx, gw
 
 
-def model_loss_grad(spec, flat, branch, trunk, y, nz, inv_batch_total, inverse=False, circuit=None):
+def model_loss_grad(spec, flat, branch, trunk, y, nz, inv_batch_total, inverse=False, circuit=None, dtype=np.complex128):
     """
     ([P + 2] buffer, pred[B]) of the header's qhea_model_loss_grad_noisy_device_exact: gradients of sum_b (pred_b - y_b)^2 *
     inv_batch_total in the flat parameter layout, then sum (pred - y)^2 and sum y^2.  spec: density_grad_reference.spec_of.
-    circuit: circuit_grad (default, with `inverse`) or shift_grad.
+    circuit: circuit_grad (default, with `inverse` and `dtype`) or shift_grad (fp64).  dtype: as in circuit_grad; with
+    np.clongdouble the model around the circuit is done in the wide type too.
     """
     n, net = spec['n'], spec['net']
-    flat = np.asarray(flat, np.float64)
-    y = np.asarray(y, np.float64).reshape(-1)
+    real = DR.real_of(dtype)
+    flat = np.asarray(flat, np.float64).astype(real)
+    y = np.asarray(y, np.float64).reshape(-1).astype(real)
+    inv_batch_total = real(inv_batch_total)
     quanonet = spec['kind'] == 'quanonet'
     if quanonet:
         cfgs = O.block_configs_quanonet(n, net)
@@ -211,23 +221,23 @@ def model_loss_grad(spec, flat, branch, trunk, y, nz, inv_batch_total, inverse=F
     assert flat.size == P, (flat.size, P)
     xs, tiles = [], []
     for name, v, cols in segs:
-        t = DGR._tiled(v, cols)
+        t = DGR._tiled(v, cols, real)
         tiles.append(t)
         if spec['trainable']:
             ow, ob = off[name]
             xs.append(t * flat[ow:ow + cols] + flat[ob:ob + cols])
         else:
-            xs.append(t * spec['scale'])
+            xs.append(t * real(spec['scale']))
     x = np.concatenate(xs, axis=1)
     w = flat[off_ans:].reshape(blk, 3, n)
     if circuit is None:
         value, gx, gw = circuit_grad(n, cfgs, x, w, nz, spec['offset'], spec['coeff'], spec['ham_diag'], spec['ham_pauli'],
-                                     inverse=inverse)
+                                     inverse=inverse, dtype=dtype)
     else:
         value, gx, gw = circuit(n, cfgs, x, w, nz, spec['offset'], spec['coeff'], spec['ham_diag'], spec['ham_pauli'])
     pred = value + (flat[0] if quanonet else 0.0)
     g = 2.0 * (pred - y) * inv_batch_total
-    out = np.zeros(P + 2)
+    out = np.zeros(P + 2, dtype=real)
     if quanonet:
         out[0] = g.sum()
     out[off_ans:P] = np.einsum('b,bskq->skq', g, gw).reshape(-1)

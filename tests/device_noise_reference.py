@@ -21,22 +21,29 @@ PZ = np.array([[1, 0], [0, -1]], dtype=np.complex128)
 PAULIS = (PX, PY, PZ)
 
 
-def amplitude_damping_kraus(t, T1):
-    gamma = 1.0 - np.exp(-t / T1) if np.isfinite(T1) else 0.0
-    return [np.array([[1, 0], [0, np.sqrt(1.0 - gamma)]], dtype=np.complex128),
-            np.array([[0, np.sqrt(gamma)], [0, 0]], dtype=np.complex128)]
+def amplitude_damping_kraus(t, T1, dtype=np.complex128):
+    """dtype (here and below): the operators' type; t, T1, T2 and p are float64 data, what is computed from them -- gamma, the
+    factors, the square roots -- is computed in its real type (density_reference.real_of)"""
+    real = DR.real_of(dtype)
+    t, T1 = real(t), real(T1)
+    gamma = 1.0 - np.exp(-t / T1) if np.isfinite(T1) else real(0.0)
+    return [np.array([[1, 0], [0, np.sqrt(1.0 - gamma)]], dtype=dtype),
+            np.array([[0, np.sqrt(gamma)], [0, 0]], dtype=dtype)]
 
 
-def phase_damping_kraus(t, T1, T2):
+def phase_damping_kraus(t, T1, T2, dtype=np.complex128):
     """pure dephasing on top of amplitude damping: the off-diagonals end at exp(-t / T2) in total"""
-    gamma = 1.0 - np.exp(-t / T1) if np.isfinite(T1) else 0.0
-    total = np.exp(-t / T2) if np.isfinite(T2) else 1.0
-    f = total / np.sqrt(1.0 - gamma) if gamma < 1.0 else 0.0
-    f = min(f, 1.0)                                                      # T2 = 2 T1 to rounding
+    real = DR.real_of(dtype)
+    t, T1, T2 = real(t), real(T1), real(T2)
+    gamma = 1.0 - np.exp(-t / T1) if np.isfinite(T1) else real(0.0)
+    total = np.exp(-t / T2) if np.isfinite(T2) else real(1.0)
+    f = total / np.sqrt(1.0 - gamma) if gamma < 1.0 else real(0.0)
+    f = min(f, real(1.0))                                                # T2 = 2 T1 to rounding
     return [np.sqrt((1.0 + f) / 2.0) * I2, np.sqrt((1.0 - f) / 2.0) * PZ]
 
 
-def depolarizing_kraus(p):
+def depolarizing_kraus(p, dtype=np.complex128):
+    p = DR.real_of(dtype)(p)
     return [np.sqrt(1.0 - p) * I2] + [np.sqrt(p / 3.0) * P for P in PAULIS]
 
 
@@ -64,7 +71,7 @@ def triple_of(channel):
 def _unitary(rho, n, q, m):
     """U rho U^dagger on wire q; m = (u00, u01, u10, u11), each a scalar or one value per row"""
     B = rho.shape[0]
-    u = np.empty((B, 2, 2), dtype=np.complex128)
+    u = np.empty((B, 2, 2), dtype=rho.dtype)
     u[:, 0, 0], u[:, 0, 1], u[:, 1, 0], u[:, 1, 1] = m
     for ax, mat in ((DR._row_axis(n, q), u), (DR._col_axis(n, q), np.conj(u))):
         r = np.moveaxis(rho, ax, 1)
@@ -90,13 +97,14 @@ _pauli = _op
 def _relax(rho, n, q, t, nz):
     if t == 0.0:
         return rho
-    rho = _kraus(rho, n, q, amplitude_damping_kraus(t, nz['t1'][q]))
-    return _kraus(rho, n, q, phase_damping_kraus(t, nz['t1'][q], nz['t2'][q]))
+    rho = _kraus(rho, n, q, amplitude_damping_kraus(t, nz['t1'][q], rho.dtype))
+    return _kraus(rho, n, q, phase_damping_kraus(t, nz['t1'][q], nz['t2'][q], rho.dtype))
 
 
 def _depolarize1(rho, n, q, p):
     if p == 0.0:
         return rho
+    p = DR.real_of(rho.dtype)(p)
     return (1.0 - p) * rho + (p / 3.0) * sum(_pauli(rho, n, q, P) for P in PAULIS)
 
 
@@ -104,18 +112,21 @@ def _depolarize2(rho, n, c, t, p):
     """(1 - p) rho + p / 15 sum over the 15 non-identity pairs: the sum over all 16 pairs, wire by wire, minus the identity's term"""
     if p == 0.0:
         return rho
+    p = DR.real_of(rho.dtype)(p)
     over_t = rho + sum(_pauli(rho, n, t, P) for P in PAULIS)
     over_both = over_t + sum(_pauli(over_t, n, c, P) for P in PAULIS)
     return (1.0 - p) * rho + (p / 15.0) * (over_both - rho)
 
 
-def final_rho(n, cfgs, x, w, nz, ham_pauli='Z'):
+def final_rho(n, cfgs, x, w, nz, ham_pauli='Z', dtype=np.complex128):
     """rho[B, D, D] after the circuit under the device noise `nz` (a dict: p1, p2, readout01, readout10, t1, t2 as length-n
     sequences, t_rx, t_rot, t_cx, idle) and the noiseless basis change of the X / Y read-outs"""
-    x = np.asarray(x, np.float64)
-    w = np.asarray(w, np.float64)
+    real = DR.real_of(dtype)
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
+    sq = DR.sq_of(dtype)
     B, D = x.shape[0], 1 << n
-    rho = np.zeros((B,) + (2,) * (2 * n), dtype=np.complex128)
+    rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     rho[(slice(None),) + (0,) * (2 * n)] = 1.0
     col, s = 0, 0
     for n_enc, ld in cfgs:
@@ -148,34 +159,36 @@ def final_rho(n, cfgs, x, w, nz, ham_pauli='Z'):
         for q in range(n):
             if ham_pauli == 'Y':
                 rho = _unitary(rho, n, q, (1.0, 0.0, 0.0, -1j))
-            rho = _unitary(rho, n, q, (DR.SQ, DR.SQ, DR.SQ, -DR.SQ))
+            rho = _unitary(rho, n, q, (sq, sq, sq, -sq))
     return np.ascontiguousarray(rho).reshape(B, D, D)
 
 
 def confuse(prob, n, readout01, readout10):
     """outcome probabilities [B, 2^n] -> probabilities of the read bitstrings: per bit q the matrix
-    [[1 - r01, r10], [r01, 1 - r10]] (column = the true bit, row = the read bit)"""
+    [[1 - r01, r10], [r01, 1 - r10]] (column = the true bit, row = the read bit), in prob's type"""
     B = prob.shape[0]
+    real = prob.dtype.type
     p = prob.reshape((B,) + (2,) * n)                                    # axis 1 + (n - 1 - q) is bit q
     for q in range(n):
-        m = np.array([[1.0 - readout01[q], readout10[q]], [readout01[q], 1.0 - readout10[q]]])
+        r01, r10 = real(readout01[q]), real(readout10[q])
+        m = np.array([[1.0 - r01, r10], [r01, 1.0 - r10]])
         ax = 1 + (n - 1 - q)
         p = np.moveaxis(np.tensordot(m, np.moveaxis(p, ax, 0), axes=(1, 0)), 0, ax)
     return p.reshape(B, 1 << n)
 
 
-def value_table(n, offset=0.0, coeff=1.0, ham_diag=None):
+def value_table(n, offset=0.0, coeff=1.0, ham_diag=None, real=np.float64):
     if ham_diag is not None:
-        return np.asarray(ham_diag, np.float64)
+        return np.asarray(ham_diag, np.float64).astype(real)
     kk = np.arange(1 << n)
-    return offset + coeff * (n - 2.0 * sum((kk >> i) & 1 for i in range(n)))
+    return real(offset) + real(coeff) * (n - 2.0 * sum((kk >> i) & 1 for i in range(n)))
 
 
-def device_moments(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z'):
+def device_moments(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', dtype=np.complex128):
     """(mean, var) per row, no bias: the expectation of a read value and the variance of one shot's value"""
-    rho = final_rho(n, cfgs, x, w, nz, ham_pauli)
+    rho = final_rho(n, cfgs, x, w, nz, ham_pauli, dtype)
     prob = np.real(np.einsum('bkk->bk', rho))
     pread = confuse(prob, n, nz['readout01'], nz['readout10'])
-    hv = value_table(n, offset, coeff, ham_diag)
+    hv = value_table(n, offset, coeff, ham_diag, DR.real_of(dtype))
     mean = pread @ hv
     return mean, pread @ (hv * hv) - mean ** 2
