@@ -887,8 +887,9 @@ int    qhea_model_forward_noisy_device_wide(const qhea_model_desc* desc, int64_t
  * read-out, a negative batch or row0, first_step < 1, NULL arrays; QHEA_EINVAL for a site with 1 - gamma == 0 in fp64, which no
  * inverse undoes (qhea_device_noise_singular_site names it: 1 and *site (0 ENC, 1 ROT, 2 CTL, 3 TGT), *wire for the first such
  * site, 0 if there is none); QHEA_EINVAL for batch * ceil(T / 4) > 2^31 - 1; QHEA_EWORKSPACE.  An empty batch (or n_steps = 0)
- * returns QHEA_OK.  There is no amplification guard: K0^-1 is a relative scaling of one half of the state by
- * 1 / sqrt(1 - gamma), which lambda's K0 takes back in every product.
+ * returns QHEA_OK.  There is no amplification guard: K0^-1 scales one half of the state by 1 / sqrt(1 - gamma), and with it the
+ * rounding already there; the relative error of a trajectory's gradient grows with the product of those factors over a wire's
+ * unfired sites since the last fired one (DESIGN.md 7p has the table; quanonet_amd.noise.JUMP_GAMMA_MAX is the Python layer's bound).
  * Launches: per CALL the kernel that writes the per-site constants and h'; per step the prep kernel, the trajectory kernel, the
  * fold kernel and the reduce kernel (with Adam in train_steps) of qhea_model_loss_grad_noisy_wide.  A linear chain, no
  * allocation, no synchronisation (hipGraph-capturable).  No atomics and fixed orders: results are bitwise reproducible.

@@ -9,6 +9,7 @@ import dataclasses
 import math
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -546,7 +547,36 @@ def device_sampled_loss_and_grad(model, inputs, y, device_noise, sampling, inv_b
     return _device_trajectory_call('device_sampled_loss_and_grad', model, inputs, y, device_noise, sampling, inv_batch_total, row0)
 
 
+# The quantum-jump gradient kernels take psi back through a damping site that did not fire by K0^-1 = diag(1, 1 / sqrt(1 - gamma))
+# and restore it only at sites that fired: a wire's run of unfired sites multiplies what rounding left in its |1> half by the
+# product of those factors.  Largest site gamma at which the fp64 numpy form of that walk keeps 32 x its error below 2^-10 of the
+# largest gradient entry on every case of tests/traj_precision_cases.py (10 and 20 blocks of LD 2 at n = 7 among them; the
+# table is in DESIGN.md 7p).  At the next setting of that table (gamma >= 1 - 1.1e-4 on every wire) the walk is wrong in every
+# digit.  Below the bound the error is heavy-tailed in the trajectory: this is the bound the table supports, not
+# a guarantee.  The C calls (quanonet_amd._lib) refuse gamma = 1 only.
+JUMP_GAMMA_MAX = 0.9998
+
+
+def jump_gamma_max(device_noise, n):
+    """(gamma, site name, wire) of the relaxation site of `device_noise` with the largest damping probability at n qubits
+    (DeviceNoise.jump_tables; no device needed)"""
+    gamma = np.asarray(device_noise.jump_tables(int(n)))[..., 0]
+    site, wire = np.unravel_index(int(np.argmax(gamma)), gamma.shape)
+    return float(gamma[site, wire]), _lib.SITE_NAMES[site], int(wire)
+
+
+def check_jump_gradient_setting(device_noise, n, who):
+    """ValueError for a setting whose largest site gamma is above JUMP_GAMMA_MAX (gamma = 1 keeps the message of
+    qhea_device_noise_singular_site)"""
+    gamma, site, wire = jump_gamma_max(device_noise, n)
+    if gamma > JUMP_GAMMA_MAX and gamma < 1.0:
+        raise ValueError(f"{who}: relaxation site {site} on wire {wire} has gamma = {gamma!r}, above {JUMP_GAMMA_MAX} "
+                         "(quanonet_amd.noise.JUMP_GAMMA_MAX): the trajectory gradient walks psi back through unfired sites by "
+                         "1 / sqrt(1 - gamma) and loses its digits there (DESIGN.md 7p)")
+
+
 def _device_trajectory_call(who, model, inputs, y, device_noise, sampling, inv_batch_total, row0):
+    check_jump_gradient_setting(device_noise, int(model.fused_desc().n_qubits), who)
     desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, who)
     B = branch.shape[0]
     y = y.detach().to(torch.float64).reshape(-1).contiguous()

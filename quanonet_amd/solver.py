@@ -531,6 +531,8 @@ class DataParallelTrainer:
         if hit:
             raise ValueError(f"train_device_noise with {key}: relaxation site {hit[0]} on wire {hit[1]} has "
                              "gamma = 1, which the trajectory gradient cannot walk back")
+        from .noise import check_jump_gradient_setting
+        check_jump_gradient_setting(self.train_device_noise, n, f"train_device_noise with {key}")
         # the pair of calls for this qubit count: the wave-resident kernel at n = 7..9, the LDS-resident one at n = 10..12
         call_loss_grad, call_steps = _lib.device_sampled_grad_calls(n)
 

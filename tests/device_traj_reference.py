@@ -27,19 +27,21 @@ def site_duration(n, nz, site, q):
     return ((n - 1 if q == 0 else n - q) if idle else 1) * nz['t_cx']
 
 
-def jump_pair(tau, T1, T2):
+def jump_pair(tau, T1, T2, real=np.float64):
+    if real is not np.float64:
+        tau, T1, T2 = real(tau), real(T1), real(T2)
     gamma = 1.0 - np.exp(-tau / T1) if np.isfinite(T1) else 0.0
     total = np.exp(-tau / T2) if np.isfinite(T2) else 1.0
     f = min(total / np.sqrt(1.0 - gamma), 1.0) if gamma < 1.0 else 0.0
     return gamma, (1.0 - f) / 2.0
 
 
-def jump_pairs(n, nz):
-    """[4, n, 2]: (gamma, pz) per site and wire"""
-    out = np.zeros((4, n, 2))
+def jump_pairs(n, nz, real=np.float64):
+    """[4, n, 2]: (gamma, pz) per site and wire, in `real` from the float64 durations and times"""
+    out = np.zeros((4, n, 2), dtype=real)
     for site in range(4):
         for q in range(n):
-            out[site, q] = jump_pair(site_duration(n, nz, site, q), nz['t1'][q], nz['t2'][q])
+            out[site, q] = jump_pair(site_duration(n, nz, site, q), nz['t1'][q], nz['t2'][q], real)
     return out
 
 
@@ -56,16 +58,19 @@ def site_channel(rho2, gamma, pz):
     return sum(wt * K @ rho2 @ K.conj().T for wt, K in site_kraus(gamma, pz))
 
 
-def readout_weights(n, offset, coeff, ham_diag, r01, r10):
+def readout_weights(n, offset, coeff, ham_diag, r01, r10, real=np.float64):
     """(off_term, h[k]): value = off_term + sum_k p_k h[k], k the true string"""
     D = 1 << n
     kk = np.arange(D)
+    if real is not np.float64:
+        r01, r10 = np.asarray(r01, np.float64).astype(real), np.asarray(r10, np.float64).astype(real)
+        offset, coeff = real(offset), real(coeff)
     if ham_diag is None:
-        h = np.zeros(D)
+        h = np.zeros(D, dtype=real)
         for i in range(n):
             h += np.where((kk >> i) & 1, -(1.0 - 2.0 * r10[i]), 1.0 - 2.0 * r01[i])
-        return float(offset), coeff * h
-    h = np.asarray(ham_diag, np.float64).copy()
+        return offset if real is not np.float64 else float(offset), coeff * h
+    h = np.asarray(ham_diag, np.float64).astype(real)
     for i in range(n):
         e = np.where((kk >> i) & 1, r10[i], r01[i])
         h = (1.0 - e) * h + e * h[kk ^ (1 << i)]
@@ -77,21 +82,25 @@ def n_calls(n, cfgs):
 
 
 def replay_values(n, cfgs, x, w, nz, shots, trajectories, seed, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0,
-                  counts=None):
+                  counts=None, dtype=np.complex128):
     """
     values[B, T]: trajectory t of row b (global row row0 + b), no bias.  nz: the dict of tests/device_noise_reference.py.
-    counts (a dict, optional) receives the number of Paulis, dephasings and jumps that fired.
+    counts (a dict, optional) receives the number of Paulis, dephasings and jumps that fired.  dtype: noise_oracle.real_of
+    (expectation mode; the dephasing thresholds are taken from the float64 pz in either type).
     """
-    x = np.asarray(x, np.float64)
-    w = np.asarray(w, np.float64)
+    real = NO.real_of(dtype)
+    assert real is np.float64 or shots == 0
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
     B = x.shape[0]
     T = int(shots) if shots > 0 else int(trajectories)
     words = NO.stream(B, T, row0, seed)
-    jp = jump_pairs(n, nz)
+    jp = jump_pairs(n, nz, real)
+    pz64 = jump_pairs(n, nz)[..., 1]
     fired = {'pauli': 0, 'dephasing': 0, 'jump': 0}
 
     M = B * T
-    psi = np.zeros((M, 1 << n), dtype=np.complex128)
+    psi = np.zeros((M, 1 << n), dtype=dtype)
     psi[:, 0] = 1.0
 
     def pauli1(q, wd, p):
@@ -102,8 +111,8 @@ def replay_values(n, cfgs, x, w, nz, shots, trajectories, seed, offset=0.0, coef
             NO._pauli(psi, n, q, c, err & (idx == c - 1))
 
     def relax(q, site, wd):
-        gamma, pz = jp[site, q]
-        zsel = wd[2] < np.uint64(NO.threshold(pz))
+        gamma = jp[site, q, 0]
+        zsel = wd[2] < np.uint64(NO.threshold(pz64[site, q]))
         fired['dephasing'] += int(zsel.sum())
         NO._pauli(psi, n, q, 3, zsel)
         if gamma == 0.0:
@@ -112,7 +121,7 @@ def replay_values(n, cfgs, x, w, nz, shots, trajectories, seed, offset=0.0, coef
         a0, a1 = psi[:, i0], psi[:, i1]
         norm = np.sum(psi.real ** 2 + psi.imag ** 2, axis=1)
         P1 = np.sum(a1.real ** 2 + a1.imag ** 2, axis=1) / norm
-        u = (wd[3].astype(np.float64) + 0.5) * 2.0 ** -32
+        u = ((wd[3].astype(np.float64) + 0.5) * 2.0 ** -32).astype(real)
         fire = u < gamma * P1
         fired['jump'] += int(fire.sum())
         with np.errstate(divide='ignore', invalid='ignore'):
@@ -127,7 +136,7 @@ def replay_values(n, cfgs, x, w, nz, shots, trajectories, seed, offset=0.0, coef
     for n_enc, ld in cfgs:
         assert n_enc == n
         for q in range(n):
-            O._rx(psi, n, q, X[:, col + q])
+            NO._rx(psi, n, q, X[:, col + q])
             wd = words(call + q)
             pauli1(q, wd, nz['p1'][q])
             relax(q, ENC, wd)
@@ -165,7 +174,7 @@ def replay_values(n, cfgs, x, w, nz, shots, trajectories, seed, offset=0.0, coef
     prob = prob / prob.sum(axis=1, keepdims=True)
     r01, r10 = nz['readout01'], nz['readout10']
     if shots == 0:
-        off, h = readout_weights(n, offset, coeff, ham_diag, r01, r10)
+        off, h = readout_weights(n, offset, coeff, ham_diag, r01, r10, real)
         vals = off + prob @ h
     else:
         thr = [(np.uint64(NO.threshold(r01[i])), np.uint64(NO.threshold(r10[i]))) for i in range(n)]

@@ -14,6 +14,7 @@ import numpy as np
 
 from oracle import hea_oracle as O
 
+WIDE = np.clongdouble                        # the extended-precision type of the trajectory references (x87: 64-bit mantissa)
 M32 = np.uint64(0xFFFFFFFF)
 _PM = (np.uint64(0xD2511F53), np.uint64(0xCD9E8D57))
 _PW = (np.uint64(0x9E3779B9), np.uint64(0xBB67AE85))
@@ -46,7 +47,27 @@ def n_locations(n, cfgs):
     return sum(n + 2 * n * ld for _, ld in cfgs)
 
 
+def real_of(dtype):
+    """the real scalar type of a complex dtype.  Every replay and walk of the trajectory references takes dtype=np.complex128 by
+    default; with np.clongdouble the inputs stay the float64 data they are and everything computed from them -- half angles,
+    sin / cos / exp, sqrt(1 - gamma), the read-out weights and every sum -- is done in the wide type.  Random words and the
+    thresholds they are compared with stay integers."""
+    return np.finfo(dtype).dtype.type
+
+
 # ---- gates on psi[M, 2^n] (complex) --------------------------------------------------------------------------------------
+def _rx(psi, n, q, theta, dagger=False):
+    """oracle.hea_oracle._rx without its cast of the angle to float64 (the same bits for a float64 angle)"""
+    th = np.asarray(theta)
+    if th.ndim == 1:
+        th = th[:, None]
+    c = np.cos(th / 2)
+    s = np.sin(th / 2)
+    if dagger:
+        s = -s
+    O._apply_1q(psi, n, q, c, -1j * s, -1j * s, c)
+
+
 def _pauli(psi, n, q, p, sel):
     """p in 1..3 (X, Y, Z) on wire q for the rows sel (boolean mask)."""
     if not np.any(sel):
@@ -66,10 +87,11 @@ def _basis_change(psi, n, pauli):
     """H (X read-out) or H S^dagger (Y read-out) on every wire."""
     if pauli == 'Z':
         return
+    sq = 1.0 / np.sqrt(real_of(psi.dtype)(2.0))
     for q in range(n):
         if pauli == 'Y':
             O._apply_1q(psi, n, q, 1.0, 0.0, 0.0, -1j)
-        O._apply_1q(psi, n, q, SQ, SQ, SQ, -SQ)
+        O._apply_1q(psi, n, q, sq, sq, sq, -sq)
 
 
 def readout_diag(diag, n, q):
@@ -87,17 +109,23 @@ def readout_diag(diag, n, q):
     return out
 
 
-def _readout_weights(n, offset, coeff, ham_diag, q):
+def _readout_weights(n, offset, coeff, ham_diag, q, real=np.float64):
     """(off_term, h[k]) of expectation mode: value = off_term + sum_k p_k h[k]."""
     k = np.arange(1 << n)
     if ham_diag is not None:
+        assert real is np.float64, 'readout_diag is fp64: noisy_traj_grad_reference.readout_table takes a type'
         return 0.0, readout_diag(np.asarray(ham_diag, np.float64), n, q)
     pop = sum((k >> i) & 1 for i in range(n))
-    return float(offset), coeff * (1.0 - 2.0 * q) * (n - 2.0 * pop)
+    if real is np.float64:
+        return float(offset), coeff * (1.0 - 2.0 * q) * (n - 2.0 * pop)
+    return real(offset), real(coeff) * (1 - 2 * real(q)) * (n - 2 * pop.astype(real))
 
 
 def stream(B, T, row0, seed):
     """words(c) of a call's B * T values, row-major: the four word arrays of Philox call c for every (row, trajectory)."""
+    ident = (int(B), int(T), int(row0), int(seed))
+    if ident in _STREAMS:
+        return _STREAMS[ident]
     rows = np.repeat(np.arange(B, dtype=np.uint64) + np.uint64(row0), T)
     trajs = np.tile(np.arange(T, dtype=np.uint64), B)
     key = (int(seed) & 0xFFFFFFFF, int(seed) >> 32)
@@ -106,9 +134,18 @@ def stream(B, T, row0, seed):
     def words(c):
         if c not in cache:
             cache[c] = philox4x32((np.uint64(c), trajs, rows & M32, rows >> np.uint64(32)), key)
+            for a in cache[c]:
+                a.setflags(write=False)
         return cache[c]
 
+    if B * T <= 64:                          # a shift rule replays the same few rows once per angle: keep their words
+        if len(_STREAMS) >= 8:
+            _STREAMS.pop(next(iter(_STREAMS)))
+        _STREAMS[ident] = words
     return words
+
+
+_STREAMS = {}
 
 
 def shot_values(prob, words, call0, n, thr, offset, coeff, ham_diag):
@@ -131,13 +168,16 @@ def shot_values(prob, words, call0, n, thr, offset, coeff, ham_diag):
     return offset + coeff * (n - 2.0 * pop)
 
 
-def replay_values(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0):
+def replay_values(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0, dtype=np.complex128,
+                  weights=None):
     """
     values[B, T]: trajectory t of row b (global row row0 + b) replayed gate by gate on the header's random stream (no bias).
     noise: an object with p1, p2, readout, shots, trajectories, seed (quanonet_amd.noise.NoiseModel or alike).
+    dtype: real_of.  weights: (off_term, h'[k]) of expectation mode where the caller has them (a wide diagonal read-out).
     """
-    x = np.asarray(x, np.float64)
-    w = np.asarray(w, np.float64)
+    real = real_of(dtype)
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
     B = x.shape[0]
     T = int(noise.shots) if noise.shots > 0 else int(noise.trajectories)
     words = stream(B, T, row0, noise.seed)
@@ -151,13 +191,13 @@ def replay_values(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ha
 
     X = np.repeat(x, T, axis=0)
     M = B * T
-    psi = np.zeros((M, 1 << n), dtype=np.complex128)
+    psi = np.zeros((M, 1 << n), dtype=dtype)
     psi[:, 0] = 1.0
     loc, col, s = 0, 0, 0
     for n_enc, ld in cfgs:
         assert n_enc == n
         for q in range(n):
-            O._rx(psi, n, q, X[:, col + q])
+            _rx(psi, n, q, X[:, col + q])
             err, idx = draw(loc + q, noise.p1, False)
             for p in (1, 2, 3):
                 _pauli(psi, n, q, p, err & (idx == p - 1))
@@ -186,7 +226,7 @@ def replay_values(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ha
     _basis_change(psi, n, pauli)
     prob = psi.real ** 2 + psi.imag ** 2
     if noise.shots == 0:
-        off, h = _readout_weights(n, offset, coeff, ham_diag, float(noise.readout))
+        off, h = weights if weights is not None else _readout_weights(n, offset, coeff, ham_diag, float(noise.readout), real)
         vals = off + prob @ h
     else:
         thr = np.uint64(threshold(noise.readout))

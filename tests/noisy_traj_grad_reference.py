@@ -26,15 +26,23 @@ def _undo_basis_change(psi, n, pauli):
     """the dagger of noise_oracle._basis_change: H, then S for a Y read-out, on every wire"""
     if pauli == 'Z':
         return
+    sq = 1.0 / np.sqrt(NO.real_of(psi.dtype)(2.0))
     for q in range(n):
-        O._apply_1q(psi, n, q, SQ, SQ, SQ, -SQ)
+        O._apply_1q(psi, n, q, sq, sq, sq, -sq)
         if pauli == 'Y':
             O._apply_1q(psi, n, q, 1.0, 0.0, 0.0, 1j)
 
 
-def readout_table(diag, n, q):
+def readout_table(diag, n, q, real=np.float64):
     """noise_oracle.readout_diag as one matrix product (that routine's 4^n terms in Python take seconds at n = 9): the same sum
-    per entry, added by numpy; tests/test_noisy_traj_grad_reference.py holds the two together at n = 7"""
+    per entry, added by numpy; tests/test_noisy_traj_grad_reference.py holds the two together at n = 7.  Wire by wire (the same
+    sum in another order, 2^n n terms) where `real` is wider than float64: a 4^n table in long double at n = 12 is too large."""
+    if real is not np.float64:
+        h, q = np.asarray(diag, np.float64).astype(real), real(q)
+        kk = np.arange(1 << n)
+        for i in range(n):
+            h = (1 - q) * h + q * h[kk ^ (1 << i)]
+        return h
     kk = np.arange(1 << n)
     conf = np.ones((1 << n, 1 << n))
     for i in range(n):
@@ -42,21 +50,23 @@ def readout_table(diag, n, q):
     return conf @ np.asarray(diag, np.float64)
 
 
-def readout_weights(n, offset, coeff, ham_diag, q):
+def readout_weights(n, offset, coeff, ham_diag, q, real=np.float64):
     """(off_term, h'[k]) of expectation mode, as noise_oracle._readout_weights"""
     if ham_diag is None:
-        return NO._readout_weights(n, offset, coeff, None, q)
-    return 0.0, readout_table(ham_diag, n, q)
+        return NO._readout_weights(n, offset, coeff, None, q, real)
+    return real(0.0) if real is not np.float64 else 0.0, readout_table(ham_diag, n, q, real)
 
 
-def traj_grad(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0):
+def traj_grad(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0, dtype=np.complex128):
     """
     (value[B], d value / d x [B, E], d value / d w [B, blk, 3, n]), each the mean over the T = noise.trajectories trajectories of
-    global row row0 + b on the stream of noise.seed (no bias): the adjoint walk per trajectory.
+    global row row0 + b on the stream of noise.seed (no bias): the adjoint walk per trajectory.  dtype: noise_oracle.real_of;
+    the results come back in its real type.
     """
     assert noise.shots == 0
-    x = np.asarray(x, np.float64)
-    w = np.asarray(w, np.float64)
+    real = NO.real_of(dtype)
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
     B, T = x.shape[0], int(noise.trajectories)
     words = NO.stream(B, T, row0, noise.seed)
 
@@ -69,7 +79,7 @@ def traj_grad(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pa
 
     X = np.repeat(x, T, axis=0)
     M = B * T
-    psi = np.zeros((M, 1 << n), dtype=np.complex128)
+    psi = np.zeros((M, 1 << n), dtype=dtype)
     psi[:, 0] = 1.0
     ops = []
 
@@ -82,7 +92,7 @@ def traj_grad(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pa
     for n_enc, ld in cfgs:
         assert n_enc == n
         for q in range(n):
-            O._rx(psi, n, q, X[:, col + q])
+            NO._rx(psi, n, q, X[:, col + q])
             ops.append(('x', q, col + q))
             err, idx = draw(loc + q, noise.p1, False)
             for p in (1, 2, 3):
@@ -114,15 +124,15 @@ def traj_grad(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pa
     assert loc == NO.n_locations(n, cfgs)
     pauli = O._check_pauli(ham_pauli, ham_diag)
     NO._basis_change(psi, n, pauli)
-    off, h = readout_weights(n, offset, coeff, ham_diag, float(noise.readout))
+    off, h = readout_weights(n, offset, coeff, ham_diag, float(noise.readout), real)
     vals = off + (psi.real ** 2 + psi.imag ** 2) @ h
     lam = psi * h[None, :]
     _undo_basis_change(psi, n, pauli)
     _undo_basis_change(lam, n, pauli)
-    gx = np.zeros((M, x.shape[1]))
-    gw = np.zeros((M,) + w.shape)
+    gx = np.zeros((M, x.shape[1]), dtype=real)
+    gw = np.zeros((M,) + w.shape, dtype=real)
     sigma = {'x': 'X', 'y': 'Y', 'z': 'Z'}
-    rot = {'x': O._rx, 'y': O._ry, 'z': O._rz}
+    rot = {'x': NO._rx, 'y': O._ry, 'z': O._rz}
     for op in reversed(ops):
         if op[0] == 'p':
             NO._pauli(psi, n, op[1], op[2], op[3])
@@ -144,27 +154,40 @@ def traj_grad(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pa
     return mean(vals), mean(gx), mean(gw)
 
 
+def half_pi(real):
+    """pi / 2 in the real type (np.pi / 2 for float64)"""
+    return np.pi / 2 if real is np.float64 else 2 * np.arctan(real(1))
+
+
 def _shift(value, x, w):
     """(value[B], d / d x [B, E], d / d w [B, blk, 3, n]) of value(x, w) -> [B] by central differences at +- pi / 2: exact
-    where every angle enters through one rotation exp(-i theta sigma / 2)"""
-    gx, gw = np.zeros(x.shape), np.zeros((x.shape[0],) + w.shape)
+    where every angle enters through one rotation exp(-i theta sigma / 2).  In the type of x."""
+    real = x.dtype.type
+    hp = half_pi(real)
+    gx, gw = np.zeros(x.shape, dtype=real), np.zeros((x.shape[0],) + w.shape, dtype=real)
     for e in range(x.shape[1]):
         xp, xm = x.copy(), x.copy()
-        xp[:, e] += np.pi / 2
-        xm[:, e] -= np.pi / 2
+        xp[:, e] += hp
+        xm[:, e] -= hp
         gx[:, e] = 0.5 * (value(xp, w) - value(xm, w))
     for idx in np.ndindex(w.shape):
         wp, wm = w.copy(), w.copy()
-        wp[idx] += np.pi / 2
-        wm[idx] -= np.pi / 2
+        wp[idx] += hp
+        wm[idx] -= hp
         gw[(slice(None),) + idx] = 0.5 * (value(x, wp) - value(x, wm))
     return value(x, w), gx, gw
 
 
-def traj_grad_shift(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0):
-    """traj_grad by central differences of noise_oracle.replay_values on the same stream"""
-    val = lambda xx, ww: NO.replay_values(n, cfgs, xx, ww, noise, offset, coeff, ham_diag, ham_pauli, row0).mean(axis=1)
-    return _shift(val, np.asarray(x, np.float64), np.asarray(w, np.float64))
+def traj_grad_shift(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', row0=0, dtype=np.complex128,
+                    weights=None):
+    """traj_grad by central differences of noise_oracle.replay_values on the same stream.  weights: readout_weights of the
+    call where the caller has them; without them a float64 replay makes noise_oracle's own, every time"""
+    real = NO.real_of(dtype)
+    if weights is None and real is not np.float64:
+        weights = readout_weights(n, offset, coeff, ham_diag, float(noise.readout), real)
+    val = lambda xx, ww: NO.replay_values(n, cfgs, xx, ww, noise, offset, coeff, ham_diag, ham_pauli, row0, dtype,
+                                          weights).mean(axis=1)
+    return _shift(val, np.asarray(x, real), np.asarray(w, real))
 
 
 def exact_grad(n, cfgs, x, w, noise, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z'):
@@ -197,20 +220,31 @@ class _Engine:
         return v, g[:, None] * gx, np.einsum('b,bskq->skq', g, gw)
 
 
-def TrajEngine(noise, row0=0, form=traj_grad):
-    return _Engine(lambda n, cfgs, x, w, off, co, hd, hp: form(n, cfgs, x, w, noise, off, co, hd, hp, row0))
+def TrajEngine(noise, row0=0, form=traj_grad, dtype=np.complex128):
+    """form: traj_grad or traj_grad_shift.  dtype: the form's; a wide engine goes with model_loss_grad(..., dtype=dtype)"""
+    kw = {} if np.dtype(dtype) == np.complex128 else dict(dtype=dtype)
+    return _Engine(lambda n, cfgs, x, w, off, co, hd, hp: form(n, cfgs, x, w, noise, off, co, hd, hp, row0, **kw))
 
 
 def ExactEngine(noise):
     return _Engine(lambda n, cfgs, x, w, off, co, hd, hp: exact_grad(n, cfgs, x, w, noise, off, co, hd, hp))
 
 
-def model_loss_grad(model, inputs, y, inv_batch_total, engine=None):
+def model_loss_grad(model, inputs, y, inv_batch_total, engine=None, dtype=np.complex128):
     """
     ([P + 2] buffer, pred[B]) of the header's calls for a QuanONetPT / HEAQNNPT (any device; the arithmetic is numpy): the
     gradients of sum_b (pred_b - y_b)^2 * inv_batch_total in model.parameters() order, then sum (pred - y)^2 and sum y^2.
     inputs: (branch, trunk) or (x,) as numpy arrays.  engine: TrajEngine / ExactEngine, or None for the ideal oracle.
+    dtype: np.complex128 -- the model around the circuit is oracle.hea_oracle's, in float64 -- or np.clongdouble with an engine of
+    that type: the frequency layers, the bias, the residual, the chain rule and the sums are then done in the wide type by
+    tests/device_noise_grad_reference.py model_loss_grad (the same model and the same flat layout) around the engine's circuit.
     """
+    if np.dtype(dtype) != np.complex128:
+        from tests import density_grad_reference as DGR
+        from tests import device_noise_grad_reference as DV
+        flat = np.concatenate([p.detach().cpu().numpy().reshape(-1) for p in model.parameters()])
+        return DV.model_loss_grad(DGR.spec_of(model), flat, inputs[0], inputs[1] if len(inputs) > 1 else None, y, None, inv_batch_total,
+                                  circuit=lambda n, cfgs, x, w, nz, *readout: engine.circuit(n, cfgs, x, w, *readout), dtype=dtype)
     from quanonet_amd.models import QuanONetPT
     q = model.quantum_layer
     n, net = model.num_qubits, tuple(model.net_size)
