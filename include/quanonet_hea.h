@@ -350,6 +350,41 @@ int    qhea_model_forward_noisy_exact(const qhea_model_desc* desc, int64_t batch
                                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The same two quantities for n = 7..9 (library version 630): qhea_model_forward_noisy_exact with the density matrix in the
+ * workspace instead of LDS.  Arguments, noise model (the text of qhea_model_forward_noisy; shots, trajectories and seed are
+ * ignored), pred and shot_std are those of the call above.
+ * rho of all rows of the call lives in the workspace, 4^n x 16 bytes per row (256 KiB, 1 MiB, 4 MiB for n = 7, 8, 9), element
+ * index bit 2q = wire q's row bit, bit 2q + 1 = its column bit.  A stage is one launch of rows x 4^(n-6) workgroups of 256
+ * threads; a workgroup copies one tile of 4^6 elements (six wires with both of their bits) into 64 KiB of LDS, runs its passes
+ * and copies the tile back.  Stage A holds wires (0..5): element = tile << 12 | local.  Stage B holds wires (0, 1, n-4 .. n-1):
+ * element = (local & 15) | tile << 4 | (local >> 4) << (2n - 8).  A sub-layer is stage A (ring passes 0..4) then stage B (ring
+ * passes 5..n-1); a block without sub-layers and the basis change of an X / Y read-out are one stage A (wires 0..5) and one
+ * stage B (wires 6..n-1).  The launch boundary is the only synchronisation between the tiles of a row: no workgroup waits on
+ * another.
+ * Launches: the prep kernel, the value-table kernel (h' and h'^2 under the readout confusion, once per call), then
+ *   2 * (sub-layers of the circuit) + 2 * (blocks without sub-layers) + (2 for an X or Y read-out)
+ * stage launches (one more for a circuit without any block), then the read-out kernel: one wave per row adds p_k h'[k] and
+ * p_k h2'[k] over diag rho, lane l the terms k = l + 64 r in the order r = 0, 1, .., then the 64 lane sums by the xor butterfly,
+ * offsets 32, 16, 8, 4, 2, 1.  No atomics, no allocation, no synchronisation (hipGraph-capturable); a row's two results are
+ * bitwise the same in any call, batch or chunking.
+ * Workspace: the tables of the call above, 2 * 2^n doubles, and batch * 4^n * 16 bytes (computed in size_t).
+ * Scope: n = 7..9, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs, the uniform qhea_noise.  There
+ * is no counterpart under a qhea_device_noise at these sizes.
+ * Errors, all before anything is launched and with the outputs untouched: QHEA_EINVAL for p1, p2 or readout outside [0, 1]
+ * (NaN included); QHEA_EUNSUPPORTED for n <= 6 (qhea_model_forward_noisy_exact is the call) and n >= 10; QHEA_EINVAL for
+ * batch * 4^(n-6) > 2^31 - 1; QHEA_EWORKSPACE for a short workspace.  An empty batch returns QHEA_OK.
+ * Cost: every stage reads and writes rho once, 2 * 4^n * 16 bytes per row; the call is bound by that traffic.
+ */
+/* DEVICE scratch bytes for qhea_model_forward_noisy_exact_wide on `batch` rows (0 on a bad descriptor, or n outside 7..9). */
+size_t qhea_model_exact_noisy_wide_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+int    qhea_model_forward_noisy_exact_wide(const qhea_model_desc* desc, int64_t batch,
+                                           const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                           const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                           const qhea_noise* noise /*HOST: p1, p2, readout used; shots, trajectories, seed ignored*/,
+                                           double* pred /*DEVICE [B]*/, double* shot_std /*DEVICE [B] or NULL*/,
+                                           void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Noise-aware training: the MSE loss of the exact noisy forward above and its exact gradient, so that a model can be trained
  * with the device's noise in the loss.  Replaces nothing in the reference (its training entry points optimise the ideal
  * circuit; ibm_inference.py reads the device's gate and readout errors only to report them).

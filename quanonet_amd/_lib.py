@@ -38,6 +38,7 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_noisy_workspace_bytes', 'qhea_model_forward_noisy',
            'qhea_model_noisy_wide_workspace_bytes', 'qhea_model_forward_noisy_wide',
            'qhea_model_exact_noisy_workspace_bytes', 'qhea_model_forward_noisy_exact',
+           'qhea_model_exact_noisy_wide_workspace_bytes', 'qhea_model_forward_noisy_exact_wide',
            'qhea_model_exact_noisy_grad_workspace_bytes', 'qhea_model_exact_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact',
            'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact',
@@ -89,7 +90,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 620           # 0.6.2: + qhea_model_loss_grad_noisy_device_exact_stored / ..._train_steps_..._stored (device-noise training past the guard: rho from stored states)
+MIN_LIB_VERSION = 630           # 0.6.3: + qhea_model_forward_noisy_exact_wide (exact noisy forward at n = 7..9: rho tiled through the workspace)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -235,6 +236,10 @@ def load():
     lib.qhea_model_exact_noisy_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
     lib.qhea_model_forward_noisy_exact.restype = ctypes.c_int
     lib.qhea_model_forward_noisy_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, npp, dp, dp, vp, ctypes.c_size_t, vp]
+    lib.qhea_model_exact_noisy_wide_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_exact_noisy_wide_workspace_bytes.argtypes = lib.qhea_model_exact_noisy_workspace_bytes.argtypes
+    lib.qhea_model_forward_noisy_exact_wide.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy_exact_wide.argtypes = lib.qhea_model_forward_noisy_exact.argtypes
     lib.qhea_model_exact_noisy_grad_workspace_bytes.restype = ctypes.c_size_t
     lib.qhea_model_exact_noisy_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
     lib.qhea_model_exact_noisy_log10_amplification.restype = ctypes.c_double
@@ -844,21 +849,23 @@ def model_forward_noisy_wide(desc, branch, trunk, params, noise, row0=0, ham_dia
     return _forward_noisy(True, desc, branch, trunk, params, noise, row0, ham_diag, out, stderr)
 
 
-def _forward_noisy_exact(device_model, desc, branch, trunk, params, noise, ham_diag, out, shot_std):
-    """The two exact entry points share one argument list: qhea_model_forward_noisy_exact (`noise` a NoiseParams) and
-    ..._noisy_device_exact (a DeviceNoiseParams)."""
+def _forward_noisy_exact(device_model, desc, branch, trunk, params, noise, ham_diag, out, shot_std, wide=False):
+    """The exact entry points share one argument list: qhea_model_forward_noisy_exact (`noise` a NoiseParams),
+    ..._noisy_device_exact (a DeviceNoiseParams) and, with its own workspace, ..._noisy_exact_wide (a NoiseParams, n = 7..9)."""
     lib = load()
-    entry = 'qhea_model_forward_noisy_device_exact' if device_model else 'qhea_model_forward_noisy_exact'
+    entry = 'qhea_model_forward_noisy_device_exact' if device_model else \
+        'qhea_model_forward_noisy_exact_wide' if wide else 'qhea_model_forward_noisy_exact'
+    sizer = lib.qhea_model_exact_noisy_wide_workspace_bytes if wide else lib.qhea_model_exact_noisy_workspace_bytes
     B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(shot_std, 'shot_std', (B,))
     pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
-    ws = _sized_ws(branch.device, lib.qhea_model_exact_noisy_workspace_bytes, ctypes.byref(desc), int(B))
+    ws = _sized_ws(branch.device, sizer, ctypes.byref(desc), int(B))
     with torch.cuda.device(branch.device):
         rc = getattr(lib, entry)(ctypes.byref(desc), int(B), _ptr(branch), _ptr(trunk), _ptr(params), _ptr(ham_diag),
                                  ctypes.byref(noise), _ptr(pred), _ptr(shot_std), _ptr(ws), 0 if ws is None else ws.numel(),
                                  _stream(branch.device))
     if rc == -2:
-        raise Unsupported(f"{entry}: unsupported circuit (n >= 7)")
+        raise Unsupported(f"{entry}: unsupported circuit ({'n <= 6 or n >= 10' if wide else 'n >= 7'})")
     _check(rc, entry)
     return pred, shot_std
 
@@ -871,6 +878,15 @@ def model_forward_noisy_exact(desc, branch, trunk, params, noise, ham_diag=None,
     anything is launched.
     """
     return _forward_noisy_exact(False, desc, branch, trunk, params, noise, ham_diag, out, shot_std)
+
+
+def model_forward_noisy_exact_wide(desc, branch, trunk, params, noise, ham_diag=None, out=None, shot_std=None):
+    """
+    qhea_model_forward_noisy_exact_wide: model_forward_noisy_exact for n = 7..9 -- the same arguments and quantities, the density
+    matrix of all rows in the workspace (4^n x 16 bytes per row).  Raises Unsupported for n <= 6 (model_forward_noisy_exact is
+    the call for those) and n >= 10, and QheaError for a bad noise setting -- in both cases before anything is launched.
+    """
+    return _forward_noisy_exact(False, desc, branch, trunk, params, noise, ham_diag, out, shot_std, wide=True)
 
 
 def device_noise_tables(n, noise):

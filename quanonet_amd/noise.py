@@ -374,6 +374,47 @@ def exact_noisy_predict(model, inputs, noise, chunk_rows=16384):
     return pred.unsqueeze(-1), shot_std
 
 
+# the density matrices of a default chunk of wide_exact_noisy_predict: 256 MiB, 17 % faster than 64 MiB and 1 GiB at n = 8 and 9
+# (profiles/r37_exact_noisy_wide_rate.json, chunk_sweep)
+WIDE_EXACT_STATE_BYTES = 1 << 28
+
+
+def wide_exact_noisy_predict(model, inputs, noise, chunk_rows=None):
+    """
+    exact_noisy_predict for n = 2..9: (pred [N, 1], shot_std [N]).  n <= 6 is exact_noisy_predict itself (bitwise; a DeviceNoise
+    is allowed there).  n = 7..9 runs qhea_model_forward_noisy_exact_wide, which keeps the density matrices of a chunk of rows in
+    device memory, 4^n x 16 bytes per row, and takes a NoiseModel only.  Rows go in chunks of the largest count whose density
+    matrices stay within 256 MiB (1024 / 256 / 64 rows at n = 7 / 8 / 9), and of no more than `chunk_rows` when given; the
+    result is bitwise the same for any chunking.
+    """
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'wide_exact_noisy_predict')
+    n = desc.n_qubits
+    if n <= 6:
+        return exact_noisy_predict(model, inputs, noise) if chunk_rows is None else \
+            exact_noisy_predict(model, inputs, noise, chunk_rows=chunk_rows)
+    if n >= 10:
+        raise ValueError(f"wide_exact_noisy_predict covers n = 2..9 (got n = {n}): a density matrix of 4^{n} elements per row "
+                         "is not carried; noisy_predict estimates a NoiseModel at n = 10..12 from trajectories and "
+                         "device_noisy_predict a DeviceNoise")
+    if isinstance(noise, DeviceNoise):
+        raise ValueError(f"wide_exact_noisy_predict evaluates a NoiseModel at n = 7..9 (got a DeviceNoise at n = {n}): the tiled "
+                         "density-matrix kernels carry the uniform channels only; exact_noisy_predict evaluates a DeviceNoise "
+                         "exactly at n <= 6, device_noisy_predict and evaluate_noisy(noise, sampling=Sampling(...)) sample one at "
+                         "n = 2..12")
+    N = branch.shape[0]
+    pred = torch.empty(N, dtype=torch.float64, device=branch.device)
+    shot_std = torch.empty(N, dtype=torch.float64, device=branch.device)
+    chunk = max(1, WIDE_EXACT_STATE_BYTES >> (2 * n + 4))
+    if chunk_rows is not None:
+        chunk = max(1, min(chunk, int(chunk_rows)))
+    nz = noise.params()
+    for s in range(0, N, chunk):
+        e = min(N, s + chunk)
+        _lib.model_forward_noisy_exact_wide(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, ham_diag=ham_diag,
+                                            out=pred[s:e], shot_std=shot_std[s:e])
+    return pred.unsqueeze(-1), shot_std
+
+
 def amplification(model, noise):
     """
     log10 of the factor by which the gradient's inverse walk amplifies the traceless part of rho for this model's circuit
@@ -410,7 +451,7 @@ def noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, row0=0):
     of noise.trajectories runs on the stream keyed noise.seed -- and its gradient with that stream held fixed, as the flat
     [P + 2] tensor of qhea_model_loss_grad_noisy_wide (the layout of exact_noisy_loss_and_grad).  d pred / d params is an
     unbiased estimate of the exact noisy derivative; the loss also carries the trajectories' variance / T (the header states
-    the estimator).  n = 7..9, where no density matrix fits; for n <= 6 exact_noisy_loss_and_grad is the call.
+    the estimator).  n = 7..9, where no density matrix fits in LDS; for n <= 6 exact_noisy_loss_and_grad is the call.
     """
     _uniform_only(noise, 'noisy_loss_and_grad',
                   "relaxation jumps depend on the state, so a sampled DeviceNoise has no fixed-stream gradient")
@@ -526,8 +567,8 @@ def device_sampled_loss_and_grad(model, inputs, y, device_noise, sampling, inv_b
     row0=row0) in expectation mode -- and an unbiased gradient of it: (flat [P + 2] tensor of qhea_model_loss_grad_noisy_device,
     pred[B]).  Per trajectory the gradient of the UNNORMALISED numerator is taken with the fired jump pattern held fixed and
     divided by the final norm; neither the norm nor the jump decisions are differentiated (the two terms cancel: the header
-    states the estimator).  The loss also carries the trajectories' variance / T.  n = 7..9, where no density matrix fits; for
-    n <= 6 device_noisy_loss_and_grad is the exact call.
+    states the estimator).  The loss also carries the trajectories' variance / T.  n = 7..9, where no density matrix fits in
+    LDS; for n <= 6 device_noisy_loss_and_grad is the exact call.
     """
     _device_noise(device_noise, 'device_sampled_loss_and_grad')
     if not isinstance(sampling, Sampling):

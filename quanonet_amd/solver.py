@@ -1176,11 +1176,15 @@ class PTSolver:
         deviation) in place of 'mean_stderr'.  A quanonet_amd.noise.DeviceNoise (per-wire rates, T1 / T2, the ring's idle
         decay) is evaluated with exact=True, or sampled with sampling= (a quanonet_amd.noise.Sampling: quantum-jump trajectories,
         device_noisy_predict; 'mean_stderr', and 'sampling' beside 'noise').  sampling belongs to a DeviceNoise without exact.
+        exact='wide': the same result through wide_exact_noisy_predict, which also serves n = 7..9 (the density matrix tiled
+        through device memory; a NoiseModel only at those sizes); exact=True keeps refusing n >= 7.
         """
         from .noise import (DeviceNoise, _TRAJECTORY_WHY, _uniform_only, device_noisy_predict, exact_noisy_predict,
-                            noisy_predict)
+                            noisy_predict, wide_exact_noisy_predict)
         if self.world > 1:
             raise RuntimeError("evaluate_noisy runs on one rank (world_size == 1)")
+        if isinstance(exact, str) and exact != 'wide':
+            raise ValueError(f"evaluate_noisy: exact={exact!r}; exact is False, True (n <= 6) or 'wide' (n <= 9)")
         if sampling is not None and (exact or not isinstance(noise, DeviceNoise)):
             raise ValueError("evaluate_noisy: sampling= is the estimator of a DeviceNoise's trajectories; exact=True draws "
                              "nothing and a NoiseModel carries its own shots, trajectories and seed")
@@ -1191,7 +1195,7 @@ class PTSolver:
         if sampling is not None:
             y_pred, stderr = device_noisy_predict(self.model, self.test_input, noise, sampling, chunk_rows=chunk_rows)
         else:
-            predict = exact_noisy_predict if exact else noisy_predict
+            predict = wide_exact_noisy_predict if exact == 'wide' else exact_noisy_predict if exact else noisy_predict
             y_pred, stderr = predict(self.model, self.test_input, noise, chunk_rows=chunk_rows)
         y_true = torch.as_tensor(np.asarray(self.test_output), dtype=torch.float64).to(y_pred.device)
         metrics = regression_metrics(y_pred, y_true)
