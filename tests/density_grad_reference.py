@@ -10,6 +10,8 @@ inverse_walk_grad is the same walk with rho recomputed by inverting the channels
 the conditioning of that inversion.  model_loss_grad adds the model around the circuit: frequency layers, bias, the MSE
 residual and the flat [P + 2] layout of the header.
 """
+from collections import namedtuple
+
 import numpy as np
 
 from oracle import hea_oracle as O
@@ -215,17 +217,19 @@ def _tiled(v, cols, real=np.float64):
     return np.tile(v, (1, -(-cols // v.shape[1])))[:, :cols]
 
 
-def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_total, inverse=False, dtype=np.complex128):
+ModelCircuit = namedtuple('ModelCircuit', 'n quanonet cfgs segs tiles off off_ans P flat x w')
+
+
+def model_circuit(spec, flat, branch, trunk, dtype=np.complex128):
     """
-    ([P + 2] buffer, pred[B]) of the header's qhea_model_loss_grad_noisy_exact: gradients of sum_b (pred_b - y_b)^2 *
-    inv_batch_total in the flat parameter layout, then sum (pred - y)^2 and sum y^2.  dtype: as in circuit_grad; with
-    np.clongdouble the frequency layers, the bias, the residual, the sums and the chain rule are done in the wide type too.
+    The model in front of its circuit, in the real type of dtype: the flat parameter layout of the header ([bias] [branch w, b]
+    [trunk w, b] ansatz  /  [w, b] ansatz), the inputs tiled over the encoding columns and through the frequency layers (or the
+    fixed scale) to the encoding angles x[B, E], and the ansatz angles w[blk, 3, n].  flat[0] is the bias of a QuanONet.  Both
+    model_loss_grad routines and the forward budgets (tests/forward_precision_cases.py) take their angles from here.
     """
     n, net = spec['n'], spec['net']
     real = DR.real_of(dtype)
     flat = np.asarray(flat, np.float64).astype(real)
-    y = np.asarray(y, np.float64).reshape(-1).astype(real)
-    inv_batch_total = real(inv_batch_total)
     quanonet = spec['kind'] == 'quanonet'
     if quanonet:
         cfgs = O.block_configs_quanonet(n, net)
@@ -234,7 +238,6 @@ def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_tot
         cfgs = O.block_configs_heaqnn(n, net)
         segs = [('x', np.asarray(branch, np.float64), net[0] * n)]
     blk = sum(ld for _, ld in cfgs)
-    # flat layout: [bias] [branch w, b] [trunk w, b] ansatz  /  [w, b] ansatz
     p = 1 if quanonet else 0
     off = {}
     if spec['trainable']:
@@ -255,6 +258,19 @@ def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_tot
             xs.append(t * real(spec['scale']))
     x = np.concatenate(xs, axis=1)
     w = flat[off_ans:].reshape(blk, 3, n)
+    return ModelCircuit(n, quanonet, cfgs, segs, tiles, off, off_ans, P, flat, x, w)
+
+
+def model_loss_grad(spec, flat, branch, trunk, y, p1, p2, readout, inv_batch_total, inverse=False, dtype=np.complex128):
+    """
+    ([P + 2] buffer, pred[B]) of the header's qhea_model_loss_grad_noisy_exact: gradients of sum_b (pred_b - y_b)^2 *
+    inv_batch_total in the flat parameter layout, then sum (pred - y)^2 and sum y^2.  dtype: as in circuit_grad; with
+    np.clongdouble the frequency layers, the bias, the residual, the sums and the chain rule are done in the wide type too.
+    """
+    real = DR.real_of(dtype)
+    y = np.asarray(y, np.float64).reshape(-1).astype(real)
+    inv_batch_total = real(inv_batch_total)
+    n, quanonet, cfgs, segs, tiles, off, off_ans, P, flat, x, w = model_circuit(spec, flat, branch, trunk, dtype)
     value, gx, gw = circuit_grad(n, cfgs, x, w, p1, p2, readout, spec['offset'], spec['coeff'], spec['ham_diag'],
                                  spec['ham_pauli'], inverse=inverse, dtype=dtype)
     pred = value + (flat[0] if quanonet else 0.0)

@@ -87,7 +87,7 @@ def final_rho(n, cfgs, x, w, p1, p2, ham_pauli='Z', dtype=np.complex128):
     real = real_of(dtype)
     x = np.asarray(x, real)
     w = np.asarray(w, real)
-    p1, p2, sq = real(p1), real(p2), sq_of(dtype)
+    p1, p2 = real(p1), real(p2)
     B, D = x.shape[0], 1 << n
     rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     rho[(slice(None),) + (0,) * (2 * n)] = 1.0
@@ -111,22 +111,33 @@ def final_rho(n, cfgs, x, w, p1, p2, ham_pauli='Z', dtype=np.complex128):
             for j in range(n):
                 rho = _cnot_depolarize2(rho, n, (j + 1) % n, j, p2)
             s += 1
+    return np.ascontiguousarray(basis_change(rho, n, ham_pauli)).reshape(B, D, D)
+
+
+def basis_change(rho, n, ham_pauli):
+    """the noiseless basis change of an X / Y read-out on rho[B, 2, .., 2]: H (X) or H S^dagger (Y) on every wire"""
     if ham_pauli != 'Z':
+        sq = sq_of(rho.dtype)
         for q in range(n):
             if ham_pauli == 'Y':
                 rho = _gate(rho, n, q, (1.0, 0.0, 0.0, -1j))
             rho = _gate(rho, n, q, (sq, sq, sq, -sq))
-    return np.ascontiguousarray(rho).reshape(B, D, D)
+    return rho
 
 
 def exact_moments(n, cfgs, x, w, p1, p2, readout, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', dtype=np.complex128):
     """(mean, var) per row, no bias: the exact expectation of a read value and the variance of one shot's value"""
     pauli = O._check_pauli(ham_pauli, ham_diag)
-    real = real_of(dtype)
     rho = final_rho(n, cfgs, x, w, float(p1), float(p2), pauli, dtype)
+    return moments_of(np.real(np.einsum('bkk->bk', rho)), n, readout, offset, coeff, ham_diag)
+
+
+def moments_of(prob, n, readout, offset=0.0, coeff=1.0, ham_diag=None):
+    """exact_moments' read-out on outcome probabilities prob[B, 2^n] = diag rho, in prob's type: the confusion applied to the
+    probabilities, the sums as matrix products"""
+    real = prob.dtype.type
     readout = real(readout)
     D = 1 << n
-    prob = np.real(np.einsum('bkk->bk', rho))
     kk = np.arange(D)
     conf = np.ones((D, D), dtype=real)
     for i in range(n):

@@ -99,6 +99,38 @@ def value_table(n, nz, offset=0.0, coeff=1.0, ham_diag=None, dtype=np.complex128
     return DNR.confuse(eye, n, nz['readout01'], nz['readout10']) @ hv
 
 
+def _forward_sweep(n, ops, angle, B, dtype, keep=None):
+    """rho from |0><0| through the timeline `ops` (every channel one superoperator contraction); keep: None, or the dict that
+    receives rho after every rotation (the stored walk)"""
+    rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
+    rho[(slice(None),) + (0,) * (2 * n)] = 1.0
+    for k, op in enumerate(ops):
+        if op[0] == 'ch':
+            rho = _kraus_on(rho, n, op[1], op[2])
+        elif op[0] == 'cnot':
+            rho = DGR._cnot(rho, n, op[1], op[2])
+        else:
+            rho = DR._gate(rho, n, op[1], DGR._rot(op[0], angle(op[2])))
+            if keep is not None:
+                keep[k] = rho
+    return rho
+
+
+def stored_final_rho(n, cfgs, x, w, nz, ham_pauli='Z', dtype=np.complex128):
+    """rho[B, D, D] of device_noise_reference.final_rho by the stored walk's forward sweep: the same timeline in other
+    arithmetic (a channel is the matrix sum_K K (x) K* on a wire's row and column bit, not a sum of K rho K^dagger)"""
+    real = DR.real_of(dtype)
+    x = np.asarray(x, real)
+    w = np.asarray(w, real)
+    B = x.shape[0]
+
+    def angle(key):
+        return x[:, key[1]] if key[0] == 'x' else np.full(B, w[key[1], key[2], key[3]])
+
+    rho = _forward_sweep(n, _ops(n, cfgs, nz, dtype), angle, B, dtype)
+    return np.ascontiguousarray(DR.basis_change(rho, n, ham_pauli)).reshape(B, 1 << n, 1 << n)
+
+
 def circuit_grad(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', inverse=False, dtype=np.complex128):
     """
     (value[B], d value / d x [B, E], d value / d w [B, blk, 3, n]) of the exact expectation under the device noise (no bias).
@@ -118,18 +150,8 @@ def circuit_grad(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pa
     def angle(key):
         return x[:, key[1]] if key[0] == 'x' else np.full(B, w[key[1], key[2], key[3]])
 
-    rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
-    rho[(slice(None),) + (0,) * (2 * n)] = 1.0
     keep = {}
-    for k, op in enumerate(ops):
-        if op[0] == 'ch':
-            rho = _kraus_on(rho, n, op[1], op[2])
-        elif op[0] == 'cnot':
-            rho = DGR._cnot(rho, n, op[1], op[2])
-        else:
-            rho = DR._gate(rho, n, op[1], DGR._rot(op[0], angle(op[2])))
-            if not inverse:
-                keep[k] = rho
+    rho = _forward_sweep(n, ops, angle, B, dtype, None if inverse else keep)
     hv = value_table(n, nz, offset, coeff, ham_diag, dtype)
     obs = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     obs.reshape(B, 1 << n, 1 << n)[:, np.arange(1 << n), np.arange(1 << n)] = hv
@@ -196,40 +218,10 @@ def model_loss_grad(spec, flat, branch, trunk, y, nz, inv_batch_total, inverse=F
     circuit: circuit_grad (default, with `inverse` and `dtype`) or shift_grad (fp64).  dtype: as in circuit_grad; with
     np.clongdouble the model around the circuit is done in the wide type too.
     """
-    n, net = spec['n'], spec['net']
     real = DR.real_of(dtype)
-    flat = np.asarray(flat, np.float64).astype(real)
     y = np.asarray(y, np.float64).reshape(-1).astype(real)
     inv_batch_total = real(inv_batch_total)
-    quanonet = spec['kind'] == 'quanonet'
-    if quanonet:
-        cfgs = O.block_configs_quanonet(n, net)
-        segs = [('trunk', np.asarray(trunk, np.float64), net[2] * n), ('branch', np.asarray(branch, np.float64), net[0] * n)]
-    else:
-        cfgs = O.block_configs_heaqnn(n, net)
-        segs = [('x', np.asarray(branch, np.float64), net[0] * n)]
-    blk = sum(ld for _, ld in cfgs)
-    # flat layout: [bias] [branch w, b] [trunk w, b] ansatz  /  [w, b] ansatz
-    p = 1 if quanonet else 0
-    off = {}
-    if spec['trainable']:
-        for name, _, cols in (segs[::-1] if quanonet else segs):
-            off[name] = (p, p + cols)
-            p += 2 * cols
-    off_ans = p
-    P = p + blk * 3 * n
-    assert flat.size == P, (flat.size, P)
-    xs, tiles = [], []
-    for name, v, cols in segs:
-        t = DGR._tiled(v, cols, real)
-        tiles.append(t)
-        if spec['trainable']:
-            ow, ob = off[name]
-            xs.append(t * flat[ow:ow + cols] + flat[ob:ob + cols])
-        else:
-            xs.append(t * real(spec['scale']))
-    x = np.concatenate(xs, axis=1)
-    w = flat[off_ans:].reshape(blk, 3, n)
+    n, quanonet, cfgs, segs, tiles, off, off_ans, P, flat, x, w = DGR.model_circuit(spec, flat, branch, trunk, dtype)
     if circuit is None:
         value, gx, gw = circuit_grad(n, cfgs, x, w, nz, spec['offset'], spec['coeff'], spec['ham_diag'], spec['ham_pauli'],
                                      inverse=inverse, dtype=dtype)

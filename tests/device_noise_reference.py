@@ -124,7 +124,6 @@ def final_rho(n, cfgs, x, w, nz, ham_pauli='Z', dtype=np.complex128):
     real = DR.real_of(dtype)
     x = np.asarray(x, real)
     w = np.asarray(w, real)
-    sq = DR.sq_of(dtype)
     B, D = x.shape[0], 1 << n
     rho = np.zeros((B,) + (2,) * (2 * n), dtype=dtype)
     rho[(slice(None),) + (0,) * (2 * n)] = 1.0
@@ -155,12 +154,18 @@ def final_rho(n, cfgs, x, w, nz, ham_pauli='Z', dtype=np.complex128):
                     if q in (ctl, tgt) or nz['idle']:
                         rho = _relax(rho, n, q, nz['t_cx'], nz)
             s += 1
+    return np.ascontiguousarray(basis_change(rho, n, ham_pauli)).reshape(B, D, D)
+
+
+def basis_change(rho, n, ham_pauli):
+    """the noiseless basis change of an X / Y read-out on rho[B, 2, .., 2], with this file's _unitary"""
     if ham_pauli != 'Z':
+        sq = DR.sq_of(rho.dtype)
         for q in range(n):
             if ham_pauli == 'Y':
                 rho = _unitary(rho, n, q, (1.0, 0.0, 0.0, -1j))
             rho = _unitary(rho, n, q, (sq, sq, sq, -sq))
-    return np.ascontiguousarray(rho).reshape(B, D, D)
+    return rho
 
 
 def confuse(prob, n, readout01, readout10):
@@ -187,8 +192,12 @@ def value_table(n, offset=0.0, coeff=1.0, ham_diag=None, real=np.float64):
 def device_moments(n, cfgs, x, w, nz, offset=0.0, coeff=1.0, ham_diag=None, ham_pauli='Z', dtype=np.complex128):
     """(mean, var) per row, no bias: the expectation of a read value and the variance of one shot's value"""
     rho = final_rho(n, cfgs, x, w, nz, ham_pauli, dtype)
-    prob = np.real(np.einsum('bkk->bk', rho))
+    return moments_of(np.real(np.einsum('bkk->bk', rho)), n, nz, offset, coeff, ham_diag)
+
+
+def moments_of(prob, n, nz, offset=0.0, coeff=1.0, ham_diag=None):
+    """device_moments' read-out on outcome probabilities prob[B, 2^n] = diag rho, in prob's type"""
     pread = confuse(prob, n, nz['readout01'], nz['readout10'])
-    hv = value_table(n, offset, coeff, ham_diag, DR.real_of(dtype))
+    hv = value_table(n, offset, coeff, ham_diag, prob.dtype.type)
     mean = pread @ hv
     return mean, pread @ (hv * hv) - mean ** 2

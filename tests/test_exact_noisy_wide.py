@@ -1,7 +1,7 @@
 """
 The exact noisy forward at n = 7..9 (qhea_model_forward_noisy_exact_wide, quanonet_amd.noise.wide_exact_noisy_predict,
 evaluate_noisy(exact='wide')): the density matrix in device memory, six wires at a time in LDS.  On the GPU: against the numpy
-density matrix (tests/density_reference.py), noiseless = ideal, the stage edges, determinism and chunk independence, errors,
+density matrix (tests/density_reference.py), noiseless = ideal, the stage edges, determinism and chunk independence, errors, the grid guard,
 graph capture and the launch count, the wide trajectory kernels against it, the solvers.  Without a GPU: the two tile index
 maps restated in numpy.  Tolerance against the references: atol 1e-10, the one the HIP path is held to against the oracle.
 """
@@ -316,6 +316,37 @@ def test_errors_launch_nothing(dev):
     both, _ = _lib.model_forward_noisy_exact_wide(desc, ins[0], ins[1], params, ok, shot_std=sd)
     torch.cuda.synchronize()
     assert none is None and torch.equal(pred, both) and torch.all(sd != 456.0)
+
+
+@gpu
+@pytest.mark.parametrize('n', [7, 8, 9])
+def test_grid_guard(dev, n):
+    """A stage has one workgroup per (row, tile), rows x 4^(n-6) of them in gridDim.x: the first batch that passes INT_MAX is
+    refused as a bad argument, before the workspace is looked at.  The workspace here holds one row, so without the guard the
+    call would answer -3: nothing is launched either way, and the largest batch the guard admits does answer -3."""
+    from quanonet_amd import _lib
+    lib = _lib.load()
+    m = _model('heaqnn', n, True, 'Z').to(dev)
+    ins = _inputs('heaqnn', 2, dev)
+    desc, params = m.fused_desc(), H.flat(m)
+    out = torch.full((2,), 123.0, dtype=torch.float64, device=dev)
+    sd = torch.full((2,), 456.0, dtype=torch.float64, device=dev)
+    ok = _lib.NoiseParams(0.01, 0.02, 0.03, 0, 1, 0)
+    need = lib.qhea_model_exact_noisy_wide_workspace_bytes(ctypes.byref(desc), 1)
+    assert need >= (4 ** n) * 16
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    limit = (2 ** 31 - 1) >> (2 * (n - 6))
+
+    def call(batch):
+        return lib.qhea_model_forward_noisy_exact_wide(ctypes.byref(desc), batch, _lib._ptr(ins[0]), None, _lib._ptr(params), None,
+                                                       ctypes.byref(ok), _lib._ptr(out), _lib._ptr(sd), _lib._ptr(ws), need,
+                                                       _lib._stream(dev))
+    with torch.cuda.device(dev):
+        assert call(limit + 1) == -1
+        assert call(limit) == -3
+    torch.cuda.synchronize()
+    _lib.check_status(dev)
+    assert torch.all(out == 123.0) and torch.all(sd == 456.0)
 
 
 @gpu
