@@ -368,8 +368,8 @@ int    qhea_model_forward_noisy_exact(const qhea_model_desc* desc, int64_t batch
  * offsets 32, 16, 8, 4, 2, 1.  No atomics, no allocation, no synchronisation (hipGraph-capturable); a row's two results are
  * bitwise the same in any call, batch or chunking.
  * Workspace: the tables of the call above, 2 * 2^n doubles, and batch * 4^n * 16 bytes (computed in size_t).
- * Scope: n = 7..9, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs, the uniform qhea_noise.  There
- * is no counterpart under a qhea_device_noise at these sizes.
+ * Scope: n = 7..9, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs, the uniform qhea_noise.  Its
+ * counterpart under a qhea_device_noise at these sizes is qhea_model_forward_noisy_device_exact_wide.
  * Errors, all before anything is launched and with the outputs untouched: QHEA_EINVAL for p1, p2 or readout outside [0, 1]
  * (NaN included); QHEA_EUNSUPPORTED for n <= 6 (qhea_model_forward_noisy_exact is the call) and n >= 10; QHEA_EINVAL for
  * batch * 4^(n-6) > 2^31 - 1; QHEA_EWORKSPACE for a short workspace.  An empty batch returns QHEA_OK.
@@ -625,6 +625,33 @@ int qhea_model_forward_noisy_device_exact(const qhea_model_desc* desc, int64_t b
                                           const qhea_device_noise* dn /*HOST*/,
                                           double* pred /*DEVICE [B]*/, double* shot_std /*DEVICE [B] or NULL*/,
                                           void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The same two quantities under the device model for n = 7..9 (library version 640): qhea_model_forward_noisy_device_exact on
+ * the tiles of qhea_model_forward_noisy_exact_wide.  Arguments, noise model, pred and shot_std are those of the call above; rho
+ * of all rows lives in the workspace, whose layout and size are those of qhea_model_forward_noisy_exact_wide (tiles, stages A
+ * and B, copy phases, pending-gate rule and grid are that call's).  Ring pass j applies the pending gates of its wires with their
+ * ENC / ROT sites, slot j's CNOT and two-qubit channel, the TGT site of wire j and the CTL site of wire (j + 1) mod n; a
+ * stage's local wires are global wires fixed at compile time (stage A: the identity; stage B: local 0, 1 -> 0, 1, local w >= 2
+ * -> w + n - 6) and its sites go to it as scalars of the launch.  Relaxation is folded into those sites and adds no launch.
+ * Launches: the prep kernel, the value-table kernel (h' and h'^2 under the per-bit asymmetric readout confusion), then
+ *   2 * (sub-layers of the circuit) + 2 * (blocks without sub-layers) + (2 for an X or Y read-out)
+ * stage launches (one more for a circuit without any block), then the read-out kernel of qhea_model_forward_noisy_exact_wide,
+ * its order of summation unchanged.  No atomics, no allocation, no synchronisation (hipGraph-capturable); a row's two results
+ * are bitwise the same in any call, batch or chunking.
+ * Errors, all before anything is launched and with the outputs untouched: those of qhea_model_forward_noisy_device_exact's
+ * setting in its order (QHEA_EINVAL); QHEA_EUNSUPPORTED for n <= 6 (qhea_model_forward_noisy_device_exact is the call) and
+ * n >= 10; the errors of qhea_model_forward_noisy_exact; QHEA_EINVAL for batch * 4^(n-6) > 2^31 - 1; QHEA_EWORKSPACE for a
+ * short workspace.  An empty batch returns QHEA_OK.
+ */
+/* DEVICE scratch bytes for qhea_model_forward_noisy_device_exact_wide on `batch` rows (0 on a bad descriptor, or n outside 7..9). */
+size_t qhea_model_device_exact_noisy_wide_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+int    qhea_model_forward_noisy_device_exact_wide(const qhea_model_desc* desc, int64_t batch,
+                                                  const double* branch /*DEVICE [B,branch_in]*/, const double* trunk /*DEVICE [B,trunk_in] or NULL*/,
+                                                  const double* params /*DEVICE flat*/, const double* ham_diag /*DEVICE [2^n] or NULL*/,
+                                                  const qhea_device_noise* dn /*HOST*/,
+                                                  double* pred /*DEVICE [B]*/, double* shot_std /*DEVICE [B] or NULL*/,
+                                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Training under the calibrated device noise model: the MSE loss of qhea_model_forward_noisy_device_exact and its exact

@@ -42,6 +42,7 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_exact_noisy_grad_workspace_bytes', 'qhea_model_exact_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact',
            'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact',
+           'qhea_model_device_exact_noisy_wide_workspace_bytes', 'qhea_model_forward_noisy_device_exact_wide',
            'qhea_model_device_noisy_grad_workspace_bytes', 'qhea_model_device_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_device_exact', 'qhea_model_train_steps_noisy_device_exact',
            'qhea_device_noise_jump_tables', 'qhea_model_noisy_device_workspace_bytes', 'qhea_model_forward_noisy_device',
@@ -90,7 +91,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 630           # 0.6.3: + qhea_model_forward_noisy_exact_wide (exact noisy forward at n = 7..9: rho tiled through the workspace)
+MIN_LIB_VERSION = 640           # 0.6.4: + qhea_model_forward_noisy_device_exact_wide (exact forward under a device noise model at n = 7..9)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -268,6 +269,10 @@ def load():
     lib.qhea_device_noise_tables.argtypes = [ctypes.c_int, dnp, f64p, f64p]
     lib.qhea_model_forward_noisy_device_exact.restype = ctypes.c_int
     lib.qhea_model_forward_noisy_device_exact.argtypes = [mdp, ctypes.c_int64, dp, dp, dp, dp, dnp, dp, dp, vp, ctypes.c_size_t, vp]
+    lib.qhea_model_device_exact_noisy_wide_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_device_exact_noisy_wide_workspace_bytes.argtypes = lib.qhea_model_exact_noisy_workspace_bytes.argtypes
+    lib.qhea_model_forward_noisy_device_exact_wide.restype = ctypes.c_int
+    lib.qhea_model_forward_noisy_device_exact_wide.argtypes = lib.qhea_model_forward_noisy_device_exact.argtypes
     spp = ctypes.POINTER(SamplingParams)
     lib.qhea_device_noise_jump_tables.restype = ctypes.c_int
     lib.qhea_device_noise_jump_tables.argtypes = [ctypes.c_int, dnp, ctypes.POINTER(ctypes.c_double)]
@@ -851,11 +856,12 @@ def model_forward_noisy_wide(desc, branch, trunk, params, noise, row0=0, ham_dia
 
 def _forward_noisy_exact(device_model, desc, branch, trunk, params, noise, ham_diag, out, shot_std, wide=False):
     """The exact entry points share one argument list: qhea_model_forward_noisy_exact (`noise` a NoiseParams),
-    ..._noisy_device_exact (a DeviceNoiseParams) and, with its own workspace, ..._noisy_exact_wide (a NoiseParams, n = 7..9)."""
+    ..._noisy_device_exact (a DeviceNoiseParams) and, with their own workspace, ..._noisy_exact_wide (a NoiseParams, n = 7..9) and
+    ..._noisy_device_exact_wide (a DeviceNoiseParams, n = 7..9)."""
     lib = load()
-    entry = 'qhea_model_forward_noisy_device_exact' if device_model else \
-        'qhea_model_forward_noisy_exact_wide' if wide else 'qhea_model_forward_noisy_exact'
-    sizer = lib.qhea_model_exact_noisy_wide_workspace_bytes if wide else lib.qhea_model_exact_noisy_workspace_bytes
+    entry = 'qhea_model_forward_noisy' + ('_device_exact' if device_model else '_exact') + ('_wide' if wide else '')
+    sizer = lib.qhea_model_device_exact_noisy_wide_workspace_bytes if wide and device_model else \
+        lib.qhea_model_exact_noisy_wide_workspace_bytes if wide else lib.qhea_model_exact_noisy_workspace_bytes
     B = _model_inputs(desc, branch, trunk, params, ham_diag)
     _dev_f64(shot_std, 'shot_std', (B,))
     pred = out if out is not None else torch.empty(B, dtype=torch.float64, device=branch.device)
@@ -912,6 +918,16 @@ def model_forward_noisy_device_exact(desc, branch, trunk, params, noise, ham_dia
     setting -- in both cases before anything is launched.
     """
     return _forward_noisy_exact(True, desc, branch, trunk, params, noise, ham_diag, out, shot_std)
+
+
+def model_forward_noisy_device_exact_wide(desc, branch, trunk, params, noise, ham_diag=None, out=None, shot_std=None):
+    """
+    qhea_model_forward_noisy_device_exact_wide: model_forward_noisy_device_exact for n = 7..9 -- the same arguments (`noise` a
+    DeviceNoiseParams) and quantities, the density matrix of all rows in the workspace (4^n x 16 bytes per row).  Raises
+    Unsupported for n <= 6 (model_forward_noisy_device_exact is the call for those) and n >= 10, and QheaError for a bad noise
+    setting -- in both cases before anything is launched.
+    """
+    return _forward_noisy_exact(True, desc, branch, trunk, params, noise, ham_diag, out, shot_std, wide=True)
 
 
 def device_noise_jump_tables(n, noise):

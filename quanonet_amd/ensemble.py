@@ -230,7 +230,8 @@ class EnsembleSolver:
     def evaluate_noisy(self, noise, out_name=None, exact=False, sampling=None):
         """PTSolver.evaluate_noisy for every member (its best checkpoint; out_dir/out_name when given, never metric.json); returns
         the list of results.  Every member uses noise.seed, so the members see common random numbers: member differences are
-        not blurred by independent noise draws.  exact=True (or 'wide', which reaches n = 9): every member's exact expectation instead (no draws at all); a
+        not blurred by independent noise draws.  exact=True (or 'wide', which reaches n = 9, or 'device': a DeviceNoise up to
+        n = 9): every member's exact expectation instead (no draws at all); a
         quanonet_amd.noise.DeviceNoise is evaluated that way, or sampled with sampling= (one Sampling, so one seed, for every
         member: common random numbers again); ValueError with neither."""
         return [m.evaluate_noisy(noise, out_name, exact=exact, sampling=sampling) for m in self.members]

@@ -99,8 +99,8 @@ def _number(v):
 class DeviceNoise:
     """
     The calibrated device noise model of qhea_device_noise (include/quanonet_hea.h), for the exact evaluation
-    (exact_noisy_predict, evaluate_noisy(exact=True)); n <= 6, and for quantum-jump trajectories (device_noisy_predict,
-    evaluate_noisy(sampling=...)); n <= 12.
+    (exact_noisy_predict, evaluate_noisy(exact=True)); n <= 6 (device_exact_noisy_predict, evaluate_noisy(exact='device'); n <= 9),
+    and for quantum-jump trajectories (device_noisy_predict, evaluate_noisy(sampling=...)); n <= 12.
     p1[q]: depolarizing probability after every single-qubit gate on wire q; p2[j]: two-qubit depolarizing probability after
     the CNOT of ring slot j (control (j+1) mod n -> target j); readout01[q] / readout10[q]: probability that bit q reads 1
     given 0 / 0 given 1; t1[q], t2[q]: relaxation times of wire q (math.inf: no decay; t2 <= 2 t1).  Each of the six is one
@@ -383,7 +383,8 @@ def wide_exact_noisy_predict(model, inputs, noise, chunk_rows=None):
     """
     exact_noisy_predict for n = 2..9: (pred [N, 1], shot_std [N]).  n <= 6 is exact_noisy_predict itself (bitwise; a DeviceNoise
     is allowed there).  n = 7..9 runs qhea_model_forward_noisy_exact_wide, which keeps the density matrices of a chunk of rows in
-    device memory, 4^n x 16 bytes per row, and takes a NoiseModel only.  Rows go in chunks of the largest count whose density
+    device memory, 4^n x 16 bytes per row, and takes a NoiseModel only (device_exact_noisy_predict is the call for a DeviceNoise
+    at those sizes).  Rows go in chunks of the largest count whose density
     matrices stay within 256 MiB (1024 / 256 / 64 rows at n = 7 / 8 / 9), and of no more than `chunk_rows` when given; the
     result is bitwise the same for any chunking.
     """
@@ -398,9 +399,9 @@ def wide_exact_noisy_predict(model, inputs, noise, chunk_rows=None):
                          "device_noisy_predict a DeviceNoise")
     if isinstance(noise, DeviceNoise):
         raise ValueError(f"wide_exact_noisy_predict evaluates a NoiseModel at n = 7..9 (got a DeviceNoise at n = {n}): the tiled "
-                         "density-matrix kernels carry the uniform channels only; exact_noisy_predict evaluates a DeviceNoise "
-                         "exactly at n <= 6, device_noisy_predict and evaluate_noisy(noise, sampling=Sampling(...)) sample one at "
-                         "n = 2..12")
+                         "density-matrix kernels of this call carry the uniform channels only; exact_noisy_predict evaluates a "
+                         "DeviceNoise exactly at n <= 6 and device_exact_noisy_predict at n <= 9, device_noisy_predict and "
+                         "evaluate_noisy(noise, sampling=Sampling(...)) sample one at n = 2..12")
     N = branch.shape[0]
     pred = torch.empty(N, dtype=torch.float64, device=branch.device)
     shot_std = torch.empty(N, dtype=torch.float64, device=branch.device)
@@ -412,6 +413,40 @@ def wide_exact_noisy_predict(model, inputs, noise, chunk_rows=None):
         e = min(N, s + chunk)
         _lib.model_forward_noisy_exact_wide(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz, ham_diag=ham_diag,
                                             out=pred[s:e], shot_std=shot_std[s:e])
+    return pred.unsqueeze(-1), shot_std
+
+
+def device_exact_noisy_predict(model, inputs, device_noise, chunk_rows=None):
+    """
+    exact_noisy_predict under a DeviceNoise for n = 2..9: (pred [N, 1], shot_std [N]).  n <= 6 is exact_noisy_predict itself
+    (bitwise).  n = 7..9 runs qhea_model_forward_noisy_device_exact_wide: the per-wire channel sites of the device model on the
+    tiles of wide_exact_noisy_predict, the density matrices of a chunk of rows in device memory, 4^n x 16 bytes per row.  Rows go
+    in chunks of the largest count whose density matrices stay within 256 MiB (1024 / 256 / 64 rows at n = 7 / 8 / 9), and of no
+    more than `chunk_rows` when given; the result is bitwise the same for any chunking.
+    """
+    if not isinstance(device_noise, DeviceNoise):
+        raise ValueError(f"device_exact_noisy_predict takes a DeviceNoise (got {type(device_noise).__name__}); a NoiseModel goes to "
+                         "wide_exact_noisy_predict, or through DeviceNoise.uniform")
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'device_exact_noisy_predict')
+    n = desc.n_qubits
+    if n <= 6:
+        return exact_noisy_predict(model, inputs, device_noise) if chunk_rows is None else \
+            exact_noisy_predict(model, inputs, device_noise, chunk_rows=chunk_rows)
+    if n >= 10:
+        raise ValueError(f"device_exact_noisy_predict covers n = 2..9 (got n = {n}): a density matrix of 4^{n} elements per row "
+                         "is not carried; device_noisy_predict estimates a DeviceNoise at n = 10..12 from quantum-jump "
+                         "trajectories")
+    N = branch.shape[0]
+    pred = torch.empty(N, dtype=torch.float64, device=branch.device)
+    shot_std = torch.empty(N, dtype=torch.float64, device=branch.device)
+    chunk = max(1, WIDE_EXACT_STATE_BYTES >> (2 * n + 4))
+    if chunk_rows is not None:
+        chunk = max(1, min(chunk, int(chunk_rows)))
+    nz = device_noise.params(n)
+    for s in range(0, N, chunk):
+        e = min(N, s + chunk)
+        _lib.model_forward_noisy_device_exact_wide(desc, branch[s:e], None if trunk is None else trunk[s:e], flat, nz,
+                                                   ham_diag=ham_diag, out=pred[s:e], shot_std=shot_std[s:e])
     return pred.unsqueeze(-1), shot_std
 
 

@@ -1178,13 +1178,19 @@ class PTSolver:
         device_noisy_predict; 'mean_stderr', and 'sampling' beside 'noise').  sampling belongs to a DeviceNoise without exact.
         exact='wide': the same result through wide_exact_noisy_predict, which also serves n = 7..9 (the density matrix tiled
         through device memory; a NoiseModel only at those sizes); exact=True keeps refusing n >= 7.
+        exact='device': a DeviceNoise through device_exact_noisy_predict, n = 2..9 (its channel sites on the same tiles); the same
+        metric keys as exact=True.
         """
-        from .noise import (DeviceNoise, _TRAJECTORY_WHY, _uniform_only, device_noisy_predict, exact_noisy_predict,
-                            noisy_predict, wide_exact_noisy_predict)
+        from .noise import (DeviceNoise, _TRAJECTORY_WHY, _uniform_only, device_exact_noisy_predict, device_noisy_predict,
+                            exact_noisy_predict, noisy_predict, wide_exact_noisy_predict)
         if self.world > 1:
             raise RuntimeError("evaluate_noisy runs on one rank (world_size == 1)")
-        if isinstance(exact, str) and exact != 'wide':
-            raise ValueError(f"evaluate_noisy: exact={exact!r}; exact is False, True (n <= 6) or 'wide' (n <= 9)")
+        if isinstance(exact, str) and exact not in ('wide', 'device'):
+            raise ValueError(f"evaluate_noisy: exact={exact!r}; exact is False, True (n <= 6), 'wide' (n <= 9) or 'device' "
+                             "(a DeviceNoise, n <= 9)")
+        if exact == 'device' and not isinstance(noise, DeviceNoise):
+            raise ValueError(f"evaluate_noisy: exact='device' evaluates a DeviceNoise (got {type(noise).__name__}); a NoiseModel "
+                             "goes to exact='wide', or through DeviceNoise.uniform")
         if sampling is not None and (exact or not isinstance(noise, DeviceNoise)):
             raise ValueError("evaluate_noisy: sampling= is the estimator of a DeviceNoise's trajectories; exact=True draws "
                              "nothing and a NoiseModel carries its own shots, trajectories and seed")
@@ -1195,7 +1201,8 @@ class PTSolver:
         if sampling is not None:
             y_pred, stderr = device_noisy_predict(self.model, self.test_input, noise, sampling, chunk_rows=chunk_rows)
         else:
-            predict = wide_exact_noisy_predict if exact == 'wide' else exact_noisy_predict if exact else noisy_predict
+            predict = wide_exact_noisy_predict if exact == 'wide' else device_exact_noisy_predict if exact == 'device' else \
+                exact_noisy_predict if exact else noisy_predict
             y_pred, stderr = predict(self.model, self.test_input, noise, chunk_rows=chunk_rows)
         y_true = torch.as_tensor(np.asarray(self.test_output), dtype=torch.float64).to(y_pred.device)
         metrics = regression_metrics(y_pred, y_true)
