@@ -448,6 +448,57 @@ int    qhea_model_train_steps_noisy_exact(const qhea_model_desc* desc, int64_t n
                                           size_t workspace_bytes, void* stream);
 
 /*
+ * The same loss and exact gradient for n = 7..9 (library version 650): the quantity, the adjoint walk, the [P+2] buffer and the
+ * guard of qhea_model_loss_grad_noisy_exact, with rho and the observable O in the workspace instead of LDS, on the tiles of
+ * qhea_model_forward_noisy_exact_wide.  Argument lists: those of the two calls above.
+ * rho and O of all rows of the call live in the workspace, 4^n x 16 bytes per row each, in the index layout of the forward.
+ * Forward sweep: the value-table kernel, the stage launches and the read-out kernel of qhea_model_forward_noisy_exact_wide;
+ * pred_b is bitwise what that call returns for row b.  Then one launch writes O_N = diag(h' - mean h') (zero elsewhere; the
+ * identity component carries no gradient), and for an X / Y read-out rho and O go through the daggers of the basis change as
+ * one stage B (wires 6..n-1) and one stage A (wires 0..5).  A reverse sub-layer is stage B (ring passes n-1..5) then stage A
+ * (ring passes 4..0), each one launch of rows x 4^(n-6) workgroups of 256 threads that hold their tile of rho and their tile of
+ * O in 2 x 64 KiB of LDS (one workgroup per CU); a block without sub-layers is one stage B and one stage A.  The tile maps, the
+ * local passes and the pending-gate rule are the forward's.
+ * Sums: a trace is added over a thread's 16 elements, over the wave by the xor butterfly (offsets 32 .. 1), over the
+ * workgroup's four waves in wave order, and written as one partial per (angle, row, tile); the partial buffer holds every angle
+ * of the circuit, and ONE fold launch at the end of the walk adds a row's tiles in tile order 0, 1, .. into rec[angle][row] (and
+ * copies pred out).  The reduce kernel of qhea_model_loss_grad_noisy_exact then adds the rows (lane l rows l, l + 64, ..; the
+ * butterfly) and, in train_steps, applies the Adam update.  No atomics, no flags, no workgroup waits on another; a row's pred
+ * and records are bitwise independent of the batch, the grid and the chunking.  qhea_model_train_steps_noisy_exact_wide is
+ * bitwise a loop of qhea_model_loss_grad_noisy_exact_wide + qhea_adam_step; its workspace must fit the largest step.
+ * Launches per step, with S = sub-layers of the circuit, Z = blocks without sub-layers, R = 1 for an X or Y read-out, else 0:
+ *   6 + 4 (S + Z + R)        (prep, value table, 2 (S + Z + R) forward stages, read-out, O_N, 2 R + 2 S + 2 Z reverse stages,
+ *                             fold, reduce; one more for a circuit without any block)
+ * No allocation, no host synchronisation (hipGraph-capturable).
+ * Workspace for `batch` rows, every region rounded up to 256 bytes, computed in size_t, with A = E + 3 n blk angles:
+ *   the prep tables of qhea_model_forward_noisy_exact | pred: batch doubles | records: A batch doubles | h', h'^2: 2 * 2^n
+ *   doubles | partials: A batch 4^(n-6) doubles | rho: batch 4^n 16 bytes | O: batch 4^n 16 bytes.
+ * Scope: n = 7..9, both models, trainable or fixed frequency, Z / X / Y and ham_diag read-outs, the uniform qhea_noise.
+ * Errors, all before anything is launched and with the outputs untouched: those of qhea_model_loss_grad_noisy_exact in its
+ * order (the guard included: p1 >= 3/4, p2 >= 15/16 or log10 A > 12 is QHEA_EUNSUPPORTED), with QHEA_EUNSUPPORTED for n <= 6
+ * (qhea_model_loss_grad_noisy_exact is the call) and n >= 10; then QHEA_EINVAL for batch * 4^(n-6) > 2^31 - 1 (train_steps:
+ * the largest step); then QHEA_EWORKSPACE.  An empty batch (or n_steps = 0) returns QHEA_OK.
+ * Cost: a forward stage moves rho once each way, a reverse stage rho and O: about three times the traffic of the exact forward.
+ */
+/* DEVICE scratch bytes for the two calls below on `batch` rows (0 on a bad descriptor, or n outside 7..9). */
+size_t qhea_model_exact_noisy_wide_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+int    qhea_model_loss_grad_noisy_exact_wide(const qhea_model_desc* desc, int64_t batch,
+                                             const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                             const double* params, const double* ham_diag,
+                                             const qhea_noise* noise /*HOST: p1, p2, readout used*/, double inv_batch_total,
+                                             double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                             void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_exact_wide(const qhea_model_desc* desc, int64_t n_steps, const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                               const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                               const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                               const double* ham_diag, const qhea_noise* noise /*HOST*/,
+                                               const double* inv_batch_total /*HOST [n_steps]*/,
+                                               double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                               double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr, double beta1,
+                                               double beta2, double eps, double weight_decay, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+
+/*
  * Noise-aware training at n = 7..9, where a density matrix no longer fits: the MSE loss of the SAMPLED noisy forward
  * (qhea_model_forward_noisy_wide, expectation mode) and its gradient with the random stream held fixed.
  *

@@ -41,6 +41,8 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_exact_noisy_wide_workspace_bytes', 'qhea_model_forward_noisy_exact_wide',
            'qhea_model_exact_noisy_grad_workspace_bytes', 'qhea_model_exact_noisy_log10_amplification',
            'qhea_model_loss_grad_noisy_exact', 'qhea_model_train_steps_noisy_exact',
+           'qhea_model_exact_noisy_wide_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_exact_wide',
+           'qhea_model_train_steps_noisy_exact_wide',
            'qhea_device_noise_tables', 'qhea_model_forward_noisy_device_exact',
            'qhea_model_device_exact_noisy_wide_workspace_bytes', 'qhea_model_forward_noisy_device_exact_wide',
            'qhea_model_device_noisy_grad_workspace_bytes', 'qhea_model_device_noisy_log10_amplification',
@@ -91,7 +93,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 640           # 0.6.4: + qhea_model_forward_noisy_device_exact_wide (exact forward under a device noise model at n = 7..9)
+MIN_LIB_VERSION = 650           # 0.6.5: + qhea_model_loss_grad_noisy_exact_wide / ..._train_steps_... (exact noisy gradient at n = 7..9)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -252,6 +254,12 @@ def load():
     lib.qhea_model_train_steps_noisy_exact.argtypes = [mdp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), dp, dp, dp, dp, dp, npp,
                                                        ctypes.POINTER(ctypes.c_double), dp, ctypes.c_int64, dp, dp,
                                                        ctypes.c_int64] + [ctypes.c_double] * 5 + [vp, ctypes.c_size_t, vp]
+    lib.qhea_model_exact_noisy_wide_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_exact_noisy_wide_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
+    lib.qhea_model_loss_grad_noisy_exact_wide.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_exact_wide.argtypes = lib.qhea_model_loss_grad_noisy_exact.argtypes
+    lib.qhea_model_train_steps_noisy_exact_wide.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_exact_wide.argtypes = lib.qhea_model_train_steps_noisy_exact.argtypes
     lib.qhea_model_noisy_wide_grad_workspace_bytes.restype = ctypes.c_size_t
     lib.qhea_model_noisy_wide_grad_workspace_bytes.argtypes = lib.qhea_model_noisy_workspace_bytes.argtypes
     lib.qhea_model_loss_grad_noisy_wide.restype = ctypes.c_int
@@ -1020,6 +1028,14 @@ def _exact_unit(size):
     return _GradUnit(size, None, False, ('noise',), lambda rc, who, desc, records: _check_noisy_grad(rc, who))
 
 
+def _check_exact_wide_grad(rc, who):
+    if rc == -2:
+        raise Unsupported(f"{who}: the tiled density-matrix gradient is built for n = 7..9 (n <= 6: the noisy_exact calls; "
+                          "n >= 10: the sampled noisy_lds calls), or rates and depth whose inverse walk is ill-conditioned "
+                          "(log10 amplification > 12, or a singular channel)")
+    _check(rc, who)
+
+
 def _sampled_unit(kind):
     return _GradUnit(f'qhea_model_noisy_{kind}_grad_workspace_bytes', 'noise', True, ('noise',),
                      lambda rc, who, desc, records: _check_noisy_wide_grad(rc, who, kind))
@@ -1031,6 +1047,8 @@ def _jump_unit(size):
 
 
 _GRAD_UNITS = {'noisy_exact': _exact_unit('qhea_model_exact_noisy_grad_workspace_bytes'),
+               'noisy_exact_wide': _GradUnit('qhea_model_exact_noisy_wide_grad_workspace_bytes', None, False, ('noise',),
+                                             lambda rc, who, desc, records: _check_exact_wide_grad(rc, who)),
                'noisy_device_exact': _exact_unit('qhea_model_device_noisy_grad_workspace_bytes'),
                'noisy_device_exact_stored': _exact_unit('qhea_model_device_noisy_stored_grad_workspace_bytes'),
                'noisy_wide': _sampled_unit('wide'),
@@ -1105,6 +1123,24 @@ def model_train_steps_noisy_exact(desc, bounds, global_batches, branch, trunk, y
     """
     return _train_steps_call('noisy_exact', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
                              first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
+
+
+def model_exact_noisy_wide_grad_workspace_bytes(desc, batch):
+    """qhea_model_exact_noisy_wide_grad_workspace_bytes: 0 for a bad descriptor or n outside 7..9."""
+    return int(load().qhea_model_exact_noisy_wide_grad_workspace_bytes(ctypes.byref(desc), int(batch)))
+
+
+def model_loss_grad_noisy_exact_wide(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None, pred=None):
+    """model_loss_grad_noisy_exact for n = 7..9 (qhea_model_loss_grad_noisy_exact_wide): rho and O tiled through the workspace."""
+    return _loss_grad_call('noisy_exact_wide', desc, branch, trunk, y, params, dict(noise=noise), inv_batch_total, grad, 0,
+                           ham_diag, pred)
+
+
+def model_train_steps_noisy_exact_wide(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg, exp_avg_sq,
+                                       first_step, lr, beta1, beta2, eps, weight_decay, noise, ham_diag=None):
+    """model_train_steps_noisy_exact for n = 7..9 (qhea_model_train_steps_noisy_exact_wide)."""
+    return _train_steps_call('noisy_exact_wide', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg,
+                             exp_avg_sq, first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
 
 
 def model_noisy_wide_grad_workspace_bytes(desc, batch, noise):

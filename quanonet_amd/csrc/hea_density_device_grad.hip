@@ -610,6 +610,7 @@ struct DevGradUnit {
                                  ham_diag, dn, refuse, count, trunk, required, workspace, stream, c);
     }
     // the table, at its offset in a workspace for `bmax` rows
+    static bool batch_ok(const ModelInfo&, int64_t) { return true; }
     static int once(const ModelInfo& mi, const qhea_device_noise* dn, char* ws, int64_t bmax, hipStream_t st) {
         DevTable t;
         fill_table(mi.n, dn, t);

@@ -26,50 +26,6 @@ namespace qhea {
 namespace {
 
 constexpr int kRedWaves = 4;                                             // reduce kernel: one parameter per wave
-struct DensGradArgs {
-    DensArgs f;                             // the forward's arguments (f.pred: the caller's pred or NULL; f.sd = NULL)
-    const double* w;                        // ansatz angles [blk, 3, n]
-    double o1_keep, o1_mix, o1_off;         // one-qubit channel on O (the forward's) ...
-    double r1_keep, r1_mix, r1_off;         // ... and its inverse on rho
-    double o2_keep, o2_mix, r2_keep, r2_mix;
-    double* pred_ws;                        // [B]
-    double* rec;                            // [E + 3 n blk][B]: d pred_b / d x[b, e], then d pred_b / d w[s, k, q]
-};
-
-// one-qubit channel with given coefficients (the forward's on O, the inverse's on rho)
-template <int S>
-__device__ __forceinline__ void channel1(double2 (&e)[16], double keep, double mix, double off) {
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int b = S == 1 ? 4 * m : m;
-        const double2 d0 = e[b], d1 = e[b + 3 * S];
-        e[b] = make_double2(keep * d0.x + mix * d1.x, keep * d0.y + mix * d1.y);
-        e[b + 3 * S] = make_double2(keep * d1.x + mix * d0.x, keep * d1.y + mix * d0.y);
-        e[b + S].x *= off; e[b + S].y *= off;
-        e[b + 2 * S].x *= off; e[b + 2 * S].y *= off;
-    }
-}
-
-// encoding of wire q: channel, trace (slot 3 of the wire's four), RX^dagger
-template <int S>
-__device__ __forceinline__ void undo_encoding(double2 (&e)[16], double2 (&o)[16], const DensGradArgs& a, double2 c, double* tr) {
-    channel1<S>(e, a.r1_keep, a.r1_mix, a.r1_off);
-    channel1<S>(o, a.o1_keep, a.o1_mix, a.o1_off);
-    tr[3] = pinned(trace16<S, 0>(o, e));
-    unrotate_x<S>(e, c.x, c.y);
-    unrotate_x<S>(o, c.x, c.y);
-}
-
-// wire q's gates of sub-layer s in reverse; tr[k] = this thread's share of d pred / d w[s, k, q], tr[3] of d pred / d x[col + q]
-template <int N, int S>
-__device__ __forceinline__ void undo_wire(double2 (&e)[16], double2 (&o)[16], const DensGradArgs& a, const double2* csr, int s,
-                                          int col, bool enc, int q, double* tr) {
-    channel1<S>(e, a.r1_keep, a.r1_mix, a.r1_off);
-    channel1<S>(o, a.o1_keep, a.o1_mix, a.o1_off);
-    undo_rotations<N, S>(e, o, a.w, s, q, tr);
-    if (enc) undo_encoding<S>(e, o, a, csr[col + q], tr);
-}
-
 // the reverse of ring_passes: passes J = N - 1 .. 0 of sub-layer s
 template <int N, int J>
 __device__ __forceinline__ void ring_passes_back(RowCtx<N>& cx, const DensGradArgs& a, const double2* csr, int s, int col,
@@ -306,17 +262,10 @@ struct DensGradUnit {
         return noisy_call_check({QHEA_MIN_QUBITS, 6 /* 2 x 4^n elements per row in LDS */, false, true}, desc, ham_diag, noise, 0,
                                 count, trunk, required, workspace, stream, c);
     }
+    static bool batch_ok(const ModelInfo&, int64_t) { return true; }
     static int once(const ModelInfo&, const qhea_noise*, char*, int64_t, hipStream_t) { return QHEA_OK; }
     static int launch_bwd(const GradBatch& b, const qhea_noise* noise) {
-        DensGradArgs a{};
-        a.f = dens_args(b.desc, b.mi, noise, b.params, b.ham_diag, b.batch, b.gates, b.cs);
-        a.f.pred = b.pred; a.f.sd = nullptr;
-        a.w = b.params + b.mi.off_ans;
-        a.o1_keep = a.f.d1_keep; a.o1_mix = a.f.d1_mix; a.o1_off = a.f.d1_off;
-        a.r1_off = 1.0 / a.f.d1_off; a.r1_keep = a.f.d1_keep * a.r1_off; a.r1_mix = -a.f.d1_mix * a.r1_off;
-        a.o2_keep = a.f.d2_keep; a.o2_mix = a.f.d2_mix;
-        a.r2_keep = 1.0 / a.f.d2_keep; a.r2_mix = -a.f.d2_mix * a.r2_keep;
-        a.pred_ws = b.pred_ws; a.rec = b.rec;
+        const DensGradArgs a = dens_grad_args(b, noise);
         return dispatch_n(b.mi.n, [&](auto n) { return launch_density_bwd<n()>(density_bwd_kernel<n()>, a.f.B, a, b.st); });
     }
 };

@@ -1,5 +1,6 @@
 // hea_density_grad.hpp -- the reverse walk through the density matrix that the gradient units share (hea_density_grad.hip:
-// the uniform channels of qhea_noise; hea_density_device_grad.hip: the channel sites of qhea_device_noise): the two compiler
+// the uniform channels of qhea_noise; hea_density_device_grad.hip: the channel sites of qhea_device_noise; hea_density_wide_grad.hip: the uniform channels on the
+// tiles of n = 7..9): the two compiler
 // pins, a thread's share of a trace, the un-rotations, the reverse of the CNOT with its two-qubit channel, the row context with
 // the sum of a pass' traces over the row, the read-out basis passes, the workspace layout and the reduce launch.  The device
 // code sits in an unnamed namespace like hea_density.hpp's: each unit compiles its own copy into its own kernels.  Host side:
@@ -161,6 +162,51 @@ __device__ __forceinline__ void undo_cnot2(double2 (&e)[16], double keep, double
     for (int k = 0; k < 16; ++k) e[k] = r[k ^ ((k >> 2) & 1) ^ (((k >> 3) & 1) << 1)];
 }
 
+// The argument record and the wire pieces of the uniform channels (hea_density_grad.hip, hea_density_wide_grad.hip)
+struct DensGradArgs {
+    DensArgs f;                             // the forward's arguments (f.pred: the caller's pred or NULL; f.sd = NULL)
+    const double* w;                        // ansatz angles [blk, 3, n]
+    double o1_keep, o1_mix, o1_off;         // one-qubit channel on O (the forward's) ...
+    double r1_keep, r1_mix, r1_off;         // ... and its inverse on rho
+    double o2_keep, o2_mix, r2_keep, r2_mix;
+    double* pred_ws;                        // [B]
+    double* rec;                            // [E + 3 n blk][B]: d pred_b / d x[b, e], then d pred_b / d w[s, k, q]
+};
+
+// one-qubit channel with given coefficients (the forward's on O, the inverse's on rho)
+template <int S>
+__device__ __forceinline__ void channel1(double2 (&e)[16], double keep, double mix, double off) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int b = S == 1 ? 4 * m : m;
+        const double2 d0 = e[b], d1 = e[b + 3 * S];
+        e[b] = make_double2(keep * d0.x + mix * d1.x, keep * d0.y + mix * d1.y);
+        e[b + 3 * S] = make_double2(keep * d1.x + mix * d0.x, keep * d1.y + mix * d0.y);
+        e[b + S].x *= off; e[b + S].y *= off;
+        e[b + 2 * S].x *= off; e[b + 2 * S].y *= off;
+    }
+}
+
+// encoding of wire q: channel, trace (slot 3 of the wire's four), RX^dagger
+template <int S>
+__device__ __forceinline__ void undo_encoding(double2 (&e)[16], double2 (&o)[16], const DensGradArgs& a, double2 c, double* tr) {
+    channel1<S>(e, a.r1_keep, a.r1_mix, a.r1_off);
+    channel1<S>(o, a.o1_keep, a.o1_mix, a.o1_off);
+    tr[3] = pinned(trace16<S, 0>(o, e));
+    unrotate_x<S>(e, c.x, c.y);
+    unrotate_x<S>(o, c.x, c.y);
+}
+
+// wire q's gates of sub-layer s in reverse; tr[k] = this thread's share of d pred / d w[s, k, q], tr[3] of d pred / d x[col + q]
+template <int N, int S>
+__device__ __forceinline__ void undo_wire(double2 (&e)[16], double2 (&o)[16], const DensGradArgs& a, const double2* csr, int s,
+                                          int col, bool enc, int q, double* tr) {
+    channel1<S>(e, a.r1_keep, a.r1_mix, a.r1_off);
+    channel1<S>(o, a.o1_keep, a.o1_mix, a.o1_off);
+    undo_rotations<N, S>(e, o, a.w, s, q, tr);
+    if (enc) undo_encoding<S>(e, o, a, csr[col + q], tr);
+}
+
 // What the passes need of the workgroup: the row's rho and O, its rank and fold, where its record goes
 template <int N> struct RowCtx {
     static constexpr int TPR = 1 << (2 * N - 4), WPR = TPR > 64 ? TPR / 64 : 1;
@@ -264,6 +310,20 @@ struct GradBatch {
     char* ws; hipStream_t st;
 };
 
+// the argument record of the uniform channels for one batch: the forward's arguments, the channels on O and their inverses on rho
+DensGradArgs dens_grad_args(const GradBatch& b, const qhea_noise* noise) {
+    DensGradArgs a{};
+    a.f = dens_args(b.desc, b.mi, noise, b.params, b.ham_diag, b.batch, b.gates, b.cs);
+    a.f.pred = b.pred; a.f.sd = nullptr;
+    a.w = b.params + b.mi.off_ans;
+    a.o1_keep = a.f.d1_keep; a.o1_mix = a.f.d1_mix; a.o1_off = a.f.d1_off;
+    a.r1_off = 1.0 / a.f.d1_off; a.r1_keep = a.f.d1_keep * a.r1_off; a.r1_mix = -a.f.d1_mix * a.r1_off;
+    a.o2_keep = a.f.d2_keep; a.o2_mix = a.f.d2_mix;
+    a.r2_keep = 1.0 / a.f.d2_keep; a.r2_mix = -a.f.d2_mix * a.r2_keep;
+    a.pred_ws = b.pred_ws; a.rec = b.rec;
+    return a;
+}
+
 // The body of the gradient units' entry points.  A unit record U (DensGradUnit of hea_density_grad.hip, DevGradUnit of
 // hea_density_device_grad.hip) gives
 //   Noise                              the call's noise setting (qhea_noise, qhea_device_noise)
@@ -271,6 +331,7 @@ struct GradBatch {
 //                                      of every other check; false: after U::check and before the return of a call without steps
 //   workspace_bytes(mi, B)             the call's workspace for B rows
 //   check(desc, ham_diag, noise, count, trunk, required, workspace, stream, c)      what opens the call
+//   batch_ok(mi, B)                    whether the unit's grids reach B rows (QHEA_EINVAL otherwise, ahead of the workspace check)
 //   once(mi, noise, ws, bmax, st)      what is launched once per call, or nothing
 //   launch_bwd(b, noise)               its argument record's fill and its backward kernel for b.mi.n
 
@@ -306,6 +367,7 @@ int grad_loss_grad(const qhea_model_desc* desc, int64_t batch, const double* bra
     NoisyCall c;
     int rc = U::check(desc, ham_diag, noise, batch, trunk, {branch, y, params, grad}, workspace, stream, c);
     if (rc != QHEA_OK || c.empty) return rc;
+    if (!U::batch_ok(c.mi, batch)) return QHEA_EINVAL;
     if (!workspace || workspace_bytes < U::workspace_bytes(c.mi, batch)) return QHEA_EWORKSPACE;
     rc = U::once(c.mi, noise, c.ws, batch, c.st);
     if (rc != QHEA_OK) return rc;
@@ -325,7 +387,7 @@ int grad_train_steps(const qhea_model_desc* desc, const TrainCall& call, const d
     if (call.first_step < 1) return QHEA_EINVAL;
     if (c.empty) return QHEA_OK;
     const int64_t bmax = call_max_batch(call, c.mi.P, *desc);
-    if (bmax < 0) return QHEA_EINVAL;
+    if (bmax < 0 || !U::batch_ok(c.mi, bmax)) return QHEA_EINVAL;
     if (!call.workspace || call.workspace_bytes < U::workspace_bytes(c.mi, bmax)) return QHEA_EWORKSPACE;    // (every region grows with the batch)
     rc = U::once(c.mi, noise, c.ws, bmax, c.st);
     if (rc != QHEA_OK) return rc;

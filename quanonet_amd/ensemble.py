@@ -101,6 +101,9 @@ class EnsembleSolver:
             # the member launches train the ideal circuit; a member that silently ignored its noise would be a wrong run
             raise ValueError(f"{type(self).__name__}: config key train_noise is not supported in member launches "
                              "(noise-aware training runs one model per PTSolver)")
+        if any(c.get('train_noise_exact') is not None for c in self.configs):
+            raise ValueError(f"{type(self).__name__}: config key train_noise_exact is not supported in member launches "
+                             "(noise-aware training runs one model per PTSolver)")
         if any(c.get('train_device_noise') is not None for c in self.configs):
             raise ValueError(f"{type(self).__name__}: config key train_device_noise is not supported in member launches "
                              "(training under a DeviceNoise runs one model per PTSolver)")

@@ -480,6 +480,35 @@ def exact_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
     return _lib.model_loss_grad_noisy_exact(desc, branch, trunk, y, flat, noise.params(), inv, grad, ham_diag=ham_diag)
 
 
+def wide_exact_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None):
+    """
+    exact_noisy_loss_and_grad for n = 2..9: the flat [P + 2] tensor.  n <= 6 is exact_noisy_loss_and_grad itself (bitwise).
+    n = 7..9 runs qhea_model_loss_grad_noisy_exact_wide: the same adjoint walk with rho and the observable of all rows in device
+    memory, 2 x 4^n x 16 bytes per row, on the tiles of wide_exact_noisy_predict, whose pred this call's loss is built on bit
+    for bit.  A NoiseModel only; the guard of exact_noisy_loss_and_grad (amplification(model, noise) <= 12) applies.
+    """
+    if isinstance(noise, DeviceNoise):
+        raise ValueError("wide_exact_noisy_loss_and_grad takes a NoiseModel, not a DeviceNoise: the tiled reverse walk carries the "
+                         "uniform channels only; device_noisy_loss_and_grad differentiates a DeviceNoise exactly at n <= 6 and "
+                         "device_trajectory_loss_and_grad by quantum-jump trajectories at n = 7..12")
+    if not hasattr(model, 'fused_desc'):
+        raise TypeError("wide_exact_noisy_loss_and_grad takes a QuanONetPT or HEAQNNPT model")
+    n = int(model.fused_desc().n_qubits)
+    if n <= 6:
+        return exact_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total)
+    if n >= 10:
+        raise ValueError(f"wide_exact_noisy_loss_and_grad covers n = 2..9 (got n = {n}): a density matrix of 4^{n} elements per "
+                         "row is not carried; sampled_noisy_loss_and_grad differentiates the sampled loss at n = 10..12")
+    desc, flat, ham_diag, branch, trunk = _call_args(model, inputs, 'wide_exact_noisy_loss_and_grad')
+    B = branch.shape[0]
+    y = y.detach().to(torch.float64).reshape(-1).contiguous()
+    grad = torch.zeros(flat.numel() + 2, dtype=torch.float64, device=branch.device)
+    if B == 0:
+        return grad
+    inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
+    return _lib.model_loss_grad_noisy_exact_wide(desc, branch, trunk, y, flat, noise.params(), inv, grad, ham_diag=ham_diag)
+
+
 def noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, row0=0):
     """
     The MSE loss of the SAMPLED noisy prediction -- noisy_predict(model, inputs, noise, row0=row0) in expectation mode, the mean

@@ -345,6 +345,22 @@ def _train_noise_states(v, train_noise=None, train_device_noise=None, sampling_k
     return 'stored'
 
 
+def _train_noise_exact(v, train_noise=None, other_keys=()):
+    """config value / argument `train_noise_exact` -> None (train_noise alone trains on the exact loss at n <= 6 and refuses
+    beyond) or 'wide' (the exact noisy loss for every n it exists for: n <= 6 as train_noise alone, n = 7..9 on tiles)"""
+    if v is None:
+        return None
+    if v != 'wide':
+        raise ValueError(f"train_noise_exact must be None or 'wide' (the exact noisy loss for n = 2..9; got {v!r})")
+    if other_keys:
+        raise ValueError(f"train_noise_exact='wide' does not combine with {other_keys[0]}: it asks for the exact loss under the "
+                         "NoiseModel of train_noise, neither a sampled loss nor a DeviceNoise")
+    if train_noise is None:
+        raise ValueError("train_noise_exact='wide' needs train_noise: it says which calls differentiate the exact loss under "
+                         "that NoiseModel")
+    return v
+
+
 def _train_sampling(v, key='train_sampling'):
     """config value / argument `train_sampling` or `train_trajectories` -> Sampling or None (a Sampling, or its asdict() form)"""
     if v is None:
@@ -358,7 +374,7 @@ def _train_sampling(v, key='train_sampling'):
 
 
 # The loss a DataParallelTrainer trains on, chosen once in __init__ by one function per family (_ideal_loss, _exact_loss,
-# _exact_device_loss, _sampled_loss, _jump_loss):
+# _exact_wide_loss, _exact_device_loss, _sampled_loss, _jump_loss):
 #   loss_grad(data, inv, grad, step, row0, ham_diag)    behind loss_and_grad; data = (desc, branch, trunk, y, params), step the
 #                                                       Adam count of the update the gradient is for, row0 its first global row
 #   steps(call, ham_diag)                               behind _steps; call = a steps entry's arguments up to weight_decay
@@ -395,9 +411,15 @@ class DataParallelTrainer:
 
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
                  fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None,
-                 train_sampling=None, train_trajectories=None, train_jump_trajectories=None, train_noise_states=None):
+                 train_sampling=None, train_trajectories=None, train_jump_trajectories=None, train_noise_states=None,
+                 train_noise_exact=None):
         self.model = model
         self.train_noise = _train_noise(train_noise)
+        self.train_noise_exact = _train_noise_exact(
+            train_noise_exact, self.train_noise,
+            [k for k, v in (('train_device_noise', train_device_noise), ('train_sampling', train_sampling),
+                            ('train_trajectories', train_trajectories), ('train_jump_trajectories', train_jump_trajectories),
+                            ('train_noise_states', train_noise_states)) if v is not None])
         self.train_device_noise = _train_device_noise(train_device_noise, train_noise)
         self.noise_states = _train_noise_states(
             train_noise_states, self.train_noise, self.train_device_noise,
@@ -498,6 +520,7 @@ class DataParallelTrainer:
         # the loss the run trains on, chosen once: loss_and_grad, train_step and _steps go through this record
         self.train_loss = (self._jump_loss(log) if self.device_sampled else
                            self._sampled_loss(log) if self.train_sampling is not None else
+                           self._exact_wide_loss(log) if self.train_noise_exact is not None else
                            self._exact_loss(log) if self.train_noise is not None else
                            self._exact_device_loss(log) if self.train_device_noise is not None else self._ideal_loss())
 
@@ -592,6 +615,51 @@ class DataParallelTrainer:
             log(f"noise-aware training: the loss and 'loss_train' are the exact noisy MSE under p1={self.train_noise.p1:g} "
                 f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g} (log10 amplification {amp:.2f})")
         return _exact_train_loss(_lib.model_loss_grad_noisy_exact, _lib.model_train_steps_noisy_exact, self.train_noise.params)
+
+    def _exact_wide_loss(self, log):
+        """train_noise with train_noise_exact='wide': the exact noisy loss for every n it exists for"""
+        # n <= 6 is the run that train_noise alone describes (qhea_model_loss_grad_noisy_exact); n = 7..9 trains on the same
+        # loss with rho and O tiled through the workspace (qhea_model_loss_grad_noisy_exact_wide): refuse here what it would
+        if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+            raise ValueError("train_noise_exact needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP device, "
+                             "Adam with betas / eps / weight_decay only)")
+        n = self.desc.n_qubits
+        if n <= 6:
+            return self._exact_loss(log)
+        from . import _lib
+        amp = _lib.model_exact_noisy_log10_amplification(self.desc, self.train_noise.params())
+        if n > 9 or not amp <= 12.0:
+            raise ValueError(f"train_noise_exact='wide': the exact noisy loss takes n <= 9 and log10 amplification <= 12 (this "
+                             f"model: n = {n}, {amp:.2f}); train_trajectories beside train_noise trains n = 7..12 on the "
+                             "sampled loss; see quanonet_amd.noise.amplification")
+        if self.peer_fused:
+            # several ranks: loss_and_grad on the shard, then the exchange as a kernel of its own, the route of _exact_loss
+            self.peer_fused = False
+            self.dp_exchange_reason = ("peer exchange as a separate kernel: the noise-aware step has no reduce kernel with "
+                                       "the exchange inside")
+        base = _exact_train_loss(_lib.model_loss_grad_noisy_exact_wide, _lib.model_train_steps_noisy_exact_wide,
+                                 self.train_noise.params)
+        said = []
+
+        def say(rows):
+            # once, at the first call: only then is the batch known that the workspace is sized for
+            if log is not None and not said:
+                said.append(rows)
+                log(f"noise-aware training: the loss and 'loss_train' are the exact noisy MSE under p1={self.train_noise.p1:g} "
+                    f"p2={self.train_noise.p2:g} readout={self.train_noise.readout:g} (log10 amplification {amp:.2f}); rho and O "
+                    f"are tiled through device memory, workspace "
+                    f"{_lib.model_exact_noisy_wide_grad_workspace_bytes(self.desc, rows) / 2**20:.1f} MiB for steps of up to "
+                    f"{rows} rows")
+
+        def loss_grad(data, inv, grad, step, row0, ham_diag):
+            say(int(data[3].numel()))                                    # data = (desc, branch, trunk, y, params)
+            return base.loss_grad(data, inv, grad, step, row0, ham_diag)
+
+        def steps(call, ham_diag):
+            bounds = call[1]                                             # call = (desc, bounds, global_batches, ...)
+            say(max((int(b) - int(a) for a, b in zip(bounds[:-1], bounds[1:])), default=0))
+            return base.steps(call, ham_diag)
+        return base._replace(loss_grad=loss_grad, steps=steps)
 
     def _exact_device_loss(self, log):
         """train_device_noise alone, rho walked back through inverses or replayed from stored states (train_noise_states)"""
@@ -924,7 +992,8 @@ class PTSolver:
                                            train_sampling=config.get('train_sampling'),
                                            train_trajectories=config.get('train_trajectories'),
                                            train_jump_trajectories=config.get('train_jump_trajectories'),
-                                           train_noise_states=config.get('train_noise_states'))
+                                           train_noise_states=config.get('train_noise_states'),
+                                           train_noise_exact=config.get('train_noise_exact'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None
