@@ -828,6 +828,62 @@ int    qhea_model_train_steps_noisy_device_exact_stored(const qhea_model_desc* d
                                                         void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The same loss and exact gradient for n = 7..9 (library version 660): the quantity, the inverse walk, the [P+2] buffer and the
+ * arguments of qhea_model_loss_grad_noisy_device_exact / qhea_model_train_steps_noisy_device_exact, on the tiles of
+ * qhea_model_loss_grad_noisy_exact_wide.  pred is the prediction of qhea_model_forward_noisy_device_exact_wide, bitwise: the
+ * forward sweep is that call's launch sequence (same value-table, stage and read-out kernels).
+ *
+ * rho and O of all rows live in the workspace.  After the forward sweep one launch writes O = diag(h' - mean h') with h' from
+ * the asymmetric readout; an X / Y read-out takes rho and O through the daggers of the basis change (two launches, no noise).
+ * A reverse sub-layer is two launches over rows * 4^(n-6) workgroups of 256 threads with the tiles of rho and O in 2 x 64 KiB
+ * of LDS: stage B with the ring passes j = n-1..5, then stage A with j = 4..0.  Per pass, in global wires: the TGT site of
+ * wire j and the CTL site of wire (j + 1) mod n (inverse form on rho, adjoint form on O), D2 of slot j (the slot's inverse on
+ * rho, its forward factors on O) with the CNOT, then per pending wire (pass 0: wire 0; every pass j <= n-2: wire j + 1) the
+ * ROT site, the three traces with their un-rotations, and in a block's first sub-layer the ENC site, its trace and RX^dagger.
+ * A block without sub-layers is two launches, wires 6..n-1 then 0..5: ENC site, trace, RX^dagger.  Traces are written as one
+ * partial per (angle, row, tile) and folded in tile order by one launch at the end, as in the uniform call.
+ * Constants: a table of [stage][local wire] records (the 66-double record of the n <= 6 call; the forward form and the readout
+ * entries stay zero) holds the inverse and adjoint form of every site and the four D2 factors of every slot at the local index
+ * the pass uses; one table kernel per call (one workgroup) places what the host composed per global wire; the reverse stages
+ * read a site's constants where they use them.
+ *
+ * Guard: qhea_model_device_noisy_log10_amplification (it answers at every n = 2..12) must be <= 7, the bound of the n <= 6
+ * call: the numpy probe of tests/test_device_exact_noisy_wide_training_abi.py (inverse against stored walk, n = 7 with 20
+ * sub-layers, n = 8 with 10) shows 9.8e-15 and 6.2e-15 at 7, 6.7e-14 and 3.1e-14 at 8.
+ * Errors, all before anything is launched and with the outputs untouched, in this order: a bad descriptor and the setting's
+ * QHEA_EINVAL cases; QHEA_EUNSUPPORTED for n outside 7..9 and for the guard (a singular channel, p1 >= 3/4, p2 >= 15/16 are
+ * +inf); then the errors of qhea_model_loss_grad_noisy_exact (read-out, negative batch, NULL arrays); QHEA_EINVAL for a batch
+ * (or a largest step) above INT_MAX >> 2 (n - 6); QHEA_EWORKSPACE.  train_steps reports first_step < 1 where
+ * qhea_model_train_steps_noisy_device_exact reports it (after these checks' QHEA_EINVAL / QHEA_EUNSUPPORTED cases, before the
+ * return of a call without steps).  An empty batch (or n_steps = 0) returns QHEA_OK.
+ * Workspace: qhea_model_device_noisy_wide_grad_workspace_bytes (0 for a bad descriptor, batch < 0 or n outside 7..9):
+ * qhea_model_exact_noisy_wide_grad_workspace_bytes for the largest step plus the table, 2 * 6 * 66 doubles rounded up to 256
+ * bytes.
+ * Launches per step: 6 + 4 (S + Z + R), S sub-layers, Z blocks without sub-layers, R = 1 for an X / Y read-out (one more for
+ * a circuit without blocks), plus the table kernel once per call.  No allocation, no synchronisation (hipGraph-capturable, one
+ * linear chain), no atomics, fixed summation orders: bitwise reproducible, a row's pred and records independent of the batch,
+ * the grid and the chunking.  qhea_model_train_steps_noisy_device_exact_wide is bitwise a loop of
+ * qhea_model_loss_grad_noisy_device_exact_wide + qhea_adam_step; its workspace must fit the largest step.
+ */
+size_t qhea_model_device_noisy_wide_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+int    qhea_model_loss_grad_noisy_device_exact_wide(const qhea_model_desc* desc, int64_t batch,
+                                                    const double* branch, const double* trunk, const double* y /*DEVICE [B]*/,
+                                                    const double* params, const double* ham_diag,
+                                                    const qhea_device_noise* dn /*HOST*/, double inv_batch_total,
+                                                    double* grad /*DEVICE [P+2]*/, double* pred /*DEVICE [B] or NULL*/,
+                                                    void* workspace, size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_device_exact_wide(const qhea_model_desc* desc, int64_t n_steps,
+                                                      const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                                      const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                                      const double* y /*DEVICE*/, double* params /*DEVICE flat, updated in place*/,
+                                                      const double* ham_diag, const qhea_device_noise* dn /*HOST*/,
+                                                      const double* inv_batch_total /*HOST [n_steps]*/,
+                                                      double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                                      double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr,
+                                                      double beta1, double beta2, double eps, double weight_decay,
+                                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Noisy forward under the calibrated device noise model by quantum-jump (Monte-Carlo wave-function) trajectories: an unbiased
  * estimate of pred of qhea_model_forward_noisy_device_exact, for the qubit counts that call cannot reach (n = 7..9) and for
  * finite shots at any n = 2..9 -- what an Estimator with default_shots = S returns on that device.  Arguments, estimators and

@@ -1,6 +1,6 @@
 // hea_density_grad.hpp -- the reverse walk through the density matrix that the gradient units share (hea_density_grad.hip:
 // the uniform channels of qhea_noise; hea_density_device_grad.hip: the channel sites of qhea_device_noise; hea_density_wide_grad.hip: the uniform channels on the
-// tiles of n = 7..9): the two compiler
+// tiles of n = 7..9; hea_density_device_wide_grad.hip: the channel sites on those tiles): the two compiler
 // pins, a thread's share of a trace, the un-rotations, the reverse of the CNOT with its two-qubit channel, the row context with
 // the sum of a pass' traces over the row, the read-out basis passes, the workspace layout and the reduce launch.  The device
 // code sits in an unnamed namespace like hea_density.hpp's: each unit compiles its own copy into its own kernels.  Host side:
@@ -325,7 +325,7 @@ DensGradArgs dens_grad_args(const GradBatch& b, const qhea_noise* noise) {
 }
 
 // The body of the gradient units' entry points.  A unit record U (DensGradUnit of hea_density_grad.hip, DevGradUnit of
-// hea_density_device_grad.hip) gives
+// hea_density_device_grad.hip, WideGradUnit and DevWideGradUnit of the two tiled units) gives
 //   Noise                              the call's noise setting (qhea_noise, qhea_device_noise)
 //   kStepCheckFirst                    where train_steps reports first_step < 1: true: with the descriptor and n_steps < 0, ahead
 //                                      of every other check; false: after U::check and before the return of a call without steps

@@ -1,5 +1,5 @@
 // hea_device_noise.hpp -- host side of the calibrated device noise model (qhea_device_noise, include/quanonet_hea.h) for the
-// units that evaluate it (hea_density_device.hip, hea_density_device_grad.hip; the trajectory units hea_noise_device.hip and
+// units that evaluate it (hea_density_device.hip, hea_density_device_grad.hip and their tiled siblings; the trajectory units hea_noise_device.hip and
 // hea_noise_device_wide.hip): the checks of a setting and what opens a density-matrix call under one, the composition of its
 // channels into the four sites per wire and their form in the kernels' tables, and for the trajectories the (gamma, pz) of every
 // site and the fill of a unit's table of per-call thresholds.  No device code.

@@ -107,6 +107,9 @@ class EnsembleSolver:
         if any(c.get('train_device_noise') is not None for c in self.configs):
             raise ValueError(f"{type(self).__name__}: config key train_device_noise is not supported in member launches "
                              "(training under a DeviceNoise runs one model per PTSolver)")
+        if any(c.get('train_device_noise_exact') is not None for c in self.configs):
+            raise ValueError(f"{type(self).__name__}: config key train_device_noise_exact is not supported in member launches "
+                             "(training under a DeviceNoise runs one model per PTSolver)")
         if any(c.get('train_sampling') is not None for c in self.configs):
             raise ValueError(f"{type(self).__name__}: config key train_sampling is not supported in member launches "
                              "(sampled-trajectory training runs one model per PTSolver)")

@@ -361,6 +361,23 @@ def _train_noise_exact(v, train_noise=None, other_keys=()):
     return v
 
 
+def _train_device_noise_exact(v, train_device_noise=None, other_keys=()):
+    """config value / argument `train_device_noise_exact` -> None (train_device_noise alone trains on the exact loss at n <= 6
+    and refuses beyond) or 'wide' (the exact loss under the DeviceNoise for every n it exists for: n <= 6 as train_device_noise
+    alone, n = 7..9 on tiles).  `other_keys`: the keys set beside it that it does not combine with."""
+    if v is None:
+        return None
+    if v != 'wide':
+        raise ValueError(f"train_device_noise_exact must be None or 'wide' (the exact device-noisy loss for n = 2..9; got {v!r})")
+    if other_keys:
+        raise ValueError(f"train_device_noise_exact='wide' does not combine with {other_keys[0]}: it asks for the exact loss "
+                         "under the DeviceNoise of train_device_noise, neither a uniform NoiseModel nor a sampled loss")
+    if train_device_noise is None:
+        raise ValueError("train_device_noise_exact='wide' needs train_device_noise: it says which calls differentiate the exact "
+                         "loss under that DeviceNoise")
+    return v
+
+
 def _train_sampling(v, key='train_sampling'):
     """config value / argument `train_sampling` or `train_trajectories` -> Sampling or None (a Sampling, or its asdict() form)"""
     if v is None:
@@ -374,7 +391,7 @@ def _train_sampling(v, key='train_sampling'):
 
 
 # The loss a DataParallelTrainer trains on, chosen once in __init__ by one function per family (_ideal_loss, _exact_loss,
-# _exact_wide_loss, _exact_device_loss, _sampled_loss, _jump_loss):
+# _exact_wide_loss, _exact_device_loss, _exact_device_wide_loss, _sampled_loss, _jump_loss):
 #   loss_grad(data, inv, grad, step, row0, ham_diag)    behind loss_and_grad; data = (desc, branch, trunk, y, params), step the
 #                                                       Adam count of the update the gradient is for, row0 its first global row
 #   steps(call, ham_diag)                               behind _steps; call = a steps entry's arguments up to weight_decay
@@ -412,7 +429,7 @@ class DataParallelTrainer:
     def __init__(self, model, lr=1e-4, world_size=1, dist=None, optimizer='adam', optimizer_kwargs=None,
                  fused='auto', peer_exchange=True, log=None, train_noise=None, train_device_noise=None,
                  train_sampling=None, train_trajectories=None, train_jump_trajectories=None, train_noise_states=None,
-                 train_noise_exact=None):
+                 train_noise_exact=None, train_device_noise_exact=None):
         self.model = model
         self.train_noise = _train_noise(train_noise)
         self.train_noise_exact = _train_noise_exact(
@@ -425,6 +442,11 @@ class DataParallelTrainer:
             train_noise_states, self.train_noise, self.train_device_noise,
             [k for k, v in (('train_sampling', train_sampling), ('train_trajectories', train_trajectories),
                             ('train_jump_trajectories', train_jump_trajectories)) if v is not None])
+        self.train_device_noise_exact = _train_device_noise_exact(
+            train_device_noise_exact, self.train_device_noise,
+            [k for k, v in (('train_noise', train_noise), ('train_sampling', train_sampling),
+                            ('train_trajectories', train_trajectories), ('train_jump_trajectories', train_jump_trajectories))
+             if v is not None])
         # train_jump_trajectories beside train_device_noise: what train_trajectories means there, for every n a quantum-jump
         # gradient exists for (7..12); train_trajectories there keeps the range it was introduced with (7..9)
         if train_jump_trajectories is not None:
@@ -522,6 +544,7 @@ class DataParallelTrainer:
                            self._sampled_loss(log) if self.train_sampling is not None else
                            self._exact_wide_loss(log) if self.train_noise_exact is not None else
                            self._exact_loss(log) if self.train_noise is not None else
+                           self._exact_device_wide_loss(log) if self.train_device_noise_exact is not None else
                            self._exact_device_loss(log) if self.train_device_noise is not None else self._ideal_loss())
 
     def _ideal_loss(self):
@@ -688,7 +711,8 @@ class DataParallelTrainer:
                              f"amplification {amp:.2f}): n <= 6 and a log10 amplification within the bound of "
                              "include/quanonet_hea.h are needed; see quanonet_amd.noise.device_amplification.  At "
                              "n = 7..9 train_trajectories beside train_device_noise trains on quantum-jump trajectories, "
-                             "and train_jump_trajectories there does at n = 7..12")
+                             "and train_jump_trajectories there does at n = 7..12; train_device_noise_exact='wide' beside "
+                             "train_device_noise trains n = 7..9 on the exact loss")
         if self.peer_fused:
             self.peer_fused = False
             self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
@@ -704,6 +728,66 @@ class DataParallelTrainer:
         calls = ((_lib.model_loss_grad_noisy_device_exact_stored, _lib.model_train_steps_noisy_device_exact_stored) if stored else
                  (_lib.model_loss_grad_noisy_device_exact, _lib.model_train_steps_noisy_device_exact))
         return _exact_train_loss(*calls, lambda: self.train_device_noise.params(n))
+
+    def _exact_device_wide_loss(self, log):
+        """train_device_noise with train_device_noise_exact='wide': the exact loss under the device model for every n it exists
+        for"""
+        # n <= 6 is the run that train_device_noise alone describes (train_noise_states honoured); n = 7..9 trains on the same
+        # loss with rho and O tiled through the workspace (qhea_model_loss_grad_noisy_device_exact_wide, the inverse walk):
+        # refuse here what it would
+        if self.desc is None or not isinstance(self.optimizer, FlatAdam):
+            raise ValueError("train_device_noise_exact needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP "
+                             "device, Adam with betas / eps / weight_decay only)")
+        n = self.desc.n_qubits
+        if n <= 6:
+            return self._exact_device_loss(log)
+        if n > 9:
+            raise ValueError(f"train_device_noise_exact='wide': the exact device-noisy loss takes n <= 9 (this model: n = {n}): "
+                             "no density matrix of that size is carried; train_jump_trajectories beside train_device_noise "
+                             "trains n = 7..12 on quantum-jump trajectories")
+        if self.noise_states == 'stored':
+            raise ValueError("train_device_noise_exact='wide' with train_noise_states='stored' at n >= 7: the stored-state walk "
+                             "does not exist on tiles (its snapshots would take units x rows x 16 x 4^n bytes); n = 7..9 trains "
+                             "through the inverse walk, within its bound on device_amplification")
+        from . import _lib
+        try:
+            rec = self.train_device_noise.params(n)
+            amp = _lib.model_device_noisy_log10_amplification(self.desc, rec)
+            refused = _lib.model_device_noisy_wide_refused(self.desc, rec)       # the library's own checks and bound
+        except _lib.QheaError as e:
+            raise ValueError(f"train_device_noise: {e}") from e
+        if refused:
+            raise ValueError(f"train_device_noise_exact='wide': the library refuses this model under this DeviceNoise (n = {n}, "
+                             f"log10 A_dev = {amp:.2f}; the inverse walk's bound is 7 and a singular channel is inf); see "
+                             "quanonet_amd.noise.device_amplification.  train_trajectories / train_jump_trajectories beside "
+                             "train_device_noise train on quantum-jump trajectories whatever A_dev is")
+        if self.peer_fused:
+            # several ranks: loss_and_grad on the shard, then the exchange as a kernel of its own, the route of _exact_loss
+            self.peer_fused = False
+            self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
+                                       "with the exchange inside")
+        base = _exact_train_loss(_lib.model_loss_grad_noisy_device_exact_wide, _lib.model_train_steps_noisy_device_exact_wide,
+                                 lambda: self.train_device_noise.params(n))
+        said = []
+
+        def say(rows):
+            # once, at the first call: only then is the batch known that the workspace is sized for
+            if log is not None and not said:
+                said.append(rows)
+                log("device-noise training: the loss and 'loss_train' are the exact device-noisy MSE under the DeviceNoise of "
+                    f"train_device_noise (log10 A_dev {amp:.2f}); rho and O are tiled through device memory, workspace "
+                    f"{_lib.model_device_noisy_wide_grad_workspace_bytes(self.desc, rows) / 2**20:.1f} MiB for steps of up to "
+                    f"{rows} rows")
+
+        def loss_grad(data, inv, grad, step, row0, ham_diag):
+            say(int(data[3].numel()))                                    # data = (desc, branch, trunk, y, params)
+            return base.loss_grad(data, inv, grad, step, row0, ham_diag)
+
+        def steps(call, ham_diag):
+            bounds = call[1]                                             # call = (desc, bounds, global_batches, ...)
+            say(max((int(b) - int(a) for a, b in zip(bounds[:-1], bounds[1:])), default=0))
+            return base.steps(call, ham_diag)
+        return base._replace(loss_grad=loss_grad, steps=steps)
 
     def broadcast_parameters(self):
         self.dist.broadcast(self.pflat, src=0)
@@ -993,7 +1077,8 @@ class PTSolver:
                                            train_trajectories=config.get('train_trajectories'),
                                            train_jump_trajectories=config.get('train_jump_trajectories'),
                                            train_noise_states=config.get('train_noise_states'),
-                                           train_noise_exact=config.get('train_noise_exact'))
+                                           train_noise_exact=config.get('train_noise_exact'),
+                                           train_device_noise_exact=config.get('train_device_noise_exact'))
         self.lr_scheduler = self._build_scheduler()
         self.best_loss = float('inf')
         self.best_model_path = None
