@@ -884,6 +884,64 @@ int    qhea_model_train_steps_noisy_device_exact_wide(const qhea_model_desc* des
                                                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The same two calls past the guard: rho replayed from stored states on tiles (library version 670).
+ *
+ * qhea_model_loss_grad_noisy_device_exact_wide_stored / qhea_model_train_steps_noisy_device_exact_wide_stored compute what the
+ * two calls above compute -- same arguments, same [P+2] buffer, n = 7..9 -- for settings whose log10 A_dev is past 7, the way
+ * the _stored calls of version 620 do for n <= 6.  A unit is one sub-layer (a block's first sub-layer carries the block's
+ * encoding gates) or the encoding of a block without sub-layers; U = sub-layers + blocks without sub-layers.  snap[u] holds
+ * every row's rho after unit u, row r at element (u * batch + r) * 4^n (64-bit arithmetic), behind the regions of the calls
+ * above.
+ * Forward sweep: the launch sequence above with the same value-table, stage B and read-out kernels; stage A of unit u is the
+ * same stage loading the row from snap[u-1] (u = 0: nothing) and storing it to snap[u], stage B of unit u works in place on
+ * snap[u].  Stage A of an X / Y basis change loads snap[U-1] and stores to the running rho buffer of the calls above, so the
+ * last snapshot stays; the read-out kernel reads that buffer (X / Y) or snap[U-1] (Z).  The arithmetic is untouched: pred is
+ * bitwise that of the calls above and of qhea_model_forward_noisy_device_exact_wide.
+ * Reverse walk: the reverse stages above -- same passes, same table, same trace partials, fold and reduce.  Stage B of unit u
+ * loads its rho tile from snap[u] and stores it to the running buffer (the snapshots are read-only after the forward sweep);
+ * stage A loads what stage B stored and stores no rho: the next unit starts from snap[u-1].  O is walked in place as above, and
+ * the daggers of the basis change are applied as above.  A circuit without blocks has U = 0, takes no snapshot and runs the
+ * launches of the calls above.
+ * Guard: rho never carries more than one unit's worth of inverse walk, so the bound is asked of one unit:
+ * qhea_model_device_noisy_log10_layer_amplification (it answers at every n = 2..12) must be <= 7 -- the bound above, measured
+ * on whole circuits, of which one unit is one.  The total log10 A_dev is no reason to refuse.
+ * Errors, all before anything is launched and with the outputs untouched, in the order of the calls above: a bad descriptor
+ * and the setting's QHEA_EINVAL cases; QHEA_EUNSUPPORTED for n outside 7..9, then for a layer amplification above 7 (a singular
+ * channel is +inf); the shared errors; QHEA_EINVAL for a batch (or a largest step) above INT_MAX >> 2 (n - 6);
+ * QHEA_EWORKSPACE.  train_steps reports first_step < 1 where the call above reports it.  The _stored calls of version 620
+ * keep refusing n >= 7, and the calls above keep their guard on the total.
+ * Workspace: qhea_model_device_noisy_wide_stored_grad_workspace_bytes (0 for a bad descriptor, batch < 0 or n outside 7..9) =
+ * qhea_model_device_noisy_wide_grad_workspace_bytes + U * batch * 16 * 4^n rounded up to 256 bytes: 4 MiB per row and unit at
+ * n = 9 (Net20-2-10-2, 60 units: 240 MiB per row), so the region passes 4 GiB at sizes people run.
+ * Launches per step: 6 + 4 (S + Z + R) as above, S sub-layers, Z blocks without sub-layers, R = 1 for an X / Y read-out, plus
+ * the table kernel once per call: 1 prep, 1 value table, 2 (S + Z + R) forward stages, 1 read-out, 1 O_N, 2 R daggers,
+ * 2 (S + Z) reverse stages, 1 fold, 1 reduce.  By byte count (an estimate) a step moves no more than the call above and one rho store
+ * per unit less.  No allocation, no synchronisation (hipGraph-capturable, one linear chain), no atomics, fixed summation orders:
+ * bitwise reproducible, a row's pred and records independent of the batch, the grid and the chunking.
+ * qhea_model_train_steps_noisy_device_exact_wide_stored is bitwise a loop of the loss_grad call + qhea_adam_step; its workspace
+ * must fit the largest step.
+ */
+size_t qhea_model_device_noisy_wide_stored_grad_workspace_bytes(const qhea_model_desc* desc, int64_t batch);
+int    qhea_model_loss_grad_noisy_device_exact_wide_stored(const qhea_model_desc* desc, int64_t batch,
+                                                           const double* branch, const double* trunk,
+                                                           const double* y /*DEVICE [B]*/, const double* params,
+                                                           const double* ham_diag, const qhea_device_noise* dn /*HOST*/,
+                                                           double inv_batch_total, double* grad /*DEVICE [P+2]*/,
+                                                           double* pred /*DEVICE [B] or NULL*/, void* workspace,
+                                                           size_t workspace_bytes, void* stream);
+int    qhea_model_train_steps_noisy_device_exact_wide_stored(const qhea_model_desc* desc, int64_t n_steps,
+                                                             const int64_t* row_begin /*HOST [n_steps+1]*/,
+                                                             const double* branch /*DEVICE*/, const double* trunk /*DEVICE or NULL*/,
+                                                             const double* y /*DEVICE*/,
+                                                             double* params /*DEVICE flat, updated in place*/,
+                                                             const double* ham_diag, const qhea_device_noise* dn /*HOST*/,
+                                                             const double* inv_batch_total /*HOST [n_steps]*/,
+                                                             double* grad /*DEVICE [n_steps][grad_stride]*/, int64_t grad_stride,
+                                                             double* exp_avg, double* exp_avg_sq, int64_t first_step, double lr,
+                                                             double beta1, double beta2, double eps, double weight_decay,
+                                                             void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Noisy forward under the calibrated device noise model by quantum-jump (Monte-Carlo wave-function) trajectories: an unbiased
  * estimate of pred of qhea_model_forward_noisy_device_exact, for the qubit counts that call cannot reach (n = 7..9) and for
  * finite shots at any n = 2..9 -- what an Estimator with default_shots = S returns on that device.  Arguments, estimators and

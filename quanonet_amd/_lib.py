@@ -58,7 +58,9 @@ EXPORTS = ['qhea_version', 'qhea_strerror', 'qhea_device_count', 'qhea_workspace
            'qhea_model_device_noisy_stored_grad_workspace_bytes', 'qhea_model_device_noisy_log10_layer_amplification',
            'qhea_model_loss_grad_noisy_device_exact_stored', 'qhea_model_train_steps_noisy_device_exact_stored',
            'qhea_model_device_noisy_wide_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_device_exact_wide',
-           'qhea_model_train_steps_noisy_device_exact_wide']
+           'qhea_model_train_steps_noisy_device_exact_wide',
+           'qhea_model_device_noisy_wide_stored_grad_workspace_bytes', 'qhea_model_loss_grad_noisy_device_exact_wide_stored',
+           'qhea_model_train_steps_noisy_device_exact_wide_stored']
 
 
 class ModelDesc(ctypes.Structure):
@@ -95,7 +97,7 @@ class SamplingParams(ctypes.Structure):
 
 
 MODEL_QUANONET, MODEL_HEAQNN = 0, 1
-MIN_LIB_VERSION = 660           # 0.6.6: + qhea_model_loss_grad_noisy_device_exact_wide / ..._train_steps_... (exact device-noise gradient at n = 7..9)
+MIN_LIB_VERSION = 670           # 0.6.7: + qhea_model_loss_grad_noisy_device_exact_wide_stored / ..._train_steps_... (stored states at n = 7..9)
 BWD_VARIANTS = {'auto': 0, 'packed': 1, 'pair': 2, 'tri': 3, 'ztri': 4, 'zpacked': 5, 'ztri2': 6, 'zquad': 7, 'zsnap': 8}
 PAULI = {'Z': 0, 'X': 1, 'Y': 2}
 
@@ -318,6 +320,12 @@ def load():
     lib.qhea_model_loss_grad_noisy_device_exact_wide.argtypes = lib.qhea_model_loss_grad_noisy_device_exact.argtypes
     lib.qhea_model_train_steps_noisy_device_exact_wide.restype = ctypes.c_int
     lib.qhea_model_train_steps_noisy_device_exact_wide.argtypes = lib.qhea_model_train_steps_noisy_device_exact.argtypes
+    lib.qhea_model_device_noisy_wide_stored_grad_workspace_bytes.restype = ctypes.c_size_t
+    lib.qhea_model_device_noisy_wide_stored_grad_workspace_bytes.argtypes = [mdp, ctypes.c_int64]
+    lib.qhea_model_loss_grad_noisy_device_exact_wide_stored.restype = ctypes.c_int
+    lib.qhea_model_loss_grad_noisy_device_exact_wide_stored.argtypes = lib.qhea_model_loss_grad_noisy_device_exact.argtypes
+    lib.qhea_model_train_steps_noisy_device_exact_wide_stored.restype = ctypes.c_int
+    lib.qhea_model_train_steps_noisy_device_exact_wide_stored.argtypes = lib.qhea_model_train_steps_noisy_device_exact.argtypes
     lib.qhea_device_noise_singular_site.restype = ctypes.c_int
     lib.qhea_device_noise_singular_site.argtypes = [ctypes.c_int, dnp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     lib.qhea_model_noisy_device_grad_workspace_bytes.restype = ctypes.c_size_t
@@ -1052,6 +1060,14 @@ def _check_device_exact_wide_grad(rc, who):
     _check(rc, who)
 
 
+def _check_device_exact_wide_stored_grad(rc, who):
+    if rc == -2:
+        raise Unsupported(f"{who}: the tiled stored-state device-noise gradient is built for n = 7..9 (n <= 6: the "
+                          "noisy_device_exact_stored calls; n >= 10: the sampled noisy_device_lds calls), or a setting whose "
+                          "largest single unit is ill-conditioned (layer log10 A_dev > 7, or a singular channel)")
+    _check(rc, who)
+
+
 def _sampled_unit(kind):
     return _GradUnit(f'qhea_model_noisy_{kind}_grad_workspace_bytes', 'noise', True, ('noise',),
                      lambda rc, who, desc, records: _check_noisy_wide_grad(rc, who, kind))
@@ -1069,6 +1085,9 @@ _GRAD_UNITS = {'noisy_exact': _exact_unit('qhea_model_exact_noisy_grad_workspace
                'noisy_device_exact_stored': _exact_unit('qhea_model_device_noisy_stored_grad_workspace_bytes'),
                'noisy_device_exact_wide': _GradUnit('qhea_model_device_noisy_wide_grad_workspace_bytes', None, False, ('noise',),
                                                     lambda rc, who, desc, records: _check_device_exact_wide_grad(rc, who)),
+               'noisy_device_exact_wide_stored': _GradUnit('qhea_model_device_noisy_wide_stored_grad_workspace_bytes', None, False,
+                                                           ('noise',), lambda rc, who, desc, records:
+                                                           _check_device_exact_wide_stored_grad(rc, who)),
                'noisy_wide': _sampled_unit('wide'),
                'noisy_lds': _sampled_unit('lds'),
                'noisy_device': _jump_unit('qhea_model_noisy_device_grad_workspace_bytes'),
@@ -1450,6 +1469,47 @@ def model_train_steps_noisy_device_exact_wide(desc, bounds, global_batches, bran
     model_loss_grad_noisy_device_exact_wide + adam_step.
     """
     return _train_steps_call('noisy_device_exact_wide', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg,
+                             exp_avg_sq, first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
+
+
+def model_device_noisy_wide_stored_grad_workspace_bytes(desc, batch, snapshots_only=False):
+    """qhea_model_device_noisy_wide_stored_grad_workspace_bytes (host only): the tiled inverse walk's workspace plus the snapshot
+    region (units x batch x 16 x 4^n bytes, rounded up to 256); snapshots_only: the region alone.  0 for a bad descriptor, a
+    negative batch or n outside 7..9."""
+    lib = load()
+    total = int(lib.qhea_model_device_noisy_wide_stored_grad_workspace_bytes(ctypes.byref(desc), int(batch)))
+    return total - int(lib.qhea_model_device_noisy_wide_grad_workspace_bytes(ctypes.byref(desc), int(batch))) if snapshots_only else total
+
+
+def model_device_noisy_wide_stored_refused(desc, noise):
+    """
+    model_device_noisy_refused for the tiled stored-state calls (qhea_model_loss_grad_noisy_device_exact_wide_stored): n outside
+    7..9, a singular channel, or a layer amplification above the library's bound -- the total amplification is no reason.
+    Host only.
+    """
+    return _device_noisy_refused('qhea_model_loss_grad_noisy_device_exact_wide_stored', desc, noise)
+
+
+def model_loss_grad_noisy_device_exact_wide_stored(desc, branch, trunk, y, params, noise, inv_batch_total, grad, ham_diag=None,
+                                                   pred=None):
+    """
+    model_loss_grad_noisy_device_exact_wide with rho replayed from stored states
+    (qhea_model_loss_grad_noisy_device_exact_wide_stored): the same quantity for settings past that call's guard; pred is bitwise
+    that call's.  The workspace grows by units x rows x 16 x 4^n bytes.
+    """
+    return _loss_grad_call('noisy_device_exact_wide_stored', desc, branch, trunk, y, params, dict(noise=noise), inv_batch_total,
+                           grad, 0, ham_diag, pred)
+
+
+def model_train_steps_noisy_device_exact_wide_stored(desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg,
+                                                     exp_avg_sq, first_step, lr, beta1, beta2, eps, weight_decay, noise,
+                                                     ham_diag=None):
+    """
+    model_train_steps_noisy_device_exact_wide with rho replayed from stored states
+    (qhea_model_train_steps_noisy_device_exact_wide_stored).  Bitwise a loop of model_loss_grad_noisy_device_exact_wide_stored +
+    adam_step.
+    """
+    return _train_steps_call('noisy_device_exact_wide_stored', desc, bounds, global_batches, branch, trunk, y, params, rows, exp_avg,
                              exp_avg_sq, first_step, lr, beta1, beta2, eps, weight_decay, dict(noise=noise), ham_diag)
 
 

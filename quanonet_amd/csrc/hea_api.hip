@@ -1577,7 +1577,7 @@ using namespace qhea;
 
 extern "C" {
 
-int qhea_version(void) { return 660; }
+int qhea_version(void) { return 670; }
 
 const char* qhea_strerror(int code) {
     switch (code) {

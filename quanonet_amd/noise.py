@@ -625,14 +625,20 @@ def device_noisy_loss_and_grad(model, inputs, y, noise, inv_batch_total=None, st
     return call(desc, branch, trunk, y, flat, noise.params(desc.n_qubits), inv, grad, ham_diag=ham_diag)
 
 
-def device_exact_noisy_loss_and_grad(model, inputs, y, device_noise, inv_batch_total=None):
+def device_exact_noisy_loss_and_grad(model, inputs, y, device_noise, inv_batch_total=None, states='inverse'):
     """
     device_noisy_loss_and_grad for n = 2..9: the flat [P + 2] tensor.  n <= 6 is device_noisy_loss_and_grad itself (inverse
     walk, bitwise).  n = 7..9 runs qhea_model_loss_grad_noisy_device_exact_wide: the same inverse walk with rho and the
     observable of all rows in device memory, 2 x 4^n x 16 bytes per row, on the tiles of device_exact_noisy_predict, whose pred
     this call's loss is built on bit for bit.  A DeviceNoise only; the guard of device_noisy_loss_and_grad
     (device_amplification(model, device_noise) <= 7) applies at every n.
+    states='stored' replays rho from the state stored after every unit and is bounded by device_layer_amplification instead:
+    at n <= 6 it is device_noisy_loss_and_grad(states='stored'), at n = 7..9 qhea_model_loss_grad_noisy_device_exact_wide_stored,
+    whose forward sweep leaves every unit's rho in device memory (units x rows x 16 x 4^n more bytes) and whose pred is the
+    inverse call's bit for bit.
     """
+    if states not in NOISE_STATES:
+        raise ValueError(f"device_exact_noisy_loss_and_grad: states must be 'inverse' or 'stored' (got {states!r})")
     if not isinstance(device_noise, DeviceNoise):
         raise ValueError(f"device_exact_noisy_loss_and_grad takes a DeviceNoise (got {type(device_noise).__name__}): a NoiseModel "
                          "goes to wide_exact_noisy_loss_and_grad (n = 2..9), or through DeviceNoise.uniform")
@@ -640,7 +646,7 @@ def device_exact_noisy_loss_and_grad(model, inputs, y, device_noise, inv_batch_t
         raise TypeError("device_exact_noisy_loss_and_grad takes a QuanONetPT or HEAQNNPT model")
     n = int(model.fused_desc().n_qubits)
     if n <= 6:
-        return device_noisy_loss_and_grad(model, inputs, y, device_noise, inv_batch_total)
+        return device_noisy_loss_and_grad(model, inputs, y, device_noise, inv_batch_total, states)
     if n >= 10:
         raise ValueError(f"device_exact_noisy_loss_and_grad covers n = 2..9 (got n = {n}): a density matrix of 4^{n} elements "
                          "per row is not carried; device_trajectory_loss_and_grad differentiates the quantum-jump loss at "
@@ -652,8 +658,8 @@ def device_exact_noisy_loss_and_grad(model, inputs, y, device_noise, inv_batch_t
     if B == 0:
         return grad
     inv = 1.0 / B if inv_batch_total is None else float(inv_batch_total)
-    return _lib.model_loss_grad_noisy_device_exact_wide(desc, branch, trunk, y, flat, device_noise.params(n), inv, grad,
-                                                        ham_diag=ham_diag)
+    call = _lib.model_loss_grad_noisy_device_exact_wide_stored if states == 'stored' else _lib.model_loss_grad_noisy_device_exact_wide
+    return call(desc, branch, trunk, y, flat, device_noise.params(n), inv, grad, ham_diag=ham_diag)
 
 
 def device_sampled_loss_and_grad(model, inputs, y, device_noise, sampling, inv_batch_total=None, row0=0):

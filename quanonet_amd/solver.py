@@ -361,20 +361,26 @@ def _train_noise_exact(v, train_noise=None, other_keys=()):
     return v
 
 
-def _train_device_noise_exact(v, train_device_noise=None, other_keys=()):
+def _train_device_noise_exact(v, train_device_noise=None, other_keys=(), train_noise_states=None):
     """config value / argument `train_device_noise_exact` -> None (train_device_noise alone trains on the exact loss at n <= 6
-    and refuses beyond) or 'wide' (the exact loss under the DeviceNoise for every n it exists for: n <= 6 as train_device_noise
-    alone, n = 7..9 on tiles).  `other_keys`: the keys set beside it that it does not combine with."""
+    and refuses beyond), 'wide' (the exact loss under the DeviceNoise for every n it exists for: n <= 6 as train_device_noise
+    alone, n = 7..9 on tiles, rho walked back through the inverse channels) or 'stored' (the same loss with rho replayed from
+    stored states at every n it exists for: n <= 6 as train_device_noise with train_noise_states='stored', n = 7..9 on tiles).
+    `other_keys`: the keys set beside it that it does not combine with."""
     if v is None:
         return None
-    if v != 'wide':
-        raise ValueError(f"train_device_noise_exact must be None or 'wide' (the exact device-noisy loss for n = 2..9; got {v!r})")
+    if v not in ('wide', 'stored'):
+        raise ValueError(f"train_device_noise_exact must be None or 'wide' (the exact device-noisy loss for n = 2..9), or 'stored' "
+                         f"(that loss with rho replayed from stored states, n = 2..9; got {v!r})")
     if other_keys:
-        raise ValueError(f"train_device_noise_exact='wide' does not combine with {other_keys[0]}: it asks for the exact loss "
+        raise ValueError(f"train_device_noise_exact={v!r} does not combine with {other_keys[0]}: it asks for the exact loss "
                          "under the DeviceNoise of train_device_noise, neither a uniform NoiseModel nor a sampled loss")
     if train_device_noise is None:
-        raise ValueError("train_device_noise_exact='wide' needs train_device_noise: it says which calls differentiate the exact "
+        raise ValueError(f"train_device_noise_exact={v!r} needs train_device_noise: it says which calls differentiate the exact "
                          "loss under that DeviceNoise")
+    if v == 'stored' and train_noise_states not in (None, 'stored'):
+        raise ValueError(f"train_device_noise_exact='stored' replays rho from stored states: train_noise_states beside it is "
+                         f"absent or 'stored' (got {train_noise_states!r})")
     return v
 
 
@@ -446,7 +452,9 @@ class DataParallelTrainer:
             train_device_noise_exact, self.train_device_noise,
             [k for k, v in (('train_noise', train_noise), ('train_sampling', train_sampling),
                             ('train_trajectories', train_trajectories), ('train_jump_trajectories', train_jump_trajectories))
-             if v is not None])
+             if v is not None], train_noise_states)
+        if self.train_device_noise_exact == 'stored':
+            self.noise_states = 'stored'
         # train_jump_trajectories beside train_device_noise: what train_trajectories means there, for every n a quantum-jump
         # gradient exists for (7..12); train_trajectories there keeps the range it was introduced with (7..9)
         if train_jump_trajectories is not None:
@@ -730,11 +738,13 @@ class DataParallelTrainer:
         return _exact_train_loss(*calls, lambda: self.train_device_noise.params(n))
 
     def _exact_device_wide_loss(self, log):
-        """train_device_noise with train_device_noise_exact='wide': the exact loss under the device model for every n it exists
-        for"""
-        # n <= 6 is the run that train_device_noise alone describes (train_noise_states honoured); n = 7..9 trains on the same
-        # loss with rho and O tiled through the workspace (qhea_model_loss_grad_noisy_device_exact_wide, the inverse walk):
-        # refuse here what it would
+        """train_device_noise with train_device_noise_exact='wide' or 'stored': the exact loss under the device model for every
+        n it exists for"""
+        # n <= 6 is the run that train_device_noise alone describes (train_noise_states honoured; 'stored' has set it); n = 7..9
+        # trains on the same loss with rho and O tiled through the workspace ('wide': qhea_model_loss_grad_noisy_device_exact_wide,
+        # the inverse walk; 'stored': ..._wide_stored, rho replayed from the states of the forward sweep): refuse here what
+        # they would
+        key = f"train_device_noise_exact={self.train_device_noise_exact!r}"
         if self.desc is None or not isinstance(self.optimizer, FlatAdam):
             raise ValueError("train_device_noise_exact needs the fused model-level path (a fp64 QuanONetPT / HEAQNNPT on a HIP "
                              "device, Adam with betas / eps / weight_decay only)")
@@ -742,13 +752,16 @@ class DataParallelTrainer:
         if n <= 6:
             return self._exact_device_loss(log)
         if n > 9:
-            raise ValueError(f"train_device_noise_exact='wide': the exact device-noisy loss takes n <= 9 (this model: n = {n}): "
+            raise ValueError(f"{key}: the exact device-noisy loss takes n <= 9 (this model: n = {n}): "
                              "no density matrix of that size is carried; train_jump_trajectories beside train_device_noise "
                              "trains n = 7..12 on quantum-jump trajectories")
+        if self.train_device_noise_exact == 'stored':
+            return self._exact_device_wide_stored_loss(log)
         if self.noise_states == 'stored':
             raise ValueError("train_device_noise_exact='wide' with train_noise_states='stored' at n >= 7: the stored-state walk "
-                             "does not exist on tiles (its snapshots would take units x rows x 16 x 4^n bytes); n = 7..9 trains "
-                             "through the inverse walk, within its bound on device_amplification")
+                             "does not exist on tiles under this value (its snapshots take units x rows x 16 x 4^n bytes); "
+                             "'wide' trains n = 7..9 through the inverse walk, within its bound on device_amplification.  "
+                             "train_device_noise_exact='stored' asks for the stored-state walk at every n = 2..9")
         from . import _lib
         try:
             rec = self.train_device_noise.params(n)
@@ -778,6 +791,55 @@ class DataParallelTrainer:
                     f"train_device_noise (log10 A_dev {amp:.2f}); rho and O are tiled through device memory, workspace "
                     f"{_lib.model_device_noisy_wide_grad_workspace_bytes(self.desc, rows) / 2**20:.1f} MiB for steps of up to "
                     f"{rows} rows")
+
+        def loss_grad(data, inv, grad, step, row0, ham_diag):
+            say(int(data[3].numel()))                                    # data = (desc, branch, trunk, y, params)
+            return base.loss_grad(data, inv, grad, step, row0, ham_diag)
+
+        def steps(call, ham_diag):
+            bounds = call[1]                                             # call = (desc, bounds, global_batches, ...)
+            say(max((int(b) - int(a) for a, b in zip(bounds[:-1], bounds[1:])), default=0))
+            return base.steps(call, ham_diag)
+        return base._replace(loss_grad=loss_grad, steps=steps)
+
+    def _exact_device_wide_stored_loss(self, log):
+        """train_device_noise with train_device_noise_exact='stored' at n = 7..9: the loss of _exact_device_wide_loss with rho
+        replayed from the states its forward sweep stored (qhea_model_loss_grad_noisy_device_exact_wide_stored)"""
+        from . import _lib
+        n = self.desc.n_qubits
+        try:
+            rec = self.train_device_noise.params(n)
+            amp = _lib.model_device_noisy_log10_amplification(self.desc, rec)
+            layer = _lib.model_device_noisy_log10_layer_amplification(self.desc, rec)
+            refused = _lib.model_device_noisy_wide_stored_refused(self.desc, rec)    # the library's own checks and bound
+        except _lib.QheaError as e:
+            raise ValueError(f"train_device_noise: {e}") from e
+        if refused:
+            raise ValueError(f"train_device_noise_exact='stored': the library refuses this model under this DeviceNoise (n = {n}, "
+                             f"log10 A_dev = {amp:.2f} in total, {layer:.2f} for one layer; the stored-state walk's bound is 7 "
+                             "for one layer and a singular channel is inf); see quanonet_amd.noise.device_layer_amplification.  "
+                             "train_trajectories / train_jump_trajectories beside train_device_noise train on quantum-jump "
+                             "trajectories whatever A_dev is")
+        if self.peer_fused:
+            # several ranks: loss_and_grad on the shard, then the exchange as a kernel of its own, the route of _exact_loss
+            self.peer_fused = False
+            self.dp_exchange_reason = ("peer exchange as a separate kernel: the device-noise step has no reduce kernel "
+                                       "with the exchange inside")
+        base = _exact_train_loss(_lib.model_loss_grad_noisy_device_exact_wide_stored,
+                                 _lib.model_train_steps_noisy_device_exact_wide_stored, lambda: self.train_device_noise.params(n))
+        per_row = _lib.model_device_noisy_wide_stored_grad_workspace_bytes(self.desc, 1, snapshots_only=True)
+        said = []
+
+        def say(rows):
+            # once, at the first call: only then is the batch known that the workspace is sized for
+            if log is not None and not said:
+                said.append(rows)
+                log("device-noise training: the loss and 'loss_train' are the exact device-noisy MSE under the DeviceNoise of "
+                    f"train_device_noise; rho is replayed from stored states (log10 A_dev {amp:.2f} in total, {layer:.2f} for "
+                    f"one layer, which is what the bound is asked of; {per_row} snapshot bytes per row); rho, O and the "
+                    "snapshots live in device memory, workspace "
+                    f"{_lib.model_device_noisy_wide_stored_grad_workspace_bytes(self.desc, rows) / 2**20:.1f} MiB for steps of "
+                    f"up to {rows} rows")
 
         def loss_grad(data, inv, grad, step, row0, ham_diag):
             say(int(data[3].numel()))                                    # data = (desc, branch, trunk, y, params)
